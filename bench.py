@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the SandCrate particle update on MI355X: particle-steps per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_PER_GPU] [--dump-outputs DIR] [--full]
 
 Workload.  N=1: BASELINE.json configs[2], the largest single-GPU configuration --
 1,048,576 synthetic uniformly seeded particles in the wave_machine.yaml world (its coefficients, both rigid
@@ -9,18 +9,24 @@ bodies incl. the motored wall, no particle source), particle diameter d = sqrt(1
 particle has ~12 neighbors, dt scaled with d, collider_noise_level 0.1 from a counter-based device RNG.
 N=4 / N=8: configs[3] / configs[4] (4,194,304 / 16,777,216 particles in all, slabs of rows, halo exchange per tick);
 N=2: 1,048,576 per GPU.  A step is one `physics_tick` of all particles; state is resident in HBM before the
-timed region and nothing is read back inside it.  The W+K-step measurement is repeated (--repeats, default 5)
-from the same initial state; `value` is the median repetition, all repetitions are listed.  A second
+timed region and nothing is read back inside it.  The W+K-step measurement is repeated (--repeats; default 1, with
+--full 5) from the same initial state; `value` is the median repetition, all repetitions are listed.  A second
 context of the same size (N > 1: a single-domain one of a slab's size, on every rank) runs --clock-warmup ticks (default 100) right before every repetition's W warm-up steps: the
 timed region is a few milliseconds behind an upload and would otherwise find the GPU's clocks down.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+--dump-outputs DIR writes the state the timed path left after its last step -- what a caller of `Crate.run` receives:
+particles.npy (P,2), velocities.npy (P,2), pressure.npy (P,) and ids.npy (P,), float64, in particle-id order; above
+64 MB in all a fixed seeded sample of 1,048,576 ids.  The inputs depend on the arguments only.
+
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+outputs if asked for, the line with the contract keys (`value`, `ms_per_step`, ...).  With --full it also carries
   roofline      SURVEY.md M4's force-pair figure: 128 algorithmic bytes per particle / (pass A + pass B) measured
                 with HIP events on the kernels' stream, against the 8 TB/s HBM peak; pass A, pass B and the whole
                 tick as sub-objects; `fp64_issue`: the VALU issue roofline from committed SQ counters
   kernels       time and algorithmic GB/s of every kernel of the tick
   cpu_baseline  the oracle's loop-structured tick (stands for the reference's NumPy path, which cannot
                 travel to the GPU box) timed on this host, one core, on a bounded sample (262,144 particles)
+  regimes       (N=1) wall time per tick of a longer run, also at 262,144 particles, and the viewer's per-frame path
 """
 from __future__ import annotations
 
@@ -77,6 +83,26 @@ def synthetic_state(n: int, seed: int = 1234):
     p = rs.rand(n, 2) * 0.96 + 0.02
     v = (rs.rand(n, 2) - 0.5) * 0.1
     return p, v
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+DUMP_SAMPLE = 1048576
+
+
+def dump_selection(n_total: int):
+    """The particle ids --dump-outputs writes: None (all of them) while 48 bytes per particle fit DUMP_LIMIT_BYTES,
+    else a fixed seeded sample of DUMP_SAMPLE ids, sorted."""
+    if 48 * n_total <= DUMP_LIMIT_BYTES:
+        return None
+    return np.sort(np.random.RandomState(0).choice(n_total, DUMP_SAMPLE, replace=False))
+
+
+def write_outputs(directory: str, particles, velocities, pressure, ids) -> None:
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    order = np.argsort(ids, kind="stable")
+    for name, a in (("particles", particles), ("velocities", velocities), ("pressure", pressure), ("ids", ids)):
+        np.save(out / f"{name}.npy", np.ascontiguousarray(np.asarray(a)[order], dtype=np.float64))
 
 
 def world_for(n_total: int):
@@ -224,12 +250,17 @@ def main() -> None:
     ap.add_argument("--clock-warmup", type=int, default=100,
                     help="ticks a second context of the same size runs before each repetition's warm-up steps (GPU clocks; "
                          "N > 1: a single-domain context of a slab's size on every rank; 0: off)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the W+K-step measurement is repeated this many times from the same initial state; `value` is the "
-                         "median repetition (each repetition times exactly K steps)")
+                         "median repetition (each repetition times exactly K steps; default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: five repetitions, per-kernel times and the roofline, the regimes of a longer "
+                         "run, the viewer's per-frame path and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step as DIR/<name>.npy (float64, particle-id order)")
     ap.add_argument("--cpu-sample", type=int, default=262144,
-                    help="particles in the CPU baseline tick (0 = skip); 262,144 is one tick of ~13 s.  N > 1: rank 0 times "
-                         "a quarter of it (65,536 particles, ~3 s) behind the timed region while the other ranks wait")
+                    help="--full: particles in the CPU baseline tick (0 = skip); 262,144 is one tick of ~13 s.  N > 1: rank 0 "
+                         "times a quarter of it (65,536 particles, ~3 s) behind the timed region while the other ranks wait")
     ap.add_argument("--noise", default="counter", choices=["counter", "none"])
     ap.add_argument("--slab-axis", default="y", choices=["x", "y"],
                     help="N > 1: cut the domain into slabs of rows (y: the halo bands are the ends of the sorted order, the "
@@ -238,8 +269,10 @@ def main() -> None:
                     help="development only: every rank uses cuda:0 and the gloo backend (halo staged through the "
                          "host), to exercise the N > 1 code path on a one-GPU box; the numbers mean nothing")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="no replay with HIP events around the kernels (no roofline in the output)")
+                    help="--full: no replay with HIP events around the kernels (nothing beyond the headline in the output)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     import torch
 
@@ -380,6 +413,13 @@ def main() -> None:
     if args.clock_warmup > 0:
         if world == 1:
             heater = make_sim()
+            # The first measured context of a run was its slowest repetition (0.161-0.164 ms per step against
+            # 0.148-0.155 for the next four, K = 20); a throwaway context of the same size that runs a few ticks first
+            # brings the first repetition -- a plain run's only one -- to where the later ones are.
+            throwaway = make_sim()
+            throwaway.run(max(args.warmup, 5))
+            settle(throwaway)
+            del throwaway
         else:  # every rank heats its own GPU with a single-domain workload of a slab's size: no communication
             hw, _ = world_for(per_gpu)
             heater = sc.Crate(hw, device=local_rank, noise=args.noise, noise_seed=1, capacity=per_gpu + 1024)
@@ -408,12 +448,25 @@ def main() -> None:
     elapsed = order[(len(order) - 1) // 2]  # the median repetition (lower middle for an even count)
     transport = getattr(sim, "transport", None)
 
+    if args.dump_outputs:  # the last repetition's state, before anything below replaces it
+        state = sim.engine.download() if world == 1 else sim.owned_state()
+        keep = dump_selection(n_total)
+        if keep is not None:
+            mask = np.isin(state[3], keep)
+            state = tuple(a[mask] for a in state)
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, state)
+            state = tuple(np.concatenate([part[k] for part in parts]) for k in range(4))
+        if rank == 0:
+            write_outputs(args.dump_outputs, *state)
+
     # ---- kernel durations: the same ticks replayed from the same initial state, every launch bracketed by two
     # HIP events on the stream the kernels run on.  Kept out of the timed region because the event records cost
     # wall time; kernel durations themselves are unaffected.
     timing = {}
     n_live = sim.particle_count if world == 1 else sim.global_particle_count()
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         sim = None
         sim = make_sim()  # same initial state, same ticks as the timed region
         eng = sim.engine
@@ -459,7 +512,11 @@ def main() -> None:
                        "transport": transport, "halo_overlap": bool(slab_sim[0].overlap) if world > 1 else None,
                        "halo_overlap_band_mode_ms_per_tick": band_mode or None,
                        "rebalance_every": rebalance_every if world > 1 else None, "halo_by_rank": halo_by_rank}}
-    if rank == 0 and args.no_kernel_events:
+    if device_flags:
+        base["device_flags"] = sorted(set(device_flags))
+    if rank == 0 and not args.full:
+        print(json.dumps(base))
+    elif rank == 0 and args.no_kernel_events:
         base["note"] = "no per-kernel events"
         print(json.dumps(base))
     elif rank == 0:
@@ -506,8 +563,6 @@ def main() -> None:
         line = dict(base)
         line["roofline"] = roofline
         line["kernels"] = kernels
-        if device_flags:
-            line["device_flags"] = sorted(set(device_flags))
         if world == 1:
             line["regimes"] = regimes(make_sim, settle, per_gpu)
             if per_gpu != 262144:  # BASELINE.json configs[1] heats up sooner (the tick doubles from tick ~105 on)

@@ -370,6 +370,37 @@ def test_full_size_properties(sc, n):
     eng.close()
 
 
+def test_bench_plain_run_dumps_the_timed_state(sc, tmp_path):
+    """bench.py without --full: one JSON line with the contract keys for exactly --steps timed steps, and --dump-outputs
+    writes the state its timed path left -- W + K ticks of `Crate.run` on bench.py's inputs, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    n, warmup, steps = 65536, 2, 5
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--particles", str(n), "--steps", str(steps), "--warmup",
+                          str(warmup), "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600,
+                         cwd=root)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "particle-steps/sec" and line["unit"] == "particle-steps/s" and line["higher_is_better"]
+    assert line["dtype"] == "f64" and line["steps"] == steps and line["repeats"]["count"] == 1
+    assert line["value"] * line["ms_per_step"] / 1000.0 == pytest.approx(n)
+    assert "roofline" not in line and "regimes" not in line and "cpu_baseline" not in line
+    crate, *_ = bench_like_crate(sc, n)
+    crate.run(warmup)
+    crate.run(steps)
+    gp, gv, gpr, gids = crate.engine.download()
+    order = np.argsort(gids, kind="stable")
+    for name, want in (("particles", gp), ("velocities", gv), ("pressure", gpr), ("ids", gids)):
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64
+        assert np.array_equal(got, want[order])
+
+
 def test_headless_driver_runs_a_variant(sc, tmp_path):
     """the reference's CLI entry, one sweep variant, state recording."""
     from sand_crate_amd.main import main

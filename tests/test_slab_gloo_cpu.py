@@ -144,16 +144,17 @@ def test_scene_with_its_particle_source_under_slabs(tmp_path, axis):
 
 
 @pytest.mark.parametrize("nproc,per_gpu,extra", [(2, 1500, ()), (8, 3000, ("--steps", "103"))])
-def test_bench_multi_gpu_path_on_cpu(nproc, per_gpu, extra):
+def test_bench_multi_gpu_path_on_cpu(nproc, per_gpu, extra, tmp_path):
     """bench.py's own N > 1 driver code (the path the driver's 2-, 4- and 8-GPU runs take: slabs of rows, halo overlap
-    requested, torch.distributed transport as the fallback, repetitions through `reload`, the JSON line) with the compute
-    side swapped for the oracle backend, under gloo: 2 ranks, and the 8-rank chain -- once with a window long enough for
-    the re-balancing of the cuts to switch on."""
+    requested, torch.distributed transport as the fallback, repetitions through `reload`, the outputs gathered from
+    every rank, the JSON line) with the compute side swapped for the oracle backend, under gloo: 2 ranks, and the
+    8-rank chain -- once with a window long enough for the re-balancing of the cuts to switch on."""
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "tests" / "bench_worker.py"),
            "--gpus", str(nproc), "--rehearse-on-one-gpu", "--particles", str(per_gpu), "--steps", "3", "--warmup", "1",
-           "--repeats", "2", "--clock-warmup", "0", "--cpu-sample", "0", "--no-kernel-events", *extra]
+           "--repeats", "2", "--clock-warmup", "0", "--cpu-sample", "0", "--no-kernel-events",
+           "--dump-outputs", str(tmp_path / "out"), *extra]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -167,6 +168,12 @@ def test_bench_multi_gpu_path_on_cpu(nproc, per_gpu, extra):
     assert line["config"]["rebalance_every"] == (50 if "--steps" in extra else 0)
     if "--steps" in extra:
         assert max(h["rebalances"] for h in halo) >= 1
+    ids = np.load(tmp_path / "out" / "ids.npy")
+    live = line["config"]["live_after_run"]
+    assert ids.dtype == np.float64 and len(ids) == live and (np.diff(ids) > 0).all() and ids[-1] < nproc * per_gpu
+    for name, shape in (("particles", (live, 2)), ("velocities", (live, 2)), ("pressure", (live,))):
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == shape and np.isfinite(got).all()
 
 
 def test_rebalanced_cuts_properties():
