@@ -334,6 +334,27 @@ int sc_side_stream(sc_ctx* ctx, void** hip_stream);
 int sc_halo_overlap_begin(sc_ctx* ctx, sc_ctx* peer);
 int sc_halo_overlap_end(sc_ctx* ctx);
 
+/* Frames: what Playback.draw_scene draws (playback.py:75-85) -- every particle as a disc coloured by its pressure
+ * (playback.py:191-206), the walls on top in white (:180-186), black elsewhere -- rendered next to the state into an
+ * RGB image of height x width x 3 bytes, row 0 at the top (the layout of pygame.image.tostring(..., 'RGB')).  The
+ * particles and pressures drawn are exactly what sc_download_state would return; among discs that cover a pixel the
+ * highest id wins (the reference draws in array order).  tests/render_spec.py is the raster rule, bit for bit.
+ * Rendering reads the state only: no counter, look-ahead promise, RNG position or pending error flag changes.
+ * SC_ERR_STATE between sc_step_begin and sc_step_finish; SC_ERR_ARG for a bad view, a null buffer, or n_segments
+ * outside 0..SC_MAX_SEGMENTS.  The device buffers it needs grow to the largest frame asked for. */
+typedef struct sc_view {
+  int32_t width, height;      /* 1..16384 */
+  double zoom;                /* finite, > 0 */
+  double center_x, center_y;  /* screen pixels; reference default width/2, height/2 */
+  double particle_radius;     /* world units */
+  int32_t segment_width;      /* pixels, >= 0 */
+  int32_t reserved;
+} sc_view;
+/* Synchronises; rgb is host memory of height*width*3 bytes. */
+int sc_render(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* rgb);
+/* Enqueued on the context's stream only; dev_rgb is device memory (e.g. a torch uint8 tensor). */
+int sc_render_device(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* dev_rgb);
+
 /* Synchronises.  Live particles stored in this context (dead ghost copies excluded); summed over
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);

@@ -51,6 +51,12 @@ class Source(C.Structure):
         ("flow", C.c_int64)]
 
 
+class View(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("zoom", C.c_double), ("center_x", C.c_double),
+                ("center_y", C.c_double), ("particle_radius", C.c_double), ("segment_width", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("particles", C.c_int64), ("neighbor_slots", C.c_int64), ("max_neighbors", C.c_int32),
                 ("wall_particles", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
@@ -123,6 +129,8 @@ SIGNATURES = {
     "sc_rng_set_state": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int32]),
     "sc_rng_get_state": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "sc_emit_particles": (C.c_int, [_P, C.POINTER(Source), C.c_int32, C.c_double, C.c_int64]),
+    "sc_render": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P]),
+    "sc_render_device": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P]),
 }
 
 _lib = None

@@ -282,6 +282,25 @@ class Crate:
         self._force_ema = {}
         self._engine.enable_force_monitor(self._hud_forces)
 
+    # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
+    def render(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None, segment_width: int = 2,
+               out=None):
+        """The frame the reference's viewer draws after `physics_tick()`, rendered on the GPU: every particle a disc of
+        ``int(width * particle_radius) * zoom`` pixels coloured by its pressure (white at 0, blue at 1 and above), the
+        walls (`segments`) on top in white, black elsewhere; ``height x width x 3`` uint8, row 0 at the top.
+
+        It shows the device state as `sc_download_state` would return it: the pressure is that of the last finished
+        tick, so right after the particles were set -- or after `from_checkpoint`, before the first tick -- every
+        particle is white.  `center` is in screen pixels (default: the frame's centre).  With `out` a CUDA uint8 tensor
+        of shape (height, width, 3) the frame is written there on the library's stream and the call returns without
+        synchronising: the library's stream does not wait for torch's, so the tensor must be ready when this is called
+        and read after `synchronize()` (or run the crate on torch's stream, `engine.set_stream`).  Otherwise it returns a
+        NumPy array.
+        The pixel rule, bit for bit: tests/render_spec.py."""
+        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
+        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        return self._engine.render(view, segments, out)
+
     # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,
     # playback.py:109-118, grown into something a run can resume from)
     def begin_checkpoint(self) -> None:

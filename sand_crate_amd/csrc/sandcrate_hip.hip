@@ -20,6 +20,7 @@
 #include "sandcrate_hip.h"
 #include "sc_kernels.h"
 #include "sc_rccl.h"
+#include "sc_render.h"
 #include "sc_rng.h"
 #include "sc_tiled.h"
 
@@ -120,6 +121,10 @@ struct sc_ctx {
   hipEvent_t snap_ready = nullptr, snap_done = nullptr;
   int* colHist = nullptr;      // sc_column_histogram
   int64_t colHistAlloc = 0;
+  // sc_render: the per-pixel key buffer and (host path) the device frame, grown to the largest frame asked for
+  unsigned long long* renderKeys = nullptr;
+  unsigned char* renderRgb = nullptr;
+  int64_t renderKeyAlloc = 0, renderRgbAlloc = 0;
   // host-mapped progress block written by the GPU, read by the host without synchronisation:
   // [0] big buckets seen by the last finished scan, [1] ticks finished, [2] live particles of that tick,
   // [4 + 4 (tick % kHaloRing) ..]: halo record counts of that tick (sent left / right, received left / right)
@@ -663,7 +668,7 @@ int sc_destroy(sc_ctx* c) {
   if (c->ev_xchg) (void)hipEventDestroy(c->ev_xchg);
   void* ptrs[] = {c->cellS, c->wslotS, c->cellT, c->wslotT, c->keys, c->keyCell, c->tileBounds, c->tileBoundsT, c->tileBand, c->cellCount, c->cellStart, c->scanDesc, c->sortedStamp, c->sortTasks, c->wrec[0], c->wrec[1],
                   c->nbr, c->rows, c->P, c->snn, c->sxy, c->svv, c->counters, c->cntById, c->offById, c->idBlockSums, c->eta,
-                  c->stage_xy, c->stage_vxy, c->stage_ids, c->owned_out, c->colHist, c->rng, c->monitor,
+                  c->stage_xy, c->stage_vxy, c->stage_ids, c->owned_out, c->colHist, c->rng, c->monitor, c->renderKeys, c->renderRgb,
                   c->snap_d[0], c->snap_d[1], c->snap_d[2], c->snap_d[3], c->snap_id_d, c->snap_rng_d};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1124,6 +1129,121 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
     HIPCHK(hipMemsetAsync(c->counters + C_FLAGS, 0, sizeof(int), c->stream));
     return check_flags(h[C_FLAGS]);
   }
+  return SC_OK;
+}
+
+// ---- rendering (sc_render.h) ------------------------------------------------------------------
+
+constexpr int kRenderMaxSide = 16384;
+constexpr long long kRenderMaxRadius = 1LL << 24;  // keeps the squared pixel distances of a disc exact in 64 bits
+
+// Checks the call and turns the view and the walls into the kernels' argument.
+static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments, int32_t ns, const void* rgb, RenderView& v) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->in_step) return fail(SC_ERR_STATE, "rendering happens between ticks");
+  if (!view || !rgb) return fail(SC_ERR_ARG, "null view or frame");
+  const sc_view& q = *view;
+  if (q.width < 1 || q.width > kRenderMaxSide || q.height < 1 || q.height > kRenderMaxSide)
+    return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", q.width, q.height, kRenderMaxSide);
+  if (!(std::isfinite(q.zoom) && q.zoom > 0)) return fail(SC_ERR_ARG, "zoom must be finite and positive");
+  if (!std::isfinite(q.center_x) || !std::isfinite(q.center_y)) return fail(SC_ERR_ARG, "the view center must be finite");
+  if (!(std::isfinite(q.particle_radius) && q.particle_radius >= 0))
+    return fail(SC_ERR_ARG, "particle_radius must be finite and not negative");
+  if (q.segment_width < 0) return fail(SC_ERR_ARG, "segment_width must not be negative");
+  if (ns < 0 || ns > kMaxSeg) return fail(SC_ERR_ARG, "%d segments, at most %d", ns, kMaxSeg);
+  if (ns > 0 && !segments) return fail(SC_ERR_ARG, "null segments");
+  v = RenderView{};
+  v.width = q.width;
+  v.height = q.height;
+  v.center_x = q.center_x;
+  v.center_y = q.center_y;
+  v.zoom = q.zoom;
+  v.half_w = q.width / 2.0;
+  v.half_h = q.height / 2.0;
+  v.sx = q.width - 1.0;
+  v.sy = q.height - 1.0;
+  // playback.py:195: int(screen_x * particle_radius) * zoom_factor, floored to whole pixels
+  const double R = std::floor(std::trunc(q.width * q.particle_radius) * q.zoom);
+  if (!(R <= (double)kRenderMaxRadius)) return fail(SC_ERR_ARG, "disc radius of %g pixels, at most %lld", R, kRenderMaxRadius);
+  v.radius = (long long)R;
+  v.radius_d = R;
+  v.w2 = (double)q.segment_width * q.segment_width;
+  const double margin = q.segment_width + 1.0;
+  for (int k = 0; k < ns; ++k) {
+    const double* e = segments + 4 * k;
+    // the same view as the particles', not floored (playback.py:180-186 hands these to pygame.draw.line)
+    const double ax = (std::trunc(e[0] * v.sx) - v.center_x) * v.zoom + v.half_w;
+    const double ay = (std::trunc(e[1] * v.sy) - v.center_y) * v.zoom + v.half_h;
+    const double bx = (std::trunc(e[2] * v.sx) - v.center_x) * v.zoom + v.half_w;
+    const double by = (std::trunc(e[3] * v.sy) - v.center_y) * v.zoom + v.half_h;
+    if (!std::isfinite(ax) || !std::isfinite(ay) || !std::isfinite(bx) || !std::isfinite(by)) continue;  // covers nothing
+    RenderSeg& r = v.seg[v.nseg++];
+    r.ax = ax;
+    r.ay = ay;
+    r.dx = bx - ax;
+    r.dy = by - ay;
+    r.len2 = r.dx * r.dx + r.dy * r.dy;
+    // the closest point a + t (b - a), t in [0, 1], lies between a and the ROUNDED a + (b - a)
+    const double ex = ax + r.dx, ey = ay + r.dy;
+    r.lox = std::min({ax, bx, ex}) - margin;
+    r.hix = std::max({ax, bx, ex}) + margin;
+    r.loy = std::min({ay, by, ey}) - margin;
+    r.hiy = std::max({ay, by, ey}) + margin;
+  }
+  return SC_OK;
+}
+
+// Grows the key buffer and enqueues splat and resolve into `rgb` (device memory).
+static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb) {
+  const int64_t pixels = (int64_t)v.width * v.height;
+  if (pixels > c->renderKeyAlloc) {
+    if (c->renderKeys) (void)hipFree(c->renderKeys);
+    c->renderKeys = nullptr;
+    c->renderKeyAlloc = 0;
+    HIPCHK(dalloc(&c->renderKeys, (size_t)pixels));
+    c->renderKeyAlloc = pixels;
+    // zero once: every resolve clears the keys it reads, which are all that the splat before it may have set
+    HIPCHK(hipMemsetAsync(c->renderKeys, 0, pixels * sizeof(unsigned long long), c->stream));
+  }
+  const int64_t bound = std::min<int64_t>(launch_bound(c), c->cap);
+  if (bound > 0) {
+    if (v.radius > kRenderWaveRadius)
+      hipLaunchKernelGGL(k_render_splat<true>, dim3((unsigned)((bound * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                         v, c->counters, c->x[0], c->y[0], c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
+    else
+      hipLaunchKernelGGL(k_render_splat<false>, dim3(grid_for(bound)), dim3(kBlock), 0, c->stream, v, c->counters, c->x[0],
+                         c->y[0], c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
+  }
+  hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
+                     ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int sc_render_device(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* dev_rgb) {
+  RenderView v;
+  int rc = render_prepare(c, view, segments, n_segments, dev_rgb, v);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  return render_launch(c, v, dev_rgb);
+}
+
+int sc_render(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* rgb) {
+  RenderView v;
+  int rc = render_prepare(c, view, segments, n_segments, rgb, v);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t bytes = 3 * (int64_t)v.width * v.height;
+  if (bytes > c->renderRgbAlloc) {
+    if (c->renderRgb) (void)hipFree(c->renderRgb);
+    c->renderRgb = nullptr;
+    c->renderRgbAlloc = 0;
+    HIPCHK(dalloc(&c->renderRgb, (size_t)bytes));
+    c->renderRgbAlloc = bytes;
+  }
+  if ((rc = render_launch(c, v, c->renderRgb))) return rc;
+  HIPCHK(hipMemcpyAsync(rgb, c->renderRgb, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return SC_OK;
 }
 

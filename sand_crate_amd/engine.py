@@ -130,6 +130,30 @@ class Engine:
         k = n.value
         return xy[:k].copy(), vxy[:k].copy(), pr[:k].copy(), ids[:k].copy()
 
+    # -- frames
+    @staticmethod
+    def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,
+             segment_width: int = 2) -> N.View:
+        """sc_view; `center` defaults to the frame's centre (width/2, height/2), as the reference's viewer has it."""
+        cx, cy = (width / 2, height / 2) if center is None else (float(center[0]), float(center[1]))
+        return N.View(int(width), int(height), float(zoom), cx, cy, float(particle_radius), int(segment_width), 0)
+
+    def render(self, view: N.View, segments, out=None):
+        """The RGB frame (height x width x 3 uint8) of the current device state with these walls (S x 2 x 2).
+        out=None: synchronises and returns a NumPy array (sc_render).  `out` a CUDA uint8 tensor of that shape: enqueued
+        on the context's stream into it (sc_render_device), no synchronisation; returns `out`."""
+        seg = N.f64(segments).reshape(-1, 2, 2)
+        shape = (int(view.height), int(view.width), 3)
+        if out is None:
+            img = np.empty(shape, dtype=np.uint8)
+            N.check(self._lib.sc_render(self._ctx, C.byref(view), N.dptr(seg), len(seg), N._P(img.ctypes.data)))
+            return img
+        if not getattr(out, "is_cuda", False) or tuple(out.shape) != shape or not out.is_contiguous() or \
+                str(out.dtype) != "torch.uint8":
+            raise ValueError(f"out must be a contiguous CUDA uint8 tensor of shape {shape}")
+        N.check(self._lib.sc_render_device(self._ctx, C.byref(view), N.dptr(seg), len(seg), N._P(out.data_ptr())))
+        return out
+
     # -- per-tick inputs
     def set_params(self, *, dt, particle_radius, wall_collision_decay, pressure_amplifier, ignored_pressure,
                    collider_noise_level, viscosity, surface_smoothing, target_pressure, gravity) -> None:

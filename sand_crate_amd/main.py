@@ -8,7 +8,9 @@ mutating the loaded config in place, variant after variant -- and runs ``ticks_t
 for each.  Instead of rendering, a variant's recording is the particle state itself: where the
 reference writes config.yaml + AVI + GIF (playback.py:109-118) this writes config.yaml + state.npz
 (positions, pressure and segments every ``--record-every`` ticks), the state dump the reference
-left commented out (playback.py:112-113).  ``--checkpoint-every K`` also writes resumable checkpoints
+left commented out (playback.py:112-113).  ``--frames`` also renders a ``screen_x`` x ``screen_y`` picture at every
+recorded tick on the GPU (`Crate.render`, what Playback.draw_scene draws) and writes them as ``frames.npz`` and, when PIL
+is installed, ``video.gif`` (playback.py:131-138; there is no AVI).  ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
 """
@@ -62,11 +64,11 @@ def deep_dictify(obj):
 
 
 class HeadlessPlayback:
-    """`Playback` minus pygame: owns a `Crate`, ticks it, records state instead of frames."""
+    """`Playback` minus pygame: owns a `Crate`, ticks it, records state (and, with `frames`, rendered pictures)."""
 
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
-                 resume: Optional[Path] = None) -> None:
+                 resume: Optional[Path] = None, frames: bool = False) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -80,6 +82,8 @@ class HeadlessPlayback:
         self._checkpoint_tick = None
         self.record_every = max(int(record_every), 1)
         self.frames: list[dict] = []
+        self.render_frames = bool(frames)
+        self.images: list[np.ndarray] = []
         self.done = False
         self.seconds = 0.0
 
@@ -96,6 +100,9 @@ class HeadlessPlayback:
                 self.frames.append({"tick": self.crate.tick, "particles": self.crate.particles.copy(),
                                     "pressure": self.crate.particles_pressure.copy(),
                                     "segments": self.crate.segments.copy()})
+                if self.render_frames:
+                    pb = self.config.playback_config
+                    self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y)))
             if self.done:
                 break
         self._collect_checkpoint()
@@ -124,11 +131,30 @@ class HeadlessPlayback:
             arrays[f"segments_{k}"] = frame["segments"]
         arrays["ticks"] = np.array([f["tick"] for f in self.frames], dtype=np.int64)
         np.savez_compressed(out_dir / "state.npz", **arrays)
+        if self.render_frames:
+            write_frames(out_dir, self.images, arrays["ticks"])
+
+
+def write_frames(out_dir: Path, frames, ticks) -> None:
+    """frames.npz (`frames` T x H x W x 3 uint8, `ticks`) and, when PIL is installed, video.gif as playback.py:131-138
+    writes it."""
+    out_dir = Path(out_dir)
+    frames = [np.asarray(f, dtype=np.uint8) for f in frames]
+    stack = np.stack(frames) if frames else np.zeros((0, 0, 0, 3), dtype=np.uint8)
+    np.savez_compressed(out_dir / "frames.npz", frames=stack, ticks=np.asarray(ticks, dtype=np.int64))
+    if not frames:
+        return
+    try:
+        from PIL import Image
+    except ImportError:
+        return
+    images = [Image.fromarray(f, "RGB") for f in frames]
+    images[0].save(out_dir / "video.gif", format="GIF", append_images=images[1:], save_all=True, duration=10, loop=0)
 
 
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
-         resume: Optional[Path] = None) -> list[dict]:
+         resume: Optional[Path] = None, frames: bool = False) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -136,7 +162,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
             break
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
-                                    checkpoint_every=checkpoint_every, resume=resume if k == 0 else None)
+                                    checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames)
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -156,6 +182,8 @@ if __name__ == "__main__":
     ap.add_argument("--record-every", type=int, default=10)
     ap.add_argument("--checkpoint-every", type=int, default=0, help="write a resumable checkpoint every K ticks (0 = never)")
     ap.add_argument("--resume", type=Path, default=None, help="continue the first variant from this checkpoint file")
+    ap.add_argument("--frames", action="store_true", help="also render a frame every --record-every ticks (frames.npz, "
+                    "video.gif)")
     a = ap.parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
-         record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume)
+         record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames)
