@@ -355,6 +355,22 @@ int sc_render(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t 
 /* Enqueued on the context's stream only; dev_rgb is device memory (e.g. a torch uint8 tensor). */
 int sc_render_device(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* dev_rgb);
 
+/* JPEG frames: baseline sequential JPEG (JFIF, SOF0), 8-bit Y Cb Cr sampled 4:4:4, the Annex K quantisation tables scaled
+ * by the IJG quality rule (quality 1..100) and the Annex K Huffman tables, a restart interval of one MCU row.  The image
+ * is encoded on the device; only the compressed bytes reach `out` (host memory).  tests/jpeg_spec.py is the bitstream,
+ * byte for byte.  Both calls synchronise.  *n_out is set to the file's size; if that exceeds `capacity`, nothing is
+ * written and SC_ERR_CAPACITY is returned (out may be null with capacity 0 to ask for the size).  sc_jpeg_bound gives a
+ * capacity that always suffices.  SC_ERR_STATE between sc_step_begin and sc_step_finish; SC_ERR_ARG for a bad size,
+ * quality or pointer.  The device workspace grows to the largest frame asked for (about 16 bytes per pixel). */
+int sc_jpeg_bound(int32_t width, int32_t height, int64_t* bound);
+/* dev_rgb: device memory of height*width*3 bytes, row 0 at the top (e.g. written by sc_render_device).  The context's
+ * stream does not wait for other streams: the frame must be ready when this is called. */
+int sc_jpeg_encode_device(sc_ctx* ctx, const uint8_t* dev_rgb, int32_t width, int32_t height, int32_t quality, uint8_t* out,
+                          int64_t capacity, int64_t* n_out);
+/* sc_render into a frame owned by the context, then that frame encoded as sc_jpeg_encode_device does. */
+int sc_render_jpeg(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, int32_t quality,
+                   uint8_t* out, int64_t capacity, int64_t* n_out);
+
 /* Synchronises.  Live particles stored in this context (dead ghost copies excluded); summed over
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);

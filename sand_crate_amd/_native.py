@@ -131,6 +131,9 @@ SIGNATURES = {
     "sc_emit_particles": (C.c_int, [_P, C.POINTER(Source), C.c_int32, C.c_double, C.c_int64]),
     "sc_render": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P]),
     "sc_render_device": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P]),
+    "sc_jpeg_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "sc_jpeg_encode_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "sc_render_jpeg": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

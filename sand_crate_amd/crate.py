@@ -301,6 +301,15 @@ class Crate:
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
         return self._engine.render(view, segments, out)
 
+    def render_jpeg(self, width: int = 1000, height: int = 1000, *, quality: int = 95, zoom: float = 1.0, center=None,
+                    segment_width: int = 2) -> bytes:
+        """`render`'s frame as a JPEG file, encoded on the GPU: only the compressed bytes leave it.  Baseline JPEG, 4:4:4,
+        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).
+        The bitstream, byte for byte: tests/jpeg_spec.py applied to `render`'s frame."""
+        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
+        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        return self._engine.render_jpeg(view, segments, quality)
+
     # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,
     # playback.py:109-118, grown into something a run can resume from)
     def begin_checkpoint(self) -> None:

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "sandcrate_hip.h"
+#include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
@@ -67,6 +68,18 @@ double sq_threshold(double R) {
 template <class T>
 hipError_t dalloc(T** p, size_t n) {
   return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
+}
+
+// Grows a device buffer of the context to hold n elements (its contents are not kept).
+template <class T>
+int grow(T*& p, int64_t& alloc, int64_t n) {
+  if (n <= alloc) return SC_OK;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  alloc = 0;
+  HIPCHK(dalloc(&p, (size_t)n));
+  alloc = n;
+  return SC_OK;
 }
 
 }  // namespace
@@ -125,6 +138,11 @@ struct sc_ctx {
   unsigned long long* renderKeys = nullptr;
   unsigned char* renderRgb = nullptr;
   int64_t renderKeyAlloc = 0, renderRgbAlloc = 0;
+  // sc_jpeg_encode_device: the encoder's workspace (coefficients, per-block masks and code lengths, the rows' bit
+  // buffers, lengths and offsets; sc_jpeg.h) and the entropy-coded data, each grown to the largest frame asked for
+  unsigned char* jpegWork = nullptr;
+  unsigned char* jpegOut = nullptr;
+  int64_t jpegWorkAlloc = 0, jpegOutAlloc = 0;
   // host-mapped progress block written by the GPU, read by the host without synchronisation:
   // [0] big buckets seen by the last finished scan, [1] ticks finished, [2] live particles of that tick,
   // [4 + 4 (tick % kHaloRing) ..]: halo record counts of that tick (sent left / right, received left / right)
@@ -668,7 +686,7 @@ int sc_destroy(sc_ctx* c) {
   if (c->ev_xchg) (void)hipEventDestroy(c->ev_xchg);
   void* ptrs[] = {c->cellS, c->wslotS, c->cellT, c->wslotT, c->keys, c->keyCell, c->tileBounds, c->tileBoundsT, c->tileBand, c->cellCount, c->cellStart, c->scanDesc, c->sortedStamp, c->sortTasks, c->wrec[0], c->wrec[1],
                   c->nbr, c->rows, c->P, c->snn, c->sxy, c->svv, c->counters, c->cntById, c->offById, c->idBlockSums, c->eta,
-                  c->stage_xy, c->stage_vxy, c->stage_ids, c->owned_out, c->colHist, c->rng, c->monitor, c->renderKeys, c->renderRgb,
+                  c->stage_xy, c->stage_vxy, c->stage_ids, c->owned_out, c->colHist, c->rng, c->monitor, c->renderKeys, c->renderRgb, c->jpegWork, c->jpegOut,
                   c->snap_d[0], c->snap_d[1], c->snap_d[2], c->snap_d[3], c->snap_id_d, c->snap_rng_d};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1138,10 +1156,10 @@ constexpr int kRenderMaxSide = 16384;
 constexpr long long kRenderMaxRadius = 1LL << 24;  // keeps the squared pixel distances of a disc exact in 64 bits
 
 // Checks the call and turns the view and the walls into the kernels' argument.
-static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments, int32_t ns, const void* rgb, RenderView& v) {
+static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments, int32_t ns, bool has_frame, RenderView& v) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (c->in_step) return fail(SC_ERR_STATE, "rendering happens between ticks");
-  if (!view || !rgb) return fail(SC_ERR_ARG, "null view or frame");
+  if (!view || !has_frame) return fail(SC_ERR_ARG, "null view or frame");
   const sc_view& q = *view;
   if (q.width < 1 || q.width > kRenderMaxSide || q.height < 1 || q.height > kRenderMaxSide)
     return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", q.width, q.height, kRenderMaxSide);
@@ -1222,7 +1240,7 @@ static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb) {
 
 int sc_render_device(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* dev_rgb) {
   RenderView v;
-  int rc = render_prepare(c, view, segments, n_segments, dev_rgb, v);
+  int rc = render_prepare(c, view, segments, n_segments, dev_rgb != nullptr, v);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
   return render_launch(c, v, dev_rgb);
@@ -1230,21 +1248,158 @@ int sc_render_device(sc_ctx* c, const sc_view* view, const double* segments, int
 
 int sc_render(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* rgb) {
   RenderView v;
-  int rc = render_prepare(c, view, segments, n_segments, rgb, v);
+  int rc = render_prepare(c, view, segments, n_segments, rgb != nullptr, v);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
   const int64_t bytes = 3 * (int64_t)v.width * v.height;
-  if (bytes > c->renderRgbAlloc) {
-    if (c->renderRgb) (void)hipFree(c->renderRgb);
-    c->renderRgb = nullptr;
-    c->renderRgbAlloc = 0;
-    HIPCHK(dalloc(&c->renderRgb, (size_t)bytes));
-    c->renderRgbAlloc = bytes;
-  }
+  if ((rc = grow(c->renderRgb, c->renderRgbAlloc, bytes))) return rc;
   if ((rc = render_launch(c, v, c->renderRgb))) return rc;
   HIPCHK(hipMemcpyAsync(rgb, c->renderRgb, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return SC_OK;
+}
+
+// ---- JPEG encoding (sc_jpeg.h) -------------------------------------------------------------------
+
+constexpr int kJpegHeaderBytes = 613;  // SOI, APP0, DQT, SOF0, DHT, DRI, SOS as jpeg_header writes them
+
+static void jpeg_quant(int quality, int q[2][64]) {
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  for (int k = 0; k < 64; ++k) {
+    q[0][k] = std::min(255, std::max(1, (kJpegLumaQ[k] * s + 50) / 100));
+    q[1][k] = std::min(255, std::max(1, (kJpegChromaQ[k] * s + 50) / 100));
+  }
+}
+
+// SOI through SOS (tests/jpeg_spec.py: header).
+static std::vector<unsigned char> jpeg_header(int width, int height, const int q[2][64]) {
+  std::vector<unsigned char> h;
+  auto u8 = [&](int v) { h.push_back((unsigned char)v); };
+  auto u16 = [&](int v) { u8(v >> 8); u8(v & 0xFF); };
+  u16(0xFFD8);
+  u16(0xFFE0); u16(16);
+  for (char ch : {'J', 'F', 'I', 'F', '\0'}) u8(ch);
+  u8(1); u8(1); u8(0); u16(1); u16(1); u8(0); u8(0);
+  u16(0xFFDB); u16(2 + 2 * 65);
+  for (int t = 0; t < 2; ++t) {
+    unsigned char zz[64];
+    for (int k = 0; k < 64; ++k) zz[kJpegZigzag.of[k]] = (unsigned char)q[t][k];
+    u8(t);
+    for (int k = 0; k < 64; ++k) u8(zz[k]);
+  }
+  u16(0xFFC0); u16(17); u8(8); u16(height); u16(width); u8(3);
+  for (int id = 1; id <= 3; ++id) { u8(id); u8(0x11); u8(id == 1 ? 0 : 1); }
+  u16(0xFFC4); u16(2 + 2 * (17 + 12) + 2 * (17 + 162));
+  for (int t = 0; t < 2; ++t) {
+    u8(t);
+    for (int k = 0; k < 16; ++k) u8(kJpegDcBits[t][k]);
+    for (int k = 0; k < 12; ++k) u8(kJpegDcVals[k]);
+    u8(0x10 | t);
+    for (int k = 0; k < 16; ++k) u8(kJpegAcBits[t][k]);
+    for (int k = 0; k < 162; ++k) u8(kJpegAcVals[t][k]);
+  }
+  u16(0xFFDD); u16(4); u16((width + 7) / 8);
+  u16(0xFFDA); u16(12); u8(3);
+  for (int id = 1; id <= 3; ++id) { u8(id); u8(id == 1 ? 0x00 : 0x11); }
+  u8(0); u8(63); u8(0);
+  return h;
+}
+
+int sc_jpeg_bound(int32_t width, int32_t height, int64_t* bound) {
+  if (width < 1 || width > kRenderMaxSide || height < 1 || height > kRenderMaxSide || !bound)
+    return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", width, height, kRenderMaxSide);
+  const int64_t mcus = (width + 7) / 8, rows = (height + 7) / 8;
+  const int64_t row_bytes = (3 * mcus * kJpegBlockBits + 7) / 8;
+  *bound = kJpegHeaderBytes + rows * (2 * row_bytes + 2) + 2;  // every byte 0xFF, a marker after each row, EOI
+  return SC_OK;
+}
+
+// Encodes the W x H x 3 RGB frame at `rgb` (device memory, checked by the caller) into `out` (host memory).
+// Enqueued on the context's stream; synchronises twice: for the total length, then for the bytes.
+static int jpeg_encode(sc_ctx* c, const unsigned char* rgb, int width, int height, int quality, uint8_t* out,
+                       int64_t capacity, int64_t* n_out) {
+  JpegDims d;
+  d.width = width;
+  d.height = height;
+  d.mcus = (width + 7) / 8;
+  d.rows = (height + 7) / 8;
+  jpeg_quant(quality, d.quant);
+  const int64_t nblocks = (int64_t)d.rows * d.mcus * 3;
+  const long long row_words = (3LL * d.mcus * kJpegBlockBits + 7) / 32 + 1;  // a row's bits, padded
+  // the workspace: coef | masks | acbits | rows' bit buffers | row bytes, row lengths | row offsets + total
+  auto up = [](int64_t n) { return (n + 255) & ~(int64_t)255; };
+  const int64_t o_mask = up(nblocks * 64 * (int64_t)sizeof(short));
+  const int64_t o_ac = o_mask + up(nblocks * (int64_t)sizeof(unsigned long long));
+  const int64_t o_rows = o_ac + up(nblocks * (int64_t)sizeof(int));
+  const int64_t o_len = o_rows + up((int64_t)d.rows * row_words * (int64_t)sizeof(unsigned));
+  const int64_t o_off = o_len + up(2 * (int64_t)d.rows * (int64_t)sizeof(int));
+  const int64_t bytes = o_off + up(((int64_t)d.rows + 1) * (int64_t)sizeof(long long));
+  int rc;
+  if ((rc = grow(c->jpegWork, c->jpegWorkAlloc, bytes))) return rc;
+  unsigned char* w = c->jpegWork;
+  short* coef = (short*)w;
+  unsigned long long* masks = (unsigned long long*)(w + o_mask);
+  int* acbits = (int*)(w + o_ac);
+  unsigned* rowbuf = (unsigned*)(w + o_rows);
+  int* row_bytes = (int*)(w + o_len);
+  int* row_len = row_bytes + d.rows;
+  long long* row_off = (long long*)(w + o_off);
+
+  hipLaunchKernelGGL(k_jpeg_dct, dim3((unsigned)((nblocks * 8 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, d, rgb,
+                     coef, masks, acbits);
+  hipLaunchKernelGGL(k_jpeg_rows, dim3((unsigned)d.rows), dim3(64), 0, c->stream, d, coef, masks, acbits, rowbuf, row_words,
+                     row_bytes, row_len);
+  hipLaunchKernelGGL(k_jpeg_scan, dim3(1), dim3(64), 0, c->stream, d.rows, row_len, row_off);
+  HIPCHK(hipGetLastError());
+  long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, row_off + d.rows, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const std::vector<unsigned char> hdr = jpeg_header(width, height, d.quant);
+  const int64_t need = (int64_t)hdr.size() + total + 2;
+  *n_out = need;
+  if (need > capacity) return fail(SC_ERR_CAPACITY, "the JPEG takes %lld bytes, the buffer holds %lld", (long long)need,
+                                   (long long)capacity);
+  if ((rc = grow(c->jpegOut, c->jpegOutAlloc, total))) return rc;
+  hipLaunchKernelGGL(k_jpeg_stuff, dim3((unsigned)d.rows), dim3(64), 0, c->stream, d.rows, rowbuf, row_words, row_bytes,
+                     row_off, c->jpegOut);
+  HIPCHK(hipGetLastError());
+  std::memcpy(out, hdr.data(), hdr.size());
+  HIPCHK(hipMemcpyAsync(out + hdr.size(), c->jpegOut, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out[need - 2] = 0xFF;
+  out[need - 1] = 0xD9;
+  return SC_OK;
+}
+
+static int jpeg_check(sc_ctx* c, int quality, const uint8_t* out, int64_t capacity, const int64_t* n_out) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->in_step) return fail(SC_ERR_STATE, "encoding happens between ticks");
+  if (quality < 1 || quality > 100) return fail(SC_ERR_ARG, "quality %d, expected 1..100", quality);
+  if (!n_out || capacity < 0 || (!out && capacity > 0)) return fail(SC_ERR_ARG, "null n_out, or a negative capacity, or a null buffer");
+  return SC_OK;
+}
+
+int sc_jpeg_encode_device(sc_ctx* c, const uint8_t* dev_rgb, int32_t width, int32_t height, int32_t quality, uint8_t* out,
+                          int64_t capacity, int64_t* n_out) {
+  int rc = jpeg_check(c, quality, out, capacity, n_out);
+  if (rc) return rc;
+  if (!dev_rgb) return fail(SC_ERR_ARG, "null frame");
+  if (width < 1 || width > kRenderMaxSide || height < 1 || height > kRenderMaxSide)
+    return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", width, height, kRenderMaxSide);
+  HIPCHK(hipSetDevice(c->device));
+  return jpeg_encode(c, dev_rgb, width, height, quality, out, capacity, n_out);
+}
+
+int sc_render_jpeg(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, int32_t quality, uint8_t* out,
+                   int64_t capacity, int64_t* n_out) {
+  int rc = jpeg_check(c, quality, out, capacity, n_out);
+  if (rc) return rc;
+  RenderView v;
+  if ((rc = render_prepare(c, view, segments, n_segments, true, v))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = grow(c->renderRgb, c->renderRgbAlloc, 3 * (int64_t)v.width * v.height))) return rc;
+  if ((rc = render_launch(c, v, c->renderRgb))) return rc;
+  return jpeg_encode(c, c->renderRgb, v.width, v.height, quality, out, capacity, n_out);
 }
 
 int sc_download_sort(sc_ctx* c, int64_t* y_floored, int64_t* ids, int64_t room, int64_t* n_out) {

@@ -154,6 +154,43 @@ class Engine:
         N.check(self._lib.sc_render_device(self._ctx, C.byref(view), N.dptr(seg), len(seg), N._P(out.data_ptr())))
         return out
 
+    def _jpeg(self, call, width: int, height: int) -> bytes:
+        """Runs call(out, capacity, n_out) into a host buffer kept between calls, growing it when the file is larger."""
+        buf = getattr(self, "_jpeg_buf", None)
+        if buf is None or len(buf) < 3 * width * height + 4096:  # (a frame's raw size: enough for all but noise)
+            buf = self._jpeg_buf = np.empty(3 * width * height + 4096, dtype=np.uint8)
+        n = C.c_int64(0)
+        rc = call(N._P(buf.ctypes.data), len(buf), C.byref(n))
+        if rc == N.ERR_CAPACITY:
+            buf = self._jpeg_buf = np.empty(n.value, dtype=np.uint8)
+            rc = call(N._P(buf.ctypes.data), len(buf), C.byref(n))
+        N.check(rc)
+        return buf[:n.value].tobytes()
+
+    def encode_jpeg(self, rgb, quality: int = 95) -> bytes:
+        """The JPEG file (sc_jpeg_encode_device) of an H x W x 3 uint8 RGB image: a contiguous CUDA tensor, which must
+        be ready on the library's stream (torch's current stream is synchronised first), or a NumPy array, which is
+        uploaded.  Synchronises.  The bitstream, byte for byte: tests/jpeg_spec.py."""
+        import torch
+        if isinstance(rgb, np.ndarray):
+            rgb = torch.from_numpy(np.ascontiguousarray(rgb)).to(f"cuda:{self.device}")
+        if not getattr(rgb, "is_cuda", False) or rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_contiguous() or \
+                str(rgb.dtype) != "torch.uint8":
+            raise ValueError("rgb must be a contiguous H x W x 3 uint8 CUDA tensor or NumPy array")
+        torch.cuda.current_stream(rgb.device).synchronize()  # (the library's stream does not wait for torch's)
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        ptr = N._P(rgb.data_ptr())
+        return self._jpeg(lambda out, cap, n: self._lib.sc_jpeg_encode_device(self._ctx, ptr, w, h, int(quality), out, cap, n),
+                          w, h)
+
+    def render_jpeg(self, view: N.View, segments, quality: int = 95) -> bytes:
+        """The frame `render` draws, encoded as `encode_jpeg` does, without leaving the GPU before it is compressed
+        (sc_render_jpeg).  Synchronises."""
+        seg = N.f64(segments).reshape(-1, 2, 2)
+        return self._jpeg(lambda out, cap, n: self._lib.sc_render_jpeg(self._ctx, C.byref(view), N.dptr(seg), len(seg),
+                                                                       int(quality), out, cap, n),
+                          int(view.width), int(view.height))
+
     # -- per-tick inputs
     def set_params(self, *, dt, particle_radius, wall_collision_decay, pressure_amplifier, ignored_pressure,
                    collider_noise_level, viscosity, surface_smoothing, target_pressure, gravity) -> None:

@@ -10,7 +10,9 @@ reference writes config.yaml + AVI + GIF (playback.py:109-118) this writes confi
 (positions, pressure and segments every ``--record-every`` ticks), the state dump the reference
 left commented out (playback.py:112-113).  ``--frames`` also renders a ``screen_x`` x ``screen_y`` picture at every
 recorded tick on the GPU (`Crate.render`, what Playback.draw_scene draws) and writes them as ``frames.npz`` and, when PIL
-is installed, ``video.gif`` (playback.py:131-138; there is no AVI).  ``--checkpoint-every K`` also writes resumable checkpoints
+is installed, ``video.gif`` (playback.py:131-138).  ``--video`` renders the same frames and encodes them as JPEG on the GPU
+(`Crate.render_jpeg`, quality ``--video-quality``, default 95 as cv2's); only the compressed frames leave it, and they
+are streamed into ``video.avi``, Motion-JPEG at 50 fps as playback.py:120-129 writes it.  ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
 """
@@ -26,6 +28,7 @@ from typing import Optional
 import numpy as np
 import yaml
 
+from .avi import AviWriter
 from .crate import Crate
 from .load_config import Config, load_config
 
@@ -68,7 +71,8 @@ class HeadlessPlayback:
 
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
-                 resume: Optional[Path] = None, frames: bool = False) -> None:
+                 resume: Optional[Path] = None, frames: bool = False, video: bool = False,
+                 video_quality: int = 95) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -84,13 +88,35 @@ class HeadlessPlayback:
         self.frames: list[dict] = []
         self.render_frames = bool(frames)
         self.images: list[np.ndarray] = []
+        self.video = bool(video)
+        self.video_quality = int(video_quality)
+        self.video_frames = 0
         self.done = False
         self.seconds = 0.0
 
     def run_live_simulation(self, ticks: Optional[int] = None) -> None:
         n = self.config.playback_config.ticks_to_record if ticks is None else ticks
         t0 = time.perf_counter()
-        for _ in range(int(n)):
+        pb = self.config.playback_config
+        avi = None
+        if self.video:
+            self.recording_dir_path.mkdir(exist_ok=True, parents=True)
+            avi = AviWriter(self.recording_dir_path / "video.avi", int(pb.screen_x), int(pb.screen_y), fps=50)
+        try:
+            self._run(int(n), avi)
+        finally:
+            if avi is not None:
+                self.video_frames = avi.frames
+                avi.close()
+        self._collect_checkpoint()
+        self.crate.synchronize()
+        self.seconds = time.perf_counter() - t0
+        if self.config.playback_config.save_recording:
+            self.save_recording(self.recording_dir_path)
+
+    def _run(self, n: int, avi: Optional[AviWriter]) -> None:
+        pb = self.config.playback_config
+        for _ in range(n):
             self.crate.physics_tick()
             if self.checkpoint_every and self.crate.tick % self.checkpoint_every == 0:
                 self._collect_checkpoint()        # the previous one has long arrived
@@ -101,15 +127,11 @@ class HeadlessPlayback:
                                     "pressure": self.crate.particles_pressure.copy(),
                                     "segments": self.crate.segments.copy()})
                 if self.render_frames:
-                    pb = self.config.playback_config
                     self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y)))
+                if avi is not None:
+                    avi.write(self.crate.render_jpeg(int(pb.screen_x), int(pb.screen_y), quality=self.video_quality))
             if self.done:
                 break
-        self._collect_checkpoint()
-        self.crate.synchronize()
-        self.seconds = time.perf_counter() - t0
-        if self.config.playback_config.save_recording:
-            self.save_recording(self.recording_dir_path)
 
     def _collect_checkpoint(self) -> None:
         if self._checkpoint_tick is None:
@@ -154,7 +176,8 @@ def write_frames(out_dir: Path, frames, ticks) -> None:
 
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
-         resume: Optional[Path] = None, frames: bool = False) -> list[dict]:
+         resume: Optional[Path] = None, frames: bool = False, video: bool = False,
+         video_quality: int = 95) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -162,7 +185,8 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
             break
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
-                                    checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames)
+                                    checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
+                                    video=video, video_quality=video_quality)
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -184,6 +208,10 @@ if __name__ == "__main__":
     ap.add_argument("--resume", type=Path, default=None, help="continue the first variant from this checkpoint file")
     ap.add_argument("--frames", action="store_true", help="also render a frame every --record-every ticks (frames.npz, "
                     "video.gif)")
+    ap.add_argument("--video", action="store_true", help="also render and JPEG-encode a frame on the GPU every "
+                    "--record-every ticks, streamed into video.avi (Motion-JPEG, 50 fps)")
+    ap.add_argument("--video-quality", type=int, default=95, help="JPEG quality of --video, 1..100 (default 95)")
     a = ap.parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
-         record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames)
+         record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
+         video=a.video, video_quality=a.video_quality)
