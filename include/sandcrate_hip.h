@@ -293,10 +293,12 @@ int sc_restore_counters(sc_ctx* ctx, int64_t tick, int64_t next_id);
 /* NumPy's legacy global generator on the device (the reference draws particle sources and collider noise from
  * `np.random`, seeded in Crate.__init__, crate.py:22).  sc_rng_set_state hands the stream to the context -- the
  * 624-word key and the position of `np.random.get_state()` -- and from then on
- *   sc_emit_particles  runs ParticleSource.generate_particles (particle_source.py:17-24) for the given sources
- *                      on the device: binomial(flow, dt) new particles each (legacy inversion branch; SC_ERR_DOMAIN
- *                      if flow * dt > 30 or dt > 0.5), rand(n, 2) position jitter, rand(n, 2) velocity noise,
- *                      capped at max_particles minus the stored count, appended with the next ids;
+ *   sc_emit_particles  runs ParticleSource.generate_particles (particle_source.py:17-24) for the given sources,
+ *                      any number of them, in order on the device: binomial(flow, dt) new particles each (the legacy
+ *                      inversion branch up to flow * dt = 30, BTPE beyond; SC_ERR_DOMAIN if flow < 1, dt <= 0 or
+ *                      dt > 0.5), rand(n, 2) position jitter, rand(n, 2) velocity noise, capped at max_particles minus
+ *                      the count the previous sources left (a source capped at 0 or less draws its binomial only),
+ *                      appended with the next ids;
  *   sc_step_finish     in SC_NOISE_HOST mode without a sc_set_noise_host call draws the tick's rand(sum C_i, 2)
  *                      block on the device,
  * bit for bit the numbers NumPy would have produced, with no count readback and no upload.  sc_rng_get_state

@@ -454,6 +454,7 @@ class Crate:
                 self._count_known = False
                 return
             except N.NativeError as err:
+                # (sc_emit_particles takes any number of sources: ERR_CAPACITY is the context's capacity)
                 if err.code == N.ERR_CAPACITY:
                     self._grow(max(self._engine.capacity, int(self.max_particles)) + 1024)
                     self._engine.emit_particles(active, self.dt, int(self.max_particles))

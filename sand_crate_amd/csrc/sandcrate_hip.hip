@@ -2094,12 +2094,12 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   if (!c->rng) return fail(SC_ERR_STATE, "sc_rng_set_state has not been called");
   if (c->in_step) return fail(SC_ERR_STATE, "particles cannot change between sc_step_begin and sc_step_finish");
   if (c->prebinned) return fail(SC_ERR_STATE, "particles cannot be emitted after sc_set_next_inputs promised the next tick");
-  if (n_sources > kMaxSources) return fail(SC_ERR_CAPACITY, "%d particle sources, at most %d", n_sources, kMaxSources);
   if (n_sources == 0) return SC_OK;
-  SourcesK k;
-  std::memset(&k, 0, sizeof k);
-  k.n = n_sources;
-  int64_t most = 0;
+  // the sources go to the device in groups of kMaxSources, one k_rng_emit launch per group in source order on the
+  // stream: each launch continues the stream and reads the stored count the previous one left, as one launch would
+  std::vector<SourcesK> groups((n_sources + kMaxSources - 1) / kMaxSources);
+  std::memset(groups.data(), 0, groups.size() * sizeof(SourcesK));
+  int64_t most = 0;  // (over ALL sources: the bounds below are per call)
   for (int i = 0; i < n_sources; ++i) {
     const sc_source& s = sources[i];
     const double p = dt;
@@ -2108,7 +2108,8 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
     if (!(p > 0.0 && p <= 0.5) || s.flow < 1)
       return fail(SC_ERR_DOMAIN, "binomial(%lld, %g): the device draws NumPy's legacy binomial for 0 < p <= 0.5 only",
                   (long long)s.flow, p);
-    SourceK& d = k.src[i];
+    SourcesK& g = groups[i / kMaxSources];
+    SourceK& d = g.src[g.n++];
     d.radius = s.radius; d.px = s.position_x; d.py = s.position_y; d.vx = s.velocity_x; d.vy = s.velocity_y;
     d.noise = s.noise; d.flow = s.flow; d.p = p;
     d.q = 1.0 - p;
@@ -2162,9 +2163,9 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   }
   if (c->next_id + most > std::numeric_limits<int>::max()) return fail(SC_ERR_CAPACITY, "particle ids exhausted");
   HIPCHK(hipSetDevice(c->device));
-  {
+  for (const SourcesK& g : groups) {
     Bracket br(c, K_APPEND);
-    hipLaunchKernelGGL(k_rng_emit, dim3(1), dim3(64), 0, c->stream, k, (long long)max_particles, c->rng, c->counters, c->x[0],
+    hipLaunchKernelGGL(k_rng_emit, dim3(1), dim3(64), 0, c->stream, g, (long long)max_particles, c->rng, c->counters, c->x[0],
                        c->y[0], c->vx[0], c->vy[0], c->id[0], (int)c->cap);
   }
   HIPCHK(hipGetLastError());
