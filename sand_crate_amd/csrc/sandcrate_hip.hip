@@ -15,6 +15,7 @@
 #include <limits>
 #include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "sandcrate_hip.h"
@@ -65,114 +66,154 @@ double sq_threshold(double R) {
   return t;
 }
 
-template <class T>
-hipError_t dalloc(T** p, size_t n) {
-  return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-}
+struct DeviceMem {
+  static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void release(void* p) { (void)hipFree(p); }
+};
 
-// Grows a device buffer of the context to hold n elements (its contents are not kept).
+template <unsigned Flags>
+struct PinnedMem {
+  static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, Flags); }
+  static void release(void* p) { (void)hipHostFree(p); }
+};
+
+// `size()` elements of T that the owner frees.  grow(n, stream) makes room for n elements and does not keep the
+// contents: it waits for `stream` (the last user of the old memory), frees, and records the new size only once the
+// allocation has succeeded -- a failed growth leaves the buffer empty, never dangling or larger than it is.
+template <class T, class Mem>
+class Owned {
+ public:
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+  Owned& operator=(Owned o) noexcept {
+    std::swap(p_, o.p_);
+    std::swap(n_, o.n_);
+    return *this;
+  }
+  ~Owned() { reset(); }
+
+  hipError_t grow(int64_t n, hipStream_t stream) {
+    if (n <= n_) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    reset();
+    void* p = nullptr;
+    const hipError_t a = Mem::alloc(&p, std::max<int64_t>(n, 1) * sizeof(T));
+    if (a != hipSuccess) return a;
+    p_ = (T*)p;
+    n_ = n;
+    return hipSuccess;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  int64_t size() const { return n_; }
+  size_t bytes() const { return (size_t)n_ * sizeof(T); }
+
+ private:
+  void reset() {
+    if (p_) Mem::release(p_);
+    p_ = nullptr;
+    n_ = 0;
+  }
+  T* p_ = nullptr;
+  int64_t n_ = 0;
+};
+
 template <class T>
-int grow(T*& p, int64_t& alloc, int64_t n) {
-  if (n <= alloc) return SC_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  alloc = 0;
-  HIPCHK(dalloc(&p, (size_t)n));
-  alloc = n;
-  return SC_OK;
-}
+using DevBuf = Owned<T, DeviceMem>;
+template <class T>
+using HostBuf = Owned<T, PinnedMem<hipHostMallocDefault>>;  // pinned host memory
+
+// What a tick takes from the caller: coefficients, walls (the segments and their padded twins) and rigid bodies.
+struct TickInputs {
+  sc_params params{};
+  int nseg = 0, nbody = 0;
+  Seg seg[kMaxSeg]{};
+  Seg pad[2 * kMaxSeg]{};
+  BodyK body[kMaxBody]{};
+};
 
 }  // namespace
 
-struct sc_ctx {
+// (hidden: its destructor, which frees the buffers, is not part of the library's exported symbols)
+struct __attribute__((visibility("hidden"))) sc_ctx {
   int device = 0;
   int num_cus = 256;
   int tile_choice = 0;  // 0 = by grid size, 1 = always the narrow pass A tile, 2 = always the wide one (SANDCRATE_TILE, for tests)
   hipStream_t own_stream = nullptr, stream = nullptr;
   int64_t cap = 0;
-  // particle sets: [0] storage order (input of a tick, output of pass B), [1] cell-sorted
-  double *x[2] = {}, *y[2] = {}, *vx[2] = {}, *vy[2] = {};
-  int* id[2] = {};
-  int *cellS = nullptr, *wslotS = nullptr, *cellT = nullptr, *wslotT = nullptr;
-  SortKey* keys = nullptr;  // a bucket slot's (x, id, storage index): k_scatter writes, k_sort_big sorts, k_reorder ranks
-  int* keyCell = nullptr;  // the packed cell of the particle in a bucket slot (k_scatter writes it next to the key)
-  int* tileBounds = nullptr;   // per block of kTileW sorted particles: its three candidate ranges (k_reorder)
-  int* tileBoundsT = nullptr;  // ... the three ranges its neighbor-table slots refer to (the search; sc_tiled.h)
-  int* tileBand = nullptr;  // per block of pass A / B: holds a particle that may be packed into a halo message
+  // the storage set (input of a tick, output of pass B); of the cell-sorted set only the ids are an array of their
+  // own (id[1]) -- positions and velocities are the pairs sxy / svv
+  DevBuf<double> x, y, vx, vy;
+  DevBuf<int> id[2];
+  DevBuf<int> cellS, wslotS, cellT, wslotT;
+  DevBuf<SortKey> keys;  // a bucket slot's (x, id, storage index): k_scatter writes, k_sort_big sorts, k_reorder ranks
+  DevBuf<int> keyCell;  // the packed cell of the particle in a bucket slot (k_scatter writes it next to the key)
+  DevBuf<int> tileBounds;   // per block of kTileW sorted particles: its three candidate ranges (k_reorder)
+  DevBuf<int> tileBoundsT;  // ... the three ranges its neighbor-table slots refer to (the search; sc_tiled.h)
+  DevBuf<int> tileBand;  // per block of pass A / B: holds a particle that may be packed into a halo message
   // halo overlap (sc_set_halo_overlap): the exchange runs on the side stream between the two launches of pass B
   bool overlap = false, band_pending = false;
   bool band_by_flag = false;  // slabs of rows: the split force kernel is ONE launch + a polling kernel on the side stream (sc_set_band_flag)
   bool band_flagged = false;  // the pending band is announced by the flag (k_wait_band), not by ev_band
   int band_epoch = 0;
   hipEvent_t ev_band = nullptr, ev_xchg = nullptr;
-  int *cellCount = nullptr, *cellStart = nullptr, *sortedStamp = nullptr;
-  unsigned long long* scanDesc = nullptr;  // the bucket scan's look-back descriptors, one per 2048 cells (k_scan_cells)
-  unsigned scanStamp = 0;                  // ... and the stamp of its last launch
-  int scan_max_polls = kScanMaxPolls;      // ... and how often a workgroup asks for a predecessor's total before it gives up (sc_set_scan_patience)
-  int2* sortTasks = nullptr;  // k_sort_big's task list (cell, chunk | length): the scan writes it
-  bool piles_now = false;     // the hint "big buckets exist", latched once per tick (sc_step_begin)
+  DevBuf<int> cellCount, cellStart, sortedStamp;
+  DevBuf<unsigned long long> scanDesc;  // the bucket scan's look-back descriptors, one per 2048 cells (k_scan_cells)
+  unsigned scanStamp = 0;               // ... and the stamp of its last launch
+  int scan_max_polls = kScanMaxPolls;   // ... and how often a workgroup asks for a predecessor's total before it gives up (sc_set_scan_patience)
+  DevBuf<int2> sortTasks;  // k_sort_big's task list (cell, chunk | length): the scan writes it
+  bool piles_now = false;  // the hint "big buckets exist", latched once per tick (sc_step_begin)
   RcclComm comm = nullptr;  // RCCL communicator of the slab chain (sc_comm_init), or null
   int comm_rank = -1, comm_world = 0;
   double *haloL = nullptr, *haloR = nullptr;  // send buffers of the last sc_halo_pack (caller-owned device memory)
   int haloCap = 0;
   int64_t halo_ring_from = 0;  // first tick whose halo counts in the progress block belong to the current state
   int64_t live_hint_from = 0;  // the live count the device publishes is usable once a tick >= this one has finished
-  RngState* rng = nullptr;     // NumPy's MT19937 stream on the device (sc_rng_set_state), or null
-  double* monitor = nullptr;   // force monitor: sum of |dv| per phase and the particle count (sc_enable_force_monitor)
+  DevBuf<RngState> rng;        // NumPy's MT19937 stream on the device (sc_rng_set_state), or empty
+  DevBuf<double> monitor;      // force monitor: sum of |dv| per phase and the particle count (sc_enable_force_monitor)
   bool monitor_on = false;
   // checkpoint (sc_checkpoint_begin / _finish): device-side snapshot, pinned host copy, side stream
-  double* snap_d[4] = {};
-  int* snap_id_d = nullptr;
-  RngState* snap_rng_d = nullptr;
-  double* snap_h[4] = {};
-  int* snap_id_h = nullptr;
-  int* snap_counters_h = nullptr;  // C_COUNT counters + [C_COUNT] = RngState follows in snap_rng_h
-  RngState* snap_rng_h = nullptr;
-  int64_t snapAlloc = 0, snap_n_bound = 0, snap_tick = -1;
+  DevBuf<double> snap_d[4];
+  DevBuf<int> snap_id_d;
+  DevBuf<RngState> snap_rng_d;
+  HostBuf<double> snap_h[4];
+  HostBuf<int> snap_id_h;
+  HostBuf<int> snap_counters_h;  // C_COUNT counters
+  HostBuf<RngState> snap_rng_h;
+  int64_t snap_n_bound = 0, snap_tick = -1;
   bool snap_has_rng = false, snap_pending = false;
   hipStream_t side_stream = nullptr;
   hipEvent_t snap_ready = nullptr, snap_done = nullptr;
-  int* colHist = nullptr;      // sc_column_histogram
-  int64_t colHistAlloc = 0;
+  DevBuf<int> colHist;  // sc_column_histogram
   // sc_render: the per-pixel key buffer and (host path) the device frame, grown to the largest frame asked for
-  unsigned long long* renderKeys = nullptr;
-  unsigned char* renderRgb = nullptr;
-  int64_t renderKeyAlloc = 0, renderRgbAlloc = 0;
+  DevBuf<unsigned long long> renderKeys;
+  DevBuf<unsigned char> renderRgb;
   // sc_jpeg_encode_device: the encoder's workspace (coefficients, per-block masks and code lengths, the rows' bit
   // buffers, lengths and offsets; sc_jpeg.h) and the entropy-coded data, each grown to the largest frame asked for
-  unsigned char* jpegWork = nullptr;
-  unsigned char* jpegOut = nullptr;
-  int64_t jpegWorkAlloc = 0, jpegOutAlloc = 0;
-  // host-mapped progress block written by the GPU, read by the host without synchronisation:
-  // [0] big buckets seen by the last finished scan, [1] ticks finished, [2] live particles of that tick,
-  // [4 + 4 (tick % kHaloRing) ..]: halo record counts of that tick (sent left / right, received left / right)
+  DevBuf<unsigned char> jpegWork, jpegOut;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
-  int* bigHintHost = nullptr;
-  int* bigHintDev = nullptr;
+  // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
+  Owned<int, PinnedMem<hipHostMallocMapped>> progress;
+  int* progress_dev = nullptr;  // ... its address on the device
   bool force_rank_big = false;
-  int64_t cellAlloc = 0;
-  double* wrec[2] = {nullptr, nullptr};  // wall records of even / odd ticks
-  int* nbr = nullptr;              // neighbor table of tiles beyond 65535 entries: -(sorted index + 1), 32 bit
-  NbrRow* rows = nullptr;  // neighbor table: a 32-byte row per sorted particle (twenty 12-bit tile slots and the count)
-  double* P = nullptr;
-  XY *sxy = nullptr, *svv = nullptr, *snn = nullptr;  // the sorted positions and velocities, the surface normals: 16-byte pairs
-  int* counters = nullptr;
+  DevBuf<double> wrec[2];  // wall records of even / odd ticks
+  DevBuf<int> nbr;         // neighbor table of tiles beyond 65535 entries: -(sorted index + 1), 32 bit
+  DevBuf<NbrRow> rows;     // neighbor table: a 32-byte row per sorted particle (twenty 12-bit tile slots and the count)
+  DevBuf<double> P;
+  DevBuf<XY> sxy, svv, snn;  // the sorted positions and velocities, the surface normals: 16-byte pairs
+  DevBuf<int> counters;
   // SC_NOISE_HOST
-  int *cntById = nullptr, *offById = nullptr, *idBlockSums = nullptr;
-  int64_t idAlloc = 0;
-  double* eta = nullptr;
-  int64_t etaAlloc = 0, etaPairs = 0;
+  DevBuf<int> cntById, offById, idBlockSums;
+  DevBuf<double> eta;  // pairs of uniforms
+  int64_t etaPairs = 0;
   bool offsets_pending = false;  // the offsets of this tick are left to the launch that draws the noise (k_rng_noise_small)
   // staging for uploads
-  double *stage_xy = nullptr, *stage_vxy = nullptr;
-  int64_t stageAlloc = 0;
+  DevBuf<double> stage_xy, stage_vxy;
+  DevBuf<int> stage_ids;
 
-  sc_params params{};
+  TickInputs now;
   bool have_params = false;
-  int nseg = 0, nbody = 0;
-  Seg seg[kMaxSeg]{};
-  Seg pad[2 * kMaxSeg]{};
-  BodyK body[kMaxBody]{};
   int noise_mode = SC_NOISE_NONE;
   uint64_t seed = 0;
   int64_t tick = 0;
@@ -188,17 +229,14 @@ struct sc_ctx {
   long long own_lo = 0, own_hi = 0;
   int slab_axis = 0;  // 0: slabs of columns (x), 1: of rows (y)
   int halo = 0, has_left = 0, has_right = 0;
-  int* stage_ids = nullptr;
   std::vector<int> ids_host;
   int64_t stats_live = -1;  // live count read by sc_step_stats inside the current tick, or -1
-  int* owned_out = nullptr;
+  DevBuf<int> owned_out;
   World w{};
-  // sc_set_next_inputs: the promised inputs of the tick after the current one
+  // sc_set_next_inputs: the promised inputs of the tick after the current one.  Its pads are never read: only the
+  // WallInputs of that tick are used (sc_step_finish), and they hold no pads.
   bool have_next = false;
-  sc_params next_params{};
-  int next_nseg = 0, next_nbody = 0;
-  Seg next_seg[kMaxSeg]{};
-  BodyK next_body[kMaxBody]{};
+  TickInputs next;
   bool prebinned = false;     // the last sc_step_finish already ran K1 of the coming tick ...
   WallInputs promised{};      // ... with these inputs
 
@@ -243,51 +281,88 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, (n + kBlock - 1) / kB
 // host knowing how many), so launches cover the capacity; surplus workgroups exit on their first load.
 int64_t launch_bound(const sc_ctx* c);
 
+// A slot of the progress block as the device last wrote it (no synchronisation: possibly stale).
+int progress_read(const sc_ctx* c, int slot) { return ((const volatile int*)c->progress.get())[slot]; }
+
+// Waits until the device has published `ticks` finished ticks, or until nothing is queued on the stream any more (the
+// counter is then simply behind: a re-upload or a restore).
+int wait_ticks_finished(sc_ctx* c, int64_t ticks, const char* what) {
+  int spins = 0;
+  while (progress_read(c, kProgressTicks) < ticks) {
+    if (++spins > 64) {
+      const hipError_t q = hipStreamQuery(c->stream);
+      if (q == hipSuccess) break;
+      if (q != hipErrorNotReady) return fail(SC_ERR_HIP, "stream error while waiting for %s: %s", what, hipGetErrorString(q));
+      spins = 0;
+    }
+    sched_yield();
+  }
+  return SC_OK;
+}
+
+// Checks and converts a tick's walls and bodies.  `with_pads`: the padded twins come too (sc_set_segments); a promised
+// tick has none (sc_set_next_inputs).
+int load_walls(TickInputs& in, const double* segments, const double* padded, bool with_pads, int ns, const sc_body* bodies,
+               int nb) {
+  if (ns < 0 || ns > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", ns, kMaxSeg);
+  if (nb < 0 || nb > kMaxBody) return fail(SC_ERR_CAPACITY, "%d bodies, at most %d", nb, kMaxBody);
+  if (ns > 0 && (!segments || (with_pads && !padded)))
+    return fail(SC_ERR_ARG, with_pads ? "null segment arrays" : "null segment array");
+  int total = 0;
+  for (int b = 0; b < nb; ++b) total += bodies[b].n_segments;
+  if (nb > 0 && total != ns) return fail(SC_ERR_ARG, "bodies own %d segments, %d given", total, ns);
+  in.nseg = ns;
+  in.nbody = nb;
+  std::memset(in.seg, 0, sizeof in.seg);
+  std::memset(in.pad, 0, sizeof in.pad);
+  std::memset(in.body, 0, sizeof in.body);
+  for (int k = 0; k < ns; ++k) in.seg[k] = Seg{segments[4 * k], segments[4 * k + 1], segments[4 * k + 2], segments[4 * k + 3]};
+  for (int k = 0; k < 2 * ns && with_pads; ++k)
+    in.pad[k] = Seg{padded[4 * k], padded[4 * k + 1], padded[4 * k + 2], padded[4 * k + 3]};
+  for (int b = 0; b < nb; ++b)
+    in.body[b] = BodyK{bodies[b].position_x,        bodies[b].position_y, bodies[b].center_velocity_x,
+                       bodies[b].center_velocity_y, bodies[b].angular_clockwise_velocity, bodies[b].n_segments, 0};
+  return SC_OK;
+}
+
+// The promised tick will not run as promised: forget the bucket counts its K1 left, the next tick bins afresh.
+int abandon_promise(sc_ctx* c) {
+  HIPCHK(hipMemsetAsync(c->cellCount, 0, c->cellCount.bytes(), c->stream));
+  c->prebinned = false;
+  return SC_OK;
+}
+
+// Each group of buffers below is sized by its last member, which grows last: once it has grown, so have the others.
+
 int ensure_cells(sc_ctx* c, int64_t ncells) {
-  if (ncells + 1 <= c->cellAlloc) return SC_OK;
+  if (ncells + 1 <= c->cellCount.size()) return SC_OK;
   if (ncells > (int64_t)1 << 28) return fail(SC_ERR_CAPACITY, "cell grid of %lld cells is too large", (long long)ncells);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->cellCount) (void)hipFree(c->cellCount);
-  if (c->cellStart) (void)hipFree(c->cellStart);
-  if (c->scanDesc) (void)hipFree(c->scanDesc);
-  if (c->sortedStamp) (void)hipFree(c->sortedStamp);
-  int64_t n = ncells + 1 + ncells / 4;
-  HIPCHK(dalloc(&c->cellCount, n));
-  HIPCHK(dalloc(&c->cellStart, n + 1));
-  HIPCHK(dalloc(&c->scanDesc, n / kScanPerBlock + 4));
-  HIPCHK(hipMemsetAsync(c->scanDesc, 0, (n / kScanPerBlock + 4) * sizeof(unsigned long long), c->stream));  // stamp 0: never launched
-  HIPCHK(dalloc(&c->sortedStamp, n));
-  HIPCHK(hipMemsetAsync(c->sortedStamp, 0, n * sizeof(int), c->stream));
-  HIPCHK(hipMemsetAsync(c->cellCount, 0, n * sizeof(int), c->stream));
-  c->cellAlloc = n;
+  const int64_t n = ncells + 1 + ncells / 4;
+  HIPCHK(c->cellStart.grow(n + 1, c->stream));
+  HIPCHK(c->scanDesc.grow(n / kScanPerBlock + 4, c->stream));
+  HIPCHK(hipMemsetAsync(c->scanDesc, 0, c->scanDesc.bytes(), c->stream));  // stamp 0: never launched
+  HIPCHK(c->sortedStamp.grow(n, c->stream));
+  HIPCHK(hipMemsetAsync(c->sortedStamp, 0, c->sortedStamp.bytes(), c->stream));
+  HIPCHK(c->cellCount.grow(n, c->stream));
+  HIPCHK(hipMemsetAsync(c->cellCount, 0, c->cellCount.bytes(), c->stream));
   return SC_OK;
 }
 
 int ensure_ids(sc_ctx* c, int64_t n) {
-  if (n <= c->idAlloc) return SC_OK;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->cntById) (void)hipFree(c->cntById);
-  if (c->offById) (void)hipFree(c->offById);
-  if (c->idBlockSums) (void)hipFree(c->idBlockSums);
-  int64_t m = n + n / 2 + 1024;
-  HIPCHK(dalloc(&c->cntById, m));
-  HIPCHK(dalloc(&c->offById, m + 1));
-  HIPCHK(dalloc(&c->idBlockSums, m / kScanPerBlock + 2));
-  c->idAlloc = m;
+  if (n <= c->cntById.size()) return SC_OK;
+  const int64_t m = n + n / 2 + 1024;
+  HIPCHK(c->offById.grow(m + 1, c->stream));
+  HIPCHK(c->idBlockSums.grow(m / kScanPerBlock + 2, c->stream));
+  HIPCHK(c->cntById.grow(m, c->stream));
   return SC_OK;
 }
 
 int ensure_stage(sc_ctx* c, int64_t n) {
-  if (n <= c->stageAlloc) return SC_OK;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->stage_xy) (void)hipFree(c->stage_xy);
-  if (c->stage_vxy) (void)hipFree(c->stage_vxy);
-  if (c->stage_ids) (void)hipFree(c->stage_ids);
-  int64_t m = n + n / 2 + 256;
-  HIPCHK(dalloc(&c->stage_xy, 2 * m));
-  HIPCHK(dalloc(&c->stage_vxy, 2 * m));
-  HIPCHK(dalloc(&c->stage_ids, m));
-  c->stageAlloc = m;
+  if (n <= c->stage_ids.size()) return SC_OK;
+  const int64_t m = n + n / 2 + 256;
+  HIPCHK(c->stage_xy.grow(2 * m, c->stream));
+  HIPCHK(c->stage_vxy.grow(2 * m, c->stream));
+  HIPCHK(c->stage_ids.grow(m, c->stream));
   return SC_OK;
 }
 
@@ -304,8 +379,8 @@ int launch_scan(sc_ctx* c, const int* in, int* out, int64_t n, int* blockSums, i
 // Kernel-argument block of this tick.  The cell grid covers [-r, 1+r]^2 -- where
 // remove_particles (crate.py:152) leaves particles -- plus three cells of margin for the hard wall
 // fix, plus a ring of always-empty cells so that c-1 / c+1 / c+-ncols never leave the arrays.
-int build_world(sc_ctx* c, World& w, const sc_params& p, int nseg, const Seg* seg, const Seg* pad, int nbody,
-                const BodyK* body, int64_t tick) {
+int build_world(sc_ctx* c, World& w, const TickInputs& in, int64_t tick) {
+  const sc_params& p = in.params;
   std::memset(&w, 0, sizeof w);
   const double inf = std::numeric_limits<double>::infinity();
   if (c->custom_grid) {
@@ -380,11 +455,11 @@ int build_world(sc_ctx* c, World& w, const sc_params& p, int nseg, const Seg* se
   w.dt_gy = w.dt * w.gy;
   w.dt_visc = w.dt * w.visc;
   w.dt_pamp = w.dt * w.pamp;
-  w.nseg = nseg;
-  w.nbody = nbody;
-  std::memcpy(w.seg, seg, sizeof w.seg);
-  if (pad) std::memcpy(w.pad, pad, sizeof w.pad);
-  std::memcpy(w.body, body, sizeof w.body);
+  w.nseg = in.nseg;
+  w.nbody = in.nbody;
+  std::memcpy(w.seg, in.seg, sizeof w.seg);
+  std::memcpy(w.pad, in.pad, sizeof w.pad);
+  std::memcpy(w.body, in.body, sizeof w.body);
   w.noise_mode = c->noise_mode;
   w.tick = (int)tick;
   w.noise_key = mix64(c->seed + (uint64_t)(tick + 1) * kGold);
@@ -395,7 +470,7 @@ int build_world(sc_ctx* c, World& w, const sc_params& p, int nseg, const Seg* se
   w.own_hi = c->slab ? c->own_hi : std::numeric_limits<long long>::max();
   w.halo = c->halo;
   {  // where the particles are expected to end: for slabs a recent tick's live count (blocks beyond it are placed one by one)
-    const int64_t done = *(volatile int*)(c->bigHintHost + 1), published = *(volatile int*)(c->bigHintHost + 2);
+    const int64_t done = progress_read(c, kProgressTicks), published = progress_read(c, kProgressLive);
     const int64_t bound = launch_bound(c);
     w.live_hint = (int)(c->slab && published > 0 && done > c->live_hint_from
                             ? std::min<int64_t>(bound, (int64_t)published + 2048)
@@ -408,7 +483,7 @@ int build_world(sc_ctx* c, World& w, const sc_params& p, int nseg, const Seg* se
 
 int make_world(sc_ctx* c) {
   if (!c->custom_grid && !c->have_params) return fail(SC_ERR_STATE, "sc_set_params has not been called");
-  int rc = build_world(c, c->w, c->params, c->nseg, c->seg, c->pad, c->nbody, c->body, c->tick);
+  int rc = build_world(c, c->w, c->now, c->tick);
   if (rc) return rc;
   return ensure_cells(c, (int64_t)c->w.nrows * c->w.ncols);
 }
@@ -454,9 +529,9 @@ int put_particles(sc_ctx* c, const double* xy, const double* vxy, int64_t n, boo
   if (c->in_step) return fail(SC_ERR_STATE, "particles cannot change between sc_step_begin and sc_step_finish");
   if (c->prebinned && !reset)
     return fail(SC_ERR_STATE, "particles cannot be appended after sc_set_next_inputs promised the next tick");
-  if (c->prebinned && reset) {  // the promised tick is abandoned: forget its bucket counts
-    HIPCHK(hipMemsetAsync(c->cellCount, 0, c->cellAlloc * sizeof(int), c->stream));
-    c->prebinned = false;
+  if (c->prebinned && reset) {
+    const int rc = abandon_promise(c);
+    if (rc) return rc;
   }
   int64_t base = reset ? 0 : c->upper;
   if (base + n > c->cap)
@@ -483,13 +558,13 @@ int put_particles(sc_ctx* c, const double* xy, const double* vxy, int64_t n, boo
         ids32[k] = (int)ids[k];
         max_id = std::max<int64_t>(max_id, ids[k]);
       }
-      dev_ids = c->stage_ids;  // its own allocation of stageAlloc entries (ensure_stage)
+      dev_ids = c->stage_ids;  // room for n ids (ensure_stage)
       HIPCHK(hipMemcpyAsync(dev_ids, ids32.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
       c->next_id = std::max<int64_t>(c->next_id, max_id + 1 - n);
     }
     Bracket br(c, K_APPEND);
     hipLaunchKernelGGL(k_append, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, c->stage_xy, c->stage_vxy, (int)n,
-                       (int)c->next_id, dev_ids, c->counters, c->x[0], c->y[0], c->vx[0], c->vy[0], c->id[0], reset ? 1 : 0, (int)c->cap);
+                       (int)c->next_id, dev_ids, c->counters, c->x, c->y, c->vx, c->vy, c->id[0], reset ? 1 : 0, (int)c->cap);
   }
   c->upper = base + n;
   c->next_id += n;
@@ -526,7 +601,7 @@ void launch_pass_a(sc_ctx* c, int kernel_id) {
   // occupancy wins (measured with 128-wide tiles: 262,144 particles 35.9 -> 32.2 us wide; 1,048,576: 78 us
   // narrow, 82 us wide)
   // (slabs size their grids by capacity; the live count a recent tick published is the better estimate of the work)
-  const int published = *(volatile int*)(c->bigHintHost + 2);
+  const int published = progress_read(c, kProgressLive);
   const int tiles = c->slab && published > 0 ? (published + kTileW - 1) / kTileW + 64 : tile_grid(c);
   if (c->tile_choice ? c->tile_choice == 2 : tiles <= (8 * 128 / kTileW) * c->num_cus)
     launch_pass_a_cap<NOISE, ENUM, DENS, kTileCapAWide>(c);
@@ -558,8 +633,8 @@ void launch_pass_b(sc_ctx* c, const WallInputs& wn, int part = 0) {
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTileW), 0, stream, c->w, c->counters, c->sxy, c->svv,
                        c->id[1], c->wslotT, c->cellT, c->nbr, c->rows, (int)c->cap, c->eta, c->offById, c->P,
-                       c->snn, c->wrec[cur], c->x[0], c->y[0], c->vx[0], c->vy[0], c->id[0], c->tileBoundsT,
-                       c->bigHintDev, wn, c->cellS, c->wslotS, c->cellCount, c->wrec[nxt], c->haloL, c->haloR, c->haloCap,
+                       c->snn, c->wrec[cur], c->x, c->y, c->vx, c->vy, c->id[0], c->tileBoundsT,
+                       c->progress_dev, wn, c->cellS, c->wslotS, c->cellCount, c->wrec[nxt], c->haloL, c->haloR, c->haloCap,
                        c->monitor, c->tileBand, part, bandw, c->band_epoch);
   };
   auto pick = [&]() {
@@ -625,42 +700,41 @@ int sc_create(int device, int64_t capacity, sc_ctx** out) {
     c->num_cus = 256;
   if (const char* tile = std::getenv("SANDCRATE_TILE"))
     c->tile_choice = !std::strcmp(tile, "narrow") ? 1 : !std::strcmp(tile, "wide") ? 2 : 0;
-  size_t n = (size_t)capacity;
+  const int64_t n = capacity;
   hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   c->stream = c->own_stream;
-  // [0]: the storage set (a tick's input and output); [1]: the sorted set, of which only the ids are an array of their
-  // own -- positions and velocities are the pairs sxy / svv
-  if (e == hipSuccess) e = dalloc(&c->x[0], n);
-  if (e == hipSuccess) e = dalloc(&c->y[0], n);
-  if (e == hipSuccess) e = dalloc(&c->vx[0], n);
-  if (e == hipSuccess) e = dalloc(&c->vy[0], n);
-  for (int s = 0; s < 2 && e == hipSuccess; ++s) e = dalloc(&c->id[s], n);
-  if (e == hipSuccess) e = dalloc(&c->cellS, n);
-  if (e == hipSuccess) e = dalloc(&c->wslotS, n);
-  if (e == hipSuccess) e = dalloc(&c->cellT, n);
-  if (e == hipSuccess) e = dalloc(&c->wslotT, n);
-  if (e == hipSuccess) e = dalloc(&c->keys, n);
-  if (e == hipSuccess) e = dalloc(&c->keyCell, n);
-  if (e == hipSuccess) e = dalloc(&c->tileBounds, 6 * (n / kTileW + 2));
-  if (e == hipSuccess) e = dalloc(&c->tileBoundsT, 6 * (n / kTileW + 2));
-  if (e == hipSuccess) e = dalloc(&c->tileBand, n / kTileW + 2);
-  if (e == hipSuccess) e = hipMemsetAsync(c->tileBand, 0, (n / kTileW + 2) * sizeof(int), c->stream);
-  if (e == hipSuccess) e = dalloc(&c->sortTasks, (size_t)kMaxSortTasks);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->bigHintHost, kProgressInts * sizeof(int), hipHostMallocMapped);
+  if (e == hipSuccess) e = c->x.grow(n, c->stream);
+  if (e == hipSuccess) e = c->y.grow(n, c->stream);
+  if (e == hipSuccess) e = c->vx.grow(n, c->stream);
+  if (e == hipSuccess) e = c->vy.grow(n, c->stream);
+  if (e == hipSuccess) e = c->id[0].grow(n, c->stream);
+  if (e == hipSuccess) e = c->id[1].grow(n, c->stream);
+  if (e == hipSuccess) e = c->cellS.grow(n, c->stream);
+  if (e == hipSuccess) e = c->wslotS.grow(n, c->stream);
+  if (e == hipSuccess) e = c->cellT.grow(n, c->stream);
+  if (e == hipSuccess) e = c->wslotT.grow(n, c->stream);
+  if (e == hipSuccess) e = c->keys.grow(n, c->stream);
+  if (e == hipSuccess) e = c->keyCell.grow(n, c->stream);
+  if (e == hipSuccess) e = c->tileBounds.grow(6 * (n / kTileW + 2), c->stream);
+  if (e == hipSuccess) e = c->tileBoundsT.grow(6 * (n / kTileW + 2), c->stream);
+  if (e == hipSuccess) e = c->tileBand.grow(n / kTileW + 2, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(c->tileBand, 0, c->tileBand.bytes(), c->stream);
+  if (e == hipSuccess) e = c->sortTasks.grow(kMaxSortTasks, c->stream);
+  if (e == hipSuccess) e = c->progress.grow(kProgressInts, c->stream);
   if (e == hipSuccess) {
-    for (int k = 0; k < kProgressInts; ++k) c->bigHintHost[k] = 0;
-    e = hipHostGetDevicePointer((void**)&c->bigHintDev, c->bigHintHost, 0);
+    std::fill_n(c->progress.get(), kProgressInts, 0);
+    e = hipHostGetDevicePointer((void**)&c->progress_dev, c->progress, 0);
   }
-  if (e == hipSuccess) e = dalloc(&c->wrec[0], 5 * n);
-  if (e == hipSuccess) e = dalloc(&c->wrec[1], 5 * n);
-  if (e == hipSuccess) e = dalloc(&c->nbr, (size_t)kMaxNbr * n);
-  if (e == hipSuccess) e = dalloc(&c->rows, n);
-  if (e == hipSuccess) e = dalloc(&c->P, n);
-  if (e == hipSuccess) e = dalloc(&c->snn, n);
-  if (e == hipSuccess) e = dalloc(&c->sxy, n);
-  if (e == hipSuccess) e = dalloc(&c->svv, n);
-  if (e == hipSuccess) e = dalloc(&c->counters, (size_t)C_ALLOC);
-  if (e == hipSuccess) e = hipMemsetAsync(c->counters, 0, C_ALLOC * sizeof(int), c->stream);
+  if (e == hipSuccess) e = c->wrec[0].grow(5 * n, c->stream);
+  if (e == hipSuccess) e = c->wrec[1].grow(5 * n, c->stream);
+  if (e == hipSuccess) e = c->nbr.grow(kMaxNbr * n, c->stream);
+  if (e == hipSuccess) e = c->rows.grow(n, c->stream);
+  if (e == hipSuccess) e = c->P.grow(n, c->stream);
+  if (e == hipSuccess) e = c->snn.grow(n, c->stream);
+  if (e == hipSuccess) e = c->sxy.grow(n, c->stream);
+  if (e == hipSuccess) e = c->svv.grow(n, c->stream);
+  if (e == hipSuccess) e = c->counters.grow(C_ALLOC, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(c->counters, 0, c->counters.bytes(), c->stream);
   if (e != hipSuccess) {
     int rc = fail(SC_ERR_HIP, "sc_create: %s", hipGetErrorString(e));
     sc_destroy(c);
@@ -675,35 +749,18 @@ int sc_destroy(sc_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   if (c->comm) (void)sc_comm_destroy(c);
-  for (int s = 0; s < 2; ++s) {
-    (void)hipFree(c->x[s]);
-    (void)hipFree(c->y[s]);
-    (void)hipFree(c->vx[s]);
-    (void)hipFree(c->vy[s]);
-    (void)hipFree(c->id[s]);
-  }
   if (c->ev_band) (void)hipEventDestroy(c->ev_band);
   if (c->ev_xchg) (void)hipEventDestroy(c->ev_xchg);
-  void* ptrs[] = {c->cellS, c->wslotS, c->cellT, c->wslotT, c->keys, c->keyCell, c->tileBounds, c->tileBoundsT, c->tileBand, c->cellCount, c->cellStart, c->scanDesc, c->sortedStamp, c->sortTasks, c->wrec[0], c->wrec[1],
-                  c->nbr, c->rows, c->P, c->snn, c->sxy, c->svv, c->counters, c->cntById, c->offById, c->idBlockSums, c->eta,
-                  c->stage_xy, c->stage_vxy, c->stage_ids, c->owned_out, c->colHist, c->rng, c->monitor, c->renderKeys, c->renderRgb, c->jpegWork, c->jpegOut,
-                  c->snap_d[0], c->snap_d[1], c->snap_d[2], c->snap_d[3], c->snap_id_d, c->snap_rng_d};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
   for (auto& v : {c->ev_used, c->ev_free})
     for (auto& e : v) {
       (void)hipEventDestroy(e.a);
       (void)hipEventDestroy(e.b);
     }
-  for (void* p : {(void*)c->snap_h[0], (void*)c->snap_h[1], (void*)c->snap_h[2], (void*)c->snap_h[3], (void*)c->snap_id_h,
-                  (void*)c->snap_counters_h, (void*)c->snap_rng_h})
-    if (p) (void)hipHostFree(p);
   if (c->snap_ready) (void)hipEventDestroy(c->snap_ready);
   if (c->snap_done) (void)hipEventDestroy(c->snap_done);
   if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-  if (c->bigHintHost) (void)hipHostFree(c->bigHintHost);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // frees the buffers
   return SC_OK;
 }
 
@@ -744,8 +801,8 @@ int sc_synchronize(sc_ctx* c) {
     if (h[C_FLAGS] & F_SCAN_TIMEOUT) {
       // the tick was abandoned behind its scan: its bucket counts were never consumed, and whatever a look-ahead
       // promised for the tick after it was never computed -- the next tick starts from the storage arrays
-      HIPCHK(hipMemsetAsync(c->cellCount, 0, c->cellAlloc * sizeof(int), c->stream));
-      c->prebinned = false;
+      rc = abandon_promise(c);
+      if (rc) return rc;
     }
     return check_flags(h[C_FLAGS]);
   }
@@ -771,7 +828,7 @@ int sc_count(sc_ctx* c, int64_t* n) {
 int sc_set_params(sc_ctx* c, const sc_params* p) {
   if (!c || !p) return fail(SC_ERR_ARG, "null argument");
   if (c->in_step) return fail(SC_ERR_STATE, "coefficients cannot change inside a tick");
-  c->params = *p;
+  c->now.params = *p;
   c->have_params = true;
   return SC_OK;
 }
@@ -780,23 +837,7 @@ int sc_set_segments(sc_ctx* c, const double* segments, const double* padded, int
                     int32_t nb) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (c->in_step) return fail(SC_ERR_STATE, "segments cannot change inside a tick");
-  if (ns < 0 || ns > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", ns, kMaxSeg);
-  if (nb < 0 || nb > kMaxBody) return fail(SC_ERR_CAPACITY, "%d bodies, at most %d", nb, kMaxBody);
-  if (ns > 0 && (!segments || !padded)) return fail(SC_ERR_ARG, "null segment arrays");
-  int total = 0;
-  for (int b = 0; b < nb; ++b) total += bodies[b].n_segments;
-  if (nb > 0 && total != ns) return fail(SC_ERR_ARG, "bodies own %d segments, %d given", total, ns);
-  c->nseg = ns;
-  c->nbody = nb;
-  std::memset(c->seg, 0, sizeof c->seg);
-  std::memset(c->pad, 0, sizeof c->pad);
-  std::memset(c->body, 0, sizeof c->body);
-  for (int k = 0; k < ns; ++k) c->seg[k] = Seg{segments[4 * k], segments[4 * k + 1], segments[4 * k + 2], segments[4 * k + 3]};
-  for (int k = 0; k < 2 * ns; ++k) c->pad[k] = Seg{padded[4 * k], padded[4 * k + 1], padded[4 * k + 2], padded[4 * k + 3]};
-  for (int b = 0; b < nb; ++b)
-    c->body[b] = BodyK{bodies[b].position_x,        bodies[b].position_y, bodies[b].center_velocity_x,
-                       bodies[b].center_velocity_y, bodies[b].angular_clockwise_velocity, bodies[b].n_segments, 0};
-  return SC_OK;
+  return load_walls(c->now, segments, padded, true, ns, bodies, nb);
 }
 
 int sc_set_noise_mode(sc_ctx* c, int mode, uint64_t seed) {
@@ -813,7 +854,7 @@ static int launch_noise_offsets(sc_ctx* c) {
   Bracket br(c, K_NOISE_OFFSETS);
   HIPCHK(hipMemsetAsync(c->cntById, 0, c->next_id * sizeof(int), c->stream));
   hipLaunchKernelGGL(k_count_by_id, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->counters, c->id[1],
-                     (const unsigned int*)c->rows, c->cntById);
+                     (const unsigned int*)c->rows.get(), c->cntById);
   return launch_scan(c, c->cntById, c->offById, c->next_id, c->idBlockSums, nullptr);
 }
 
@@ -827,16 +868,8 @@ int sc_step_begin(sc_ctx* c) {
   // host is, and a bounded queue keeps per-tick hints (big buckets) at most that many ticks stale.
   constexpr int64_t kMaxTicksQueued = 4;
   if (!c->custom_grid) {
-    int spins = 0;
-    while (c->tick - (int64_t) * (volatile int*)(c->bigHintHost + 1) > kMaxTicksQueued) {
-      if (++spins > 64) {
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q == hipSuccess) break;  // nothing queued: the counter is simply behind (re-upload)
-        if (q != hipErrorNotReady) return fail(SC_ERR_HIP, "stream error while waiting for queued ticks: %s", hipGetErrorString(q));
-        spins = 0;
-      }
-      sched_yield();
-    }
+    const int rc = wait_ticks_finished(c, c->tick - kMaxTicksQueued, "queued ticks");
+    if (rc) return rc;
   }
   int rc = make_world(c);
   if (rc) return rc;
@@ -845,7 +878,7 @@ int sc_step_begin(sc_ctx* c) {
   int cap = (int)c->cap;
   // big buckets were seen by the last scan the host knows about (an unsynchronised, possibly stale hint in host-mapped
   // memory), read ONCE per tick
-  c->piles_now = c->force_rank_big || *(volatile int*)c->bigHintHost > 0;
+  c->piles_now = c->force_rank_big || progress_read(c, kProgressBigBuckets) > 0;
   if (c->prebinned) {
     // the previous sc_step_finish ran K1 of this tick with the promised inputs: they must be the inputs
     const WallInputs now = wall_inputs_of(w);
@@ -854,7 +887,7 @@ int sc_step_begin(sc_ctx* c) {
     c->prebinned = false;
   } else {
     Bracket br(c, K_WALL_BIN);
-    hipLaunchKernelGGL(k_wall_bin, dim3(grid), dim3(kBlock), 0, c->stream, w, c->counters, c->x[0], c->y[0], c->cellS,
+    hipLaunchKernelGGL(k_wall_bin, dim3(grid), dim3(kBlock), 0, c->stream, w, c->counters, c->x, c->y, c->cellS,
                        c->wslotS, c->cellCount, c->wrec[c->tick & 1], cap);
   }
   {
@@ -868,10 +901,10 @@ int sc_step_begin(sc_ctx* c) {
   {
     Bracket br(c, K_SCATTER);
     if (piles_expected(c))
-      hipLaunchKernelGGL(k_scatter<true>, dim3(grid), dim3(kBlock), 0, c->stream, c->counters, c->cellS, c->x[0],
+      hipLaunchKernelGGL(k_scatter<true>, dim3(grid), dim3(kBlock), 0, c->stream, c->counters, c->cellS, c->x,
                          c->id[0], Buckets{c->cellStart}, c->cellCount, c->keys, c->keyCell, cap, w.live_hint);
     else
-      hipLaunchKernelGGL(k_scatter<false>, dim3(grid), dim3(kBlock), 0, c->stream, c->counters, c->cellS, c->x[0],
+      hipLaunchKernelGGL(k_scatter<false>, dim3(grid), dim3(kBlock), 0, c->stream, c->counters, c->cellS, c->x,
                          c->id[0], Buckets{c->cellStart}, c->cellCount, c->keys, c->keyCell, cap, w.live_hint);
   }
   const int stamp = (int)((c->tick + 1) & 0x3FFFFFFF);
@@ -886,8 +919,8 @@ int sc_step_begin(sc_ctx* c) {
     Bracket br(c, K_REORDER);
     hipLaunchKernelGGL(k_reorder, dim3((int)std::max<int64_t>(1, (launch_bound(c) + kReorderBlock - 1) / kReorderBlock)),
                        dim3(kReorderBlock), 0, c->stream, c->counters, c->keys, c->keyCell,
-                       c->cellS, Buckets{c->cellStart}, c->wslotS, c->y[0], c->vx[0], c->vy[0], c->sxy, c->svv,
-                       c->id[1], c->cellT, c->wslotT, c->sortedStamp, stamp, w.ncols, c->tileBounds, w.live_hint, c->bigHintDev);
+                       c->cellS, Buckets{c->cellStart}, c->wslotS, c->y, c->vx, c->vy, c->sxy, c->svv,
+                       c->id[1], c->cellT, c->wslotT, c->sortedStamp, stamp, w.ncols, c->tileBounds, w.live_hint, c->progress_dev);
   }
   // SC_NOISE_HOST (and the stand-alone search) stop after the lists: the host's rand block can only be
   // indexed once every count is known.  Otherwise the search and pass A are one launch.
@@ -918,7 +951,7 @@ int sc_step_begin(sc_ctx* c) {
 int sc_step_stats(sc_ctx* c, sc_stats* out) {
   if (!c || !out) return fail(SC_ERR_ARG, "null argument");
   if (!c->in_step) return fail(SC_ERR_STATE, "sc_step_stats needs sc_step_begin first");
-  hipLaunchKernelGGL(k_count_stats, dim3(1), dim3(kBlock), 0, c->stream, c->counters, (const unsigned int*)c->rows, c->wslotT);
+  hipLaunchKernelGGL(k_count_stats, dim3(1), dim3(kBlock), 0, c->stream, c->counters, (const unsigned int*)c->rows.get(), c->wslotT);
   int h[C_COUNT];
   int rc = read_counters(c, h);
   if (rc) return rc;
@@ -940,14 +973,7 @@ int sc_set_noise_host(sc_ctx* c, const double* u01, int64_t n_pairs) {
     int rc = launch_noise_offsets(c);
     if (rc) return rc;
   }
-  if (n_pairs > c->etaAlloc) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->eta) (void)hipFree(c->eta);
-    c->eta = nullptr;
-    int64_t m = n_pairs + n_pairs / 2 + 1024;
-    HIPCHK(dalloc(&c->eta, 2 * m));
-    c->etaAlloc = m;
-  }
+  if (2 * n_pairs > c->eta.size()) HIPCHK(c->eta.grow(2 * (n_pairs + n_pairs / 2 + 1024), c->stream));
   if (n_pairs > 0)
     HIPCHK(hipMemcpyAsync(c->eta, u01, 2 * n_pairs * sizeof(double), hipMemcpyHostToDevice, c->stream));
   c->etaPairs = n_pairs;
@@ -961,22 +987,16 @@ int sc_step_finish(sc_ctx* c) {
     if (!c->rng) return fail(SC_ERR_STATE, "SC_NOISE_HOST: sc_set_noise_host must be called every tick (or sc_rng_set_state once)");
     // the device holds the stream: draw the tick's rand(sum C_i, 2) there; sum C_i is the last entry of the
     // offsets sc_step_begin scanned, so the host never learns it
-    const int64_t room = (int64_t)kMaxNbr * c->cap;
-    if (room > c->etaAlloc) {
-      HIPCHK(hipStreamSynchronize(c->stream));
-      if (c->eta) (void)hipFree(c->eta);
-      c->eta = nullptr;
-      HIPCHK(dalloc(&c->eta, 2 * (size_t)room));
-      c->etaAlloc = room;
-    }
+    HIPCHK(c->eta.grow(2 * kMaxNbr * c->cap, c->stream));
+    const long long eta_pairs = c->eta.size() / 2;
     if (c->next_id > 0) {
       Bracket br(c, K_NOISE_OFFSETS);
       if (c->offsets_pending)
-        hipLaunchKernelGGL(k_rng_noise_small, dim3(1), dim3(kSmallBlock), 0, c->stream, c->rng, c->id[1], (const unsigned int*)c->rows,
-                           (int)c->next_id, c->cntById, c->offById, c->eta, (long long)c->etaAlloc, c->counters);
+        hipLaunchKernelGGL(k_rng_noise_small, dim3(1), dim3(kSmallBlock), 0, c->stream, c->rng, c->id[1], (const unsigned int*)c->rows.get(),
+                           (int)c->next_id, c->cntById, c->offById, c->eta, eta_pairs, c->counters);
       else
         hipLaunchKernelGGL(k_rng_noise, dim3(1), dim3(kRngBlock), 0, c->stream, c->rng, c->offById + c->next_id, c->eta,
-                           (long long)c->etaAlloc, c->counters);
+                           eta_pairs, c->counters);
       c->offsets_pending = false;
     }
     c->etaPairs = 0;
@@ -989,8 +1009,7 @@ int sc_step_finish(sc_ctx* c) {
   const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on;  // the monitor runs with the plain kernel
   if (fused) {
     World next;
-    int rc = build_world(c, next, c->next_params, c->next_nseg, c->next_seg, nullptr, c->next_nbody, c->next_body,
-                         c->tick + 1);
+    int rc = build_world(c, next, c->next, c->tick + 1);
     if (rc) return rc;
     if (next.nrows != c->w.nrows || next.ncols != c->w.ncols) {
       rc = ensure_cells(c, (int64_t)next.nrows * next.ncols);  // the radius changed: the grid may have grown
@@ -1034,11 +1053,7 @@ int sc_step(sc_ctx* c, int32_t n_ticks) {
     int rc = sc_step_begin(c);
     if (rc) return rc;
     if (t + 1 < n_ticks) {  // the next tick of this call has the same inputs: promise them
-      c->next_params = c->params;
-      c->next_nseg = c->nseg;
-      c->next_nbody = c->nbody;
-      std::memcpy(c->next_seg, c->seg, sizeof c->next_seg);
-      std::memcpy(c->next_body, c->body, sizeof c->next_body);
+      c->next = c->now;
       c->have_next = true;
     }
     rc = sc_step_finish(c);
@@ -1073,22 +1088,9 @@ int sc_set_next_inputs(sc_ctx* c, const sc_params* p, const double* segments, in
                        int32_t nb) {
   if (!c || !p) return fail(SC_ERR_ARG, "null argument");
   if (!c->in_step) return fail(SC_ERR_STATE, "sc_set_next_inputs belongs between sc_step_begin and sc_step_finish");
-  if (ns < 0 || ns > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", ns, kMaxSeg);
-  if (nb < 0 || nb > kMaxBody) return fail(SC_ERR_CAPACITY, "%d bodies, at most %d", nb, kMaxBody);
-  if (ns > 0 && !segments) return fail(SC_ERR_ARG, "null segment array");
-  int total = 0;
-  for (int b = 0; b < nb; ++b) total += bodies[b].n_segments;
-  if (nb > 0 && total != ns) return fail(SC_ERR_ARG, "bodies own %d segments, %d given", total, ns);
-  c->next_params = *p;
-  c->next_nseg = ns;
-  c->next_nbody = nb;
-  std::memset(c->next_seg, 0, sizeof c->next_seg);
-  std::memset(c->next_body, 0, sizeof c->next_body);
-  for (int k = 0; k < ns; ++k)
-    c->next_seg[k] = Seg{segments[4 * k], segments[4 * k + 1], segments[4 * k + 2], segments[4 * k + 3]};
-  for (int b = 0; b < nb; ++b)
-    c->next_body[b] = BodyK{bodies[b].position_x,        bodies[b].position_y, bodies[b].center_velocity_x,
-                            bodies[b].center_velocity_y, bodies[b].angular_clockwise_velocity, bodies[b].n_segments, 0};
+  const int rc = load_walls(c->next, segments, nullptr, false, ns, bodies, nb);
+  if (rc) return rc;
+  c->next.params = *p;
   c->have_next = true;
   return SC_OK;
 }
@@ -1114,8 +1116,8 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
   std::vector<double> hx(n), hy(n), hvx(n), hvy(n), hp(n, 0.0);
   std::vector<int> hid(n);
   size_t b = n * sizeof(double);
-  if ((rc = fetch(c, hx.data(), c->x[0], b)) || (rc = fetch(c, hy.data(), c->y[0], b)) ||
-      (rc = fetch(c, hvx.data(), c->vx[0], b)) || (rc = fetch(c, hvy.data(), c->vy[0], b)) ||
+  if ((rc = fetch(c, hx.data(), c->x, b)) || (rc = fetch(c, hy.data(), c->y, b)) ||
+      (rc = fetch(c, hvx.data(), c->vx, b)) || (rc = fetch(c, hvy.data(), c->vy, b)) ||
       (rc = fetch(c, hid.data(), c->id[0], n * sizeof(int))))
     return rc;
   // pressure is valid for the particles of the last finished tick, which are exactly the stored
@@ -1214,23 +1216,19 @@ static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments
 // Grows the key buffer and enqueues splat and resolve into `rgb` (device memory).
 static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb) {
   const int64_t pixels = (int64_t)v.width * v.height;
-  if (pixels > c->renderKeyAlloc) {
-    if (c->renderKeys) (void)hipFree(c->renderKeys);
-    c->renderKeys = nullptr;
-    c->renderKeyAlloc = 0;
-    HIPCHK(dalloc(&c->renderKeys, (size_t)pixels));
-    c->renderKeyAlloc = pixels;
+  if (pixels > c->renderKeys.size()) {
+    HIPCHK(c->renderKeys.grow(pixels, c->stream));
     // zero once: every resolve clears the keys it reads, which are all that the splat before it may have set
-    HIPCHK(hipMemsetAsync(c->renderKeys, 0, pixels * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->renderKeys, 0, c->renderKeys.bytes(), c->stream));
   }
   const int64_t bound = std::min<int64_t>(launch_bound(c), c->cap);
   if (bound > 0) {
     if (v.radius > kRenderWaveRadius)
       hipLaunchKernelGGL(k_render_splat<true>, dim3((unsigned)((bound * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                         v, c->counters, c->x[0], c->y[0], c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
+                         v, c->counters, c->x, c->y, c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
     else
-      hipLaunchKernelGGL(k_render_splat<false>, dim3(grid_for(bound)), dim3(kBlock), 0, c->stream, v, c->counters, c->x[0],
-                         c->y[0], c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
+      hipLaunchKernelGGL(k_render_splat<false>, dim3(grid_for(bound)), dim3(kBlock), 0, c->stream, v, c->counters, c->x,
+                         c->y, c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
   }
   hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
                      ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
@@ -1252,7 +1250,7 @@ int sc_render(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
   const int64_t bytes = 3 * (int64_t)v.width * v.height;
-  if ((rc = grow(c->renderRgb, c->renderRgbAlloc, bytes))) return rc;
+  HIPCHK(c->renderRgb.grow(bytes, c->stream));
   if ((rc = render_launch(c, v, c->renderRgb))) return rc;
   HIPCHK(hipMemcpyAsync(rgb, c->renderRgb, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1334,8 +1332,7 @@ static int jpeg_encode(sc_ctx* c, const unsigned char* rgb, int width, int heigh
   const int64_t o_len = o_rows + up((int64_t)d.rows * row_words * (int64_t)sizeof(unsigned));
   const int64_t o_off = o_len + up(2 * (int64_t)d.rows * (int64_t)sizeof(int));
   const int64_t bytes = o_off + up(((int64_t)d.rows + 1) * (int64_t)sizeof(long long));
-  int rc;
-  if ((rc = grow(c->jpegWork, c->jpegWorkAlloc, bytes))) return rc;
+  HIPCHK(c->jpegWork.grow(bytes, c->stream));
   unsigned char* w = c->jpegWork;
   short* coef = (short*)w;
   unsigned long long* masks = (unsigned long long*)(w + o_mask);
@@ -1359,7 +1356,7 @@ static int jpeg_encode(sc_ctx* c, const unsigned char* rgb, int width, int heigh
   *n_out = need;
   if (need > capacity) return fail(SC_ERR_CAPACITY, "the JPEG takes %lld bytes, the buffer holds %lld", (long long)need,
                                    (long long)capacity);
-  if ((rc = grow(c->jpegOut, c->jpegOutAlloc, total))) return rc;
+  HIPCHK(c->jpegOut.grow(total, c->stream));
   hipLaunchKernelGGL(k_jpeg_stuff, dim3((unsigned)d.rows), dim3(64), 0, c->stream, d.rows, rowbuf, row_words, row_bytes,
                      row_off, c->jpegOut);
   HIPCHK(hipGetLastError());
@@ -1397,7 +1394,7 @@ int sc_render_jpeg(sc_ctx* c, const sc_view* view, const double* segments, int32
   RenderView v;
   if ((rc = render_prepare(c, view, segments, n_segments, true, v))) return rc;
   HIPCHK(hipSetDevice(c->device));
-  if ((rc = grow(c->renderRgb, c->renderRgbAlloc, 3 * (int64_t)v.width * v.height))) return rc;
+  HIPCHK(c->renderRgb.grow(3 * (int64_t)v.width * v.height, c->stream));
   if ((rc = render_launch(c, v, c->renderRgb))) return rc;
   return jpeg_encode(c, c->renderRgb, v.width, v.height, quality, out, capacity, n_out);
 }
@@ -1582,12 +1579,12 @@ int sc_points_to_segments(int device, const double* xy, int64_t n, const double*
   if (n < 0 || ns < 0 || (n > 0 && !xy) || (ns > 0 && !segments)) return fail(SC_ERR_ARG, "bad arguments");
   if (n == 0 || ns == 0) return SC_OK;
   HIPCHK(hipSetDevice(device));
-  double *dxy = nullptr, *dseg = nullptr, *dnear = nullptr, *ddist = nullptr;
-  size_t t = (size_t)n * ns;
-  hipError_t e = dalloc(&dxy, 2 * (size_t)n);
-  if (e == hipSuccess) e = dalloc(&dseg, 4 * (size_t)ns);
-  if (e == hipSuccess) e = dalloc(&dnear, 2 * t);
-  if (e == hipSuccess) e = dalloc(&ddist, t);
+  DevBuf<double> dxy, dseg, dnear, ddist;
+  const int64_t t = n * ns;
+  hipError_t e = dxy.grow(2 * n, nullptr);
+  if (e == hipSuccess) e = dseg.grow(4 * ns, nullptr);
+  if (e == hipSuccess) e = dnear.grow(2 * t, nullptr);
+  if (e == hipSuccess) e = ddist.grow(t, nullptr);
   if (e == hipSuccess) e = hipMemcpy(dxy, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dseg, segments, 4 * ns * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
@@ -1597,10 +1594,6 @@ int sc_points_to_segments(int device, const double* xy, int64_t n, const double*
   }
   if (e == hipSuccess && nearest) e = hipMemcpy(nearest, dnear, 2 * t * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && distances) e = hipMemcpy(distances, ddist, t * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dxy);
-  (void)hipFree(dseg);
-  (void)hipFree(dnear);
-  (void)hipFree(ddist);
   if (e != hipSuccess) return fail(SC_ERR_HIP, "sc_points_to_segments: %s", hipGetErrorString(e));
   return SC_OK;
 }
@@ -1628,7 +1621,7 @@ int sc_set_slab(sc_ctx* c, int64_t col_lo, int64_t col_hi, int32_t halo, int32_t
   c->has_left = has_left ? 1 : 0;
   c->has_right = has_right ? 1 : 0;
   c->halo_ring_from = c->tick;  // new cuts: the halo counts of earlier ticks say nothing about the coming ones
-  if (!c->owned_out) HIPCHK(dalloc(&c->owned_out, 1));
+  HIPCHK(c->owned_out.grow(1, c->stream));
   return SC_OK;
 }
 
@@ -1650,22 +1643,14 @@ int sc_halo_sizes(sc_ctx* c, int64_t cap_records, int64_t* send_left, int64_t* r
   const int64_t src = c->tick - kHaloLag;
   if (src < c->halo_ring_from) return SC_OK;  // no history yet: whole buffers
   // tick `src` has finished on the device (at most a few ticks are ever queued), so its counts are published
-  int spins = 0;
-  while ((int64_t) * (volatile int*)(c->bigHintHost + 1) <= src) {
-    if (++spins > 64) {
-      const hipError_t q = hipStreamQuery(c->stream);
-      if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) return fail(SC_ERR_HIP, "stream error while waiting for halo counts: %s", hipGetErrorString(q));
-      spins = 0;
-    }
-    sched_yield();
-  }
-  if ((int64_t) * (volatile int*)(c->bigHintHost + 1) <= src) return SC_OK;  // counter behind (fresh upload): whole buffers
-  const volatile int* ring = c->bigHintHost + 4 + 4 * (src % kHaloRing);
-  *send_left = halo_message_records(ring[0], cap_records);
-  *send_right = halo_message_records(ring[1], cap_records);
-  *recv_left = halo_message_records(ring[2], cap_records);
-  *recv_right = halo_message_records(ring[3], cap_records);
+  const int rc = wait_ticks_finished(c, src + 1, "halo counts");
+  if (rc) return rc;
+  if (progress_read(c, kProgressTicks) <= src) return SC_OK;  // counter behind (fresh upload): whole buffers
+  const int ring = kProgressHaloRing + 4 * (int)(src % kHaloRing);
+  *send_left = halo_message_records(progress_read(c, ring), cap_records);
+  *send_right = halo_message_records(progress_read(c, ring + 1), cap_records);
+  *recv_left = halo_message_records(progress_read(c, ring + 2), cap_records);
+  *recv_right = halo_message_records(progress_read(c, ring + 3), cap_records);
   return SC_OK;
 }
 
@@ -1674,17 +1659,11 @@ int sc_column_histogram(sc_ctx* c, int64_t col0, int32_t ncols, int64_t* hist) {
   if (c->in_step) return fail(SC_ERR_STATE, "sc_column_histogram inside a tick");
   if (!c->have_params && !c->custom_grid) return fail(SC_ERR_STATE, "sc_set_params has not been called");
   HIPCHK(hipSetDevice(c->device));
-  if (ncols > c->colHistAlloc) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->colHist) (void)hipFree(c->colHist);
-    c->colHist = nullptr;
-    HIPCHK(dalloc(&c->colHist, (size_t)ncols + 256));
-    c->colHistAlloc = ncols + 256;
-  }
+  if (ncols > c->colHist.size()) HIPCHK(c->colHist.grow(ncols + 256, c->stream));
   HIPCHK(hipMemsetAsync(c->colHist, 0, ncols * sizeof(int), c->stream));
-  const double d = c->custom_grid ? c->custom_d : c->params.particle_radius * 2;
-  hipLaunchKernelGGL(k_column_histogram, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->counters, c->x[0],
-                     c->slab_axis ? c->y[0] : c->x[0], d, (long long)col0, (int)ncols, c->colHist);
+  const double d = c->custom_grid ? c->custom_d : c->now.params.particle_radius * 2;
+  hipLaunchKernelGGL(k_column_histogram, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->counters, c->x,
+                     c->slab_axis ? c->y : c->x, d, (long long)col0, (int)ncols, c->colHist);
   std::vector<int> h(ncols);
   HIPCHK(hipMemcpyAsync(h.data(), c->colHist, ncols * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1716,8 +1695,8 @@ int sc_halo_pack(sc_ctx* c, double* dev_left, double* dev_right, int64_t cap_rec
   c->haloR = dev_right;
   c->haloCap = (int)cap_records;
   Bracket br(c, K_HALO_PACK);
-  hipLaunchKernelGGL(k_halo_pack, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->w, c->counters, c->x[0],
-                     c->y[0], c->vx[0], c->vy[0], c->id[0], dev_left, dev_right, (int)cap_records, (int)c->cap);
+  hipLaunchKernelGGL(k_halo_pack, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->w, c->counters, c->x,
+                     c->y, c->vx, c->vy, c->id[0], dev_left, dev_right, (int)cap_records, (int)c->cap);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -1731,16 +1710,16 @@ int sc_halo_unpack(sc_ctx* c, const double* from_left, int64_t left_records, con
   Bracket br(c, K_HALO_UNPACK);
   const int capL = from_left ? (int)left_records : 0, capR = from_right ? (int)right_records : 0;
   const dim3 grid(grid_for(capL + capR)), block(kBlock);
-  int* ring = c->bigHintDev + 4 + 4 * (int)(c->tick % kHaloRing);
+  int* ring = c->progress_dev + kProgressHaloRing + 4 * (int)(c->tick % kHaloRing);
   if (c->prebinned) {  // the stored particles went through K1 of the coming tick in pass B: same for the arrivals
     hipLaunchKernelGGL(k_halo_unpack<true>, grid, block, 0, c->stream, from_left, from_right, capL, capR,
-                       c->counters, c->x[0], c->y[0], c->vx[0], c->vy[0], c->id[0], (int)c->cap, c->haloL, c->haloR,
+                       c->counters, c->x, c->y, c->vx, c->vy, c->id[0], (int)c->cap, c->haloL, c->haloR,
                        c->promised, c->cellS, c->wslotS, c->cellCount, c->wrec[c->tick & 1], ring);
   } else {
     WallInputs none;
     std::memset(&none, 0, sizeof none);
     hipLaunchKernelGGL(k_halo_unpack<false>, grid, block, 0, c->stream, from_left, from_right, capL, capR,
-                       c->counters, c->x[0], c->y[0], c->vx[0], c->vy[0], c->id[0], (int)c->cap, c->haloL, c->haloR, none,
+                       c->counters, c->x, c->y, c->vx, c->vy, c->id[0], (int)c->cap, c->haloL, c->haloR, none,
                        c->cellS, c->wslotS, c->cellCount, c->wrec[c->tick & 1], ring);
   }
   HIPCHK(hipGetLastError());
@@ -1902,9 +1881,9 @@ int sc_owned_count(sc_ctx* c, int64_t* n) {
   if (c->in_step) return fail(SC_ERR_STATE, "sc_owned_count inside a tick");
   int rc = c->slab ? make_world(c) : SC_OK;
   if (rc) return rc;
-  if (!c->owned_out) HIPCHK(dalloc(&c->owned_out, 1));
+  HIPCHK(c->owned_out.grow(1, c->stream));
   HIPCHK(hipMemsetAsync(c->owned_out, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_owned_count, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->counters, c->x[0],
+  hipLaunchKernelGGL(k_owned_count, dim3(grid_for(launch_bound(c))), dim3(kBlock), 0, c->stream, c->counters, c->x,
                      c->owned_out);
   int h = 0;
   HIPCHK(hipMemcpyAsync(&h, c->owned_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1920,7 +1899,7 @@ int sc_enable_force_monitor(sc_ctx* c, int on) {
   if (c->in_step) return fail(SC_ERR_STATE, "the force monitor cannot change inside a tick");
   if (c->prebinned) return fail(SC_ERR_STATE, "the force monitor cannot change after sc_set_next_inputs promised the next tick");
   HIPCHK(hipSetDevice(c->device));
-  if (on && !c->monitor) HIPCHK(dalloc(&c->monitor, (size_t)kMonPhases + 1));
+  if (on) HIPCHK(c->monitor.grow(kMonPhases + 1, c->stream));
   if (on) HIPCHK(hipMemsetAsync(c->monitor, 0, (kMonPhases + 1) * sizeof(double), c->stream));
   c->monitor_on = on != 0;
   return SC_OK;
@@ -1960,32 +1939,20 @@ int sc_checkpoint_begin(sc_ctx* c) {
   }
   if (!c->snap_ready) HIPCHK(hipEventCreateWithFlags(&c->snap_ready, hipEventDisableTiming));
   if (!c->snap_done) HIPCHK(hipEventCreateWithFlags(&c->snap_done, hipEventDisableTiming));
-  if (!c->snap_counters_h) HIPCHK(hipHostMalloc((void**)&c->snap_counters_h, C_COUNT * sizeof(int), hipHostMallocDefault));
-  if (!c->snap_rng_h) HIPCHK(hipHostMalloc((void**)&c->snap_rng_h, sizeof(RngState), hipHostMallocDefault));
-  if (!c->snap_rng_d) HIPCHK(dalloc(&c->snap_rng_d, 1));
+  HIPCHK(c->snap_counters_h.grow(C_COUNT, c->side_stream));
+  HIPCHK(c->snap_rng_h.grow(1, c->side_stream));
+  HIPCHK(c->snap_rng_d.grow(1, c->side_stream));
   const int64_t n = launch_bound(c);  // a host-side bound of the stored count; the exact count travels with the copy
-  if (n > c->snapAlloc) {
-    HIPCHK(hipStreamSynchronize(c->side_stream));
-    for (int k = 0; k < 4; ++k) {
-      if (c->snap_d[k]) (void)hipFree(c->snap_d[k]);
-      if (c->snap_h[k]) (void)hipHostFree(c->snap_h[k]);
-      c->snap_d[k] = nullptr;
-      c->snap_h[k] = nullptr;
-    }
-    if (c->snap_id_d) (void)hipFree(c->snap_id_d);
-    if (c->snap_id_h) (void)hipHostFree(c->snap_id_h);
-    c->snap_id_d = nullptr;
-    c->snap_id_h = nullptr;
+  if (n > c->snap_id_h.size()) {  // (snap_id_h grows last: once it has grown, so have the others)
     const int64_t m = std::min<int64_t>(c->cap, n + n / 2 + 1024);
     for (int k = 0; k < 4; ++k) {
-      HIPCHK(dalloc(&c->snap_d[k], (size_t)m));
-      HIPCHK(hipHostMalloc((void**)&c->snap_h[k], std::max<size_t>(m, 1) * sizeof(double), hipHostMallocDefault));
+      HIPCHK(c->snap_d[k].grow(m, c->side_stream));
+      HIPCHK(c->snap_h[k].grow(m, c->side_stream));
     }
-    HIPCHK(dalloc(&c->snap_id_d, (size_t)m));
-    HIPCHK(hipHostMalloc((void**)&c->snap_id_h, std::max<size_t>(m, 1) * sizeof(int), hipHostMallocDefault));
-    c->snapAlloc = m;
+    HIPCHK(c->snap_id_d.grow(m, c->side_stream));
+    HIPCHK(c->snap_id_h.grow(m, c->side_stream));
   }
-  const double* src[4] = {c->x[0], c->y[0], c->vx[0], c->vy[0]};
+  const double* src[4] = {c->x, c->y, c->vx, c->vy};
   // on the context's stream: after the last tick, before the next one changes the storage arrays
   for (int k = 0; k < 4 && n > 0; ++k)
     HIPCHK(hipMemcpyAsync(c->snap_d[k], src[k], n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -2024,8 +1991,9 @@ int sc_checkpoint_finish(sc_ctx* c, double* xy, double* vxy, int64_t* ids, int64
   *n_out = n;
   if (tick) *tick = c->snap_tick;
   if (next_id) *next_id = c->snap_counters_h[C_NEXT_ID];
-  if (rng_pos) *rng_pos = c->snap_has_rng ? c->snap_rng_h->pos : -1;
-  if (rng_key && c->snap_has_rng) std::memcpy(rng_key, c->snap_rng_h->mt, sizeof c->snap_rng_h->mt);
+  const RngState& rs = *c->snap_rng_h;
+  if (rng_pos) *rng_pos = c->snap_has_rng ? rs.pos : -1;
+  if (rng_key && c->snap_has_rng) std::memcpy(rng_key, rs.mt, sizeof rs.mt);
   if (n > room) return fail(SC_ERR_CAPACITY, "host arrays hold %lld, the checkpoint has %lld particles", (long long)room, (long long)n);
   for (int64_t k = 0; k < n; ++k) {
     const int s = order[k];
@@ -2047,14 +2015,14 @@ int sc_restore_counters(sc_ctx* c, int64_t tick, int64_t next_id) {
   if (c->in_step) return fail(SC_ERR_STATE, "sc_restore_counters inside a tick");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->prebinned) {  // a promised tick is abandoned: forget its bucket counts
-    HIPCHK(hipMemsetAsync(c->cellCount, 0, c->cellAlloc * sizeof(int), c->stream));
-    c->prebinned = false;
+  if (c->prebinned) {
+    const int rc = abandon_promise(c);
+    if (rc) return rc;
   }
   c->tick = tick;
   c->halo_ring_from = tick;
   c->live_hint_from = tick;
-  c->bigHintHost[1] = (int)tick;  // "ticks finished": nothing of the new numbering is queued
+  c->progress[kProgressTicks] = (int)tick;  // nothing of the new numbering is queued
   c->next_id = std::max<int64_t>(c->next_id, next_id);
   const int nid = (int)c->next_id;
   HIPCHK(hipMemcpyAsync(c->counters + C_NEXT_ID, &nid, sizeof nid, hipMemcpyHostToDevice, c->stream));
@@ -2068,7 +2036,7 @@ int sc_rng_set_state(sc_ctx* c, const uint32_t* key, int32_t pos) {
   if (!c || !key || pos < 0 || pos > kMtN) return fail(SC_ERR_ARG, "an MT19937 state is 624 words and a position in [0, 624]");
   if (c->in_step) return fail(SC_ERR_STATE, "the generator cannot change inside a tick");
   HIPCHK(hipSetDevice(c->device));
-  if (!c->rng) HIPCHK(dalloc(&c->rng, 1));
+  HIPCHK(c->rng.grow(1, c->stream));
   RngState h;
   std::memcpy(h.mt, key, sizeof h.mt);
   h.pos = pos;
@@ -2139,10 +2107,10 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   // host-side bounds of the stored count and of the ids: at most `bound` particles per source; the live count a
   // recent tick published (progress block) keeps the bound from drifting away without any synchronisation
   // (the device writes the tick number last: the three words belong together when it reads the same before and after)
-  int64_t done = *(volatile int*)(c->bigHintHost + 1);
-  const int64_t live = *(volatile int*)(c->bigHintHost + 2), published_ids = *(volatile int*)(c->bigHintHost + 3);
+  int64_t done = progress_read(c, kProgressTicks);
+  const int64_t live = progress_read(c, kProgressLive), published_ids = progress_read(c, kProgressNextId);
   std::atomic_thread_fence(std::memory_order_acquire);
-  if (*(volatile int*)(c->bigHintHost + 1) != done) done = -1;  // a tick finished in between: no hint this time
+  if (progress_read(c, kProgressTicks) != done) done = -1;  // a tick finished in between: no hint this time
   int64_t upper = c->upper + most;
   if (done > c->live_hint_from && c->tick >= done && c->tick - done <= 8)
     upper = std::min(upper, live + (c->tick - done + 1) * most);
@@ -2165,8 +2133,8 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   HIPCHK(hipSetDevice(c->device));
   for (const SourcesK& g : groups) {
     Bracket br(c, K_APPEND);
-    hipLaunchKernelGGL(k_rng_emit, dim3(1), dim3(64), 0, c->stream, g, (long long)max_particles, c->rng, c->counters, c->x[0],
-                       c->y[0], c->vx[0], c->vy[0], c->id[0], (int)c->cap);
+    hipLaunchKernelGGL(k_rng_emit, dim3(1), dim3(64), 0, c->stream, g, (long long)max_particles, c->rng, c->counters, c->x,
+                       c->y, c->vx, c->vy, c->id[0], (int)c->cap);
   }
   HIPCHK(hipGetLastError());
   c->upper = upper;

@@ -772,6 +772,18 @@ __global__ void __launch_bounds__(kBlock) k_scatter(const int* __restrict__ coun
 }
 
 // ------------------------------------------------------------------------------------------
+// The progress block: ints in host-mapped memory that kernels write and the host reads without synchronising.
+// ------------------------------------------------------------------------------------------
+constexpr int kHaloRing = 8;            // ticks of halo counts the ring holds
+constexpr int kProgressBigBuckets = 0;  // big buckets seen by the last finished scan (k_reorder)
+constexpr int kProgressTicks = 1;       // ticks finished (pass B; written last, behind a release)
+constexpr int kProgressLive = 2;        // live particles of that tick (pass B)
+constexpr int kProgressNextId = 3;      // the device's id counter after that tick (pass B)
+constexpr int kProgressHaloRing = 4;    // + 4 (tick % kHaloRing): halo records of that tick -- sent left / right,
+                                        // received left / right (k_halo_unpack)
+constexpr int kProgressInts = kProgressHaloRing + 4 * kHaloRing;
+
+// ------------------------------------------------------------------------------------------
 // K4  reorder: final slot = bucket start + rank of (x, id) inside the bucket, which makes the
 // whole array sorted by (row, x, id) = np.lexsort((x, y_floored)) with its stable tie-break
 // (collision_detector.py:127).  Moves the particle's state to the sorted arrays.  Keys and ids
@@ -795,11 +807,11 @@ __global__ void __launch_bounds__(kReorderBlock)
               const double* __restrict__ vyS, XY* __restrict__ xyT, XY* __restrict__ vvT, int* __restrict__ idT,
               int* __restrict__ cellT,
               int* __restrict__ wslotT, const int* __restrict__ sortedStamp, int stamp, int ncols,
-              int* __restrict__ tileBounds, int live_hint, volatile int* __restrict__ bigHint) {
+              int* __restrict__ tileBounds, int live_hint, volatile int* __restrict__ progress) {
   SC_TIMELINE_KERNEL(4);
   // a hint for the host, in host-mapped memory: were there big buckets?  It is read without any synchronisation when a
   // later tick is enqueued and only decides whether k_sort_big and the grouping kernel variants are launched
-  if (blockIdx.x == 0 && threadIdx.x == 0) bigHint[0] = counters[C_NBIG];
+  if (blockIdx.x == 0 && threadIdx.x == 0) progress[kProgressBigBuckets] = counters[C_NBIG];
   __shared__ SortKey ck[kRankChunk];
   __shared__ int wcell[kReorderBlock + 2 * kRankWindow];
   __shared__ int pick;
@@ -1179,9 +1191,6 @@ __global__ void __launch_bounds__(kBlock)
 // sc_halo_sizes).  A header that announces more means records were cut off: F_HALO_OVERFLOW.  `ring`: the four
 // counts of this tick (sent left, sent right, received from the left, from the right) are published in
 // host-mapped memory, slot tick % kHaloRing, for the message sizes of a later tick.
-constexpr int kHaloRing = 8;
-constexpr int kProgressInts = 4 + 4 * kHaloRing;  // [big buckets, ticks finished, live count, -] + the ring
-
 template <bool FUSED>
 __global__ void __launch_bounds__(kBlock)
     k_halo_unpack(const double* __restrict__ bufL, const double* __restrict__ bufR, int capL, int capR,

@@ -1220,13 +1220,13 @@ __global__ void __launch_bounds__(kTileW)
     counters[C_NBIG] = 0;
     counters[C_NTASKS] = 0;
     SC_TIMELINE_EPOCH(w.tick + 1);
-    // host-mapped: the host keeps at most a few ticks of launches queued (progress[1]), sizes heuristics by a recent live
-    // count ([2]) and keeps its bound of the ids handed out near the device's count ([3]: sc_emit_particles).  The tick
-    // number goes LAST, behind a release: a reader that sees the same tick before and after reading [2] and [3] has
-    // that tick's values
-    progress[2] = n;
-    progress[3] = counters[C_NEXT_ID];
-    __hip_atomic_store(const_cast<int*>(&progress[1]), w.tick + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // host-mapped: the host keeps at most a few ticks of launches queued (ticks finished), sizes heuristics by a recent
+    // live count and keeps its bound of the ids handed out near the device's count (sc_emit_particles).  The tick
+    // number goes LAST, behind a release: a reader that sees the same tick before and after reading the live count and
+    // the next id has that tick's values
+    progress[kProgressLive] = n;
+    progress[kProgressNextId] = counters[C_NEXT_ID];
+    __hip_atomic_store(const_cast<int*>(&progress[kProgressTicks]), w.tick + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   if (BANDED && part == 3 && n == 0 && blockIdx.x == 0 && t == 0)  // nothing at all: nobody else would publish the epoch
     __hip_atomic_store(&counters[C_BAND_FLAG], epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
