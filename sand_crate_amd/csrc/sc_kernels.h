@@ -326,27 +326,11 @@ __global__ void __launch_bounds__(kBlock) k_scan_fix(int* __restrict__ out, int 
 // first instruction (tick_abandoned): the bucket starts are not to be trusted, so the tick is SKIPPED, the storage
 // arrays keep the state the tick started from, and the error reaches the caller with that state intact.
 constexpr int kSortThreshold = 96;  // buckets above this many particles are listed for k_sort_big
-#ifndef SC_SORT_BLOCK
-#define SC_SORT_BLOCK 512
-#define SC_SORT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))
-#endif
-constexpr int kSortBlock = SC_SORT_BLOCK;
-#ifndef SC_SORT_WAVES_ATTR
-#define SC_SORT_WAVES_ATTR
-#endif  // threads of a sorting task
-#ifndef SC_SORT_CHUNK
-#define SC_SORT_CHUNK 1024
-#endif
-constexpr int kSortChunk = SC_SORT_CHUNK;  // slots per sorting task (12 B of LDS per slot for the keys)
-#ifndef SC_SORT_GRID_PER_CU
-#define SC_SORT_GRID_PER_CU 4
-#endif
-constexpr int kSortGridPerCu = SC_SORT_GRID_PER_CU;  // k_sort_big's workgroups per CU (each takes every grid-th task)
-constexpr int kSortBins = 256;         // bins of a chunk (by sampled splitters)
-#ifndef SC_MAX_SORT_TASKS
-#define SC_MAX_SORT_TASKS 16384
-#endif
-constexpr int kMaxSortTasks = SC_MAX_SORT_TASKS;   // room in k_sort_big's task list (a bucket that does not fit is ranked in K4 by counting)
+constexpr int kSortBlock = 512;       // threads of a sorting task
+constexpr int kSortChunk = 1024;      // slots per sorting task (12 B of LDS per slot for the keys)
+constexpr int kSortGridPerCu = 4;     // k_sort_big's workgroups per CU (each takes every grid-th task)
+constexpr int kSortBins = 256;        // bins of a chunk (by sampled splitters)
+constexpr int kMaxSortTasks = 16384;  // room in k_sort_big's task list (a bucket that does not fit is ranked in K4 by counting)
 static_assert(kSortChunk <= 2048, "a task packs its chunk's length - 1 into 11 bits");
 
 // A bucket slot's sort key: the particle's x, its id (the tie-break) and its storage index, one 16-byte record -- written by
@@ -502,7 +486,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_cells(const int* __restrict__ i
 
 __device__ __forceinline__ bool key_less(double xa, int ia, double xb, int ib) { return xa < xb || (xa == xb && ia < ib); }
 
-__global__ void __launch_bounds__(kSortBlock) SC_SORT_WAVES_ATTR
+__global__ void __launch_bounds__(kSortBlock) __attribute__((amdgpu_waves_per_eu(8, 8)))
     k_sort_big(const int* __restrict__ counters, const int2* __restrict__ sortTasks,
                Buckets bk, SortKey* __restrict__ keys, int* __restrict__ sortedStamp, int stamp) {
   SC_TIMELINE_KERNEL(5);
@@ -679,36 +663,31 @@ __global__ void __launch_bounds__(kSortBlock) SC_SORT_WAVES_ATTR
 // The bucket slot receives the sort key and the particle's storage index (one SortKey record) and the packed cell,
 // so that K4 ranks over CONTIGUOUS keys instead of chasing storage index -> x.
 // ------------------------------------------------------------------------------------------
-// XCD-aware block -> chunk mapping (same idea as sc_tiled.h: tile_of_block): workgroups are dealt round-robin over
-// the 8 XCDs, so giving every XCD one contiguous run of chunks keeps neighboring chunks -- whose gathers and
-// scattered stores fall into the same cache lines -- inside one L2.  Placement is a speed matter only.
-// `live_hint`: the particles expected to be live (World::live_hint): only the blocks that hold them are dealt into
-// runs, the rest of a grid sized by capacity keeps its own index.
-__device__ __forceinline__ int chunk_of_block(int live_hint) {
-#ifdef SC_NO_XCD_CHUNKS
-  return blockIdx.x;
-#else
-  const int nb = min((int)gridDim.x, (int)((live_hint + blockDim.x - 1) / blockDim.x)), b = blockIdx.x;
+// XCD-aware block placement.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share an L2), while
+// neighboring chunks and tiles of the sorted order share cache lines (a chunk's gathers and scattered stores; a tile's
+// overlaps with its neighbors in the same rows and with the tiles one grid row away).  Giving every XCD one contiguous run
+// of them keeps those overlaps inside one L2 instead of fetching them once per XCD (measured with FETCH_SIZE: profiles/).
+// Placement is a speed matter only; nothing depends on it.
+// Block b of the nb blocks expected to hold particles -> its place in its XCD's run.  A grid sized by capacity (a slab's)
+// is dealt only up to nb: dealing ALL of it into runs would give the last XCDs nothing but empty blocks (measured on a
+// slab with 30 % slack: pass A +15 %, pass B +13 %); blocks from nb on keep their own index.
+// ends_first: the run is walked from both ends towards the middle.  Blocks start in index order and a kernel ends with its
+// slowest block: in a pile-up those are the blocks beside the piles along the floor and the ceiling -- the first of the
+// first XCD's run and the last of the last one's, which in plain order start when everything else is nearly done.  Two
+// contiguous fronts per XCD keep the overlaps in its L2 as before.
+__device__ __forceinline__ int xcd_deal(int b, int nb, bool ends_first) {
   if (b >= nb) return b;
-  const int q = nb >> 3, r = nb & 7, xcd = b & 7;
-  return xcd * q + min(xcd, r) + (b >> 3);
-#endif
+  const int q = nb >> 3, r = nb & 7, xcd = b & 7, l = b >> 3;
+  const int start = xcd * q + min(xcd, r);
+  if (!ends_first) return start + l;
+  const int len = q + (xcd < r ? 1 : 0);
+  return (l & 1) ? start + len - 1 - (l >> 1) : start + (l >> 1);
 }
 
-// The same runs walked from both ends towards the middle (like the search's tiles, sc_tiled.h): blocks start in index
-// order and a kernel ends with its slowest block -- in a pile-up the blocks of the piles along floor and ceiling, the first
-// of the first XCD's run and the last of the last one's.  (The scatter; K4 gains nothing from it: its slowest waves are
-// the ones of the first XCD's first blocks either way.)
-__device__ __forceinline__ int chunk_of_block_ends_first(int live_hint) {
-#ifdef SC_NO_ENDS_FIRST
-  return chunk_of_block(live_hint);
-#else
-  const int nb = min((int)gridDim.x, (int)((live_hint + blockDim.x - 1) / blockDim.x)), b = blockIdx.x;
-  if (b >= nb) return b;
-  const int q = nb >> 3, r = nb & 7, xcd = b & 7;
-  const int start = xcd * q + min(xcd, r), len = q + (xcd < r ? 1 : 0), l = b >> 3;
-  return (l & 1) ? start + len - 1 - (l >> 1) : start + (l >> 1);
-#endif
+// `live_hint`: the particles expected to be live (World::live_hint).  (Ends first: the scatter; K4 gains nothing from it,
+// its slowest waves are the ones of the first XCD's first blocks either way.)
+__device__ __forceinline__ int chunk_of_block(int live_hint, bool ends_first = false) {
+  return xcd_deal(blockIdx.x, min((int)gridDim.x, (int)((live_hint + blockDim.x - 1) / blockDim.x)), ends_first);
 }
 
 template <bool GROUP>
@@ -718,7 +697,7 @@ __global__ void __launch_bounds__(kBlock) k_scatter(const int* __restrict__ coun
                                                     SortKey* __restrict__ keys, int* __restrict__ keyCell, int cap,
                                                     int live_hint) {
   SC_TIMELINE_KERNEL(3);
-  int i = chunk_of_block_ends_first(live_hint) * blockDim.x + threadIdx.x;  // (pile-up regime: 33.6 -> 30.0 us; uniform: the same)
+  int i = chunk_of_block(live_hint, true) * blockDim.x + threadIdx.x;  // (pile-up regime: 33.6 -> 30.0 us; uniform: the same)
   const int ic = min(i, cap - 1);  // loads that do not depend on the stored count go out first
   int c = cellS[ic];
   const int cpacked = c;
@@ -796,10 +775,7 @@ constexpr int kRankChunk = 256;   // keys streamed through LDS per step (3 KB pe
 constexpr int kReorderBlock = 64; // one wave per workgroup: a big bucket is shared by 4x more CUs
 
 constexpr int kRankWindow = 12;   // slots either side of a particle in which a small bucket's ends are looked for
-#ifndef SC_RANK_SIDE
-#define SC_RANK_SIDE 4
-#endif
-constexpr int kRankSide = SC_RANK_SIDE;  // searches of a sorted bucket's other chunks that advance together (2: the same; 8: registers, 53 us)
+constexpr int kRankSide = 4;  // searches of a sorted bucket's other chunks that advance together (2: the same; 8: registers, 53 us)
 
 __global__ void __launch_bounds__(kReorderBlock)
     k_reorder(const int* __restrict__ counters, const SortKey* __restrict__ keys, const int* __restrict__ keyCell, const int* __restrict__ cellS, Buckets bk,
@@ -986,17 +962,17 @@ __global__ void __launch_bounds__(kReorderBlock)
   SC_STAMP(5, 5);
   if (!live) return;
   const int dst = b + rank;
-  // The candidates of a block of SC_TILE_W consecutive sorted particles lie in three index ranges (sc_tiled.h);
+  // The candidates of a block of kTileW consecutive sorted particles lie in three index ranges (sc_tiled.h);
   // the block's first and last particle know them from their cells.  Published here, one kernel ahead of the
   // tiled passes, so that those can stage their tile without waiting for bucket lookups of their own.
-  if (dst % SC_TILE_W == 0) {
-    int* tb = tileBounds + 6 * (dst / SC_TILE_W);
+  if (dst % kTileW == 0) {
+    int* tb = tileBounds + 6 * (dst / kTileW);
     tb[0] = bk(c - 1);
     tb[2] = bk(c + ncols - 1);
     tb[4] = bk(c - ncols - 1);
   }
-  if (dst % SC_TILE_W == SC_TILE_W - 1 || dst == nlive - 1) {
-    int* tb = tileBounds + 6 * (dst / SC_TILE_W);
+  if (dst % kTileW == kTileW - 1 || dst == nlive - 1) {
+    int* tb = tileBounds + 6 * (dst / kTileW);
     tb[1] = bk(c + 2);
     tb[3] = bk(c + ncols + 2);
     tb[5] = bk(c - ncols + 2);

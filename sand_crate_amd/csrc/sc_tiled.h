@@ -31,40 +31,13 @@
 
 namespace sc {
 
-// Tile geometry (measured, profiles/README.md): 256 particles per workgroup beat 128 by 2-3 % (less halo per
-// particle: 3 x (256 + 12) entries for 256 particles) and 64 lose 3-6 %.
-#ifndef SC_SCAN_BATCH
-#define SC_SCAN_BATCH 4
-#endif
-#ifndef SC_COOP
-#define SC_COOP 2
-#endif
-#ifndef SC_LEAD_IN
-#define SC_LEAD_IN 1
-#endif
-#ifndef SC_COOP_FAST
-#define SC_COOP_FAST 1
-#endif
-#ifndef SC_B_LEAN_LOOP
-#define SC_B_LEAN_LOOP 1
-#endif
-#ifndef SC_SERIAL_ONCE
-#define SC_SERIAL_ONCE 1
-#endif
-#ifndef SC_CAP_A
-#define SC_CAP_A 1024
-#define SC_CAP_AW 1536
-#define SC_CAP_B 960
-#endif
-constexpr int kTileW = SC_TILE_W;      // particles (= threads) per workgroup
 // pass A tile, (x, y) records: 16 KiB when many workgroups share a CU (more waves in flight), 24 KiB when the
 // whole grid is resident anyway (fewer tiles fall out of LDS); the launcher picks (measured: profiles/)
-constexpr int kTileCapA = SC_CAP_A, kTileCapAWide = SC_CAP_AW;
-constexpr int kTileCapB = SC_CAP_B;   // pass B tile: (x, y), (sx, sy), P of the three ranges: 40 B per entry, 37.5 KiB
-#ifndef SC_DENSE_TILE
-#define SC_DENSE_TILE (SC_TILE_W * 43 / 10)
-#endif
-constexpr int kDenseTile = SC_DENSE_TILE;  // 1100 entries for 256 particles (the usual tile has ~800)
+constexpr int kTileCapA = 1024, kTileCapAWide = 1536;
+constexpr int kTileCapB = 960;   // pass B tile: (x, y), (sx, sy), P of the three ranges: 40 B per entry, 37.5 KiB
+constexpr int kDenseTile = kTileW * 43 / 10;  // 1100 entries for 256 particles (the usual tile has ~800)
+// candidates of a scan examined per iteration, their LDS reads issued together (pass_a_body)
+constexpr int kScanBatch = 4;
 constexpr int kSlotMax = 65535;    // lists are staged as u16 tile slots in pass A
 constexpr int kRowSlotMax = 4095;  // ... and stored as 12-bit slots of the tile pass B will stage
 
@@ -105,10 +78,10 @@ __device__ __forceinline__ NbrRow row_pack(const unsigned int (&lw)[kMaxNbr / 2]
   return r;
 }
 
-// A thread's list while it is being built, in LDS: kMaxNbr entries of 16 bits and SC_SCAN_BATCH spare ones (the writes of a
+// A thread's list while it is being built, in LDS: kMaxNbr entries of 16 bits and kScanBatch spare ones (the writes of a
 // full list, below), thread-major -- the row is then copied to the table as it is.  The stride is an odd number of
 // 32-bit words, so that the rows of consecutive lanes start in different banks.
-constexpr int kListWords = ((kMaxNbr + SC_SCAN_BATCH) / 2) | 1;
+constexpr int kListWords = ((kMaxNbr + kScanBatch) / 2) | 1;
 constexpr int kListStride = 4 * kListWords;
 struct Lists {
   char* base;
@@ -146,32 +119,17 @@ __device__ __forceinline__ double rsqrt_nr(double s) {
 }
 
 
-// XCD-aware block -> tile mapping.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and
-// b + 8 share an L2), while a tile overlaps its neighbors in the sorted order (same rows) and the
-// tiles one grid row away (next / previous rows).  Giving every XCD one contiguous run of tiles
-// keeps those overlaps inside one L2 instead of fetching them once per XCD (measured with
-// FETCH_SIZE: profiles/).  Placement is a speed matter only; nothing depends on it.
-// `tiles`: the blocks expected to hold particles.  A slab's grid is sized by its capacity; dealing ALL of it into
-// runs would give the last XCDs nothing but empty blocks (measured on a slab with 30 % slack: pass A +15 %, pass B
-// +13 %).  Blocks beyond `tiles` keep their own index.
-__device__ __forceinline__ int tile_of_block(int tiles) {
-  const int nb = min((int)gridDim.x, tiles), b = blockIdx.x;
-  if (b >= nb) return b;
-  const int q = nb >> 3, r = nb & 7, xcd = b & 7;
-  return xcd * q + min(xcd, r) + (b >> 3);
+// XCD-aware block -> tile mapping (sc_kernels.h: xcd_deal); `tiles`: the blocks expected to hold particles.  The
+// search walks its runs ends first, the force pass in plain order.
+__device__ __forceinline__ int tile_of_block(int tiles, bool ends_first = false) {
+  return xcd_deal(blockIdx.x, min((int)gridDim.x, tiles), ends_first);
 }
 __device__ __forceinline__ int tiles_expected(const World& w) { return (w.live_hint + kTileW - 1) / kTileW; }
 
-// The same runs, walked from both ends towards the middle (the search).  Blocks start in index order and the
-// kernel ends with its slowest block: in a pile-up those are the blocks beside the piles along the floor and the
-// ceiling -- the first tiles of the first XCD's run and the last tiles of the last one's, which in plain order start
-// when everything else is nearly done.  Two contiguous fronts per XCD keep the overlaps in its L2 as before.
-__device__ __forceinline__ int tile_of_block_ends_first(int tiles) {
-  const int nb = min((int)gridDim.x, tiles), b = blockIdx.x;
-  if (b >= nb) return b;
-  const int q = nb >> 3, r = nb & 7, xcd = b & 7;
-  const int start = xcd * q + min(xcd, r), len = q + (xcd < r ? 1 : 0), l = b >> 3;
-  return (l & 1) ? start + len - 1 - (l >> 1) : start + (l >> 1);
+// The tile of a block from the six bounds published for it (by k_reorder for pass A, by pass A for pass B)
+__device__ __forceinline__ Tile published_tile(const int* tb) {
+  const int tb0 = tb[0], tb1 = tb[1], tb2 = tb[2], tb3 = tb[3], tb4 = tb[4], tb5 = tb[5];
+  return Tile{tb0, tb1 - tb0, tb2, tb3 - tb2, tb4, tb5 - tb4};
 }
 
 // Phases 3-5 of pass A for one particle.  LDS: where the tile is (compile time, see the header).
@@ -204,11 +162,20 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
   XY pi = {0.0, 0.0};
   if (live) pi = load_xy(self);
   if (ENUM && !diag::kNoSearch) {
+    const double xi = pi.x, yi = pi.y;
+    // The four scans in the reference's order and their window conditions: window(xj, xi) says 0 = stop the scan,
+    // 1 = outside the window, 2 = inside.
+    // same strip, after i: x_j <= x_i + d                                  (:106-109)
+    const auto win_after = [&](double xj, double xq) { return xj > xq + w.d ? 0 : 2; };
+    // next strip: x_i - d <= x_j <= x_i + d                                (:112-119)
+    const auto win_next = [&](double xj, double xq) { return xj > xq + w.d ? 0 : (xj >= xq - w.d ? 2 : 1); };
+    // reverse edges (:85-88): i is a forward candidate of j, same strip
+    const auto win_before = [&](double xj, double xq) { return !(xq <= xj + w.d) ? 0 : 2; };
+    // reverse edges from the previous strip
+    const auto win_prev = [&](double xj, double xq) { return !(xq <= xj + w.d) ? 0 : (xq >= xj - w.d ? 2 : 1); };
     if (slots_fit && (LDS ? live : true)) {
-      const double xi = pi.x, yi = pi.y;
       // One scan: `count` candidates from tile slot `first`, walking by `step`, examined one by one in
-      // order with the reference's window conditions: window(xj, xi) says 0 = stop the scan, 1 =
-      // outside the window, 2 = inside.
+      // order with the window conditions.
       //   LDS tile: straight from the tile.
       //   Tile too large for LDS (a block in or next to a pile-up; all threads of the block take
       //   part): the workgroup moves a window of CAP slots over the tile, placed on a grid of
@@ -228,54 +195,56 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
       char* const lbase = list.base;
       const unsigned lo0 = t * (unsigned)kListStride, lend = kMaxNbr * kRow + lo0;
       unsigned lo = lo0;
+      // One batched stretch of a scan: `count` candidates from tile slot `first` by `step`, read from txy[slot - ws] (ws: the
+      // first slot txy holds -- 0 for an LDS tile, the window's start otherwise), kScanBatch per iteration: their LDS reads
+      // are issued together (one latency per batch instead of one per candidate) and their tests are independent
+      // instruction streams.  The loop stops on a conservative test of dx (never before the reference's window ends: a
+      // candidate beyond d (1 + 2^-20) in x can neither be in the window nor within d); a hit is decided exactly -- the
+      // reference's window expression AND the distance predicate -- and appended at the list offset `at`.
+      // The last candidate of a batch may lie one to kScanBatch - 1 slots past the stretch: the tile array has that much
+      // padding at both ends, what is read there is never a hit (v + k < count).  x is monotone along a scan, so the last
+      // candidate of the batch decides the stop.  Returns the candidates walked; `stopped`: the scan is over (or was
+      // over before: then nothing is walked).
+      auto stretch = [&](int first, int ws, int count, int step, auto window, unsigned& at, bool& stopped) -> int {
+        int v = 0;
+        for (; v < count && !stopped; v += kScanBatch) {
+          XY q[kScanBatch];
+#pragma unroll
+          for (int k = 0; k < kScanBatch; ++k) q[k] = txy[first - ws + (v + k) * step];
+          // A candidate within the distance is inside the reference's window unless its |dx| is within 2^-20 d of d (then
+          // the rounding of x +- d could decide otherwise: World::dsafe, sandcrate_hip.hip) -- the window expression
+          // itself (two additions and two compares per candidate in the backward scans) is evaluated only for a batch
+          // in which some lane has such a hit: exact ties at distance d, i.e. tests, not fluids.
+          unsigned inc[kScanBatch];
+          bool edge = false;
+#pragma unroll
+          for (int k = 0; k < kScanBatch; ++k) {
+            const double dx = q[k].x - xi, dy = q[k].y - yi;
+            const bool near = (dx * dx + dy * dy <= w.t_nbr) & (v + k < count);
+            edge |= near & !(fabs(dx) < w.dsafe);
+            inc[k] = near ? kRow : 0u;
+          }
+          if (__ballot(edge)) {
+#pragma unroll
+            for (int k = 0; k < kScanBatch; ++k)
+              if (window(q[k].x, xi) != 2) inc[k] = 0u;
+          }
+          const double dxl = q[kScanBatch - 1].x - xi;
+          const bool stop = step > 0 ? dxl > dstop : dxl < -dstop;
+#pragma unroll
+          for (int k = 0; k < kScanBatch; ++k) {  // trim (:91-93): a full list writes its spare rows
+            *(unsigned short*)(lbase + at) = (unsigned short)(first + (v + k) * step);
+            at += inc[k];
+          }
+          at = min(at, lend);  // once per batch: a list that fills up inside a batch runs into the kScanBatch spare rows
+          stopped = stop | (at == lend);
+        }
+        return min(v, count);
+      };
       auto scan = [&](bool want, int first, int count, int step, auto window) {
         if constexpr (LDS) {
-          // kBatch candidates per iteration: their LDS reads are issued together (one latency per batch
-          // instead of one per candidate) and their tests are independent instruction streams.  The loop
-          // stops on a conservative test of dx (never before the reference's window ends: a candidate
-          // beyond d (1 + 2^-20) in x can neither be in the window nor within d); a hit is decided
-          // exactly -- the reference's window expression AND the distance predicate.
-          constexpr int kBatch = SC_SCAN_BATCH;
-          // The last candidate of a batch may lie one to kBatch - 1 slots past the range: the tile array has that
-          // much padding at both ends, what is read there is never a hit (v + k < count).  x is monotone along a
-          // scan, so the last candidate of the batch decides the stop.
           bool done = !want || lo == lend;
-          for (int v = 0; v < count && !done; v += kBatch) {
-            XY q[kBatch];
-#pragma unroll
-            for (int k = 0; k < kBatch; ++k) q[k] = txy[first + (v + k) * step];
-            // A candidate within the distance is inside the reference's window unless its |dx| is within 2^-20 d of d (then
-            // the rounding of x +- d could decide otherwise: World::dsafe, sandcrate_hip.hip) -- the window expression
-            // itself (two additions and two compares per candidate in the backward scans) is evaluated only for a batch
-            // in which some lane has such a hit: exact ties at distance d, i.e. tests, not fluids.
-            unsigned inc[kBatch];
-            bool edge = false;
-#pragma unroll
-            for (int k = 0; k < kBatch; ++k) {
-              const double dx = q[k].x - xi, dy = q[k].y - yi;
-#ifdef SC_ABL_NOVALID
-              const bool near = (dx * dx + dy * dy <= w.t_nbr);  // (timing ablation only: reads past the range may hit)
-#else
-              const bool near = (dx * dx + dy * dy <= w.t_nbr) & (v + k < count);
-#endif
-              edge |= near & !(fabs(dx) < w.dsafe);
-              inc[k] = near ? kRow : 0u;
-            }
-            if (__ballot(edge)) {
-#pragma unroll
-              for (int k = 0; k < kBatch; ++k)
-                if (window(q[k].x, xi) != 2) inc[k] = 0u;
-            }
-            const double dxl = q[kBatch - 1].x - xi;
-            const bool stop = step > 0 ? dxl > dstop : dxl < -dstop;
-#pragma unroll
-            for (int k = 0; k < kBatch; ++k) {  // trim (:91-93): a full list writes its spare rows
-              *(unsigned short*)(lbase + lo) = (unsigned short)(first + (v + k) * step);
-              lo += inc[k];
-            }
-            lo = min(lo, lend);  // once per batch: a list that fills up inside a batch runs into the kBatch spare rows
-            done = stop | (lo == lend);
-          }
+          stretch(first, 0, count, step, window, lo, done);
         } else {
           const int lane = t & 63, wave0 = t & ~63;
           int pos = first, left = want ? count : 0;
@@ -317,17 +286,14 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
             probe.clock_stage();
             const int ws = rws;
             auto inside = [&](int p) { return (unsigned)(p - ws) < (unsigned)CAP; };
-            // This thread's next stretch inside the window, at most kSerial candidates, walked like an LDS tile's scan:
-            // kWinBatch candidates per iteration, their LDS reads issued together, hits decided exactly, an append is a
-            // store and a clamped add (no branch), the batch's last candidate decides a conservative stop.  For that
-            // last candidate to be one of the scan's own the stretch is a multiple of kWinBatch unless the range ends
-            // in it (up to three candidates before the window's end wait for the wave-wide turn or the next window).
-            constexpr int kWinBatch = SC_SCAN_BATCH;
-            static_assert(kSerial % kWinBatch == 0, "the serial stretch is a whole number of batches");
+            // This thread's next stretch inside the window, at most kSerial candidates, walked like an LDS tile's scan
+            // (`stretch`).  For the last candidate of a batch to be one of the scan's own the stretch is a multiple of
+            // kScanBatch unless the range ends in it (up to three candidates before the window's end wait for the
+            // wave-wide turn or the next window).
+            static_assert(kSerial % kScanBatch == 0, "the serial stretch is a whole number of batches");
             {
               const int avail = step > 0 ? ws + CAP - pos : pos - ws + 1;  // slots of the window from pos on
-              const int lim = left <= avail ? left : (avail & ~(kWinBatch - 1));
-#if SC_SERIAL_ONCE
+              const int lim = left <= avail ? left : (avail & ~(kScanBatch - 1));
               // a thread walks kSerial candidates on its own ONCE per scan, in the first window that holds its position:
               // what is left after that is a long walk (the serial stretch ends most scans), and in the windows that follow
               // its next 32 candidates would cost the wave this loop's eight iterations and spare the wave-wide turn nothing
@@ -335,42 +301,9 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
               const bool mine_now = left > 0 && inside(pos);
               const int cnt = mine_now && fresh ? min(lim, kSerial) : 0;
               fresh = fresh && !mine_now;
-#else
-              const int cnt = left > 0 && inside(pos) ? min(lim, kSerial) : 0;
-#endif
-              const int base = pos - ws;
               unsigned lw = lo0 + (unsigned)C * kRow;
               bool stopped = false;
-              int v = 0;
-              for (; v < cnt && !stopped; v += kWinBatch) {
-                XY q[kWinBatch];
-#pragma unroll
-                for (int k = 0; k < kWinBatch; ++k) q[k] = txy[base + (v + k) * step];
-                unsigned inc[kWinBatch];
-                bool edge = false;  // (as in the LDS scan: the window expression only for a batch with a hit at the window's edge)
-#pragma unroll
-                for (int k = 0; k < kWinBatch; ++k) {
-                  const double dx = q[k].x - xi, dy = q[k].y - yi;
-                  const bool near = (dx * dx + dy * dy <= w.t_nbr) & (v + k < cnt);
-                  edge |= near & !(fabs(dx) < w.dsafe);
-                  inc[k] = near ? kRow : 0u;
-                }
-                if (__ballot(edge)) {
-#pragma unroll
-                  for (int k = 0; k < kWinBatch; ++k)
-                    if (window(q[k].x, xi) != 2) inc[k] = 0u;
-                }
-                const double dxl = q[kWinBatch - 1].x - xi;
-                const bool stop = step > 0 ? dxl > dstop : dxl < -dstop;
-#pragma unroll
-                for (int k = 0; k < kWinBatch; ++k) {  // trim (:91-93): a full list writes its spare rows
-                  *(unsigned short*)(lbase + lw) = (unsigned short)(pos + (v + k) * step);
-                  lw += inc[k];
-                }
-                lw = min(lw, lend);
-                stopped = stop | (lw == lend);
-              }
-              const int walked = min(v, cnt);
+              const int walked = stretch(pos, ws, cnt, step, window, lw, stopped);
               C = (int)((lw - lo0) / kRow);
               pos += walked * step;
               left = stopped ? 0 : left - walked;
@@ -405,7 +338,7 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
               }
               // the rest of the owner's stretch inside this window, kCoop x 64 candidates per step (their LDS reads
               // issued together), hits ranked in scan order
-              constexpr int kCoop = SC_COOP;
+              constexpr int kCoop = 2;
               const int need = kMaxNbr - oC;
               int taken = 0, done = 0;
               bool stopped = false;
@@ -420,11 +353,9 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
                     const bool valid = c * 64 + lane < nc;
                     const double dx = q[c].x - oxi, dy = q[c].y - oyi;
                     const bool near = dx * dx + dy * dy <= w.t_nbr;
-#if SC_COOP_FAST
                     // 64 candidates none of which is within the distance or past the window's end (the rule in these
                     // walks: a sparse particle beside a pile of thousands) leave nothing to record: no verdicts, no ranks
                     if (!__ballot(valid && (near || window(q[c].x, oxi) == 0))) continue;
-#endif
                     const int verdict = valid ? window(q[c].x, oxi) : 1;
                     const bool hit = verdict == 2 && near;
                     const unsigned long long stopm = __ballot(verdict == 0);
@@ -451,8 +382,7 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
           probe.clock_round();
         }
       };
-      // same strip, after i: x_j <= x_i + d                                  (:106-109)
-      scan(live, self + 1, e0 - (i + 1), 1, [&](double xj, double xq) { return xj > xq + w.d ? 0 : 2; });
+      scan(live, self + 1, e0 - (i + 1), 1, win_after);
       SC_STAMP(0, 3);
       probe.hits_after_first(C);
       // The scans of the adjacent strips start at a CELL's first particle, up to a cell's worth of candidates short of the
@@ -463,7 +393,7 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
       // lanes with the longest lead-in were the slowest.)
       auto lead_in = [&](int first, int count, int step) -> int {
         int s = 0;
-        if constexpr (LDS && SC_LEAD_IN) {
+        if constexpr (LDS) {
 #pragma unroll
           for (int h = 4; h >= 1; h >>= 1) {
             const int probe = s + h - 1;
@@ -474,63 +404,40 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
         }
         return s;
       };
-      // next strip: x_i - d <= x_j <= x_i + d                                (:112-119)
       {
         const int first = tl.n0 + (b1 - tl.a1), count = e1 - b1, s = lead_in(first, count, 1);
-        scan(live && C < kMaxNbr, first + s, count - s, 1,
-             [&](double xj, double xq) { return xj > xq + w.d ? 0 : (xj >= xq - w.d ? 2 : 1); });
+        scan(live && C < kMaxNbr, first + s, count - s, 1, win_next);
       }
       SC_STAMP(0, 4);
       probe.hits_after_second(C);
-      // reverse edges (:85-88): i is a forward candidate of j, same strip
-      scan(live && C < kMaxNbr, self - 1, i - b0, -1, [&](double xj, double xq) { return !(xq <= xj + w.d) ? 0 : 2; });
+      scan(live && C < kMaxNbr, self - 1, i - b0, -1, win_before);
       SC_STAMP(0, 5);
-      // reverse edges from the previous strip
       {
         const int first = tl.n0 + tl.n1 + (em - 1 - tl.a2), count = em - bm, s = lead_in(first, count, -1);
-        scan(live && C < kMaxNbr, first - s, count - s, -1,
-             [&](double xj, double xq) { return !(xq <= xj + w.d) ? 0 : (xq >= xj - w.d ? 2 : 1); });
+        scan(live && C < kMaxNbr, first - s, count - s, -1, win_prev);
       }
       if constexpr (LDS) C = (int)((lo - lo0) / kRow);
       probe.flush();
     } else if (live) {
       // a tile beyond 65535 particles (a block inside one gigantic bucket) cannot use u16 slots:
-      // entries go straight to the table as -(index+1); correctness path only
-      const double xi = pi.x, yi = pi.y;
-      const double xhi = xi + w.d, xlo = xi - w.d;
-      auto push = [&](int j) { nbr[(size_t)C++ * cap + i] = -j - 1; };
-      for (int j = i + 1; j < e0 && C < kMaxNbr; ++j) {
-        const XY pj = sxy[j];
-        const double xj = pj.x;
-        if (xj > xhi) break;
-        const double dx = xj - xi, dy = pj.y - yi;
-        if (dx * dx + dy * dy <= w.t_nbr) push(j);
-      }
-      for (int j = b1; j < e1 && C < kMaxNbr; ++j) {
-        const XY pj = sxy[j];
-        const double xj = pj.x;
-        if (xj > xhi) break;
-        if (xj >= xlo) {
-          const double dx = xj - xi, dy = pj.y - yi;
-          if (dx * dx + dy * dy <= w.t_nbr) push(j);
+      // entries go straight to the table as -(index+1); correctness path only.  One scan: sorted indices from `j` by
+      // `step` up to `end` (excluded, forward) / down to `end` (included, backward).
+      auto scan_global = [&](int j, int end, int step, auto window) {
+        for (; (step > 0 ? j < end : j >= end) && C < kMaxNbr; j += step) {
+          const XY pj = sxy[j];
+          const double xj = pj.x;
+          const int verdict = window(xj, xi);
+          if (verdict == 0) break;
+          if (verdict == 2) {
+            const double dx = xj - xi, dy = pj.y - yi;
+            if (dx * dx + dy * dy <= w.t_nbr) nbr[(size_t)C++ * cap + i] = -j - 1;
+          }
         }
-      }
-      for (int j = i - 1; j >= b0 && C < kMaxNbr; --j) {
-        const XY pj = sxy[j];
-        const double xj = pj.x;
-        if (!(xi <= xj + w.d)) break;
-        const double dx = xj - xi, dy = pj.y - yi;
-        if (dx * dx + dy * dy <= w.t_nbr) push(j);
-      }
-      for (int j = em - 1; j >= bm && C < kMaxNbr; --j) {
-        const XY pj = sxy[j];
-        const double xj = pj.x;
-        if (!(xi <= xj + w.d)) break;
-        if (xi >= xj - w.d) {
-          const double dx = xj - xi, dy = pj.y - yi;
-          if (dx * dx + dy * dy <= w.t_nbr) push(j);
-        }
-      }
+      };
+      scan_global(i + 1, e0, 1, win_after);
+      scan_global(b1, e1, 1, win_next);
+      scan_global(i - 1, b0, -1, win_before);
+      scan_global(em - 1, bm, -1, win_prev);
     }
   } else if (live) {
     // lists were built by an earlier launch: bring them in
@@ -612,6 +519,13 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
     }
     __syncthreads();
   };
+  // the list's entries renumbered into the reach: an entry of range k loses sub[k]
+  auto renumber = [&](const int* sub) {
+    for (int s = 0; s < C; ++s) {
+      const int e = list(s, t);
+      list(s, t) = (unsigned short)(e - (e < sr1 ? sub[0] : e < sr2 ? sub[1] : sub[2]));
+    }
+  };
   if constexpr (STAGE && !LDS) if (strim) {
     extremes();
     if constexpr (!LDS) {
@@ -620,12 +534,8 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
         const int mt = reach(nb, sub);
         if (mt <= CAP) {  // uniform
           staged = true;
-          if (live)
-            for (int s = 0; s < C; ++s) {
-              const int e = list(s, t);
-              list(s, t) = (unsigned short)(e - (e < sr1 ? sub[0] : e < sr2 ? sub[1] : sub[2]));
-            }
-          const Tile part{nb[0], nb[1] - nb[0], nb[2], nb[3] - nb[2], nb[4], nb[5] - nb[4]};
+          if (live) renumber(sub);
+          const Tile part = published_tile(nb);
           for (int slot = t; slot < mt; slot += kTileW) {
             const int j = tile_index(part, slot);
             txy[slot] = sxy[j];
@@ -652,20 +562,21 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
     constexpr int kFetch = LDS ? 1 : 4;  // global-memory tiles: four neighbors per round trip
     XY qq[kFetch];
     const int Cloop = diag::pairs_a(C);
+    // one pair: slot s of the list, the neighbor at q
+    auto pair = [&](int s, const XY q) {
+      double rx, ry;
+      pair_offset<NOISE>(w, z, s, eta, off, ox - q.x, oy - q.y, rx, ry);
+      z += kGold;
+      const double s2 = rx * rx + ry * ry;
+      const double rinv = rsqrt_nr(s2);
+      const double c = fmin(fmax(s2 * rinv * w.inv_d, 0.0), 1.0);  // crate.py:270: clip(dist / d, 0, 1)
+      sumc += c;
+      const double g = fma(-c, c, c) * rinv;             // crate.py:342 with n = r / dist (:174)
+      ax += g * rx;
+      ay += g * ry;
+    };
     if (STAGE && !LDS && staged) {  // the neighbors are in the staged reach: an LDS tile's loop
-      for (int s = 0; s < Cloop; ++s) {
-        const XY q = txy[list(s, t)];
-        double rx, ry;
-        pair_offset<NOISE>(w, z, s, eta, off, ox - q.x, oy - q.y, rx, ry);
-        z += kGold;
-        const double s2 = rx * rx + ry * ry;
-        const double rinv = rsqrt_nr(s2);
-        const double c = fmin(fmax(s2 * rinv * w.inv_d, 0.0), 1.0);
-        sumc += c;
-        const double g = fma(-c, c, c) * rinv;
-        ax += g * rx;
-        ay += g * ry;
-      }
+      for (int s = 0; s < Cloop; ++s) pair(s, txy[list(s, t)]);
     } else
     for (int s = 0; s < Cloop; ++s) {
       if (s % kFetch == 0) {
@@ -684,16 +595,7 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
 #pragma unroll
       for (int k = 1; k < kFetch; ++k)
         if (s % kFetch == k) q = qq[k];
-      double rx, ry;
-      pair_offset<NOISE>(w, z, s, eta, off, ox - q.x, oy - q.y, rx, ry);
-      z += kGold;
-      const double s2 = rx * rx + ry * ry;
-      const double rinv = rsqrt_nr(s2);
-      const double c = fmin(fmax(s2 * rinv * w.inv_d, 0.0), 1.0);  // crate.py:270: clip(dist / d, 0, 1)
-      sumc += c;
-      const double g = fma(-c, c, c) * rinv;             // crate.py:342 with n = r / dist (:174)
-      ax += g * rx;
-      ay += g * ry;
+      pair(s, q);
     }
     P[i] = C ? fmax(((double)C - sumc) - w.ignored, 0.0) : 0.0;  // crate.py:265-273
     snn[i] = XY{ax, ay};
@@ -730,12 +632,7 @@ __device__ __forceinline__ void pass_a_body(const World& w, const Tile& tl, cons
 #pragma unroll
       for (int k = 0; k < kMaxNbr / 2; ++k) lw[k] = 0u;
       if (in_rows) {
-        if (trim && !staged) {
-          for (int s = 0; s < C; ++s) {
-            const int e = list(s, t);
-            list(s, t) = (unsigned short)(e - (e < sr1 ? sub[0] : e < sr2 ? sub[1] : sub[2]));
-          }
-        }
+        if (trim && !staged) renumber(sub);
 #pragma unroll
         for (int k = 0; k < kMaxNbr / 2; ++k) lw[k] = list.word(k, t);  // (entries from C on: whatever the scans left there)
       } else if (slots_fit) {  // (a tile beyond 16-bit slots wrote the 32-bit table as it searched)
@@ -770,7 +667,7 @@ __global__ void __launch_bounds__(kTileW)
              const double* __restrict__ eta, const int* __restrict__ offById, double* __restrict__ P, XY* __restrict__ snn,
              const int* __restrict__ tileBounds, int* __restrict__ tileBand,
              int* __restrict__ tileBoundsT) {
-  constexpr int kPad = SC_SCAN_BATCH - 1;  // a batched scan may read this far past either end of the tile
+  constexpr int kPad = kScanBatch - 1;  // a batched scan may read this far past either end of the tile
   __shared__ XY txy_padded[CAP + 2 * kPad];
   XY* const txy = txy_padded + kPad;
   __shared__ unsigned int list_words[kTileW * kListWords];  // tile slots of the neighbors, a row per thread (Lists)
@@ -779,7 +676,7 @@ __global__ void __launch_bounds__(kTileW)
 
   const int t = threadIdx.x;
   SC_TIMELINE_KERNEL(0);
-  const int tile_id = tile_of_block_ends_first(tiles_expected(w));
+  const int tile_id = tile_of_block(tiles_expected(w), true);
   const int i0 = tile_id * kTileW;
   const int i = i0 + t;
   SC_STAMP(0, 0);
@@ -788,8 +685,7 @@ __global__ void __launch_bounds__(kTileW)
   const int cpacked = cell[ic];
   const int idi = (DENS && NOISE != SC_NOISE_NONE) ? id[ic] : 0;
   // the tile's three ranges: k_reorder published them, so staging need not wait for the bucket lookups below
-  const int* tb = tileBounds + 6 * tile_id;
-  const int tb0 = tb[0], tb1 = tb[1], tb2 = tb[2], tb3 = tb[3], tb4 = tb[4], tb5 = tb[5];
+  const Tile tl = published_tile(tileBounds + 6 * tile_id);
   const int n = counters[C_NT];
   if (i0 >= n || tick_abandoned(counters)) return;
   const int m = min(kTileW, n - i0);
@@ -810,13 +706,6 @@ __global__ void __launch_bounds__(kTileW)
   }
 
   // 1. the particle's own candidate ranges (cell -> six bucket boundaries)
-  Tile tl;
-  tl.a0 = tb0;
-  tl.n0 = tb1 - tb0;
-  tl.a1 = tb2;
-  tl.n1 = tb3 - tb2;
-  tl.a2 = tb4;
-  tl.n2 = tb5 - tb4;
   int e0 = 0, b0 = 0, b1 = 0, e1 = 0, bm = 0, em = 0;
   if (live) {
     const int c = cpacked & kCellMask;
@@ -900,13 +789,6 @@ __global__ void __launch_bounds__(kTileW)
 // its count and the wave's exec mask only ever narrows (a flat `if (s < count)` per unrolled slot restores it every time:
 // four control instructions per slot instead of three, and a wave whose lanes are all done still visits every slot).
 template <int S, int N, class F>
-__device__ __forceinline__ void nested_slots_flat(const int count, F&& f) {  // (the flat form, for comparison)
-  if constexpr (S < N) {
-    if (S < count) f(std::integral_constant<int, S>{});
-    nested_slots_flat<S + 1, N>(count, f);
-  }
-}
-template <int S, int N, class F>
 __device__ __forceinline__ void nested_slots(const int count, F&& f) {
   if constexpr (S < N) {
     if (S < count) {
@@ -965,9 +847,7 @@ __device__ __forceinline__ PairSums pass_b_pairs(const World& w, const Tile& tl,
   const uint64_t zbase = noise_base(w.noise_key, idi);
   const double k_ss = w.k_ss, k_pp = w.k_pp;
   double k_0 = w.k_0;
-#if SC_B_LEAN_LOOP
   asm volatile("" : "+v"(k_0));  // (held in a vector register: as the third operand of an fma next to k_pp it was moved there once per pair)
-#endif
   double tx = 0, ty = 0, mtx = 0, mty = 0;
   // one pair: slot s (a compile-time constant) with the hash key z
   auto pair = [&](auto slot, const uint64_t z, const uint64_t mix) {
@@ -988,7 +868,6 @@ __device__ __forceinline__ PairSums pass_b_pairs(const World& w, const Tile& tl,
       mty += wt * ry;
     }
   };
-#if SC_B_LEAN_LOOP
   // nested slot tests (nested_slots), the hash's running key and its constants in vector registers (noise_regs)
   const NoiseRegs nr = noise_regs();
   uint64_t z = zbase;
@@ -996,9 +875,6 @@ __device__ __forceinline__ PairSums pass_b_pairs(const World& w, const Tile& tl,
     pair(slot, z, nr.mix);
     z += nr.gold;
   });
-#else
-  nested_slots_flat<0, kMaxNbr>(Cn, [&](auto slot) { pair(slot, zbase + (uint64_t) decltype(slot)::value * kGold, kMix); });
-#endif
   return PairSums{tx, ty, mtx, mty};
 }
 
@@ -1030,11 +906,7 @@ __device__ __forceinline__ void pass_b_finish(const World& w, const Tile& tl, co
     ux += ov.x;  // crate.py:175: the neighbors' start-of-tick velocities
     uy += ov.y;
   };
-#if SC_B_LEAN_LOOP
   nested_slots<0, kMaxNbr>(Cn, add_velocity);
-#else
-  nested_slots_flat<0, kMaxNbr>(Cn, add_velocity);
-#endif
 
   // 4. per-particle epilogue
   double Ux = 0, Uy = 0, Cx = 0, Cy = 0, V = 0;
@@ -1184,12 +1056,7 @@ __global__ void __launch_bounds__(kTileW)
       window_block = part == 3;
     } else {  // part 3: the blocks between the windows, bandw .. nt - bandw - 1 (checked once the count is here)
       const int nb = min((int)gridDim.x - 2 * bandw, max(tiles_expected(w) - 2 * bandw, 0)), ib = b - 2 * bandw;
-      int k = ib;
-      if (ib < nb) {
-        const int q = nb >> 3, r = nb & 7, xcd = ib & 7;
-        k = xcd * q + min(xcd, r) + (ib >> 3);
-      }
-      tile_id = bandw + k;
+      tile_id = bandw + xcd_deal(ib, nb, false);
       between = true;
     }
   } else {
@@ -1202,8 +1069,7 @@ __global__ void __launch_bounds__(kTileW)
   // scalars and its row of the table (three 16-byte loads) -- none of these loads waits for another
   const int ic = min(i, cap - 1);
   // (a block between the windows may map beyond the last block of the arrays before the live count says so)
-  const int* tb = tileBounds + 6 * (BANDED ? min(tile_id, (cap - 1) / kTileW) : tile_id);
-  const int tb0 = tb[0], tb1 = tb[1], tb2 = tb[2], tb3 = tb[3], tb4 = tb[4], tb5 = tb[5];
+  const Tile tl = published_tile(tileBounds + 6 * (BANDED ? min(tile_id, (cap - 1) / kTileW) : tile_id));
   const int cpacked = cell[ic];
   const NbrRow row = rows[ic];
   const int Craw = row_count(row);
@@ -1264,13 +1130,6 @@ __global__ void __launch_bounds__(kTileW)
   Seg seg_next{0, 0, 0, 0};
   if (FUSED) seg_next = wn.seg[seg_k];
 
-  Tile tl;
-  tl.a0 = tb0;
-  tl.n0 = tb1 - tb0;
-  tl.a1 = tb2;
-  tl.n1 = tb3 - tb2;
-  tl.a2 = tb4;
-  tl.n2 = tb5 - tb4;
   const int total = tl.n0 + tl.n1 + tl.n2;
   const bool in_lds = total <= kTileCapB;
   // the table entry of slot s: from the row's packed words (the pair loops keep the ten words, not twenty entries, in
