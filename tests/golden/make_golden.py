@@ -4,7 +4,8 @@
 Runs only in the build container (needs /root/reference); the fixtures it writes
 are data (inputs + expected outputs) and are committed, the reference is not.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          # everything
+    python tests/golden/make_golden.py walls    # only the tick_walls_* fixtures
 
 The reference imports two packages that are absent here and that it uses only
 for annotations (nptyping) and for one 2-D rotation at load time
@@ -247,6 +248,31 @@ def tick_cases():
                 save(f"tick_{yaml_name.split('.')[0]}_t{t}", **tap.finish())
 
 
+# ---------------------------------------------------------------- walls at the edges of the device's shortcuts
+def wall_cases():
+    """tests/wall_cases.py's worlds, ticked once by the reference: SC_MAX_SEGMENTS / SC_MAX_BODIES with junctions of
+    3-5 segments of different bodies (two motored), contacts and rows decided by the last ulp (sqrt rule, floor(p/d)),
+    fast crossings near the device's near-segment masks and just beyond / inside far_box."""
+    sys.path.insert(0, str(HERE.parent.parent))
+    sys.path.insert(0, str(HERE.parent))
+    import wall_cases as wc
+    cases = {"tick_walls_junctions": wc.junction_case(), "tick_walls_edges": wc.edges_case(),
+             "tick_walls_fast": wc.near_now_case(with_pile=False), "tick_walls_farbox": wc.far_box_case()}
+    for name, case in cases.items():
+        cfg = load_config(REF / "config" / "wave_machine.yaml")
+        world = cfg.world_config
+        world.rigid_bodies = case.bodies
+        world.coefficients = dict(case.coef)
+        world.particle_sources = []
+        np.random.seed(2024)
+        crate = Crate(world)
+        crate.particles = case.p.copy()
+        crate.particle_velocities = case.v.copy()
+        tap = TickTap(crate)
+        crate.physics_tick()
+        save(name, **tap.finish())
+
+
 # ---------------------------------------------------------------- G4 trajectories
 # The scenes are chaotic: a 1e-17 difference in summation order grows ~10x every 6-8 ticks
 # (measured: stirring_cup reaches 2e-3 by tick 94, wave_machine 1e-7 by tick 137), so the
@@ -270,7 +296,11 @@ def trajectory_cases():
 
 if __name__ == "__main__":
     np.seterr(all="ignore")
+    if sys.argv[1:] == ["walls"]:  # only the wall fixtures (savez_compressed output is not byte-stable)
+        wall_cases()
+        sys.exit(0)
     neighbor_cases()
     geometry_cases()
     tick_cases()
     trajectory_cases()
+    wall_cases()

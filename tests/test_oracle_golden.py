@@ -85,7 +85,8 @@ def test_scene_trajectory_matches_reference(scene):
             np.testing.assert_allclose(crate.particles_pressure, g[f"pressure_t{t}"], rtol=RTOL, atol=1e-9)
 
 
-@pytest.mark.parametrize("name", ["tick_synth512_cup", "tick_stirring_cup_t300", "tick_wave_machine_t100"])
+@pytest.mark.parametrize("name", ["tick_synth512_cup", "tick_stirring_cup_t300", "tick_wave_machine_t100"]
+                         + golden_names("tick_walls_"))
 def test_loop_structured_tick_matches_reference(name):
     """oracle.tick_loops (what bench.py times as the reference's NumPy path) is the same function."""
     from oracle.tick_loops import tick_loops
