@@ -6,6 +6,7 @@ are data (inputs + expected outputs) and are committed, the reference is not.
 
     python tests/golden/make_golden.py          # everything
     python tests/golden/make_golden.py walls    # only the tick_walls_* fixtures
+    python tests/golden/make_golden.py tiles    # only nbr_tile_edges
 
 The reference imports two packages that are absent here and that it uses only
 for annotations (nptyping) and for one 2-D rotation at load time
@@ -273,6 +274,17 @@ def wall_cases():
         save(name, **tap.finish())
 
 
+# ---------------------------------------------------------------- tiles at the sizes where the tiled passes change path
+def tile_cases():
+    """tests/tile_cases.py: the three-range worlds whose block has 961 and 1101 candidates -- one past pass B's LDS budget,
+    one past pass A's dense-tile limit -- in one world, searched by the reference."""
+    sys.path.insert(0, str(HERE.parent.parent))
+    sys.path.insert(0, str(HERE.parent))
+    import tile_cases as tc
+    pts, _ = tc.stacked([tc.three_ranges(961), tc.three_ranges(1101)])
+    neighbor_case("tile_edges", pts, tc.D)
+
+
 # ---------------------------------------------------------------- G4 trajectories
 # The scenes are chaotic: a 1e-17 difference in summation order grows ~10x every 6-8 ticks
 # (measured: stirring_cup reaches 2e-3 by tick 94, wave_machine 1e-7 by tick 137), so the
@@ -299,8 +311,12 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["walls"]:  # only the wall fixtures (savez_compressed output is not byte-stable)
         wall_cases()
         sys.exit(0)
+    if sys.argv[1:] == ["tiles"]:
+        tile_cases()
+        sys.exit(0)
     neighbor_cases()
     geometry_cases()
     tick_cases()
     trajectory_cases()
     wall_cases()
+    tile_cases()

@@ -900,20 +900,7 @@ def test_random_worlds_match_oracle(sc, seed):
 
 
 # ------------------------------------------------------------------ one gigantic bucket (tiles beyond 65,535 entries)
-def _cluster_lists(pts, d):
-    """Neighbor lists of a cluster whose particles are ALL within d of each other and in one strip: to the
-    right in (x, index) order, then to the left descending, cut at 20 (collision_detector.py:85-93)."""
-    n = len(pts)
-    order = np.lexsort((np.arange(n), pts[:, 0]))
-    pos = np.empty(n, dtype=np.int64)
-    pos[order] = np.arange(n)
-    table = np.full((n, 20), -1, dtype=np.int64)
-    for i in range(n):
-        k = pos[i]
-        seq = list(order[k + 1:k + 21]) + list(order[max(k - 20, 0):k][::-1])
-        seq = seq[:20]
-        table[i, :len(seq)] = seq
-    return np.full(n, 20, dtype=np.int32), table
+from tile_cases import cluster_lists as _cluster_lists  # noqa: E402  (the closed form lives with the tile worlds)
 
 
 def test_one_gigantic_bucket(sc):
