@@ -373,6 +373,27 @@ int sc_jpeg_encode_device(sc_ctx* ctx, const uint8_t* dev_rgb, int32_t width, in
 int sc_render_jpeg(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, int32_t quality,
                    uint8_t* out, int64_t capacity, int64_t* n_out);
 
+/* GIF frames: the image data of one frame of an animated GIF (the LZW minimum code size 8, the data sub-blocks, the
+ * block terminator) over a fixed palette of 256 colours: entry 0 is black, entry k is (k, k, 255).  A frame of sc_render
+ * is a palette image by construction: the background is index 0, a wall 255, a disc of colour byte c max(c, 1) -- the
+ * one loss is that (0, 0, 255), a pressure of 1 and above, is stored as (1, 1, 255).  The LZW dictionary is restarted
+ * with a clear code every 1024 pixels, so the frame is compressed on the device in independent chunks; only the
+ * compressed bytes reach `out` (host memory).  tests/gif_spec.py is the bitstream, byte for byte, and
+ * sand_crate_amd/gif.py (GifWriter) puts such frames into a file.  Both calls synchronise.  *n_out is always set, to the
+ * size of the image data once the arguments are valid; if that exceeds `capacity`, nothing is written and
+ * SC_ERR_CAPACITY is returned (out may be null with capacity 0 to ask for the size).  sc_gif_bound gives a capacity that
+ * always suffices.  SC_ERR_STATE between sc_step_begin and sc_step_finish; SC_ERR_ARG for a bad size (each side
+ * 1..16384) or pointer.  The device workspace grows to the largest frame asked for (about 5 bytes per pixel). */
+int sc_gif_bound(int32_t width, int32_t height, int64_t* bound);
+/* dev_index: device memory of height*width palette indices, row 0 at the top.  The context's stream does not wait for
+ * other streams: the frame must be ready when this is called. */
+int sc_gif_encode_device(sc_ctx* ctx, const uint8_t* dev_index, int32_t width, int32_t height, uint8_t* out,
+                         int64_t capacity, int64_t* n_out);
+/* sc_render's frame, resolved to palette indices in a buffer owned by the context, then encoded as
+ * sc_gif_encode_device does. */
+int sc_render_gif(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* out,
+                  int64_t capacity, int64_t* n_out);
+
 /* Synchronises.  Live particles stored in this context (dead ghost copies excluded); summed over
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);

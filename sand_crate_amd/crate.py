@@ -310,6 +310,17 @@ class Crate:
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
         return self._engine.render_jpeg(view, segments, quality)
 
+    def render_gif(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None,
+                   segment_width: int = 2) -> bytes:
+        """`render`'s frame as the image data of one GIF frame, compressed on the GPU: only the LZW bytes leave it;
+        `gif.GifWriter` strings such frames into ``video.gif``.  The frame has a GIF's worth of colours by construction
+        -- black and (c, c, 255) -- so nothing is quantised: palette entry 0 is black, entry k is (k, k, 255).  The one
+        loss: (0, 0, 255), a pressure of 1 and above, is stored as entry 1, (1, 1, 255).
+        The bitstream, byte for byte: tests/gif_spec.py (`image_data(indices(frame))`) applied to `render`'s frame."""
+        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
+        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        return self._engine.render_gif(view, segments)
+
     # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,
     # playback.py:109-118, grown into something a run can resume from)
     def begin_checkpoint(self) -> None:

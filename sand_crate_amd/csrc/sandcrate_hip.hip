@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "sandcrate_hip.h"
+#include "sc_gif.h"
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_rccl.h"
@@ -192,6 +193,10 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   // sc_jpeg_encode_device: the encoder's workspace (coefficients, per-block masks and code lengths, the rows' bit
   // buffers, lengths and offsets; sc_jpeg.h) and the entropy-coded data, each grown to the largest frame asked for
   DevBuf<unsigned char> jpegWork, jpegOut;
+  // sc_gif_encode_device: the encoder's workspace (the chunks' codes, counts and bit offsets; sc_gif.h) and the image
+  // data, and sc_render_gif's frame of palette indices, each grown to the largest frame asked for
+  DevBuf<unsigned char> gifWork, gifIndex;
+  DevBuf<unsigned> gifOut;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -1213,8 +1218,9 @@ static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments
   return SC_OK;
 }
 
-// Grows the key buffer and enqueues splat and resolve into `rgb` (device memory).
-static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb) {
+// Grows the key buffer and enqueues splat and resolve into `rgb` (device memory), or with `as_index` the resolve that
+// writes one palette index per pixel into it (4-byte aligned).
+static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb, bool as_index = false) {
   const int64_t pixels = (int64_t)v.width * v.height;
   if (pixels > c->renderKeys.size()) {
     HIPCHK(c->renderKeys.grow(pixels, c->stream));
@@ -1230,8 +1236,12 @@ static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb) {
       hipLaunchKernelGGL(k_render_splat<false>, dim3(grid_for(bound)), dim3(kBlock), 0, c->stream, v, c->counters, c->x,
                          c->y, c->id[0], c->P, c->normals_valid ? 1 : 0, (int)bound, c->renderKeys);
   }
-  hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
-                     ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
+  if (as_index)
+    hipLaunchKernelGGL(k_render_resolve_index, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys,
+                       rgb);
+  else
+    hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
+                       ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -1397,6 +1407,85 @@ int sc_render_jpeg(sc_ctx* c, const sc_view* view, const double* segments, int32
   HIPCHK(c->renderRgb.grow(3 * (int64_t)v.width * v.height, c->stream));
   if ((rc = render_launch(c, v, c->renderRgb))) return rc;
   return jpeg_encode(c, c->renderRgb, v.width, v.height, quality, out, capacity, n_out);
+}
+
+// ---- GIF encoding (sc_gif.h) ---------------------------------------------------------------------
+
+int sc_gif_bound(int32_t width, int32_t height, int64_t* bound) {
+  if (width < 1 || width > kRenderMaxSide || height < 1 || height > kRenderMaxSide || !bound)
+    return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", width, height, kRenderMaxSide);
+  const int64_t pixels = (int64_t)width * height, chunks = (pixels + kGifChunk - 1) / kGifChunk;
+  const int64_t bytes = (11 * (pixels + chunks + 1) + 7) / 8;  // a code per pixel, a clear per chunk, the end code
+  *bound = 2 + bytes + (bytes + 254) / 255;                    // minimum code size, sub-block lengths, terminator
+  return SC_OK;
+}
+
+// Encodes the W x H palette indices at `index` (device memory, checked by the caller) into `out` (host memory).
+// Enqueued on the context's stream; synchronises twice: for the total length, then for the bytes.
+static int gif_encode(sc_ctx* c, const unsigned char* index, int width, int height, uint8_t* out, int64_t capacity,
+                      int64_t* n_out) {
+  const int64_t pixels = (int64_t)width * height, chunks = (pixels + kGifChunk - 1) / kGifChunk;
+  // the workspace: codes | code counts | bit offsets + the end code's, the two totals
+  auto up = [](int64_t n) { return (n + 255) & ~(int64_t)255; };
+  const int64_t o_count = up(chunks * kGifChunk * (int64_t)sizeof(unsigned short));
+  const int64_t o_off = o_count + up(chunks * (int64_t)sizeof(int));
+  HIPCHK(c->gifWork.grow(o_off + up((chunks + 3) * (int64_t)sizeof(long long)), c->stream));
+  unsigned char* w = c->gifWork;
+  unsigned short* codes = (unsigned short*)w;
+  int* ncodes = (int*)(w + o_count);
+  long long* bit_off = (long long*)(w + o_off);
+  long long* totals = bit_off + chunks + 1;
+
+  hipLaunchKernelGGL(k_gif_lzw, dim3((unsigned)chunks), dim3(64), 0, c->stream, index, (long long)pixels, codes, ncodes);
+  hipLaunchKernelGGL(k_gif_scan, dim3(1), dim3(64), 0, c->stream, (int)chunks, ncodes, bit_off, totals);
+  HIPCHK(hipGetLastError());
+  long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, totals, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *n_out = total;
+  if (total > capacity) return fail(SC_ERR_CAPACITY, "the GIF image data takes %lld bytes, the buffer holds %lld", total,
+                                    (long long)capacity);
+  const int64_t words = (total + 3) / 4;
+  HIPCHK(c->gifOut.grow(words, c->stream));
+  HIPCHK(hipMemsetAsync(c->gifOut, 0, (size_t)words * sizeof(unsigned), c->stream));
+  hipLaunchKernelGGL(k_gif_merge, dim3((unsigned)chunks), dim3(64), 0, c->stream, (int)chunks, codes, ncodes, bit_off, totals,
+                     c->gifOut);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, c->gifOut, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return SC_OK;
+}
+
+// (*n_out is set whatever follows: 0 until the size is known)
+static int gif_check(sc_ctx* c, const uint8_t* out, int64_t capacity, int64_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->in_step) return fail(SC_ERR_STATE, "encoding happens between ticks");
+  if (!n_out || capacity < 0 || (!out && capacity > 0)) return fail(SC_ERR_ARG, "null n_out, or a negative capacity, or a null buffer");
+  return SC_OK;
+}
+
+int sc_gif_encode_device(sc_ctx* c, const uint8_t* dev_index, int32_t width, int32_t height, uint8_t* out, int64_t capacity,
+                         int64_t* n_out) {
+  int rc = gif_check(c, out, capacity, n_out);
+  if (rc) return rc;
+  if (!dev_index) return fail(SC_ERR_ARG, "null frame");
+  if (width < 1 || width > kRenderMaxSide || height < 1 || height > kRenderMaxSide)
+    return fail(SC_ERR_ARG, "frame of %d x %d pixels; each side 1..%d", width, height, kRenderMaxSide);
+  HIPCHK(hipSetDevice(c->device));
+  return gif_encode(c, dev_index, width, height, out, capacity, n_out);
+}
+
+int sc_render_gif(sc_ctx* c, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* out, int64_t capacity,
+                  int64_t* n_out) {
+  int rc = gif_check(c, out, capacity, n_out);
+  if (rc) return rc;
+  RenderView v;
+  if ((rc = render_prepare(c, view, segments, n_segments, true, v))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(c->gifIndex.grow((int64_t)v.width * v.height, c->stream));
+  if ((rc = render_launch(c, v, c->gifIndex, true))) return rc;
+  return gif_encode(c, c->gifIndex, v.width, v.height, out, capacity, n_out);
 }
 
 int sc_download_sort(sc_ctx* c, int64_t* y_floored, int64_t* ids, int64_t room, int64_t* n_out) {

@@ -6,7 +6,8 @@
 //   splat    per covered pixel, a no-return atomicMax of key = (id + 1) << 8 | c: the largest key is the highest id, so
 //            "the particle drawn last wins" (the reference draws in array = id order) holds in any execution order
 //   resolve  per pixel: white if a wall covers it, else background (key 0) or (c, c, 255) from the key's low byte;
-//            it also clears the key it read, which leaves the W x H 64-bit key buffer zero for the next frame
+//            it also clears the key it read, which leaves the W x H 64-bit key buffer zero for the next frame.
+//            k_render_resolve_index writes the same pixel as one palette index instead (the GIF path, sc_gif.h)
 #pragma once
 #include "sc_device.h"
 
@@ -94,21 +95,22 @@ __device__ __forceinline__ bool wall_covers(const RenderSeg& s, double fi, doubl
   return 4.0 * e <= w2;
 }
 
-// Four pixels per thread, written as three dwords (or byte by byte when `rgb` is not 4-byte aligned, and for the
-// last pixels of a frame whose size is not a multiple of four).  Each key is cleared once read: the buffer is all
-// zero between frames (zeroed once when allocated), so no separate clear has to run before the next splat.
-__global__ void __launch_bounds__(kBlock) k_render_resolve(RenderView v, unsigned long long* __restrict__ keys,
-                                                           unsigned char* __restrict__ rgb, int aligned) {
-  const unsigned total = (unsigned)v.width * (unsigned)v.height;  // at most 16384^2
-  const unsigned p0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
-  if (p0 >= total) return;
-  const int m = (int)min(4u, total - p0);
-  unsigned long long key[4] = {0ull, 0ull, 0ull, 0ull};
+// What resolve knows of a thread's four pixels p0 .. p0 + 3 (the first m of them inside the frame): the key of each,
+// cleared once read -- the buffer is all zero between frames (zeroed once when allocated), so no separate clear has
+// to run before the next splat -- and whether a wall covers it.
+struct ResolvedQuad {
+  unsigned long long key[4];
+  bool wall[4];
+};
+
+__device__ __forceinline__ ResolvedQuad resolve_quad(const RenderView& v, unsigned long long* __restrict__ keys,
+                                                     unsigned p0, int m) {
+  ResolvedQuad r = {{0ull, 0ull, 0ull, 0ull}, {false, false, false, false}};
   double fi[4], fj[4];
   int i = (int)(p0 % (unsigned)v.width), j = (int)(p0 / (unsigned)v.width);
   for (int q = 0; q < 4; ++q) {
     if (q < m) {
-      key[q] = keys[p0 + q];
+      r.key[q] = keys[p0 + q];
       keys[p0 + q] = 0ull;
     }
     fi[q] = (double)i;
@@ -118,15 +120,26 @@ __global__ void __launch_bounds__(kBlock) k_render_resolve(RenderView v, unsigne
       ++j;
     }
   }
-  bool wall[4] = {false, false, false, false};
   for (int s = 0; s < v.nseg; ++s) {
     const RenderSeg g = v.seg[s];
-    for (int q = 0; q < 4; ++q) wall[q] = wall[q] || wall_covers(g, fi[q], fj[q], v.w2);
+    for (int q = 0; q < 4; ++q) r.wall[q] = r.wall[q] || wall_covers(g, fi[q], fj[q], v.w2);
   }
+  return r;
+}
+
+// Four pixels per thread, written as three dwords (or byte by byte when `rgb` is not 4-byte aligned, and for the
+// last pixels of a frame whose size is not a multiple of four).
+__global__ void __launch_bounds__(kBlock) k_render_resolve(RenderView v, unsigned long long* __restrict__ keys,
+                                                           unsigned char* __restrict__ rgb, int aligned) {
+  const unsigned total = (unsigned)v.width * (unsigned)v.height;  // at most 16384^2
+  const unsigned p0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
+  if (p0 >= total) return;
+  const int m = (int)min(4u, total - p0);
+  const ResolvedQuad r = resolve_quad(v, keys, p0, m);
   unsigned c[4];
   for (int q = 0; q < 4; ++q) {
-    const unsigned k = (unsigned)(key[q] & 0xFF);
-    c[q] = wall[q] ? 0xFFFFFFu : (key[q] == 0 ? 0u : (k | (k << 8) | (255u << 16)));  // bytes r, g, b
+    const unsigned k = (unsigned)(r.key[q] & 0xFF);
+    c[q] = r.wall[q] ? 0xFFFFFFu : (r.key[q] == 0 ? 0u : (k | (k << 8) | (255u << 16)));  // bytes r, g, b
   }
   unsigned char* out = rgb + 3 * (size_t)p0;
   if (m == 4 && aligned) {
@@ -140,6 +153,24 @@ __global__ void __launch_bounds__(kBlock) k_render_resolve(RenderView v, unsigne
       out[3 * q + 1] = (unsigned char)(c[q] >> 8);
       out[3 * q + 2] = (unsigned char)(c[q] >> 16);
     }
+  }
+}
+
+// The same frame as one palette index per pixel (sc_gif.h; tests/gif_spec.py: indices): 0 for the background, 255 for
+// a wall, max(c, 1) for a disc of colour byte c.  `index` is 4-byte aligned: four pixels are one dword.
+__global__ void __launch_bounds__(kBlock) k_render_resolve_index(RenderView v, unsigned long long* __restrict__ keys,
+                                                                 unsigned char* __restrict__ index) {
+  const unsigned total = (unsigned)v.width * (unsigned)v.height;
+  const unsigned p0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
+  if (p0 >= total) return;
+  const int m = (int)min(4u, total - p0);
+  const ResolvedQuad r = resolve_quad(v, keys, p0, m);
+  unsigned c[4];
+  for (int q = 0; q < 4; ++q) c[q] = r.wall[q] ? 255u : (r.key[q] == 0 ? 0u : max((unsigned)(r.key[q] & 0xFF), 1u));
+  if (m == 4) {
+    *(unsigned*)(index + p0) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+  } else {
+    for (int q = 0; q < m; ++q) index[p0 + q] = (unsigned char)c[q];
   }
 }
 

@@ -155,7 +155,8 @@ class Engine:
         return out
 
     def _jpeg(self, call, width: int, height: int) -> bytes:
-        """Runs call(out, capacity, n_out) into a host buffer kept between calls, growing it when the file is larger."""
+        """Runs call(out, capacity, n_out) -- a JPEG or a GIF encoder -- into a host buffer kept between calls, growing it
+        when the file is larger."""
         buf = getattr(self, "_jpeg_buf", None)
         if buf is None or len(buf) < 3 * width * height + 4096:  # (a frame's raw size: enough for all but noise)
             buf = self._jpeg_buf = np.empty(3 * width * height + 4096, dtype=np.uint8)
@@ -189,6 +190,31 @@ class Engine:
         seg = N.f64(segments).reshape(-1, 2, 2)
         return self._jpeg(lambda out, cap, n: self._lib.sc_render_jpeg(self._ctx, C.byref(view), N.dptr(seg), len(seg),
                                                                        int(quality), out, cap, n),
+                          int(view.width), int(view.height))
+
+    def encode_gif(self, index) -> bytes:
+        """The image data of one GIF frame (sc_gif_encode_device; `gif.GifWriter.write` takes it) of an H x W uint8 image
+        of palette indices -- entry 0 is black, entry k is (k, k, 255): a contiguous CUDA tensor, which must be ready on
+        the library's stream (torch's current stream is synchronised first), or a NumPy array, which is uploaded.
+        Synchronises.  The bitstream, byte for byte: tests/gif_spec.py."""
+        import torch
+        if isinstance(index, np.ndarray):
+            index = torch.from_numpy(np.ascontiguousarray(index)).to(f"cuda:{self.device}")
+        if not getattr(index, "is_cuda", False) or index.dim() != 2 or not index.is_contiguous() or \
+                str(index.dtype) != "torch.uint8":
+            raise ValueError("index must be a contiguous H x W uint8 CUDA tensor or NumPy array")
+        torch.cuda.current_stream(index.device).synchronize()  # (the library's stream does not wait for torch's)
+        h, w = int(index.shape[0]), int(index.shape[1])
+        ptr = N._P(index.data_ptr())
+        return self._jpeg(lambda out, cap, n: self._lib.sc_gif_encode_device(self._ctx, ptr, w, h, out, cap, n), w, h)
+
+    def render_gif(self, view: N.View, segments) -> bytes:
+        """The frame `render` draws as palette indices (background 0, a wall 255, a disc of colour byte c max(c, 1): the
+        one loss is that (0, 0, 255) becomes (1, 1, 255)), encoded as `encode_gif` does without leaving the GPU before it
+        is compressed (sc_render_gif).  Synchronises."""
+        seg = N.f64(segments).reshape(-1, 2, 2)
+        return self._jpeg(lambda out, cap, n: self._lib.sc_render_gif(self._ctx, C.byref(view), N.dptr(seg), len(seg),
+                                                                      out, cap, n),
                           int(view.width), int(view.height))
 
     # -- per-tick inputs

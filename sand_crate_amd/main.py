@@ -12,7 +12,10 @@ left commented out (playback.py:112-113).  ``--frames`` also renders a ``screen_
 recorded tick on the GPU (`Crate.render`, what Playback.draw_scene draws) and writes them as ``frames.npz`` and, when PIL
 is installed, ``video.gif`` (playback.py:131-138).  ``--video`` renders the same frames and encodes them as JPEG on the GPU
 (`Crate.render_jpeg`, quality ``--video-quality``, default 95 as cv2's); only the compressed frames leave it, and they
-are streamed into ``video.avi``, Motion-JPEG at 50 fps as playback.py:120-129 writes it.  ``--checkpoint-every K`` also writes resumable checkpoints
+are streamed into ``video.avi``, Motion-JPEG at 50 fps as playback.py:120-129 writes it.  ``--gif`` does the same for
+``video.gif``: every recorded tick is rendered and LZW-compressed on the GPU (`Crate.render_gif`) and streamed into the file
+(`gif.GifWriter`; 10 ms per frame, looping, as playback.py:131-138), without PIL and without keeping frames in memory;
+with ``--frames`` as well, ``frames.npz`` is still written and this ``video.gif`` is the one kept.  ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
 """
@@ -30,6 +33,7 @@ import yaml
 
 from .avi import AviWriter
 from .crate import Crate
+from .gif import GifWriter
 from .load_config import Config, load_config
 
 options = {
@@ -72,7 +76,7 @@ class HeadlessPlayback:
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-                 video_quality: int = 95) -> None:
+                 video_quality: int = 95, gif: bool = False) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -91,6 +95,8 @@ class HeadlessPlayback:
         self.video = bool(video)
         self.video_quality = int(video_quality)
         self.video_frames = 0
+        self.gif = bool(gif)
+        self.gif_frames = 0
         self.done = False
         self.seconds = 0.0
 
@@ -102,19 +108,26 @@ class HeadlessPlayback:
         if self.video:
             self.recording_dir_path.mkdir(exist_ok=True, parents=True)
             avi = AviWriter(self.recording_dir_path / "video.avi", int(pb.screen_x), int(pb.screen_y), fps=50)
+        gif = None
         try:
-            self._run(int(n), avi)
+            if self.gif:
+                self.recording_dir_path.mkdir(exist_ok=True, parents=True)
+                gif = GifWriter(self.recording_dir_path / "video.gif", int(pb.screen_x), int(pb.screen_y), delay_cs=1, loop=0)
+            self._run(int(n), avi, gif)
         finally:
             if avi is not None:
                 self.video_frames = avi.frames
                 avi.close()
+            if gif is not None:
+                self.gif_frames = gif.frames
+                gif.close()
         self._collect_checkpoint()
         self.crate.synchronize()
         self.seconds = time.perf_counter() - t0
         if self.config.playback_config.save_recording:
             self.save_recording(self.recording_dir_path)
 
-    def _run(self, n: int, avi: Optional[AviWriter]) -> None:
+    def _run(self, n: int, avi: Optional[AviWriter], gif: Optional[GifWriter] = None) -> None:
         pb = self.config.playback_config
         for _ in range(n):
             self.crate.physics_tick()
@@ -130,6 +143,8 @@ class HeadlessPlayback:
                     self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y)))
                 if avi is not None:
                     avi.write(self.crate.render_jpeg(int(pb.screen_x), int(pb.screen_y), quality=self.video_quality))
+                if gif is not None:
+                    gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y)))
             if self.done:
                 break
 
@@ -154,17 +169,17 @@ class HeadlessPlayback:
         arrays["ticks"] = np.array([f["tick"] for f in self.frames], dtype=np.int64)
         np.savez_compressed(out_dir / "state.npz", **arrays)
         if self.render_frames:
-            write_frames(out_dir, self.images, arrays["ticks"])
+            write_frames(out_dir, self.images, arrays["ticks"], gif=not self.gif)
 
 
-def write_frames(out_dir: Path, frames, ticks) -> None:
-    """frames.npz (`frames` T x H x W x 3 uint8, `ticks`) and, when PIL is installed, video.gif as playback.py:131-138
-    writes it."""
+def write_frames(out_dir: Path, frames, ticks, gif: bool = True) -> None:
+    """frames.npz (`frames` T x H x W x 3 uint8, `ticks`) and, with `gif` and when PIL is installed, video.gif as
+    playback.py:131-138 writes it (`gif=False`: the caller has written, or does not want, a video.gif)."""
     out_dir = Path(out_dir)
     frames = [np.asarray(f, dtype=np.uint8) for f in frames]
     stack = np.stack(frames) if frames else np.zeros((0, 0, 0, 3), dtype=np.uint8)
     np.savez_compressed(out_dir / "frames.npz", frames=stack, ticks=np.asarray(ticks, dtype=np.int64))
-    if not frames:
+    if not frames or not gif:
         return
     try:
         from PIL import Image
@@ -177,7 +192,7 @@ def write_frames(out_dir: Path, frames, ticks) -> None:
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-         video_quality: int = 95) -> list[dict]:
+         video_quality: int = 95, gif: bool = False) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -186,7 +201,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
-                                    video=video, video_quality=video_quality)
+                                    video=video, video_quality=video_quality, gif=gif)
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -211,7 +226,10 @@ if __name__ == "__main__":
     ap.add_argument("--video", action="store_true", help="also render and JPEG-encode a frame on the GPU every "
                     "--record-every ticks, streamed into video.avi (Motion-JPEG, 50 fps)")
     ap.add_argument("--video-quality", type=int, default=95, help="JPEG quality of --video, 1..100 (default 95)")
+    ap.add_argument("--gif", action="store_true", help="also render and LZW-compress a frame on the GPU every "
+                    "--record-every ticks, streamed into video.gif (10 ms per frame, looping); replaces the video.gif "
+                    "of --frames")
     a = ap.parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
-         video=a.video, video_quality=a.video_quality)
+         video=a.video, video_quality=a.video_quality, gif=a.gif)
