@@ -394,6 +394,19 @@ int sc_gif_encode_device(sc_ctx* ctx, const uint8_t* dev_index, int32_t width, i
 int sc_render_gif(sc_ctx* ctx, const sc_view* view, const double* segments, int32_t n_segments, uint8_t* out,
                   int64_t capacity, int64_t* n_out);
 
+/* HUD: the text the reference's viewer draws at the top left of every frame (Playback.draw_debug_text, playback.py:215-219;
+ * Crate.debug_prints is that text).  From this call on every frame made by sc_render, sc_render_device, sc_render_jpeg and
+ * sc_render_gif carries `text` in white -- (255, 255, 255), palette index 255 -- drawn over the discs and walls before an
+ * encoder reads the frame, in a built-in bitmap font, not antialiased: ASCII 0x20..0x7E in cells of 8 x 16 pixels, any
+ * other byte drawn as '?'.  The text is split into lines at '\n'; line l starts at pixel row y + l * 18 * scale,
+ * character k of a line at pixel column x + k * 8 * scale, a glyph bit covers scale x scale pixels, pixels outside the
+ * frame are dropped.  tests/text_spec.py is the pixel rule, bit for bit.  The text is copied (it need not end in a zero
+ * byte); n_bytes == 0 clears the HUD (text may then be null), and a new context has none.  Synchronises the context's
+ * stream: frames enqueued before the call keep the text they were enqueued with.  Like rendering it leaves the simulation
+ * alone.  SC_ERR_ARG for n_bytes outside 0..65536, a null text with n_bytes > 0, x or y outside 0..16384 or scale
+ * outside 1..64; the HUD is then what it was. */
+int sc_set_hud(sc_ctx* ctx, const char* text, int32_t n_bytes, int32_t x, int32_t y, int32_t scale);
+
 /* Synchronises.  Live particles stored in this context (dead ghost copies excluded); summed over
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);

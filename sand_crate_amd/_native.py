@@ -137,6 +137,7 @@ SIGNATURES = {
     "sc_gif_bound": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "sc_gif_encode_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "sc_render_gif": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "sc_set_hud": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 _lib = None

@@ -46,6 +46,7 @@ import yaml
 
 from . import _native as N
 from .engine import Engine
+from .hud_font import default_placement
 from .load_config import WorldConfig
 from .particle_source import build_particle_sources
 from .rigid_body import build_rigid_bodies
@@ -114,6 +115,7 @@ class Crate:
         self._hud_forces = False
         self._force_ema = {}
         self._pending_checkpoint = None
+        self._hud_sent = None      # (text bytes, x, y, scale) the engine draws on frames, or None: no HUD
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -216,6 +218,7 @@ class Crate:
         rng = old.rng_get_state() if self._noise == "host" else None
         self._engine = Engine(int(needed * 1.5) + 1024, device=old.device)
         self._engine.set_noise_mode(_NOISE_MODES[self._noise], self._noise_seed)
+        self._hud_sent = None  # (a new context has no HUD)
         if rng is not None:
             self._engine.rng_set_state(*rng)
         old.close()
@@ -283,8 +286,30 @@ class Crate:
         self._engine.enable_force_monitor(self._hud_forces)
 
     # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
+    def _set_hud(self, hud, width: int) -> None:
+        """The `hud` argument of `render`, `render_jpeg` and `render_gif`: True draws `debug_prints` (what
+        Playback.draw_debug_text shows, playback.py:215-219), a str draws that string, None or False nothing.  The text
+        goes at the reference's margin in the built-in bitmap font, scaled for a frame this wide
+        (hud_font.default_placement); characters outside ASCII become ``?``.  The engine is told only when the text or
+        its placement changed since the last frame."""
+        want = None
+        if hud is not None and hud is not False:
+            text = self.debug_prints if hud is True else hud
+            if not isinstance(text, str):
+                raise TypeError("hud must be None, a bool or a str")
+            data = text.encode("ascii", "replace")
+            if data:
+                want = (data, *default_placement(width))
+        if want != self._hud_sent:
+            self._hud_sent = None
+            if want is None:
+                self._engine.set_hud(None)
+            else:
+                self._engine.set_hud(*want)
+            self._hud_sent = want
+
     def render(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None, segment_width: int = 2,
-               out=None):
+               out=None, hud=None):
         """The frame the reference's viewer draws after `physics_tick()`, rendered on the GPU: every particle a disc of
         ``int(width * particle_radius) * zoom`` pixels coloured by its pressure (white at 0, blue at 1 and above), the
         walls (`segments`) on top in white, black elsewhere; ``height x width x 3`` uint8, row 0 at the top.
@@ -295,30 +320,36 @@ class Crate:
         of shape (height, width, 3) the frame is written there on the library's stream and the call returns without
         synchronising: the library's stream does not wait for torch's, so the tensor must be ready when this is called
         and read after `synchronize()` (or run the crate on torch's stream, `engine.set_stream`).  Otherwise it returns a
-        NumPy array.
-        The pixel rule, bit for bit: tests/render_spec.py."""
+        NumPy array.  `hud=True` writes the HUD text (`debug_prints`) over the frame at the top left, `hud` a str that
+        string (`_set_hud`); telling the engine a new text synchronises.
+        The pixel rule, bit for bit: tests/render_spec.py, and tests/text_spec.py for the text."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        self._set_hud(hud, width)
         return self._engine.render(view, segments, out)
 
     def render_jpeg(self, width: int = 1000, height: int = 1000, *, quality: int = 95, zoom: float = 1.0, center=None,
-                    segment_width: int = 2) -> bytes:
+                    segment_width: int = 2, hud=None) -> bytes:
         """`render`'s frame as a JPEG file, encoded on the GPU: only the compressed bytes leave it.  Baseline JPEG, 4:4:4,
-        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).
+        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).  `hud` as
+        in `render`: the text is on the frame before it is encoded.
         The bitstream, byte for byte: tests/jpeg_spec.py applied to `render`'s frame."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        self._set_hud(hud, width)
         return self._engine.render_jpeg(view, segments, quality)
 
     def render_gif(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None,
-                   segment_width: int = 2) -> bytes:
+                   segment_width: int = 2, hud=None) -> bytes:
         """`render`'s frame as the image data of one GIF frame, compressed on the GPU: only the LZW bytes leave it;
         `gif.GifWriter` strings such frames into ``video.gif``.  The frame has a GIF's worth of colours by construction
         -- black and (c, c, 255) -- so nothing is quantised: palette entry 0 is black, entry k is (k, k, 255).  The one
-        loss: (0, 0, 255), a pressure of 1 and above, is stored as entry 1, (1, 1, 255).
+        loss: (0, 0, 255), a pressure of 1 and above, is stored as entry 1, (1, 1, 255).  `hud` as in `render`: the text
+        is white like the walls, entry 255.
         The bitstream, byte for byte: tests/gif_spec.py (`image_data(indices(frame))`) applied to `render`'s frame."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        self._set_hud(hud, width)
         return self._engine.render_gif(view, segments)
 
     # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,

@@ -20,6 +20,7 @@
 
 #include "sandcrate_hip.h"
 #include "sc_gif.h"
+#include "sc_hud.h"
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_rccl.h"
@@ -197,6 +198,11 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   // data, and sc_render_gif's frame of palette indices, each grown to the largest frame asked for
   DevBuf<unsigned char> gifWork, gifIndex;
   DevBuf<unsigned> gifOut;
+  // sc_set_hud: the text every rendered frame carries and its lines' (start, length); hud_lines == 0: no HUD
+  DevBuf<unsigned char> hudText;
+  DevBuf<HudLine> hudLines;
+  int hud_lines = 0, hud_longest = 0;  // ... how many lines, and the bytes of the longest
+  int hud_x = 0, hud_y = 0, hud_scale = 1;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -1218,8 +1224,23 @@ static int render_prepare(sc_ctx* c, const sc_view* view, const double* segments
   return SC_OK;
 }
 
-// Grows the key buffer and enqueues splat and resolve into `rgb` (device memory), or with `as_index` the resolve that
-// writes one palette index per pixel into it (4-byte aligned).
+// Enqueues the HUD overlay over a resolved frame: over the text's bounding box clipped to the frame, or not at all
+// when there is no HUD or the box is empty.
+static void hud_launch(sc_ctx* c, const RenderView& v, unsigned char* frame, bool as_index) {
+  if (c->hud_lines == 0) return;
+  const long long bw = std::min<long long>(v.width - c->hud_x, (long long)c->hud_longest * kFontCols * c->hud_scale);
+  const long long bh = std::min<long long>(v.height - c->hud_y, (long long)c->hud_lines * kHudPitch * c->hud_scale);
+  if (bw <= 0 || bh <= 0) return;
+  const HudBox b{v.width, c->hud_x, c->hud_y, (int)bw, (int)bh, c->hud_scale};
+  const dim3 grid((unsigned)((bw + kHudTileW - 1) / kHudTileW), (unsigned)((bh + kHudTileH - 1) / kHudTileH));
+  if (as_index)
+    hipLaunchKernelGGL(k_hud_overlay<true>, grid, dim3(kBlock), 0, c->stream, b, c->hudText, c->hudLines, frame);
+  else
+    hipLaunchKernelGGL(k_hud_overlay<false>, grid, dim3(kBlock), 0, c->stream, b, c->hudText, c->hudLines, frame);
+}
+
+// Grows the key buffer and enqueues splat, resolve and the HUD overlay into `rgb` (device memory), or with `as_index`
+// the resolve that writes one palette index per pixel into it (4-byte aligned).
 static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb, bool as_index = false) {
   const int64_t pixels = (int64_t)v.width * v.height;
   if (pixels > c->renderKeys.size()) {
@@ -1242,7 +1263,43 @@ static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb, boo
   else
     hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
                        ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
+  hud_launch(c, v, rgb, as_index);
   HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int sc_set_hud(sc_ctx* c, const char* text, int32_t n_bytes, int32_t x, int32_t y, int32_t scale) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (n_bytes < 0 || n_bytes > kHudMaxBytes) return fail(SC_ERR_ARG, "HUD text of %d bytes; 0..%d", n_bytes, kHudMaxBytes);
+  if (n_bytes > 0 && !text) return fail(SC_ERR_ARG, "null HUD text");
+  if (x < 0 || x > kRenderMaxSide || y < 0 || y > kRenderMaxSide)
+    return fail(SC_ERR_ARG, "HUD origin (%d, %d); each coordinate 0..%d", x, y, kRenderMaxSide);
+  if (scale < 1 || scale > kHudMaxScale) return fail(SC_ERR_ARG, "HUD scale %d; 1..%d", scale, kHudMaxScale);
+  HIPCHK(hipSetDevice(c->device));
+  c->hud_lines = 0;  // (a call that fails below leaves no HUD)
+  if (n_bytes > 0) {
+    // the lines as str.split("\n") cuts them: a trailing newline yields an empty last line
+    std::vector<HudLine> lines;
+    int start = 0, longest = 0;
+    for (int k = 0; k <= n_bytes; ++k) {
+      if (k < n_bytes && text[k] != '\n') continue;
+      lines.push_back(HudLine{start, k - start});
+      longest = std::max(longest, k - start);
+      start = k + 1;
+    }
+    HIPCHK(c->hudText.grow(n_bytes, c->stream));
+    HIPCHK(c->hudLines.grow((int64_t)lines.size(), c->stream));
+    HIPCHK(hipMemcpyAsync(c->hudText, text, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hudLines, lines.data(), lines.size() * sizeof(HudLine), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // `text` and `lines` are the caller's and ours: read before we return
+    c->hud_longest = longest;
+    c->hud_x = x;
+    c->hud_y = y;
+    c->hud_scale = scale;
+    c->hud_lines = (int)lines.size();
+    return SC_OK;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
   return SC_OK;
 }
 

@@ -217,6 +217,14 @@ class Engine:
                                                                       out, cap, n),
                           int(view.width), int(view.height))
 
+    def set_hud(self, text: bytes | None, x: int = 6, y: int = 6, scale: int = 1) -> None:
+        """From now on every frame of `render`, `render_jpeg` and `render_gif` carries `text` in white over the discs and
+        walls: lines split at ``\\n``, the first at pixel (x, y), in the built-in 8 x 16 bitmap font (hud_font.py) with
+        every glyph bit `scale` x `scale` pixels; bytes outside ASCII 0x20..0x7E are drawn as ``?``.  None or b"" clears
+        it.  Synchronises (sc_set_hud).  The pixel rule, bit for bit: tests/text_spec.py."""
+        data = bytes(text) if text else b""
+        N.check(self._lib.sc_set_hud(self._ctx, data if data else None, len(data), int(x), int(y), int(scale)))
+
     # -- per-tick inputs
     def set_params(self, *, dt, particle_radius, wall_collision_decay, pressure_amplifier, ignored_pressure,
                    collider_noise_level, viscosity, surface_smoothing, target_pressure, gravity) -> None:

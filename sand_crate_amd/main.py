@@ -15,7 +15,10 @@ is installed, ``video.gif`` (playback.py:131-138).  ``--video`` renders the same
 are streamed into ``video.avi``, Motion-JPEG at 50 fps as playback.py:120-129 writes it.  ``--gif`` does the same for
 ``video.gif``: every recorded tick is rendered and LZW-compressed on the GPU (`Crate.render_gif`) and streamed into the file
 (`gif.GifWriter`; 10 ms per frame, looping, as playback.py:131-138), without PIL and without keeping frames in memory;
-with ``--frames`` as well, ``frames.npz`` is still written and this ``video.gif`` is the one kept.  ``--checkpoint-every K`` also writes resumable checkpoints
+with ``--frames`` as well, ``frames.npz`` is still written and this ``video.gif`` is the one kept.  ``--hud`` writes the
+HUD text the reference's viewer shows (`Crate.debug_prints`: tick, particle count, timing and the coefficient list --
+what tells one variant's video from the next) on every frame of ``--frames``, ``--video`` and ``--gif``, on the GPU, in
+a built-in bitmap font.  ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
 """
@@ -76,7 +79,7 @@ class HeadlessPlayback:
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-                 video_quality: int = 95, gif: bool = False) -> None:
+                 video_quality: int = 95, gif: bool = False, hud: bool = False) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -97,6 +100,7 @@ class HeadlessPlayback:
         self.video_frames = 0
         self.gif = bool(gif)
         self.gif_frames = 0
+        self.hud = bool(hud)
         self.done = False
         self.seconds = 0.0
 
@@ -129,6 +133,7 @@ class HeadlessPlayback:
 
     def _run(self, n: int, avi: Optional[AviWriter], gif: Optional[GifWriter] = None) -> None:
         pb = self.config.playback_config
+        hud = True if self.hud else None
         for _ in range(n):
             self.crate.physics_tick()
             if self.checkpoint_every and self.crate.tick % self.checkpoint_every == 0:
@@ -140,11 +145,12 @@ class HeadlessPlayback:
                                     "pressure": self.crate.particles_pressure.copy(),
                                     "segments": self.crate.segments.copy()})
                 if self.render_frames:
-                    self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y)))
+                    self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y), hud=hud))
                 if avi is not None:
-                    avi.write(self.crate.render_jpeg(int(pb.screen_x), int(pb.screen_y), quality=self.video_quality))
+                    avi.write(self.crate.render_jpeg(int(pb.screen_x), int(pb.screen_y), quality=self.video_quality,
+                                                     hud=hud))
                 if gif is not None:
-                    gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y)))
+                    gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y), hud=hud))
             if self.done:
                 break
 
@@ -192,7 +198,7 @@ def write_frames(out_dir: Path, frames, ticks, gif: bool = True) -> None:
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-         video_quality: int = 95, gif: bool = False) -> list[dict]:
+         video_quality: int = 95, gif: bool = False, hud: bool = False) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -201,7 +207,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
-                                    video=video, video_quality=video_quality, gif=gif)
+                                    video=video, video_quality=video_quality, gif=gif, hud=hud)
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -211,7 +217,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
     return summary
 
 
-if __name__ == "__main__":
+def argument_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("config_file_path", type=Path)
     ap.add_argument("play_recording", type=Path, nargs="?", default=None)
@@ -229,7 +235,13 @@ if __name__ == "__main__":
     ap.add_argument("--gif", action="store_true", help="also render and LZW-compress a frame on the GPU every "
                     "--record-every ticks, streamed into video.gif (10 ms per frame, looping); replaces the video.gif "
                     "of --frames")
-    a = ap.parse_args()
+    ap.add_argument("--hud", action="store_true", help="write the HUD text (tick, particle count, timing, coefficients) on "
+                    "every frame of --frames, --video and --gif")
+    return ap
+
+
+if __name__ == "__main__":
+    a = argument_parser().parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
-         video=a.video, video_quality=a.video_quality, gif=a.gif)
+         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud)

@@ -1,11 +1,17 @@
 """GPU time of one rendered frame (sc_render_device: clear + splat + resolve), measured with HIP events.
 
-    python scripts/render_time.py [--reps 50]
+    python scripts/render_time.py [--reps 50] [--hud]
 
 Scenes: bench.py's M2 inputs (1,048,576 particles in the wave_machine world) after 5 ticks at 1000 x 1000 and
 4096 x 4096, and config/wave_machine.yaml after 200 ticks of its source at 1000 x 1000 (discs of radius 5).  The
 library runs on torch's current stream so that the events bracket exactly the render's launches.  Prints one JSON line
 per case: median and min over the repetitions, in microseconds.
+
+--hud measures the HUD overlay (sc_set_hud) instead: config/wave_machine.yaml after 200 ticks with `show_forces()` on, at
+1000 x 1000; `render` (device time, HIP events), `render_jpeg` and `render_gif` (host wall time: both synchronise), each
+without and with `hud=True`, in two alternating rounds, and the time `hud=True` adds (the difference of the medians of
+all rounds).  Beside it the host alternative: download the frame, PIL.ImageDraw.text, upload it again (skipped without
+PIL).  The rows without a HUD use nothing this option's commit added, so the same script times an older library.
 """
 import argparse
 import json
@@ -16,33 +22,113 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
-def time_render(crate, width, height, reps):
+def stats(times):
+    times = sorted(times)
+    return {"median_us": round(times[len(times) // 2], 2), "min_us": round(times[0], 2)}
+
+
+def device_times(crate, width, height, reps, **kw):
+    """Device time of `reps` renders (with these keywords of `Crate.render`), HIP events around each."""
     import torch
     stream = torch.cuda.current_stream()
     crate.engine.set_stream(stream.cuda_stream)
     out = torch.empty((height, width, 3), dtype=torch.uint8, device="cuda")
     for _ in range(3):  # first-use costs: buffer growth, code object load
-        crate.render(width, height, out=out)
+        crate.render(width, height, out=out, **kw)
     torch.cuda.synchronize()
     times = []
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(stream)
-        crate.render(width, height, out=out)
+        crate.render(width, height, out=out, **kw)
         b.record(stream)
         b.synchronize()
         times.append(1000.0 * a.elapsed_time(b))
     crate.engine.use_own_stream()
-    times.sort()
-    return {"median_us": round(times[len(times) // 2], 2), "min_us": round(times[0], 2)}
+    return times
+
+
+def time_render(crate, width, height, reps):
+    return stats(device_times(crate, width, height, reps))
+
+
+def wall_times(call, reps):
+    """Host wall time of a call that ends in a device synchronise."""
+    import time
+    for _ in range(3):
+        call()
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        times.append(1e6 * (time.perf_counter() - t0))
+    return times
+
+
+def hud_report(reps):
+    import numpy as np
+    import sand_crate_amd as sc
+    side = 1000
+    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
+    crate.show_forces()
+    for _ in range(200):
+        crate.physics_tick()
+    crate.synchronize()
+    has_hud = hasattr(crate.engine, "set_hud")
+    text = crate.debug_prints
+    lines = text.split("\n")
+    head = {"scene": "wave_machine", "ticks": 200, "particles": crate.particle_count, "frame": f"{side}x{side}"}
+    print(json.dumps({**head, "hud_bytes": len(text), "hud_lines": len(lines), "hud_longest_line": max(map(len, lines)),
+                      "hud_available": has_hud}), flush=True)
+    cases = {
+        "render": ("device", lambda **kw: device_times(crate, side, side, reps, **kw)),
+        "render_jpeg": ("wall", lambda **kw: wall_times(lambda: crate.render_jpeg(side, side, **kw), reps)),
+        "render_gif": ("wall", lambda **kw: wall_times(lambda: crate.render_gif(side, side, **kw), reps)),
+    }
+    for name, (clock, measure) in cases.items():
+        got = {False: [], True: []}
+        for rnd in range(2):
+            for hud in ((False, True) if has_hud else (False,)):
+                times = measure(**({"hud": True} if hud else {}))
+                got[hud] += times
+                print(json.dumps({**head, "case": name, "hud": hud, "round": rnd, "clock": clock, **stats(times)}), flush=True)
+        if has_hud:
+            off, on = stats(got[False])["median_us"], stats(got[True])["median_us"]
+            print(json.dumps({**head, "case": name, "hud_added_us": round(on - off, 2), "off_median_us": off,
+                              "on_median_us": on}), flush=True)
+    try:
+        from PIL import Image, ImageDraw
+    except ImportError:
+        print(json.dumps({**head, "case": "host HUD (download + PIL text + upload)", "skipped": "PIL is not installed"}))
+        return
+    import torch
+
+    def host_hud():
+        frame = crate.render(side, side)
+        image = Image.fromarray(frame, "RGB")
+        ImageDraw.Draw(image).multiline_text((6, 6), text, fill=(255, 255, 255))
+        dev = torch.from_numpy(np.array(image)).cuda()
+        torch.cuda.synchronize()
+        return dev
+
+    plain = stats(wall_times(lambda: crate.render(side, side), reps))
+    whole = stats(wall_times(host_hud, reps))
+    print(json.dumps({**head, "case": "host HUD (download + PIL text + upload)", "clock": "wall", **whole,
+                      "render_to_host_median_us": plain["median_us"],
+                      "added_over_device_frame_us": round(whole["median_us"] - stats(device_times(crate, side, side, reps))["median_us"], 2)}),
+          flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--hud", action="store_true", help="measure the HUD overlay instead (see above)")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
+    if args.hud:
+        hud_report(args.reps)
+        return
     import bench
     import sand_crate_amd as sc
 

@@ -1,0 +1,260 @@
+"""GPU tests of the HUD overlay (sc_set_hud, `Engine.set_hud`, the `hud=` argument of `Crate.render`, `render_jpeg` and
+`render_gif`, `main --hud`): a frame with a HUD equals tests/text_spec.py's `draw` of the frame without one bit for bit,
+its JPEG and GIF equal tests/jpeg_spec.py and tests/gif_spec.py of that frame byte for byte, clearing brings the plain
+frame back, and drawing changes nothing in the simulation."""
+import copy
+from pathlib import Path
+
+import numpy as np
+import pytest
+import yaml
+
+import gif_spec as G
+import hud_cases as K
+import jpeg_spec as J
+import text_spec as T
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+CASES = K.cases()
+VIEW = dict(segment_width=20)  # thick walls: the frame's edge is white ten pixels deep, under the text's first columns
+
+
+@pytest.fixture(scope="module")
+def sc():
+    import sand_crate_amd
+    return sand_crate_amd
+
+
+def scene(sc, name):
+    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
+
+
+@pytest.fixture(scope="module")
+def crate(sc):
+    """400 particles all over the wave_machine world after one tick (so they have pressures), discs of a few pixels
+    at the frame sizes used here."""
+    n = 400
+    wc = copy.deepcopy(scene(sc, "wave_machine"))
+    d = float(np.sqrt(12.0 / (np.pi * n)))
+    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
+    wc.particle_sources = []
+    rs = np.random.RandomState(77)
+    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
+    crate.particles = rs.rand(n, 2) * 0.96 + 0.02
+    crate.particle_velocities = (rs.rand(n, 2) - 0.5) * 0.1
+    crate.physics_tick()
+    return crate
+
+
+@pytest.fixture(scope="module")
+def plain(crate):
+    """The frames without a HUD, taken before any HUD was set, at every size used here."""
+    sizes = {(c.width, c.height) for c in CASES.values()} | {(64, 48), (61, 37), (96, 80)}
+    frames = {size: crate.render(*size, **VIEW) for size in sorted(sizes)}
+    for f in frames.values():
+        f.setflags(write=False)
+    return frames
+
+
+def same(got: bytes, want: bytes):
+    if got != want:
+        n = min(len(got), len(want))
+        first = next((k for k in range(n) if got[k] != want[k]), n)
+        raise AssertionError(f"{len(got)} bytes vs {len(want)}, first difference at byte {first}")
+
+
+def same_frame(got, want):
+    assert got.shape == want.shape and got.dtype == want.dtype
+    if not np.array_equal(got, want):
+        bad = np.argwhere((got != want).any(axis=-1))
+        raise AssertionError(f"{len(bad)} pixels differ, the first at row {bad[0][0]}, column {bad[0][1]}")
+
+
+def test_the_scene_puts_something_under_the_text(plain):
+    c = CASES["cut"]
+    frame = plain[(c.width, c.height)]
+    ink = T.ink(c.text, c.x, c.y, c.scale, c.width, c.height)
+    assert ink[9, 6] and (frame[9, 6] == 255).all() and (frame[:10, :10] == 255).all()  # a wall under the first `T`
+    under = frame[ink]
+    coloured = (under[:, 2] == 255) & (under[:, 0] < 255)
+    assert coloured.any() and len(np.unique(under, axis=0)) > 2  # discs of several pressures
+    box = (slice(c.y, c.y + c.box[1]), slice(c.x, c.x + c.box[0]))
+    assert (frame[box][~ink[box]] != 0).any()  # ... and next to the ink, where the overlay must leave them alone
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_every_case(crate, plain, name):
+    c = CASES[name]
+    base = plain[(c.width, c.height)]
+    eng = crate.engine
+    eng.set_hud(c.text, c.x, c.y, c.scale)
+    try:
+        got = crate.render(c.width, c.height, **VIEW)
+        data = crate.render_gif(c.width, c.height, **VIEW)
+    finally:
+        eng.set_hud(None)
+    want = T.draw(base, c.text, c.x, c.y, c.scale)
+    same_frame(got, want)
+    same(data, G.image_data(G.indices(want)))
+    if c.box == (0, 0):
+        same_frame(got, base)
+    same_frame(crate.render(c.width, c.height, **VIEW), base)  # cleared
+
+
+def test_unaligned_device_frame(crate, plain):
+    """61 x 37 into a tensor that starts one byte past a 4-byte boundary (sc_render_device)."""
+    import torch
+    c = CASES["odd"]
+    w, h = c.width, c.height
+    buf = torch.zeros(3 * w * h + 8, dtype=torch.uint8, device="cuda")
+    out = buf[1:1 + 3 * w * h].view(h, w, 3)
+    assert out.data_ptr() % 4 == 1 and out.is_contiguous()
+    torch.cuda.synchronize()
+    text = c.text.decode()
+    assert crate.render(w, h, out=out, hud=text, **VIEW) is out
+    crate.synchronize()
+    same_frame(out.cpu().numpy(), T.draw(plain[(w, h)], c.text, 6, 6, 1))
+    got = buf.cpu().numpy()
+    assert got[0] == 0 and not got[1 + 3 * w * h:].any()  # nothing outside the frame
+    assert crate.render(w, h, out=out, **VIEW) is out  # and without: the plain frame again
+    crate.synchronize()
+    same_frame(out.cpu().numpy(), plain[(w, h)])
+
+
+def test_render_gif_with_hud(crate, plain):
+    c = CASES["cut"]
+    w, h = c.width, c.height
+    text = c.text.decode()
+    want = G.indices(T.draw(plain[(w, h)], c.text, 6, 6, 1))
+    data = crate.render_gif(w, h, hud=text, **VIEW)
+    same(data, G.image_data(want))
+    frames, _, _, _ = G.decode(G.header(w, h) + G.frame(w, h, data) + b"\x3B")
+    ink = T.ink(c.text, 6, 6, 1, w, h)
+    assert (frames[0][ink] == 255).all()
+    assert np.array_equal(frames[0] == 255, ink | (G.indices(plain[(w, h)]) == 255))  # index 255: the ink and the walls
+    same(crate.render_gif(w, h, **VIEW), G.image_data(G.indices(plain[(w, h)])))
+
+
+def test_render_jpeg_with_hud(crate, plain):
+    c = CASES["odd"]
+    w, h = c.width, c.height
+    for q in (95, 50):
+        same(crate.render_jpeg(w, h, quality=q, hud=c.text.decode(), **VIEW),
+             J.encode(T.draw(plain[(w, h)], c.text, 6, 6, 1), q))
+    same(crate.render_jpeg(w, h, **VIEW), J.encode(plain[(w, h)], 95))
+
+
+def test_hud_true_draws_debug_prints(sc):
+    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate.show_forces()
+    for _ in range(5):
+        crate.physics_tick()
+    text = crate.debug_prints
+    assert text.startswith("Tick: 5\n") and "Forces" in text and "viscosity" in text
+    for w, h in ((200, 150), (1440, 90)):  # scale 1, and scale 2 from 1440 pixels up
+        base = crate.render(w, h)
+        got = crate.render(w, h, hud=True)
+        want = T.draw(base, text.encode("ascii", "replace"), 6, 6, T.default_scale(w))
+        same_frame(got, want)
+        assert (got != base).any()
+        same_frame(crate.render(w, h), base)
+    assert T.default_scale(1440) == 2
+    crate.physics_tick()  # the text follows the tick
+    base = crate.render(200, 150)
+    assert crate.debug_prints.startswith("Tick: 6\n")
+    same_frame(crate.render(200, 150, hud=True), T.draw(base, crate.debug_prints.encode("ascii", "replace"), 6, 6, 1))
+
+
+def test_drawing_is_read_only(sc):
+    def trajectory(draw):
+        crate = sc.Crate(scene(sc, "wave_machine"))
+        for _ in range(20):
+            crate.physics_tick()
+            if draw:
+                before = crate.engine.download(), crate.engine.rng_get_state()
+                crate.render(160, 120, hud=True)
+                crate.render_gif(100, 130, zoom=3.0, center=(20.0, 100.0), hud="a\nbc")
+                crate.render_jpeg(96, 64, hud=True)
+                after = crate.engine.download(), crate.engine.rng_get_state()
+                for x, y in zip(before[0], after[0]):
+                    assert np.array_equal(x, y)
+                assert np.array_equal(before[1][0], after[1][0]) and before[1][1] == after[1][1]
+        assert crate.tick == 20
+        return (*crate.engine.download(), crate.engine.rng_get_state())
+
+    a, b = trajectory(False), trajectory(True)
+    for x, y in zip(a[:4], b[:4]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a[4][0], b[4][0]) and a[4][1] == b[4][1]
+
+
+def test_argument_errors(crate, plain):
+    from sand_crate_amd import _native as N
+    eng = crate.engine
+    lib, ctx = eng._lib, eng._ctx
+    text = b"ok"
+
+    def call(t=text, n=len(text), x=6, y=6, scale=1, ctx=ctx):
+        return lib.sc_set_hud(ctx, t, n, x, y, scale)
+
+    big = b"x" * 65537
+    for bad in (dict(n=-1), dict(t=big, n=65537), dict(t=None), dict(x=-1), dict(x=16385), dict(y=-1), dict(y=16385),
+                dict(scale=0), dict(scale=65), dict(scale=-3), dict(ctx=None), dict(t=None, n=0, scale=0)):
+        assert call(**bad) == N.ERR_ARG, bad
+        assert lib.sc_last_error()
+    with pytest.raises(N.NativeError) as err:
+        eng.set_hud(b"ok", scale=0)
+    assert err.value.code == N.ERR_ARG
+    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # none of them set anything
+    # the edges of the ranges are valid, and a valid call afterwards works
+    assert call(t=big, n=65536, x=16384, y=16384, scale=64) == 0
+    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # (an origin outside the frame)
+    assert call(x=0, y=0) == 0
+    same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))
+    assert call(x=-1) == N.ERR_ARG
+    same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))  # a refused call changes nothing
+    assert call(t=None, n=0) == 0  # clears; the text may be null
+    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])
+
+
+def test_a_new_context_has_no_hud(sc, crate):
+    crate.engine.set_hud(b"one context's text")
+    try:
+        other = sc.Engine(capacity=16)
+        view = other.view(64, 48, 0.01)
+        assert not other.render(view, np.zeros((0, 2, 2))).any()
+        other.close()
+    finally:
+        crate.engine.set_hud(None)
+
+
+def small_screen_config(tmp_path, width=160, height=120) -> Path:
+    with open(ROOT / "config" / "wave_machine.yaml") as f:
+        cfg = yaml.safe_load(f)
+    cfg["playback"].update(screen_x=width, screen_y=height)
+    path = tmp_path / "small_screen.yaml"
+    with open(path, "w") as f:
+        yaml.safe_dump(cfg, f)
+    return path
+
+
+def test_headless_driver_with_hud(tmp_path):
+    from sand_crate_amd.main import main
+    cfg = small_screen_config(tmp_path)
+    first = {}
+    for hud in (False, True):
+        out = tmp_path / ("hud" if hud else "plain")
+        main(cfg, out, variants=1, ticks=20, record_every=10, gif=True, hud=hud)
+        frames, pal, _, _ = G.decode((out / "variant_00" / "video.gif").read_bytes())
+        assert len(frames) == 2 and np.array_equal(pal, G.palette())
+        first[hud] = frames[0]
+    # the top left: "Tick: 10" in the first line, "Particles: ..." in the second, where no particle has got to yet
+    ink = T.ink(b"Tick: 10", 6, 6, 1, 160, 120)
+    line = (slice(6, 24), slice(6, 100))
+    assert not (first[False][line] == 255).any() and np.array_equal(first[True][line] == 255, ink[line])
+    below = (slice(24, 42), slice(6, 6 + 8 * 10))
+    assert not (first[False][below] == 255).any() and (first[True][below] == 255).any()
+    changed = first[True] != first[False]
+    assert not changed[:6].any() and not changed[:, :6].any()
