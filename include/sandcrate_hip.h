@@ -203,7 +203,13 @@ const char* sc_kernel_name(int index);
  * grid columns [col_lo, col_hi), column = floor(x / diameter) of the position a particle has when
  * the tick starts.  Particles within `halo` columns outside the slab are ghosts: they take part in
  * the wall fix, the neighbor search and pass A exactly like owned particles, are never integrated,
- * and are dropped at the end of the tick.  Ids are global (sc_upload_state_ids), so tie-breaks and
+ * and are dropped at the end of the tick.  Three columns reach all an owned particle needs as long as no hard wall
+ * fix exceeds one radius along the slab axis (one contact never does; a joint of two segments can).  A fix that does,
+ * on an owned particle that is put at least half a column beyond the slab's edge, or comes from beyond the band to
+ * less than 2.5 columns from the edge, is reported: SC_ERR_DOMAIN at the next synchronising call.
+ * A particle that crosses a whole slab in one tick -- sc_halo_unpack finds a record from the left beyond the slab's
+ * right edge, or the mirror image -- belongs to a slab that never receives it: reported the same way.
+ * Ids are global (sc_upload_state_ids), so tie-breaks and
  * the counter-based noise are the same as on one GPU.  Not available with SC_NOISE_HOST.
  *
  * Per tick:  sc_halo_pack -> exchange the two buffers with the neighbors (RCCL send/recv on

@@ -506,6 +506,7 @@ WallInputs wall_inputs_of(const World& w) {
   k.r = w.r; k.d = w.d; k.inv_d = w.inv_d; k.lo = w.lo; k.hi = w.hi; k.t_wall = w.t_wall; k.touch_box = w.touch_box; k.far_box = w.far_box;
   k.row0 = w.row0; k.col0 = w.col0; k.row0d = w.row0d; k.col0d = w.col0d; k.own_lo = w.own_lo; k.own_hi = w.own_hi;
   k.nrows = w.nrows; k.ncols = w.ncols; k.nseg = w.nseg; k.nbody = w.nbody; k.slab = w.slab; k.slab_axis = w.slab_axis;
+  k.halo = w.halo; k.has_left = w.has_left; k.has_right = w.has_right;
   std::memcpy(k.seg, w.seg, sizeof k.seg);
   std::memcpy(k.body, w.body, sizeof k.body);
   return k;
@@ -532,6 +533,13 @@ int check_flags(int flags) {
   if (flags & F_HALO_LATE)
     return fail(SC_ERR_DOMAIN, "a particle moved more than the band margin (%d columns / %d rows) in one tick and missed the "
                 "overlapped halo message: run without halo overlap", kBandMarginColumns, kBandMarginRows);
+  if (flags & F_HALO_CROSSED)
+    return fail(SC_ERR_DOMAIN, "a particle crossed a whole slab in one tick: the slab it is in now never received it; it was "
+                "dropped (use fewer, wider slabs or a shorter dt)");
+  if (flags & F_HALO_REACH)
+    return fail(SC_ERR_DOMAIN, "the hard wall fix moved a particle next to a slab cut by more than one radius along the slab "
+                "axis (several wall contacts at once, as at a joint of two segments): the ghost band of three columns / rows "
+                "may not have reached all it needs; place the cuts away from such joints");
   return SC_OK;
 }
 
@@ -1862,8 +1870,9 @@ int sc_halo_unpack(sc_ctx* c, const double* from_left, int64_t left_records, con
                        c->counters, c->x, c->y, c->vx, c->vy, c->id[0], (int)c->cap, c->haloL, c->haloR,
                        c->promised, c->cellS, c->wslotS, c->cellCount, c->wrec[c->tick & 1], ring);
   } else {
-    WallInputs none;
-    std::memset(&none, 0, sizeof none);
+    const int rc = make_world(c);  // (the slab and the diameter the records are judged by)
+    if (rc) return rc;
+    const WallInputs none = wall_inputs_of(c->w);
     hipLaunchKernelGGL(k_halo_unpack<false>, grid, block, 0, c->stream, from_left, from_right, capL, capR,
                        c->counters, c->x, c->y, c->vx, c->vy, c->id[0], (int)c->cap, c->haloL, c->haloR, none,
                        c->cellS, c->wslotS, c->cellCount, c->wrec[c->tick & 1], ring);

@@ -83,6 +83,7 @@ struct WallInputs {
   double r, d, inv_d, lo, hi, t_wall, touch_box, far_box, row0d, col0d;
   long long row0, col0, own_lo, own_hi;
   int nrows, ncols, nseg, nbody, slab, slab_axis;
+  int halo, has_left, has_right;  // (the reach check of the wall fix: F_HALO_REACH)
   Seg seg[kMaxSeg];
   BodyK body[kMaxBody];
 };
@@ -108,7 +109,8 @@ enum Counter {
   C_ALLOC = 96
 };
 
-enum Flag { F_OUT_OF_GRID = 1, F_NAN = 2, F_HALO_OVERFLOW = 4, F_CAPACITY = 8, F_HALO_LATE = 16, F_BAND_TIMEOUT = 32, F_SCAN_TIMEOUT = 64 };
+enum Flag { F_OUT_OF_GRID = 1, F_NAN = 2, F_HALO_OVERFLOW = 4, F_CAPACITY = 8, F_HALO_LATE = 16, F_BAND_TIMEOUT = 32, F_SCAN_TIMEOUT = 64,
+            F_HALO_REACH = 128, F_HALO_CROSSED = 256 };
 
 // columns / rows a particle may move in one tick and still be packed in time (halo overlap).  With slabs of rows the
 // band blocks are few whatever the margin; with columns every row has them, and each column of margin adds as many.

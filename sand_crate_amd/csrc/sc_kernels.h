@@ -84,8 +84,9 @@ __device__ __forceinline__ int wall_and_cell(const W& w, double& px, double& py,
   wslot = -1;
   if (px < w.lo || px > w.hi || py < w.lo || py > w.hi) return -1;  // crate.py:152 (dead ghosts carry x = +inf)
   bool ghost = false;
+  long long col = 0;  // slab mode: the column (row) of the position the tick starts with
   if (w.slab) {
-    long long col = (long long)floor((w.slab_axis ? py : px) / w.d);
+    col = (long long)floor((w.slab_axis ? py : px) / w.d);
     ghost = col < w.own_lo || col >= w.own_hi;
   }
   // bounding-box reject (exact-safe: the boxes are inflated far beyond rounding error)
@@ -157,6 +158,19 @@ __device__ __forceinline__ int wall_and_cell(const W& w, double& px, double& py,
       }
       px += fx;  // crate.py:211
       py += fy;
+      // Slabs: three ghost columns reach every neighbor's neighbor as long as no fix exceeds r along the slab axis (one
+      // contact stays below r; a joint of two segments pushes twice).  An owner i then misses a particle m only if
+      // f_i - f_m > d, and then (slab.py, "Ghost band") either i was put at least half a column beyond its slab's edge or m
+      // came from the fourth column or beyond to less than 2.5 columns from the edge.  Either is seen by the particle's
+      // OWNER from the fix it got (0.01 d of margin for the rounding): flagged, never silently wrong.
+      const double fa = w.slab_axis ? fy : fx;
+      if (w.slab && !ghost && fabs(fa) > w.r) {
+        const double pa = w.slab_axis ? py : px;
+        const double hi = (double)w.own_hi, lo = (double)w.own_lo, h = (double)w.halo;
+        if ((fa > 0 && w.has_right && (pa > (hi + 0.49) * w.d || (col < w.own_hi - w.halo && pa > (hi - h + 0.49) * w.d))) ||
+            (fa < 0 && w.has_left && (pa < (lo - 0.49) * w.d || (col >= w.own_lo + w.halo && pa < (lo + h - 0.49) * w.d))))
+          atomicOr(&counters[C_FLAGS], F_HALO_REACH);
+      }
       wslot = rec;
       double* out = wrec + 5 * (size_t)rec;
       out[0] = Ux;
@@ -1164,7 +1178,8 @@ __global__ void __launch_bounds__(kBlock)
 // particles): the stored count is the sorted count of that tick, nobody changes it, and the appended
 // particles get their K1 here.
 // `capL` / `capR`: records the transport actually moved from the left / right (the agreed message sizes of
-// sc_halo_sizes).  A header that announces more means records were cut off: F_HALO_OVERFLOW.  `ring`: the four
+// sc_halo_sizes).  A header that announces more means records were cut off: F_HALO_OVERFLOW.  `wn`: the coming tick's slab
+// (and, FUSED, all of its wall inputs).  `ring`: the four
 // counts of this tick (sent left, sent right, received from the left, from the right) are published in
 // host-mapped memory, slot tick % kHaloRing, for the message sizes of a later tick.
 template <bool FUSED>
@@ -1185,6 +1200,13 @@ __global__ void __launch_bounds__(kBlock)
       atomicOr(&counters[C_FLAGS], F_CAPACITY);
     } else {
       double px = r[0], py = r[1];
+      // A record from the left that lies beyond this slab's right edge (or the mirror image) crossed the whole slab in one
+      // tick: its sender has given it up, here it is a ghost at best, and the slab it is in never hears of it.
+      if (fabs(px) < 1e300) {
+        const double col = floor((wn.slab_axis ? py : px) / wn.d);
+        if (k < nl ? (wn.has_right && col >= (double)wn.own_hi) : (wn.has_left && col < (double)wn.own_lo))
+          atomicOr(&counters[C_FLAGS], F_HALO_CROSSED);
+      }
       if (FUSED) {
         int wsn = -1;
         cnext = wall_and_cell(wn, px, py, wsn, counters, base + k, wrec_next);

@@ -11,16 +11,27 @@ Decomposition
     (with columns a third of the force kernel's blocks hold band particles and its split into two launches costs
     ~25 us per tick at a million particles; bench.py uses rows: its window is the uniform start of the workload).
 Ghost band
-    3 columns on each side.  Interaction range is one diameter after the hard wall fix, which moves
-    a particle by at most 0.1 d per wall contact, and pass B needs pressure and surface normal of
-    the neighbors of owned particles, which need THEIR neighbors: 2 x 1.2 d = 2.4 d < 3 columns.
+    3 columns on each side.  Interaction range is one diameter AFTER the hard wall fix, and pass B needs pressure and
+    surface normal of the neighbors j of an owned particle i, which need THEIR neighbors k: before the fix i and k are
+    up to 2 d + f_i - f_k apart along the slab axis, f being each one's fix.  One wall contact sets a particle to distance
+    r from the wall: |f| < r, the span stays strictly below 3 d and three columns suffice -- only just (the tight case).
+    But every touching segment is a contact of its own: at a joint of two segments the fix doubles, up to d, and with a
+    joint on either side the span reaches 4 d.  What is then missed:  i owned left of the cut H (x_i < H d), m not sent
+    (x_m >= (H + 3) d), after the fix at most 2 d apart, so f_i - f_m > d.  Either f_m >= -r: then i was put at
+    (H + 0.5) d or beyond; or f_i <= r: then m was put below (H + 2.5) d; if neither held they would end more than 2 d
+    apart.  Both are seen by the particle's OWNER from the fix it applied (m's owner lies right of H; were it not the
+    next slab, m would have crossed that owner's own edge by far more than half a column), mirrored at a slab's left
+    edge: the wall pass raises F_HALO_REACH there, SC_ERR_DOMAIN at the next synchronising call -- reported, never
+    silently wrong.  The report can be needless: the lists that would tell do not exist yet.
 Per tick
     pack (device) -> one fixed-size message to each neighbor (RCCL send/recv over xGMI when the
     process group is NCCL; staged through the host for gloo) -> unpack (device) -> the ordinary tick.
     A record is (x, y, vx, vy, id); record 0 of a message is the count, so the host never needs to
     know how many particles cross.  A particle that has left its slab is in the message too and is
     owned by the receiver from then on (migration rides the halo message).  There is no other
-    collective on the data path.
+    collective on the data path.  A particle that crosses a WHOLE slab in one tick (eight columns at the least) reaches
+    only the sender's neighbor, not its new owner: the unpack kernel sees a record from the left beyond its own right edge,
+    or the mirror image, and raises F_HALO_CROSSED (SC_ERR_DOMAIN) -- never a silently smaller particle count.
 Message sizes
     a message carries the records its direction had six ticks earlier plus headroom, not the whole buffer
     (Engine.halo_sizes: sender and receiver derive the size from the same published count, nothing synchronises).
@@ -320,12 +331,16 @@ class SlabCrate:
         self.axis = axis
         cols = column_of(p[:, 1 if axis == "y" else 0], d)
         # (a scene that starts empty -- the YAML scenes do, their sources fill them -- is cut into equal widths of the box)
-        self.slabs = partition_columns(cols if len(cols) else np.arange(0, int(math.ceil(1.0 / d)) + 1, dtype=np.int64), self.world)
-        if cuts is not None:  # the caller's cut columns instead of the equal-count ones
+        # The caller's cut columns instead of the equal-count ones.  partition_columns is not asked then: it refuses a
+        # state whose particles span fewer than world * (2 * halo + 2) columns, which says nothing about cuts that were
+        # not derived from the particles -- the outer slabs are open-ended, so the cuts need only their count and spacing.
+        if cuts is not None:
             if len(cuts) != self.world - 1 or any(b - a < 2 * HALO_COLUMNS + 2 for a, b in zip(cuts[:-1], cuts[1:])):
                 raise ValueError("cuts: world - 1 increasing columns, at least 2 * halo + 2 apart")
             bounds = [-2 ** 40] + [int(c) for c in cuts] + [2 ** 40]
             self.slabs = [(bounds[k], bounds[k + 1]) for k in range(self.world)]
+        else:
+            self.slabs = partition_columns(cols if len(cols) else np.arange(0, int(math.ceil(1.0 / d)) + 1, dtype=np.int64), self.world)
         self.lo, self.hi = self.slabs[self.rank]
         own = (cols >= self.lo) & (cols < self.hi)
         ids = np.flatnonzero(own).astype(np.int64)

@@ -143,7 +143,9 @@ def test_scene_with_its_particle_source_under_slabs(tmp_path, axis):
     assert np.array_equal(got["pressure"], pr)
 
 
-@pytest.mark.parametrize("nproc,per_gpu,extra", [(2, 1500, ()), (8, 3000, ("--steps", "103"))])
+# (8 ranks: 6000 particles each make slabs of 14 rows.  At 3000 they were 10 rows wide, and in tick 63 a particle thrown out of
+# the corner at 58 d / dt crossed one of them whole -- lost without a word then, F_HALO_CROSSED now.)
+@pytest.mark.parametrize("nproc,per_gpu,extra", [(2, 1500, ()), (8, 6000, ("--steps", "103"))])
 def test_bench_multi_gpu_path_on_cpu(nproc, per_gpu, extra, tmp_path):
     """bench.py's own N > 1 driver code (the path the driver's 2-, 4- and 8-GPU runs take: slabs of rows, halo overlap
     requested, torch.distributed transport as the fallback, repetitions through `reload`, the outputs gathered from
