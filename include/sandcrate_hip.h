@@ -413,6 +413,34 @@ int sc_render_gif(sc_ctx* ctx, const sc_view* view, const double* segments, int3
  * outside 1..64; the HUD is then what it was. */
 int sc_set_hud(sc_ctx* ctx, const char* text, int32_t n_bytes, int32_t x, int32_t y, int32_t scale);
 
+/* Debug arrows: the layer the reference's viewer draws between the walls and the HUD text (Playback.draw_debug_arrows,
+ * playback.py:95-107).  From this call on every frame made by sc_render, sc_render_device, sc_render_jpeg and
+ * sc_render_gif carries the arrows in green -- (0, 255, 0), palette index 1 -- drawn over the discs and walls after
+ * resolve, before the HUD text and before an encoder reads the frame.  An arrow runs from `start` to `end`, both in world
+ * units and mapped to the screen as the walls' ends are (not floored): a body two pixels wide that stops two pixels
+ * before `end` and a head four pixels wide with its tip on `end`, pygame_utils.draw_arrow with the viewer's sizes;
+ * shorter than two pixels it is the head alone.  An arrow with a number that is not finite, or whose ends fall on the
+ * same screen point, draws nothing; pixels outside the frame are dropped.  tests/arrow_spec.py is the pixel rule, bit
+ * for bit.
+ *   SC_ARROWS_OFF       none.  A new context has none.
+ *   SC_ARROWS_LIST      the `n` arrows at `arrows`, 0..1,048,576 of them; n == 0 is SC_ARROWS_OFF.  The list is copied.
+ *   SC_ARROWS_VELOCITY  nothing is uploaded: one arrow for every stored live particle whose id is a multiple of `every`
+ *                       (>= 1), as of the frame's own time: from its position p to p + d / (|d| + 0.001)^0.3 with
+ *                       d = velocity * scale (`scale` finite), the compression of playback.py:99, computed on the device
+ *                       (its pow may differ from the host's in the last bits).  Positions and velocities are those
+ *                       sc_download_state returns; particles that are not finite (the dead ghost copies of slab mode
+ *                       among them) are skipped.
+ * While arrows are set, sc_render_gif stores a disc of colour byte c as palette index max(c, 2) instead of max(c, 1):
+ * index 1 is the arrows', and a GIF's colour table needs (0, 255, 0) there (gif.py: palette(arrows=True)).
+ * Synchronises the context's stream: frames enqueued before the call keep the arrows they were enqueued with.  Like
+ * rendering it leaves the simulation alone.  SC_ERR_ARG for an unknown mode, n outside 0..1,048,576, a null list with n > 0,
+ * every < 1 or a scale that is not finite -- each checked in every mode, so SC_ARROWS_OFF is (ctx, SC_ARROWS_OFF, NULL, 0,
+ * 1.0, 1); the arrows are then what they were.
+ * SC_ERR_STATE between sc_step_begin and sc_step_finish. */
+typedef struct sc_arrow { double start_x, start_y, end_x, end_y; } sc_arrow;   /* world units */
+enum { SC_ARROWS_OFF = 0, SC_ARROWS_LIST = 1, SC_ARROWS_VELOCITY = 2 };
+int sc_set_arrows(sc_ctx* ctx, int32_t mode, const sc_arrow* arrows, int64_t n, double scale, int64_t every);
+
 /* Synchronises.  Live particles stored in this context (dead ghost copies excluded); summed over
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);

@@ -16,6 +16,8 @@ MAX_SEGMENTS = 16
 MAX_BODIES = 8
 NUM_KERNELS = 12
 NOISE_NONE, NOISE_HOST, NOISE_COUNTER = 0, 1, 2
+ARROWS_OFF, ARROWS_LIST, ARROWS_VELOCITY = 0, 1, 2
+MAX_ARROWS = 1 << 20
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -55,6 +57,10 @@ class View(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("zoom", C.c_double), ("center_x", C.c_double),
                 ("center_y", C.c_double), ("particle_radius", C.c_double), ("segment_width", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class Arrow(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("start_x", "start_y", "end_x", "end_y")]
 
 
 class Stats(C.Structure):
@@ -138,6 +144,7 @@ SIGNATURES = {
     "sc_gif_encode_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "sc_render_gif": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "sc_set_hud": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sc_set_arrows": (C.c_int, [_P, C.c_int32, C.POINTER(Arrow), C.c_int64, C.c_double, C.c_int64]),
 }
 
 _lib = None

@@ -81,6 +81,19 @@ def tick_geometry(rigid_bodies, particle_radius, cache):
     return seg, np.concatenate(plus + minus), bodies
 
 
+def arrow_ends(pairs) -> np.ndarray:
+    """K x 2 x 2 (start, end) of the reference's debug arrows, an array-like K x 2 x 2 of (start, direction), as
+    Playback.draw_debug_arrows draws them (playback.py:95-107): entries with a NaN are dropped (:97), the direction is
+    compressed, d / (|d| + 0.001) ^ 0.3 (:99), and the arrow ends at start + that."""
+    a = np.asarray(pairs, dtype=np.float64).reshape(-1, 2, 2)
+    a = a[~np.isnan(a).any(axis=(1, 2))]
+    start, d = a[:, 0], a[:, 1]
+    with np.errstate(all="ignore"):
+        norm = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+        d = d / np.power(norm + 0.001, 0.3)[:, None]
+        return np.stack([start, start + d], axis=1)
+
+
 class Crate:
     def __init__(self, world_config: WorldConfig, *, device: int = 0, noise: str = "host", noise_seed: int = 0,
                  capacity: int | None = None) -> None:
@@ -116,6 +129,7 @@ class Crate:
         self._force_ema = {}
         self._pending_checkpoint = None
         self._hud_sent = None      # (text bytes, x, y, scale) the engine draws on frames, or None: no HUD
+        self._arrows_sent = None   # ("list", bytes of the K x 2 x 2 ends) or ("velocity", scale, every), or None: no arrows
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -219,6 +233,7 @@ class Crate:
         self._engine = Engine(int(needed * 1.5) + 1024, device=old.device)
         self._engine.set_noise_mode(_NOISE_MODES[self._noise], self._noise_seed)
         self._hud_sent = None  # (a new context has no HUD)
+        self._arrows_sent = None  # (... and no arrows)
         if rng is not None:
             self._engine.rng_set_state(*rng)
         old.close()
@@ -308,8 +323,42 @@ class Crate:
                 self._engine.set_hud(*want)
             self._hud_sent = want
 
+    def _set_arrows(self, arrows, every: int, scale) -> None:
+        """The `arrows`, `arrow_every` and `arrow_scale` arguments of `render`, `render_jpeg` and `render_gif`: the debug
+        arrows of Playback.draw_debug_arrows (playback.py:95-107), green, over the walls and under the HUD text.  None or
+        False draws none; True draws `debug_arrows`, the reference's list of (start, direction) in world units; an
+        array-like K x 2 x 2 of (start, direction) is drawn the same way (`arrow_ends`: NaN entries dropped, the
+        direction compressed on the host); "velocity" draws, without downloading anything, one arrow for every particle
+        whose index is a multiple of `every`, along velocity * `scale` compressed the same way on the device -- `scale`
+        defaults to `dt`, the step the particle is about to take.  Anything else is a TypeError.  The engine is told only
+        when the request changed since the last frame."""
+        want = None
+        if arrows is None or arrows is False:
+            pass
+        elif isinstance(arrows, str):
+            if arrows != "velocity":
+                raise TypeError('arrows must be None, a bool, "velocity" or an array-like K x 2 x 2 of (start, direction)')
+            want = ("velocity", float(self.dt if scale is None else scale), int(every))
+        else:
+            try:
+                ends = arrow_ends(self.debug_arrows if arrows is True else arrows)
+            except (TypeError, ValueError):
+                raise TypeError('arrows must be None, a bool, "velocity" or an array-like K x 2 x 2 of (start, direction)') \
+                    from None
+            if len(ends):
+                want = ("list", ends.tobytes())
+        if want != getattr(self, "_arrows_sent", None):
+            self._arrows_sent = None
+            if want is None:
+                self._engine.set_arrows(N.ARROWS_OFF)
+            elif want[0] == "list":
+                self._engine.set_arrows(N.ARROWS_LIST, np.frombuffer(want[1], dtype=np.float64))
+            else:
+                self._engine.set_arrows(N.ARROWS_VELOCITY, None, want[1], want[2])
+            self._arrows_sent = want
+
     def render(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None, segment_width: int = 2,
-               out=None, hud=None):
+               out=None, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None):
         """The frame the reference's viewer draws after `physics_tick()`, rendered on the GPU: every particle a disc of
         ``int(width * particle_radius) * zoom`` pixels coloured by its pressure (white at 0, blue at 1 and above), the
         walls (`segments`) on top in white, black elsewhere; ``height x width x 3`` uint8, row 0 at the top.
@@ -321,35 +370,43 @@ class Crate:
         synchronising: the library's stream does not wait for torch's, so the tensor must be ready when this is called
         and read after `synchronize()` (or run the crate on torch's stream, `engine.set_stream`).  Otherwise it returns a
         NumPy array.  `hud=True` writes the HUD text (`debug_prints`) over the frame at the top left, `hud` a str that
-        string (`_set_hud`); telling the engine a new text synchronises.
-        The pixel rule, bit for bit: tests/render_spec.py, and tests/text_spec.py for the text."""
+        string (`_set_hud`); telling the engine a new text synchronises.  `arrows` draws the viewer's debug arrows
+        between the walls and the text: True the list `debug_arrows`, an array of (start, direction) that, "velocity" one
+        per `arrow_every`-th particle along its velocity times `arrow_scale` (`_set_arrows`).
+        The pixel rule, bit for bit: tests/render_spec.py, tests/arrow_spec.py for the arrows and tests/text_spec.py for
+        the text."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
         self._set_hud(hud, width)
+        self._set_arrows(arrows, arrow_every, arrow_scale)
         return self._engine.render(view, segments, out)
 
     def render_jpeg(self, width: int = 1000, height: int = 1000, *, quality: int = 95, zoom: float = 1.0, center=None,
-                    segment_width: int = 2, hud=None) -> bytes:
+                    segment_width: int = 2, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None) -> bytes:
         """`render`'s frame as a JPEG file, encoded on the GPU: only the compressed bytes leave it.  Baseline JPEG, 4:4:4,
-        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).  `hud` as
-        in `render`: the text is on the frame before it is encoded.
+        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).  `hud`,
+        `arrows`, `arrow_every` and `arrow_scale` as in `render`: text and arrows are on the frame before it is encoded.
         The bitstream, byte for byte: tests/jpeg_spec.py applied to `render`'s frame."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
         self._set_hud(hud, width)
+        self._set_arrows(arrows, arrow_every, arrow_scale)
         return self._engine.render_jpeg(view, segments, quality)
 
     def render_gif(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None,
-                   segment_width: int = 2, hud=None) -> bytes:
+                   segment_width: int = 2, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None) -> bytes:
         """`render`'s frame as the image data of one GIF frame, compressed on the GPU: only the LZW bytes leave it;
         `gif.GifWriter` strings such frames into ``video.gif``.  The frame has a GIF's worth of colours by construction
         -- black and (c, c, 255) -- so nothing is quantised: palette entry 0 is black, entry k is (k, k, 255).  The one
         loss: (0, 0, 255), a pressure of 1 and above, is stored as entry 1, (1, 1, 255).  `hud` as in `render`: the text
-        is white like the walls, entry 255.
+        is white like the walls, entry 255.  `arrows`, `arrow_every` and `arrow_scale` as in `render`: a frame with arrows
+        keeps entry 1 for them -- (0, 255, 0) in `gif.palette(arrows=True)` -- and stores a disc of colour byte c as
+        max(c, 2), so there (0, 0, 255) and (1, 1, 255) both become (2, 2, 255).
         The bitstream, byte for byte: tests/gif_spec.py (`image_data(indices(frame))`) applied to `render`'s frame."""
         view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
         segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
         self._set_hud(hud, width)
+        self._set_arrows(arrows, arrow_every, arrow_scale)
         return self._engine.render_gif(view, segments)
 
     # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "sandcrate_hip.h"
+#include "sc_arrows.h"
 #include "sc_gif.h"
 #include "sc_hud.h"
 #include "sc_jpeg.h"
@@ -203,6 +204,11 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   DevBuf<HudLine> hudLines;
   int hud_lines = 0, hud_longest = 0;  // ... how many lines, and the bytes of the longest
   int hud_x = 0, hud_y = 0, hud_scale = 1;
+  // sc_set_arrows: the arrows every rendered frame carries; SC_ARROWS_OFF: none
+  DevBuf<sc_arrow> arrowList;
+  int arrow_mode = SC_ARROWS_OFF;
+  int64_t arrow_n = 0, arrow_every = 1;  // ... the list's length; velocity mode: ids that are multiples of this
+  double arrow_scale = 1.0;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -1247,8 +1253,26 @@ static void hud_launch(sc_ctx* c, const RenderView& v, unsigned char* frame, boo
     hipLaunchKernelGGL(k_hud_overlay<false>, grid, dim3(kBlock), 0, c->stream, b, c->hudText, c->hudLines, frame);
 }
 
-// Grows the key buffer and enqueues splat, resolve and the HUD overlay into `rgb` (device memory), or with `as_index`
-// the resolve that writes one palette index per pixel into it (4-byte aligned).
+// Enqueues the arrow pass over a resolved frame: a wave per kArrowListPerWave arrows of the list, or a thread per slot
+// under the host's bound of the live count, or nothing at all when no arrows are set.
+static void arrows_launch(sc_ctx* c, const RenderView& v, unsigned char* frame, bool as_index) {
+  if (c->arrow_mode == SC_ARROWS_OFF) return;
+  const bool from_list = c->arrow_mode == SC_ARROWS_LIST;
+  const int64_t count = from_list ? c->arrow_n : std::min<int64_t>(launch_bound(c), c->cap);
+  if (count <= 0) return;
+  const ArrowView a{v.width, v.height, v.center_x, v.center_y, v.zoom, v.half_w, v.half_h, v.sx, v.sy};
+  const sc_arrow* list = from_list ? c->arrowList.get() : nullptr;
+  const int64_t threads = from_list ? (count + kArrowListPerWave - 1) / kArrowListPerWave * 64 : count;
+  if (as_index)
+    hipLaunchKernelGGL(k_arrows<true>, dim3(grid_for(threads)), dim3(kBlock), 0, c->stream, a, list, (int)count, c->counters,
+                       c->x, c->y, c->vx, c->vy, c->id[0], c->arrow_scale, (long long)c->arrow_every, frame);
+  else
+    hipLaunchKernelGGL(k_arrows<false>, dim3(grid_for(threads)), dim3(kBlock), 0, c->stream, a, list, (int)count, c->counters,
+                       c->x, c->y, c->vx, c->vy, c->id[0], c->arrow_scale, (long long)c->arrow_every, frame);
+}
+
+// Grows the key buffer and enqueues splat, resolve, the arrows and the HUD overlay into `rgb` (device memory), or with
+// `as_index` the resolve that writes one palette index per pixel into it (4-byte aligned).
 static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb, bool as_index = false) {
   const int64_t pixels = (int64_t)v.width * v.height;
   if (pixels > c->renderKeys.size()) {
@@ -1267,10 +1291,11 @@ static int render_launch(sc_ctx* c, const RenderView& v, unsigned char* rgb, boo
   }
   if (as_index)
     hipLaunchKernelGGL(k_render_resolve_index, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys,
-                       rgb);
+                       rgb, c->arrow_mode == SC_ARROWS_OFF ? 1u : 2u);  // (entry 1 is the arrows' when there are any)
   else
     hipLaunchKernelGGL(k_render_resolve, dim3(grid_for((pixels + 3) / 4)), dim3(kBlock), 0, c->stream, v, c->renderKeys, rgb,
                        ((uintptr_t)rgb & 3) == 0 ? 1 : 0);
+  arrows_launch(c, v, rgb, as_index);
   hud_launch(c, v, rgb, as_index);
   HIPCHK(hipGetLastError());
   return SC_OK;
@@ -1308,6 +1333,34 @@ int sc_set_hud(sc_ctx* c, const char* text, int32_t n_bytes, int32_t x, int32_t 
     return SC_OK;
   }
   HIPCHK(hipStreamSynchronize(c->stream));
+  return SC_OK;
+}
+
+int sc_set_arrows(sc_ctx* c, int32_t mode, const sc_arrow* arrows, int64_t n, double scale, int64_t every) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->in_step) return fail(SC_ERR_STATE, "the arrows are set between ticks");
+  if (mode != SC_ARROWS_OFF && mode != SC_ARROWS_LIST && mode != SC_ARROWS_VELOCITY)
+    return fail(SC_ERR_ARG, "arrow mode %d; SC_ARROWS_OFF, _LIST or _VELOCITY", mode);
+  // (every argument is checked in every mode: a caller's mistake shows at once, not when the mode changes)
+  if (n < 0 || n > kArrowMaxList) return fail(SC_ERR_ARG, "%lld arrows; 0..%lld", (long long)n, kArrowMaxList);
+  if (n > 0 && !arrows) return fail(SC_ERR_ARG, "null arrow list");
+  if (every < 1) return fail(SC_ERR_ARG, "an arrow for every %lld-th particle; at least 1", (long long)every);
+  if (!std::isfinite(scale)) return fail(SC_ERR_ARG, "the arrows' scale must be finite");
+  HIPCHK(hipSetDevice(c->device));
+  c->arrow_mode = SC_ARROWS_OFF;  // (a call that fails below leaves no arrows)
+  if (mode == SC_ARROWS_LIST && n > 0) {
+    HIPCHK(c->arrowList.grow(n, c->stream));
+    HIPCHK(hipMemcpyAsync(c->arrowList, arrows, (size_t)n * sizeof(sc_arrow), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // `arrows` is the caller's: read before we return
+  if (mode == SC_ARROWS_LIST && n > 0) {
+    c->arrow_n = n;
+    c->arrow_mode = SC_ARROWS_LIST;
+  } else if (mode == SC_ARROWS_VELOCITY) {
+    c->arrow_scale = scale;
+    c->arrow_every = every;
+    c->arrow_mode = SC_ARROWS_VELOCITY;
+  }
   return SC_OK;
 }
 

@@ -157,16 +157,17 @@ __global__ void __launch_bounds__(kBlock) k_render_resolve(RenderView v, unsigne
 }
 
 // The same frame as one palette index per pixel (sc_gif.h; tests/gif_spec.py: indices): 0 for the background, 255 for
-// a wall, max(c, 1) for a disc of colour byte c.  `index` is 4-byte aligned: four pixels are one dword.
+// a wall, max(c, lowest) for a disc of colour byte c -- lowest = 1, or 2 when entry 1 belongs to the arrows
+// (sc_arrows.h).  `index` is 4-byte aligned: four pixels are one dword.
 __global__ void __launch_bounds__(kBlock) k_render_resolve_index(RenderView v, unsigned long long* __restrict__ keys,
-                                                                 unsigned char* __restrict__ index) {
+                                                                 unsigned char* __restrict__ index, unsigned lowest) {
   const unsigned total = (unsigned)v.width * (unsigned)v.height;
   const unsigned p0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
   if (p0 >= total) return;
   const int m = (int)min(4u, total - p0);
   const ResolvedQuad r = resolve_quad(v, keys, p0, m);
   unsigned c[4];
-  for (int q = 0; q < 4; ++q) c[q] = r.wall[q] ? 255u : (r.key[q] == 0 ? 0u : max((unsigned)(r.key[q] & 0xFF), 1u));
+  for (int q = 0; q < 4; ++q) c[q] = r.wall[q] ? 255u : (r.key[q] == 0 ? 0u : max((unsigned)(r.key[q] & 0xFF), lowest));
   if (m == 4) {
     *(unsigned*)(index + p0) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
   } else {

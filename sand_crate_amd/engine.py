@@ -210,7 +210,7 @@ class Engine:
 
     def render_gif(self, view: N.View, segments) -> bytes:
         """The frame `render` draws as palette indices (background 0, a wall 255, a disc of colour byte c max(c, 1): the
-        one loss is that (0, 0, 255) becomes (1, 1, 255)), encoded as `encode_gif` does without leaving the GPU before it
+        one loss is that (0, 0, 255) becomes (1, 1, 255); while arrows are set an arrow is 1 and a disc max(c, 2)), encoded as `encode_gif` does without leaving the GPU before it
         is compressed (sc_render_gif).  Synchronises."""
         seg = N.f64(segments).reshape(-1, 2, 2)
         return self._jpeg(lambda out, cap, n: self._lib.sc_render_gif(self._ctx, C.byref(view), N.dptr(seg), len(seg),
@@ -224,6 +224,17 @@ class Engine:
         it.  Synchronises (sc_set_hud).  The pixel rule, bit for bit: tests/text_spec.py."""
         data = bytes(text) if text else b""
         N.check(self._lib.sc_set_hud(self._ctx, data if data else None, len(data), int(x), int(y), int(scale)))
+
+    def set_arrows(self, mode: int, arrows=None, scale: float = 1.0, every: int = 1) -> None:
+        """From now on every frame of `render`, `render_jpeg` and `render_gif` carries debug arrows in green, over the
+        discs and walls and under the HUD text (sc_set_arrows).  `mode` N.ARROWS_LIST: `arrows`, K x 2 x 2 of (start, end)
+        in world units, at most N.MAX_ARROWS of them.  N.ARROWS_VELOCITY: one arrow per live particle whose id is a
+        multiple of `every`, from its position along velocity * `scale`, compressed as playback.py:99 does, all on the
+        device.  N.ARROWS_OFF: none.  Synchronises.  The pixel rule, bit for bit: tests/arrow_spec.py."""
+        a = None if arrows is None else N.f64(arrows).reshape(-1, 4)
+        n = 0 if a is None else len(a)
+        ptr = None if n == 0 else C.cast(a.ctypes.data, C.POINTER(N.Arrow))
+        N.check(self._lib.sc_set_arrows(self._ctx, int(mode), ptr, n, float(scale), int(every)))
 
     # -- per-tick inputs
     def set_params(self, *, dt, particle_radius, wall_collision_decay, pressure_amplifier, ignored_pressure,

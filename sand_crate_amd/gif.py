@@ -16,6 +16,8 @@ Layout::
 
 The header goes out when the file is opened, one frame per `write`, the trailer at `close()`: nothing is kept in memory.
 One loss against `Crate.render`: its colour (0, 0, 255) (a pressure of 1 and above) is palette entry 1, (1, 1, 255).
+A writer opened with ``arrows=True`` takes frames rendered with debug arrows: entry 1 is their green, (0, 255, 0), and
+the loss is that (0, 0, 255) and (1, 1, 255) are both entry 2, (2, 2, 255).
 """
 from __future__ import annotations
 
@@ -23,13 +25,15 @@ import struct
 from pathlib import Path
 
 
-def palette() -> bytes:
-    """The 768 bytes of the global colour table."""
-    return bytes(3) + b"".join(bytes((k, k, 255)) for k in range(1, 256))
+def palette(arrows: bool = False) -> bytes:
+    """The 768 bytes of the global colour table.  `arrows`: entry 1 is the debug arrows' green, (0, 255, 0), as frames
+    rendered with arrows use it (their discs start at entry 2: colour bytes 0 and 1 both become (2, 2, 255))."""
+    table = bytes(3) + b"".join(bytes((k, k, 255)) for k in range(1, 256))
+    return table[:3] + bytes((0, 255, 0)) + table[6:] if arrows else table
 
 
 class GifWriter:
-    def __init__(self, path, width: int, height: int, delay_cs: int = 1, loop: int = 0):
+    def __init__(self, path, width: int, height: int, delay_cs: int = 1, loop: int = 0, arrows: bool = False):
         if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
             raise ValueError("width and height must be 1..65535")
         if not (0 <= int(delay_cs) <= 65535 and 0 <= int(loop) <= 65535):
@@ -38,7 +42,7 @@ class GifWriter:
         self.width, self.height, self.delay_cs, self.loop = int(width), int(height), int(delay_cs), int(loop)
         self._frames = 0
         self._f = open(self.path, "wb")
-        self._f.write(b"GIF89a" + struct.pack("<HHBBB", self.width, self.height, 0xF7, 0, 0) + palette()
+        self._f.write(b"GIF89a" + struct.pack("<HHBBB", self.width, self.height, 0xF7, 0, 0) + palette(arrows)
                       + b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", self.loop) + b"\x00")
 
     @property

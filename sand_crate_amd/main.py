@@ -18,7 +18,9 @@ are streamed into ``video.avi``, Motion-JPEG at 50 fps as playback.py:120-129 wr
 with ``--frames`` as well, ``frames.npz`` is still written and this ``video.gif`` is the one kept.  ``--hud`` writes the
 HUD text the reference's viewer shows (`Crate.debug_prints`: tick, particle count, timing and the coefficient list --
 what tells one variant's video from the next) on every frame of ``--frames``, ``--video`` and ``--gif``, on the GPU, in
-a built-in bitmap font.  ``--checkpoint-every K`` also writes resumable checkpoints
+a built-in bitmap font.  ``--arrows [EVERY]`` draws the viewer's debug-arrow layer on the same frames, fed from the
+device: a green arrow along the velocity of every EVERY-th particle (`Crate.render(arrows="velocity")`).
+``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
 """
@@ -79,7 +81,7 @@ class HeadlessPlayback:
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-                 video_quality: int = 95, gif: bool = False, hud: bool = False) -> None:
+                 video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -101,6 +103,7 @@ class HeadlessPlayback:
         self.gif = bool(gif)
         self.gif_frames = 0
         self.hud = bool(hud)
+        self.arrows = max(int(arrows or 0), 0)  # velocity arrows for every this-many-th particle; 0: none
         self.done = False
         self.seconds = 0.0
 
@@ -116,7 +119,8 @@ class HeadlessPlayback:
         try:
             if self.gif:
                 self.recording_dir_path.mkdir(exist_ok=True, parents=True)
-                gif = GifWriter(self.recording_dir_path / "video.gif", int(pb.screen_x), int(pb.screen_y), delay_cs=1, loop=0)
+                gif = GifWriter(self.recording_dir_path / "video.gif", int(pb.screen_x), int(pb.screen_y), delay_cs=1, loop=0,
+                                arrows=self.arrows > 0)
             self._run(int(n), avi, gif)
         finally:
             if avi is not None:
@@ -134,6 +138,7 @@ class HeadlessPlayback:
     def _run(self, n: int, avi: Optional[AviWriter], gif: Optional[GifWriter] = None) -> None:
         pb = self.config.playback_config
         hud = True if self.hud else None
+        arrows = dict(arrows="velocity", arrow_every=self.arrows) if self.arrows else {}
         for _ in range(n):
             self.crate.physics_tick()
             if self.checkpoint_every and self.crate.tick % self.checkpoint_every == 0:
@@ -145,12 +150,12 @@ class HeadlessPlayback:
                                     "pressure": self.crate.particles_pressure.copy(),
                                     "segments": self.crate.segments.copy()})
                 if self.render_frames:
-                    self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y), hud=hud))
+                    self.images.append(self.crate.render(int(pb.screen_x), int(pb.screen_y), hud=hud, **arrows))
                 if avi is not None:
                     avi.write(self.crate.render_jpeg(int(pb.screen_x), int(pb.screen_y), quality=self.video_quality,
-                                                     hud=hud))
+                                                     hud=hud, **arrows))
                 if gif is not None:
-                    gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y), hud=hud))
+                    gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y), hud=hud, **arrows))
             if self.done:
                 break
 
@@ -198,7 +203,7 @@ def write_frames(out_dir: Path, frames, ticks, gif: bool = True) -> None:
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-         video_quality: int = 95, gif: bool = False, hud: bool = False) -> list[dict]:
+         video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -207,7 +212,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
-                                    video=video, video_quality=video_quality, gif=gif, hud=hud)
+                                    video=video, video_quality=video_quality, gif=gif, hud=hud, arrows=arrows)
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -237,6 +242,9 @@ def argument_parser() -> argparse.ArgumentParser:
                     "of --frames")
     ap.add_argument("--hud", action="store_true", help="write the HUD text (tick, particle count, timing, coefficients) on "
                     "every frame of --frames, --video and --gif")
+    ap.add_argument("--arrows", type=int, nargs="?", const=1, default=0, metavar="EVERY", help="draw a green arrow along "
+                    "the velocity of every EVERY-th particle (default: every one) on every frame of --frames, --video and "
+                    "--gif")
     return ap
 
 
@@ -244,4 +252,4 @@ if __name__ == "__main__":
     a = argument_parser().parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
-         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud)
+         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows)

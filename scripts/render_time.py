@@ -1,6 +1,6 @@
 """GPU time of one rendered frame (sc_render_device: clear + splat + resolve), measured with HIP events.
 
-    python scripts/render_time.py [--reps 50] [--hud]
+    python scripts/render_time.py [--reps 50] [--hud | --arrows]
 
 Scenes: bench.py's M2 inputs (1,048,576 particles in the wave_machine world) after 5 ticks at 1000 x 1000 and
 4096 x 4096, and config/wave_machine.yaml after 200 ticks of its source at 1000 x 1000 (discs of radius 5).  The
@@ -12,6 +12,12 @@ per case: median and min over the repetitions, in microseconds.
 without and with `hud=True`, in two alternating rounds, and the time `hud=True` adds (the difference of the medians of
 all rounds).  Beside it the host alternative: download the frame, PIL.ImageDraw.text, upload it again (skipped without
 PIL).  The rows without a HUD use nothing this option's commit added, so the same script times an older library.
+
+--arrows measures the debug arrows (sc_set_arrows) instead: the M2 inputs after 5 ticks at 1000 x 1000, `render` (device
+time, HIP events) without arrows, with a list of 2,048 seeded arrows, and with velocity arrows for every 64th particle,
+in three alternating rounds; then the medians over all rounds, what each kind of arrows adds, and the spread of the
+arrow-free rounds' medians.  The rows without arrows use nothing this option's commit added, so the same script times an
+older library.
 """
 import argparse
 import json
@@ -119,15 +125,55 @@ def hud_report(reps):
           flush=True)
 
 
+def arrows_report(reps, rounds=3):
+    import numpy as np
+    import bench
+    import sand_crate_amd as sc
+    side, n = 1000, 1048576
+    wc, _ = bench.world_for(n)
+    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
+    crate.particles, crate.particle_velocities = bench.synthetic_state(n)
+    crate.run(5)
+    crate.synchronize()
+    has_arrows = hasattr(crate.engine, "set_arrows")
+    rs = np.random.RandomState(2048)
+    pairs = np.stack([rs.rand(2048, 2), (rs.rand(2048, 2) - 0.5) * 0.1], axis=1)  # (start, direction): 10 to 40 pixels
+    head = {"scene": "M2", "ticks": 5, "particles": crate.particle_count, "frame": f"{side}x{side}"}
+    print(json.dumps({**head, "arrows_available": has_arrows}), flush=True)
+    kinds = {"none": {}}
+    if has_arrows:
+        kinds["list of 2048"] = {"arrows": pairs}
+        kinds["velocity, every 64th"] = {"arrows": "velocity", "arrow_every": 64}
+    got = {kind: [] for kind in kinds}
+    medians = {kind: [] for kind in kinds}
+    for rnd in range(rounds):
+        for kind, kw in kinds.items():
+            times = device_times(crate, side, side, reps, **kw)
+            got[kind] += times
+            medians[kind].append(stats(times)["median_us"])
+            print(json.dumps({**head, "arrows": kind, "round": rnd, "clock": "device", **stats(times)}), flush=True)
+    off = stats(got["none"])["median_us"]
+    print(json.dumps({**head, "arrows": "none", "all_rounds": True, **stats(got["none"]),
+                      "spread_of_round_medians_us": round(max(medians["none"]) - min(medians["none"]), 2)}), flush=True)
+    for kind in list(kinds)[1:]:
+        on = stats(got[kind])["median_us"]
+        print(json.dumps({**head, "arrows": kind, "all_rounds": True, **stats(got[kind]),
+                          "added_us": round(on - off, 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--hud", action="store_true", help="measure the HUD overlay instead (see above)")
+    ap.add_argument("--arrows", action="store_true", help="measure the debug arrows instead (see above)")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
     if args.hud:
         hud_report(args.reps)
+        return
+    if args.arrows:
+        arrows_report(args.reps)
         return
     import bench
     import sand_crate_amd as sc
