@@ -445,6 +445,55 @@ int sc_set_arrows(sc_ctx* ctx, int32_t mode, const sc_arrow* arrows, int64_t n, 
  * the ranks this is the global particle count. */
 int sc_owned_count(sc_ctx* ctx, int64_t* n);
 
+/* The probe: numbers instead of pictures.  One pass over the stored state (40 bytes per particle) reduces it on the
+ * device to a row of SC_PROBE_FIELDS float64 values and, with n_bins > 0, a profile of the free surface; the particles and
+ * pressures measured are exactly what sc_download_state would return (particles whose x is not finite, |x| < 1e300 as in
+ * sc_owned_count, are skipped).  tests/probe_spec.py is the rule.  The row:
+ *    0 tick          ticks finished by the context when the state was measured
+ *    1 n             live particles
+ *    2..5            sum_x, sum_y, sum_vx, sum_vy
+ *    6 sum_ke        sum of 0.5 (vx vx + vy vy)
+ *    7 sum_p         sum of the pressures
+ *    8..11           min_x, max_x, min_y, max_y (+inf / -inf for an empty crate)
+ *   12 max_speed2    max of vx vx + vy vy and 0        13 max_p   max of the pressures and 0
+ *   14 n_pressed     particles with pressure > 0       15 n_binned  particles that fell into a bin of the profile
+ * The profile: bin k of n_bins (0..SC_PROBE_MAX_BINS) over [x0, x1) holds the particles with floor((x - x0) / w) == k,
+ * w = (x1 - x0) / n_bins in float64; counts[k] is how many, tops[k] the smallest y among them -- gravity points to +y, so
+ * that is the free surface -- or +inf for an empty bin.
+ * Counts, minima, maxima, max_speed2 (vx vx + vy vy is not contracted) and the profile are exact.  The six sums are added
+ * in an order that depends on the stored particle count alone and with no floating-point atomics: the same state measured
+ * twice, or once by the log and once on demand, gives the same 128 bytes; against another order of summation they differ
+ * by rounding (probe_spec.py states the bound).  A NaN velocity or pressure at a finite position counts and propagates.
+ *
+ * sc_probe_now     one measurement of the state as it stands; synchronises.  counts / tops may be NULL when n_bins == 0.
+ * sc_probe_enable  from now on every finished tick (sc_step_finish, so also sc_tick and every tick of sc_step) appends
+ *                  one row and one profile to a log of capacity_rows (1..1,048,576) rows in device memory, on the
+ *                  context's stream after the force kernel: no synchronisation, no host traffic, the row index is a
+ *                  device counter.  A tick that finds the log full is not recorded and a device counter of dropped ticks
+ *                  goes up; memory is never overrun.  Enabling again starts an empty log with the new settings.  While
+ *                  enabled, results are bit for bit what they are without it (ticks are then never fused with their
+ *                  successor's wall pass: a fused tick leaves the NEXT tick's removal and wall fix in the storage arrays,
+ *                  which is not the state sc_download_state stands for).
+ * sc_probe_disable stops logging and discards what was not read.
+ * sc_probe_read    synchronises; delivers and clears what was logged since the last read, oldest first: rows is
+ *                  room x SC_PROBE_FIELDS, counts and tops room x n_bins (not touched, and may be NULL, when n_bins == 0).
+ *                  *n_out rows were delivered; with less room than rows logged the rest stay for the next read (the
+ *                  log's space is reused once all of it has been read).  *n_dropped is the counter of dropped ticks,
+ *                  which is cleared.
+ * SC_ERR_ARG for null pointers, n_bins outside 0..SC_PROBE_MAX_BINS, n_bins > 0 with bounds that are not finite or
+ * x1 <= x0, capacity_rows outside 1..1,048,576, room < 0.  SC_ERR_STATE for sc_probe_now / sc_probe_read between
+ * sc_step_begin and sc_step_finish, for sc_probe_read without sc_probe_enable, for sc_probe_enable / sc_probe_disable
+ * inside a tick or after sc_set_next_inputs promised the next tick, and for all four on a context in slab mode
+ * (sc_set_slab).  Like rendering the probe reads the state only: no counter, look-ahead promise, RNG position or pending
+ * error flag changes, and its launches are not bracketed by the timing events. */
+#define SC_PROBE_FIELDS 16
+#define SC_PROBE_MAX_BINS 1024
+int sc_probe_now(sc_ctx* ctx, int32_t n_bins, double x0, double x1, double* row16, int32_t* counts, double* tops);
+int sc_probe_enable(sc_ctx* ctx, int64_t capacity_rows, int32_t n_bins, double x0, double x1);
+int sc_probe_disable(sc_ctx* ctx);
+int sc_probe_read(sc_ctx* ctx, double* rows, int32_t* counts, double* tops, int64_t room, int64_t* n_out,
+                  int64_t* n_dropped);
+
 #ifdef __cplusplus
 }
 #endif

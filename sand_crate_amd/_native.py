@@ -18,6 +18,10 @@ NUM_KERNELS = 12
 NOISE_NONE, NOISE_HOST, NOISE_COUNTER = 0, 1, 2
 ARROWS_OFF, ARROWS_LIST, ARROWS_VELOCITY = 0, 1, 2
 MAX_ARROWS = 1 << 20
+PROBE_FIELDS = 16
+PROBE_MAX_BINS = 1024
+PROBE_MAX_ROWS = 1 << 20
+PROBE_BLOCK, PROBE_BLOCKS = 1024, 256  # the probe's fixed launch (csrc/sc_probe.h: kProbeBlock, kProbeBlocks)
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -145,6 +149,10 @@ SIGNATURES = {
     "sc_render_gif": (C.c_int, [_P, C.POINTER(View), _D, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "sc_set_hud": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "sc_set_arrows": (C.c_int, [_P, C.c_int32, C.POINTER(Arrow), C.c_int64, C.c_double, C.c_int64]),
+    "sc_probe_now": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, _D, _I32, _D]),
+    "sc_probe_enable": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_double, C.c_double]),
+    "sc_probe_disable": (C.c_int, [_P]),
+    "sc_probe_read": (C.c_int, [_P, _D, _I32, _D, C.c_int64, _I64, _I64]),
 }
 
 _lib = None

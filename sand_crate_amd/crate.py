@@ -49,6 +49,7 @@ from .engine import Engine
 from .hud_font import default_placement
 from .load_config import WorldConfig
 from .particle_source import build_particle_sources
+from .probe import FIELDS, as_dict
 from .rigid_body import build_rigid_bodies
 from .utils.geometry_utils import pad_segments
 
@@ -130,6 +131,8 @@ class Crate:
         self._pending_checkpoint = None
         self._hud_sent = None      # (text bytes, x, y, scale) the engine draws on frames, or None: no HUD
         self._arrows_sent = None   # ("list", bytes of the K x 2 x 2 ends) or ("velocity", scale, every), or None: no arrows
+        self._observe = None       # (capacity, bins, x0, x1) of the device log of observables, or None: not logging
+        self._observed = []        # rows read from an engine that is gone, or before the log was switched off
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -236,6 +239,9 @@ class Crate:
         self._arrows_sent = None  # (... and no arrows)
         if rng is not None:
             self._engine.rng_set_state(*rng)
+        if getattr(self, "_observe", None) is not None:  # the log moves on: what the old context holds is kept
+            self._observed.append(old.probe_read())
+            self._engine.probe_enable(*self._observe)
         old.close()
         if len(p):
             self._engine.upload(p, v)
@@ -299,6 +305,48 @@ class Crate:
         self._hud_forces = bool(on)
         self._force_ema = {}
         self._engine.enable_force_monitor(self._hud_forces)
+
+    # ------------------------------------------------------------------ observables (sc_probe_*; tests/probe_spec.py)
+    def measure(self, bins: int = 0, x_range=(0.0, 1.0)) -> dict:
+        """The state as it stands, reduced on the device to the sixteen numbers of `probe.FIELDS` -- {name: value} -- and,
+        with `bins`, the profile of the free surface over `x_range`: `count` (bins,) int32 particles per column and
+        `top` (bins,) the smallest y in each (gravity points to +y), +inf where a column is empty.  Nothing but these
+        numbers is downloaded; synchronises.  The simulation is left alone."""
+        row, counts, tops = self._engine.probe_now(bins, float(x_range[0]), float(x_range[1]))
+        return as_dict(row, counts, tops)
+
+    def observe(self, on: bool = True, *, capacity: int = 4096, bins: int = 0, x_range=(0.0, 1.0)) -> None:
+        """Switch the device log: while on, every tick (`physics_tick` and each tick of `run`) appends what `measure`
+        would return to a log of `capacity` rows in device memory, with no synchronisation and no download until
+        `observations()` reads it.  A tick that finds the log full is dropped and counted.  Switching the log (on again
+        with other settings, or off) keeps what was logged so far for the next `observations()`."""
+        if self._observe is not None:
+            self._observed.append(self._engine.probe_read())
+        if on:
+            want = (int(capacity), int(bins), float(x_range[0]), float(x_range[1]))
+            self._observe = None
+            self._engine.probe_enable(*want)
+            self._observe = want
+        elif self._observe is not None:
+            self._observe = None
+            self._engine.probe_disable()
+
+    def observations(self) -> dict:
+        """What was logged since the last call, oldest first: a T-long float64 array per name of `probe.FIELDS`, `count`
+        (T x bins, int32) and `top` (T x bins) when the log has bins, and `dropped`, the ticks that found the log
+        full.  T = 0 when nothing was logged.  Synchronises.  (`tick` counts the ticks of the GPU context: it starts
+        over when the crate had to grow into a larger one.)"""
+        chunks, self._observed = self._observed, []
+        if self._observe is not None:
+            chunks.append(self._engine.probe_read())
+        bins = self._observe[1] if self._observe is not None else (chunks[-1][1].shape[1] if chunks else 0)
+        if any(c[1].shape[1] != bins for c in chunks):  # the bins changed between reads: the profiles of the last setting
+            chunks = [c if c[1].shape[1] == bins else (c[0], np.zeros((len(c[0]), bins), dtype=np.int32),
+                                                      np.full((len(c[0]), bins), np.inf), c[3]) for c in chunks]
+        rows = np.concatenate([c[0] for c in chunks]) if chunks else np.zeros((0, len(FIELDS)))
+        counts = np.concatenate([c[1] for c in chunks]) if chunks else np.zeros((0, bins), dtype=np.int32)
+        tops = np.concatenate([c[2] for c in chunks]) if chunks else np.zeros((0, bins))
+        return as_dict(rows, counts, tops, dropped=sum(c[3] for c in chunks))
 
     # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
     def _set_hud(self, hud, width: int) -> None:

@@ -24,6 +24,7 @@
 #include "sc_hud.h"
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
+#include "sc_probe.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
 #include "sc_rng.h"
@@ -176,6 +177,15 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   DevBuf<RngState> rng;        // NumPy's MT19937 stream on the device (sc_rng_set_state), or empty
   DevBuf<double> monitor;      // force monitor: sum of |dv| per phase and the particle count (sc_enable_force_monitor)
   bool monitor_on = false;
+  // the probe (sc_probe.h): the workgroups' partial records, its own words (ticket, log head, dropped ticks), the row and
+  // profile of sc_probe_now, and the log of sc_probe_enable -- rows, bin counts and the bins' tops as 64-bit keys
+  DevBuf<double> probePartials, probeNowRow, probeRows;
+  DevBuf<int> probeWords, probeNowCounts, probeCounts;
+  DevBuf<unsigned long long> probeNowTops, probeTops;
+  bool probe_on = false;
+  int64_t probe_cap = 0, probe_tail = 0;  // ... its capacity in rows, and the first row not yet delivered
+  int probe_bins = 0;
+  double probe_x0 = 0.0, probe_x1 = 1.0;
   // checkpoint (sc_checkpoint_begin / _finish): device-side snapshot, pinned host copy, side stream
   DevBuf<double> snap_d[4];
   DevBuf<int> snap_id_d;
@@ -297,6 +307,7 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, (n + kBlock - 1) / kB
 // In slab mode the stored count changes on the device every tick (halo records arrive without the
 // host knowing how many), so launches cover the capacity; surplus workgroups exit on their first load.
 int64_t launch_bound(const sc_ctx* c);
+int probe_launch(sc_ctx* c, bool to_log);
 
 // A slot of the progress block as the device last wrote it (no synchronisation: possibly stale).
 int progress_read(const sc_ctx* c, int slot) { return ((const volatile int*)c->progress.get())[slot]; }
@@ -704,6 +715,59 @@ void launch_pass_b_any(sc_ctx* c, bool fused, const WallInputs& wn) {
     launch_pass_b<NOISE, false>(c, wn);
 }
 
+// ---- the probe (sc_probe.h) ---------------------------------------------------------------------
+
+int probe_check_bins(int32_t n_bins, double x0, double x1) {
+  if (n_bins < 0 || n_bins > kProbeMaxBins) return fail(SC_ERR_ARG, "%d bins; 0..%d", n_bins, kProbeMaxBins);
+  if (n_bins > 0 && !(std::isfinite(x0) && std::isfinite(x1) && x1 > x0))
+    return fail(SC_ERR_ARG, "the profile's range must be finite with x1 > x0");
+  return SC_OK;
+}
+
+int probe_ensure(sc_ctx* c) {
+  if (c->probeWords.size() >= PW_COUNT) return SC_OK;
+  HIPCHK(c->probePartials.grow((int64_t)kProbeBlocks * kProbeFields, c->stream));
+  HIPCHK(c->probeNowRow.grow(kProbeFields, c->stream));
+  HIPCHK(c->probeNowCounts.grow(kProbeMaxBins, c->stream));
+  HIPCHK(c->probeNowTops.grow(kProbeMaxBins, c->stream));
+  HIPCHK(c->probeWords.grow(PW_COUNT, c->stream));
+  HIPCHK(hipMemsetAsync(c->probeWords, 0, c->probeWords.bytes(), c->stream));
+  return SC_OK;
+}
+
+// Enqueues one measurement: into the log's next row (`to_log`; the device decides which, or that the log is full), or
+// into the row and profile of sc_probe_now with the bins given.
+int probe_launch(sc_ctx* c, bool to_log, int n_bins, double x0, double x1) {
+  ProbeArgs a{};
+  a.nbins = n_bins;
+  a.x0 = x0;
+  a.w = n_bins > 0 ? (x1 - x0) / n_bins : 1.0;
+  a.tick = (double)c->tick;
+  a.pressure_valid = c->normals_valid ? 1 : 0;
+  a.cap = (int)c->cap;
+  a.log_rows = to_log ? c->probe_cap : -1;
+  hipLaunchKernelGGL(k_probe, dim3(kProbeBlocks), dim3(kProbeBlock), 0, c->stream, a, c->counters, c->x, c->y, c->vx, c->vy,
+                     c->P, c->probePartials, c->probeWords, to_log ? c->probeRows : c->probeNowRow,
+                     to_log ? c->probeCounts : c->probeNowCounts, to_log ? c->probeTops : c->probeNowTops);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int probe_launch(sc_ctx* c, bool to_log) { return probe_launch(c, to_log, c->probe_bins, c->probe_x0, c->probe_x1); }
+
+// the bins' tops as the kernel keeps them (probe_key; all ones: an empty bin) back to float64
+void probe_decode_tops(const unsigned long long* keys, double* tops, int64_t n) {
+  for (int64_t k = 0; k < n; ++k) {
+    const unsigned long long key = keys[k];
+    if (key == kProbeEmptyTop) {
+      tops[k] = std::numeric_limits<double>::infinity();
+    } else {
+      const unsigned long long b = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+      std::memcpy(&tops[k], &b, 8);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1031,7 +1095,9 @@ int sc_step_finish(sc_ctx* c) {
   WallInputs wn;
   std::memset(&wn, 0, sizeof wn);
   const bool slab_ready = !c->slab || c->haloL || !(c->has_left || c->has_right);
-  const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on;  // the monitor runs with the plain kernel
+  // (the monitor runs with the plain kernel; the probe's log measures the state sc_download_state stands for, which a
+  // fused tick does not leave in the storage arrays)
+  const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on && !c->probe_on;
   if (fused) {
     World next;
     int rc = build_world(c, next, c->next, c->tick + 1);
@@ -1067,6 +1133,7 @@ int sc_step_finish(sc_ctx* c) {
   // without downloads does not accumulate `upper` as everything ever emitted
   if (c->stats_live >= 0 && !c->slab) c->upper = c->stats_live;
   c->stats_live = -1;
+  if (c->probe_on && !c->slab && !c->custom_grid) return probe_launch(c, true);
   return SC_OK;
 }
 
@@ -2097,6 +2164,113 @@ int sc_owned_count(sc_ctx* c, int64_t* n) {
   HIPCHK(hipMemcpyAsync(&h, c->owned_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *n = h;
+  return SC_OK;
+}
+
+// ---- the probe ----------------------------------------------------------------------------------
+
+int sc_probe_now(sc_ctx* c, int32_t n_bins, double x0, double x1, double* row16, int32_t* counts, double* tops) {
+  if (!c || !row16) return fail(SC_ERR_ARG, "null argument");
+  int rc = probe_check_bins(n_bins, x0, x1);
+  if (rc) return rc;
+  if (n_bins > 0 && (!counts || !tops)) return fail(SC_ERR_ARG, "null profile arrays");
+  if (c->slab) return fail(SC_ERR_STATE, "the probe is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, "measuring happens between ticks");
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = probe_ensure(c))) return rc;
+  std::vector<unsigned long long> keys((size_t)n_bins);
+  if (n_bins > 0) {
+    HIPCHK(hipMemsetAsync(c->probeNowCounts, 0, (size_t)n_bins * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->probeNowTops, 0xFF, (size_t)n_bins * sizeof(unsigned long long), c->stream));
+  }
+  if ((rc = probe_launch(c, false, n_bins, x0, x1))) return rc;
+  HIPCHK(hipMemcpyAsync(row16, c->probeNowRow, kProbeFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (n_bins > 0) {
+    HIPCHK(hipMemcpyAsync(counts, c->probeNowCounts, (size_t)n_bins * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(keys.data(), c->probeNowTops, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  probe_decode_tops(keys.data(), tops, n_bins);
+  return SC_OK;
+}
+
+int sc_probe_enable(sc_ctx* c, int64_t capacity_rows, int32_t n_bins, double x0, double x1) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (capacity_rows < 1 || capacity_rows > (int64_t)1 << 20)
+    return fail(SC_ERR_ARG, "a log of %lld rows; 1..1048576", (long long)capacity_rows);
+  int rc = probe_check_bins(n_bins, x0, x1);
+  if (rc) return rc;
+  if (c->slab) return fail(SC_ERR_STATE, "the probe is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, "the probe's log cannot change inside a tick");
+  if (c->prebinned) return fail(SC_ERR_STATE, "the probe's log cannot change after sc_set_next_inputs promised the next tick");
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = probe_ensure(c))) return rc;
+  c->probe_on = false;  // (a call that fails below leaves no log)
+  HIPCHK(c->probeRows.grow(capacity_rows * kProbeFields, c->stream));
+  HIPCHK(c->probeCounts.grow(capacity_rows * n_bins, c->stream));
+  HIPCHK(c->probeTops.grow(capacity_rows * n_bins, c->stream));
+  if (n_bins > 0) {
+    HIPCHK(hipMemsetAsync(c->probeCounts, 0, (size_t)capacity_rows * n_bins * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(c->probeTops, 0xFF, (size_t)capacity_rows * n_bins * sizeof(unsigned long long), c->stream));
+  }
+  HIPCHK(hipMemsetAsync(c->probeWords, 0, c->probeWords.bytes(), c->stream));
+  c->probe_cap = capacity_rows;
+  c->probe_tail = 0;
+  c->probe_bins = n_bins;
+  c->probe_x0 = x0;
+  c->probe_x1 = x1;
+  c->probe_on = true;
+  return SC_OK;
+}
+
+int sc_probe_disable(sc_ctx* c) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->slab) return fail(SC_ERR_STATE, "the probe is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, "the probe's log cannot change inside a tick");
+  if (c->prebinned) return fail(SC_ERR_STATE, "the probe's log cannot change after sc_set_next_inputs promised the next tick");
+  c->probe_on = false;
+  return SC_OK;
+}
+
+int sc_probe_read(sc_ctx* c, double* rows, int32_t* counts, double* tops, int64_t room, int64_t* n_out, int64_t* n_dropped) {
+  if (!c || !n_out || !n_dropped) return fail(SC_ERR_ARG, "null argument");
+  if (room < 0) return fail(SC_ERR_ARG, "room for %lld rows", (long long)room);
+  if (room > 0 && (!rows || (c->probe_on && c->probe_bins > 0 && (!counts || !tops)))) return fail(SC_ERR_ARG, "null arrays");
+  if (c->slab) return fail(SC_ERR_STATE, "the probe is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, "the log is read between ticks");
+  if (!c->probe_on) return fail(SC_ERR_STATE, "sc_probe_enable first");
+  HIPCHK(hipSetDevice(c->device));
+  int words[PW_COUNT];
+  HIPCHK(hipMemcpyAsync(words, c->probeWords, sizeof words, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int64_t head = std::min<int64_t>(words[PW_HEAD], c->probe_cap), tail = std::min(c->probe_tail, head);
+  const int64_t m = std::min(head - tail, room);
+  const size_t nb = (size_t)c->probe_bins;
+  if (m > 0) {
+    HIPCHK(hipMemcpyAsync(rows, c->probeRows + tail * kProbeFields, (size_t)m * kProbeFields * sizeof(double),
+                          hipMemcpyDeviceToHost, c->stream));
+    std::vector<unsigned long long> keys((size_t)m * nb);
+    if (nb > 0) {
+      HIPCHK(hipMemcpyAsync(counts, c->probeCounts + tail * nb, (size_t)m * nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(keys.data(), c->probeTops + tail * nb, keys.size() * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    probe_decode_tops(keys.data(), tops, (int64_t)keys.size());
+  }
+  c->probe_tail = tail + m;
+  if (c->probe_tail == head) {  // all of it has been read: the log starts over, its bins empty
+    if (nb > 0 && head > 0) {
+      HIPCHK(hipMemsetAsync(c->probeCounts, 0, (size_t)head * nb * sizeof(int), c->stream));
+      HIPCHK(hipMemsetAsync(c->probeTops, 0xFF, (size_t)head * nb * sizeof(unsigned long long), c->stream));
+    }
+    HIPCHK(hipMemsetAsync(c->probeWords + PW_HEAD, 0, sizeof(int), c->stream));
+    c->probe_tail = 0;
+  }
+  if (words[PW_DROPPED]) HIPCHK(hipMemsetAsync(c->probeWords + PW_DROPPED, 0, sizeof(int), c->stream));
+  *n_out = m;
+  *n_dropped = words[PW_DROPPED];
   return SC_OK;
 }
 

@@ -425,6 +425,47 @@ class Engine:
         N.check(self._lib.sc_owned_count(self._ctx, C.byref(n)))
         return n.value
 
+    # -- the probe: observables of the state, reduced on the device (sc_probe_*; the rule is tests/probe_spec.py)
+    PROBE_LAUNCH_THREADS = N.PROBE_BLOCK * N.PROBE_BLOCKS  # threads of the probe's fixed launch: one slot each per turn
+
+    def probe_now(self, bins: int = 0, x0: float = 0.0, x1: float = 1.0):
+        """-> (row (16,) float64 in `probe.FIELDS` order, counts (bins,) int32, tops (bins,) float64) of the state as it
+        stands (sc_probe_now); synchronises."""
+        bins = int(bins)
+        row = np.zeros(N.PROBE_FIELDS)
+        counts = np.zeros(max(bins, 0), dtype=np.int32)
+        tops = np.zeros(max(bins, 0))
+        N.check(self._lib.sc_probe_now(self._ctx, bins, float(x0), float(x1), N.dptr(row),
+                                       N.i32ptr(counts) if bins > 0 else None, N.dptr(tops) if bins > 0 else None))
+        return row, counts, tops
+
+    def probe_enable(self, capacity: int, bins: int = 0, x0: float = 0.0, x1: float = 1.0) -> None:
+        """From now on every finished tick appends a row (and a profile of `bins` bins over [x0, x1)) to a log of
+        `capacity` rows in device memory, without synchronising (sc_probe_enable)."""
+        N.check(self._lib.sc_probe_enable(self._ctx, int(capacity), int(bins), float(x0), float(x1)))
+        self._probe_log = (int(capacity), int(bins))
+
+    def probe_disable(self) -> None:
+        N.check(self._lib.sc_probe_disable(self._ctx))
+        self._probe_log = None
+
+    def probe_read(self, room: int | None = None):
+        """-> (rows (T, 16), counts (T, bins), tops (T, bins), dropped): what was logged since the last read, oldest
+        first, at most `room` rows (default: the log's capacity), and the ticks that found the log full
+        (sc_probe_read); synchronises."""
+        capacity, bins = getattr(self, "_probe_log", None) or (0, 0)
+        room = capacity if room is None else int(room)
+        rows = np.zeros((max(room, 0), N.PROBE_FIELDS))
+        counts = np.zeros((max(room, 0), bins), dtype=np.int32)
+        tops = np.zeros((max(room, 0), bins))
+        n, dropped = C.c_int64(0), C.c_int64(0)
+        with_bins = bins > 0 and room > 0
+        N.check(self._lib.sc_probe_read(self._ctx, N.dptr(rows) if room > 0 else None,
+                                        N.i32ptr(counts) if with_bins else None, N.dptr(tops) if with_bins else None,
+                                        room, C.byref(n), C.byref(dropped)))
+        k = n.value
+        return rows[:k].copy(), counts[:k].copy(), tops[:k].copy(), dropped.value
+
     # -- force monitor
     def enable_force_monitor(self, on: bool = True) -> None:
         N.check(self._lib.sc_enable_force_monitor(self._ctx, 1 if on else 0))

@@ -20,6 +20,10 @@ HUD text the reference's viewer shows (`Crate.debug_prints`: tick, particle coun
 what tells one variant's video from the next) on every frame of ``--frames``, ``--video`` and ``--gif``, on the GPU, in
 a built-in bitmap font.  ``--arrows [EVERY]`` draws the viewer's debug-arrow layer on the same frames, fed from the
 device: a green arrow along the velocity of every EVERY-th particle (`Crate.render(arrows="velocity")`).
+``--observe [BINS]`` records numbers instead of pictures: every tick the device reduces the state to the sixteen
+observables of `probe.FIELDS` (particle count, momentum and kinetic-energy sums, extents, pressure) and, with BINS, a
+profile of the free surface in BINS columns over the world's width, into a log in device memory (`Crate.observe`) that is
+read every 4096 ticks and written as ``observables.npz`` next to ``config.yaml``.
 ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
@@ -40,6 +44,9 @@ from .avi import AviWriter
 from .crate import Crate
 from .gif import GifWriter
 from .load_config import Config, load_config
+from .probe import FIELDS, concatenate
+
+OBSERVE_EVERY = 4096  # ticks between two reads of the device log of --observe (its capacity)
 
 options = {
     "pressure_amplifier": [20, 40],
@@ -81,7 +88,8 @@ class HeadlessPlayback:
     def __init__(self, config: Config, recording_dir_path: Optional[Path] = None, *, noise: str = "host",
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-                 video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0) -> None:
+                 video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
+                 observe: Optional[int] = None) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -104,6 +112,9 @@ class HeadlessPlayback:
         self.gif_frames = 0
         self.hud = bool(hud)
         self.arrows = max(int(arrows or 0), 0)  # velocity arrows for every this-many-th particle; 0: none
+        self.observe = None if observe is None else max(int(observe), 0)  # bins of the profile (0: none); None: no log
+        self.observed: list[dict] = []
+        self.observables: Optional[dict] = None
         self.done = False
         self.seconds = 0.0
 
@@ -139,8 +150,13 @@ class HeadlessPlayback:
         pb = self.config.playback_config
         hud = True if self.hud else None
         arrows = dict(arrows="velocity", arrow_every=self.arrows) if self.arrows else {}
-        for _ in range(n):
+        observe = getattr(self, "observe", None)
+        if observe is not None:
+            self.crate.observe(capacity=max(min(n, OBSERVE_EVERY), 1), bins=observe, x_range=(0.0, 1.0))
+        for k in range(n):
             self.crate.physics_tick()
+            if observe is not None and (k + 1) % OBSERVE_EVERY == 0:
+                self.observed.append(self.crate.observations())
             if self.checkpoint_every and self.crate.tick % self.checkpoint_every == 0:
                 self._collect_checkpoint()        # the previous one has long arrived
                 self.crate.begin_checkpoint()     # returns at once; the transfer overlaps the next ticks
@@ -158,6 +174,11 @@ class HeadlessPlayback:
                     gif.write(self.crate.render_gif(int(pb.screen_x), int(pb.screen_y), hud=hud, **arrows))
             if self.done:
                 break
+        if observe is not None:
+            self.observed.append(self.crate.observations())
+            self.crate.observe(False)
+            self.observables = concatenate(self.observed, observe)
+            self.observed = []
 
     def _collect_checkpoint(self) -> None:
         if self._checkpoint_tick is None:
@@ -179,6 +200,10 @@ class HeadlessPlayback:
             arrays[f"segments_{k}"] = frame["segments"]
         arrays["ticks"] = np.array([f["tick"] for f in self.frames], dtype=np.int64)
         np.savez_compressed(out_dir / "state.npz", **arrays)
+        observables = getattr(self, "observables", None)
+        if observables is not None:
+            np.savez_compressed(out_dir / "observables.npz", fields=np.array(FIELDS), x_range=np.array([0.0, 1.0]),
+                                dt=np.float64(self.crate.dt), **observables)
         if self.render_frames:
             write_frames(out_dir, self.images, arrays["ticks"], gif=not self.gif)
 
@@ -203,7 +228,8 @@ def write_frames(out_dir: Path, frames, ticks, gif: bool = True) -> None:
 def main(config_file_path, play_recording: Optional[Path] = None, *, variants: Optional[int] = None,
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
-         video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0) -> list[dict]:
+         video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
+         observe: Optional[int] = None) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -212,13 +238,20 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
         out = Path(play_recording) / f"variant_{k:02d}" if play_recording is not None else None
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
-                                    video=video, video_quality=video_quality, gif=gif, hud=hud, arrows=arrows)
+                                    video=video, video_quality=video_quality, gif=gif, hud=hud, arrows=arrows,
+                                    **({} if observe is None else {"observe": observe}))
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
                         "coefficients": {name: variant.world_config.coefficients[name] for name in options}})
+        last = ""
+        if observe is not None:  # the last logged tick in numbers
+            obs = playback.observables
+            for name in ("sum_ke", "max_speed2", "n"):
+                summary[-1][name] = float(obs[name][-1]) if len(obs[name]) else float("nan")
+            last = f", sum_ke {summary[-1]['sum_ke']:.6g}, max_speed2 {summary[-1]['max_speed2']:.6g}, n {summary[-1]['n']:.0f}"
         print(f"variant {k}: {summary[-1]['ticks']} ticks, {summary[-1]['particles']} particles, "
-              f"{playback.seconds:.2f} s -> {playback.recording_dir_path}")
+              f"{playback.seconds:.2f} s{last} -> {playback.recording_dir_path}")
     return summary
 
 
@@ -245,6 +278,9 @@ def argument_parser() -> argparse.ArgumentParser:
     ap.add_argument("--arrows", type=int, nargs="?", const=1, default=0, metavar="EVERY", help="draw a green arrow along "
                     "the velocity of every EVERY-th particle (default: every one) on every frame of --frames, --video and "
                     "--gif")
+    ap.add_argument("--observe", type=int, nargs="?", const=0, default=None, metavar="BINS", help="log the observables of "
+                    "every tick on the GPU (particle count, momentum and kinetic-energy sums, extents, pressure) and, "
+                    "with BINS, the free surface in BINS columns; written as observables.npz")
     return ap
 
 
@@ -252,4 +288,4 @@ if __name__ == "__main__":
     a = argument_parser().parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
-         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows)
+         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows, observe=a.observe)
