@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(kBlock) k_render_splat(RenderView v, const int
   // sc_download_state's pairing: the pressure of the last finished tick belongs to the slots it left live
   const int np = pressure_valid ? min(ns, counters[C_NT]) : 0;
   const double p = slot < np ? P[slot] : 0.0;
-  // playback.py:197-200: 255 - int(p * 255), clipped to [0, 255]; not finite -> 0
+  // playback.py:197-200: 255 - int(p * 255), clipped to [0, 255]; NaN and +inf -> 0, -inf -> 255
   const double cc = 255.0 - trunc(p * 255.0);
   const unsigned c = cc >= 255.0 ? 255u : (cc > 0.0 ? (unsigned)cc : 0u);
   const unsigned long long key = ((unsigned long long)(unsigned)(id[slot] + 1) << 8) | c;

@@ -8,8 +8,8 @@ view     cx = trunc(x (W - 1)); X = (cx - center_x) zoom + W/2 in float64 in tha
 discs    R = floor(trunc(W particle_radius) zoom) (playback.py:195 uses screen_x for both axes).  Pixel (i, j) is covered
          iff (i - px)^2 + (j - py)^2 <= R^2 in integers, inside the frame only; R = 0 paints the centre pixel.  Particles
          whose x or y is not finite, or whose disc misses the frame (tested in float64), are skipped.
-colour   c = 255 - trunc(p 255) clipped to [0, 255], 0 for a pressure that is not finite; the pixel is (c, c, 255)
-         (playback.py:197-200).
+colour   c = 255 - trunc(p 255) clipped to [0, 255]: 0 for a pressure of NaN or +inf, 255 for -inf; the pixel is
+         (c, c, 255) (playback.py:197-200).
 order    among discs covering a pixel the highest id wins (the reference draws in array order).
 walls    drawn last, white, endpoints mapped by the same view but not floored.  Pixel (i, j) is covered iff
          4 e <= w^2, e the squared distance to the segment in float64:  dx = bx - ax, dy = by - ay, L = dx dx + dy dy,
