@@ -494,6 +494,56 @@ int sc_probe_disable(sc_ctx* ctx);
 int sc_probe_read(sc_ctx* ctx, double* rows, int32_t* counts, double* tops, int64_t room, int64_t* n_out,
                   int64_t* n_dropped);
 
+/* Tracking: the state as small packed frames, and such a frame back into a context.  A frame (format 1, little-endian;
+ * tests/track_spec.py is the rule, byte for byte) is
+ *   a 64-byte header   "SCTK", u32 version = 1, i64 tick (ticks finished by the context, as in the probe's rows), i64 n,
+ *                      i32 n_segments, i32 flags (bit 0: the pressure was valid), f64 lo = -0.25, f64 span = 1.5, zeros;
+ *   n_segments x 4 f64 the walls the tick ran with (the unpadded segments of sc_set_segments / sc_tick);
+ *   four planes, each zero-padded to a multiple of 8 bytes: u32 id[n], u16 qx[n], u16 qy[n], u8 c[n].
+ * n counts the stored slots, as sc_count does.  A coordinate is q = floor((x - lo) * (65534 / span) + 0.5) clamped to
+ * 0..65534, each operation rounded on its own in float64, and 65535 when it is not finite; back: lo + q * (span / 65534),
+ * +inf for 65535 -- within half a step, 1.14445e-5, of what was stored.  c is the colour byte sc_render gives the slot
+ * (255 - trunc(P * 255) clipped, 255 without a valid pressure); back: P = (255 - c + 0.5) / 255, which renders as c again.
+ * Records stand in the storage order of the moment; ids are unique, and the renderer orders by id.
+ *
+ * sc_track_bound    the size of a frame of n particles and n_segments walls.
+ * sc_track_capture  packs the state as it stands on the device and downloads the one frame; synchronises.  *n_bytes is
+ *                   the frame's size; if that exceeds `room` nothing is written and SC_ERR_CAPACITY is returned (out may
+ *                   be null with room 0 to ask for the size).
+ * sc_track_enable   from now on every finished tick (sc_step_finish, so also sc_tick and every tick of sc_step) whose
+ *                   count of finished ticks is a multiple of `every` (>= 1) appends one frame to a log of capacity_bytes
+ *                   (1..2^40) in device memory, on the context's stream after the force kernel: no synchronisation, no
+ *                   host traffic.  The frame's size is known on the device only; its place is taken with one atomic add
+ *                   on a byte cursor that lives there.  A frame that does not fit is not written, not even in part, and a
+ *                   device counter of dropped frames goes up.  Enabling again starts an empty log.  While enabled,
+ *                   results are bit for bit what they are without it (ticks are then never fused with their successor's
+ *                   wall pass, for the probe's reason).
+ * sc_track_disable  stops logging and discards what was not read.
+ * sc_track_read     synchronises; delivers what was logged since the last read, oldest first and back to back (every
+ *                   frame's header gives its length), and rewinds the cursor: *n_bytes, *n_frames, and *dropped, the
+ *                   counter of dropped frames, which is cleared.  With less room than bytes logged nothing is delivered
+ *                   or forgotten: *n_bytes is what is needed, SC_ERR_CAPACITY is returned.
+ * sc_track_load     `frame` (host memory, n_bytes) becomes the context's state: dequantised positions, zero velocities,
+ *                   the ids, P from c -- with `plain` from c = 100 for every particle, the reference's colour for particles
+ *                   that come without a pressure, (100, 100, 255) -- all n slots live with a valid pressure, the next
+ *                   appended particle's id above the frame's largest.  The frame is checked on the host first: the magic,
+ *                   the version, n >= 0, 0 <= n_segments <= SC_MAX_SEGMENTS, n_bytes equal to the size such a frame has,
+ *                   a finite range, ids below 2^31 - 1 (SC_ERR_ARG), n within the context's capacity (SC_ERR_CAPACITY); a
+ *                   frame that fails launches nothing and leaves the context as it was.  Synchronises.  The tick counter
+ *                   and the walls of the context stay as they are: the frame's own are for the caller to read
+ *                   (sand_crate_amd/track.py: parse).  The surface normals of sc_download_normals are not the frame's.
+ * SC_ERR_ARG for null pointers, a negative room, every < 1 or a capacity outside 1..2^40.  SC_ERR_STATE between
+ * sc_step_begin and sc_step_finish, for sc_track_read without sc_track_enable, for sc_track_enable / sc_track_disable
+ * after sc_set_next_inputs promised the next tick, and for all of them but sc_track_bound on a context in slab mode
+ * (sc_set_slab).  Packing reads the state only: no counter, look-ahead promise, RNG position or pending error flag
+ * changes, and its launches are not bracketed by the timing events. */
+int sc_track_bound(int64_t n, int32_t n_segments, int64_t* bytes);
+int sc_track_capture(sc_ctx* ctx, uint8_t* out, int64_t room, int64_t* n_bytes);
+int sc_track_enable(sc_ctx* ctx, int64_t every, int64_t capacity_bytes);
+int sc_track_disable(sc_ctx* ctx);
+int sc_track_read(sc_ctx* ctx, uint8_t* out, int64_t room, int64_t* n_bytes, int64_t* n_frames, int64_t* dropped);
+int sc_track_load(sc_ctx* ctx, const uint8_t* frame, int64_t n_bytes, int32_t plain);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,12 @@ SIGNATURES = {
     "sc_probe_enable": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_double, C.c_double]),
     "sc_probe_disable": (C.c_int, [_P]),
     "sc_probe_read": (C.c_int, [_P, _D, _I32, _D, C.c_int64, _I64, _I64]),
+    "sc_track_bound": (C.c_int, [C.c_int64, C.c_int32, _I64]),
+    "sc_track_capture": (C.c_int, [_P, _P, C.c_int64, _I64]),
+    "sc_track_enable": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "sc_track_disable": (C.c_int, [_P]),
+    "sc_track_read": (C.c_int, [_P, _P, C.c_int64, _I64, _I64, _I64]),
+    "sc_track_load": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ from .hud_font import default_placement
 from .load_config import WorldConfig
 from .particle_source import build_particle_sources
 from .probe import FIELDS, as_dict
+from . import track as _track
 from .rigid_body import build_rigid_bodies
 from .utils.geometry_utils import pad_segments
 
@@ -133,6 +134,8 @@ class Crate:
         self._arrows_sent = None   # ("list", bytes of the K x 2 x 2 ends) or ("velocity", scale, every), or None: no arrows
         self._observe = None       # (capacity, bins, x0, x1) of the device log of observables, or None: not logging
         self._observed = []        # rows read from an engine that is gone, or before the log was switched off
+        self._track = None         # (every, capacity_bytes) of the device log of packed frames, or None: not tracking
+        self._tracked = []         # (frames, dropped) read from an engine that is gone, or before the log was switched off
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -242,6 +245,9 @@ class Crate:
         if getattr(self, "_observe", None) is not None:  # the log moves on: what the old context holds is kept
             self._observed.append(old.probe_read())
             self._engine.probe_enable(*self._observe)
+        if getattr(self, "_track", None) is not None:  # ... and so does the log of frames
+            self._tracked.append(self._read_track(old))
+            self._engine.track_enable(*self._track)
         old.close()
         if len(p):
             self._engine.upload(p, v)
@@ -347,6 +353,46 @@ class Crate:
         counts = np.concatenate([c[1] for c in chunks]) if chunks else np.zeros((0, bins), dtype=np.int32)
         tops = np.concatenate([c[2] for c in chunks]) if chunks else np.zeros((0, bins))
         return as_dict(rows, counts, tops, dropped=sum(c[3] for c in chunks))
+
+    # ------------------------------------------------------------------ packed frames (sc_track_*; tests/track_spec.py)
+    def capture_frame(self) -> bytes:
+        """The state as it stands as one packed frame (`track.parse` reads it, `track.Player` draws it): nine bytes per
+        particle -- id, position on a 16-bit grid over [-0.25, 1.25], the colour byte `render` would give it -- behind the
+        tick number and the walls as they stand.  Packed on the device; only the frame is downloaded.  Synchronises; the
+        simulation is left alone."""
+        self._send_tick_inputs()  # (the walls as they stand: before the first tick the engine has seen none)
+        return self._engine.track_capture()
+
+    def track(self, on: bool = True, *, every: int = 1, capacity_bytes: int = 1 << 26) -> None:
+        """Switch the device log of frames: while on, every tick whose number is a multiple of `every` (`physics_tick`
+        and each tick of `run`) appends what `capture_frame` would return to a log of `capacity_bytes` in device memory,
+        with no synchronisation and no download until `tracked()` reads it.  A frame that does not fit is dropped whole
+        and counted.  Switching the log (on again with other settings, or off) keeps what was logged so far for the next
+        `tracked()`."""
+        if self._track is not None:
+            self._tracked.append(self._read_track(self._engine))
+        if on:
+            want = (int(every), int(capacity_bytes))
+            self._track = None
+            self._engine.track_enable(*want)
+            self._track = want
+        elif self._track is not None:
+            self._track = None
+            self._engine.track_disable()
+
+    @staticmethod
+    def _read_track(engine):
+        blob, _, dropped = engine.track_read()
+        return _track.split(blob), dropped
+
+    def tracked(self) -> tuple[list[bytes], int]:
+        """-> (the frames logged since the last call, oldest first; how many were dropped because the log was full).
+        Synchronises.  (A frame's tick counts the ticks of the GPU context: it starts over when the crate had to grow
+        into a larger one.)"""
+        chunks, self._tracked = self._tracked, []
+        if self._track is not None:
+            chunks.append(self._read_track(self._engine))
+        return [f for c in chunks for f in c[0]], sum(c[1] for c in chunks)
 
     # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
     def _set_hud(self, hud, width: int) -> None:

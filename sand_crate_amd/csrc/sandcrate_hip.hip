@@ -25,6 +25,7 @@
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_probe.h"
+#include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
 #include "sc_rng.h"
@@ -186,6 +187,12 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   int64_t probe_cap = 0, probe_tail = 0;  // ... its capacity in rows, and the first row not yet delivered
   int probe_bins = 0;
   double probe_x0 = 0.0, probe_x1 = 1.0;
+  // tracking (sc_track.h): the frame of sc_track_capture, the log of sc_track_enable with its words (byte cursor, frames,
+  // dropped frames, and where the frame being packed starts), and the frame sc_track_load unpacks
+  DevBuf<unsigned char> trackNow, trackLog, trackLoad;
+  DevBuf<unsigned long long> trackWords;
+  bool track_on = false;
+  int64_t track_every = 1, track_cap = 0;  // ... every how many ticks a frame is logged, and the log's capacity in bytes
   // checkpoint (sc_checkpoint_begin / _finish): device-side snapshot, pinned host copy, side stream
   DevBuf<double> snap_d[4];
   DevBuf<int> snap_id_d;
@@ -308,6 +315,7 @@ int grid_for(int64_t n) { return (int)std::max<int64_t>(1, (n + kBlock - 1) / kB
 // host knowing how many), so launches cover the capacity; surplus workgroups exit on their first load.
 int64_t launch_bound(const sc_ctx* c);
 int probe_launch(sc_ctx* c, bool to_log);
+int track_launch(sc_ctx* c, bool to_log);
 
 // A slot of the progress block as the device last wrote it (no synchronisation: possibly stale).
 int progress_read(const sc_ctx* c, int slot) { return ((const volatile int*)c->progress.get())[slot]; }
@@ -768,6 +776,46 @@ void probe_decode_tops(const unsigned long long* keys, double* tops, int64_t n) 
   }
 }
 
+// ---- tracking (sc_track.h) ----------------------------------------------------------------------
+
+int track_ensure(sc_ctx* c) {
+  if (c->trackWords.size() >= TW_COUNT) return SC_OK;
+  HIPCHK(c->trackWords.grow(TW_COUNT, c->stream));
+  HIPCHK(hipMemsetAsync(c->trackWords, 0, c->trackWords.bytes(), c->stream));
+  return SC_OK;
+}
+
+// Enqueues one frame of the state as it stands, with the walls the last tick ran with: appended to the log (`to_log`;
+// the device decides where, or that it does not fit), or at the start of trackNow, which holds `trackNow.size()` bytes.
+int track_launch(sc_ctx* c, bool to_log) {
+  TrackArgs a{};
+  a.tick = c->tick;
+  a.log_bytes = to_log ? c->track_cap : -1;
+  a.room = c->trackNow.size();
+  a.scale = kTrackCodes / kTrackSpan;
+  a.pressure_valid = c->normals_valid ? 1 : 0;
+  a.cap = (int)c->cap;
+  a.nseg = c->now.nseg;
+  std::memcpy(a.seg, c->now.seg, sizeof a.seg);
+  unsigned char* base = to_log ? c->trackLog.get() : c->trackNow.get();
+  hipLaunchKernelGGL(k_track_reserve, dim3(1), dim3(64), 0, c->stream, a, c->counters, c->trackWords, base);
+  const int64_t bound = std::min<int64_t>(launch_bound(c), c->cap);
+  const int64_t groups = track_pad8(bound) / kTrackPerThread;
+  if (groups > 0)
+    hipLaunchKernelGGL(k_track_pack, dim3(grid_for(groups)), dim3(kBlock), 0, c->stream, a, c->counters, c->trackWords, c->x,
+                       c->y, c->id[0], c->P, base);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int track_refuse(const sc_ctx* c, bool switching) {
+  if (c->slab) return fail(SC_ERR_STATE, "tracking is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, switching ? "the track log cannot change inside a tick" : "tracking happens between ticks");
+  if (switching && c->prebinned)
+    return fail(SC_ERR_STATE, "the track log cannot change after sc_set_next_inputs promised the next tick");
+  return SC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1095,9 +1143,9 @@ int sc_step_finish(sc_ctx* c) {
   WallInputs wn;
   std::memset(&wn, 0, sizeof wn);
   const bool slab_ready = !c->slab || c->haloL || !(c->has_left || c->has_right);
-  // (the monitor runs with the plain kernel; the probe's log measures the state sc_download_state stands for, which a
-  // fused tick does not leave in the storage arrays)
-  const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on && !c->probe_on;
+  // (the monitor runs with the plain kernel; the probe's log and the track log record the state sc_download_state
+  // stands for, which a fused tick does not leave in the storage arrays)
+  const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on && !c->probe_on && !c->track_on;
   if (fused) {
     World next;
     int rc = build_world(c, next, c->next, c->tick + 1);
@@ -1133,7 +1181,11 @@ int sc_step_finish(sc_ctx* c) {
   // without downloads does not accumulate `upper` as everything ever emitted
   if (c->stats_live >= 0 && !c->slab) c->upper = c->stats_live;
   c->stats_live = -1;
-  if (c->probe_on && !c->slab && !c->custom_grid) return probe_launch(c, true);
+  if (c->probe_on && !c->slab && !c->custom_grid) {
+    const int rc = probe_launch(c, true);
+    if (rc) return rc;
+  }
+  if (c->track_on && !c->slab && !c->custom_grid && c->tick % c->track_every == 0) return track_launch(c, true);
   return SC_OK;
 }
 
@@ -2164,6 +2216,146 @@ int sc_owned_count(sc_ctx* c, int64_t* n) {
   HIPCHK(hipMemcpyAsync(&h, c->owned_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *n = h;
+  return SC_OK;
+}
+
+// ---- tracking -------------------------------------------------------------------------------------
+
+int sc_track_bound(int64_t n, int32_t n_segments, int64_t* bytes) {
+  if (!bytes) return fail(SC_ERR_ARG, "null argument");
+  if (n < 0 || n > (int64_t)100000000) return fail(SC_ERR_ARG, "%lld particles", (long long)n);
+  if (n_segments < 0 || n_segments > kMaxSeg) return fail(SC_ERR_ARG, "%d segments; 0..%d", n_segments, kMaxSeg);
+  *bytes = track_planes(n, n_segments).end;
+  return SC_OK;
+}
+
+int sc_track_capture(sc_ctx* c, uint8_t* out, int64_t room, int64_t* n_bytes) {
+  if (!c || !n_bytes || room < 0 || (room > 0 && !out)) return fail(SC_ERR_ARG, "null argument or negative room");
+  *n_bytes = 0;
+  int rc = track_refuse(c, false);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = track_ensure(c))) return rc;
+  HIPCHK(c->trackNow.grow(track_planes(std::min<int64_t>(launch_bound(c), c->cap), c->now.nseg).end, c->stream));
+  if ((rc = track_launch(c, false))) return rc;
+  unsigned long long words[TW_COUNT];
+  HIPCHK(hipMemcpyAsync(words, c->trackWords, sizeof words, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int64_t bytes = track_planes((int64_t)words[TW_N], c->now.nseg).end;
+  if ((long long)words[TW_AT] < 0)
+    return fail(SC_ERR_HIP, "the device stores %lld particles, more than the host's bound", (long long)words[TW_N]);
+  *n_bytes = bytes;
+  if (bytes > room) return fail(SC_ERR_CAPACITY, "a frame of %lld bytes, room for %lld", (long long)bytes, (long long)room);
+  HIPCHK(hipMemcpyAsync(out, c->trackNow, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return SC_OK;
+}
+
+int sc_track_enable(sc_ctx* c, int64_t every, int64_t capacity_bytes) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (every < 1) return fail(SC_ERR_ARG, "every %lld; at least 1", (long long)every);
+  if (capacity_bytes < 1 || capacity_bytes > ((int64_t)1 << 40))
+    return fail(SC_ERR_ARG, "a log of %lld bytes; 1..2^40", (long long)capacity_bytes);
+  int rc = track_refuse(c, true);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = track_ensure(c))) return rc;
+  c->track_on = false;  // (a call that fails below leaves no log)
+  HIPCHK(c->trackLog.grow(track_pad8(capacity_bytes), c->stream));
+  HIPCHK(hipMemsetAsync(c->trackWords, 0, c->trackWords.bytes(), c->stream));
+  c->track_every = every;
+  c->track_cap = capacity_bytes;
+  c->track_on = true;
+  return SC_OK;
+}
+
+int sc_track_disable(sc_ctx* c) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  const int rc = track_refuse(c, true);
+  if (rc) return rc;
+  c->track_on = false;
+  return SC_OK;
+}
+
+int sc_track_read(sc_ctx* c, uint8_t* out, int64_t room, int64_t* n_bytes, int64_t* n_frames, int64_t* dropped) {
+  if (!c || !n_bytes || !n_frames || !dropped || room < 0 || (room > 0 && !out))
+    return fail(SC_ERR_ARG, "null argument or negative room");
+  *n_bytes = *n_frames = *dropped = 0;
+  const int rc = track_refuse(c, false);
+  if (rc) return rc;
+  if (!c->track_on) return fail(SC_ERR_STATE, "sc_track_enable first");
+  unsigned long long words[TW_COUNT];
+  HIPCHK(hipMemcpyAsync(words, c->trackWords, sizeof words, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int64_t bytes = std::min<int64_t>((int64_t)words[TW_CURSOR], c->track_cap);
+  *n_bytes = bytes;
+  if (bytes > room)  // nothing is delivered and nothing forgotten
+    return fail(SC_ERR_CAPACITY, "%lld bytes logged, room for %lld", (long long)bytes, (long long)room);
+  if (bytes > 0) {
+    HIPCHK(hipMemcpyAsync(out, c->trackLog, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  *n_frames = (int64_t)words[TW_FRAMES];
+  *dropped = (int64_t)words[TW_DROPPED];
+  HIPCHK(hipMemsetAsync(c->trackWords, 0, c->trackWords.bytes(), c->stream));  // the log starts over
+  return SC_OK;
+}
+
+int sc_track_load(sc_ctx* c, const uint8_t* frame, int64_t n_bytes, int32_t plain) {
+  if (!c || !frame) return fail(SC_ERR_ARG, "null argument");
+  if (c->slab) return fail(SC_ERR_STATE, "tracking is not available in slab mode");
+  if (c->in_step) return fail(SC_ERR_STATE, "particles cannot change between sc_step_begin and sc_step_finish");
+  if (n_bytes < kTrackHeaderBytes) return fail(SC_ERR_ARG, "%lld bytes are no frame", (long long)n_bytes);
+  uint32_t magic, version;
+  int64_t n;
+  int32_t nseg;
+  double lo, span;
+  std::memcpy(&magic, frame, 4);
+  std::memcpy(&version, frame + 4, 4);
+  std::memcpy(&n, frame + 16, 8);
+  std::memcpy(&nseg, frame + 24, 4);
+  std::memcpy(&lo, frame + 32, 8);
+  std::memcpy(&span, frame + 40, 8);
+  if (magic != kTrackMagic) return fail(SC_ERR_ARG, "not a track frame (magic %08x)", magic);
+  if (version != kTrackVersion) return fail(SC_ERR_ARG, "track frame of version %u; this library reads %u", version, kTrackVersion);
+  if (n < 0) return fail(SC_ERR_ARG, "a frame of %lld particles", (long long)n);
+  if (nseg < 0 || nseg > kMaxSeg) return fail(SC_ERR_ARG, "a frame of %d segments; 0..%d", nseg, kMaxSeg);
+  if (n > c->cap)
+    return fail(SC_ERR_CAPACITY, "%lld particles exceed the context capacity %lld", (long long)n, (long long)c->cap);
+  const TrackPlanes pl = track_planes(n, nseg);
+  if (n_bytes != pl.end) return fail(SC_ERR_ARG, "%lld bytes; a frame of %lld particles and %d segments has %lld",
+                                     (long long)n_bytes, (long long)n, nseg, (long long)pl.end);
+  if (!(std::isfinite(lo) && std::isfinite(span) && span > 0)) return fail(SC_ERR_ARG, "the frame's coordinate range is not finite");
+  int64_t max_id = -1;
+  for (int64_t k = 0; k < n; ++k) {
+    uint32_t v;
+    std::memcpy(&v, frame + pl.id + 4 * k, 4);
+    if (v > (uint32_t)std::numeric_limits<int>::max() - 1) return fail(SC_ERR_ARG, "particle id out of range");
+    max_id = std::max<int64_t>(max_id, v);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (c->prebinned) {
+    const int rc = abandon_promise(c);
+    if (rc) return rc;
+  }
+  HIPCHK(c->trackLoad.grow(n_bytes, c->stream));
+  HIPCHK(hipMemcpyAsync(c->trackLoad, frame, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
+  TrackLoad a{};
+  a.n = (int)n;
+  a.nseg = nseg;
+  a.plain = plain ? 1 : 0;
+  a.next_id = (int)(max_id + 1);
+  a.lo = lo;
+  a.step = span / kTrackCodes;
+  hipLaunchKernelGGL(k_track_unpack, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, a, c->trackLoad, c->counters, c->x, c->y,
+                     c->vx, c->vy, c->id[0], c->P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));  // `frame` is the caller's: read before we return
+  c->upper = n;
+  c->next_id = max_id + 1;
+  c->normals_valid = 1;  // every slot carries the pressure its colour stands for
+  c->halo_ring_from = c->tick;
+  c->live_hint_from = c->tick;
   return SC_OK;
 }
 

@@ -466,6 +466,62 @@ class Engine:
         k = n.value
         return rows[:k].copy(), counts[:k].copy(), tops[:k].copy(), dropped.value
 
+    # -- tracking: the state as packed frames (sc_track_*; the format is tests/track_spec.py, the host side track.py)
+    @staticmethod
+    def track_bound(n: int, n_segments: int) -> int:
+        """The size in bytes of a frame of `n` particles and `n_segments` walls (sc_track_bound)."""
+        b = C.c_int64(0)
+        N.check(N.load().sc_track_bound(int(n), int(n_segments), C.byref(b)))
+        return b.value
+
+    def _track_fetch(self, call, room: int) -> tuple:
+        buf = getattr(self, "_track_buf", None)
+        if buf is None or len(buf) < room:
+            buf = self._track_buf = np.empty(max(int(room), 1), dtype=np.uint8)
+        rc = call(N._P(buf.ctypes.data), len(buf))
+        return rc, buf
+
+    def track_capture(self) -> bytes:
+        """The state as it stands as one packed frame, with the walls of the last set_segments / tick
+        (sc_track_capture); synchronises."""
+        n = C.c_int64(0)
+        rc, buf = self._track_fetch(lambda out, room: self._lib.sc_track_capture(self._ctx, out, room, C.byref(n)), 1 << 16)
+        if rc == N.ERR_CAPACITY and n.value > len(buf):
+            rc, buf = self._track_fetch(lambda out, room: self._lib.sc_track_capture(self._ctx, out, room, C.byref(n)),
+                                        n.value)
+        N.check(rc)
+        return buf[:n.value].tobytes()
+
+    def track_enable(self, every: int = 1, capacity_bytes: int = 1 << 26) -> None:
+        """From now on every tick whose number is a multiple of `every` appends a frame to a log of `capacity_bytes` in
+        device memory, without synchronising; a frame that does not fit is dropped whole and counted
+        (sc_track_enable)."""
+        N.check(self._lib.sc_track_enable(self._ctx, int(every), int(capacity_bytes)))
+        self._track_log = int(capacity_bytes)
+
+    def track_disable(self) -> None:
+        N.check(self._lib.sc_track_disable(self._ctx))
+        self._track_log = None
+
+    def track_read(self):
+        """-> (bytes: the frames logged since the last read, oldest first, back to back; how many; dropped frames)
+        (sc_track_read); synchronises and rewinds the log."""
+        n, frames, dropped = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        call = lambda out, room: self._lib.sc_track_read(self._ctx, out, room, C.byref(n), C.byref(frames),  # noqa: E731
+                                                         C.byref(dropped))
+        rc, buf = self._track_fetch(call, 1 << 16)
+        if rc == N.ERR_CAPACITY and n.value > len(buf):
+            rc, buf = self._track_fetch(call, n.value)
+        N.check(rc)
+        return buf[:n.value].tobytes(), frames.value, dropped.value
+
+    def track_load(self, frame: bytes, plain: bool = False) -> None:
+        """The frame becomes the context's state: dequantised positions, zero velocities, its ids, the pressure its
+        colour bytes stand for (`plain`: the reference's playback colour for all) (sc_track_load); synchronises."""
+        data = np.frombuffer(bytes(frame), dtype=np.uint8)
+        N.check(self._lib.sc_track_load(self._ctx, N._P(data.ctypes.data) if len(data) else None, len(data),
+                                        1 if plain else 0))
+
     # -- force monitor
     def enable_force_monitor(self, on: bool = True) -> None:
         N.check(self._lib.sc_enable_force_monitor(self._ctx, 1 if on else 0))

@@ -24,6 +24,10 @@ device: a green arrow along the velocity of every EVERY-th particle (`Crate.rend
 observables of `probe.FIELDS` (particle count, momentum and kinetic-energy sums, extents, pressure) and, with BINS, a
 profile of the free surface in BINS columns over the world's width, into a log in device memory (`Crate.observe`) that is
 read every 4096 ticks and written as ``observables.npz`` next to ``config.yaml``.
+``--track [EVERY]`` records the run itself as packed frames (`Crate.track`): every EVERY-th tick the device packs the state
+into nine bytes per particle in a log in device memory -- no download and no synchronisation in the tick loop -- which is
+read when the host's bound of the particle count says the next frames may no longer fit, and streamed into ``track.sctk``
+(`track.TrackWriter`); ``python -m sand_crate_amd.replay`` turns that file into frames or videos at any view.
 ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
@@ -45,8 +49,10 @@ from .crate import Crate
 from .gif import GifWriter
 from .load_config import Config, load_config
 from .probe import FIELDS, concatenate
+from .track import FILE_NAME as TRACK_FILE, TrackWriter, frame_bytes
 
 OBSERVE_EVERY = 4096  # ticks between two reads of the device log of --observe (its capacity)
+TRACK_LOG_BYTES = 1 << 26  # the device log of --track: at least this, and at least four frames of max_particles
 
 options = {
     "pressure_amplifier": [20, 40],
@@ -89,7 +95,7 @@ class HeadlessPlayback:
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
                  video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
-                 observe: Optional[int] = None) -> None:
+                 observe: Optional[int] = None, track: int = 0) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -115,6 +121,9 @@ class HeadlessPlayback:
         self.observe = None if observe is None else max(int(observe), 0)  # bins of the profile (0: none); None: no log
         self.observed: list[dict] = []
         self.observables: Optional[dict] = None
+        self.track = max(int(track or 0), 0)  # a packed frame every this-many-th tick into track.sctk; 0: none
+        self.track_frames = 0
+        self.track_dropped = 0
         self.done = False
         self.seconds = 0.0
 
@@ -132,8 +141,11 @@ class HeadlessPlayback:
                 self.recording_dir_path.mkdir(exist_ok=True, parents=True)
                 gif = GifWriter(self.recording_dir_path / "video.gif", int(pb.screen_x), int(pb.screen_y), delay_cs=1, loop=0,
                                 arrows=self.arrows > 0)
+            if getattr(self, "track", 0):
+                self._track_begin()
             self._run(int(n), avi, gif)
         finally:
+            self._track_end()
             if avi is not None:
                 self.video_frames = avi.frames
                 avi.close()
@@ -155,6 +167,8 @@ class HeadlessPlayback:
             self.crate.observe(capacity=max(min(n, OBSERVE_EVERY), 1), bins=observe, x_range=(0.0, 1.0))
         for k in range(n):
             self.crate.physics_tick()
+            if getattr(self, "_track_writer", None) is not None and self.crate.tick % self.track == 0:
+                self._track_tick()
             if observe is not None and (k + 1) % OBSERVE_EVERY == 0:
                 self.observed.append(self.crate.observations())
             if self.checkpoint_every and self.crate.tick % self.checkpoint_every == 0:
@@ -179,6 +193,43 @@ class HeadlessPlayback:
             self.crate.observe(False)
             self.observables = concatenate(self.observed, observe)
             self.observed = []
+
+    # --track: the log lives on the device; the host only keeps an upper bound of the bytes it may hold by now
+    def _track_frame_bound(self) -> int:
+        crate = self.crate
+        most = max(int(crate.max_particles), crate.engine.capacity)  # (the device never stores more than either)
+        return frame_bytes(most, len(crate.segments) if crate.rigid_bodies else 0)
+
+    def _track_begin(self) -> None:
+        self.recording_dir_path.mkdir(exist_ok=True, parents=True)
+        self._track_writer = TrackWriter(self.recording_dir_path / TRACK_FILE, config=deep_dictify(self.config))
+        self._track_capacity = max(TRACK_LOG_BYTES, 4 * self._track_frame_bound())
+        self._track_used = 0
+        self.crate.track(every=self.track, capacity_bytes=self._track_capacity)
+
+    def _track_drain(self) -> None:
+        frames, dropped = self.crate.tracked()
+        self._track_writer.write_all(frames)
+        self.track_dropped += dropped
+        self._track_used = 0
+
+    def _track_tick(self) -> None:
+        """After a tick that logged a frame: read the log out when the next frame may no longer fit."""
+        self._track_used += self._track_frame_bound()
+        if self._track_used + self._track_frame_bound() > self._track_capacity:
+            self._track_drain()
+
+    def _track_end(self) -> None:
+        writer = getattr(self, "_track_writer", None)
+        if writer is None:
+            return
+        try:
+            self._track_drain()
+            self.crate.track(False)
+        finally:
+            self.track_frames = writer.frames
+            writer.close()
+            self._track_writer = None
 
     def _collect_checkpoint(self) -> None:
         if self._checkpoint_tick is None:
@@ -229,7 +280,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
          video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
-         observe: Optional[int] = None) -> list[dict]:
+         observe: Optional[int] = None, track: int = 0) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -239,7 +290,8 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
         playback = HeadlessPlayback(config=variant, recording_dir_path=out, noise=noise, record_every=record_every,
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
                                     video=video, video_quality=video_quality, gif=gif, hud=hud, arrows=arrows,
-                                    **({} if observe is None else {"observe": observe}))
+                                    **({} if observe is None else {"observe": observe}),
+                                    **({"track": track} if track else {}))
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -281,6 +333,9 @@ def argument_parser() -> argparse.ArgumentParser:
     ap.add_argument("--observe", type=int, nargs="?", const=0, default=None, metavar="BINS", help="log the observables of "
                     "every tick on the GPU (particle count, momentum and kinetic-energy sums, extents, pressure) and, "
                     "with BINS, the free surface in BINS columns; written as observables.npz")
+    ap.add_argument("--track", type=int, nargs="?", const=1, default=0, metavar="EVERY", help="record every EVERY-th tick "
+                    "(default: every one) as a packed frame on the GPU, nine bytes per particle, streamed into track.sctk; "
+                    "python -m sand_crate_amd.replay draws it at any view")
     return ap
 
 
@@ -288,4 +343,5 @@ if __name__ == "__main__":
     a = argument_parser().parse_args()
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
-         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows, observe=a.observe)
+         video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows, observe=a.observe,
+         track=a.track)
