@@ -544,6 +544,41 @@ int sc_track_disable(sc_ctx* ctx);
 int sc_track_read(sc_ctx* ctx, uint8_t* out, int64_t room, int64_t* n_bytes, int64_t* n_frames, int64_t* dropped);
 int sc_track_load(sc_ctx* ctx, const uint8_t* frame, int64_t n_bytes, int32_t plain);
 
+/* The state to and from DEVICE memory of the caller (e.g. torch CUDA tensors), in particle-index order: what
+ * sc_download_state / sc_upload_state move through the host, without the host.
+ *
+ * sc_export_state_device  writes exactly what sc_download_state would write into host memory at the same point of the
+ *     stream: xy and vxy n x 2 interleaved, pressure and ids of length n, in ascending id order; slots whose x is not
+ *     finite (the dead ghost copies of slab mode) are skipped; the pressure is that of the last finished tick for the slots
+ *     it left live and 0 for every other (tests/state_spec.py is the rule).  *dev_n (device memory, required) receives n.
+ *     Any of the four arrays may be NULL; xy and vxy are written as 16-byte records and must be aligned to 16 bytes.
+ *     `room` is the room of the arrays in particles; elements past n are left as they were.  Enqueued on the context's
+ *     stream only: nothing synchronises, nothing reaches the host, and the context's stream does not wait for other
+ *     streams -- the arrays must not be in use elsewhere when this is called.  Like rendering it reads the state only: no
+ *     counter, look-ahead promise, RNG position or pending error flag changes, and like the probe's its launches are not
+ *     bracketed by the timing events.  Works in slab mode, as sc_download_state does.
+ *     The ranking is a radix sort of (id, slot) pairs on the device -- least significant digit first, four passes of
+ *     eight bits, each a count per tile of 256 keys, a two-level scan of the counts and a stable scatter (csrc/sc_state.h)
+ *     -- so the result is exact, does not depend on timing, no workgroup waits for another, and the cost is linear in
+ *     the stored count whatever the ids are (a bitmap over the ids would cost 2^31 bits for one large id, and a slab does
+ *     not know the largest id of the ghosts it was sent).  The workspace belongs to the context: 24 bytes per particle of
+ *     the host's bound of the stored count (in slab mode: of the capacity), grown -- which synchronises once -- to the
+ *     largest bound asked for.
+ *     SC_ERR_STATE between sc_step_begin and sc_step_finish; SC_ERR_ARG for a null dev_n, a negative room or a misaligned
+ *     array; SC_ERR_CAPACITY when room is below the host's bound of the stored count -- checked before anything is
+ *     launched, the arrays are then untouched.
+ * sc_import_state_device  sc_upload_state (dev_ids NULL: particle i gets id i) or sc_upload_state_ids with the arrays in
+ *     device memory: the n particles become the context's state, pressures and normals are no longer valid, a pending
+ *     promise (sc_set_next_inputs) is abandoned; the same SC_ERR_STATE and SC_ERR_CAPACITY rules.  No particle data
+ *     passes through the host.  The arrays are read on the context's stream, which does not wait for other streams: they
+ *     must be ready when this is called and stay untouched until the stream has passed the call.  With ids the call
+ *     synchronises once, to bring back two words: the largest id and whether one lies outside 0..2^31 - 2 -- then
+ *     SC_ERR_ARG, and the context is as it was.  Duplicate ids are the caller's responsibility, as in sc_upload_state_ids. */
+int sc_export_state_device(sc_ctx* ctx, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
+                           int64_t* dev_n);
+int sc_import_state_device(sc_ctx* ctx, const double* dev_xy, const double* dev_vxy, const int64_t* dev_ids /* may be NULL */,
+                           int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

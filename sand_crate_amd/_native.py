@@ -22,6 +22,9 @@ PROBE_FIELDS = 16
 PROBE_MAX_BINS = 1024
 PROBE_MAX_ROWS = 1 << 20
 PROBE_BLOCK, PROBE_BLOCKS = 1024, 256  # the probe's fixed launch (csrc/sc_probe.h: kProbeBlock, kProbeBlocks)
+# the device export's launches (csrc/sc_state.h, sc_kernels.h): keys per workgroup of a sorting pass (kStateTile), counts
+# per workgroup of the scan between its two kernels (kScanPerBlock), rows per workgroup of the gather (kBlock)
+STATE_TILE, STATE_SCAN_BLOCK, STATE_GATHER_BLOCK = 256, 2048, 256
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -159,6 +162,8 @@ SIGNATURES = {
     "sc_track_disable": (C.c_int, [_P]),
     "sc_track_read": (C.c_int, [_P, _P, C.c_int64, _I64, _I64, _I64]),
     "sc_track_load": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
+    "sc_export_state_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
+    "sc_import_state_device": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
 }
 
 _lib = None

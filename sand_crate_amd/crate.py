@@ -206,6 +206,48 @@ class Crate:
         self._cache = (particles, velocities, np.zeros(len(particles)))
         self._count, self._count_known = len(particles), True
 
+    def state_tensors(self, *, pressure: bool = True, ids: bool = False, sync: bool = True):
+        """The state as torch CUDA tensors on the crate's device, without crossing to the host: ``(particles,
+        velocities[, pressure][, ids])`` -- float64 (n, 2) twice, float64 (n,), int64 (n,) -- holding exactly what the
+        `particles`, `particle_velocities` and `particles_pressure` attributes hold, in the same particle-index order,
+        ranked and gathered on the GPU (sc_export_state_device).
+
+        `sync=True` synchronises, reads the 8-byte count and returns views cut to n.  `sync=False` returns tensors of the
+        context's capacity plus, last, the one-element int64 count tensor, and does not synchronise: rows from the count
+        on are uninitialised.  The tensors are written on the library's stream, and the library's stream does not wait
+        for torch's: read them after `synchronize()` -- or run the crate on torch's stream, `engine.set_stream`, and
+        everything torch enqueues afterwards sees them."""
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        room = eng.capacity
+        out = [torch.empty((room, 2), dtype=torch.float64, device=dev), torch.empty((room, 2), dtype=torch.float64, device=dev),
+               torch.empty(room, dtype=torch.float64, device=dev) if pressure else None,
+               torch.empty(room, dtype=torch.int64, device=dev) if ids else None]
+        count = torch.empty(1, dtype=torch.int64, device=dev)  # (always written; nothing of torch's touches the new tensors)
+        if sync:  # (... unless their memory was freed with work still queued on torch's stream)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.export_state(*out, count=count)
+        if not sync:
+            return (*(t for t in out if t is not None), count)
+        eng.synchronize()
+        n = int(count.item())
+        self._count, self._count_known = n, True
+        return tuple(t[:n] for t in out if t is not None)
+
+    def load_state_tensors(self, particles, velocities, ids=None) -> None:
+        """The device form of the `particles` / `particle_velocities` setters: float64 (n, 2) CUDA tensors -- and `ids`,
+        int64 (n,), for particles that keep their identity, e.g. what `state_tensors(ids=True)` returned -- become the
+        crate's state without crossing to the host (sc_import_state_device).  Pressures are zero until the next tick.
+        The tensors are read on the library's stream, which does not wait for torch's: they must be ready when this is
+        called (`torch.cuda.current_stream().synchronize()`, or run the crate on torch's stream, `engine.set_stream`)."""
+        n = int(particles.shape[0]) if getattr(particles, "is_cuda", False) and particles.dim() == 2 else 0
+        if n > self._engine.capacity:
+            self._grow(n)
+        self._engine.import_state(particles, velocities, ids)
+        self._cache = None
+        self._count, self._count_known = int(particles.shape[0]), True
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

@@ -25,6 +25,7 @@
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_probe.h"
+#include "sc_state.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
@@ -226,6 +227,11 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   int arrow_mode = SC_ARROWS_OFF;
   int64_t arrow_n = 0, arrow_every = 1;  // ... the list's length; velocity mode: ids that are multiples of this
   double arrow_scale = 1.0;
+  // sc_export_state_device (sc_state.h): the radix sort's (id, slot) pairs -- two sets that take turns --, the tiles'
+  // digit counts and their scan, each grown to the launch bound asked for; sc_import_state_device: the ids as 32-bit
+  // values and its two words (largest id plus one, out-of-range flag)
+  DevBuf<unsigned> stateKeys[2];
+  DevBuf<int> stateSlots[2], stateHist, stateOffs, stateSums, stateIds, stateWords;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -568,31 +574,54 @@ int check_flags(int flags) {
   return SC_OK;
 }
 
-int put_particles(sc_ctx* c, const double* xy, const double* vxy, int64_t n, bool reset, const int64_t* ids = nullptr) {
+// What every upload and append starts with: the call is allowed and the particles fit; a reset gives up a promised tick.
+int put_check(sc_ctx* c, const void* xy, const void* vxy, int64_t n, bool reset) {
   if (n < 0 || (n > 0 && (!xy || !vxy))) return fail(SC_ERR_ARG, "bad particle arrays");
   if (c->in_step) return fail(SC_ERR_STATE, "particles cannot change between sc_step_begin and sc_step_finish");
   if (c->prebinned && !reset)
     return fail(SC_ERR_STATE, "particles cannot be appended after sc_set_next_inputs promised the next tick");
+  const int64_t base = reset ? 0 : c->upper;
+  if (base + n > c->cap)
+    return fail(SC_ERR_CAPACITY, "%lld particles exceed the context capacity %lld", (long long)(base + n), (long long)c->cap);
+  if ((reset ? 0 : c->next_id) + n > std::numeric_limits<int>::max()) return fail(SC_ERR_CAPACITY, "particle ids exhausted");
+  return SC_OK;
+}
+
+// ... and ends with: n particles in DEVICE memory (P x 2 interleaved; ids 32-bit with their largest, or null: the next
+// ids) go behind the stored ones, or replace them.  After put_check.
+int put_from_device(sc_ctx* c, const double* dev_xy, const double* dev_vxy, const int* dev_ids, int64_t max_id, int64_t n,
+                    bool reset) {
   if (c->prebinned && reset) {
     const int rc = abandon_promise(c);
     if (rc) return rc;
   }
-  int64_t base = reset ? 0 : c->upper;
-  if (base + n > c->cap)
-    return fail(SC_ERR_CAPACITY, "%lld particles exceed the context capacity %lld", (long long)(base + n), (long long)c->cap);
+  const int64_t base = reset ? 0 : c->upper;
   if (reset) {
     c->next_id = 0;
     c->normals_valid = 0;
     c->halo_ring_from = c->tick;  // counts published before this belong to another state
   }
-  if (c->next_id + n > std::numeric_limits<int>::max()) return fail(SC_ERR_CAPACITY, "particle ids exhausted");
   if (n > 0) {
-    int rc = ensure_stage(c, n);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->stage_xy, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->stage_vxy, vxy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int* dev_ids = nullptr;
-    int64_t max_id = -1;
+    if (dev_ids) c->next_id = std::max<int64_t>(c->next_id, max_id + 1 - n);
+    Bracket br(c, K_APPEND);
+    hipLaunchKernelGGL(k_append, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, dev_xy, dev_vxy, (int)n, (int)c->next_id,
+                       dev_ids, c->counters, c->x, c->y, c->vx, c->vy, c->id[0], reset ? 1 : 0, (int)c->cap);
+  }
+  c->upper = base + n;
+  c->next_id += n;
+  c->live_hint_from = c->tick;  // counts published by earlier ticks do not include these particles
+  hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, c->stream, c->counters, (int)n, reset ? 1 : 0, (int)c->next_id, (int)c->cap);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int put_particles(sc_ctx* c, const double* xy, const double* vxy, int64_t n, bool reset, const int64_t* ids = nullptr) {
+  int rc = put_check(c, xy, vxy, n, reset);
+  if (rc) return rc;
+  int* dev_ids = nullptr;
+  int64_t max_id = -1;
+  if (n > 0) {
+    if ((rc = ensure_stage(c, n))) return rc;
     std::vector<int>& ids32 = c->ids_host;  // outlives the asynchronous copy below
     if (ids) {
       HIPCHK(hipStreamSynchronize(c->stream));  // an earlier copy out of ids_host has finished
@@ -604,18 +633,11 @@ int put_particles(sc_ctx* c, const double* xy, const double* vxy, int64_t n, boo
       }
       dev_ids = c->stage_ids;  // room for n ids (ensure_stage)
       HIPCHK(hipMemcpyAsync(dev_ids, ids32.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-      c->next_id = std::max<int64_t>(c->next_id, max_id + 1 - n);
     }
-    Bracket br(c, K_APPEND);
-    hipLaunchKernelGGL(k_append, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, c->stage_xy, c->stage_vxy, (int)n,
-                       (int)c->next_id, dev_ids, c->counters, c->x, c->y, c->vx, c->vy, c->id[0], reset ? 1 : 0, (int)c->cap);
+    HIPCHK(hipMemcpyAsync(c->stage_xy, xy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->stage_vxy, vxy, 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  c->upper = base + n;
-  c->next_id += n;
-  c->live_hint_from = c->tick;  // counts published by earlier ticks do not include these particles
-  hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, c->stream, c->counters, (int)n, reset ? 1 : 0, (int)c->next_id, (int)c->cap);
-  HIPCHK(hipGetLastError());
-  return SC_OK;
+  return put_from_device(c, c->stage_xy, c->stage_vxy, dev_ids, max_id, n, reset);
 }
 
 int64_t launch_bound(const sc_ctx* c) { return c->slab ? c->cap : c->upper; }
@@ -1294,6 +1316,78 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
     return check_flags(h[C_FLAGS]);
   }
   return SC_OK;
+}
+
+// ---- the state in the caller's device memory (sc_state.h) ---------------------------------------
+
+// Room for a sort of m pairs: sized by the last member, which grows last.
+static int state_ensure(sc_ctx* c, int64_t m) {
+  if (m <= c->stateSlots[1].size()) return SC_OK;
+  const int64_t cells = (m + kStateTile - 1) / kStateTile * kStateBins;  // a count per tile and digit
+  HIPCHK(c->stateHist.grow(cells, c->stream));
+  HIPCHK(c->stateOffs.grow(cells + 1, c->stream));
+  HIPCHK(c->stateSums.grow(cells / kScanPerBlock + 2, c->stream));
+  HIPCHK(c->stateKeys[0].grow(m, c->stream));
+  HIPCHK(c->stateKeys[1].grow(m, c->stream));
+  HIPCHK(c->stateSlots[0].grow(m, c->stream));
+  HIPCHK(c->stateSlots[1].grow(m, c->stream));
+  return SC_OK;
+}
+
+int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
+                           int64_t* dev_n) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_n) return fail(SC_ERR_ARG, "null count pointer");
+  if (room < 0) return fail(SC_ERR_ARG, "negative room");
+  if (((uintptr_t)dev_xy | (uintptr_t)dev_vxy) & 15) return fail(SC_ERR_ARG, "xy and vxy must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_export_state_device inside a tick");
+  const int64_t m = std::min<int64_t>(launch_bound(c), c->cap);
+  if (room < m)
+    return fail(SC_ERR_CAPACITY, "device arrays hold %lld, up to %lld particles stored", (long long)room, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = state_ensure(c, m);
+  if (rc) return rc;
+  const int tiles = (int)((m + kStateTile - 1) / kStateTile);
+  for (int pass = 0; pass < kStatePasses && m > 0; ++pass) {
+    const int in = pass & 1, shift = pass * kStateDigitBits;
+    hipLaunchKernelGGL(k_state_hist, dim3(tiles), dim3(kStateTile), 0, c->stream, c->counters,
+                       pass == 0 ? c->x.get() : nullptr, c->id[0].get(), (int)c->cap, c->stateKeys[in].get(),
+                       c->stateSlots[in].get(), (int)m, shift, tiles, c->stateHist.get());
+    if ((rc = launch_scan(c, c->stateHist, c->stateOffs, (int64_t)tiles * kStateBins, c->stateSums, nullptr))) return rc;
+    hipLaunchKernelGGL(k_state_scatter, dim3(tiles), dim3(kStateTile), 0, c->stream, c->stateKeys[in].get(),
+                       c->stateSlots[in].get(), c->stateKeys[in ^ 1].get(), c->stateSlots[in ^ 1].get(), (int)m, shift, tiles,
+                       c->stateOffs.get());
+  }
+  const StateOut o{dev_xy, dev_vxy, dev_pressure, (long long*)dev_ids, (long long*)dev_n};
+  hipLaunchKernelGGL(k_state_gather, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->counters, o, c->stateKeys[0].get(),
+                     c->stateSlots[0].get(), (int)m, (int)c->cap, c->normals_valid ? 1 : 0, c->x.get(), c->y.get(),
+                     c->vx.get(), c->vy.get(), c->P.get());
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int sc_import_state_device(sc_ctx* c, const double* dev_xy, const double* dev_vxy, const int64_t* dev_ids, int64_t n) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  int rc = put_check(c, dev_xy, dev_vxy, n, true);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  int* ids32 = nullptr;
+  int64_t max_id = -1;
+  if (dev_ids && n > 0) {
+    HIPCHK(c->stateWords.grow(2, c->stream));
+    HIPCHK(c->stateIds.grow(n, c->stream));
+    HIPCHK(hipMemsetAsync(c->stateWords, 0, 2 * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_state_check_ids, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, (const long long*)dev_ids, (int)n,
+                       c->stateIds.get(), c->stateWords.get());
+    HIPCHK(hipGetLastError());
+    int words[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(words, c->stateWords, sizeof words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (words[1]) return fail(SC_ERR_ARG, "particle id out of range");
+    ids32 = c->stateIds;
+    max_id = (int64_t)words[0] - 1;
+  }
+  return put_from_device(c, dev_xy, dev_vxy, ids32, max_id, n, true);
 }
 
 // ---- rendering (sc_render.h) ------------------------------------------------------------------

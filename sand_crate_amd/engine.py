@@ -60,6 +60,20 @@ class PackedInputs:
         self.struct, self.ref, self._seg, self._pad, self._bodies = t, C.byref(t), seg, pad, arr
 
 
+def _state_tensor(t, name: str, dtype: str, tail: tuple, device: int, rows: int | None = None) -> int:
+    """The number of rows of `t` once it is what the device state calls take: a contiguous CUDA tensor on `device` of
+    this dtype and shape (rows, *tail).  ValueError otherwise -- before the library is touched, as `render(out=)` does."""
+    want = f"{name} must be a contiguous CUDA {dtype} tensor of shape ({'N' if rows is None else rows}{''.join(f', {k}' for k in tail)}) on cuda:{device}"
+    if not getattr(t, "is_cuda", False) or str(getattr(t, "dtype", None)) != f"torch.{dtype}" or not t.is_contiguous():
+        raise ValueError(want)
+    shape = tuple(t.shape)
+    if len(shape) != 1 + len(tail) or shape[1:] != tuple(tail) or (rows is not None and shape[0] != rows):
+        raise ValueError(want)
+    if t.device.index != device:
+        raise ValueError(want)
+    return int(shape[0])
+
+
 class Engine:
     def __init__(self, capacity: int, device: int = 0):
         self._lib = N.load()
@@ -129,6 +143,39 @@ class Engine:
         N.check(self._lib.sc_download_state(self._ctx, N.dptr(xy), N.dptr(vxy), N.dptr(pr), N.i64ptr(ids), room, C.byref(n)))
         k = n.value
         return xy[:k].copy(), vxy[:k].copy(), pr[:k].copy(), ids[:k].copy()
+
+    # -- the state in torch's memory (sc_export_state_device / sc_import_state_device; the rule is tests/state_spec.py)
+    def export_state(self, particles=None, velocities=None, pressure=None, ids=None, *, count, room: int | None = None):
+        """`download()` into CUDA tensors, without the host: `particles` and `velocities` float64 (R, 2), `pressure`
+        float64 (R,), `ids` int64 (R,) -- any of them None -- and `count`, int64 (1,), which receives n.  Rows 0..n-1 are
+        written in particle-index order, the rest is left alone.  `room` defaults to R, the tensors' common row count (0
+        without tensors).  Enqueued on the context's stream, no synchronisation: the library's stream does not wait for
+        torch's, so the tensors must not be in use when this is called and are read after `synchronize()` (or run the
+        engine on torch's stream, `set_stream`).  Returns `count`."""
+        rows = None
+        for t, name, dtype, tail in ((particles, "particles", "float64", (2,)), (velocities, "velocities", "float64", (2,)),
+                                     (pressure, "pressure", "float64", ()), (ids, "ids", "int64", ())):
+            if t is not None:
+                rows = _state_tensor(t, name, dtype, tail, self.device, rows)
+        _state_tensor(count, "count", "int64", (), self.device, 1)
+        room = (rows or 0) if room is None else int(room)
+        if rows is not None and room > rows:
+            raise ValueError(f"room {room} exceeds the tensors' {rows} rows")
+        ptr = lambda t: None if t is None else N._P(t.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_export_state_device(self._ctx, ptr(particles), ptr(velocities), ptr(pressure), ptr(ids), room,
+                                                 ptr(count)))
+        return count
+
+    def import_state(self, particles, velocities, ids=None) -> None:
+        """`upload` (ids None: particle i gets id i) or `upload_with_ids` from CUDA tensors, without the host: float64
+        (n, 2) twice and int64 (n,).  The tensors are read on the context's stream, which does not wait for torch's:
+        they must be ready when this is called.  With ids it synchronises once (the largest id comes back)."""
+        n = _state_tensor(particles, "particles", "float64", (2,), self.device)
+        _state_tensor(velocities, "velocities", "float64", (2,), self.device, n)
+        if ids is not None:
+            _state_tensor(ids, "ids", "int64", (), self.device, n)
+        N.check(self._lib.sc_import_state_device(self._ctx, N._P(particles.data_ptr()), N._P(velocities.data_ptr()),
+                                                 None if ids is None else N._P(ids.data_ptr()), n))
 
     # -- frames
     @staticmethod
