@@ -69,7 +69,9 @@ constexpr int kJpegDct[8][8] = {{1448, 1448, 1448, 1448, 1448, 1448, 1448, 1448}
                                 {400, -1138, 1703, -2009, 2009, -1703, 1138, -400}};
 
 // The longest a block's codes can be: a DC code of 11 bits plus 11 extra bits, and 63 AC codes of 16 bits plus 10
-// (the quantised AC coefficients stay below 1024 in magnitude, so size 10 is the largest category).
+// (the quantised AC coefficients stay below 1024 in magnitude, so size 10 is the largest category: the sign patterns of
+// the (0,4), (4,0) and (4,4) basis functions reach 1020 at quality 100 and nothing reaches more, which
+// tests/test_jpeg_cases_cpu.py::test_quantised_ac_coefficients_stay_below_1024 pins).
 constexpr int kJpegBlockBits = 22 + 63 * 26;
 constexpr int kJpegWaveBits = 64 * kJpegBlockBits + 32;          // one round of the rows kernel, word offset included
 constexpr int kJpegWindowWords = (kJpegWaveBits + 31) / 32 + 2;  // its LDS window (13.3 KB)
