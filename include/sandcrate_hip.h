@@ -579,6 +579,50 @@ int sc_export_state_device(sc_ctx* ctx, double* dev_xy, double* dev_vxy, double*
 int sc_import_state_device(sc_ctx* ctx, const double* dev_xy, const double* dev_vxy, const int64_t* dev_ids /* may be NULL */,
                            int64_t n);
 
+/* Fixed-radius pair lists in DEVICE memory of the caller (e.g. torch CUDA tensors), as a CSR edge list in index order:
+ * which points lie within `radius` of which.  tests/pairs_spec.py is the rule: with all arithmetic in separately rounded
+ * float64, (i, j) is a pair iff i != j and fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius), dx = fl(x_i - x_j); with
+ * SC_PAIRS_HALF in `flags` only j > i is kept.  A point with a coordinate that is not finite has no partners and is
+ * nobody's; coincident points are each other's.  No cap on a row's length, any radius whose square is a normal finite
+ * float64 (about 1.5e-154 .. 1.3e154).  The result is a pure function of the points.
+ *
+ * sc_pairs_count_device  the points are the n rows of dev_xy (n x 2 interleaved float64, aligned to 16 bytes), or with
+ *     dev_xy NULL the state: the particles exactly as sc_export_state_device would write them at the same point of the
+ *     stream -- ascending id, slots whose x is not finite skipped -- so index i is the row of that export, not the id, and
+ *     n is known on the device only (`n` is then ignored).  Writes dev_offsets[0 .. n], int64: the exclusive scan of the
+ *     row lengths, so dev_offsets[n] = E, the number of pairs, which may exceed 2^32; entries past n are left as they
+ *     were.  dev_counts[0] = n, dev_counts[1] = E.  `room_rows` is the room of dev_offsets in rows (it holds room_rows + 1
+ *     entries) and must be at least the host's bound of the point count: n, or for the state the bound
+ *     sc_export_state_device uses.  The domain: every finite coordinate c needs fl(|c| / radius) < 2^31.  A point outside
+ *     is found on the device: dev_counts[1] = -1 then, dev_counts[0] = n, and nothing else is written, here or by the fill
+ *     -- no host round trip.  The grid of the search stays in the context's workspace for sc_pairs_fill_device.
+ * sc_pairs_fill_device   row i's partners go to dev_partners[dev_offsets[i] ...], int64 and ascending in j, and -- unless
+ *     dev_d2 is NULL -- each pair's squared distance next to it: the very number that was compared, no square root.  An
+ *     entry e is written only when e < room_pairs: a list longer than the room is clipped there, nothing is written past
+ *     the room.  Reads the workspace of the last count of this context, not the caller's points or offsets.
+ *     SC_ERR_STATE when there is no such count, or when a tick, an upload, an append, an emission, an import or a track
+ *     load has touched the state since (whichever form the count had).
+ * Both enqueue on the context's stream only: nothing synchronises, nothing reaches the host, and the context's stream does
+ * not wait for other streams -- the arrays must be ready, and not in use elsewhere, when the calls are made.  Like the
+ * export they read the state only: no counter, look-ahead promise, RNG position, pending error flag or particle array
+ * changes, and their launches are not bracketed by the timing events.
+ *     The search bins the points into cells a little larger than the radius -- h = radius (1 + 2^-20), so that the
+ * rounding of x / h cannot separate a pair by more than one cell (csrc/sc_pairs.h has the argument) -- in a hashed table of
+ * at least two buckets per point, with a stable radix sort of (bucket, index) pairs, counts each row's partners in the
+ * nine cells around its point, scans the counts in 64 bits on two levels, and fills each row by merging its nine runs.
+ * No workgroup waits for another, no floating-point atomics, and no atomic's order reaches the output.  The workspace
+ * belongs to the context: about 100 bytes per point of the host's bound, grown -- which synchronises once -- to the largest
+ * bound asked for.
+ *     SC_ERR_STATE between sc_step_begin and sc_step_finish, and for the state form on a context in slab mode
+ * (sc_set_slab: partners across a cut live on another rank).  SC_ERR_ARG for a null context, null dev_offsets, dev_counts
+ * or (with room) dev_partners, a misaligned dev_xy, a negative n or room, unknown flags, or a radius outside the range
+ * above.  SC_ERR_CAPACITY when room_rows is below the host's bound, or for more than 2^28 points -- checked before
+ * anything is launched, the arrays are then untouched. */
+enum { SC_PAIRS_HALF = 1 };
+int sc_pairs_count_device(sc_ctx* ctx, const double* dev_xy /* NULL: the state */, int64_t n, double radius, int32_t flags,
+                          int64_t* dev_offsets, int64_t room_rows, int64_t* dev_counts /* [2]: n, E */);
+int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* may be NULL */, int64_t room_pairs);
+
 #ifdef __cplusplus
 }
 #endif

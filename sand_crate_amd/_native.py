@@ -25,6 +25,16 @@ PROBE_BLOCK, PROBE_BLOCKS = 1024, 256  # the probe's fixed launch (csrc/sc_probe
 # the device export's launches (csrc/sc_state.h, sc_kernels.h): keys per workgroup of a sorting pass (kStateTile), counts
 # per workgroup of the scan between its two kernels (kScanPerBlock), rows per workgroup of the gather (kBlock)
 STATE_TILE, STATE_SCAN_BLOCK, STATE_GATHER_BLOCK = 256, 2048, 256
+# the pair search's launches and table (csrc/sc_pairs.h, sc_state.h, sc_kernels.h): rows per workgroup of its row kernels
+# (kBlock), keys per workgroup of a pass of the binning sort (kStateTile), entries per workgroup of the scans
+# (kScanPerBlock); the hashed table has the smallest power of two of buckets that is at least PAIRS_LOAD per point and
+# PAIRS_MIN_BUCKETS, a cell (cx, cy) -- floor(x / h), floor(y / h) as 32-bit words, h = radius * PAIRS_CELL_FACTOR -- lies in
+# bucket `pairs_bucket(cx, cy, buckets)`
+PAIRS_BLOCK, PAIRS_SORT_TILE, PAIRS_SCAN_BLOCK = 256, 256, 2048
+PAIRS_LOAD, PAIRS_MIN_BUCKETS = 2, 256
+PAIRS_HASH_X, PAIRS_HASH_Y, PAIRS_HASH_MIX = 0x9E3779B1, 0x85EBCA77, 0x2C1B3C6D
+PAIRS_CELL_FACTOR = 1.0 + 2.0 ** -20
+PAIRS_HALF = 1
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -164,7 +174,27 @@ SIGNATURES = {
     "sc_track_load": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     "sc_export_state_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
     "sc_import_state_device": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
+    "sc_pairs_count_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32, _P, C.c_int64, _P]),
+    "sc_pairs_fill_device": (C.c_int, [_P, _P, _P, C.c_int64]),
 }
+
+
+def pairs_buckets(bound: int) -> int:
+    """The size of the pair search's hashed table for a host bound of `bound` points."""
+    t = PAIRS_MIN_BUCKETS
+    while t < PAIRS_LOAD * bound:
+        t *= 2
+    return t
+
+
+def pairs_bucket(cx: int, cy: int, buckets: int) -> int:
+    """The bucket of cell (cx, cy) in a table of `buckets` buckets (csrc/sc_pairs.h: pairs_bucket), in 32-bit arithmetic."""
+    m = 0xFFFFFFFF
+    v = (((cx & m) * PAIRS_HASH_X) & m) ^ (((cy & m) * PAIRS_HASH_Y) & m)
+    v ^= v >> 15
+    v = (v * PAIRS_HASH_MIX) & m
+    v ^= v >> 13
+    return v & (buckets - 1)
 
 _lib = None
 

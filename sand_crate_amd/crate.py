@@ -96,6 +96,11 @@ def arrow_ends(pairs) -> np.ndarray:
         return np.stack([start, start + d], axis=1)
 
 
+def _point_rows(points) -> int:
+    """The rows of a caller's (n, 2) tensor of points; what is no such tensor is left to the engine's check (0 rows)."""
+    return int(points.shape[0]) if getattr(points, "is_cuda", False) and len(points.shape) == 2 else 0
+
+
 class Crate:
     def __init__(self, world_config: WorldConfig, *, device: int = 0, noise: str = "host", noise_seed: int = 0,
                  capacity: int | None = None) -> None:
@@ -247,6 +252,55 @@ class Crate:
         self._engine.import_state(particles, velocities, ids)
         self._cache = None
         self._count, self._count_known = int(particles.shape[0]), True
+
+    def pair_tensors(self, radius: float | None = None, *, points=None, half: bool = False, squared_distances: bool = False,
+                     max_pairs: int | None = None):
+        """Which particles lie within `radius` (default: `diameter`) of which, as a CSR edge list in torch CUDA tensors on
+        the crate's device, searched on the GPU (sc_pairs_count_device / sc_pairs_fill_device): ``(offsets, partners[, d2])``
+        -- int64 (n + 1,), int64 (E,), float64 (E,).  Row i's partners are ``partners[offsets[i]:offsets[i + 1]]``, ascending;
+        i and j are rows of `state_tensors()` at the same point of the stream, not ids.  (i, j) is a pair iff i != j and
+        dx*dx + dy*dy <= radius*radius in separately rounded float64 (tests/pairs_spec.py); `half` keeps j > i only;
+        `squared_distances` adds the number that was compared, per pair.  A particle with a coordinate that is not finite
+        has no partners.  `points`, a float64 (n, 2) CUDA tensor, is searched instead of the state.  No cap on a row's
+        length; `sand_crate_amd.pairs.edge_index` turns the result into a (2, E) tensor.
+
+        By default the call synchronises once between counting and filling, reads n and E (16 bytes) and returns tensors
+        cut to them; a coordinate with |c| / radius >= 2^31 raises ValueError.  With `max_pairs=K` nothing synchronises:
+        `offsets` comes at capacity + 1 entries (n + 1 with `points`), `partners` and `d2` at K entries, and last the int64
+        `counts` tensor (n, E): entries of `offsets` past n and of `partners` past min(E, K) are uninitialised, E > K means
+        the list was clipped at K entries, E = -1 is the domain error (nothing else was written).  The tensors are written
+        on the library's stream, and the library's stream does not wait for torch's: read them after `synchronize()`, and
+        have `points` ready before the call -- or run the crate on torch's stream, `engine.set_stream`, and everything
+        torch enqueues afterwards sees them."""
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(self.diameter if radius is None else radius)
+        rows = eng.capacity if points is None else _point_rows(points)
+        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        sync = max_pairs is None
+        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=half)
+        if sync:
+            eng.synchronize()
+            n, total = (int(v) for v in counts.cpu())
+            if total < 0:
+                raise ValueError(f"pair_tensors: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
+            if points is None:
+                self._count, self._count_known = n, True
+        else:
+            total = int(max_pairs)
+            if total < 0:
+                raise ValueError("max_pairs must not be negative")
+        partners = torch.empty(total, dtype=torch.int64, device=dev)
+        d2 = torch.empty(total, dtype=torch.float64, device=dev) if squared_distances else None
+        eng.pairs_fill(partners, d2)
+        if sync:
+            eng.synchronize()
+            return (offsets[:n + 1], partners) + ((d2,) if squared_distances else ())
+        return (offsets, partners) + ((d2,) if squared_distances else ()) + (counts,)
 
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()

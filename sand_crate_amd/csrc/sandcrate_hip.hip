@@ -26,6 +26,7 @@
 #include "sc_kernels.h"
 #include "sc_probe.h"
 #include "sc_state.h"
+#include "sc_pairs.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
@@ -232,6 +233,21 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   // values and its two words (largest id plus one, out-of-range flag)
   DevBuf<unsigned> stateKeys[2];
   DevBuf<int> stateSlots[2], stateHist, stateOffs, stateSums, stateIds, stateWords;
+  // sc_pairs_count_device / sc_pairs_fill_device (sc_pairs.h): the points in index order, the (bucket, index) pairs of the
+  // binning sort -- two sets that take turns -- with the tiles' digit counts and their scan, the buckets' counts and
+  // starts, the members' positions and cells in bucket order, the row lengths, their 64-bit scan with its block sums, the
+  // domain flag and the two words (n, E); each grown to the largest bound asked for.  `pairs_valid`: the workspace holds
+  // the grid of a count, and nothing has changed the state since.
+  DevBuf<XY> pairsXY, pairsSXY;
+  DevBuf<uint2> pairsCell;
+  DevBuf<unsigned> pairsKeys[2];
+  DevBuf<int> pairsIdx[2], pairsHist, pairsHistOffs, pairsHistSums, pairsBucketCount, pairsBucketStart, pairsBucketSums;
+  DevBuf<int> pairsRowLen, pairsFlag;
+  DevBuf<long long> pairsOffs, pairsSums, pairsWords;
+  bool pairs_valid = false;
+  int64_t pairs_m = 0;   // ... the bound its launches were sized by
+  int pairs_sorted = 0;  // ... which of the two sets holds the sorted pairs
+  PairsGrid pairs_grid{};
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -596,6 +612,7 @@ int put_from_device(sc_ctx* c, const double* dev_xy, const double* dev_vxy, cons
     if (rc) return rc;
   }
   const int64_t base = reset ? 0 : c->upper;
+  c->pairs_valid = false;
   if (reset) {
     c->next_id = 0;
     c->normals_valid = 0;
@@ -1032,6 +1049,7 @@ int sc_step_begin(sc_ctx* c) {
   }
   int rc = make_world(c);
   if (rc) return rc;
+  c->pairs_valid = false;
   const World& w = c->w;
   int grid = grid_for(launch_bound(c));
   int cap = (int)c->cap;
@@ -1334,17 +1352,9 @@ static int state_ensure(sc_ctx* c, int64_t m) {
   return SC_OK;
 }
 
-int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
-                           int64_t* dev_n) {
-  if (!c) return fail(SC_ERR_ARG, "null context");
-  if (!dev_n) return fail(SC_ERR_ARG, "null count pointer");
-  if (room < 0) return fail(SC_ERR_ARG, "negative room");
-  if (((uintptr_t)dev_xy | (uintptr_t)dev_vxy) & 15) return fail(SC_ERR_ARG, "xy and vxy must be aligned to 16 bytes");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_export_state_device inside a tick");
-  const int64_t m = std::min<int64_t>(launch_bound(c), c->cap);
-  if (room < m)
-    return fail(SC_ERR_CAPACITY, "device arrays hold %lld, up to %lld particles stored", (long long)room, (long long)m);
-  HIPCHK(hipSetDevice(c->device));
+// Ranks the m slots of the launch by id into stateKeys[0] / stateSlots[0]: slots that are not stored, or whose x is not
+// finite, carry kStateDead and come last.
+static int state_rank(sc_ctx* c, int64_t m) {
   int rc = state_ensure(c, m);
   if (rc) return rc;
   const int tiles = (int)((m + kStateTile - 1) / kStateTile);
@@ -1358,6 +1368,22 @@ int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* d
                        c->stateSlots[in].get(), c->stateKeys[in ^ 1].get(), c->stateSlots[in ^ 1].get(), (int)m, shift, tiles,
                        c->stateOffs.get());
   }
+  return SC_OK;
+}
+
+int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
+                           int64_t* dev_n) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_n) return fail(SC_ERR_ARG, "null count pointer");
+  if (room < 0) return fail(SC_ERR_ARG, "negative room");
+  if (((uintptr_t)dev_xy | (uintptr_t)dev_vxy) & 15) return fail(SC_ERR_ARG, "xy and vxy must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_export_state_device inside a tick");
+  const int64_t m = std::min<int64_t>(launch_bound(c), c->cap);
+  if (room < m)
+    return fail(SC_ERR_CAPACITY, "device arrays hold %lld, up to %lld particles stored", (long long)room, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = state_rank(c, m);
+  if (rc) return rc;
   const StateOut o{dev_xy, dev_vxy, dev_pressure, (long long*)dev_ids, (long long*)dev_n};
   hipLaunchKernelGGL(k_state_gather, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->counters, o, c->stateKeys[0].get(),
                      c->stateSlots[0].get(), (int)m, (int)c->cap, c->normals_valid ? 1 : 0, c->x.get(), c->y.get(),
@@ -1388,6 +1414,137 @@ int sc_import_state_device(sc_ctx* c, const double* dev_xy, const double* dev_vx
     max_id = (int64_t)words[0] - 1;
   }
   return put_from_device(c, dev_xy, dev_vxy, ids32, max_id, n, true);
+}
+
+// ---- pair lists (sc_pairs.h) --------------------------------------------------------------------
+
+constexpr int64_t kPairsMaxPoints = (int64_t)1 << 28;
+
+static unsigned pairs_buckets(int64_t m) {
+  unsigned t = kPairsMinBuckets;
+  while ((int64_t)t < kPairsLoad * m) t <<= 1;
+  return t;
+}
+
+// Room for a search over m points in `buckets` buckets: each group is sized by its last member, which grows last.
+static int pairs_ensure(sc_ctx* c, int64_t m, int64_t buckets) {
+  HIPCHK(c->pairsFlag.grow(1, c->stream));
+  HIPCHK(c->pairsWords.grow(PW_WORDS, c->stream));
+  if (buckets + 1 > c->pairsBucketStart.size()) {
+    HIPCHK(c->pairsBucketCount.grow(buckets, c->stream));
+    HIPCHK(c->pairsBucketSums.grow(buckets / kScanPerBlock + 2, c->stream));
+    HIPCHK(c->pairsBucketStart.grow(buckets + 1, c->stream));
+  }
+  if (m + 1 > c->pairsOffs.size()) {
+    const int64_t cells = (m + kStateTile - 1) / kStateTile * kStateBins;  // a count per tile and digit
+    HIPCHK(c->pairsHist.grow(cells, c->stream));
+    HIPCHK(c->pairsHistOffs.grow(cells + 1, c->stream));
+    HIPCHK(c->pairsHistSums.grow(cells / kScanPerBlock + 2, c->stream));
+    for (int k = 0; k < 2; ++k) {
+      HIPCHK(c->pairsKeys[k].grow(m, c->stream));
+      HIPCHK(c->pairsIdx[k].grow(m, c->stream));
+    }
+    HIPCHK(c->pairsXY.grow(m, c->stream));
+    HIPCHK(c->pairsSXY.grow(m, c->stream));
+    HIPCHK(c->pairsCell.grow(m, c->stream));
+    HIPCHK(c->pairsRowLen.grow(m, c->stream));
+    HIPCHK(c->pairsSums.grow(m / kScanPerBlock + 2, c->stream));
+    HIPCHK(c->pairsOffs.grow(m + 1, c->stream));
+  }
+  return SC_OK;
+}
+
+int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double radius, int32_t flags, int64_t* dev_offsets,
+                          int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_offsets || !dev_counts) return fail(SC_ERR_ARG, "null offsets or counts pointer");
+  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
+  if (flags & ~SC_PAIRS_HALF) return fail(SC_ERR_ARG, "unknown flags %d", flags);
+  const double r2 = radius * radius;
+  if (!(radius > 0) || !std::isfinite(radius) || !std::isfinite(r2) || r2 < std::numeric_limits<double>::min())
+    return fail(SC_ERR_ARG, "the radius must be finite and positive, and so must its square (about 1.5e-154 .. 1.3e154)");
+  if (dev_xy && n < 0) return fail(SC_ERR_ARG, "negative point count");
+  if ((uintptr_t)dev_xy & 15) return fail(SC_ERR_ARG, "the points must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_count_device inside a tick");
+  if (!dev_xy && c->slab)
+    return fail(SC_ERR_STATE, "the pairs of the state are not available in slab mode: partners across a cut live on another rank");
+  const int64_t m = dev_xy ? n : std::min<int64_t>(launch_bound(c), c->cap);
+  if (m > kPairsMaxPoints) return fail(SC_ERR_CAPACITY, "%lld points, at most %lld", (long long)m, (long long)kPairsMaxPoints);
+  if (room_rows < m)
+    return fail(SC_ERR_CAPACITY, "offsets hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  c->pairs_valid = false;
+  const unsigned buckets = pairs_buckets(m);
+  int rc = pairs_ensure(c, m, buckets);
+  if (rc) return rc;
+  PairsGrid g{};
+  g.radius = radius;
+  g.h = radius * kPairsCellFactor;
+  g.r2 = r2;
+  g.mask = buckets - 1;
+  g.half = (flags & SC_PAIRS_HALF) ? 1 : 0;
+  const int grid = grid_for(m);
+  if (!dev_xy) {
+    if ((rc = state_rank(c, m))) return rc;
+    hipLaunchKernelGGL(k_pairs_gather, dim3(grid), dim3(kBlock), 0, c->stream, c->stateKeys[0].get(), c->stateSlots[0].get(),
+                       (int)m, c->x.get(), c->y.get(), c->pairsXY.get(), c->pairsWords.get());
+  }
+  HIPCHK(hipMemsetAsync(c->pairsFlag, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(c->pairsBucketCount, 0, (size_t)buckets * sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_pairs_key, dim3(grid), dim3(kBlock), 0, c->stream, g, dev_xy ? (const XY*)dev_xy : c->pairsXY.get(),
+                     c->pairsXY.get(), dev_xy ? (long long)n : -1LL, c->pairsWords.get(), (int)m, c->pairsKeys[0].get(),
+                     c->pairsIdx[0].get(), c->pairsBucketCount.get(), c->pairsFlag.get());
+  // the binning sort: the keys are 0 .. buckets (a dead point's), so as many digits as `buckets` has
+  int bits = 1;
+  while ((buckets >> bits) != 0) ++bits;
+  const int passes = m > 0 ? (bits + kStateDigitBits - 1) / kStateDigitBits : 0;
+  const int tiles = (int)((m + kStateTile - 1) / kStateTile);
+  int in = 0;
+  for (int pass = 0; pass < passes; ++pass, in ^= 1) {
+    const int shift = pass * kStateDigitBits;
+    hipLaunchKernelGGL(k_state_hist, dim3(tiles), dim3(kStateTile), 0, c->stream, (const int*)nullptr, (const double*)nullptr,
+                       (const int*)nullptr, 0, c->pairsKeys[in].get(), c->pairsIdx[in].get(), (int)m, shift, tiles,
+                       c->pairsHist.get());
+    if ((rc = launch_scan(c, c->pairsHist, c->pairsHistOffs, (int64_t)tiles * kStateBins, c->pairsHistSums, nullptr))) return rc;
+    hipLaunchKernelGGL(k_state_scatter, dim3(tiles), dim3(kStateTile), 0, c->stream, c->pairsKeys[in].get(),
+                       c->pairsIdx[in].get(), c->pairsKeys[in ^ 1].get(), c->pairsIdx[in ^ 1].get(), (int)m, shift, tiles,
+                       c->pairsHistOffs.get());
+  }
+  if ((rc = launch_scan(c, c->pairsBucketCount, c->pairsBucketStart, buckets, c->pairsBucketSums, nullptr))) return rc;
+  hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairsKeys[in].get(), c->pairsIdx[in].get(),
+                     (int)m, c->pairsXY.get(), c->pairsFlag.get(), c->pairsSXY.get(), c->pairsCell.get());
+  hipLaunchKernelGGL(k_pairs_count, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairsWords.get(), c->pairsFlag.get(), (int)m,
+                     c->pairsXY.get(), c->pairsBucketStart.get(), c->pairsSXY.get(), c->pairsCell.get(), c->pairsIdx[in].get(),
+                     c->pairsRowLen.get());
+  const int nb = (int)(m / kScanPerBlock + 1);  // entry n <= m lies in one of them
+  hipLaunchKernelGGL(k_scan64_local, dim3(nb), dim3(kBlock), 0, c->stream, c->pairsRowLen.get(), c->pairsOffs.get(),
+                     c->pairsWords.get(), c->pairsFlag.get(), c->pairsSums.get());
+  hipLaunchKernelGGL(k_scan64_fix, dim3(nb), dim3(kBlock), 0, c->stream, c->pairsOffs.get(), (long long*)dev_offsets,
+                     c->pairsWords.get(), c->pairsFlag.get(), c->pairsSums.get(), (long long*)dev_counts);
+  HIPCHK(hipGetLastError());
+  c->pairs_valid = true;
+  c->pairs_m = m;
+  c->pairs_sorted = in;
+  c->pairs_grid = g;
+  return SC_OK;
+}
+
+int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64_t room_pairs) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (room_pairs < 0) return fail(SC_ERR_ARG, "negative room");
+  if (!dev_partners && room_pairs > 0) return fail(SC_ERR_ARG, "null partners pointer");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_fill_device inside a tick");
+  if (!c->pairs_valid)
+    return fail(SC_ERR_STATE, "no pair count to fill from: sc_pairs_count_device comes first, and the state must not change in between");
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t m = c->pairs_m;
+  if (room_pairs == 0) return SC_OK;
+  hipLaunchKernelGGL(k_pairs_fill, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->pairs_grid, c->pairsWords.get(),
+                     c->pairsFlag.get(), (int)m, c->pairsXY.get(), c->pairsOffs.get(), c->pairsBucketStart.get(),
+                     c->pairsSXY.get(), c->pairsCell.get(), c->pairsIdx[c->pairs_sorted].get(), (long long*)dev_partners, dev_d2,
+                     (long long)room_pairs);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
 }
 
 // ---- rendering (sc_render.h) ------------------------------------------------------------------
@@ -2432,6 +2589,7 @@ int sc_track_load(sc_ctx* c, const uint8_t* frame, int64_t n_bytes, int32_t plai
     const int rc = abandon_promise(c);
     if (rc) return rc;
   }
+  c->pairs_valid = false;
   HIPCHK(c->trackLoad.grow(n_bytes, c->stream));
   HIPCHK(hipMemcpyAsync(c->trackLoad, frame, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
   TrackLoad a{};
@@ -2731,6 +2889,7 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   if (c->in_step) return fail(SC_ERR_STATE, "particles cannot change between sc_step_begin and sc_step_finish");
   if (c->prebinned) return fail(SC_ERR_STATE, "particles cannot be emitted after sc_set_next_inputs promised the next tick");
   if (n_sources == 0) return SC_OK;
+  c->pairs_valid = false;
   // the sources go to the device in groups of kMaxSources, one k_rng_emit launch per group in source order on the
   // stream: each launch continues the stream and reads the stored count the previous one left, as one launch would
   std::vector<SourcesK> groups((n_sources + kMaxSources - 1) / kMaxSources);

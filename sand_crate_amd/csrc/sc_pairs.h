@@ -1,0 +1,294 @@
+// Fixed-radius pair lists on the device (sc_pairs_count_device / sc_pairs_fill_device): for n points and a radius, the
+// CSR list of all (i, j), i != j, whose rounded squared distance is at most the rounded radius * radius -- offsets (the
+// exclusive scan of the row lengths, 64 bit) and partners, row by row and ascending in j.  The rule is specified in NumPy
+// by tests/pairs_spec.py; the result is a pure function of the points.  Included once by sandcrate_hip.hip.
+//
+// The points are the caller's array, or the state in particle-index order: the export's ranking (sc_state.h) and
+// k_pairs_gather.  Either way they are copied into the context's workspace, so the fill does not read the caller's memory
+// again.  Then
+//   k_pairs_key     the cell of every point, (floor(x / h), floor(y / h)), its bucket in a hashed table of kPairsLoad * n
+//                   buckets (a power of two; pairs_bucket below) and the bucket's count (integer atomics: a count does not
+//                   depend on their order).  The key of a point is its bucket; a point with a coordinate that is not
+//                   finite gets the key `buckets`, which sorts behind all of them: it is in no bucket, so it is
+//                   nobody's partner.  The same kernel raises the domain flag (below);
+//   k_state_hist / k_scan_* / k_state_scatter (sc_state.h)  the stable radix sort of (bucket, index) pairs, as many passes
+//                   of eight bits as the bucket index has: every bucket's members end up contiguous and ascending in index;
+//   k_scan_* over the buckets' counts: where every bucket starts;
+//   k_pairs_place   the members' positions and cells in that order (a candidate is then one 16-byte and one 8-byte read);
+//   k_pairs_count   a thread per row walks the buckets of its point's nine cells and counts the partners;
+//   k_scan64_local / k_scan64_fix  the exclusive scan of the row lengths in 64 bits -- two levels like k_scan_local /
+//                   k_scan_fix, no workgroup waits for another -- into the workspace and the caller's offsets, and E;
+//   k_pairs_fill    a thread per row merges its nine runs (each ascending in j) by always taking the smallest head; the
+//                   cursors live in LDS (a dynamically indexed register array would go to scratch).
+// A hashed table: the bounding box is known on the device only, and a loaded state may be arbitrarily sparse.  Several of
+// one point's nine cells may share a bucket, so a candidate is accepted only when its OWN cell is the cell looked for:
+// every candidate is then seen exactly once.  No floating-point atomics, nothing that decides the output depends on the
+// order of an atomic.
+//
+// The cell rule.  The decision is d2 = fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius) with dx = fl(x_i - x_j), never the
+// cells: the 3 x 3 search must only never lose such a pair.  With radius^2 a normal finite number (checked on the host),
+// a pair has |x_i - x_j| <= radius (1 + 2^-50): three roundings on the way to d2, one in radius^2.  The computed cell is
+// floor(fl(x / h)); fl(x / h) is off by at most 2^-53 |x / h| <= 2^-22 cells inside the domain |x| / radius < 2^31 (so
+// 0.03 / 0.01 may well floor to 3 where 0.03 < 3 * 0.01).  With h = fl(radius (1 + 2^-20)) the computed quotients of a
+// pair differ by at most (1 + 2^-50) / ((1 + 2^-20)(1 - 2^-53)) + 2^-21 < 1, and two numbers that differ by at most 1
+// have floors that differ by at most 1.  The same for y.  So the cell is a little larger than the radius, by a factor the
+// rounding of the division cannot use up at the largest cell index there is.
+// The domain: every finite coordinate needs fl(|c| / radius) < 2^31, so that its cell is an int (h > radius: its quotient
+// is no larger).  k_pairs_key raises a flag otherwise; every later kernel of the count and of the fill returns at once when
+// it is up, except that E = -1 is written: no host round trip.  Inside the domain |cell| <= 2^31 / (1 + 2^-20), 2047
+// short of the ends of int, so cx +- 1 does not overflow (the cells are kept as unsigned words all the same).
+#pragma once
+#include "sc_device.h"
+#include "sc_kernels.h"
+#include "sc_state.h"
+
+namespace sc {
+
+constexpr int kPairsLoad = 2;               // buckets per point, at least (then rounded up to a power of two)
+constexpr unsigned kPairsMinBuckets = 256;
+constexpr unsigned kPairsHashX = 0x9E3779B1u, kPairsHashY = 0x85EBCA77u, kPairsHashMix = 0x2C1B3C6Du;
+constexpr double kPairsCellFactor = 1.0 + 1.0 / 1048576.0;  // h = radius * (1 + 2^-20)
+constexpr double kPairsDomain = 2147483648.0;                // |c| / radius must stay below 2^31
+
+// the workspace's 64-bit words
+enum PairsWord { PW_N = 0, PW_E = 1, PW_WORDS = 2 };
+
+struct PairsGrid {
+  double h, radius, r2;
+  unsigned mask;  // buckets - 1
+  int half;       // keep j > i only
+};
+
+__device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsigned mask) {
+  unsigned v = (cx * kPairsHashX) ^ (cy * kPairsHashY);
+  v ^= v >> 15;
+  v *= kPairsHashMix;
+  v ^= v >> 13;
+  return v & mask;
+}
+
+__device__ __forceinline__ unsigned pairs_cell(double c, double h) { return (unsigned)(int)floor(c / h); }
+
+// The state form: row k is the slot with the k-th smallest id, as in k_state_gather; n is the border to kStateDead.
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_gather(const unsigned* __restrict__ keys, const int* __restrict__ slots, int m, const double* __restrict__ x,
+                   const double* __restrict__ y, XY* __restrict__ xy, long long* __restrict__ words) {
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k == 0 && (m == 0 || keys[0] == kStateDead)) words[PW_N] = 0;
+  if (k >= m) return;
+  if (keys[k] == kStateDead) return;
+  if (k == m - 1 || keys[k + 1] == kStateDead) words[PW_N] = (long long)k + 1;
+  const int s = slots[k];
+  xy[k] = XY{x[s], y[s]};
+}
+
+// `n_host` >= 0: the caller's points, n is known (and written to words); -1: xy is the workspace, n is words[PW_N].
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_key(PairsGrid g, const XY* __restrict__ src, XY* __restrict__ xy, long long n_host, long long* __restrict__ words,
+                int m, unsigned* __restrict__ keys, int* __restrict__ index, int* __restrict__ bucketCount,
+                int* __restrict__ flag) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long long n = n_host >= 0 ? n_host : words[PW_N];
+  if (i == 0 && n_host >= 0) words[PW_N] = n_host;
+  if (i >= m) return;
+  unsigned key = g.mask + 1u;  // dead: behind every bucket
+  if (i < n) {
+    const XY p = src[i];
+    if (src != xy) xy[i] = p;
+    const double ax = fabs(p.x), ay = fabs(p.y);
+    const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
+    if ((fx && !(ax / g.radius < kPairsDomain)) || (fy && !(ay / g.radius < kPairsDomain))) atomicOr(flag, 1);
+    else if (fx && fy) {
+      key = pairs_bucket(pairs_cell(p.x, g.h), pairs_cell(p.y, g.h), g.mask);
+      atomicAdd(&bucketCount[key], 1);
+    }
+  }
+  keys[i] = key;
+  index[i] = i;
+}
+
+// Sorted place k holds point index[k]: its position and cell go there too.
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_place(PairsGrid g, const unsigned* __restrict__ keys, const int* __restrict__ index, int m,
+                  const XY* __restrict__ xy, const int* __restrict__ flag, XY* __restrict__ sxy, uint2* __restrict__ scell) {
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k >= m || *flag) return;
+  if (keys[k] > g.mask) return;
+  const XY p = xy[index[k]];
+  sxy[k] = p;
+  scell[k] = make_uint2(pairs_cell(p.x, g.h), pairs_cell(p.y, g.h));
+}
+
+// Is (i, j) a pair, with p the point i and q the point j; d2 is the number that was compared.
+__device__ __forceinline__ bool pairs_accept(const PairsGrid& g, int i, int j, XY p, XY q, double& d2) {
+  const double dx = p.x - q.x, dy = p.y - q.y;
+  d2 = dx * dx + dy * dy;
+  return j != i && (!g.half || j > i) && d2 <= g.r2;
+}
+
+// The first place from k on, below `end`, whose point lies in cell (cx, cy) and is a partner of i; `end` when none.
+__device__ __forceinline__ int pairs_advance(const PairsGrid& g, int i, XY p, unsigned cx, unsigned cy, int k, int end,
+                                             const XY* __restrict__ sxy, const uint2* __restrict__ scell,
+                                             const int* __restrict__ sidx) {
+  for (; k < end; ++k) {
+    const uint2 cell = scell[k];
+    double d2;
+    if (cell.x == cx && cell.y == cy && pairs_accept(g, i, sidx[k], p, sxy[k], d2)) break;
+  }
+  return k;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_count(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
+                  const XY* __restrict__ xy, const int* __restrict__ start, const XY* __restrict__ sxy,
+                  const uint2* __restrict__ scell, const int* __restrict__ sidx, int* __restrict__ rowLen) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= m || *flag) return;
+  int count = 0;
+  if (i < words[PW_N]) {
+    const XY p = xy[i];
+    if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
+      const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
+      for (int c = 0; c < 9; ++c) {
+        const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
+        const unsigned b = pairs_bucket(cx, cy, g.mask);
+        const int end = start[b + 1];
+        for (int k = start[b]; k < end; ++k) {
+          const uint2 cell = scell[k];
+          double d2;
+          if (cell.x == cx && cell.y == cy && pairs_accept(g, i, sidx[k], p, sxy[k], d2)) ++count;
+        }
+      }
+    }
+  }
+  rowLen[i] = count;
+}
+
+// The exclusive scan of in[0 .. n) in 64 bits into out[0 .. n] (out[n] is the total), n = words[PW_N] <= the launch's
+// bound: k_scan_local / k_scan_fix with wider sums.  Entries of `in` from n on are not read.
+__device__ __forceinline__ long long wave_scan_add64(long long v) {
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    k_scan64_local(const int* __restrict__ in, long long* __restrict__ out, const long long* __restrict__ words,
+                   const int* __restrict__ flag, long long* __restrict__ blockSums) {
+  __shared__ long long waveTot[kBlock / 64];
+  if (*flag) return;
+  const long long n = words[PW_N];
+  const long long base = (long long)blockIdx.x * kScanPerBlock + (long long)threadIdx.x * kScanPerThread;
+  long long v[kScanPerThread];
+  long long sum = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k) {
+    const long long e = base + k < n ? in[base + k] : 0;
+    v[k] = sum;
+    sum += e;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long incl = wave_scan_add64(sum);
+  if (lane == 63) waveTot[wv] = incl;
+  __syncthreads();
+  long long wbase = 0;
+  for (int k = 0; k < wv; ++k) wbase += waveTot[k];
+  const long long excl = wbase + incl - sum;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k)
+    if (base + k <= n) out[base + k] = excl + v[k];
+  if (threadIdx.x == kBlock - 1) blockSums[blockIdx.x] = excl + sum;
+}
+
+// ... adds the totals of the workgroups before, writes the caller's copy, and -- the thread that holds entry n -- E and
+// the caller's two words.  With the domain flag up: E = -1 and the caller's words, nothing else.
+__global__ void __launch_bounds__(kBlock)
+    k_scan64_fix(long long* __restrict__ out, long long* __restrict__ out_caller, long long* __restrict__ words,
+                 const int* __restrict__ flag, const long long* __restrict__ blockSums, long long* __restrict__ counts) {
+  __shared__ long long waveTot[kBlock / 64];
+  const long long n = words[PW_N];
+  if (*flag) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      words[PW_E] = -1;
+      counts[0] = n;
+      counts[1] = -1;
+    }
+    return;
+  }
+  long long acc = 0;
+  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) acc += blockSums[b];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) waveTot[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  long long off = 0;
+  for (int k = 0; k < kBlock / 64; ++k) off += waveTot[k];
+  const long long base = (long long)blockIdx.x * kScanPerBlock + (long long)threadIdx.x * kScanPerThread;
+#pragma unroll
+  for (int k = 0; k < kScanPerThread; ++k) {
+    if (base + k <= n) {
+      const long long v = out[base + k] + off;
+      out[base + k] = v;
+      out_caller[base + k] = v;
+      if (base + k == n) {
+        words[PW_E] = v;
+        counts[0] = n;
+        counts[1] = v;
+      }
+    }
+  }
+}
+
+// Row i's partners at offs[i], ascending in j: the nine runs are each ascending (the sort is stable), the smallest head
+// goes out next.  Entry e is written only when e < room.
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_fill(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
+                 const XY* __restrict__ xy, const long long* __restrict__ offs, const int* __restrict__ start,
+                 const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx,
+                 long long* __restrict__ partners, double* __restrict__ d2_out, long long room) {
+  __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
+  const int tid = (int)threadIdx.x;
+  const int i = (int)(blockIdx.x * blockDim.x + tid);
+  if (i >= m || *flag || i >= words[PW_N]) return;  // (no barrier below: every thread is on its own)
+  long long e = offs[i];
+  const long long row_end = offs[i + 1];
+  if (e >= room || e == row_end) return;
+  const XY p = xy[i];
+  const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
+  for (int c = 0; c < 9; ++c) {
+    const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
+    const unsigned b = pairs_bucket(cx, cy, g.mask);
+    const int end = start[b + 1];
+    const int k = pairs_advance(g, i, p, cx, cy, start[b], end, sxy, scell, sidx);
+    s_cur[c][tid] = k;
+    s_end[c][tid] = end;
+    s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
+  }
+  while (e < room && e < row_end) {
+    int best = INT_MAX, bc = 0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      const int h = s_head[c][tid];
+      if (h < best) {
+        best = h;
+        bc = c;
+      }
+    }
+    if (best == INT_MAX) break;  // (never: the row has row_end - offs[i] partners)
+    const int k = s_cur[bc][tid];
+    double d2;
+    (void)pairs_accept(g, i, best, p, sxy[k], d2);
+    partners[e] = best;
+    if (d2_out) d2_out[e] = d2;
+    ++e;
+    const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
+    const int end = s_end[bc][tid];
+    const int next = pairs_advance(g, i, p, cx, cy, k + 1, end, sxy, scell, sidx);
+    s_cur[bc][tid] = next;
+    s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
+  }
+}
+
+}  // namespace sc

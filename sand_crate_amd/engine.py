@@ -177,6 +177,45 @@ class Engine:
         N.check(self._lib.sc_import_state_device(self._ctx, N._P(particles.data_ptr()), N._P(velocities.data_ptr()),
                                                  None if ids is None else N._P(ids.data_ptr()), n))
 
+    # -- pair lists in torch's memory (sc_pairs_count_device / sc_pairs_fill_device; the rule is tests/pairs_spec.py)
+    def pairs_count(self, points=None, *, radius: float, offsets, counts, half: bool = False, room: int | None = None):
+        """Counts the pairs within `radius` among `points`, a float64 (n, 2) CUDA tensor -- or with None among the state's
+        particles in particle-index order -- into `offsets`, int64 (R + 1,): the exclusive scan of the row lengths, entries
+        0..n.  `counts`, int64 (2,), receives n and E, the number of pairs (E = -1: a coordinate outside the domain
+        |c| / radius < 2^31).  `half` keeps j > i only.  `room` defaults to R rows.  Enqueued on the context's stream, no
+        synchronisation, with the stream rules of `export_state`.  Returns `counts`."""
+        n = 0 if points is None else _state_tensor(points, "points", "float64", (2,), self.device)
+        rows = _state_tensor(offsets, "offsets", "int64", (), self.device) - 1
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        if rows < 0:
+            raise ValueError("offsets must hold at least one entry")
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the offsets' {rows} rows")
+        radius = float(radius)
+        if not (0.0 < radius < float("inf")):
+            raise ValueError("radius must be finite and positive")
+        # (an empty tensor has no address, and a null address asks for the state: no point is read, any address serves)
+        xy = None if points is None else N._P(points.data_ptr() if n else offsets.data_ptr())
+        N.check(self._lib.sc_pairs_count_device(self._ctx, xy, n, radius,
+                                                N.PAIRS_HALF if half else 0, N._P(offsets.data_ptr()), room,
+                                                N._P(counts.data_ptr())))
+        return counts
+
+    def pairs_fill(self, partners, d2=None, *, room: int | None = None):
+        """Fills `partners`, int64 (K,), and `d2`, float64 (K,) or None, from the last `pairs_count`: row i's partners at
+        offsets[i], ascending, and each pair's squared distance.  Entries from `room` (default K) on are left alone: a
+        list longer than the room is clipped.  Enqueued on the context's stream, no synchronisation."""
+        rows = _state_tensor(partners, "partners", "int64", (), self.device)
+        if d2 is not None:
+            _state_tensor(d2, "d2", "float64", (), self.device, rows)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the tensors' {rows} entries")
+        N.check(self._lib.sc_pairs_fill_device(self._ctx, N._P(partners.data_ptr()),
+                                               None if d2 is None else N._P(d2.data_ptr()), room))
+        return partners
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

@@ -1,0 +1,17 @@
+"""Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners)."""
+from __future__ import annotations
+
+
+def row_lengths(offsets):
+    """The number of partners of every row: int64 (n,)."""
+    return offsets[1:] - offsets[:-1]
+
+
+def edge_index(offsets, partners):
+    """The (2, E) int64 edge list (row 0: i, row 1: j) of a CSR pair list, in (i, j) order -- the `edge_index` of a
+    graph network.  `partners` may be shorter than offsets[-1] (a clipped list): the edges are then cut to its length."""
+    import torch
+    n = offsets.shape[0] - 1
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=offsets.device), row_lengths(offsets))
+    k = min(int(rows.shape[0]), int(partners.shape[0]))
+    return torch.stack([rows[:k], partners[:k]])
