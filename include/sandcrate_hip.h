@@ -79,9 +79,12 @@ typedef struct sc_stats {
   int64_t neighbor_slots; /* sum of C_i: how many (rand, rand) pairs crate.py:169 draws this tick */
   int32_t max_neighbors;  /* max C_i */
   int32_t wall_particles; /* particles with at least one wall contact (crate.py:229) */
-  int32_t flags;          /* nonzero: SC_ERR_DOMAIN condition seen on the device */
+  int32_t flags;          /* nonzero: an error condition seen on the device (reported by the next synchronising call).
+                           * With SC_FLAG_SCAN_TIMEOUT the tick is abandoned (sc_set_scan_patience): `particles` is the
+                           * stored count, the other numbers are 0 -- the host draws no noise for such a tick */
   int32_t reserved;
 } sc_stats;
+#define SC_FLAG_SCAN_TIMEOUT 64
 
 typedef struct sc_ctx sc_ctx;
 
@@ -161,7 +164,24 @@ int sc_synchronize(sc_ctx* ctx);
 /* The bucket scan is one pass with decoupled look-back: a workgroup waits for the totals of the workgroups before it,
  * which the dispatcher starts first.  The wait is bounded -- `polls` attempts per predecessor (default 2^22; negative:
  * give up at once, for tests) -- and a workgroup that gives up abandons the TICK: its later kernels do nothing, the particles
- * stay as the tick found them, and the next synchronising call returns SC_ERR_HIP.  (A knob for tests of that path.) */
+ * stay as the tick found them, and the next synchronising call returns SC_ERR_HIP.  (A knob for tests of that path.)
+ *
+ * What an abandoned tick leaves, and what the caller may do after it:
+ *   - The state is the one the tick found, but for the hard wall fix of the tick's first kernel, which runs ahead of the
+ *     scan and in place (crate.py:202-211, applied once): velocities, ids and the count are exact, the pressures are those
+ *     of the last finished tick.  The tick counter has advanced (SC_NOISE_COUNTER keys the noise by it); the stream of
+ *     SC_NOISE_HOST has not moved, whether the device holds it or the host draws it (sc_step_stats says so: no noise).
+ *   - Every tick started before the error is read is abandoned whole -- it does not even apply a wall fix.
+ *   - The error is read, cleared and repaired by sc_synchronize and sc_download_state, whichever is called first, exactly
+ *     once; the run then goes on from the stored state (a tick, an upload, an append) as if the abandoned ticks had not
+ *     been asked for.  sc_synchronize BETWEEN sc_step_begin and sc_step_finish reports it too but leaves the rest of the
+ *     tick abandoned: the first of the two calls after sc_step_finish reports it again and repairs.  sc_count does not
+ *     read errors.
+ *   - Before that reader, calls that only read the state on the device -- sc_export_state_device, sc_render*,
+ *     sc_probe_now, sc_track_capture -- deliver it as described above: positions, velocities, ids and count exact,
+ *     pressures those of the last finished tick, exactly what sc_download_state then returns.
+ *   - The logs (sc_probe_enable, sc_track_enable) hold NO row / frame for an abandoned tick, and count none as dropped:
+ *     every row is the state after a tick that happened. */
 int sc_set_scan_patience(sc_ctx* ctx, int64_t polls);
 
 /* Parity taps, valid between sc_step_begin and sc_step_finish.  Synchronise.  All arrays have one

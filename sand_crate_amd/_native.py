@@ -40,6 +40,7 @@ ERR_HIP = -2
 ERR_CAPACITY = -3
 ERR_STATE = -4
 ERR_DOMAIN = -5
+FLAG_SCAN_TIMEOUT = 64  # sc_stats.flags: the tick is abandoned (SC_FLAG_SCAN_TIMEOUT)
 
 
 class NativeError(RuntimeError):

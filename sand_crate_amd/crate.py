@@ -365,10 +365,16 @@ class Crate:
             eng.step_begin()
             stats = eng.step_stats()
             self.last_stats = stats
-            # crate.py:165-170 draws rand(C_i, 2) particle by particle; one block is the same stream
-            eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
-            eng.step_finish()
-            self._count, self._count_known = stats.particles, True
+            if stats.flags & N.FLAG_SCAN_TIMEOUT:
+                # the tick is abandoned (sc_step_stats): it has no lists, so nothing is drawn for it -- np.random stays
+                # where it stands -- and the count is the one the crate had
+                eng.set_noise_host(np.zeros((0, 2)))
+                eng.step_finish()
+            else:
+                # crate.py:165-170 draws rand(C_i, 2) particle by particle; one block is the same stream
+                eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
+                eng.step_finish()
+                self._count, self._count_known = stats.particles, True
         else:
             eng.tick(self._pack_tick_inputs())
             self._count_known = False

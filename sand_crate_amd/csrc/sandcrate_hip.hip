@@ -590,6 +590,34 @@ int check_flags(int flags) {
   return SC_OK;
 }
 
+// What every reader of the error bits does with them (sc_synchronize, sc_download_state; `h`: the counters as read):
+// they are cleared on the stream and reported, once.  A tick abandoned behind its scan (F_SCAN_TIMEOUT) -- and every tick
+// queued behind it, which the flag abandoned too -- has left more than the flag, and all of it is put right here, so that
+// the next tick starts from the storage arrays whichever call came first:
+//   cellCount   holds the counts of the abandoned tick's K1, which no scatter took back; a look-ahead may have promised
+//               a K1 that pass B never ran (abandon_promise)
+//   C_NBIG / C_NTASKS   pass B zeroes them, and returned before it did: every abandoned scan added its buckets and
+//               appended its tasks, which k_sort_big would run beside the next tick's
+//   C_NT        is the partial sum of a workgroup that gave up; between ticks it says which slots have a pressure, and
+//               goes back to what the last finished tick left (C_NT_DONE: C_NS, unless particles were appended since;
+//               0 after an upload, whatever normals_valid says -- sc_step_finish sets it for an abandoned tick too)
+// Inside a tick (sc_synchronize between sc_step_begin and sc_step_finish) the bit stays up: the rest of the tick must
+// not run on what the scan left, so it is reported now and again -- with the repair -- by the first reader after the tick.
+int recover_flags(sc_ctx* c, const int* h) {
+  const int flags = h[C_FLAGS];
+  if (!flags) return SC_OK;
+  const bool abandoned = (flags & F_SCAN_TIMEOUT) != 0;
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(c->counters + C_FLAGS), abandoned && c->in_step ? F_SCAN_TIMEOUT : 0, 1, c->stream));
+  if (abandoned && !c->in_step) {
+    const int rc = abandon_promise(c);
+    if (rc) return rc;
+    static_assert(C_NTASKS == C_NBIG + 1, "one memset for the two");
+    HIPCHK(hipMemsetAsync(c->counters + C_NBIG, 0, 2 * sizeof(int), c->stream));
+    HIPCHK(hipMemcpyAsync(c->counters + C_NT, c->counters + C_NT_DONE, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  }
+  return check_flags(flags);
+}
+
 // What every upload and append starts with: the call is allowed and the particles fit; a reset gives up a promised tick.
 int put_check(sc_ctx* c, const void* xy, const void* vxy, int64_t n, bool reset) {
   if (n < 0 || (n > 0 && (!xy || !vxy))) return fail(SC_ERR_ARG, "bad particle arrays");
@@ -972,17 +1000,7 @@ int sc_synchronize(sc_ctx* c) {
   int rc = read_counters(c, h);
   if (rc) return rc;
   if (!c->in_step) c->upper = h[C_NS];
-  if (h[C_FLAGS]) {
-    HIPCHK(hipMemsetAsync(c->counters + C_FLAGS, 0, sizeof(int), c->stream));
-    if (h[C_FLAGS] & F_SCAN_TIMEOUT) {
-      // the tick was abandoned behind its scan: its bucket counts were never consumed, and whatever a look-ahead
-      // promised for the tick after it was never computed -- the next tick starts from the storage arrays
-      rc = abandon_promise(c);
-      if (rc) return rc;
-    }
-    return check_flags(h[C_FLAGS]);
-  }
-  return SC_OK;
+  return recover_flags(c, h);
 }
 
 int sc_set_scan_patience(sc_ctx* c, int64_t polls) {
@@ -1132,13 +1150,20 @@ int sc_step_stats(sc_ctx* c, sc_stats* out) {
   int h[C_COUNT];
   int rc = read_counters(c, h);
   if (rc) return rc;
+  out->flags = h[C_FLAGS];
+  out->reserved = 0;
+  if (h[C_FLAGS] & F_SCAN_TIMEOUT) {
+    // the tick is abandoned: C_NT is a partial sum and the rows counted are an earlier tick's.  The particles are the
+    // stored ones, there are no lists, and the host's bound of the stored count is not taken from this tick
+    out->particles = h[C_NS];
+    out->neighbor_slots = out->max_neighbors = out->wall_particles = 0;
+    return SC_OK;
+  }
   c->stats_live = h[C_NT];
   out->particles = h[C_NT];
   out->neighbor_slots = (int64_t)(uint32_t)h[C_SUMC] + ((int64_t)h[C_SUMC_HI] << 32);
   out->max_neighbors = h[C_MAXC];
   out->wall_particles = h[C_WREC];
-  out->flags = h[C_FLAGS];
-  out->reserved = 0;
   return SC_OK;
 }
 
@@ -1297,6 +1322,10 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
   c->upper = n;
   if (n_out) *n_out = n;
   if (n > room) return fail(SC_ERR_CAPACITY, "host arrays hold %lld, %lld particles live", (long long)room, (long long)n);
+  // the error bits are this call's to report, once the state is out; what an abandoned tick left is repaired first, so that
+  // the pressures are cut where the last finished tick left them
+  const int flagged = recover_flags(c, h);
+  if (h[C_FLAGS] & F_SCAN_TIMEOUT) h[C_NT] = h[C_NT_DONE];
   std::vector<double> hx(n), hy(n), hvx(n), hvy(n), hp(n, 0.0);
   std::vector<int> hid(n);
   size_t b = n * sizeof(double);
@@ -1329,11 +1358,7 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
     if (pressure) pressure[k] = s < np ? hp[s] : 0.0;
     if (ids) ids[k] = hid[s];
   }
-  if (h[C_FLAGS]) {
-    HIPCHK(hipMemsetAsync(c->counters + C_FLAGS, 0, sizeof(int), c->stream));
-    return check_flags(h[C_FLAGS]);
-  }
-  return SC_OK;
+  return flagged;
 }
 
 // ---- the state in the caller's device memory (sc_state.h) ---------------------------------------

@@ -98,7 +98,7 @@ enum Counter {
   C_MAXC = 5,   // max neighbor count
   C_SUMC_HI = 6,
   C_NEXT_ID = 7,  // id the next emitted particle gets (k_rng_emit counts on the device; uploads set it)
-  C_SPARE8 = 8,
+  C_NT_DONE = 8,  // C_NT as the last FINISHED tick left it (pass B; 0 after an upload): an abandoned tick's scan overwrites C_NT
   C_TICKET = 9,  // workgroups that have finished the current halo kernel (last one publishes / bumps)
   C_NBIG = 10,   // buckets above kSortThreshold listed this tick
   C_NTASKS = 11, // ... and k_sort_big's tasks for them (one 64-bit atomic with C_NBIG: keep the two adjacent, C_NBIG even)
@@ -111,6 +111,19 @@ enum Counter {
 
 enum Flag { F_OUT_OF_GRID = 1, F_NAN = 2, F_HALO_OVERFLOW = 4, F_CAPACITY = 8, F_HALO_LATE = 16, F_BAND_TIMEOUT = 32, F_SCAN_TIMEOUT = 64,
             F_HALO_REACH = 128, F_HALO_CROSSED = 256 };
+
+// A tick whose bucket scan gave up is abandoned: its later kernels do nothing (k_scan_cells), and so do the ticks queued
+// behind it -- the flag stays up until the host reads it and repairs what the scan left (recover_flags).
+__device__ __forceinline__ bool tick_abandoned(const int* __restrict__ counters) {
+  return (__hip_atomic_load(&counters[C_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & F_SCAN_TIMEOUT) != 0;
+}
+
+// The storage slots whose pressure belongs to the last finished tick, of `ns` stored ones: those that tick left live.
+// The scan of an abandoned tick has overwritten C_NT with a partial sum; until the host puts it back (recover_flags: to
+// C_NT_DONE) the rule is applied here, so that whoever reads the state before the flags sees the pressures as they stand.
+__device__ __forceinline__ int pressure_slots(const int* __restrict__ counters, int ns) {
+  return min(ns, counters[tick_abandoned(counters) ? C_NT_DONE : C_NT]);
+}
 
 // columns / rows a particle may move in one tick and still be packed in time (halo overlap).  With slabs of rows the
 // band blocks are few whatever the margin; with columns every row has them, and each column of margin adds as many.

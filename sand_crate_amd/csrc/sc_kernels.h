@@ -45,6 +45,7 @@ __global__ void k_append(const double* __restrict__ xy, const double* __restrict
 
 __global__ void k_bump(int* counters, int m, int reset, int next_id, int cap) {
   counters[C_NS] = min((reset ? 0 : counters[C_NS]) + m, cap);
+  if (reset) counters[C_NT_DONE] = 0;  // no slot of the new state has a pressure until a tick finishes
   counters[C_NEXT_ID] = next_id;  // the host's id counter after this append (an upper bound once the device emits)
 }
 
@@ -258,7 +259,8 @@ __global__ void __launch_bounds__(kBlock) k_wall_bin(World w, int* __restrict__ 
   double px = x[ic], py = y[ic];
   const double px0 = px, py0 = py;
   int c = -1;
-  if (i < counters[C_NS]) {
+  // (a tick queued behind an abandoned one is abandoned whole: no second wall fix, no bucket counts on top of the first's)
+  if (i < counters[C_NS] && !tick_abandoned(counters)) {
     int wslot;
     c = wall_and_cell(w, px, py, wslot, counters, i, wrec);
     cellS[i] = c;
@@ -338,7 +340,10 @@ __global__ void __launch_bounds__(kBlock) k_scan_fix(int* __restrict__ out, int 
 // only, which the dispatcher starts first; the wait is bounded all the same (`max_polls`: sc_set_scan_patience).  A
 // workgroup that gives up raises F_SCAN_TIMEOUT -- and with that flag up every later kernel of the tick returns at its
 // first instruction (tick_abandoned): the bucket starts are not to be trusted, so the tick is SKIPPED, the storage
-// arrays keep the state the tick started from, and the error reaches the caller with that state intact.
+// arrays keep the state the tick started from, and the error reaches the caller with that state intact.  The ticks
+// queued behind it find the flag up and do nothing at all (K1 and the noise kernels included); what this kernel itself
+// leaves wrong -- C_NBIG / C_NTASKS and the task list, which pass B did not reset, C_NT, a partial sum, and the counts
+// no scatter took back -- is put right by the host when it reads the flag (recover_flags).
 constexpr int kSortThreshold = 96;  // buckets above this many particles are listed for k_sort_big
 constexpr int kSortBlock = 512;       // threads of a sorting task
 constexpr int kSortChunk = 1024;      // slots per sorting task (12 B of LDS per slot for the keys)
@@ -355,11 +360,6 @@ struct alignas(16) SortKey {
   int id;
   int src;
 };
-
-// A tick whose bucket scan gave up is abandoned: its later kernels do nothing (k_scan_cells).
-__device__ __forceinline__ bool tick_abandoned(const int* __restrict__ counters) {
-  return (__hip_atomic_load(&counters[C_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & F_SCAN_TIMEOUT) != 0;
-}
 
 struct Buckets {
   const int* __restrict__ start;
@@ -1049,7 +1049,8 @@ __global__ void __launch_bounds__(kBlock) k_count_stats(int* __restrict__ counte
 __global__ void k_count_by_id(const int* __restrict__ counters, const int* __restrict__ id,
                               const unsigned int* __restrict__ rows, int* __restrict__ cntById) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < counters[C_NT]) cntById[id[i]] = row_count_of(rows, (size_t)i);
+  // (an abandoned tick has no lists: the counts stay zero, and so does the length of the tick's noise block)
+  if (i < counters[C_NT] && !tick_abandoned(counters)) cntById[id[i]] = row_count_of(rows, (size_t)i);
 }
 
 // Collider offset eta_ij of crate.py:169 for slot `slot` of a particle.  `z` is the particle's

@@ -80,7 +80,8 @@ __global__ void __launch_bounds__(kProbeBlock)
   if ((int)blockIdx.x >= nb) return;  // no slot of this workgroup is stored
   long long row = 0;
   if (a.log_rows >= 0) {
-    row = __hip_atomic_load(&words[PW_HEAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tick_abandoned(counters)) return;  // the log holds a row per tick that happened: an abandoned one leaves none
+    row =__hip_atomic_load(&words[PW_HEAD], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (row >= a.log_rows) {  // the log is full: the tick is not recorded, only counted
       if (blockIdx.x == 0 && tid == 0) words[PW_DROPPED] += 1;
       return;
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(kProbeBlock)
   }
   __syncthreads();
 
-  const int np = a.pressure_valid ? min(ns, counters[C_NT]) : 0;
+  const int np = a.pressure_valid ? pressure_slots(counters, ns) : 0;
   const double inf = __builtin_inf();
   double acc[kProbeFields];
 #pragma unroll

@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(kBlock) k_render_splat(RenderView v, const int
   const double Rd = v.radius_d;
   if (!(X + Rd >= 0.0 && X - Rd <= v.sx && Y + Rd >= 0.0 && Y - Rd <= v.sy)) return;  // the disc misses the frame
   // sc_download_state's pairing: the pressure of the last finished tick belongs to the slots it left live
-  const int np = pressure_valid ? min(ns, counters[C_NT]) : 0;
+  const int np = pressure_valid ? pressure_slots(counters, ns) : 0;
   const double p = slot < np ? P[slot] : 0.0;
   // playback.py:197-200: 255 - int(p * 255), clipped to [0, 255]; NaN and +inf -> 0, -inf -> 255
   const double cc = 255.0 - trunc(p * 255.0);

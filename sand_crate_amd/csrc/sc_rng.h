@@ -288,6 +288,7 @@ __global__ void __launch_bounds__(kRngBlock)
     k_rng_noise(RngState* __restrict__ state, const int* __restrict__ pairs_ptr, double* __restrict__ eta,
                 long long eta_pairs_room, int* __restrict__ counters) {
   __shared__ uint32_t mt[2 * kMtN];
+  if (tick_abandoned(counters)) return;  // a tick that did not happen draws nothing: the stream stays where it stands
   rng_noise_block(mt, state, *pairs_ptr, eta, eta_pairs_room, counters, LdsBarrier{});
 }
 
@@ -305,6 +306,7 @@ __global__ void __launch_bounds__(kSmallBlock)
   __shared__ int waveTot[kSmallBlock / 64];
   __shared__ int carry_s;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tick_abandoned(counters)) return;  // (as k_rng_noise: no lists to count, no noise to draw)
   const int n = counters[C_NT];
   for (int k = tid; k < ids; k += kSmallBlock) cntById[k] = 0;
   __syncthreads();

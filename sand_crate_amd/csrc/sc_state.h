@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(kBlock)
   if (o.vxy) ((XY*)o.vxy)[k] = XY{vx[s], vy[s]};
   if (o.pressure) {
     const int ns = min(counters[C_NS], cap);
-    const int np = pressure_valid ? min(ns, counters[C_NT]) : 0;
+    const int np = pressure_valid ? pressure_slots(counters, ns) : 0;
     o.pressure[k] = s < np ? P[s] : 0.0;
   }
   if (o.ids) o.ids[k] = (long long)key;

@@ -1079,6 +1079,7 @@ __global__ void __launch_bounds__(kTileW)
   if (tick_abandoned(counters)) return;  // (before anything is written: the storage arrays keep the state the tick started from)
   if (tile_id == 0 && t == 0 && part != 2) {
     counters[C_NS] = n;    // the storage arrays now hold the n live particles
+    counters[C_NT_DONE] = n;  // ... each with this tick's pressure (C_NT itself does not survive an abandoned tick's scan)
     counters[C_SUMC] = 0;  // per-tick counters start the next tick at zero (sc_step_stats reads them
                            // between sc_step_begin and sc_step_finish, i.e. before this kernel)
     counters[C_SUMC_HI] = 0;

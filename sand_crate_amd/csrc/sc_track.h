@@ -83,6 +83,8 @@ __global__ void __launch_bounds__(64) k_track_reserve(TrackArgs a, const int* __
     long long at = -1;
     if (a.log_bytes < 0) {
       if (bytes <= a.room) at = 0;
+    } else if (tick_abandoned(counters)) {
+      // the log holds a frame per tick that happened: an abandoned one leaves none, and none is counted as dropped
     } else if ((long long)words[TW_CURSOR] + bytes <= a.log_bytes) {
       at = (long long)atomicAdd(&words[TW_CURSOR], (unsigned long long)bytes);
       words[TW_FRAMES] += 1;
@@ -123,7 +125,7 @@ __global__ void __launch_bounds__(kBlock) k_track_pack(TrackArgs a, const int* _
   const long long at = (long long)words[TW_AT];
   if (at < 0) return;  // dropped
   const int n = (int)words[TW_N];
-  const int np = a.pressure_valid ? min(n, counters[C_NT]) : 0;
+  const int np = a.pressure_valid ? pressure_slots(counters, n) : 0;
   const TrackPlanes pl = track_planes(n, a.nseg);
   unsigned char* frame = base + at;
   unsigned* pid = (unsigned*)(frame + pl.id);
@@ -187,6 +189,7 @@ __global__ void __launch_bounds__(kBlock) k_track_unpack(TrackLoad a, const unsi
   if (i == 0) {
     counters[C_NS] = a.n;
     counters[C_NT] = a.n;
+    counters[C_NT_DONE] = a.n;
     counters[C_NEXT_ID] = a.next_id;
   }
   if (i >= a.n) return;
