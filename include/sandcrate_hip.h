@@ -578,7 +578,7 @@ int sc_track_load(sc_ctx* ctx, const uint8_t* frame, int64_t n_bytes, int32_t pl
  *     counter, look-ahead promise, RNG position or pending error flag changes, and like the probe's its launches are not
  *     bracketed by the timing events.  Works in slab mode, as sc_download_state does.
  *     The ranking is a radix sort of (id, slot) pairs on the device -- least significant digit first, four passes of
- *     eight bits, each a count per tile of 256 keys, a two-level scan of the counts and a stable scatter (csrc/sc_state.h)
+ *     eight bits, each a count per tile of 256 keys, a two-level scan of the counts and a stable scatter (csrc/sc_radix.h)
  *     -- so the result is exact, does not depend on timing, no workgroup waits for another, and the cost is linear in
  *     the stored count whatever the ids are (a bitmap over the ids would cost 2^31 bits for one large id, and a slab does
  *     not know the largest id of the ghosts it was sent).  The workspace belongs to the context: 24 bytes per particle of

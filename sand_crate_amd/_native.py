@@ -22,11 +22,12 @@ PROBE_FIELDS = 16
 PROBE_MAX_BINS = 1024
 PROBE_MAX_ROWS = 1 << 20
 PROBE_BLOCK, PROBE_BLOCKS = 1024, 256  # the probe's fixed launch (csrc/sc_probe.h: kProbeBlock, kProbeBlocks)
-# the device export's launches (csrc/sc_state.h, sc_kernels.h): keys per workgroup of a sorting pass (kStateTile), counts
-# per workgroup of the scan between its two kernels (kScanPerBlock), rows per workgroup of the gather (kBlock)
+# the device export's launches (csrc/sc_radix.h, sc_kernels.h, sc_state.h): keys per workgroup of a sorting pass
+# (kRadixTile), counts per workgroup of the scan between its two kernels (kScanPerBlock), rows per workgroup of the gather
+# (kBlock)
 STATE_TILE, STATE_SCAN_BLOCK, STATE_GATHER_BLOCK = 256, 2048, 256
-# the pair search's launches and table (csrc/sc_pairs.h, sc_state.h, sc_kernels.h): rows per workgroup of its row kernels
-# (kBlock), keys per workgroup of a pass of the binning sort (kStateTile), entries per workgroup of the scans
+# the pair search's launches and table (csrc/sc_pairs.h, sc_radix.h, sc_kernels.h): rows per workgroup of its row kernels
+# (kBlock), keys per workgroup of a pass of the binning sort (kRadixTile, the same sort), entries per workgroup of the scans
 # (kScanPerBlock); the hashed table has the smallest power of two of buckets that is at least PAIRS_LOAD per point and
 # PAIRS_MIN_BUCKETS, a cell (cx, cy) -- floor(x / h), floor(y / h) as 32-bit words, h = radius * PAIRS_CELL_FACTOR -- lies in
 # bucket `pairs_bucket(cx, cy, buckets)`

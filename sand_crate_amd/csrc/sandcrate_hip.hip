@@ -25,6 +25,7 @@
 #include "sc_jpeg.h"
 #include "sc_kernels.h"
 #include "sc_probe.h"
+#include "sc_radix.h"
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_track.h"
@@ -131,6 +132,26 @@ using DevBuf = Owned<T, DeviceMem>;
 template <class T>
 using HostBuf = Owned<T, PinnedMem<hipHostMallocDefault>>;  // pinned host memory
 
+// The workspace of a radix sort (sc_radix.h; radix_sort below): the (key, value) pairs -- two sets that take turns --,
+// the tiles' digit counts, their scan and its block sums.
+struct RadixSpace {
+  DevBuf<unsigned> keys[2];
+  DevBuf<int> vals[2], hist, offs, sums;
+  // Room for a sort of m pairs: sized by the last member, which grows last.
+  int ensure(int64_t m, hipStream_t stream) {
+    if (m <= vals[1].size()) return SC_OK;
+    const int64_t cells = (m + kRadixTile - 1) / kRadixTile * kRadixBins;  // a count per tile and digit
+    HIPCHK(hist.grow(cells, stream));
+    HIPCHK(offs.grow(cells + 1, stream));
+    HIPCHK(sums.grow(cells / kScanPerBlock + 2, stream));
+    for (int k = 0; k < 2; ++k) {
+      HIPCHK(keys[k].grow(m, stream));
+      HIPCHK(vals[k].grow(m, stream));
+    }
+    return SC_OK;
+  }
+};
+
 // What a tick takes from the caller: coefficients, walls (the segments and their padded twins) and rigid bodies.
 struct TickInputs {
   sc_params params{};
@@ -228,25 +249,24 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   int arrow_mode = SC_ARROWS_OFF;
   int64_t arrow_n = 0, arrow_every = 1;  // ... the list's length; velocity mode: ids that are multiples of this
   double arrow_scale = 1.0;
-  // sc_export_state_device (sc_state.h): the radix sort's (id, slot) pairs -- two sets that take turns --, the tiles'
-  // digit counts and their scan, each grown to the launch bound asked for; sc_import_state_device: the ids as 32-bit
-  // values and its two words (largest id plus one, out-of-range flag)
-  DevBuf<unsigned> stateKeys[2];
-  DevBuf<int> stateSlots[2], stateHist, stateOffs, stateSums, stateIds, stateWords;
-  // sc_pairs_count_device / sc_pairs_fill_device (sc_pairs.h): the points in index order, the (bucket, index) pairs of the
-  // binning sort -- two sets that take turns -- with the tiles' digit counts and their scan, the buckets' counts and
-  // starts, the members' positions and cells in bucket order, the row lengths, their 64-bit scan with its block sums, the
-  // domain flag and the two words (n, E); each grown to the largest bound asked for.  `pairs_valid`: the workspace holds
-  // the grid of a count, and nothing has changed the state since.
+  // sc_export_state_device (sc_state.h): the sort of the (id, slot) pairs, grown to the launch bound asked for;
+  // sc_import_state_device: the ids as 32-bit values and its two words (largest id plus one, out-of-range flag)
+  RadixSpace stateSort;
+  DevBuf<int> stateIds, stateWords;
+  // sc_pairs_count_device / sc_pairs_fill_device (sc_pairs.h): the points in index order, the binning sort of the
+  // (bucket, index) pairs -- a workspace of its own: the fill reads its result, and an export may come in between --,
+  // the buckets' counts and starts, the members' positions and cells in bucket order, the row lengths, their 64-bit scan
+  // with its block sums, the domain flag and the two words (n, E); each grown to the largest bound asked for.
+  // `pairs_valid`: the workspace holds the grid of a count, and nothing has changed the state since.
   DevBuf<XY> pairsXY, pairsSXY;
   DevBuf<uint2> pairsCell;
-  DevBuf<unsigned> pairsKeys[2];
-  DevBuf<int> pairsIdx[2], pairsHist, pairsHistOffs, pairsHistSums, pairsBucketCount, pairsBucketStart, pairsBucketSums;
+  RadixSpace pairsSort;
+  DevBuf<int> pairsBucketCount, pairsBucketStart, pairsBucketSums;
   DevBuf<int> pairsRowLen, pairsFlag;
   DevBuf<long long> pairsOffs, pairsSums, pairsWords;
   bool pairs_valid = false;
   int64_t pairs_m = 0;   // ... the bound its launches were sized by
-  int pairs_sorted = 0;  // ... which of the two sets holds the sorted pairs
+  int pairs_set = 0;     // ... which of pairsSort's two sets holds the sorted pairs
   PairsGrid pairs_grid{};
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
@@ -431,6 +451,29 @@ int launch_scan(sc_ctx* c, const int* in, int* out, int64_t n, int* blockSums, i
   hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(kBlock), 0, c->stream, in, out, (int)n, blockSums);
   hipLaunchKernelGGL(k_scan_fix, dim3(nb), dim3(kBlock), 0, c->stream, out, (int)n, blockSums, nb, total_out);
   HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// Sorts the m pairs of `w` by the lowest `passes` digits of their keys (sc_radix.h) and yields in *set which of the two
+// sets holds the result.  The pairs are those of set 0, or -- `first` is not RadixStored -- made by the first pass:
+// (first(i), i).
+template <class Key>
+int radix_sort(sc_ctx* c, RadixSpace& w, Key first, int64_t m, int passes, int* set) {
+  const int tiles = (int)((m + kRadixTile - 1) / kRadixTile);
+  int in = 0, rc;
+  for (int pass = 0; pass < passes && m > 0; ++pass, in ^= 1) {
+    const int shift = pass * kRadixDigitBits;
+    if (pass == 0)
+      hipLaunchKernelGGL(k_radix_hist<Key>, dim3(tiles), dim3(kRadixTile), 0, c->stream, first, w.keys[in].get(),
+                         w.vals[in].get(), (int)m, shift, tiles, w.hist.get());
+    else
+      hipLaunchKernelGGL(k_radix_hist<RadixStored>, dim3(tiles), dim3(kRadixTile), 0, c->stream, RadixStored{},
+                         w.keys[in].get(), w.vals[in].get(), (int)m, shift, tiles, w.hist.get());
+    if ((rc = launch_scan(c, w.hist, w.offs, (int64_t)tiles * kRadixBins, w.sums, nullptr))) return rc;
+    hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kRadixTile), 0, c->stream, w.keys[in].get(), w.vals[in].get(),
+                       w.keys[in ^ 1].get(), w.vals[in ^ 1].get(), (int)m, shift, tiles, w.offs.get());
+  }
+  *set = in;
   return SC_OK;
 }
 
@@ -1312,6 +1355,25 @@ static int fetch(sc_ctx* c, void* dst, const void* src, size_t bytes) {
   return SC_OK;
 }
 
+// The index order on the host: the slots 0 .. n -- with `x`, only those whose x is finite: slab mode leaves dead ghost
+// copies (x = +inf) behind -- ascending by id.  (On the device: state_row_live in sc_state.h.)
+static std::vector<int> index_order(const int* id, const double* x, int64_t n) {
+  std::vector<int> order;
+  order.reserve(n);
+  for (int64_t k = 0; k < n; ++k)
+    if (!x || std::isfinite(x[k])) order.push_back((int)k);
+  std::sort(order.begin(), order.end(), [&](int p, int q) { return id[p] < id[q]; });
+  return order;
+}
+
+// Row k of `out` (may be null) is the pair (a[stride s], b[stride s]) of slot s = order[k].
+static void write_pairs(double* out, const std::vector<int>& order, const double* a, const double* b, int stride = 1) {
+  for (size_t k = 0; k < order.size() && out; ++k) {
+    out[2 * k] = a[(size_t)stride * order[k]];
+    out[2 * k + 1] = b[(size_t)stride * order[k]];
+  }
+}
+
 int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int64_t* ids, int64_t room, int64_t* n_out) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (c->in_step) return fail(SC_ERR_STATE, "sc_download_state inside a tick");
@@ -1338,23 +1400,13 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
   int64_t np = c->normals_valid ? std::min<int64_t>(n, h[C_NT]) : 0;
   if (pressure && np > 0 && (rc = fetch(c, hp.data(), c->P, np * sizeof(double)))) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  std::vector<int> order;
-  order.reserve(n);
-  for (int64_t k = 0; k < n; ++k)
-    if (std::isfinite(hx[k])) order.push_back((int)k);  // slab mode leaves dead ghost copies (x = +inf) behind
-  std::sort(order.begin(), order.end(), [&](int a, int b2) { return hid[a] < hid[b2]; });
+  const std::vector<int> order = index_order(hid.data(), hx.data(), n);
   n = (int64_t)order.size();
   if (n_out) *n_out = n;
+  write_pairs(xy, order, hx.data(), hy.data());
+  write_pairs(vxy, order, hvx.data(), hvy.data());
   for (int64_t k = 0; k < n; ++k) {
-    int s = order[k];
-    if (xy) {
-      xy[2 * k] = hx[s];
-      xy[2 * k + 1] = hy[s];
-    }
-    if (vxy) {
-      vxy[2 * k] = hvx[s];
-      vxy[2 * k + 1] = hvy[s];
-    }
+    const int s = order[k];
     if (pressure) pressure[k] = s < np ? hp[s] : 0.0;
     if (ids) ids[k] = hid[s];
   }
@@ -1363,37 +1415,12 @@ int sc_download_state(sc_ctx* c, double* xy, double* vxy, double* pressure, int6
 
 // ---- the state in the caller's device memory (sc_state.h) ---------------------------------------
 
-// Room for a sort of m pairs: sized by the last member, which grows last.
-static int state_ensure(sc_ctx* c, int64_t m) {
-  if (m <= c->stateSlots[1].size()) return SC_OK;
-  const int64_t cells = (m + kStateTile - 1) / kStateTile * kStateBins;  // a count per tile and digit
-  HIPCHK(c->stateHist.grow(cells, c->stream));
-  HIPCHK(c->stateOffs.grow(cells + 1, c->stream));
-  HIPCHK(c->stateSums.grow(cells / kScanPerBlock + 2, c->stream));
-  HIPCHK(c->stateKeys[0].grow(m, c->stream));
-  HIPCHK(c->stateKeys[1].grow(m, c->stream));
-  HIPCHK(c->stateSlots[0].grow(m, c->stream));
-  HIPCHK(c->stateSlots[1].grow(m, c->stream));
-  return SC_OK;
-}
-
-// Ranks the m slots of the launch by id into stateKeys[0] / stateSlots[0]: slots that are not stored, or whose x is not
-// finite, carry kStateDead and come last.
-static int state_rank(sc_ctx* c, int64_t m) {
-  int rc = state_ensure(c, m);
+// Ranks the m slots of the launch by id into set *set of stateSort: slots that are not stored, or whose x is not finite,
+// carry kStateDead and come last.
+static int state_rank(sc_ctx* c, int64_t m, int* set) {
+  const int rc = c->stateSort.ensure(m, c->stream);
   if (rc) return rc;
-  const int tiles = (int)((m + kStateTile - 1) / kStateTile);
-  for (int pass = 0; pass < kStatePasses && m > 0; ++pass) {
-    const int in = pass & 1, shift = pass * kStateDigitBits;
-    hipLaunchKernelGGL(k_state_hist, dim3(tiles), dim3(kStateTile), 0, c->stream, c->counters,
-                       pass == 0 ? c->x.get() : nullptr, c->id[0].get(), (int)c->cap, c->stateKeys[in].get(),
-                       c->stateSlots[in].get(), (int)m, shift, tiles, c->stateHist.get());
-    if ((rc = launch_scan(c, c->stateHist, c->stateOffs, (int64_t)tiles * kStateBins, c->stateSums, nullptr))) return rc;
-    hipLaunchKernelGGL(k_state_scatter, dim3(tiles), dim3(kStateTile), 0, c->stream, c->stateKeys[in].get(),
-                       c->stateSlots[in].get(), c->stateKeys[in ^ 1].get(), c->stateSlots[in ^ 1].get(), (int)m, shift, tiles,
-                       c->stateOffs.get());
-  }
-  return SC_OK;
+  return radix_sort(c, c->stateSort, StateKey{c->counters, c->x, c->id[0], (int)c->cap}, m, kStatePasses, set);
 }
 
 int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
@@ -1407,12 +1434,13 @@ int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* d
   if (room < m)
     return fail(SC_ERR_CAPACITY, "device arrays hold %lld, up to %lld particles stored", (long long)room, (long long)m);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = state_rank(c, m);
+  int set;
+  const int rc = state_rank(c, m, &set);
   if (rc) return rc;
   const StateOut o{dev_xy, dev_vxy, dev_pressure, (long long*)dev_ids, (long long*)dev_n};
-  hipLaunchKernelGGL(k_state_gather, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->counters, o, c->stateKeys[0].get(),
-                     c->stateSlots[0].get(), (int)m, (int)c->cap, c->normals_valid ? 1 : 0, c->x.get(), c->y.get(),
-                     c->vx.get(), c->vy.get(), c->P.get());
+  hipLaunchKernelGGL(k_state_gather, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->counters, o,
+                     c->stateSort.keys[set].get(), c->stateSort.vals[set].get(), (int)m, (int)c->cap,
+                     c->normals_valid ? 1 : 0, c->x.get(), c->y.get(), c->vx.get(), c->vy.get(), c->P.get());
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -1460,15 +1488,9 @@ static int pairs_ensure(sc_ctx* c, int64_t m, int64_t buckets) {
     HIPCHK(c->pairsBucketSums.grow(buckets / kScanPerBlock + 2, c->stream));
     HIPCHK(c->pairsBucketStart.grow(buckets + 1, c->stream));
   }
+  const int rc = c->pairsSort.ensure(m, c->stream);
+  if (rc) return rc;
   if (m + 1 > c->pairsOffs.size()) {
-    const int64_t cells = (m + kStateTile - 1) / kStateTile * kStateBins;  // a count per tile and digit
-    HIPCHK(c->pairsHist.grow(cells, c->stream));
-    HIPCHK(c->pairsHistOffs.grow(cells + 1, c->stream));
-    HIPCHK(c->pairsHistSums.grow(cells / kScanPerBlock + 2, c->stream));
-    for (int k = 0; k < 2; ++k) {
-      HIPCHK(c->pairsKeys[k].grow(m, c->stream));
-      HIPCHK(c->pairsIdx[k].grow(m, c->stream));
-    }
     HIPCHK(c->pairsXY.grow(m, c->stream));
     HIPCHK(c->pairsSXY.grow(m, c->stream));
     HIPCHK(c->pairsCell.grow(m, c->stream));
@@ -1510,36 +1532,27 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   g.half = (flags & SC_PAIRS_HALF) ? 1 : 0;
   const int grid = grid_for(m);
   if (!dev_xy) {
-    if ((rc = state_rank(c, m))) return rc;
-    hipLaunchKernelGGL(k_pairs_gather, dim3(grid), dim3(kBlock), 0, c->stream, c->stateKeys[0].get(), c->stateSlots[0].get(),
-                       (int)m, c->x.get(), c->y.get(), c->pairsXY.get(), c->pairsWords.get());
+    int set;
+    if ((rc = state_rank(c, m, &set))) return rc;
+    hipLaunchKernelGGL(k_pairs_gather, dim3(grid), dim3(kBlock), 0, c->stream, c->stateSort.keys[set].get(),
+                       c->stateSort.vals[set].get(), (int)m, c->x.get(), c->y.get(), c->pairsXY.get(), c->pairsWords.get());
   }
   HIPCHK(hipMemsetAsync(c->pairsFlag, 0, sizeof(int), c->stream));
   HIPCHK(hipMemsetAsync(c->pairsBucketCount, 0, (size_t)buckets * sizeof(int), c->stream));
+  RadixSpace& w = c->pairsSort;
   hipLaunchKernelGGL(k_pairs_key, dim3(grid), dim3(kBlock), 0, c->stream, g, dev_xy ? (const XY*)dev_xy : c->pairsXY.get(),
-                     c->pairsXY.get(), dev_xy ? (long long)n : -1LL, c->pairsWords.get(), (int)m, c->pairsKeys[0].get(),
-                     c->pairsIdx[0].get(), c->pairsBucketCount.get(), c->pairsFlag.get());
+                     c->pairsXY.get(), dev_xy ? (long long)n : -1LL, c->pairsWords.get(), (int)m, w.keys[0].get(),
+                     w.vals[0].get(), c->pairsBucketCount.get(), c->pairsFlag.get());
   // the binning sort: the keys are 0 .. buckets (a dead point's), so as many digits as `buckets` has
   int bits = 1;
   while ((buckets >> bits) != 0) ++bits;
-  const int passes = m > 0 ? (bits + kStateDigitBits - 1) / kStateDigitBits : 0;
-  const int tiles = (int)((m + kStateTile - 1) / kStateTile);
-  int in = 0;
-  for (int pass = 0; pass < passes; ++pass, in ^= 1) {
-    const int shift = pass * kStateDigitBits;
-    hipLaunchKernelGGL(k_state_hist, dim3(tiles), dim3(kStateTile), 0, c->stream, (const int*)nullptr, (const double*)nullptr,
-                       (const int*)nullptr, 0, c->pairsKeys[in].get(), c->pairsIdx[in].get(), (int)m, shift, tiles,
-                       c->pairsHist.get());
-    if ((rc = launch_scan(c, c->pairsHist, c->pairsHistOffs, (int64_t)tiles * kStateBins, c->pairsHistSums, nullptr))) return rc;
-    hipLaunchKernelGGL(k_state_scatter, dim3(tiles), dim3(kStateTile), 0, c->stream, c->pairsKeys[in].get(),
-                       c->pairsIdx[in].get(), c->pairsKeys[in ^ 1].get(), c->pairsIdx[in ^ 1].get(), (int)m, shift, tiles,
-                       c->pairsHistOffs.get());
-  }
+  int in;
+  if ((rc = radix_sort(c, w, RadixStored{}, m, (bits + kRadixDigitBits - 1) / kRadixDigitBits, &in))) return rc;
   if ((rc = launch_scan(c, c->pairsBucketCount, c->pairsBucketStart, buckets, c->pairsBucketSums, nullptr))) return rc;
-  hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairsKeys[in].get(), c->pairsIdx[in].get(),
-                     (int)m, c->pairsXY.get(), c->pairsFlag.get(), c->pairsSXY.get(), c->pairsCell.get());
+  hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, w.keys[in].get(), w.vals[in].get(), (int)m,
+                     c->pairsXY.get(), c->pairsFlag.get(), c->pairsSXY.get(), c->pairsCell.get());
   hipLaunchKernelGGL(k_pairs_count, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairsWords.get(), c->pairsFlag.get(), (int)m,
-                     c->pairsXY.get(), c->pairsBucketStart.get(), c->pairsSXY.get(), c->pairsCell.get(), c->pairsIdx[in].get(),
+                     c->pairsXY.get(), c->pairsBucketStart.get(), c->pairsSXY.get(), c->pairsCell.get(), w.vals[in].get(),
                      c->pairsRowLen.get());
   const int nb = (int)(m / kScanPerBlock + 1);  // entry n <= m lies in one of them
   hipLaunchKernelGGL(k_scan64_local, dim3(nb), dim3(kBlock), 0, c->stream, c->pairsRowLen.get(), c->pairsOffs.get(),
@@ -1549,7 +1562,7 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   HIPCHK(hipGetLastError());
   c->pairs_valid = true;
   c->pairs_m = m;
-  c->pairs_sorted = in;
+  c->pairs_set = in;
   c->pairs_grid = g;
   return SC_OK;
 }
@@ -1566,7 +1579,7 @@ int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64
   if (room_pairs == 0) return SC_OK;
   hipLaunchKernelGGL(k_pairs_fill, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->pairs_grid, c->pairsWords.get(),
                      c->pairsFlag.get(), (int)m, c->pairsXY.get(), c->pairsOffs.get(), c->pairsBucketStart.get(),
-                     c->pairsSXY.get(), c->pairsCell.get(), c->pairsIdx[c->pairs_sorted].get(), (long long*)dev_partners, dev_d2,
+                     c->pairsSXY.get(), c->pairsCell.get(), c->pairsSort.vals[c->pairs_set].get(), (long long*)dev_partners, dev_d2,
                      (long long)room_pairs);
   HIPCHK(hipGetLastError());
   return SC_OK;
@@ -2090,13 +2103,7 @@ int sc_download_normals(sc_ctx* c, double* sxy, int64_t room, int64_t* n_out) {
   if ((rc = fetch(c, ab.data(), c->snn, 2 * n * sizeof(double))) || (rc = fetch(c, id.data(), c->id[1], n * sizeof(int))))
     return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  std::vector<int> order(n);
-  std::iota(order.begin(), order.end(), 0);
-  std::sort(order.begin(), order.end(), [&](int p, int q) { return id[p] < id[q]; });
-  for (int64_t k = 0; k < n && sxy; ++k) {
-    sxy[2 * k] = ab[2 * order[k]];
-    sxy[2 * k + 1] = ab[2 * order[k] + 1];
-  }
+  write_pairs(sxy, index_order(id.data(), nullptr, n), ab.data(), ab.data() + 1, 2);
   return SC_OK;
 }
 
@@ -2833,11 +2840,7 @@ int sc_checkpoint_finish(sc_ctx* c, double* xy, double* vxy, int64_t* ids, int64
   HIPCHK(hipEventSynchronize(c->snap_done));
   c->snap_pending = false;
   const int64_t stored = std::min<int64_t>(c->snap_counters_h[C_NS], c->snap_n_bound);
-  std::vector<int> order;
-  order.reserve(stored);
-  for (int64_t k = 0; k < stored; ++k)
-    if (std::isfinite(c->snap_h[0][k])) order.push_back((int)k);  // slab mode leaves dead ghost copies (x = +inf) behind
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return c->snap_id_h[a] < c->snap_id_h[b]; });
+  const std::vector<int> order = index_order(c->snap_id_h, c->snap_h[0], stored);
   const int64_t n = (int64_t)order.size();
   *n_out = n;
   if (tick) *tick = c->snap_tick;
@@ -2846,18 +2849,9 @@ int sc_checkpoint_finish(sc_ctx* c, double* xy, double* vxy, int64_t* ids, int64
   if (rng_pos) *rng_pos = c->snap_has_rng ? rs.pos : -1;
   if (rng_key && c->snap_has_rng) std::memcpy(rng_key, rs.mt, sizeof rs.mt);
   if (n > room) return fail(SC_ERR_CAPACITY, "host arrays hold %lld, the checkpoint has %lld particles", (long long)room, (long long)n);
-  for (int64_t k = 0; k < n; ++k) {
-    const int s = order[k];
-    if (xy) {
-      xy[2 * k] = c->snap_h[0][s];
-      xy[2 * k + 1] = c->snap_h[1][s];
-    }
-    if (vxy) {
-      vxy[2 * k] = c->snap_h[2][s];
-      vxy[2 * k + 1] = c->snap_h[3][s];
-    }
-    if (ids) ids[k] = c->snap_id_h[s];
-  }
+  write_pairs(xy, order, c->snap_h[0], c->snap_h[1]);
+  write_pairs(vxy, order, c->snap_h[2], c->snap_h[3]);
+  for (int64_t k = 0; k < n && ids; ++k) ids[k] = c->snap_id_h[order[k]];
   return SC_OK;
 }
 

@@ -225,6 +225,14 @@ __device__ __forceinline__ int wave_scan_add(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31: rows 2, 3 += rows 0 + 1
   return v;
 }
+__device__ __forceinline__ long long wave_scan_add(long long v) {
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
 
 // Lane i's copy of lane (i ^ J)'s value: on the DPP path for J below 16 (quad permutes, row shifts under bank masks,
 // a row rotate), through the LDS crossbar otherwise.  Every lane of the wave must call this.
@@ -249,6 +257,10 @@ __device__ __forceinline__ double xor_lane(double v) {
 }
 
 __device__ __forceinline__ int wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
 }

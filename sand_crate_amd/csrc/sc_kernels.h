@@ -284,9 +284,38 @@ __global__ void __launch_bounds__(kBlock) k_wall_bin(World w, int* __restrict__ 
 constexpr int kScanPerThread = 8;
 constexpr int kScanPerBlock = kBlock * kScanPerThread;
 
+// The block-level body of the two, on the sum type (k_scan64_local / k_scan64_fix in sc_pairs.h are the same two levels
+// in 64 bits).  Every thread of the workgroup calls these: there is a barrier inside.
+//
+// The sum of the `sum`s of the threads before this one in its workgroup.
+template <class T>
+__device__ __forceinline__ T scan_block_excl(T sum) {
+  __shared__ T waveTot[kBlock / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const T incl = wave_scan_add(sum);
+  if (lane == 63) waveTot[wv] = incl;
+  __syncthreads();
+  T wbase = 0;
+  for (int k = 0; k < wv; ++k) wbase += waveTot[k];
+  return wbase + incl - sum;
+}
+
+// The sum of the blockSums of the workgroups before this one.
+template <class T>
+__device__ __forceinline__ T scan_blocks_before(const T* __restrict__ blockSums) {
+  __shared__ T waveTot[kBlock / 64];
+  T acc = 0;
+  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) acc += blockSums[b];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) waveTot[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  T off = 0;
+  for (int k = 0; k < kBlock / 64; ++k) off += waveTot[k];
+  return off;
+}
+
 __global__ void __launch_bounds__(kBlock) k_scan_local(const int* __restrict__ in, int* __restrict__ out, int n,
                                                        int* __restrict__ blockSums) {
-  __shared__ int waveTot[kBlock / 64];
   int base = blockIdx.x * kScanPerBlock + threadIdx.x * kScanPerThread;
   int v[kScanPerThread];
   int sum = 0;
@@ -296,13 +325,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_local(const int* __restrict__ i
     v[k] = sum;
     sum += e;
   }
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int incl = wave_scan_add(sum);
-  if (lane == 63) waveTot[wv] = incl;
-  __syncthreads();
-  int wbase = 0;
-  for (int k = 0; k < wv; ++k) wbase += waveTot[k];
-  int excl = wbase + incl - sum;
+  const int excl = scan_block_excl(sum);
 #pragma unroll
   for (int k = 0; k < kScanPerThread; ++k)
     if (base + k < n) out[base + k] = excl + v[k];
@@ -311,14 +334,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_local(const int* __restrict__ i
 
 __global__ void __launch_bounds__(kBlock) k_scan_fix(int* __restrict__ out, int n, const int* __restrict__ blockSums,
                                                      int nblocks, int* __restrict__ total_out) {
-  __shared__ int waveTot[kBlock / 64];
-  int acc = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) acc += blockSums[b];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) waveTot[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  int off = 0;
-  for (int k = 0; k < kBlock / 64; ++k) off += waveTot[k];
+  const int off = scan_blocks_before(blockSums);
   int base = blockIdx.x * kScanPerBlock + threadIdx.x * kScanPerThread;
 #pragma unroll
   for (int k = 0; k < kScanPerThread; ++k)

@@ -3,21 +3,22 @@
 // exclusive scan of the row lengths, 64 bit) and partners, row by row and ascending in j.  The rule is specified in NumPy
 // by tests/pairs_spec.py; the result is a pure function of the points.  Included once by sandcrate_hip.hip.
 //
-// The points are the caller's array, or the state in particle-index order: the export's ranking (sc_state.h) and
-// k_pairs_gather.  Either way they are copied into the context's workspace, so the fill does not read the caller's memory
+// The points are the caller's array, or the state in particle-index order: the export's ranking and its rule of the
+// live rows (sc_state.h), and k_pairs_gather.  Either way they are copied into the context's workspace, so the fill does not read the caller's memory
 // again.  Then
 //   k_pairs_key     the cell of every point, (floor(x / h), floor(y / h)), its bucket in a hashed table of kPairsLoad * n
 //                   buckets (a power of two; pairs_bucket below) and the bucket's count (integer atomics: a count does not
 //                   depend on their order).  The key of a point is its bucket; a point with a coordinate that is not
 //                   finite gets the key `buckets`, which sorts behind all of them: it is in no bucket, so it is
 //                   nobody's partner.  The same kernel raises the domain flag (below);
-//   k_state_hist / k_scan_* / k_state_scatter (sc_state.h)  the stable radix sort of (bucket, index) pairs, as many passes
-//                   of eight bits as the bucket index has: every bucket's members end up contiguous and ascending in index;
+//   the stable radix sort of sc_radix.h over those (bucket, index) pairs, as many passes of eight bits as the bucket index
+//                   has: every bucket's members end up contiguous and ascending in index;
 //   k_scan_* over the buckets' counts: where every bucket starts;
 //   k_pairs_place   the members' positions and cells in that order (a candidate is then one 16-byte and one 8-byte read);
 //   k_pairs_count   a thread per row walks the buckets of its point's nine cells and counts the partners;
-//   k_scan64_local / k_scan64_fix  the exclusive scan of the row lengths in 64 bits -- two levels like k_scan_local /
-//                   k_scan_fix, no workgroup waits for another -- into the workspace and the caller's offsets, and E;
+//   k_scan64_local / k_scan64_fix  the exclusive scan of the row lengths in 64 bits -- the two levels of k_scan_local /
+//                   k_scan_fix (sc_kernels.h), no workgroup waits for another -- into the workspace and the caller's
+//                   offsets, and E;
 //   k_pairs_fill    a thread per row merges its nine runs (each ascending in j) by always taking the smallest head; the
 //                   cursors live in LDS (a dynamically indexed register array would go to scratch).
 // A hashed table: the bounding box is known on the device only, and a loaded state may be arbitrarily sparse.  Several of
@@ -69,15 +70,12 @@ __device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsig
 
 __device__ __forceinline__ unsigned pairs_cell(double c, double h) { return (unsigned)(int)floor(c / h); }
 
-// The state form: row k is the slot with the k-th smallest id, as in k_state_gather; n is the border to kStateDead.
+// The state form: row k is the slot with the k-th smallest id, as in k_state_gather.
 __global__ void __launch_bounds__(kBlock)
     k_pairs_gather(const unsigned* __restrict__ keys, const int* __restrict__ slots, int m, const double* __restrict__ x,
                    const double* __restrict__ y, XY* __restrict__ xy, long long* __restrict__ words) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k == 0 && (m == 0 || keys[0] == kStateDead)) words[PW_N] = 0;
-  if (k >= m) return;
-  if (keys[k] == kStateDead) return;
-  if (k == m - 1 || keys[k + 1] == kStateDead) words[PW_N] = (long long)k + 1;
+  if (!state_row_live(keys, k, m, &words[PW_N])) return;
   const int s = slots[k];
   xy[k] = XY{x[s], y[s]};
 }
@@ -166,19 +164,9 @@ __global__ void __launch_bounds__(kBlock)
 
 // The exclusive scan of in[0 .. n) in 64 bits into out[0 .. n] (out[n] is the total), n = words[PW_N] <= the launch's
 // bound: k_scan_local / k_scan_fix with wider sums.  Entries of `in` from n on are not read.
-__device__ __forceinline__ long long wave_scan_add64(long long v) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 __global__ void __launch_bounds__(kBlock)
     k_scan64_local(const int* __restrict__ in, long long* __restrict__ out, const long long* __restrict__ words,
                    const int* __restrict__ flag, long long* __restrict__ blockSums) {
-  __shared__ long long waveTot[kBlock / 64];
   if (*flag) return;
   const long long n = words[PW_N];
   const long long base = (long long)blockIdx.x * kScanPerBlock + (long long)threadIdx.x * kScanPerThread;
@@ -190,13 +178,7 @@ __global__ void __launch_bounds__(kBlock)
     v[k] = sum;
     sum += e;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long incl = wave_scan_add64(sum);
-  if (lane == 63) waveTot[wv] = incl;
-  __syncthreads();
-  long long wbase = 0;
-  for (int k = 0; k < wv; ++k) wbase += waveTot[k];
-  const long long excl = wbase + incl - sum;
+  const long long excl = scan_block_excl(sum);
 #pragma unroll
   for (int k = 0; k < kScanPerThread; ++k)
     if (base + k <= n) out[base + k] = excl + v[k];
@@ -208,7 +190,6 @@ __global__ void __launch_bounds__(kBlock)
 __global__ void __launch_bounds__(kBlock)
     k_scan64_fix(long long* __restrict__ out, long long* __restrict__ out_caller, long long* __restrict__ words,
                  const int* __restrict__ flag, const long long* __restrict__ blockSums, long long* __restrict__ counts) {
-  __shared__ long long waveTot[kBlock / 64];
   const long long n = words[PW_N];
   if (*flag) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -218,13 +199,7 @@ __global__ void __launch_bounds__(kBlock)
     }
     return;
   }
-  long long acc = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) acc += blockSums[b];
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) waveTot[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  long long off = 0;
-  for (int k = 0; k < kBlock / 64; ++k) off += waveTot[k];
+  const long long off = scan_blocks_before(blockSums);
   const long long base = (long long)blockIdx.x * kScanPerBlock + (long long)threadIdx.x * kScanPerThread;
 #pragma unroll
   for (int k = 0; k < kScanPerThread; ++k) {

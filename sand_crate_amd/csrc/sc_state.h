@@ -3,34 +3,22 @@
 // sc_download_state delivers to the host.  Included once by sandcrate_hip.hip.  The export only reads the state: no
 // counter of the tick, flag or particle array is written.
 //
-// The storage arrays are in cell-sorted order; the caller's order is ascending id.  The ranking is an LSD radix sort of
-// (id, slot) pairs, hand-written: kStatePasses passes over kStateDigitBits bits each, and per pass
-//   k_state_hist     a workgroup counts the digits of its kStateTile keys in LDS (integer atomics) and writes its 256
-//                    counts digit-major: hist[digit * tiles + tile].  The first pass also MAKES the pairs: the key of a
-//                    stored slot whose x is finite is its id, every other slot of the launch gets kStateDead, which is
-//                    above every id (ids stay below 2^31 - 1) and so sorts behind all of them;
-//   k_scan_local / k_scan_fix (sc_kernels.h)  the exclusive scan of those counts: in digit-major order it is, for every
-//                    (digit, tile), the place of the tile's first key with that digit;
-//   k_state_scatter  a key goes to that place plus its rank among the tile's keys of the same digit: the lanes of a wave
-//                    that hold the same digit find each other with eight ballots, the waves' counts meet in LDS.  Keys of
-//                    equal digit keep their order (the sort is stable), so four passes order by the whole key.
-// No workgroup waits for another, no floating-point or order-dependent atomics: the result is a pure function of the
-// stored state.  k_state_gather then moves slot slots[k] to row k: (x, y) and (vx, vy) as 16-byte records, the pressure,
-// the id, and -- the one thread that sits on the border between ids and kStateDead -- the count.
+// The storage arrays are in cell-sorted order; the caller's order is ascending id.  The ranking is the radix sort of
+// sc_radix.h over (id, slot) pairs, kStatePasses passes.  Its first pass makes the pairs from the stored state (StateKey):
+// the key of a stored slot whose x is finite is its id, every other slot of the launch gets kStateDead, which is above
+// every id (ids stay below 2^31 - 1) and so sorts behind all of them.  The index-order rule on the device is then
+// state_row_live: row k is live while its key is an id, and n is where the ids end.  k_state_gather moves slot slots[k]
+// to row k: (x, y) and (vx, vy) as 16-byte records, the pressure and the id.
 // Cost: linear in the launch bound (the stored count; in slab mode the capacity), whatever the ids are.
 #pragma once
 #include "sc_device.h"
+#include "sc_radix.h"
 
 namespace sc {
 
-constexpr int kStateTile = 256;       // keys (= threads) per workgroup of a sorting pass
-constexpr int kStateDigitBits = 8;
-constexpr int kStateBins = 1 << kStateDigitBits;
-constexpr int kStatePasses = 4;       // 32 bits: ids below 2^31 - 1 and kStateDead above them (an even number: the
-                                      // pairs end in the set they started in)
+constexpr int kStatePasses = 4;  // 32 bits: ids below 2^31 - 1 and kStateDead above them
 constexpr unsigned kStateDead = 0xFFFFFFFFu;
-static_assert(kStateBins == kStateTile, "thread t writes the tile's count of digit t");
-static_assert(kStatePasses * kStateDigitBits == 32 && kStatePasses % 2 == 0, "the passes cover the key");
+static_assert(kStatePasses * kRadixDigitBits == 32, "the passes cover the key");
 
 // what the export writes; any of the four arrays may be null
 struct StateOut {
@@ -41,64 +29,25 @@ struct StateOut {
   long long* n;
 };
 
-// `x` given: the first pass, which makes the pairs of the m slots of the launch from the stored state.
-__global__ void __launch_bounds__(kStateTile)
-    k_state_hist(const int* __restrict__ counters, const double* __restrict__ x, const int* __restrict__ id, int cap,
-                 unsigned* __restrict__ keys, int* __restrict__ slots, int m, int shift, int tiles, int* __restrict__ hist) {
-  __shared__ int s_h[kStateBins];
-  const int tid = (int)threadIdx.x;
-  s_h[tid] = 0;
-  __syncthreads();
-  const int i = (int)blockIdx.x * kStateTile + tid;
-  if (i < m) {
-    unsigned key;
-    if (x) {
-      const int ns = min(counters[C_NS], cap);
-      key = (i < ns && fabs(x[i]) < __builtin_inf()) ? (unsigned)id[i] : kStateDead;  // (NaN compares false: dead)
-      keys[i] = key;
-      slots[i] = i;
-    } else {
-      key = keys[i];
-    }
-    atomicAdd(&s_h[(key >> shift) & (kStateBins - 1)], 1);
+// The key of slot i, for the first pass of the ranking (k_radix_hist).
+struct StateKey {
+  const int* counters;
+  const double* x;
+  const int* id;
+  int cap;
+  __device__ unsigned operator()(int i) const {
+    const int ns = min(counters[C_NS], cap);
+    return (i < ns && fabs(x[i]) < __builtin_inf()) ? (unsigned)id[i] : kStateDead;  // (NaN compares false: dead)
   }
-  __syncthreads();
-  hist[(size_t)tid * tiles + blockIdx.x] = s_h[tid];
-}
+};
 
-__global__ void __launch_bounds__(kStateTile)
-    k_state_scatter(const unsigned* __restrict__ keys_in, const int* __restrict__ slots_in, unsigned* __restrict__ keys_out,
-                    int* __restrict__ slots_out, int m, int shift, int tiles, const int* __restrict__ offs) {
-  __shared__ int s_cnt[kStateTile / 64][kStateBins];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int w = 0; w < kStateTile / 64; ++w) s_cnt[w][tid] = 0;
-  __syncthreads();
-  const int i = (int)blockIdx.x * kStateTile + tid;
-  const bool on = i < m;
-  const unsigned key = on ? keys_in[i] : 0u;
-  const int slot = on ? slots_in[i] : 0;
-  const int digit = (int)((key >> shift) & (kStateBins - 1));
-  // the lanes of this wave that hold a key with the same digit (every lane of the wave takes part in the ballots)
-  unsigned long long peers = __ballot(on);
-#pragma unroll
-  for (int b = 0; b < kStateDigitBits; ++b) {
-    const bool bit = (digit >> b) & 1;
-    const unsigned long long set = __ballot(on && bit);
-    peers &= bit ? set : ~set;
-  }
-  const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-  if (on && rank == 0) s_cnt[wv][digit] = __popcll(peers);
-  __syncthreads();
-  if (on) {
-    int before = 0;
-    for (int w = 0; w < wv; ++w) before += s_cnt[w][digit];
-    const int dest = offs[(size_t)digit * tiles + blockIdx.x] + before + rank;
-    if ((unsigned)dest < (unsigned)m) {  // (always, when the counts are this launch's)
-      keys_out[dest] = key;
-      slots_out[dest] = slot;
-    }
-  }
+// Is k a live row of the m ranked keys?  The one thread that sits on the border between ids and kStateDead writes the
+// count to *n.  Every thread of a launch over at least max(m, 1) rows calls this.
+__device__ __forceinline__ bool state_row_live(const unsigned* __restrict__ keys, int k, int m, long long* __restrict__ n) {
+  if (k == 0 && (m == 0 || keys[0] == kStateDead)) *n = 0;
+  if (k >= m || keys[k] == kStateDead) return false;
+  if (k == m - 1 || keys[k + 1] == kStateDead) *n = (long long)k + 1;
+  return true;
 }
 
 // Row k of the caller's arrays is the slot with the k-th smallest id.  The pressure follows sc_download_state's rule:
@@ -109,11 +58,7 @@ __global__ void __launch_bounds__(kBlock)
                    const double* __restrict__ y, const double* __restrict__ vx, const double* __restrict__ vy,
                    const double* __restrict__ P) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k == 0 && (m == 0 || keys[0] == kStateDead)) *o.n = 0;
-  if (k >= m) return;
-  const unsigned key = keys[k];
-  if (key == kStateDead) return;
-  if (k == m - 1 || keys[k + 1] == kStateDead) *o.n = (long long)k + 1;
+  if (!state_row_live(keys, k, m, o.n)) return;
   const int s = slots[k];
   if (o.xy) ((XY*)o.xy)[k] = XY{x[s], y[s]};
   if (o.vxy) ((XY*)o.vxy)[k] = XY{vx[s], vy[s]};
@@ -122,7 +67,7 @@ __global__ void __launch_bounds__(kBlock)
     const int np = pressure_valid ? pressure_slots(counters, ns) : 0;
     o.pressure[k] = s < np ? P[s] : 0.0;
   }
-  if (o.ids) o.ids[k] = (long long)key;
+  if (o.ids) o.ids[k] = (long long)keys[k];
 }
 
 // The import's ids: 64-bit in the caller's memory, 32-bit in the library's.  words[0] becomes the largest id plus one

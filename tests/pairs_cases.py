@@ -98,6 +98,18 @@ def non_finite():
     return pts, radius
 
 
+def three_passes():
+    """The smallest n whose table has 65536 buckets: the keys 0 .. 65536 then need 17 bits, and the binning sort a third
+    pass of eight.  40 points with a coordinate that is not finite carry the key 65536, the only one with a non-zero third
+    digit: that pass has to move them behind every live point (every smaller case has an even number of passes)."""
+    n = 32768 // N.PAIRS_LOAD + 1
+    pts, radius = cloud(51, n)
+    values = [np.nan, np.inf, -np.inf]
+    for k, i in enumerate(np.random.RandomState(52).choice(n, 40, replace=False)):
+        pts[i, k % 2] = values[k % 3]
+    return pts, radius
+
+
 def lattice(radius, reach=3):
     """Points on exact multiples of the radius, negative ones and -0.0 included (fl(k * radius), k = -reach .. reach)."""
     k = np.arange(-reach, reach + 1, dtype=np.float64)
@@ -166,6 +178,7 @@ def cases():
     out["long_rows"] = long_rows()
     out["non_finite"] = non_finite()
     out["domain_rim"] = domain_rim()
+    out["three_passes"] = three_passes()
     for pts, _ in out.values():
         pts.setflags(write=False)
     return out

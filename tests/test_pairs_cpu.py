@@ -108,6 +108,8 @@ def test_constants_mirror_the_kernels():
     assert int(constant("kPairsHashY").rstrip("u"), 16) == N.PAIRS_HASH_Y
     assert int(constant("kPairsHashMix").rstrip("u"), 16) == N.PAIRS_HASH_MIX
     assert constant("kPairsCellFactor") == "1.0 + 1.0 / 1048576.0" and N.PAIRS_CELL_FACTOR == 1.0 + 1.0 / 1048576.0
+    text = (ROOT / "sand_crate_amd" / "csrc" / "sc_radix.h").read_text()     # the sort both the export and the search run
+    assert int(constant("kRadixTile")) == N.STATE_TILE == N.PAIRS_SORT_TILE
     header = HEADER.read_text()
     assert re.search(r"SC_PAIRS_HALF\s*=\s*1\b", header)
     assert re.search(r"#define SC_ABI_VERSION 5\b", header) and re.search(r"#define SC_NUM_KERNELS 12\b", header)
