@@ -643,6 +643,37 @@ int sc_pairs_count_device(sc_ctx* ctx, const double* dev_xy /* NULL: the state *
                           int64_t* dev_offsets, int64_t room_rows, int64_t* dev_counts /* [2]: n, E */);
 int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* may be NULL */, int64_t room_pairs);
 
+/* The clusters of that graph in DEVICE memory of the caller: what hangs together.  tests/cluster_spec.py is the rule: a
+ * cluster is a connected component of the graph above -- i ~ j iff (i, j) is a pair of the full list, whether or not the
+ * count had SC_PAIRS_HALF -- over the points whose coordinates are all finite; a point with a coordinate that is not finite
+ * is in no cluster and bridges none.  Clusters are numbered 0 .. C-1 in ascending order of their smallest member index:
+ * dev_roots[c] is that member, dev_sizes[c] the member count, dev_labels[i] the cluster of point i, or -1 for a point in
+ * none.  The result is a pure function of the points.
+ *
+ * sc_pairs_label_device  labels the points of the last sc_pairs_count_device of this context, in either form and with any
+ *     flags: it reads the grid that count left in the workspace, not the caller's points.  Writes dev_labels[0 .. n-1]
+ *     (int64), always whole; dev_sizes[c] and dev_roots[c] (int64, either may be NULL) for c < min(C, room_clusters) only:
+ *     entries from the room on are left as they were; dev_counts[0] = n, dev_counts[1] = C.  `room_rows`, the room of
+ *     dev_labels, must be at least the bound the count was sized by.  After a count that found a point outside the domain
+ *     dev_counts[1] = -1 is written and nothing else.  The workspace of the count is left as it is: sc_pairs_fill_device
+ *     may follow, and the labelling may be repeated.
+ * It enqueues on the context's stream only, with the rules of the two calls above: nothing synchronises, nothing reaches
+ * the host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches
+ * are not bracketed by the timing events.
+ *     The algorithm: every point starts as a set of its own (parent[i] = i); a thread per row walks its nine cells as the
+ * count does and unites its set with that of every partner j < i -- finds with path halving, the larger root hooked under
+ * the smaller by a compare-and-swap, so parent[x] <= x throughout and a set's root is its smallest member in whatever order
+ * the atomics land; ceil(log2(max(m, 2))) launches of pointer jumping, m the bound, then leave every parent at its root;
+ * an exclusive scan of "is a root" numbers the clusters; one more pass writes labels, roots and (integer atomics) sizes.
+ * No workgroup waits for another and no atomic's order reaches the output (csrc/sc_clusters.h).  The workspace belongs to
+ * the context: about 16 bytes per point of the bound, grown -- which synchronises once -- to the largest bound asked for.
+ *     SC_ERR_ARG for a null context, null dev_labels or dev_counts, or a negative room.  SC_ERR_STATE between
+ * sc_step_begin and sc_step_finish, when there is no count, and when a tick, an upload, an append, an emission, an import
+ * or a track load has touched the state since (the fill's rule).  SC_ERR_CAPACITY when room_rows is below the count's
+ * bound.  All checked before anything is launched: the arrays are then untouched. */
+int sc_pairs_label_device(sc_ctx* ctx, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes /* may be NULL */,
+                          int64_t* dev_roots /* may be NULL */, int64_t room_clusters, int64_t* dev_counts /* [2]: n, C */);
+
 #ifdef __cplusplus
 }
 #endif

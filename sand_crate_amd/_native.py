@@ -178,6 +178,7 @@ SIGNATURES = {
     "sc_import_state_device": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
     "sc_pairs_count_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32, _P, C.c_int64, _P]),
     "sc_pairs_fill_device": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "sc_pairs_label_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
 }
 
 

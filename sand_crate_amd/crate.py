@@ -302,6 +302,53 @@ class Crate:
             return (offsets[:n + 1], partners) + ((d2,) if squared_distances else ())
         return (offsets, partners) + ((d2,) if squared_distances else ()) + (counts,)
 
+    def cluster_tensors(self, radius: float | None = None, *, points=None, max_clusters: int | None = None):
+        """What hangs together: the connected components of the graph `pair_tensors` defines at the same `radius` (default:
+        `diameter`), labelled on the GPU from the pair search's grid (sc_pairs_count_device, then sc_pairs_label_device),
+        as torch CUDA tensors on the crate's device: ``(labels, sizes, roots)`` -- int64 (n,), (C,), (C,).  ``labels[i]``
+        is the cluster of row i of `state_tensors()` at the same point of the stream, or -1 for a particle with a
+        coordinate that is not finite: it is in no cluster and bridges none.  Clusters are numbered 0..C-1 in ascending
+        order of their smallest member, ``roots[c]``; ``sizes[c]`` is the member count (tests/cluster_spec.py is the
+        rule; `sand_crate_amd.pairs.largest_cluster` and `cluster_size_of` read the result).  `points`, a float64 (n, 2)
+        CUDA tensor, is labelled instead of the state.
+
+        By default the call synchronises once, reads n and C (16 bytes) and returns tensors cut to them; a coordinate with
+        |c| / radius >= 2^31 raises ValueError.  With `max_clusters=K` nothing synchronises: `labels` comes at capacity
+        entries (n with `points`), `sizes` and `roots` at K entries, and last the int64 `counts` tensor (n, C): entries of
+        `labels` past n and of `sizes` and `roots` past min(C, K) are uninitialised, C > K means that the clusters from K
+        on were not written (`labels` is whole all the same), C = -1 is the domain error (nothing else was written).  The
+        tensors are written on the library's stream, and the library's stream does not wait for torch's: read them after
+        `synchronize()`, and have `points` ready before the call -- or run the crate on torch's stream,
+        `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(self.diameter if radius is None else radius)
+        rows = eng.capacity if points is None else _point_rows(points)
+        sync = max_clusters is None
+        room = rows if sync else int(max_clusters)
+        if room < 0:
+            raise ValueError("max_clusters must not be negative")
+        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)  # (a temporary: the label reads the workspace)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)          # (n, E) of the count, then (n, C)
+        labels = torch.empty(rows, dtype=torch.int64, device=dev)
+        sizes = torch.empty(room, dtype=torch.int64, device=dev)
+        roots = torch.empty(room, dtype=torch.int64, device=dev)
+        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        eng.pairs_label(labels, sizes, roots, counts=counts)
+        if not sync:
+            self._cluster_offsets = offsets  # (held until the next call: the count that writes it is still queued)
+            return labels, sizes, roots, counts
+        eng.synchronize()
+        n, total = (int(v) for v in counts.cpu())
+        if total < 0:
+            raise ValueError(f"cluster_tensors: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
+        if points is None:
+            self._count, self._count_known = n, True
+        return labels[:n], sizes[:total], roots[:total]
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

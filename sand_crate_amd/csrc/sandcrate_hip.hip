@@ -28,6 +28,7 @@
 #include "sc_radix.h"
 #include "sc_state.h"
 #include "sc_pairs.h"
+#include "sc_clusters.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
@@ -268,6 +269,10 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   int64_t pairs_m = 0;   // ... the bound its launches were sized by
   int pairs_set = 0;     // ... which of pairsSort's two sets holds the sorted pairs
   PairsGrid pairs_grid{};
+  // sc_pairs_label_device (sc_clusters.h): the parents, the root marks, their scan (the dense numbers) with its block sums
+  // and the clusters' sizes -- apart from the pairs workspace, which a fill after the labelling still reads; each grown to
+  // the largest bound asked for
+  DevBuf<int> clusterParent, clusterIsRoot, clusterSize, clusterSums, clusterDense;
   int64_t emit_most = 0;  // the largest per-call bound of emitted particles so far (sc_emit_particles)
   // the progress block (kProgress* in sc_kernels.h): written by the GPU, read by the host without synchronisation
   Owned<int, PinnedMem<hipHostMallocMapped>> progress;
@@ -1581,6 +1586,55 @@ int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64
                      c->pairsFlag.get(), (int)m, c->pairsXY.get(), c->pairsOffs.get(), c->pairsBucketStart.get(),
                      c->pairsSXY.get(), c->pairsCell.get(), c->pairsSort.vals[c->pairs_set].get(), (long long*)dev_partners, dev_d2,
                      (long long)room_pairs);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- clusters (sc_clusters.h) --------------------------------------------------------------------
+
+int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
+                          int64_t room_clusters, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_labels || !dev_counts) return fail(SC_ERR_ARG, "null labels or counts pointer");
+  if (room_rows < 0 || room_clusters < 0) return fail(SC_ERR_ARG, "negative room");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_label_device inside a tick");
+  if (!c->pairs_valid)
+    return fail(SC_ERR_STATE, "no pair count to label from: sc_pairs_count_device comes first, and the state must not change in between");
+  const int64_t m = c->pairs_m;
+  if (room_rows < m)
+    return fail(SC_ERR_CAPACITY, "labels hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  if (m + 1 > c->clusterDense.size()) {  // (sized by the last member, which grows last)
+    HIPCHK(c->clusterParent.grow(m, c->stream));
+    HIPCHK(c->clusterIsRoot.grow(m, c->stream));
+    HIPCHK(c->clusterSize.grow(m, c->stream));
+    HIPCHK(c->clusterSums.grow(m / kScanPerBlock + 2, c->stream));
+    HIPCHK(c->clusterDense.grow(m + 1, c->stream));
+  }
+  PairsGrid g = c->pairs_grid;
+  g.half = 0;  // the components are those of the full graph, whichever form the count had
+  const int grid = grid_for(m);
+  const long long* words = c->pairsWords.get();
+  const int* flag = c->pairsFlag.get();
+  int* parent = c->clusterParent.get();
+  hipLaunchKernelGGL(k_cluster_init, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
+  hipLaunchKernelGGL(k_cluster_union, dim3(grid), dim3(kBlock), 0, c->stream, g, words, flag, (int)m, c->pairsXY.get(),
+                     c->pairsBucketStart.get(), c->pairsSXY.get(), c->pairsCell.get(),
+                     c->pairsSort.vals[c->pairs_set].get(), parent);
+  // a tree of at most m nodes is at most m - 1 deep, and a round halves (rounding up) every depth
+  int rounds = 1;
+  while (((int64_t)1 << rounds) < m) ++rounds;
+  for (int r = 0; r < rounds; ++r)
+    hipLaunchKernelGGL(k_cluster_jump, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
+  hipLaunchKernelGGL(k_cluster_mark, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->pairsXY.get(), parent,
+                     c->clusterIsRoot.get(), c->clusterSize.get());
+  const int rc = launch_scan(c, c->clusterIsRoot, c->clusterDense, m, c->clusterSums, nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_cluster_write, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->pairsXY.get(), parent,
+                     c->clusterDense.get(), c->clusterSize.get(), (long long*)dev_labels, (long long*)dev_roots,
+                     (long long)room_clusters);
+  hipLaunchKernelGGL(k_cluster_finish, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->clusterDense.get(),
+                     c->clusterSize.get(), (long long*)dev_sizes, (long long)room_clusters, (long long*)dev_counts);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

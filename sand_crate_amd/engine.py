@@ -216,6 +216,33 @@ class Engine:
                                                None if d2 is None else N._P(d2.data_ptr()), room))
         return partners
 
+    def pairs_label(self, labels, sizes=None, roots=None, *, counts, room: int | None = None,
+                    room_clusters: int | None = None):
+        """Labels the clusters -- the connected components -- of the graph of the last `pairs_count`, whichever `half` it
+        had (sc_pairs_label_device; the rule is tests/cluster_spec.py): `labels`, int64 (R,), receives every point's
+        cluster, -1 for a point with a coordinate that is not finite; `sizes` and `roots`, int64 (K,) or None, each
+        cluster's member count and smallest member; clusters are numbered 0..C-1 ascending in that member.  `counts`,
+        int64 (2,), receives n and C (C = -1: the count found a coordinate outside the domain, nothing else is written).
+        `room` defaults to R rows, `room_clusters` to K (0 without `sizes` and `roots`): clusters from it on are not
+        written.  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
+        rows = _state_tensor(labels, "labels", "int64", (), self.device)
+        clusters = None
+        for t, name in ((sizes, "sizes"), (roots, "roots")):
+            if t is not None:
+                clusters = _state_tensor(t, name, "int64", (), self.device, clusters)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the labels' {rows} rows")
+        room_clusters = (clusters or 0) if room_clusters is None else int(room_clusters)
+        if room_clusters > (clusters or 0):
+            raise ValueError(f"room_clusters {room_clusters} exceeds the tensors' {clusters or 0} entries")
+        # (an empty tensor has no address: nothing is written there, any address serves)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_label_device(self._ctx, ptr(labels), room, ptr(sizes), ptr(roots), room_clusters,
+                                                N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

@@ -1,4 +1,5 @@
-"""Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners)."""
+"""Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
+`Crate.cluster_tensors` (labels, sizes)."""
 from __future__ import annotations
 
 
@@ -15,3 +16,19 @@ def edge_index(offsets, partners):
     rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=offsets.device), row_lengths(offsets))
     k = min(int(rows.shape[0]), int(partners.shape[0]))
     return torch.stack([rows[:k], partners[:k]])
+
+
+def cluster_size_of(labels, sizes):
+    """The size of every point's cluster (`Crate.cluster_tensors`): int64 (n,), 0 for a point in no cluster (label -1)."""
+    import torch
+    if sizes.shape[0] == 0:
+        return torch.zeros_like(labels)
+    return torch.where(labels >= 0, sizes[labels.clamp(min=0)], torch.zeros_like(labels))
+
+
+def largest_cluster(sizes):
+    """-> (index, size) of the largest cluster, the first of equals; (-1, 0) when there is none."""
+    if sizes.shape[0] == 0:
+        return -1, 0
+    c = int(sizes.argmax())
+    return c, int(sizes[c])
