@@ -1,0 +1,201 @@
+// Host side of the state in the caller's device memory: export and import, pair lists and clusters.
+#pragma once
+#include "sc_host.h"
+#include "sc_state.h"
+#include "sc_pairs.h"
+#include "sc_clusters.h"
+
+extern "C" {
+
+// ---- the state in the caller's device memory (sc_state.h) ---------------------------------------
+
+// Ranks the m slots of the launch by id into set *set of state.sort: slots that are not stored, or whose x is not finite,
+// carry kStateDead and come last.
+static int state_rank(sc_ctx* c, int64_t m, int* set) {
+  if (const int rc = c->state.sort.ensure(m, c->stream)) return rc;
+  return radix_sort(c, c->state.sort, StateKey{c->counters, c->x, c->id[0], (int)c->cap}, m, kStatePasses, set);
+}
+
+int sc_export_state_device(sc_ctx* c, double* dev_xy, double* dev_vxy, double* dev_pressure, int64_t* dev_ids, int64_t room,
+                           int64_t* dev_n) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_n) return fail(SC_ERR_ARG, "null count pointer");
+  if (room < 0) return fail(SC_ERR_ARG, "negative room");
+  if (((uintptr_t)dev_xy | (uintptr_t)dev_vxy) & 15) return fail(SC_ERR_ARG, "xy and vxy must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_export_state_device inside a tick");
+  const int64_t m = slot_bound(c);
+  if (room < m)
+    return fail(SC_ERR_CAPACITY, "device arrays hold %lld, up to %lld particles stored", (long long)room, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  int set;
+  if (const int rc = state_rank(c, m, &set)) return rc;
+  const StateOut o{dev_xy, dev_vxy, dev_pressure, (long long*)dev_ids, (long long*)dev_n};
+  hipLaunchKernelGGL(k_state_gather, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->counters, o,
+                     c->state.sort.keys[set].get(), c->state.sort.vals[set].get(), (int)m, (int)c->cap,
+                     c->normals_valid ? 1 : 0, c->x.get(), c->y.get(), c->vx.get(), c->vy.get(), c->P.get());
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int sc_import_state_device(sc_ctx* c, const double* dev_xy, const double* dev_vxy, const int64_t* dev_ids, int64_t n) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  int rc = put_check(c, dev_xy, dev_vxy, n, true);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  int* ids32 = nullptr;
+  int64_t max_id = -1;
+  if (dev_ids && n > 0) {
+    HIPCHK(c->state.words.grow(2, c->stream));
+    HIPCHK(c->state.ids.grow(n, c->stream));
+    HIPCHK(hipMemsetAsync(c->state.words, 0, 2 * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_state_check_ids, dim3(grid_for(n)), dim3(kBlock), 0, c->stream, (const long long*)dev_ids, (int)n,
+                       c->state.ids.get(), c->state.words.get());
+    HIPCHK(hipGetLastError());
+    int words[2] = {0, 0};
+    if ((rc = read_back(c, words, c->state.words, sizeof words))) return rc;
+    if (words[1]) return fail(SC_ERR_ARG, "particle id out of range");
+    ids32 = c->state.ids;
+    max_id = (int64_t)words[0] - 1;
+  }
+  return put_from_device(c, dev_xy, dev_vxy, ids32, max_id, n, true);
+}
+
+// ---- pair lists (sc_pairs.h) --------------------------------------------------------------------
+
+constexpr int64_t kPairsMaxPoints = (int64_t)1 << 28;
+
+static unsigned pairs_buckets(int64_t m) {
+  unsigned t = kPairsMinBuckets;
+  while ((int64_t)t < kPairsLoad * m) t <<= 1;
+  return t;
+}
+
+
+int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double radius, int32_t flags, int64_t* dev_offsets,
+                          int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_offsets || !dev_counts) return fail(SC_ERR_ARG, "null offsets or counts pointer");
+  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
+  if (flags & ~SC_PAIRS_HALF) return fail(SC_ERR_ARG, "unknown flags %d", flags);
+  const double r2 = radius * radius;
+  if (!(radius > 0) || !std::isfinite(radius) || !std::isfinite(r2) || r2 < std::numeric_limits<double>::min())
+    return fail(SC_ERR_ARG, "the radius must be finite and positive, and so must its square (about 1.5e-154 .. 1.3e154)");
+  if (dev_xy && n < 0) return fail(SC_ERR_ARG, "negative point count");
+  if ((uintptr_t)dev_xy & 15) return fail(SC_ERR_ARG, "the points must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_count_device inside a tick");
+  if (!dev_xy && c->slab)
+    return fail(SC_ERR_STATE, "the pairs of the state are not available in slab mode: partners across a cut live on another rank");
+  const int64_t m = dev_xy ? n : slot_bound(c);
+  if (m > kPairsMaxPoints) return fail(SC_ERR_CAPACITY, "%lld points, at most %lld", (long long)m, (long long)kPairsMaxPoints);
+  if (room_rows < m)
+    return fail(SC_ERR_CAPACITY, "offsets hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  c->pairs.valid = false;
+  const unsigned buckets = pairs_buckets(m);
+  int rc = c->pairs.ensure(m, buckets, c->stream);
+  if (rc) return rc;
+  PairsGrid g{};
+  g.radius = radius;
+  g.h = radius * kPairsCellFactor;
+  g.r2 = r2;
+  g.mask = buckets - 1;
+  g.half = (flags & SC_PAIRS_HALF) ? 1 : 0;
+  const int grid = grid_for(m);
+  if (!dev_xy) {
+    int set;
+    if ((rc = state_rank(c, m, &set))) return rc;
+    hipLaunchKernelGGL(k_pairs_gather, dim3(grid), dim3(kBlock), 0, c->stream, c->state.sort.keys[set].get(),
+                       c->state.sort.vals[set].get(), (int)m, c->x.get(), c->y.get(), c->pairs.xy.get(), c->pairs.words.get());
+  }
+  HIPCHK(hipMemsetAsync(c->pairs.flag, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(c->pairs.bucketCount, 0, (size_t)buckets * sizeof(int), c->stream));
+  RadixSpace& w = c->pairs.sort;
+  hipLaunchKernelGGL(k_pairs_key, dim3(grid), dim3(kBlock), 0, c->stream, g, dev_xy ? (const XY*)dev_xy : c->pairs.xy.get(),
+                     c->pairs.xy.get(), dev_xy ? (long long)n : -1LL, c->pairs.words.get(), (int)m, w.keys[0].get(),
+                     w.vals[0].get(), c->pairs.bucketCount.get(), c->pairs.flag.get());
+  // the binning sort: the keys are 0 .. buckets (a dead point's), so as many digits as `buckets` has
+  int bits = 1;
+  while ((buckets >> bits) != 0) ++bits;
+  int in;
+  if ((rc = radix_sort(c, w, RadixStored{}, m, (bits + kRadixDigitBits - 1) / kRadixDigitBits, &in))) return rc;
+  if ((rc = launch_scan(c, c->pairs.bucketCount, c->pairs.bucketStart, buckets, c->pairs.bucketSums, nullptr))) return rc;
+  hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, w.keys[in].get(), w.vals[in].get(), (int)m,
+                     c->pairs.xy.get(), c->pairs.flag.get(), c->pairs.sxy.get(), c->pairs.cell.get());
+  hipLaunchKernelGGL(k_pairs_count, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), (int)m,
+                     c->pairs.xy.get(), c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(), w.vals[in].get(),
+                     c->pairs.rowLen.get());
+  const int nb = (int)(m / kScanPerBlock + 1);  // entry n <= m lies in one of them
+  hipLaunchKernelGGL(k_scan64_local, dim3(nb), dim3(kBlock), 0, c->stream, c->pairs.rowLen.get(), c->pairs.offs.get(),
+                     c->pairs.words.get(), c->pairs.flag.get(), c->pairs.sums.get());
+  hipLaunchKernelGGL(k_scan64_fix, dim3(nb), dim3(kBlock), 0, c->stream, c->pairs.offs.get(), (long long*)dev_offsets,
+                     c->pairs.words.get(), c->pairs.flag.get(), c->pairs.sums.get(), (long long*)dev_counts);
+  HIPCHK(hipGetLastError());
+  c->pairs.valid = true;
+  c->pairs.m = m;
+  c->pairs.set = in;
+  c->pairs.grid = g;
+  return SC_OK;
+}
+
+int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64_t room_pairs) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (room_pairs < 0) return fail(SC_ERR_ARG, "negative room");
+  if (!dev_partners && room_pairs > 0) return fail(SC_ERR_ARG, "null partners pointer");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_fill_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to fill from: sc_pairs_count_device comes first, and the state must not change in between");
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t m = c->pairs.m;
+  if (room_pairs == 0) return SC_OK;
+  hipLaunchKernelGGL(k_pairs_fill, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->pairs.grid, c->pairs.words.get(),
+                     c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.offs.get(), c->pairs.bucketStart.get(),
+                     c->pairs.sxy.get(), c->pairs.cell.get(), c->pairs.sort.vals[c->pairs.set].get(), (long long*)dev_partners, dev_d2,
+                     (long long)room_pairs);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- clusters (sc_clusters.h) --------------------------------------------------------------------
+
+int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
+                          int64_t room_clusters, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_labels || !dev_counts) return fail(SC_ERR_ARG, "null labels or counts pointer");
+  if (room_rows < 0 || room_clusters < 0) return fail(SC_ERR_ARG, "negative room");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_label_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to label from: sc_pairs_count_device comes first, and the state must not change in between");
+  const int64_t m = c->pairs.m;
+  if (room_rows < m)
+    return fail(SC_ERR_CAPACITY, "labels hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = c->clusters.ensure(m, c->stream);
+  if (rc) return rc;
+  PairsGrid g = c->pairs.grid;
+  g.half = 0;  // the components are those of the full graph, whichever form the count had
+  const int grid = grid_for(m);
+  const long long* words = c->pairs.words.get();
+  const int* flag = c->pairs.flag.get();
+  int* parent = c->clusters.parent.get();
+  hipLaunchKernelGGL(k_cluster_init, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
+  hipLaunchKernelGGL(k_cluster_union, dim3(grid), dim3(kBlock), 0, c->stream, g, words, flag, (int)m, c->pairs.xy.get(),
+                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), parent);
+  // a tree of at most m nodes is at most m - 1 deep, and a round halves (rounding up) every depth
+  int rounds = 1;
+  while (((int64_t)1 << rounds) < m) ++rounds;
+  for (int r = 0; r < rounds; ++r)
+    hipLaunchKernelGGL(k_cluster_jump, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
+  hipLaunchKernelGGL(k_cluster_mark, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->pairs.xy.get(), parent,
+                     c->clusters.isRoot.get(), c->clusters.size.get());
+  if ((rc = launch_scan(c, c->clusters.isRoot, c->clusters.dense, m, c->clusters.sums, nullptr))) return rc;
+  hipLaunchKernelGGL(k_cluster_write, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->pairs.xy.get(), parent,
+                     c->clusters.dense.get(), c->clusters.size.get(), (long long*)dev_labels, (long long*)dev_roots,
+                     (long long)room_clusters);
+  hipLaunchKernelGGL(k_cluster_finish, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->clusters.dense.get(),
+                     c->clusters.size.get(), (long long*)dev_sizes, (long long)room_clusters, (long long*)dev_counts);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// A stable LSD radix sort of (32-bit key, 32-bit value) pairs, hand-written.  Included once by sandcrate_hip.hip, whose
+// A stable LSD radix sort of (32-bit key, 32-bit value) pairs, hand-written.  Included once by sandcrate_hip.hip; sc_host.h's
 // radix_sort runs the passes over a RadixSpace.
 //
 // A pass orders by kRadixDigitBits bits of the key, from the lowest digit up, and moves the pairs from one set of arrays

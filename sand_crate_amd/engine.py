@@ -34,6 +34,24 @@ assert struct.calcsize(_BODY_FMT) == _BODY_SIZE and struct.calcsize(_PARAMS_FMT)
 assert N.TickInputs.params.offset == 0
 
 
+def _pack_bodies(bodies):
+    """-> (the sc_body array of `bodies`, an iterable of (position, center_velocity, omega, n_segments); how many)."""
+    bodies = list(bodies)
+    arr = (N.Body * max(len(bodies), 1))()
+    # (packed straight into the C structs: this runs every tick, and a ctypes constructor per body and field costs
+    # the host more than the GPU spends on a small scene's kernel)
+    for k, (pos, vel, omega, nseg) in enumerate(bodies):
+        struct.pack_into(_BODY_FMT, arr, _BODY_SIZE * k, pos[0], pos[1], vel[0], vel[1], omega, nseg, 0)
+    return arr, len(bodies)
+
+
+def _pack_params(coef, gravity, into=None) -> N.Params:
+    """sc_params of the nine coefficients `coef` maps by name and the gravity, at the start of `into` or in a new one."""
+    p = N.Params() if into is None else into
+    struct.pack_into(_PARAMS_FMT, p, 0, *[coef[k] for k in _COEF_ORDER], gravity[0], gravity[1])
+    return p
+
+
 class PackedInputs:
     """sc_tick_inputs plus the NumPy buffers it points into (kept alive with it)."""
 
@@ -44,19 +62,13 @@ class PackedInputs:
         pad = N.f64(padded).reshape(-1, 2, 2)
         if len(pad) != 2 * len(seg):
             raise ValueError("padded must hold two segments per wall segment")
-        bodies = list(bodies)
-        arr = (N.Body * max(len(bodies), 1))()
-        # (packed straight into the C structs: this runs every tick, and a ctypes constructor per body and field costs
-        # the host more than the GPU spends on a small scene's kernel)
-        for k, (pos, vel, omega, nseg) in enumerate(bodies):
-            struct.pack_into(_BODY_FMT, arr, _BODY_SIZE * k, pos[0], pos[1], vel[0], vel[1], omega, nseg, 0)
         t = N.TickInputs()
-        struct.pack_into(_PARAMS_FMT, t, 0, *[coef[k] for k in _COEF_ORDER], gravity[0], gravity[1])
+        _pack_params(coef, gravity, t)  # (params is the struct's first member)
         t.segments = N.dptr(seg)
         t.padded = N.dptr(pad)
+        arr, t.n_bodies = _pack_bodies(bodies)
         t.bodies = arr
         t.n_segments = len(seg)
-        t.n_bodies = len(bodies)
         self.struct, self.ref, self._seg, self._pad, self._bodies = t, C.byref(t), seg, pad, arr
 
 
@@ -267,19 +279,23 @@ class Engine:
         N.check(self._lib.sc_render_device(self._ctx, C.byref(view), N.dptr(seg), len(seg), N._P(out.data_ptr())))
         return out
 
-    def _jpeg(self, call, width: int, height: int) -> bytes:
-        """Runs call(out, capacity, n_out) -- a JPEG or a GIF encoder -- into a host buffer kept between calls, growing it
-        when the file is larger."""
-        buf = getattr(self, "_jpeg_buf", None)
-        if buf is None or len(buf) < 3 * width * height + 4096:  # (a frame's raw size: enough for all but noise)
-            buf = self._jpeg_buf = np.empty(3 * width * height + 4096, dtype=np.uint8)
+    def _fetch_bytes(self, call, guess: int) -> bytes:
+        """Runs call(out, room, n_out) -- an encoder, or a reader of tracked frames -- into a host buffer kept between
+        calls, of at least `guess` bytes, and once more into a larger one when the library asks for more than it holds."""
+        buf = getattr(self, "_fetch_buf", None)
+        if buf is None or len(buf) < guess:
+            buf = self._fetch_buf = np.empty(max(int(guess), 1), dtype=np.uint8)
         n = C.c_int64(0)
         rc = call(N._P(buf.ctypes.data), len(buf), C.byref(n))
-        if rc == N.ERR_CAPACITY:
-            buf = self._jpeg_buf = np.empty(n.value, dtype=np.uint8)
+        if rc == N.ERR_CAPACITY and n.value > len(buf):
+            buf = self._fetch_buf = np.empty(n.value, dtype=np.uint8)
             rc = call(N._P(buf.ctypes.data), len(buf), C.byref(n))
         N.check(rc)
         return buf[:n.value].tobytes()
+
+    @staticmethod
+    def _frame_guess(width: int, height: int) -> int:
+        return 3 * width * height + 4096  # (a frame's raw size: enough for all but noise)
 
     def encode_jpeg(self, rgb, quality: int = 95) -> bytes:
         """The JPEG file (sc_jpeg_encode_device) of an H x W x 3 uint8 RGB image: a contiguous CUDA tensor, which must
@@ -294,16 +310,16 @@ class Engine:
         torch.cuda.current_stream(rgb.device).synchronize()  # (the library's stream does not wait for torch's)
         h, w = int(rgb.shape[0]), int(rgb.shape[1])
         ptr = N._P(rgb.data_ptr())
-        return self._jpeg(lambda out, cap, n: self._lib.sc_jpeg_encode_device(self._ctx, ptr, w, h, int(quality), out, cap, n),
-                          w, h)
+        return self._fetch_bytes(lambda out, cap, n: self._lib.sc_jpeg_encode_device(self._ctx, ptr, w, h, int(quality), out,
+                                                                                     cap, n), self._frame_guess(w, h))
 
     def render_jpeg(self, view: N.View, segments, quality: int = 95) -> bytes:
         """The frame `render` draws, encoded as `encode_jpeg` does, without leaving the GPU before it is compressed
         (sc_render_jpeg).  Synchronises."""
         seg = N.f64(segments).reshape(-1, 2, 2)
-        return self._jpeg(lambda out, cap, n: self._lib.sc_render_jpeg(self._ctx, C.byref(view), N.dptr(seg), len(seg),
-                                                                       int(quality), out, cap, n),
-                          int(view.width), int(view.height))
+        return self._fetch_bytes(lambda out, cap, n: self._lib.sc_render_jpeg(self._ctx, C.byref(view), N.dptr(seg), len(seg),
+                                                                              int(quality), out, cap, n),
+                                 self._frame_guess(int(view.width), int(view.height)))
 
     def encode_gif(self, index) -> bytes:
         """The image data of one GIF frame (sc_gif_encode_device; `gif.GifWriter.write` takes it) of an H x W uint8 image
@@ -319,16 +335,17 @@ class Engine:
         torch.cuda.current_stream(index.device).synchronize()  # (the library's stream does not wait for torch's)
         h, w = int(index.shape[0]), int(index.shape[1])
         ptr = N._P(index.data_ptr())
-        return self._jpeg(lambda out, cap, n: self._lib.sc_gif_encode_device(self._ctx, ptr, w, h, out, cap, n), w, h)
+        return self._fetch_bytes(lambda out, cap, n: self._lib.sc_gif_encode_device(self._ctx, ptr, w, h, out, cap, n),
+                                 self._frame_guess(w, h))
 
     def render_gif(self, view: N.View, segments) -> bytes:
         """The frame `render` draws as palette indices (background 0, a wall 255, a disc of colour byte c max(c, 1): the
         one loss is that (0, 0, 255) becomes (1, 1, 255); while arrows are set an arrow is 1 and a disc max(c, 2)), encoded as `encode_gif` does without leaving the GPU before it
         is compressed (sc_render_gif).  Synchronises."""
         seg = N.f64(segments).reshape(-1, 2, 2)
-        return self._jpeg(lambda out, cap, n: self._lib.sc_render_gif(self._ctx, C.byref(view), N.dptr(seg), len(seg),
-                                                                      out, cap, n),
-                          int(view.width), int(view.height))
+        return self._fetch_bytes(lambda out, cap, n: self._lib.sc_render_gif(self._ctx, C.byref(view), N.dptr(seg), len(seg),
+                                                                             out, cap, n),
+                                 self._frame_guess(int(view.width), int(view.height)))
 
     def set_hud(self, text: bytes | None, x: int = 6, y: int = 6, scale: int = 1) -> None:
         """From now on every frame of `render`, `render_jpeg` and `render_gif` carries `text` in white over the discs and
@@ -352,10 +369,8 @@ class Engine:
     # -- per-tick inputs
     def set_params(self, *, dt, particle_radius, wall_collision_decay, pressure_amplifier, ignored_pressure,
                    collider_noise_level, viscosity, surface_smoothing, target_pressure, gravity) -> None:
-        g = np.asarray(gravity, dtype=np.float64).reshape(2)
-        p = N.Params(float(dt), float(particle_radius), float(wall_collision_decay), float(pressure_amplifier),
-                     float(ignored_pressure), float(collider_noise_level), float(viscosity), float(surface_smoothing),
-                     float(target_pressure), float(g[0]), float(g[1]))
+        named = locals()  # (the nine coefficients by name, as _pack_params takes them)
+        p = _pack_params(named, np.asarray(gravity, dtype=np.float64).reshape(2))
         N.check(self._lib.sc_set_params(self._ctx, C.byref(p)))
 
     def set_segments(self, segments, padded, bodies) -> None:
@@ -364,28 +379,15 @@ class Engine:
         pad = N.f64(padded).reshape(-1, 2, 2)
         if len(pad) != 2 * len(seg):
             raise ValueError("padded must hold two segments per wall segment")
-        bodies = list(bodies)
-        arr = (N.Body * max(len(bodies), 1))()
-        for k, (pos, vel, omega, nseg) in enumerate(bodies):
-            pos = np.asarray(pos, dtype=np.float64).reshape(2)
-            vel = np.asarray(vel, dtype=np.float64).reshape(2)
-            arr[k] = N.Body(pos[0], pos[1], vel[0], vel[1], float(omega), int(nseg), 0)
-        N.check(self._lib.sc_set_segments(self._ctx, N.dptr(seg), N.dptr(pad), len(seg), arr, len(bodies)))
+        arr, n_bodies = _pack_bodies(bodies)
+        N.check(self._lib.sc_set_segments(self._ctx, N.dptr(seg), N.dptr(pad), len(seg), arr, n_bodies))
 
     def set_next_inputs(self, *, gravity, segments, bodies, **coef) -> None:
         """Promise the inputs of the next tick (between step_begin and step_finish); see the header."""
-        g = np.asarray(gravity, dtype=np.float64).reshape(2)
-        p = N.Params(*(float(coef[k]) for k in ("dt", "particle_radius", "wall_collision_decay", "pressure_amplifier",
-                                               "ignored_pressure", "collider_noise_level", "viscosity",
-                                               "surface_smoothing", "target_pressure")), float(g[0]), float(g[1]))
+        p = _pack_params(coef, np.asarray(gravity, dtype=np.float64).reshape(2))
         seg = N.f64(segments).reshape(-1, 2, 2)
-        bodies = list(bodies)
-        arr = (N.Body * max(len(bodies), 1))()
-        for k, (pos, vel, omega, nseg) in enumerate(bodies):
-            pos = np.asarray(pos, dtype=np.float64).reshape(2)
-            vel = np.asarray(vel, dtype=np.float64).reshape(2)
-            arr[k] = N.Body(pos[0], pos[1], vel[0], vel[1], float(omega), int(nseg), 0)
-        N.check(self._lib.sc_set_next_inputs(self._ctx, C.byref(p), N.dptr(seg), len(seg), arr, len(bodies)))
+        arr, n_bodies = _pack_bodies(bodies)
+        N.check(self._lib.sc_set_next_inputs(self._ctx, C.byref(p), N.dptr(seg), len(seg), arr, n_bodies))
 
     def pack_inputs(self, coef, gravity, segments, padded, bodies) -> "PackedInputs":
         """The inputs of one tick as one C struct (sc_tick_inputs): `coef` maps the nine per-tick coefficient
@@ -587,23 +589,10 @@ class Engine:
         N.check(N.load().sc_track_bound(int(n), int(n_segments), C.byref(b)))
         return b.value
 
-    def _track_fetch(self, call, room: int) -> tuple:
-        buf = getattr(self, "_track_buf", None)
-        if buf is None or len(buf) < room:
-            buf = self._track_buf = np.empty(max(int(room), 1), dtype=np.uint8)
-        rc = call(N._P(buf.ctypes.data), len(buf))
-        return rc, buf
-
     def track_capture(self) -> bytes:
         """The state as it stands as one packed frame, with the walls of the last set_segments / tick
         (sc_track_capture); synchronises."""
-        n = C.c_int64(0)
-        rc, buf = self._track_fetch(lambda out, room: self._lib.sc_track_capture(self._ctx, out, room, C.byref(n)), 1 << 16)
-        if rc == N.ERR_CAPACITY and n.value > len(buf):
-            rc, buf = self._track_fetch(lambda out, room: self._lib.sc_track_capture(self._ctx, out, room, C.byref(n)),
-                                        n.value)
-        N.check(rc)
-        return buf[:n.value].tobytes()
+        return self._fetch_bytes(lambda out, room, n: self._lib.sc_track_capture(self._ctx, out, room, n), 1 << 16)
 
     def track_enable(self, every: int = 1, capacity_bytes: int = 1 << 26) -> None:
         """From now on every tick whose number is a multiple of `every` appends a frame to a log of `capacity_bytes` in
@@ -619,14 +608,10 @@ class Engine:
     def track_read(self):
         """-> (bytes: the frames logged since the last read, oldest first, back to back; how many; dropped frames)
         (sc_track_read); synchronises and rewinds the log."""
-        n, frames, dropped = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        call = lambda out, room: self._lib.sc_track_read(self._ctx, out, room, C.byref(n), C.byref(frames),  # noqa: E731
-                                                         C.byref(dropped))
-        rc, buf = self._track_fetch(call, 1 << 16)
-        if rc == N.ERR_CAPACITY and n.value > len(buf):
-            rc, buf = self._track_fetch(call, n.value)
-        N.check(rc)
-        return buf[:n.value].tobytes(), frames.value, dropped.value
+        frames, dropped = C.c_int64(0), C.c_int64(0)
+        data = self._fetch_bytes(lambda out, room, n: self._lib.sc_track_read(self._ctx, out, room, n, C.byref(frames),
+                                                                              C.byref(dropped)), 1 << 16)
+        return data, frames.value, dropped.value
 
     def track_load(self, frame: bytes, plain: bool = False) -> None:
         """The frame becomes the context's state: dequantised positions, zero velocities, its ids, the pressure its

@@ -1,6 +1,6 @@
 """Frames that sit on the edges of the raster rule (tests/test_render_cases_cpu.py, tests/test_gpu_render_cases.py).
 
-The renderer (csrc/sc_render.h; render_prepare / render_launch in sandcrate_hip.hip) decides a pixel by a handful of
+The renderer (csrc/sc_render.h; render_prepare / render_launch in csrc/sc_host_frames.h) decides a pixel by a handful of
 comparisons, each of which a scene reaches only by luck:
   kRenderWaveRadius = 4   a thread per disc up to R = 4, a wave per disc beyond (`radii`: R = 0 .. 6, and R = 4 | 5 at one
                           particle_radius through the zoom);

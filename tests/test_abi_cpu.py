@@ -47,6 +47,32 @@ def test_abi_version_and_error_string(lib):
     assert isinstance(lib.sc_last_error(), bytes)
 
 
+def first_parameter(name):
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    found = re.search(r"\b" + name + r"\s*\(([^),]*)", text)
+    assert found, f"{name} is not declared in the header"
+    return " ".join(found.group(1).split())
+
+
+def test_every_call_on_a_context_refuses_a_null_one_before_anything_else(lib):
+    """Every export whose first parameter is the context -- sc_destroy apart, which takes a null one -- called with a null
+    context and zeros or nulls for the rest: SC_ERR_ARG and a message, before any dereference and any HIP call (there is
+    no GPU here).  The guards are per function and their code lives in several files: one moved behind a use of the
+    context would crash this test."""
+    from sand_crate_amd import _native as N
+    lib.sc_last_error.restype = ctypes.c_char_p
+    swept = []
+    for name, (restype, argtypes) in sorted(N.SIGNATURES.items()):
+        if name == "sc_destroy" or not re.fullmatch(r"sc_ctx\s*\*\s*\w*", first_parameter(name)):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+        assert fn(*[kind() for kind in argtypes]) == N.ERR_ARG, name
+        assert lib.sc_last_error(), name
+        swept.append(name)
+    assert len(swept) >= 60 and "sc_step_finish" in swept and "sc_render_gif" in swept and "sc_checkpoint_begin" in swept
+
+
 def test_struct_layouts_match_header():
     from sand_crate_amd import _native as N
     assert ctypes.sizeof(N.Params) == 11 * 8
