@@ -195,6 +195,9 @@ int sc_download_neighbors(sc_ctx* ctx, int64_t* ids, int32_t* counts, int64_t* n
                           int64_t n_capacity, int64_t* n_out);
 /* After sc_step_finish: surface normals s_i of apply_tension pass 1 (crate.py:337-342) in id order. */
 int sc_download_normals(sc_ctx* ctx, double* sxy, int64_t n_capacity, int64_t* n_out);
+/* After sc_step_finish: the pressures of apply_pressure pass 1 (crate.py:261-275) in id order, one per particle of the
+ * finished tick -- those whose position the tick left NaN included, which sc_download_state no longer lists. */
+int sc_download_pressure(sc_ctx* ctx, double* pressure, int64_t n_capacity, int64_t* n_out);
 
 /* Stand-alone forms of two reference functions (its tests/test_distance.py pins both).
  * sc_neighbor_search = detect_particle_collisions (collision_detector.py:9-49) on arbitrary

@@ -184,7 +184,8 @@ def tick_core(particles, velocities, segments, bodies, coef, eta_u01=None, neigh
                             particle-major/slot-minor order -- what the reference draws per particle at
                             crate.py:169 -- or already padded (P, 20, 2), or a callable total -> (total, 2)
                             invoked once the neighbor counts are known
-    Returns a dict: particles, velocities, pressure and the intermediates tests compare.
+    Returns a dict: particles, velocities, pressure and the intermediates tests compare (pair_distance: |r| of every
+    listed pair after the noise, inf in the unused slots; overlap: its w = 1 - clip(|r| / d, 0, 1)).
     """
     p0 = np.asarray(particles, dtype=np.float64)
     v0 = np.asarray(velocities, dtype=np.float64)
@@ -277,6 +278,7 @@ def tick_core(particles, velocities, segments, bodies, coef, eta_u01=None, neigh
         "particles": p_new, "velocities": v, "pressure": pressure,
         "fixed_positions": p, "wall_count": V, "wall_u": u, "wall_vel": wall_vel,
         "neighbor_counts": counts, "neighbor_table": table,
+        "pair_distance": np.where(valid, dist, np.inf), "overlap": w,
         "surface_normals": s, "v_after_tension": v_after_tension, "v_after_pressure": v_after_pressure,
         "v_after_viscosity": v_after_viscosity, "v_after_bounce": v_after_bounce, "ccd_factor": fac,
     }

@@ -119,6 +119,7 @@ SIGNATURES = {
     "sc_download_sort": (C.c_int, [_P, _I64, _I64, C.c_int64, _I64]),
     "sc_download_neighbors": (C.c_int, [_P, _I64, _I32, _I64, _D, C.c_int64, _I64]),
     "sc_download_normals": (C.c_int, [_P, _D, C.c_int64, _I64]),
+    "sc_download_pressure": (C.c_int, [_P, _D, C.c_int64, _I64]),
     "sc_neighbor_search": (C.c_int, [C.c_int, _D, C.c_int64, C.c_double, _I64, _I64, _I32, _I64]),
     "sc_points_to_segments": (C.c_int, [C.c_int, _D, C.c_int64, _D, C.c_int32, _D, _D]),
     "sc_pad_segments": (C.c_int, [_D, C.c_int32, C.c_double, _D]),

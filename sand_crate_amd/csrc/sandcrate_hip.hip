@@ -1028,6 +1028,25 @@ int sc_download_normals(sc_ctx* c, double* sxy, int64_t room, int64_t* n_out) {
   return SC_OK;
 }
 
+int sc_download_pressure(sc_ctx* c, double* pressure, int64_t room, int64_t* n_out) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (c->in_step || !c->normals_valid) return fail(SC_ERR_STATE, "sc_download_pressure needs a finished tick");
+  int h[C_COUNT];
+  int rc = read_counters(c, h);
+  if (rc) return rc;
+  int64_t n = h[C_NT];
+  if (n_out) *n_out = n;
+  if (n > room) return fail(SC_ERR_CAPACITY, "host arrays too small");
+  std::vector<double> hp(n);
+  std::vector<int> id(n);
+  if ((rc = fetch(c, hp.data(), c->P, n * sizeof(double))) || (rc = fetch(c, id.data(), c->id[1], n * sizeof(int))))
+    return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const std::vector<int> order = index_order(id.data(), nullptr, n);
+  for (size_t k = 0; k < order.size() && pressure; ++k) pressure[k] = hp[order[k]];
+  return SC_OK;
+}
+
 // ---- stand-alone reference functions ----------------------------------------------------------
 
 int sc_neighbor_search(int device, const double* xy, int64_t n, double diameter, int64_t* y_floored,

@@ -457,6 +457,14 @@ class Engine:
         N.check(self._lib.sc_download_normals(self._ctx, N.dptr(s), room, C.byref(n)))
         return s[:n.value].copy()
 
+    def download_pressure(self):
+        """-> the finished tick's pressures in id order, one per particle it had -- the rows it left NaN included."""
+        room = self.capacity
+        pr = np.empty(room)
+        n = C.c_int64(0)
+        N.check(self._lib.sc_download_pressure(self._ctx, N.dptr(pr), room, C.byref(n)))
+        return pr[:n.value].copy()
+
     # -- multi-GPU slabs (device pointers are plain integers, e.g. torch_tensor.data_ptr())
     def set_slab(self, col_lo: int, col_hi: int, halo: int, has_left: bool, has_right: bool) -> None:
         N.check(self._lib.sc_set_slab(self._ctx, int(col_lo), int(col_hi), int(halo), int(has_left), int(has_right)))
