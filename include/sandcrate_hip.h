@@ -677,6 +677,49 @@ int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* m
 int sc_pairs_label_device(sc_ctx* ctx, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes /* may be NULL */,
                           int64_t* dev_roots /* may be NULL */, int64_t room_clusters, int64_t* dev_counts /* [2]: n, C */);
 
+/* Nearest-k neighbour tables of that graph in DEVICE memory of the caller: a table of fixed shape, rows x k, for code that
+ * wants neighbors[i, 0 .. k) rather than a CSR list of data-dependent length.  tests/nearest_spec.py is the rule: j is a
+ * partner of row r iff fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius), dx = fl(x_r - x_j) -- the arithmetic of the pair list
+ * -- and, in the self form only, j != r; row r of the table holds its partners in ascending order of the key (d2, j) -- d2
+ * the float64 that was compared, bit-equal d2 ordered by the smaller j --, the first min(k, partners) of them; the places
+ * behind hold -1, and +inf in dev_d2.  A point with a coordinate that is not finite is nobody's partner, a row whose own
+ * point or query is not finite is empty.  The result is a pure function of the points and the queries.
+ *
+ * sc_pairs_nearest_device  searches the grid of the last sc_pairs_count_device of this context, in either form and with any
+ *     flags (SC_PAIRS_HALF is ignored: the table is cut from the full list): it reads the workspace that count left, never
+ *     the count's caller's points, and leaves it as it is -- sc_pairs_fill_device, sc_pairs_label_device and further tables
+ *     may follow.  The rows: with dev_queries NULL the count's n points themselves (the self form; n is known on the
+ *     device only for the state form), else the n_queries rows of dev_queries (n_queries x 2 interleaved float64, aligned
+ *     to 16 bytes), which need not be points: a query that coincides with a point has it as a partner at d2 = 0.  Writes,
+ *     for every row below the row count, all k places of dev_neighbors (int64, rows x k contiguous) and -- unless NULL --
+ *     of dev_d2 (float64, the same shape) and dev_partners[row] (int64), the number of partners without the cap: in the
+ *     self form the row length of the full pair list.  Rows from the row count on are left as they were.  `room_rows`,
+ *     the room of the three arrays in rows, must be at least the bound the count was sized by (self form) or n_queries.
+ *     dev_counts[0] = the row count, dev_counts[1] = the number of rows with more partners than k: 0 means that the table
+ *     is the whole pair list.  The domain of the queries is that of the points, fl(|c| / radius) < 2^31 for every finite
+ *     coordinate; after a count that found a point outside it, or with a query outside it, dev_counts[1] = -1 is written
+ *     and nothing else.  A query outside raises a flag of this call's own: the count's verdict, which the fill and the
+ *     label read, stays as the count left it.
+ * It enqueues on the context's stream only, with the rules of the calls above: nothing synchronises, nothing reaches the
+ * host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches are
+ * not bracketed by the timing events.
+ *     The algorithm: a thread per row walks the buckets of its nine cells as the count does and keeps its k best so far as
+ * a sorted list in LDS, slot-major, inserting by (d2, j) -- candidates arrive in bucket order, which is not the key's --,
+ * with the key of the last place in registers, so that a full list rejects most candidates with one compare.  A
+ * workgroup is one wave of 64 rows with LDS for 16, 32 or 64 places per row, whichever holds k (12, 24, 49 KiB).  It writes
+ * its block of rows together, consecutive lanes to consecutive entries (csrc/sc_nearest.h).  One integer atomic per cut row: no
+ * atomic's order reaches the output, and no workgroup waits for another.
+ *     SC_ERR_ARG for a null context, null dev_neighbors or dev_counts, k outside 1 .. SC_NEAREST_MAX_K, a negative
+ * n_queries or room, or misaligned queries.  SC_ERR_STATE between sc_step_begin and sc_step_finish, when there is no
+ * count, and when a tick, an upload, an append, an emission, an import or a track load has touched the state since (the
+ * fill's rule).  SC_ERR_CAPACITY when room_rows is too small, or for more than 2^28 queries.  All checked before anything
+ * is launched: the arrays are then untouched. */
+enum { SC_NEAREST_MAX_K = 64 };
+int sc_pairs_nearest_device(sc_ctx* ctx, const double* dev_queries /* NULL: the points themselves */, int64_t n_queries,
+                            int32_t k, int64_t* dev_neighbors /* rows x k */, double* dev_d2 /* rows x k, may be NULL */,
+                            int64_t* dev_partners /* rows, may be NULL */, int64_t room_rows,
+                            int64_t* dev_counts /* [2]: rows, cut */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,12 @@ PAIRS_LOAD, PAIRS_MIN_BUCKETS = 2, 256
 PAIRS_HASH_X, PAIRS_HASH_Y, PAIRS_HASH_MIX = 0x9E3779B1, 0x85EBCA77, 0x2C1B3C6D
 PAIRS_CELL_FACTOR = 1.0 + 2.0 ** -20
 PAIRS_HALF = 1
+# the nearest-k table (csrc/sc_nearest.h): the largest k (SC_NEAREST_MAX_K), the rows per workgroup of its kernel
+# (kNearestBlock: one wave, whatever k -- `nearest_width(k)`), and the places per row its LDS holds: the smallest of
+# NEAREST_SLOTS that is at least k (`nearest_slots(k)`), each a kernel of its own
+NEAREST_MAX_K = 64
+NEAREST_BLOCK = 64
+NEAREST_SLOTS = (16, 32, 64)
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -180,6 +186,7 @@ SIGNATURES = {
     "sc_pairs_count_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32, _P, C.c_int64, _P]),
     "sc_pairs_fill_device": (C.c_int, [_P, _P, _P, C.c_int64]),
     "sc_pairs_label_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "sc_pairs_nearest_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
 }
 
 
@@ -199,6 +206,21 @@ def pairs_bucket(cx: int, cy: int, buckets: int) -> int:
     v = (v * PAIRS_HASH_MIX) & m
     v ^= v >> 13
     return v & (buckets - 1)
+
+
+def nearest_slots(k: int) -> int:
+    """The places per row in the LDS of the nearest-k kernel that serves a table of k places per row (csrc/sc_nearest.h)."""
+    if not 1 <= k <= NEAREST_MAX_K:
+        raise ValueError(f"k must be 1 .. {NEAREST_MAX_K}")
+    return next(slots for slots in NEAREST_SLOTS if k <= slots)
+
+
+def nearest_width(k: int) -> int:
+    """The rows per workgroup of the nearest-k kernel for a table of k places per row: one wave for every k -- wider
+    workgroups for a small k measured slower (profiles/nearest_time.txt)."""
+    nearest_slots(k)
+    return NEAREST_BLOCK
+
 
 _lib = None
 

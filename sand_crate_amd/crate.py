@@ -349,6 +349,62 @@ class Crate:
             self._count, self._count_known = n, True
         return labels[:n], sizes[:total], roots[:total]
 
+    def neighbor_tensors(self, k: int, radius: float | None = None, *, points=None, queries=None,
+                         squared_distances: bool = False, partner_counts: bool = False, sync: bool = True):
+        """The k nearest particles within `radius` (default: `diameter`) of every particle, as a table of fixed shape in
+        torch CUDA tensors on the crate's device, selected on the GPU from the pair search's grid (sc_pairs_count_device,
+        then sc_pairs_nearest_device): ``(neighbors[, d2][, partners])`` -- int64 (n, k), float64 (n, k), int64 (n,).
+        ``neighbors[i]`` holds the partners of row i of `state_tensors()` at the same point of the stream -- the row of
+        `pair_tensors` -- in ascending order of (squared distance, index), the nearest k of them, and -1 in the places
+        behind (tests/nearest_spec.py is the rule; `sand_crate_amd.pairs.neighbor_mask` and `neighbor_edge_index` read the
+        result).  `squared_distances` adds the numbers that were compared, +inf in the padding; `partner_counts` every
+        row's number of partners without the cap, the row length of `pair_tensors`.  `points`, a float64 (n, 2) CUDA
+        tensor, is searched instead of the state.  With `queries`, a float64 (q, 2) CUDA tensor, the rows are those points
+        instead -- probes, sensors, the cursor: they need not be particles, and one that lies on a particle has it as a
+        partner at distance 0 -- and the tensors have q rows.  `k` is 1 .. 64.
+
+        The shape is known before anything runs, so nothing synchronises between counting and selecting.  `sync=True`
+        synchronises once at the end, reads 16 bytes and returns tensors cut to the row count; a coordinate of a particle
+        or a query with |c| / radius >= 2^31 raises ValueError.  `sync=False` synchronises nothing: the tensors come at
+        capacity rows (n with `points`, q with `queries`) and last the int64 `counts` tensor (rows, cut): rows from the
+        row count on are uninitialised, cut is the number of rows that had more than k partners, cut = -1 is the domain
+        error (nothing else was written).  The tensors are written on the library's stream, and the library's stream does
+        not wait for torch's: read them after `synchronize()`, and have `points` and `queries` ready before the call -- or
+        run the crate on torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        import torch
+        k = int(k)
+        if not 1 <= k <= N.NEAREST_MAX_K:
+            raise ValueError(f"k must be 1 .. {N.NEAREST_MAX_K}")
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(self.diameter if radius is None else radius)
+        bound = eng.capacity if points is None else _point_rows(points)
+        rows = bound if queries is None else _point_rows(queries)
+        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the table reads the workspace)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, cut)
+        neighbors = torch.empty((rows, k), dtype=torch.int64, device=dev)
+        d2 = torch.empty((rows, k), dtype=torch.float64, device=dev) if squared_distances else None
+        partners = torch.empty(rows, dtype=torch.int64, device=dev) if partner_counts else None
+        out = tuple(t for t in (neighbors, d2, partners) if t is not None)
+        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        count_counts = counts
+        if queries is not None:  # (the count's n stays readable: with queries the table's row count is q)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+        eng.pairs_nearest(neighbors, d2, partners, k=k, queries=queries, counts=counts)
+        if not sync:
+            self._neighbor_temporaries = (offsets, count_counts)  # (held until the next call: the count is still queued)
+            return (*out, counts)
+        eng.synchronize()
+        n, cut = (int(v) for v in counts.cpu())
+        if cut < 0:
+            raise ValueError(f"neighbor_tensors: a coordinate of a point or a query lies outside the domain "
+                             f"|c| / radius < 2^31 (radius {radius!r})")
+        if points is None:
+            self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
+        return tuple(t[:n] for t in out)
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

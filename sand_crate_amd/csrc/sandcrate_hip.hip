@@ -15,6 +15,7 @@
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_clusters.h"
+#include "sc_nearest.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"

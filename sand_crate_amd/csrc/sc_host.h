@@ -264,6 +264,16 @@ struct ClusterSpace {
   }
 };
 
+// sc_pairs_nearest_device (sc_nearest.h; sc_host_state.h): the flag a query outside the domain raises -- a flag of its own:
+// the count's stays as the count left it, a fill or a label after the table still reads it.
+struct NearestSpace {
+  DevBuf<int> flag;
+  int ensure(hipStream_t stream) {
+    HIPCHK(flag.grow(1, stream));
+    return SC_OK;
+  }
+};
+
 // The checkpoint (sc_checkpoint_begin / _finish; sc_host_snapshot.h): device-side snapshot, pinned host copy, and the
 // events that order them on the context's stream and the side stream.
 struct Snapshot {
@@ -390,6 +400,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   StateIo state;
   PairsSpace pairs;
   ClusterSpace clusters;
+  NearestSpace nearest;
   Snapshot snap;
   SlabLink link;
 };

@@ -1,9 +1,10 @@
-// Host side of the state in the caller's device memory: export and import, pair lists and clusters.
+// Host side of the state in the caller's device memory: export and import, pair lists, clusters and nearest-k tables.
 #pragma once
 #include "sc_host.h"
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_clusters.h"
+#include "sc_nearest.h"
 
 extern "C" {
 
@@ -194,6 +195,56 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
                      (long long)room_clusters);
   hipLaunchKernelGGL(k_cluster_finish, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->clusters.dense.get(),
                      c->clusters.size.get(), (long long*)dev_sizes, (long long)room_clusters, (long long*)dev_counts);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- nearest-k tables (sc_nearest.h) -------------------------------------------------------------
+
+}  // extern "C"
+
+template <int K>
+static void nearest_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int k, const NearestOut& out) {
+  const int64_t grid = std::max<int64_t>(1, (rows + kNearestBlock - 1) / kNearestBlock);  // (one at least: it writes the counts)
+  hipLaunchKernelGGL(k_nearest<K>, dim3((unsigned)grid), dim3(kNearestBlock), 0, c->stream, g, c->pairs.words.get(),
+                     c->pairs.flag.get(), c->nearest.flag.get(), c->pairs.xy.get(), queries, (long long)rows, k,
+                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), out);
+}
+
+extern "C" {
+
+int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, int32_t k, int64_t* dev_neighbors,
+                            double* dev_d2, int64_t* dev_partners, int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_neighbors || !dev_counts) return fail(SC_ERR_ARG, "null neighbors or counts pointer");
+  if (k < 1 || k > SC_NEAREST_MAX_K) return fail(SC_ERR_ARG, "k is %d, it must be 1 .. %d", (int)k, (int)SC_NEAREST_MAX_K);
+  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
+  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
+  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_nearest_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to search in: sc_pairs_count_device comes first, and the state must not change in between");
+  if (dev_queries && n_queries > kPairsMaxPoints)
+    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
+  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
+  if (room_rows < rows)
+    return fail(SC_ERR_CAPACITY, "the table holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
+                dev_queries ? "queries" : "points");
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = c->nearest.ensure(c->stream);
+  if (rc) return rc;
+  static_assert(kNearestMaxK == SC_NEAREST_MAX_K, "the header's bound is the kernel's");
+  PairsGrid g = c->pairs.grid;
+  g.half = 0;  // the table is cut from the full list, whichever form the count had
+  const XY* queries = (const XY*)dev_queries;
+  const NearestOut out{(long long*)dev_neighbors, dev_d2, (long long*)dev_partners, (long long*)dev_counts};
+  HIPCHK(hipMemsetAsync(c->nearest.flag, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_nearest_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
+                     queries, (long long)n_queries, c->pairs.flag.get(), c->nearest.flag.get(), out.counts);
+  if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, g, queries, rows, k, out);
+  else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, g, queries, rows, k, out);
+  else nearest_launch<kNearestMaxK>(c, g, queries, rows, k, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -255,6 +255,36 @@ class Engine:
                                                 N._P(counts.data_ptr())))
         return counts
 
+    def pairs_nearest(self, neighbors, d2=None, partners=None, *, k: int, queries=None, counts, room: int | None = None):
+        """The nearest-k table of the last `pairs_count`, whichever `half` it had (sc_pairs_nearest_device; the rule is
+        tests/nearest_spec.py): `neighbors`, int64 (R, k), receives per row the k nearest partners within the count's
+        radius, ascending in (d2, j) and padded with -1; `d2`, float64 (R, k) or None, their squared distances, padded
+        with +inf; `partners`, int64 (R,) or None, every row's number of partners without the cap.  The rows are the
+        count's points, or with `queries`, a float64 (q, 2) CUDA tensor, those points of any kind: a query is not its own
+        partner's rival, a point it coincides with is a partner at d2 = 0.  `counts`, int64 (2,), receives the row count
+        and the number of rows with more than k partners (-1: a point or a query lies outside the domain, nothing else
+        is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.  Returns
+        `counts`."""
+        k = int(k)
+        if not 1 <= k <= N.NEAREST_MAX_K:
+            raise ValueError(f"k must be 1 .. {N.NEAREST_MAX_K}")
+        rows = _state_tensor(neighbors, "neighbors", "int64", (k,), self.device)
+        if d2 is not None:
+            _state_tensor(d2, "d2", "float64", (k,), self.device, rows)
+        if partners is not None:
+            _state_tensor(partners, "partners", "int64", (), self.device, rows)
+        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the table's {rows} rows")
+        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
+        # for the self form)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_nearest_device(self._ctx, ptr(queries), q, k, ptr(neighbors), ptr(d2), ptr(partners),
+                                                  room, N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

@@ -1,5 +1,5 @@
 """Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
-`Crate.cluster_tensors` (labels, sizes)."""
+`Crate.cluster_tensors` (labels, sizes), and for the nearest-k tables of `Crate.neighbor_tensors` (neighbors)."""
 from __future__ import annotations
 
 
@@ -32,3 +32,16 @@ def largest_cluster(sizes):
         return -1, 0
     c = int(sizes.argmax())
     return c, int(sizes[c])
+
+
+def neighbor_mask(neighbors):
+    """Which places of a nearest-k table (`Crate.neighbor_tensors`) hold a partner: bool (rows, k); the padding is -1."""
+    return neighbors >= 0
+
+
+def neighbor_edge_index(neighbors):
+    """The (2, E) int64 edge list (row 0: the table's row, row 1: the partner) of a nearest-k table's valid places, in
+    (row, place) order -- nearest first within a row.  With `queries` row 0 numbers the queries, not the points."""
+    import torch
+    rows, places = torch.nonzero(neighbor_mask(neighbors), as_tuple=True)  # (row-major: rows ascending, then places)
+    return torch.stack([rows, neighbors[rows, places]])
