@@ -720,6 +720,59 @@ int sc_pairs_nearest_device(sc_ctx* ctx, const double* dev_queries /* NULL: the 
                             int64_t* dev_partners /* rows, may be NULL */, int64_t room_rows,
                             int64_t* dev_counts /* [2]: rows, cut */);
 
+/* Weighted neighbourhood sums over that graph in DEVICE memory of the caller: what is there, not who -- the density at a
+ * particle or a probe, a smoothed velocity, a raster of a field, the "sum over neighbours" of a message-passing layer.
+ * tests/field_spec.py is the rule: j is a partner of row r iff fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius), dx =
+ * fl(x_r - x_j) -- the arithmetic of the pair list -- and, in the self form without SC_FIELDS_SELF only, j != r; with
+ * t = fl(1 - fl(d2 / r2)), r2 = fl(radius radius), the weight w is 1, t, fl(t t) or fl(fl(t t) t) for `power` 0, 1, 2, 3
+ * (3 is the poly6 shape; 0 <= t <= 1 for a partner), and
+ *     dev_wsum[r]    = ((0 + w_j1) + w_j2) + ...
+ *     dev_sums[r, c] = ((0 + fl(w_j1 v[j1, c])) + fl(w_j2 v[j2, c])) + ...
+ * over the partners in ASCENDING j, from +0.0, every product and every sum rounded on its own.  A point with a coordinate
+ * that is not finite is nobody's partner; a row whose own point or query is not finite gets 0 everywhere.  The values are
+ * taken as they are: a NaN or an infinity propagates by IEEE rules, 0 * inf at d2 == r2 is NaN.  The result is a pure
+ * function of the points, the queries and the values: two calls give the same bits.
+ *
+ * sc_pairs_sum_device  sums over the grid of the last sc_pairs_count_device of this context, in either form and with any
+ *     flags (SC_PAIRS_HALF is ignored: the sums run over the full list): it reads the workspace that count left, never the
+ *     count's caller's points, and leaves it as it is -- fills, labels, tables and further sums may follow.  The rows: with
+ *     dev_queries NULL the count's n points themselves (the self form; with SC_FIELDS_SELF point r is its own partner at
+ *     d2 = 0, in its place in index order), else the n_queries rows of dev_queries (n_queries x 2 interleaved float64,
+ *     aligned to 16 bytes; SC_FIELDS_SELF has no meaning and is ignored), which need not be points.  dev_values is
+ *     values_rows x channels contiguous float64, row j the values of point j of the count; channels is 0 ..
+ *     SC_FIELDS_MAX_CHANNELS, with 0 dev_values, values_rows and dev_sums are not looked at and only dev_wsum is written.
+ *     Writes dev_sums (rows x channels contiguous) and -- unless NULL -- dev_wsum for every row below the row count; rows
+ *     from the row count on are left as they were.  `room_rows`, the room of the two arrays in rows, must be at least
+ *     the bound the count was sized by (self form) or n_queries.  dev_counts[0] = the row count, dev_counts[1] = the
+ *     status: 0 when all is well; -1 after a count that found a point outside the domain fl(|c| / radius) < 2^31, or with
+ *     a query outside it; -2 when values_rows is below the count's n, which for the state form is known on the device
+ *     only.  With a status below 0 only dev_counts[1] is written, and no row of dev_values at or beyond values_rows is ever
+ *     read.  The status comes from a flag of this call's own: the count's verdict, which the fill and the label read, stays
+ *     as the count left it.
+ * It enqueues on the context's stream only, with the rules of the calls above: nothing synchronises, nothing reaches the
+ * host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches are
+ * not bracketed by the timing events.
+ *     The algorithm: a check pass over the queries and the values' rows, then a thread per row merges the nine runs of its
+ * nine cells, each ascending in j, by always taking the smallest head -- the merge of sc_pairs_fill_device, cursors in LDS
+ * -- and instead of storing the partner adds to the weight sum and to the channel sums in registers, reading values[j, :]
+ * where it lies.  Four kernels, for 1, 2, 4 and 8 channels; a call with 3 runs the one for 4.  Nothing of the list's size
+ * is written and there is no workspace beyond the flag.  No floating-point atomics, no atomic's order reaches the output,
+ * no workgroup waits for another (csrc/sc_fields.h).  scripts/fields_time.py measures it on an MI355X against the list
+ * route -- sc_pairs_fill_device with distances, then torch's gather, multiply and index_add_ --:
+ * profiles/fields_time.txt has the times.
+ *     SC_ERR_ARG for a null context, null dev_counts, dev_sums and dev_wsum both NULL, channels outside 0 ..
+ * SC_FIELDS_MAX_CHANNELS, channels > 0 with dev_values or dev_sums NULL, power outside 0 .. 3, unknown flags, a negative
+ * n_queries, values_rows or room, or misaligned queries.  SC_ERR_STATE between sc_step_begin and sc_step_finish, when
+ * there is no count, and when a tick, an upload, an append, an emission, an import or a track load has touched the state
+ * since (the fill's rule).  SC_ERR_CAPACITY when room_rows is too small, or for more than 2^28 queries.  All checked
+ * before anything is launched: the arrays are then untouched. */
+enum { SC_FIELDS_MAX_CHANNELS = 8, SC_FIELDS_SELF = 1 };
+int sc_pairs_sum_device(sc_ctx* ctx, const double* dev_queries /* NULL: the points themselves */, int64_t n_queries,
+                        const double* dev_values /* points x channels, may be NULL with channels 0 */, int64_t values_rows,
+                        int32_t channels, int32_t power, int32_t flags, double* dev_sums /* rows x channels */,
+                        double* dev_wsum /* rows, may be NULL */, int64_t room_rows,
+                        int64_t* dev_counts /* [2]: rows, status */);
+
 #ifdef __cplusplus
 }
 #endif

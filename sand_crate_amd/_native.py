@@ -42,6 +42,14 @@ PAIRS_HALF = 1
 NEAREST_MAX_K = 64
 NEAREST_BLOCK = 64
 NEAREST_SLOTS = (16, 32, 64)
+# the weighted sums (csrc/sc_fields.h): the most channels of one call (SC_FIELDS_MAX_CHANNELS), the channels its four
+# kernels are made for -- a call runs the smallest that holds its own, `fields_kernel_channels(c)` --, the flag that makes
+# a point its own partner (SC_FIELDS_SELF), the rows per workgroup (kBlock) and the status values of counts[1]
+FIELDS_MAX_CHANNELS = 8
+FIELDS_KERNEL_CHANNELS = (1, 2, 4, 8)
+FIELDS_SELF = 1
+FIELDS_BLOCK = 256
+FIELDS_OK, FIELDS_DOMAIN, FIELDS_VALUES_SHORT = 0, -1, -2
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -187,6 +195,8 @@ SIGNATURES = {
     "sc_pairs_fill_device": (C.c_int, [_P, _P, _P, C.c_int64]),
     "sc_pairs_label_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "sc_pairs_nearest_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    "sc_pairs_sum_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
+                                      _P]),
 }
 
 
@@ -220,6 +230,13 @@ def nearest_width(k: int) -> int:
     workgroups for a small k measured slower (profiles/nearest_time.txt)."""
     nearest_slots(k)
     return NEAREST_BLOCK
+
+
+def fields_kernel_channels(channels: int) -> int:
+    """The channels of the sum kernel that serves a call with `channels` channels (csrc/sc_fields.h); 0 runs the first."""
+    if not 0 <= channels <= FIELDS_MAX_CHANNELS:
+        raise ValueError(f"channels must be 0 .. {FIELDS_MAX_CHANNELS}")
+    return next(c for c in FIELDS_KERNEL_CHANNELS if channels <= c)
 
 
 _lib = None

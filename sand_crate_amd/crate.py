@@ -405,6 +405,89 @@ class Crate:
             self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
         return tuple(t[:n] for t in out)
 
+    def field_tensors(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
+                      points=None, queries=None, weight_sums: bool = False, sync: bool = True):
+        """What is there within `radius` (default: `diameter`) of every particle: the weighted sums of an SPH
+        interpolation, as torch CUDA tensors on the crate's device, summed on the GPU over the pair search's grid
+        (sc_pairs_count_device, then sc_pairs_sum_device): ``(sums[, wsum])`` -- float64 (n, C) and (n,).
+        ``sums[i] = sum_j w_ij * values[j]`` over the partners j of row i of `state_tensors()` at the same point of the
+        stream -- the row of `pair_tensors`, and with `include_self` particle i itself --, ``wsum[i] = sum_j w_ij``, with
+        ``w = (1 - d2 / radius**2) ** power``, `power` 0 .. 3 (3: the poly6 shape; 0: w = 1, `wsum` counts the partners).
+        The sums are added in ascending j, every operation rounded on its own: a pure function of the state, the same
+        bits on every call (tests/field_spec.py is the rule; `sand_crate_amd.pairs.normalized` divides the two,
+        `grid_queries` makes a raster of probes).  `values` is a float64 (n, C) or (n,) CUDA tensor whose rows are in the
+        order of `state_tensors()` -- or of `points`, a float64 (n, 2) CUDA tensor that is searched instead of the state;
+        it is made contiguous, any C is served, eight columns per launch against the same count, and (n,) gives sums of
+        shape (n,).  With ``values=None`` only ``(wsum,)`` comes back: the density.  With `queries`, a float64 (q, 2) CUDA
+        tensor, the rows are those points instead -- probes, sensors, the cell centres of an image: they need not be
+        particles, a particle one lies on is a partner at distance 0, `include_self` means nothing -- and the tensors
+        have q rows.  A particle or query with a coordinate that is not finite gives and gets nothing.
+
+        The shape is known before anything runs, so nothing synchronises between counting and summing.  `sync=True`
+        synchronises once at the end, reads 16 bytes and returns tensors cut to the row count; ValueError when a
+        coordinate of a particle or a query has |c| / radius >= 2^31, and when `values` has fewer rows than there are
+        particles.  `sync=False` synchronises nothing: the tensors come at capacity rows (n with `points`, q with
+        `queries`) and last the int64 `counts` tensor (rows, status): rows from the row count on are uninitialised, status
+        -1 is the domain error and -2 the short `values` (nothing else was written).  The tensors are written on the
+        library's stream, and the library's stream does not wait for torch's: read them after `synchronize()`, and have
+        `values`, `points` and `queries` ready before the call -- or run the crate on torch's stream, `engine.set_stream`,
+        and everything torch enqueues afterwards sees them.  What the wrapper itself asks of torch -- the contiguous copy,
+        the split into eights of more than 8 columns and their concatenation -- runs on torch's stream: with `sync=False`
+        those need the crate on torch's stream."""
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(self.diameter if radius is None else radius)
+        power = int(power)
+        if not 0 <= power <= 3:
+            raise ValueError("power must be 0 .. 3")
+        flat = False
+        if values is not None:
+            if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
+                raise ValueError("values must be a CUDA float64 tensor of shape (n, C) or (n,)")
+            flat = values.dim() == 1
+            values = (values.unsqueeze(1) if flat else values).contiguous()
+            if values.shape[1] < 1:
+                raise ValueError("values must have at least one column")
+        step = N.FIELDS_MAX_CHANNELS
+        width = 0 if values is None else int(values.shape[1])
+        chunks = [values] if width <= step else [values[:, at:at + step].contiguous() for at in range(0, width, step)]
+        bound = eng.capacity if points is None else _point_rows(points)
+        rows = bound if queries is None else _point_rows(queries)
+        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the sum reads the workspace)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, status)
+        want_wsum = weight_sums or values is None
+        wsum = torch.empty(rows, dtype=torch.float64, device=dev) if want_wsum else None
+        parts = [None if v is None else torch.empty((rows, v.shape[1]), dtype=torch.float64, device=dev) for v in chunks]
+        if sync:  # (what torch was asked for above is done, and nothing of torch's touches the new tensors)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        count_counts = counts
+        if queries is not None:  # (the count's n stays readable: with queries the sums' row count is q)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+        for at, (v, part) in enumerate(zip(chunks, parts)):
+            eng.pairs_sum(v, part, wsum if at == 0 else None, power=power, include_self=include_self, queries=queries,
+                          counts=counts)
+        if not sync:
+            self._field_temporaries = (offsets, count_counts, chunks, parts)  # (held until the next call: still queued)
+        else:
+            eng.synchronize()
+            n, status = (int(v) for v in counts.cpu())
+            if status == N.FIELDS_DOMAIN:
+                raise ValueError(f"field_tensors: a coordinate of a point or a query lies outside the domain "
+                                 f"|c| / radius < 2^31 (radius {radius!r})")
+            if status == N.FIELDS_VALUES_SHORT:
+                raise ValueError(f"field_tensors: values has {values.shape[0]} rows, fewer than there are points")
+            if points is None:
+                self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
+        out = ()
+        if values is not None:
+            sums = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+            out = (sums.view(-1) if flat else sums,)
+        if want_wsum:
+            out += (wsum,)
+        return (*out, counts) if not sync else tuple(t[:n] for t in out)
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

@@ -16,6 +16,7 @@
 #include "sc_pairs.h"
 #include "sc_clusters.h"
 #include "sc_nearest.h"
+#include "sc_fields.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"

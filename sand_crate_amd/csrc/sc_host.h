@@ -274,6 +274,16 @@ struct NearestSpace {
   }
 };
 
+// sc_pairs_sum_device (sc_fields.h; sc_host_state.h): the flag of the call's own -- a query outside the domain, values
+// with fewer rows than the count has points: the count's flag stays as the count left it.
+struct FieldsSpace {
+  DevBuf<int> flag;
+  int ensure(hipStream_t stream) {
+    HIPCHK(flag.grow(1, stream));
+    return SC_OK;
+  }
+};
+
 // The checkpoint (sc_checkpoint_begin / _finish; sc_host_snapshot.h): device-side snapshot, pinned host copy, and the
 // events that order them on the context's stream and the side stream.
 struct Snapshot {
@@ -401,6 +411,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   PairsSpace pairs;
   ClusterSpace clusters;
   NearestSpace nearest;
+  FieldsSpace fields;
   Snapshot snap;
   SlabLink link;
 };

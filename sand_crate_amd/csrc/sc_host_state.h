@@ -1,10 +1,12 @@
-// Host side of the state in the caller's device memory: export and import, pair lists, clusters and nearest-k tables.
+// Host side of the state in the caller's device memory: export and import, pair lists, clusters, nearest-k tables and
+// weighted neighbourhood sums.
 #pragma once
 #include "sc_host.h"
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_clusters.h"
 #include "sc_nearest.h"
+#include "sc_fields.h"
 
 extern "C" {
 
@@ -245,6 +247,66 @@ int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_quer
   if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, g, queries, rows, k, out);
   else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, g, queries, rows, k, out);
   else nearest_launch<kNearestMaxK>(c, g, queries, rows, k, out);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- weighted neighbourhood sums (sc_fields.h) ---------------------------------------------------
+
+}  // extern "C"
+
+template <int C>
+static void fields_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int self, int power, int channels,
+                          const double* values, const FieldsOut& out) {
+  hipLaunchKernelGGL(k_fields_sum<C>, dim3(grid_for(rows)), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(),
+                     c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries, (long long)rows, self, power,
+                     channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), values, out);
+}
+
+extern "C" {
+
+int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* dev_values, int64_t values_rows,
+                        int32_t channels, int32_t power, int32_t flags, double* dev_sums, double* dev_wsum, int64_t room_rows,
+                        int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_counts) return fail(SC_ERR_ARG, "null counts pointer");
+  if (!dev_sums && !dev_wsum) return fail(SC_ERR_ARG, "neither sums nor weight sums to write");
+  if (channels < 0 || channels > SC_FIELDS_MAX_CHANNELS)
+    return fail(SC_ERR_ARG, "%d channels, it must be 0 .. %d", (int)channels, (int)SC_FIELDS_MAX_CHANNELS);
+  if (channels > 0 && (!dev_values || !dev_sums)) return fail(SC_ERR_ARG, "null values or sums pointer with %d channels", (int)channels);
+  if (power < 0 || power > 3) return fail(SC_ERR_ARG, "power is %d, it must be 0 .. 3", (int)power);
+  if (flags & ~SC_FIELDS_SELF) return fail(SC_ERR_ARG, "unknown flags %d", flags);
+  if (room_rows < 0 || values_rows < 0) return fail(SC_ERR_ARG, "negative room or number of value rows");
+  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
+  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_sum_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to sum over: sc_pairs_count_device comes first, and the state must not change in between");
+  if (dev_queries && n_queries > kPairsMaxPoints)
+    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
+  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
+  if (room_rows < rows)
+    return fail(SC_ERR_CAPACITY, "the sums hold %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
+                dev_queries ? "queries" : "points");
+  HIPCHK(hipSetDevice(c->device));
+  static_assert(kFieldsMaxChannels == SC_FIELDS_MAX_CHANNELS, "the header's bound is the kernel's");
+  const int rc = c->fields.ensure(c->stream);
+  if (rc) return rc;
+  PairsGrid g = c->pairs.grid;
+  g.half = 0;  // the sums run over the full list, whichever form the count had
+  const XY* queries = (const XY*)dev_queries;
+  const double* values = channels ? dev_values : nullptr;
+  const FieldsOut out{channels ? dev_sums : nullptr, dev_wsum, (long long*)dev_counts};
+  const int self = (flags & SC_FIELDS_SELF) ? 1 : 0;
+  HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_fields_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
+                     queries, (long long)n_queries, values, (long long)values_rows, c->pairs.words.get(), c->pairs.flag.get(),
+                     c->fields.flag.get(), out.counts);
+  if (channels <= 1) fields_launch<1>(c, g, queries, rows, self, power, channels, values, out);
+  else if (channels <= 2) fields_launch<2>(c, g, queries, rows, self, power, channels, values, out);
+  else if (channels <= 4) fields_launch<4>(c, g, queries, rows, self, power, channels, values, out);
+  else fields_launch<8>(c, g, queries, rows, self, power, channels, values, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -285,6 +285,50 @@ class Engine:
                                                   room, N._P(counts.data_ptr())))
         return counts
 
+    def pairs_sum(self, values=None, sums=None, wsum=None, *, power: int = 3, include_self: bool = True, queries=None,
+                  counts, room: int | None = None, values_rows: int | None = None):
+        """The weighted sums over the partners of the last `pairs_count`, whichever `half` it had (sc_pairs_sum_device;
+        the rule is tests/field_spec.py): `sums`, float64 (R, C), receives per row the sum of w * values[j, :] over its
+        partners j within the count's radius, added in ascending j, and `wsum`, float64 (R,) or None, the sum of the
+        weights w = (1 - d2 / radius^2) ** power, `power` 0 .. 3.  `values` is float64 (V, C), row j the values of point j
+        of the count, C at most 8; with `values` and `sums` None only `wsum` is written.  The rows are the count's points
+        -- `include_self`: point r is a partner of its own row -- or with `queries`, a float64 (q, 2) CUDA tensor, those
+        points of any kind.  `counts`, int64 (2,), receives the row count and the status: 0, -1 when a point or a query
+        lies outside the domain, -2 when `values` has fewer rows than the count has points (then nothing else is written).
+        `room` defaults to R rows, `values_rows` to V.  Enqueued on the context's stream, no synchronisation.  Returns
+        `counts`."""
+        power = int(power)
+        if not 0 <= power <= 3:
+            raise ValueError("power must be 0 .. 3")
+        if (values is None) != (sums is None):
+            raise ValueError("values and sums come together")
+        if sums is None and wsum is None:
+            raise ValueError("neither sums nor wsum to write")
+        channels, rows = 0, None
+        if values is not None:
+            if values.dim() != 2 or not 1 <= values.shape[1] <= N.FIELDS_MAX_CHANNELS:
+                raise ValueError(f"values must be (points, C) with C 1 .. {N.FIELDS_MAX_CHANNELS}")
+            channels = int(values.shape[1])
+            held = _state_tensor(values, "values", "float64", (channels,), self.device)
+            values_rows = held if values_rows is None else int(values_rows)
+            if not 0 <= values_rows <= held:
+                raise ValueError(f"values_rows {values_rows} exceeds the values' {held} rows")
+            rows = _state_tensor(sums, "sums", "float64", (channels,), self.device)
+        if wsum is not None:
+            rows = _state_tensor(wsum, "wsum", "float64", (), self.device, rows)
+        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the tensors' {rows} rows")
+        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
+        # for the self form)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_sum_device(self._ctx, ptr(queries), q, ptr(values), values_rows or 0, channels, power,
+                                              N.FIELDS_SELF if include_self else 0, ptr(sums), ptr(wsum), room,
+                                              N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

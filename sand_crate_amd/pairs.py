@@ -1,5 +1,6 @@
 """Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
-`Crate.cluster_tensors` (labels, sizes), and for the nearest-k tables of `Crate.neighbor_tensors` (neighbors)."""
+`Crate.cluster_tensors` (labels, sizes), for the nearest-k tables of `Crate.neighbor_tensors` (neighbors) and for the
+weighted sums of `Crate.field_tensors` (sums, wsum)."""
 from __future__ import annotations
 
 
@@ -45,3 +46,25 @@ def neighbor_edge_index(neighbors):
     import torch
     rows, places = torch.nonzero(neighbor_mask(neighbors), as_tuple=True)  # (row-major: rows ascending, then places)
     return torch.stack([rows, neighbors[rows, places]])
+
+
+def normalized(sums, wsum):
+    """The Shepard-normalised field of `Crate.field_tensors(values, weight_sums=True)`: sums / wsum, row by row -- the
+    weighted mean of the partners' values --, and 0 where wsum is 0 (a row without partners, or with none inside the
+    radius at power >= 1).  `sums` is (rows, C) or (rows,), `wsum` (rows,)."""
+    import torch
+    w = wsum if sums.dim() == 1 else wsum.unsqueeze(1)
+    return torch.where(w == 0, torch.zeros_like(sums), sums / w)
+
+
+def grid_queries(x0, x1, y0, y1, nx, ny, device=None):
+    """The centres of the nx x ny cells of the rectangle [x0, x1] x [y0, y1] as a float64 (nx * ny, 2) tensor of
+    queries in row-major order, y the slow axis: query iy * nx + ix is (x0 + (ix + 0.5) (x1 - x0) / nx,
+    y0 + (iy + 0.5) (y1 - y0) / ny).  `Crate.field_tensors(v, queries=grid_queries(...))[0].reshape(ny, nx, -1)` is an
+    image of the field, row 0 at y0."""
+    import torch
+    if nx < 0 or ny < 0:
+        raise ValueError("nx and ny must not be negative")
+    x = x0 + (torch.arange(nx, dtype=torch.float64, device=device) + 0.5) * ((x1 - x0) / nx if nx else 0.0)
+    y = y0 + (torch.arange(ny, dtype=torch.float64, device=device) + 0.5) * ((y1 - y0) / ny if ny else 0.0)
+    return torch.stack([x.repeat(ny), y.repeat_interleave(nx)], dim=1)
