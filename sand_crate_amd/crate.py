@@ -163,9 +163,6 @@ class Crate:
         return self._count
 
     # ------------------------------------------------------------------ state attributes
-    def _count_or_unknown(self) -> bool:
-        return (not self._count_known) or self._count > 0
-
     def _empty(self) -> None:
         self._cache = (np.zeros((0, 2)), np.zeros((0, 2)), np.zeros((0,)))
 
@@ -515,15 +512,28 @@ class Crate:
         self._noise = "host-sync"
 
     def _grow(self, needed: int) -> None:
-        p, v, _ = self._state() if self._count_or_unknown() else (np.zeros((0, 2)), np.zeros((0, 2)), None)
+        """A larger context takes the place of the one the state has outgrown, and the run goes on as if the crate had
+        had the room from the start: a run does not depend on the capacity.  The state goes over through the old
+        context's snapshot (sc_checkpoint_begin / sc_checkpoint_finish) -- particles and velocities with their ids, the
+        tick number, the next id to hand out, the device's generator -- so counter noise, exported ids, the logs' tick
+        numbers and the phase of `track(every=)` continue; noise mode and seed, the logs, and what the old engine was
+        told (`Engine.adopt_settings`: stream, scan patience, timing, force monitor) are set again; HUD text and arrows
+        are sent again with the next frame.  Pressures are not part of a snapshot: as after any upload they are zero
+        until the next tick -- the callers grow right before one, or replace the state anyway.  `engine.timing()` counts
+        the launches of the context that is there.  Costs a synchronisation and a copy of the state through the host."""
         old = self._engine
-        rng = old.rng_get_state() if self._noise == "host" else None
+        pending = getattr(self, "_pending_checkpoint", None)
+        if pending is not None and "snapshot" not in pending:  # begin_checkpoint's capture lives in the old context
+            pending["snapshot"] = old.checkpoint_finish()
+        old.checkpoint_begin()
+        snap = old.checkpoint_finish()
         self._engine = Engine(int(needed * 1.5) + 1024, device=old.device)
         self._engine.set_noise_mode(_NOISE_MODES[self._noise], self._noise_seed)
+        self._engine.adopt_settings(old)
         self._hud_sent = None  # (a new context has no HUD)
         self._arrows_sent = None  # (... and no arrows)
-        if rng is not None:
-            self._engine.rng_set_state(*rng)
+        if self._noise == "host" and snap["rng"] is not None:
+            self._engine.rng_set_state(*snap["rng"])
         if getattr(self, "_observe", None) is not None:  # the log moves on: what the old context holds is kept
             self._observed.append(old.probe_read())
             self._engine.probe_enable(*self._observe)
@@ -531,8 +541,11 @@ class Crate:
             self._tracked.append(self._read_track(old))
             self._engine.track_enable(*self._track)
         old.close()
-        if len(p):
-            self._engine.upload(p, v)
+        if len(snap["ids"]):
+            self._engine.upload_with_ids(snap["particles"], snap["velocities"], snap["ids"])
+        self._engine.restore_counters(snap["tick"], snap["next_id"])
+        self._count, self._count_known = len(snap["ids"]), True
+        self._cache = None
 
     # ------------------------------------------------------------------ the tick
     def physics_tick(self) -> None:
@@ -628,8 +641,8 @@ class Crate:
     def observations(self) -> dict:
         """What was logged since the last call, oldest first: a T-long float64 array per name of `probe.FIELDS`, `count`
         (T x bins, int32) and `top` (T x bins) when the log has bins, and `dropped`, the ticks that found the log
-        full.  T = 0 when nothing was logged.  Synchronises.  (`tick` counts the ticks of the GPU context: it starts
-        over when the crate had to grow into a larger one.)"""
+        full.  T = 0 when nothing was logged.  Synchronises.  (`tick` counts the ticks of the GPU context, and goes on
+        counting when the crate had to grow into a larger one: `_grow`.)"""
         chunks, self._observed = self._observed, []
         if self._observe is not None:
             chunks.append(self._engine.probe_read())
@@ -675,8 +688,8 @@ class Crate:
 
     def tracked(self) -> tuple[list[bytes], int]:
         """-> (the frames logged since the last call, oldest first; how many were dropped because the log was full).
-        Synchronises.  (A frame's tick counts the ticks of the GPU context: it starts over when the crate had to grow
-        into a larger one.)"""
+        Synchronises.  (A frame's tick counts the ticks of the GPU context, and goes on counting when the crate had to
+        grow into a larger one: `_grow`.)"""
         chunks, self._tracked = self._tracked, []
         if self._track is not None:
             chunks.append(self._read_track(self._engine))
@@ -825,7 +838,9 @@ class Crate:
         if self._pending_checkpoint is None:
             raise RuntimeError("begin_checkpoint first")
         meta, self._pending_checkpoint = self._pending_checkpoint, None
-        snap = self._engine.checkpoint_finish()
+        snap = meta.pop("snapshot", None)  # (collected already when the crate grew out of the context that took it)
+        if snap is None:
+            snap = self._engine.checkpoint_finish()
         pressure = meta.pop("pressure")
         meta["next_id"] = int(snap["next_id"])
         meta["engine_tick"] = int(snap["tick"])

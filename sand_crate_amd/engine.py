@@ -93,6 +93,24 @@ class Engine:
         N.check(self._lib.sc_create(int(device), int(capacity), C.byref(self._ctx)))
         self.capacity = int(capacity)
         self.device = int(device)
+        # the settings a context is given and cannot be asked for: kept here, so that a context that replaces this one
+        # can be given the same (`adopt_settings`; Crate._grow)
+        self.stream = None            # the hipStream_t handed to `set_stream`, or None: the context's own stream
+        self.scan_patience = None     # what `set_scan_patience` was given, or None: the library's default
+        self.timing_on = False
+        self.force_monitor_on = False
+
+    def adopt_settings(self, other: "Engine") -> None:
+        """The settings `other` was given become this context's: the stream, the scan's patience, timing and the force
+        monitor.  (Noise mode, generator, HUD, arrows and the logs belong to their owner: crate.py.)"""
+        if other.stream is not None:
+            self.set_stream(other.stream)
+        if other.scan_patience is not None:
+            self.set_scan_patience(other.scan_patience)
+        if other.timing_on:
+            self.enable_timing(True)
+        if other.force_monitor_on:
+            self.enable_force_monitor(True)
 
     # -- lifetime
     def close(self) -> None:
@@ -109,9 +127,11 @@ class Engine:
     def set_stream(self, stream_handle: int) -> None:
         """Enqueue on this hipStream_t (0 = HIP's default stream), e.g. torch's current stream."""
         N.check(self._lib.sc_set_stream(self._ctx, N._P(int(stream_handle))))
+        self.stream = int(stream_handle)
 
     def use_own_stream(self) -> None:
         N.check(self._lib.sc_use_own_stream(self._ctx))
+        self.stream = None
 
     # -- state
     def upload(self, particles, velocities) -> None:
@@ -501,6 +521,7 @@ class Engine:
         """How often a workgroup of the bucket scan asks for a predecessor's total before the tick is abandoned
         (sc_set_scan_patience; negative: at once -- the path's test)."""
         N.check(self._lib.sc_set_scan_patience(self._ctx, int(polls)))
+        self.scan_patience = int(polls)
 
     # -- parity taps (between step_begin and step_finish)
     def download_sort(self):
@@ -705,6 +726,7 @@ class Engine:
     # -- force monitor
     def enable_force_monitor(self, on: bool = True) -> None:
         N.check(self._lib.sc_enable_force_monitor(self._ctx, 1 if on else 0))
+        self.force_monitor_on = bool(on)
 
     def force_monitor(self):
         """-> (sum of |dv| per phase (6,), particles summed) since the last call; synchronises."""
@@ -758,6 +780,7 @@ class Engine:
     # -- timing
     def enable_timing(self, on: bool = True) -> None:
         N.check(self._lib.sc_enable_timing(self._ctx, 1 if on else 0))
+        self.timing_on = bool(on)
 
     def reset_timing(self) -> None:
         N.check(self._lib.sc_reset_timing(self._ctx))

@@ -1,0 +1,389 @@
+"""GPU tests of the capacity rule: a run does not depend on the capacity the crate's context happened to get
+(`Crate._grow`; the worlds are tests/growth_cases.py, their premises tests/test_growth_cases_cpu.py).
+
+A crate that starts at capacity 16 and grows mid-run -- out of the particle sources, out of `crate.particles =`, out of
+the device emission's SC_ERR_CAPACITY -- is compared tick by tick with the oracle restarted from the device's previous
+state, given the true ids and the crate's tick, and byte for byte with a twin that had the room from the start: the
+state, the logs of `observe` and `track`, the force monitor, the frames, a checkpoint and what continues from it, and the
+settings the engine was given."""
+import copy
+import json
+
+import numpy as np
+import pytest
+
+import force_cases as fc
+import growth_cases as G
+from conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+
+CASES = G.cases()
+NOISES = ("none", "counter", "host-sync")
+HUD = "grown\ncrate"
+ARROWS = [[[0.2, 0.2], [0.3, 0.0]], [[0.8, 0.7], [0.0, -0.3]]]
+
+
+@pytest.fixture(scope="module")
+def sc():
+    import sand_crate_amd
+    return sand_crate_amd
+
+
+def make_crate(sc, case, noise, capacity):
+    wc = sc.WorldConfig(rigid_bodies=copy.deepcopy(case.bodies), particle_sources=copy.deepcopy(getattr(case, "sources", [])),
+                        coefficients=copy.deepcopy(case.coef))
+    return sc.Crate(wc, noise=noise, noise_seed=G.SEED, capacity=capacity)       # (seeds np.random, crate.py:22)
+
+
+def ticked_set_state_crate(sc, case, capacity):
+    """A crate of this capacity with the set-state case's first particles, ticked up to the replacement."""
+    crate = make_crate(sc, case, "counter", capacity)
+    crate.particles, crate.particle_velocities = case.first[0], case.first[1]
+    for _ in range(case.ticks_before):
+        crate.physics_tick()
+    return crate
+
+
+def set_flows(sources, case, tick, since=None):
+    """The flow edits of the case that are due at `tick` (`since`: every edit from that tick up to `tick`)."""
+    for t in range(tick if since is None else since, tick + 1):
+        flows = case.flows_at(t)
+        if flows is not None:
+            for s, f in zip(sources, flows):
+                s.flow = f
+
+
+def tick(crate, case):
+    set_flows(crate.particle_sources, case, crate.tick)
+    crate.physics_tick()
+
+
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def final_state(crate):
+    """What the two capacities must agree on: `engine.download()` and `state_tensors(ids=True)`, as NumPy arrays."""
+    return tuple(crate.engine.download()) + tuple(t.cpu().numpy() for t in crate.state_tensors(ids=True))
+
+
+def same_stream(a, b):
+    return a[2] == b[2] and np.array_equal(a[1], b[1])
+
+
+# ------------------------------------------------------------------ against the oracle
+def run_against_oracle(sc, case, noise, capacity):
+    """The case on a crate of this capacity, every tick against one oracle tick restarted from the device's previous
+    state: ids, counts and removals exact, floats within the suite's tolerances; the oracle draws the sources (and the
+    host-drawn noise) from the generator as the crate found it, and must leave it where the crate left it.  -> the
+    final state."""
+    crate = make_crate(sc, case, noise, capacity)
+    stage = G.Stage(case.bodies, case.coef, case.sources)
+    p, v = np.zeros((0, 2)), np.zeros((0, 2))
+    ids = np.zeros(0, dtype=np.int64)
+    next_id = 0
+    growths, expected, room = [], [], capacity
+    for t in range(case.ticks):
+        set_flows(stage.sources, case, t)
+        found = np.random.get_state()
+        engine = crate.engine
+        tick(crate, case)
+        if crate.engine is not engine:
+            growths.append((t, crate.engine.capacity))
+        left = np.random.get_state()
+        np.random.set_state(found)
+        for _, pos, vel in stage.emit(t, len(p)):
+            if pos is not None:
+                if len(p) + len(pos) > room:                      # crate.py: _create_new_particles, the host's emission
+                    room = G.grown(len(p) + len(pos))
+                    expected.append((t, room))
+                p, v = np.vstack((p, pos)), np.vstack((v, vel))
+                ids = np.concatenate((ids, next_id + np.arange(len(pos))))
+                next_id += len(pos)
+        stage.advance()
+        p, v, ids = stage.remove(p, v, ids)
+        assert crate.tick == t + 1
+        eta = {"none": None, "counter": G.counter_eta(ids, crate.tick - 1),
+               "host-sync": lambda total: np.random.rand(total, 2)}[noise]
+        out = stage.core(p, v, eta)
+        assert same_stream(np.random.get_state(), left), f"tick {t}: the crate drew another stretch of np.random"
+        gp, gv, gpr, gids = crate.engine.download()
+        where = f"{case.name}, noise {noise}, capacity {capacity}, tick {t}"
+        assert np.array_equal(gids, ids), where                   # ids, counts and removals: exact
+        assert crate.particle_count == len(ids), where
+        assert crate.measure()["tick"] == t + 1, where            # the context's own tick number
+        np.testing.assert_allclose(gp, out["particles"], rtol=fc.RTOL, atol=fc.ATOL["particles"], err_msg=where)
+        np.testing.assert_allclose(gv, out["velocities"], rtol=fc.RTOL, atol=fc.ATOL["velocities"], err_msg=where)
+        np.testing.assert_allclose(gpr, out["pressure"], rtol=fc.RTOL, atol=fc.ATOL["pressure"], err_msg=where)
+        p, v = gp, gv
+    assert growths == expected, f"{case.name}, capacity {capacity}: grew at {growths}"
+    if noise == "host-sync":  # (the noise draws from np.random between the sources' draws: other counts, other capacities)
+        assert len(growths) == len(case.growths[capacity]) and [t for t, _ in growths] == [t for t, _ in case.growths[capacity]]
+    else:
+        assert tuple(growths) == case.growths[capacity]
+    return final_state(crate)
+
+
+@pytest.mark.parametrize("noise", NOISES)
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_every_capacity_matches_the_oracle_and_the_ample_one(sc, name, noise):
+    case = CASES[name]
+    finals = [run_against_oracle(sc, case, noise, capacity) for capacity in case.capacities]
+    assert len(finals[-1][0]) > 200
+    for got in finals[:-1]:
+        for a, b in zip(got, finals[-1]):
+            same_bytes(a, b)
+
+
+# ------------------------------------------------------------------ against the reference
+@pytest.mark.parametrize("scene", ["stirring_cup", "wave_machine"])
+def test_scene_trajectory_matches_reference_from_capacity_16(sc, scene):
+    """The default noise mode draws the sources on the device: the first emission does not fit 16 slots
+    (SC_ERR_CAPACITY), the crate grows and asks again -- and the stream must stand where one successful call leaves it,
+    or every later draw differs from the reference's.  Tolerances of test_scene_trajectory_matches_reference."""
+    g = load_golden(f"traj_{scene}")
+    crate = sc.Crate(sc.load_config(f"config/{scene}.yaml").world_config, noise="host", capacity=16)
+    first = crate.engine
+    ticks = [int(t) for t in g["ticks"]]
+    for t in range(1, max(ticks) + 1):
+        crate.physics_tick()
+        if t in ticks:
+            assert crate.particles.shape == g[f"particles_t{t}"].shape, f"particle count differs at tick {t}"
+            assert np.array_equal(crate.segments, g[f"segments_t{t}"])
+            np.testing.assert_allclose(crate.particles, g[f"particles_t{t}"], rtol=1e-5, atol=1e-9)
+            np.testing.assert_allclose(crate.particle_velocities, g[f"velocities_t{t}"], rtol=1e-5, atol=1e-7)
+            np.testing.assert_allclose(crate.particles_pressure, g[f"pressure_t{t}"], rtol=1e-5, atol=1e-9)
+    assert crate.engine is not first and crate.engine.capacity > crate.particle_count > 16
+    assert crate._noise == "host" and crate.measure()["tick"] == max(ticks)
+
+
+# ------------------------------------------------------------------ the add-ons across a growth
+@pytest.fixture()
+def spy(monkeypatch):
+    """What `physics_tick` reads from the engine for the HUD, recorded: the particles the force monitor summed and the
+    launches the timing counted, per read (the tick clears both when it has read them)."""
+    from sand_crate_amd.engine import Engine
+    seen = {"summed": [], "launches": []}
+    force_monitor, timing = Engine.force_monitor, Engine.timing
+
+    def spy_force_monitor(self):
+        out = force_monitor(self)
+        seen["summed"].append(out[1])
+        return out
+
+    def spy_timing(self):
+        out = timing(self)
+        seen["launches"].append(sum(launches for _, launches in out.values()))
+        return out
+
+    monkeypatch.setattr(Engine, "force_monitor", spy_force_monitor)
+    monkeypatch.setattr(Engine, "timing", spy_timing)
+    return seen
+
+
+def addon_run(sc, case, capacity, seen):
+    crate = make_crate(sc, case, "counter", capacity)
+    crate.observe(capacity=64, bins=8)
+    crate.track(every=3, capacity_bytes=1 << 22)
+    crate.show_forces(True)
+    crate.show_kernel_times(True)
+    crate.render(96, 80, hud=HUD, arrows=ARROWS)                  # the HUD and the arrows are set before any growth
+    seen["summed"].clear()
+    seen["launches"].clear()
+    engines = [crate.engine]
+    for _ in range(case.ticks):
+        tick(crate, case)
+        if crate.engine is not engines[-1]:
+            engines.append(crate.engine)
+    return dict(crate=crate, contexts=len(engines), obs=crate.observations(), tracked=crate.tracked(),
+                ema=dict(crate._force_ema), summed=list(seen["summed"]), launches=list(seen["launches"]),
+                frame=crate.render(96, 80, hud=HUD, arrows=ARROWS), bare=crate.render(96, 80))
+
+
+def test_add_ons_across_two_growths(sc, spy):
+    import probe_spec
+    import track_spec
+    case = CASES["sources_two_growths"]
+    grown, twin = (addon_run(sc, case, capacity, spy) for capacity in case.capacities)
+    assert (grown["contexts"], twin["contexts"]) == (3, 1)
+    # observe: the tick column runs on; the whole log is the twin's
+    assert grown["obs"]["tick"].tolist() == list(range(1, case.ticks + 1)) and grown["obs"]["dropped"] == 0
+    for name in (*probe_spec.FIELDS, "count", "top"):
+        same_bytes(grown["obs"][name], twin["obs"][name])
+    # track(every=3): the phase runs on; the frames are the twin's
+    frames, dropped = grown["tracked"]
+    assert dropped == 0 and [track_spec.header(f)["tick"] for f in frames] == list(range(3, case.ticks + 1, 3))
+    assert (frames, dropped) == twin["tracked"]
+    # show_forces: the monitor sums in every tick, after each growth too, and the EMA is the twin's.  (The kernel adds
+    # each wave's |dv| to the phase's sum with an atomic: the order differs from run to run, so a sum of n <= 2,000
+    # positive terms is the twin's within n * 2^-53 < 3e-13 relative, and so is an average of such sums with positive
+    # weights.)
+    assert len(grown["summed"]) == case.ticks and all(count > 0 for count in grown["summed"])
+    assert grown["summed"] == twin["summed"] and set(grown["ema"]) == set(twin["ema"]) and len(grown["ema"]) == 6
+    for phase, value in twin["ema"].items():
+        assert grown["ema"][phase] == pytest.approx(value, rel=1e-12, abs=0.0), phase
+    assert grown["ema"]["gravity"] > 0 and grown["ema"]["pressure"] > 0
+    # show_kernel_times: the new contexts time their launches
+    assert len(grown["launches"]) == case.ticks and all(n > 0 for n in grown["launches"])
+    # the HUD and the arrows are on a frame rendered after the growths
+    same_bytes(grown["frame"], twin["frame"])
+    same_bytes(grown["bare"], twin["bare"])
+    green = (grown["frame"] == (0, 255, 0)).all(axis=-1)
+    assert green.sum() > 20 and not (grown["bare"] == (0, 255, 0)).all(axis=-1).any()
+    white = (grown["frame"] == 255).all(axis=-1) & ~(grown["bare"] == 255).all(axis=-1)
+    assert white.sum() > 40                                       # the text's ink
+    for a, b in zip(final_state(grown["crate"]), final_state(twin["crate"])):
+        same_bytes(a, b)
+
+
+# ------------------------------------------------------------------ checkpoints
+def meta_of(path):
+    with np.load(path, allow_pickle=False) as z:
+        return json.loads(str(z["meta"])), {k: z[k] for k in z.files if k != "meta"}
+
+
+def test_checkpoint_after_the_second_growth_continues_the_run(sc, tmp_path):
+    """The grown crate and crates made from its checkpoint, with ample room and with 16 slots, run on to equal bytes."""
+    case = CASES["sources_two_growths"]
+    (_, _), (second, capacity) = G.TWO_GROWTHS
+    crate = make_crate(sc, case, "counter", G.FIRST_CAPACITY)
+    while crate.tick < second + 2:
+        tick(crate, case)
+    assert crate.engine.capacity == capacity
+    path = tmp_path / "grown.npz"
+    crate.save_checkpoint(path)
+    meta, arrays = meta_of(path)
+    assert meta["engine_tick"] == meta["tick"] == crate.tick == second + 2
+    _, _, _, ids = crate.engine.download()
+    assert np.array_equal(arrays["ids"], ids) and meta["next_id"] > ids.max() and len(ids) < ids.max()   # ids with gaps
+    for _ in range(5):
+        tick(crate, case)
+    want = final_state(crate)
+    for room in (case.ample, G.FIRST_CAPACITY):                   # (from 16 slots the fresh crate grows before it loads)
+        again = sc.Crate.from_checkpoint(path, capacity=room)    # (puts np.random back where the checkpoint found it)
+        set_flows(again.particle_sources, case, again.tick, since=0)  # (edits of the sources are not part of a checkpoint)
+        assert again.tick == second + 2 and again.engine.capacity >= max(room, len(ids))
+        for _ in range(5):
+            tick(again, case)
+        assert again.measure()["tick"] == crate.measure()["tick"] == second + 7
+        for a, b in zip(want, final_state(again)):
+            same_bytes(a, b)
+
+
+def test_checkpoint_begun_before_a_growth_is_finished_after_it(sc, tmp_path):
+    """`begin_checkpoint` captures in the context of that moment; the crate may outgrow it before `finish_checkpoint`."""
+    case = CASES["sources_two_growths"]
+    first = G.TWO_GROWTHS[0][0]
+    files = []
+    for capacity in case.capacities:
+        crate = make_crate(sc, case, "counter", capacity)
+        while crate.tick < first:
+            tick(crate, case)
+        engine = crate.engine
+        crate.begin_checkpoint()
+        tick(crate, case)
+        assert (crate.engine is not engine) == (capacity == G.FIRST_CAPACITY)
+        path = tmp_path / f"begun_{capacity}.npz"
+        crate.finish_checkpoint(path)
+        files.append(meta_of(path))
+    (meta, arrays), (twin_meta, twin_arrays) = files
+    assert meta == twin_meta and meta["tick"] == meta["engine_tick"] == first
+    assert sorted(arrays) == sorted(twin_arrays) and len(arrays["ids"]) > 8
+    for name in arrays:
+        same_bytes(arrays[name], twin_arrays[name])
+
+
+# ------------------------------------------------------------------ crate.particles = more than the capacity
+def set_state_run(sc, case, capacity):
+    crate = ticked_set_state_crate(sc, case, capacity)
+    engine = crate.engine
+    crate.particles = case.second
+    states = []
+    for _ in range(case.ticks_after):
+        crate.physics_tick()
+        states.append(crate.engine.download())
+    return crate.engine is not engine, states, crate.measure()["tick"]
+
+
+def test_set_state_growth_equals_a_crate_with_the_room(sc):
+    case = G.set_state_growth()
+    (replaced, states, last), (twin_replaced, twin_states, twin_last) = (set_state_run(sc, case, c) for c in case.capacities)
+    assert replaced and not twin_replaced
+    assert last == twin_last == case.ticks_before + case.ticks_after   # the tick comes from the old context, as without a growth
+    for got, want in zip(states, twin_states):
+        for a, b in zip(got, want):
+            same_bytes(a, b)
+    # the first tick after the replacement starts from a state the oracle knows exactly
+    t, out, _ = list(G.run_set_state(case))[case.ticks_before]
+    gp, gv, gpr, gids = states[0]
+    assert t == case.ticks_before and np.array_equal(gids, np.arange(len(case.second)))
+    np.testing.assert_allclose(gp, out["particles"], rtol=fc.RTOL, atol=fc.ATOL["particles"])
+    np.testing.assert_allclose(gv, out["velocities"], rtol=fc.RTOL, atol=fc.ATOL["velocities"])
+    np.testing.assert_allclose(gpr, out["pressure"], rtol=fc.RTOL, atol=fc.ATOL["pressure"])
+
+
+def test_load_state_tensors_growth_equals_a_crate_with_the_room(sc):
+    """The device form of the setter (`load_state_tensors`), with ids that have gaps: they are the caller's, the tick is
+    the old context's."""
+    import torch
+    case = G.set_state_growth()
+    ids = np.arange(len(case.second), dtype=np.int64) * 3 + 7
+    finals = []
+    for capacity in case.capacities:
+        crate = ticked_set_state_crate(sc, case, capacity)
+        engine = crate.engine
+        dev = torch.device("cuda", engine.device)
+        tensors = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (case.second, np.zeros_like(case.second), ids)]
+        torch.cuda.current_stream(dev).synchronize()
+        crate.load_state_tensors(*tensors)
+        assert (crate.engine is not engine) == (capacity == case.capacities[0])
+        assert np.array_equal(crate.engine.download()[3], ids)
+        crate.physics_tick()
+        crate.physics_tick()
+        assert crate.measure()["tick"] == case.ticks_before + 2
+        finals.append(final_state(crate))
+    for a, b in zip(*finals):
+        same_bytes(a, b)
+
+
+# ------------------------------------------------------------------ what the engine was told
+def test_engine_settings_hold_after_a_growth(sc, monkeypatch):
+    import torch
+    case = G.set_state_growth()
+    small, _ = case.capacities
+    crate = ticked_set_state_crate(sc, case, small)
+    assert (crate.engine.scan_patience, crate.engine.stream) == (None, None)
+    stream = torch.cuda.Stream()
+
+    def forbidden(*args, **kw):
+        raise AssertionError("the call synchronised")
+
+    with torch.cuda.stream(stream):
+        handle = torch.cuda.current_stream().cuda_stream
+        assert handle == stream.cuda_stream != 0
+        crate.engine.set_scan_patience(5000)
+        crate.engine.set_stream(handle)
+        try:
+            engine = crate.engine
+            assert (engine.scan_patience, engine.stream) == (5000, handle)
+            crate.particles = case.second                         # more than the capacity: `_grow` makes a new context
+            assert crate.engine is not engine
+            assert (crate.engine.scan_patience, crate.engine.stream) == (5000, handle)
+            crate.physics_tick()
+            with monkeypatch.context() as m:
+                m.setattr(type(crate.engine), "synchronize", forbidden)
+                m.setattr(torch.cuda, "synchronize", forbidden)
+                m.setattr(torch.cuda.Stream, "synchronize", forbidden)
+                m.setattr(torch.Tensor, "item", forbidden)
+                m.setattr(torch.Tensor, "cpu", forbidden)
+                out = crate.state_tensors(ids=True, sync=False)
+            stream.synchronize()                                  # torch's stream alone: the crate enqueued on it
+            n = int(out[-1].item())
+            got = tuple(t[:n].cpu().numpy() for t in out[:-1])
+        finally:
+            crate.engine.use_own_stream()
+    assert crate.engine.stream is None and n == len(case.second)
+    for a, b in zip(got, crate.engine.download()):
+        same_bytes(a, b)

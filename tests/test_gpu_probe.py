@@ -199,7 +199,7 @@ def test_grow_keeps_the_log(sc):
         crate.physics_tick()
     obs = crate.observations()
     assert obs["n"][:3].tolist() == [n] * 3 and obs["n"][3] == len(more) >= obs["n"][4] > n   # before and after, in order
-    assert obs["tick"].tolist() == [1.0, 2.0, 3.0, 1.0, 2.0]          # (the new context counts its own ticks)
+    assert obs["tick"].tolist() == [1.0, 2.0, 3.0, 4.0, 5.0]          # (the new context counts on: the tick goes over)
     assert obs["count"].shape == (5, 8) and obs["dropped"] == 0
     same_bytes(np.array([obs[name][-1] for name in S.FIELDS]), row_of(crate.measure(8)))
 

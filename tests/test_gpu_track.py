@@ -305,7 +305,7 @@ def test_grow_keeps_the_log(sc):
     for _ in range(2):
         crate.physics_tick()
     frames, dropped = crate.tracked()
-    assert dropped == 0 and [S.header(f)["tick"] for f in frames] == [1, 2, 3, 1, 2]
+    assert dropped == 0 and [S.header(f)["tick"] for f in frames] == [1, 2, 3, 4, 5]  # (the new context counts on)
     assert [S.header(f)["n"] for f in frames[:3]] == [n] * 3 and S.header(frames[3])["n"] == len(more)
     assert frames[-1] == crate.engine.track_capture()
 
