@@ -773,6 +773,59 @@ int sc_pairs_sum_device(sc_ctx* ctx, const double* dev_queries /* NULL: the poin
                         double* dev_wsum /* rows, may be NULL */, int64_t room_rows,
                         int64_t* dev_counts /* [2]: rows, status */);
 
+/* The gradient of those sums with respect to POSITIONS, in DEVICE memory of the caller: what torch's autograd needs to
+ * differentiate sc_pairs_sum_device through the coordinates of the points or of the queries (`Crate.field_function`).
+ * The gradient with respect to the values needs no call of its own: the weight depends on d2 only and d2 is bitwise
+ * symmetric, so it is sc_pairs_sum_device with rows and partners swapped.  tests/field_grad_spec.py (`position_grad`) is
+ * the rule: j is a partner of row r iff fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius), dx = fl(x_r - x_j), and in the
+ * self form j != r always (d2_rr is identically 0; SC_FIELDS_SELF plays no part); with t = fl(1 - fl(d2 / r2)) and
+ * m = 1, t, fl(t t) for `power` 1, 2, 3,
+ *     s           = ((((0 + row_s[r]) + part_s[j]) + fl(row_a[r, 0] part_b[j, 0])) + fl(row_a[r, 1] part_b[j, 1])) + ...
+ *     ax          = ((0 + fl(fl(s m) dx_j1)) + fl(fl(s m) dx_j2)) + ...          ay likewise with dy
+ *     dev_grad[r] = (fl(k ax), fl(k ay)),  k = fl(-(2 power) / r2)
+ * over the partners in ASCENDING j, from +0.0, every product and every sum rounded on its own; an absent row_s or part_s
+ * adds nothing.  With `power` 0 the weights are constant: every row gets +0.0.  A point with a coordinate that is not
+ * finite is nobody's partner; a row whose own point or query is not finite gets fl(k 0).  The arrays are taken as they
+ * are: a NaN or an infinity propagates by IEEE rules.  A pure function of its inputs: two calls give the same bits.
+ *     The three uses, with G and gw the upstream gradients of dev_sums and dev_wsum and V the values: the self form with
+ * respect to the points has row_a = [G | V], part_b = [V | G] (twice the channels: s = G_r V_j + V_r G_j) and row_s =
+ * part_s = gw; the query form with respect to the queries has row_a = G, part_b = V, row_s = gw over a count of the
+ * points; the query form with respect to the points has the POINTS as dev_queries over a count of the queries, row_a = V,
+ * part_b = G, part_s = gw.  More than SC_FIELDS_MAX_CHANNELS channels go in groups, the scalars with the first, and the
+ * results are added in ascending group order.
+ *
+ * sc_pairs_sum_grad_device  runs over the grid of the last sc_pairs_count_device of this context, as sc_pairs_sum_device
+ *     does, and leaves the workspace as it is.  The rows: with dev_queries NULL the count's n points themselves, else
+ *     the n_queries rows of dev_queries (n_queries x 2 interleaved float64, aligned to 16 bytes).  dev_row_a is row_a_rows
+ *     x channels and dev_part_b part_b_rows x channels contiguous float64; channels is 0 .. SC_FIELDS_MAX_CHANNELS, with 0
+ *     neither is looked at.  dev_row_s (row_a_rows entries) and dev_part_s (part_b_rows entries) may each be NULL.
+ *     Writes dev_grad (rows x 2 interleaved, aligned to 16 bytes) for every row below the row count; rows from the row
+ *     count on are left as they were.  `room_rows`, the room of dev_grad in rows, must be at least the bound the count was
+ *     sized by (self form) or n_queries.  dev_counts[0] = the row count, dev_counts[1] = the status: 0 when all is well;
+ *     -1 after a count that found a point outside the domain, or with a query outside it; -2 when row_a_rows is below the
+ *     row count and dev_row_a (with channels > 0) or dev_row_s is given, or part_b_rows is below the count's n and
+ *     dev_part_b (with channels > 0) or dev_part_s is given.  With a status below 0 only dev_counts[1] is written, and no
+ *     row of an array at or beyond its stated length is ever read.  The status comes from a flag of this call's own.
+ * It enqueues on the context's stream only, with the rules of sc_pairs_sum_device.
+ *     The algorithm: a check pass, then a thread per row walks the merge of sc_pairs_sum_device with its own row_a[r, :]
+ * and row_s[r] in registers, gathers part_b[j, :] and part_s[j] where they lie, keeps two sums and writes one 16-byte
+ * record.  Four kernels, for 1, 2, 4 and 8 channels.  No floating-point atomics, no atomic's order reaches the output,
+ * no workgroup waits for another, nothing of the list's size is written (csrc/sc_fields_grad.h).
+ * scripts/field_grad_time.py measures it on an MI355X against torch's autograd of the list route:
+ * profiles/field_grad_time.txt has the times.
+ *     SC_ERR_ARG for a null context, null dev_counts or dev_grad, channels outside 0 .. SC_FIELDS_MAX_CHANNELS, channels
+ * > 0 with dev_row_a or dev_part_b NULL, power outside 0 .. 3, a negative n_queries, row count or room, or misaligned
+ * queries or gradient.  SC_ERR_STATE and SC_ERR_CAPACITY as for sc_pairs_sum_device.  All checked before anything is
+ * launched: the arrays are then untouched. */
+int sc_pairs_sum_grad_device(sc_ctx* ctx, const double* dev_queries /* NULL: the points themselves */, int64_t n_queries,
+                             const double* dev_row_a /* rows x channels */, int64_t row_a_rows,
+                             const double* dev_part_b /* points x channels */, int64_t part_b_rows,
+                             int32_t channels /* 0 .. SC_FIELDS_MAX_CHANNELS */,
+                             const double* dev_row_s /* rows, may be NULL */,
+                             const double* dev_part_s /* points, may be NULL */, int32_t power,
+                             double* dev_grad /* rows x 2 */, int64_t room_rows,
+                             int64_t* dev_counts /* [2]: rows, status */);
+
 #ifdef __cplusplus
 }
 #endif

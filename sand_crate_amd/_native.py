@@ -197,6 +197,8 @@ SIGNATURES = {
     "sc_pairs_nearest_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "sc_pairs_sum_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
                                       _P]),
+    "sc_pairs_sum_grad_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, C.c_int32,
+                                           _P, C.c_int64, _P]),
 }
 
 

@@ -485,6 +485,18 @@ class Crate:
             out += (wsum,)
         return (*out, counts) if not sync else tuple(t[:n] for t in out)
 
+    def field_function(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
+                       points=None, queries=None, weight_sums: bool = False):
+        """`field_tensors(..., sync=True)` under torch autograd: the same arguments, the same results bit for bit, attached
+        to the graph when `values`, `points` or `queries` requires grad -- `backward()` then gives their gradients from
+        the same grid kernels (sc_pairs_sum_device with rows and partners swapped for the values,
+        sc_pairs_sum_grad_device for the positions; tests/field_grad_spec.py is the rule).  When nothing requires grad it
+        is `field_tensors` and nothing more.  Once differentiable; no gradient with respect to `radius`, no `sync=False`
+        form: `sand_crate_amd.fields.field_function` has the details."""
+        from .fields import field_function
+        return field_function(self, values, radius, power=power, include_self=include_self, points=points, queries=queries,
+                              weight_sums=weight_sums)
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

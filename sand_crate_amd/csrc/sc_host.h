@@ -275,7 +275,8 @@ struct NearestSpace {
 };
 
 // sc_pairs_sum_device (sc_fields.h; sc_host_state.h): the flag of the call's own -- a query outside the domain, values
-// with fewer rows than the count has points: the count's flag stays as the count left it.
+// with fewer rows than the count has points: the count's flag stays as the count left it.  sc_pairs_sum_grad_device
+// (sc_fields_grad.h) raises the same flag for the same reasons: every call zeroes it first, on the one stream.
 struct FieldsSpace {
   DevBuf<int> flag;
   int ensure(hipStream_t stream) {

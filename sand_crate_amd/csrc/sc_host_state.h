@@ -1,5 +1,5 @@
 // Host side of the state in the caller's device memory: export and import, pair lists, clusters, nearest-k tables and
-// weighted neighbourhood sums.
+// weighted neighbourhood sums with their position gradient.
 #pragma once
 #include "sc_host.h"
 #include "sc_state.h"
@@ -7,6 +7,7 @@
 #include "sc_clusters.h"
 #include "sc_nearest.h"
 #include "sc_fields.h"
+#include "sc_fields_grad.h"
 
 extern "C" {
 
@@ -307,6 +308,65 @@ int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries,
   else if (channels <= 2) fields_launch<2>(c, g, queries, rows, self, power, channels, values, out);
   else if (channels <= 4) fields_launch<4>(c, g, queries, rows, self, power, channels, values, out);
   else fields_launch<8>(c, g, queries, rows, self, power, channels, values, out);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- the position gradient of the sums (sc_fields_grad.h) -----------------------------------------
+
+}  // extern "C"
+
+template <int C>
+static void fields_grad_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int power, int channels,
+                               const FieldsGradIn& in, double* grad, long long* counts) {
+  hipLaunchKernelGGL(k_fields_grad<C>, dim3(grid_for(rows)), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(),
+                     c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries, (long long)rows, power, channels,
+                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), in, (XY*)grad, counts);
+}
+
+extern "C" {
+
+int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* dev_row_a,
+                             int64_t row_a_rows, const double* dev_part_b, int64_t part_b_rows, int32_t channels,
+                             const double* dev_row_s, const double* dev_part_s, int32_t power, double* dev_grad,
+                             int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_counts) return fail(SC_ERR_ARG, "null counts pointer");
+  if (!dev_grad) return fail(SC_ERR_ARG, "null gradient pointer");
+  if (channels < 0 || channels > SC_FIELDS_MAX_CHANNELS)
+    return fail(SC_ERR_ARG, "%d channels, it must be 0 .. %d", (int)channels, (int)SC_FIELDS_MAX_CHANNELS);
+  if (channels > 0 && (!dev_row_a || !dev_part_b)) return fail(SC_ERR_ARG, "null row_a or part_b pointer with %d channels", (int)channels);
+  if (power < 0 || power > 3) return fail(SC_ERR_ARG, "power is %d, it must be 0 .. 3", (int)power);
+  if (room_rows < 0 || row_a_rows < 0 || part_b_rows < 0) return fail(SC_ERR_ARG, "negative room or number of rows");
+  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
+  if (((uintptr_t)dev_queries | (uintptr_t)dev_grad) & 15) return fail(SC_ERR_ARG, "the queries and the gradient must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_sum_grad_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to sum over: sc_pairs_count_device comes first, and the state must not change in between");
+  if (dev_queries && n_queries > kPairsMaxPoints)
+    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
+  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
+  if (room_rows < rows)
+    return fail(SC_ERR_CAPACITY, "the gradient holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
+                dev_queries ? "queries" : "points");
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = c->fields.ensure(c->stream);
+  if (rc) return rc;
+  PairsGrid g = c->pairs.grid;
+  g.half = 0;  // the gradient runs over the full list, whichever form the count had
+  const XY* queries = (const XY*)dev_queries;
+  const FieldsGradIn in{channels ? dev_row_a : nullptr, channels ? dev_part_b : nullptr, dev_row_s, dev_part_s};
+  long long* counts = (long long*)dev_counts;
+  HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_fields_grad_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
+                     queries, (long long)n_queries, in.row_a || in.row_s ? 1 : 0, (long long)row_a_rows,
+                     in.part_b || in.part_s ? 1 : 0, (long long)part_b_rows, c->pairs.words.get(), c->pairs.flag.get(),
+                     c->fields.flag.get(), counts);
+  if (channels <= 1) fields_grad_launch<1>(c, g, queries, rows, power, channels, in, dev_grad, counts);
+  else if (channels <= 2) fields_grad_launch<2>(c, g, queries, rows, power, channels, in, dev_grad, counts);
+  else if (channels <= 4) fields_grad_launch<4>(c, g, queries, rows, power, channels, in, dev_grad, counts);
+  else fields_grad_launch<8>(c, g, queries, rows, power, channels, in, dev_grad, counts);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -349,6 +349,55 @@ class Engine:
                                               N._P(counts.data_ptr())))
         return counts
 
+    def pairs_sum_grad(self, grad, row_a=None, part_b=None, row_s=None, part_s=None, *, power: int = 3, queries=None,
+                       counts, room: int | None = None, row_rows: int | None = None, part_rows: int | None = None):
+        """The gradient of the weighted sums with respect to positions, over the partners of the last `pairs_count`
+        (sc_pairs_sum_grad_device; the rule is `position_grad` of tests/field_grad_spec.py): `grad`, float64 (R, 2),
+        receives per row ``k * sum_j s_rj * t_rj ** (power - 1) * (dx_rj, dy_rj)``, ``k = -2 * power / radius**2``,
+        ``s_rj = row_s[r] + part_s[j] + row_a[r] . part_b[j]``, added in ascending j.  `row_a`, float64 (A, C), and
+        `row_s`, float64 (A,), belong to the rows; `part_b`, float64 (B, C), and `part_s`, float64 (B,), to the count's
+        points; C is at most 8, `row_a` and `part_b` come together, each of the four may be None.  The rows are the count's
+        points -- a point is never its own partner here -- or with `queries`, a float64 (q, 2) CUDA tensor, those points.
+        `counts`, int64 (2,), receives the row count and the status: 0, -1 when a point or a query lies outside the
+        domain, -2 when the row arrays have fewer rows than there are rows or the partner arrays fewer than the count has
+        points (then nothing else is written).  `room` defaults to R rows, `row_rows` to A, `part_rows` to B.  Enqueued
+        on the context's stream, no synchronisation.  Returns `counts`."""
+        power = int(power)
+        if not 0 <= power <= 3:
+            raise ValueError("power must be 0 .. 3")
+        if (row_a is None) != (part_b is None):
+            raise ValueError("row_a and part_b come together")
+        rows = _state_tensor(grad, "grad", "float64", (2,), self.device)
+        channels, held_a, held_b = 0, None, None
+        if row_a is not None:
+            if row_a.dim() != 2 or not 1 <= row_a.shape[1] <= N.FIELDS_MAX_CHANNELS:
+                raise ValueError(f"row_a must be (rows, C) with C 1 .. {N.FIELDS_MAX_CHANNELS}")
+            channels = int(row_a.shape[1])
+            held_a = _state_tensor(row_a, "row_a", "float64", (channels,), self.device)
+            held_b = _state_tensor(part_b, "part_b", "float64", (channels,), self.device)
+        if row_s is not None:
+            held_a = _state_tensor(row_s, "row_s", "float64", (), self.device, held_a)
+        if part_s is not None:
+            held_b = _state_tensor(part_s, "part_s", "float64", (), self.device, held_b)
+        row_rows = (held_a or 0) if row_rows is None else int(row_rows)
+        part_rows = (held_b or 0) if part_rows is None else int(part_rows)
+        if not 0 <= row_rows <= (held_a or 0):
+            raise ValueError(f"row_rows {row_rows} exceeds the row arrays' {held_a or 0} rows")
+        if not 0 <= part_rows <= (held_b or 0):
+            raise ValueError(f"part_rows {part_rows} exceeds the partner arrays' {held_b or 0} rows")
+        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the gradient's {rows} rows")
+        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
+        # for the self form, or says that an array is absent)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_sum_grad_device(self._ctx, ptr(queries), q, ptr(row_a), row_rows, ptr(part_b), part_rows,
+                                                   channels, ptr(row_s), ptr(part_s), power, ptr(grad), room,
+                                                   N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,
