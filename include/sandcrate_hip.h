@@ -826,6 +826,57 @@ int sc_pairs_sum_grad_device(sc_ctx* ctx, const double* dev_queries /* NULL: the
                              double* dev_grad /* rows x 2 */, int64_t room_rows,
                              int64_t* dev_counts /* [2]: rows, status */);
 
+/* Distance histograms over that graph in DEVICE memory of the caller: how far apart -- per row a table of shell counts,
+ * how many partners lie in each distance band (the radial descriptors of a learned simulator), and the same counts summed
+ * over the rows (the numerator of the radial distribution function g(r)).  tests/hist_spec.py is the rule: edges2[0 ..
+ * bins] are the SQUARED edges, e2[k] = fl(edge_k edge_k), computed once by the caller in float64, strictly ascending,
+ * e2[0] >= 0; j is a partner of row r iff d2 = fl(fl(dx dx) + fl(dy dy)) <= e2[bins], dx = fl(x_r - x_j) -- the
+ * arithmetic of the pair list -- and, in the self form, j != r (there is no flag for the point itself: its distance to
+ * itself is not a distance); a partner is in bin b iff e2[b] <= d2 < e2[b + 1], the last bin closed on top, d2 <=
+ * e2[bins]; a partner with d2 < e2[0] is in no bin; coincident distinct points have d2 = 0 and are in bin 0 iff e2[0] is
+ * 0.  A point with a coordinate that is not finite is nobody's partner; a row whose own point or query is not finite is
+ * all zero.  table[r, b] is the number of partners of row r in bin b, total[b] the sum of table[r, b] over the rows below
+ * the row count: in the self form it counts ordered pairs, each unordered pair twice.  No square root is taken anywhere,
+ * and the result is a pure function of the points, the queries and the edges.
+ *
+ * sc_pairs_hist_device  counts over the grid of the last sc_pairs_count_device of this context, in either form and with
+ *     any flags (SC_PAIRS_HALF is ignored): it reads the workspace that count left, never the count's caller's points,
+ *     and leaves it as it is -- fills, labels, tables, sums and further histograms may follow.  edges2 is HOST memory,
+ *     bins + 1 entries, read before the call returns; edges2[bins] may be at most the count's fl(radius radius), so that
+ *     one count serves several histograms: partners beyond the last edge are in no bin.  The rows: with dev_queries NULL
+ *     the count's n points themselves, else the n_queries rows of dev_queries (n_queries x 2 interleaved float64,
+ *     aligned to 16 bytes), which need not be points.  Writes -- unless NULL -- dev_table (int32, rows x bins contiguous)
+ *     for every row below the row count, rows from the row count on are left as they were, and dev_total (int64, bins
+ *     entries).  `room_rows`, the room of dev_table in rows, must be at least the bound the count was sized by (self form)
+ *     or n_queries; without a table it is not looked at beyond its sign.  dev_counts[0] = the row count, dev_counts[1] =
+ *     the status: 0 when all is well; -1 after a count that found a point outside the domain fl(|c| / radius) < 2^31 (the
+ *     count's radius), or with a query outside it.  With a status below 0 only dev_counts[1] is written -- neither the
+ *     table nor the totals.  The status comes from a flag of this call's own: the count's verdict, which the fill and the
+ *     label read, stays as the count left it.
+ * It enqueues on the context's stream only, with the rules of sc_pairs_sum_device: nothing synchronises, nothing reaches
+ * the host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches
+ * are not bracketed by the timing events.
+ *     The algorithm: a check pass over the queries, then a thread per row walks the buckets of its nine cells as the
+ * count does -- a histogram is integer counts, the order in which a row's partners are met cannot reach it, so there is
+ * no merge --, places every accepted d2 by a binary search over the squared edges in LDS (exact compares) and adds one
+ * to its own int32 counter in LDS, slot-major.  A workgroup is one wave of 64 rows; three kernels, with a search of 4, 5 or 6
+ * steps for up to 16, 32 or 64 bins, each with 64 lines of counters in LDS (17 KiB: the LDS holds the occupancy at nine
+ * waves on a CU, where the walk was measured fastest).  It writes its block of rows of the table together, consecutive lanes to consecutive
+ * entries, sums its columns over its rows in 64 bits and adds them with one 64-bit integer atomic per non-zero bin to a
+ * context-owned accumulator, which a last small launch copies to dev_total when the status is 0 (csrc/sc_hist.h).  Only
+ * integer atomics: no atomic's order reaches the output, and no workgroup waits for another.  Nothing of the list's size
+ * is written.  scripts/hist_time.py measures it on an MI355X against the list route -- sc_pairs_fill_device with
+ * distances, then torch's bucketize and bincount --: profiles/hist_time.txt has the times.
+ *     SC_ERR_ARG for a null context, null dev_counts, dev_table and dev_total both NULL, bins outside 1 ..
+ * SC_HIST_MAX_BINS, a null or not strictly ascending edges2, a negative or non-finite edges2[0], edges2[bins] above the
+ * count's squared radius, a negative n_queries or room, or misaligned queries.  SC_ERR_STATE and SC_ERR_CAPACITY as for
+ * sc_pairs_sum_device.  All checked before anything is launched: the arrays are then untouched. */
+enum { SC_HIST_MAX_BINS = 64 };
+int sc_pairs_hist_device(sc_ctx* ctx, const double* dev_queries /* NULL: the points themselves */, int64_t n_queries,
+                         const double* edges2 /* HOST, bins + 1 */, int32_t bins,
+                         int32_t* dev_table /* rows x bins, may be NULL */, int64_t* dev_total /* bins, may be NULL */,
+                         int64_t room_rows, int64_t* dev_counts /* [2]: rows, status */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,13 @@ FIELDS_KERNEL_CHANNELS = (1, 2, 4, 8)
 FIELDS_SELF = 1
 FIELDS_BLOCK = 256
 FIELDS_OK, FIELDS_DOMAIN, FIELDS_VALUES_SHORT = 0, -1, -2
+# the distance histograms (csrc/sc_hist.h): the most bins of one call (SC_HIST_MAX_BINS), the rows per workgroup of its
+# kernel (kHistBlock: one wave), the bins its search is made for -- the smallest of HIST_SLOTS that is at least the call's,
+# `hist_slots(bins)`, each a kernel of its own -- and the status values of counts[1]
+HIST_MAX_BINS = 64
+HIST_BLOCK = 64
+HIST_SLOTS = (16, 32, 64)
+HIST_OK, HIST_DOMAIN = 0, -1
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -199,6 +206,7 @@ SIGNATURES = {
                                       _P]),
     "sc_pairs_sum_grad_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, C.c_int32,
                                            _P, C.c_int64, _P]),
+    "sc_pairs_hist_device": (C.c_int, [_P, _P, C.c_int64, _D, C.c_int32, _P, _P, C.c_int64, _P]),
 }
 
 
@@ -239,6 +247,30 @@ def fields_kernel_channels(channels: int) -> int:
     if not 0 <= channels <= FIELDS_MAX_CHANNELS:
         raise ValueError(f"channels must be 0 .. {FIELDS_MAX_CHANNELS}")
     return next(c for c in FIELDS_KERNEL_CHANNELS if channels <= c)
+
+
+def hist_slots(bins: int) -> int:
+    """The bins per row of the search of the histogram kernel that serves a call with `bins` bins (csrc/sc_hist.h)."""
+    if not 1 <= bins <= HIST_MAX_BINS:
+        raise ValueError(f"bins must be 1 .. {HIST_MAX_BINS}")
+    return next(slots for slots in HIST_SLOTS if bins <= slots)
+
+
+def hist_squared_edges(edges) -> np.ndarray:
+    """The squared edges sc_pairs_hist_device takes, from the B + 1 distances `edges` (tests/hist_spec.py): float64,
+    ``e2[k] = edges[k] * edges[k]`` rounded once.  ValueError unless B is 1 .. HIST_MAX_BINS, the edges are finite,
+    ``0 <= edges[0] < edges[1] < ...``, and the squares are still strictly ascending and finite (two edges one ulp apart
+    may square to the same number, tiny ones to 0)."""
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or not 2 <= e.shape[0] <= HIST_MAX_BINS + 1:
+        raise ValueError(f"edges must be a sequence of B + 1 distances, B 1 .. {HIST_MAX_BINS}")
+    if not np.isfinite(e).all() or e[0] < 0 or not (e[1:] > e[:-1]).all():
+        raise ValueError("edges must be finite, not negative and strictly ascending")
+    with np.errstate(over="ignore", under="ignore"):
+        e2 = e * e
+    if not np.isfinite(e2).all() or not (e2[1:] > e2[:-1]).all():
+        raise ValueError("the squares of the edges must be finite and still strictly ascending")
+    return e2
 
 
 _lib = None

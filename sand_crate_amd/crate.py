@@ -497,6 +497,65 @@ class Crate:
         return field_function(self, values, radius, power=power, include_self=include_self, points=points, queries=queries,
                               weight_sums=weight_sums)
 
+    def distance_histogram(self, edges, *, points=None, queries=None, per_row: bool = False, totals: bool = True,
+                           sync: bool = True):
+        """How far apart the particles are: the histogram of the pair distances over the bins `edges` delimits, as torch
+        CUDA tensors on the crate's device, counted on the GPU over the pair search's grid (sc_pairs_count_device at the
+        radius ``edges[-1]``, then sc_pairs_hist_device): ``([table, ]total)`` -- int32 (n, B) with `per_row`, int64 (B,)
+        with `totals`.  `edges` is a host sequence or NumPy array of B + 1 float64 distances, B 1 .. 64, ``0 <= edges[0]
+        < edges[1] < ...`` (`sand_crate_amd.pairs.shell_edges` makes equal-width ones).  ``table[i, b]`` is the number of
+        partners j != i of row i of `state_tensors()` at the same point of the stream with ``edges[b]**2 <= d2 <
+        edges[b + 1]**2``, the last bin closed on top, d2 the separately rounded float64 dx*dx + dy*dy of `pair_tensors`:
+        the squares are compared, no square root is taken (tests/hist_spec.py is the rule).  ``total[b]`` is the sum of
+        the column: it counts ORDERED pairs, each unordered pair twice (`sand_crate_amd.pairs.radial_distribution` turns
+        it into g(r)).  Only integers are added: the same result on every call.  `points`, a float64 (n, 2) CUDA tensor,
+        is searched instead of the state.  With `queries`, a float64 (q, 2) CUDA tensor, the rows are those points
+        instead -- probes, sensors: they need not be particles, a particle one lies on is a partner at distance 0 --
+        and the table has q rows.  A particle or query with a coordinate that is not finite gives and gets nothing.
+
+        The shape is known before anything runs, so nothing synchronises between counting and binning.  `sync=True`
+        synchronises once at the end, reads 16 bytes and returns the table cut to the row count; ValueError when a
+        coordinate of a particle or a query has |c| / edges[-1] >= 2^31.  `sync=False` synchronises nothing: the table
+        comes at capacity rows (n with `points`, q with `queries`) and last the int64 `counts` tensor (rows, status):
+        rows from the row count on are uninitialised, status -1 is the domain error (nothing else was written).  The
+        tensors are written on the library's stream, and the library's stream does not wait for torch's: read them
+        after `synchronize()`, and have `points` and `queries` ready before the call -- or run the crate on torch's
+        stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        import torch
+        if not per_row and not totals:
+            raise ValueError("neither per_row nor totals: nothing to return")
+        e = np.array(edges, dtype=np.float64)
+        bins = len(N.hist_squared_edges(e)) - 1
+        if not e[-1] > 0:  # (never: the edges ascend from 0 or more)
+            raise ValueError("the last edge must be positive")
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(e[-1])
+        bound = eng.capacity if points is None else _point_rows(points)
+        rows = bound if queries is None else _point_rows(queries)
+        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the histogram reads the workspace)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, status)
+        table = torch.empty((rows, bins), dtype=torch.int32, device=dev) if per_row else None
+        total = torch.empty(bins, dtype=torch.int64, device=dev) if totals else None
+        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        count_counts = counts
+        if queries is not None:  # (the count's n stays readable: with queries the table's row count is q)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+        eng.pairs_hist(table, total, edges=e, queries=queries, counts=counts)
+        if not sync:
+            self._hist_temporaries = (offsets, count_counts)  # (held until the next call: the count is still queued)
+            return (*(t for t in (table, total) if t is not None), counts)
+        eng.synchronize()
+        n, status = (int(v) for v in counts.cpu())
+        if status == N.HIST_DOMAIN:
+            raise ValueError(f"distance_histogram: a coordinate of a point or a query lies outside the domain "
+                             f"|c| / radius < 2^31 (radius {radius!r})")
+        if points is None:
+            self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
+        return (() if table is None else (table[:n],)) + (() if total is None else (total,))
+
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
         if name != "MT19937":

@@ -18,6 +18,7 @@
 #include "sc_nearest.h"
 #include "sc_fields.h"
 #include "sc_fields_grad.h"
+#include "sc_hist.h"
 #include "sc_track.h"
 #include "sc_rccl.h"
 #include "sc_render.h"

@@ -285,6 +285,19 @@ struct FieldsSpace {
   }
 };
 
+// sc_pairs_hist_device (sc_hist.h; sc_host_state.h): the accumulator of the totals, kHistMaxBins 64-bit words, and behind
+// it the word that holds the flag of the call's own -- a query outside the domain: the count's flag stays as the count
+// left it.  One buffer, so that one memset prepares both.
+struct HistSpace {
+  DevBuf<long long> words;
+  int ensure(hipStream_t stream) {
+    HIPCHK(words.grow(kHistMaxBins + 1, stream));
+    return SC_OK;
+  }
+  long long* acc() const { return words.get(); }
+  int* flag() const { return (int*)(words.get() + kHistMaxBins); }
+};
+
 // The checkpoint (sc_checkpoint_begin / _finish; sc_host_snapshot.h): device-side snapshot, pinned host copy, and the
 // events that order them on the context's stream and the side stream.
 struct Snapshot {
@@ -413,6 +426,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   ClusterSpace clusters;
   NearestSpace nearest;
   FieldsSpace fields;
+  HistSpace hist;
   Snapshot snap;
   SlabLink link;
 };

@@ -1,5 +1,5 @@
-// Host side of the state in the caller's device memory: export and import, pair lists, clusters, nearest-k tables and
-// weighted neighbourhood sums with their position gradient.
+// Host side of the state in the caller's device memory: export and import, pair lists, clusters, nearest-k tables,
+// weighted neighbourhood sums with their position gradient, and distance histograms.
 #pragma once
 #include "sc_host.h"
 #include "sc_state.h"
@@ -8,6 +8,7 @@
 #include "sc_nearest.h"
 #include "sc_fields.h"
 #include "sc_fields_grad.h"
+#include "sc_hist.h"
 
 extern "C" {
 
@@ -367,6 +368,70 @@ int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_que
   else if (channels <= 2) fields_grad_launch<2>(c, g, queries, rows, power, channels, in, dev_grad, counts);
   else if (channels <= 4) fields_grad_launch<4>(c, g, queries, rows, power, channels, in, dev_grad, counts);
   else fields_grad_launch<8>(c, g, queries, rows, power, channels, in, dev_grad, counts);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+// ---- distance histograms (sc_hist.h) --------------------------------------------------------------
+
+}  // extern "C"
+
+template <int NB>
+static void hist_launch(sc_ctx* c, const PairsGrid& g, const HistEdges& edges, int bins, const XY* queries, int64_t rows,
+                        const HistOut& out) {
+  const int64_t grid = std::max<int64_t>(1, (rows + kHistBlock - 1) / kHistBlock);  // (one at least: it writes the counts)
+  hipLaunchKernelGGL(k_hist<NB>, dim3((unsigned)grid), dim3(kHistBlock), 0, c->stream, g, edges, bins, c->pairs.words.get(),
+                     c->pairs.flag.get(), c->hist.flag(), c->pairs.xy.get(), queries, (long long)rows,
+                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), c->hist.acc(), out);
+}
+
+extern "C" {
+
+int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* edges2, int32_t bins,
+                         int32_t* dev_table, int64_t* dev_total, int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_counts) return fail(SC_ERR_ARG, "null counts pointer");
+  if (!dev_table && !dev_total) return fail(SC_ERR_ARG, "neither a table nor totals to write");
+  if (bins < 1 || bins > SC_HIST_MAX_BINS) return fail(SC_ERR_ARG, "%d bins, it must be 1 .. %d", (int)bins, (int)SC_HIST_MAX_BINS);
+  if (!edges2) return fail(SC_ERR_ARG, "null edges pointer");
+  if (!(edges2[0] >= 0) || !std::isfinite(edges2[0])) return fail(SC_ERR_ARG, "the first squared edge must be finite and not negative");
+  for (int k = 0; k < bins; ++k)
+    if (!(edges2[k] < edges2[k + 1])) return fail(SC_ERR_ARG, "the squared edges must be strictly ascending (edge %d is not)", k + 1);
+  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
+  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
+  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_hist_device inside a tick");
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to take a histogram of: sc_pairs_count_device comes first, and the state must not change in between");
+  if (!(edges2[bins] <= c->pairs.grid.r2))
+    return fail(SC_ERR_ARG, "the last squared edge %.17g lies beyond the count's squared radius %.17g", edges2[bins], c->pairs.grid.r2);
+  if (dev_queries && n_queries > kPairsMaxPoints)
+    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
+  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
+  if (dev_table && room_rows < rows)
+    return fail(SC_ERR_CAPACITY, "the table holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
+                dev_queries ? "queries" : "points");
+  HIPCHK(hipSetDevice(c->device));
+  static_assert(kHistMaxBins == SC_HIST_MAX_BINS, "the header's bound is the kernel's");
+  const int rc = c->hist.ensure(c->stream);
+  if (rc) return rc;
+  PairsGrid g = c->pairs.grid;
+  g.half = 0;           // the histogram runs over the full list, whichever form the count had
+  g.r2 = edges2[bins];  // ... up to its own last edge: the cells are the count's, which are no smaller
+  HistEdges edges{};
+  std::copy(edges2, edges2 + bins + 1, edges.e2);
+  const XY* queries = (const XY*)dev_queries;
+  const HistOut out{(int*)dev_table, (long long*)dev_total, (long long*)dev_counts};
+  HIPCHK(hipMemsetAsync(c->hist.words, 0, (kHistMaxBins + 1) * sizeof(long long), c->stream));  // the accumulator and the flag
+  hipLaunchKernelGGL(k_hist_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, c->pairs.grid.radius,
+                     queries, (long long)n_queries, c->pairs.flag.get(), c->hist.flag(), out.counts);
+  if (bins <= kHistFewBins) hist_launch<kHistFewBins>(c, g, edges, bins, queries, rows, out);
+  else if (bins <= kHistMidBins) hist_launch<kHistMidBins>(c, g, edges, bins, queries, rows, out);
+  else hist_launch<kHistMaxBins>(c, g, edges, bins, queries, rows, out);
+  if (dev_total)
+    hipLaunchKernelGGL(k_hist_finish, dim3(1), dim3(kHistBlock), 0, c->stream, (int)bins, c->pairs.flag.get(), c->hist.flag(),
+                       c->hist.acc(), out.total);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

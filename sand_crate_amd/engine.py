@@ -398,6 +398,37 @@ class Engine:
                                                    N._P(counts.data_ptr())))
         return counts
 
+    def pairs_hist(self, table=None, total=None, *, edges, queries=None, counts, room: int | None = None):
+        """The distance histogram over the partners of the last `pairs_count`, whichever `half` it had
+        (sc_pairs_hist_device; the rule is tests/hist_spec.py): `table`, int32 (R, B) or None, receives per row the number
+        of partners in each of the B bins, `total`, int64 (B,) or None, their sums over the rows -- in the self form
+        ordered pairs, each unordered pair twice.  `edges` is a host sequence of B + 1 distances, B 1 .. 64, ``0 <=
+        edges[0] < edges[1] < ...``, squared here in float64 (`_native.hist_squared_edges`); a partner at squared
+        distance d2 is in bin b iff ``edges[b]**2 <= d2 < edges[b + 1]**2``, the last bin closed on top, and
+        ``edges[-1]`` may be at most the count's radius.  The rows are the count's points -- a point is never its own
+        partner -- or with `queries`, a float64 (q, 2) CUDA tensor, those points of any kind.  `counts`, int64 (2,),
+        receives the row count and the status: 0, or -1 when a point or a query lies outside the domain (then nothing
+        else is written).  `room` defaults to R rows (0 without a table).  Enqueued on the context's stream, no
+        synchronisation.  Returns `counts`."""
+        e2 = N.hist_squared_edges(edges)
+        bins = len(e2) - 1
+        if table is None and total is None:
+            raise ValueError("neither table nor total to write")
+        rows = 0 if table is None else _state_tensor(table, "table", "int32", (bins,), self.device)
+        if total is not None:
+            _state_tensor(total, "total", "int64", (), self.device, bins)
+        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room = rows if room is None else int(room)
+        if room > rows:
+            raise ValueError(f"room {room} exceeds the table's {rows} rows")
+        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
+        # for the self form, or says that an output is absent)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_hist_device(self._ctx, ptr(queries), q, N.dptr(e2), bins, ptr(table), ptr(total), room,
+                                               N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

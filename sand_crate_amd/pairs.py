@@ -1,6 +1,7 @@
 """Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
-`Crate.cluster_tensors` (labels, sizes), for the nearest-k tables of `Crate.neighbor_tensors` (neighbors) and for the
-weighted sums of `Crate.field_tensors` (sums, wsum)."""
+`Crate.cluster_tensors` (labels, sizes), for the nearest-k tables of `Crate.neighbor_tensors` (neighbors), for the
+weighted sums of `Crate.field_tensors` (sums, wsum) and for the distance histograms of `Crate.distance_histogram`
+(edges, total)."""
 from __future__ import annotations
 
 
@@ -55,6 +56,35 @@ def normalized(sums, wsum):
     import torch
     w = wsum if sums.dim() == 1 else wsum.unsqueeze(1)
     return torch.where(w == 0, torch.zeros_like(sums), sums / w)
+
+
+def shell_edges(radius, bins, inner=0.0):
+    """B + 1 equal-width edges from `inner` to `radius` as a float64 NumPy array, for `Crate.distance_histogram`:
+    ``edges[k] = inner + k * (radius - inner) / bins``, the last exactly `radius`."""
+    import numpy as np
+    bins = int(bins)
+    radius, inner = float(radius), float(inner)
+    if bins < 1 or not 0.0 <= inner < radius < float("inf"):
+        raise ValueError("bins must be at least 1 and 0 <= inner < radius, both finite")
+    edges = inner + np.arange(bins + 1, dtype=np.float64) * ((radius - inner) / bins)
+    edges[-1] = radius
+    return edges
+
+
+def radial_distribution(total, edges, n, area):
+    """The radial distribution function g(r) of `Crate.distance_histogram`'s totals, one value per bin, as a float64
+    torch tensor: ``g[b] = total[b] / (n * (n / area) * pi * (edges[b + 1]**2 - edges[b]**2))`` -- the partners counted
+    in the shell over the partners an ideal gas of the same density, n particles on `area`, would have there.  `total`
+    counts ORDERED pairs, each unordered pair twice, as the self form of the histogram does: every one of the n
+    particles looks around.  Edge effects are not corrected: particles near the boundary of `area` see fewer partners."""
+    import math
+
+    import torch
+    e = torch.as_tensor(edges, dtype=torch.float64, device=total.device)
+    if e.dim() != 1 or e.shape[0] != total.shape[0] + 1:
+        raise ValueError("edges must have one entry more than total")
+    shell = math.pi * (e[1:] ** 2 - e[:-1] ** 2)
+    return total.to(torch.float64) / (float(n) * (float(n) / float(area)) * shell)
 
 
 def grid_queries(x0, x1, y0, y1, nx, ny, device=None):
