@@ -646,6 +646,33 @@ int sc_pairs_count_device(sc_ctx* ctx, const double* dev_xy /* NULL: the state *
                           int64_t* dev_offsets, int64_t room_rows, int64_t* dev_counts /* [2]: n, E */);
 int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* may be NULL */, int64_t room_pairs);
 
+/* Batched point clouds: many disjoint clouds -- the frames of a minibatch -- in one count, one grid and one launch of every
+ * reader.  dev_ptr holds clouds + 1 ascending int64 offsets in DEVICE memory, ptr[0] = 0 and ptr[clouds] = n; cloud b is the
+ * rows ptr[b] .. ptr[b + 1] of the points and may be empty.  j is a partner of row i iff both lie in one cloud and the
+ * rule of the call accepts them: indices stay global, the orders are the orders of the unbatched calls, and every result
+ * equals, bit for bit, the per-cloud results concatenated with the partner indices shifted by ptr[b] (tests/batch_spec.py).
+ * The clouds may overlap in space completely: they share the one grid, the cloud is mixed into the bucket hash, and a
+ * candidate counts only when its index lies in the row's [ptr[b], ptr[b + 1]) -- the hash is for speed, the range for
+ * exactness (csrc/sc_pairs.h).
+ *
+ * sc_pairs_set_batch_device  applies to the NEXT sc_pairs_count_device of this context and is consumed by it, whatever
+ *     that call returns; the count must have the caller's points (dev_xy NULL with a batch pending: SC_ERR_ARG).  The
+ *     count copies dev_ptr into the workspace on the context's stream -- it must be ready then, as the points must --
+ *     and the readers never read it again.  clouds = 0 or dev_ptr NULL clears a pending batch.  The grid the count
+ *     leaves is batched, which the context knows on the host: sc_pairs_fill_device, sc_pairs_nearest_device,
+ *     sc_pairs_sum_device and sc_pairs_sum_grad_device read it as such.  sc_pairs_label_device and sc_pairs_hist_device
+ *     are NOT batched yet: on a batched grid they return SC_ERR_ARG and write nothing.
+ * sc_pairs_set_query_batch_device  with queries a second array, dev_query_ptr, also clouds + 1 entries ending at
+ *     n_queries: query rows query_ptr[b] .. query_ptr[b + 1] see the points of cloud b only; a cloud may have points and
+ *     no queries, or queries and no points (rows without partners).  Applies to the next query-form reader of the batched
+ *     grid and is consumed by it; it is read by that reader's launches only.  SC_ERR_ARG when the last count left no
+ *     batched grid; a query-form reader on a batched grid without it returns SC_ERR_ARG; NULL clears.
+ * Offsets that do not start at 0, that descend, or that do not end at n (n_queries) are found on the device, no host
+ * round trip: dev_counts[1] = -3 -- next to -1, the domain, and -2, short arrays -- and nothing else is written, by the
+ * count, the fill or any reader.  SC_ERR_ARG for a null context or negative clouds, SC_ERR_CAPACITY for more than 2^28. */
+int sc_pairs_set_batch_device(sc_ctx* ctx, const int64_t* dev_ptr, int64_t clouds);
+int sc_pairs_set_query_batch_device(sc_ctx* ctx, const int64_t* dev_query_ptr);
+
 /* The clusters of that graph in DEVICE memory of the caller: what hangs together.  tests/cluster_spec.py is the rule: a
  * cluster is a connected component of the graph above -- i ~ j iff (i, j) is a pair of the full list, whether or not the
  * count had SC_PAIRS_HALF -- over the points whose coordinates are all finite; a point with a coordinate that is not finite

@@ -30,10 +30,13 @@ STATE_TILE, STATE_SCAN_BLOCK, STATE_GATHER_BLOCK = 256, 2048, 256
 # (kBlock), keys per workgroup of a pass of the binning sort (kRadixTile, the same sort), entries per workgroup of the scans
 # (kScanPerBlock); the hashed table has the smallest power of two of buckets that is at least PAIRS_LOAD per point and
 # PAIRS_MIN_BUCKETS, a cell (cx, cy) -- floor(x / h), floor(y / h) as 32-bit words, h = radius * PAIRS_CELL_FACTOR -- lies in
-# bucket `pairs_bucket(cx, cy, buckets)`
+# bucket `pairs_bucket(cx, cy, buckets)`; in the batched form (sc_pairs_set_batch_device) the cloud is a third factor of the
+# hash, `pairs_bucket(cx, cy, buckets, cloud)`, and PAIRS_BATCH is the status of offsets that are not in order
 PAIRS_BLOCK, PAIRS_SORT_TILE, PAIRS_SCAN_BLOCK = 256, 256, 2048
 PAIRS_LOAD, PAIRS_MIN_BUCKETS = 2, 256
 PAIRS_HASH_X, PAIRS_HASH_Y, PAIRS_HASH_MIX = 0x9E3779B1, 0x85EBCA77, 0x2C1B3C6D
+PAIRS_HASH_CLOUD = 0xC2B2AE3D
+PAIRS_DOMAIN, PAIRS_BATCH = -1, -3
 PAIRS_CELL_FACTOR = 1.0 + 2.0 ** -20
 PAIRS_HALF = 1
 # the nearest-k table (csrc/sc_nearest.h): the largest k (SC_NEAREST_MAX_K), the rows per workgroup of its kernel
@@ -200,6 +203,8 @@ SIGNATURES = {
     "sc_import_state_device": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
     "sc_pairs_count_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32, _P, C.c_int64, _P]),
     "sc_pairs_fill_device": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "sc_pairs_set_batch_device": (C.c_int, [_P, _P, C.c_int64]),
+    "sc_pairs_set_query_batch_device": (C.c_int, [_P, _P]),
     "sc_pairs_label_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "sc_pairs_nearest_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "sc_pairs_sum_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
@@ -218,10 +223,11 @@ def pairs_buckets(bound: int) -> int:
     return t
 
 
-def pairs_bucket(cx: int, cy: int, buckets: int) -> int:
-    """The bucket of cell (cx, cy) in a table of `buckets` buckets (csrc/sc_pairs.h: pairs_bucket), in 32-bit arithmetic."""
+def pairs_bucket(cx: int, cy: int, buckets: int, cloud: int = 0) -> int:
+    """The bucket of cell (cx, cy) -- of cloud `cloud` in the batched form -- in a table of `buckets` buckets
+    (csrc/sc_pairs.h: pairs_bucket), in 32-bit arithmetic.  Cloud 0 hashes as an unbatched cell does."""
     m = 0xFFFFFFFF
-    v = (((cx & m) * PAIRS_HASH_X) & m) ^ (((cy & m) * PAIRS_HASH_Y) & m)
+    v = (((cx & m) * PAIRS_HASH_X) & m) ^ (((cy & m) * PAIRS_HASH_Y) & m) ^ (((cloud & m) * PAIRS_HASH_CLOUD) & m)
     v ^= v >> 15
     v = (v * PAIRS_HASH_MIX) & m
     v ^= v >> 13

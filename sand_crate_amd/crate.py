@@ -38,6 +38,7 @@ There is no CPU implementation behind this class: without libsandcrate_hip.so an
 from __future__ import annotations
 
 import copy
+import functools
 import json
 import time
 
@@ -101,7 +102,45 @@ def _point_rows(points) -> int:
     return int(points.shape[0]) if getattr(points, "is_cuda", False) and len(points.shape) == 2 else 0
 
 
+_BATCH_ORDER = "batch offsets must start at 0, not descend and end at the number of points"
+
+
+def _check_batch(who: str, device: int, points, queries, batch, query_batch) -> None:
+    """The `batch=` / `query_batch=` arguments of a neighbourhood call: ValueError before anything is enqueued."""
+    from .engine import _batch_tensor
+    if batch is None:
+        if query_batch is not None:
+            raise ValueError(f"{who}: query_batch without batch")
+        return
+    if points is None:
+        raise ValueError(f"{who}: batch needs points, the state is one cloud")
+    entries = _batch_tensor(batch, "batch", device)
+    if queries is None:
+        if query_batch is not None:
+            raise ValueError(f"{who}: query_batch without queries")
+    elif query_batch is None:
+        raise ValueError(f"{who}: queries of a batched call need query_batch, their clouds")
+    else:
+        _batch_tensor(query_batch, "query_batch", device, entries)
+
+
+def _batch_keywords(method):
+    """`batch=` and `query_batch=` for a method whose own parameter list stays as it is (`neighbor_tensors`: its list is
+    part of the tested surface): the two keywords are taken here and wait in `self._batch_args` for the method, which
+    reads them; `inspect.signature` shows the method's own list."""
+    @functools.wraps(method)
+    def call(self, *args, batch=None, query_batch=None, **kw):
+        self._batch_args = (batch, query_batch)
+        try:
+            return method(self, *args, **kw)
+        finally:
+            self._batch_args = (None, None)
+    return call
+
+
 class Crate:
+    _batch_args = (None, None)
+
     def __init__(self, world_config: WorldConfig, *, device: int = 0, noise: str = "host", noise_seed: int = 0,
                  capacity: int | None = None) -> None:
         if noise not in _NOISE_MODES:
@@ -251,7 +290,7 @@ class Crate:
         self._count, self._count_known = int(particles.shape[0]), True
 
     def pair_tensors(self, radius: float | None = None, *, points=None, half: bool = False, squared_distances: bool = False,
-                     max_pairs: int | None = None):
+                     max_pairs: int | None = None, batch=None):
         """Which particles lie within `radius` (default: `diameter`) of which, as a CSR edge list in torch CUDA tensors on
         the crate's device, searched on the GPU (sc_pairs_count_device / sc_pairs_fill_device): ``(offsets, partners[, d2])``
         -- int64 (n + 1,), int64 (E,), float64 (E,).  Row i's partners are ``partners[offsets[i]:offsets[i + 1]]``, ascending;
@@ -268,21 +307,31 @@ class Crate:
         the list was clipped at K entries, E = -1 is the domain error (nothing else was written).  The tensors are written
         on the library's stream, and the library's stream does not wait for torch's: read them after `synchronize()`, and
         have `points` ready before the call -- or run the crate on torch's stream, `engine.set_stream`, and everything
-        torch enqueues afterwards sees them."""
+        torch enqueues afterwards sees them.
+
+        `batch`, an int64 CUDA tensor of B + 1 ascending offsets from 0 to n (`sand_crate_amd.pairs.batch_ptr` makes one
+        from the clouds' sizes), makes `points` B disjoint clouds in one call -- the frames of a minibatch, which may
+        overlap in space completely: cloud b is ``points[batch[b]:batch[b + 1]]``, a pair never crosses clouds, indices are
+        global, and the result is, bit for bit, the per-cloud results concatenated with the partners shifted by
+        ``batch[b]`` (tests/batch_spec.py).  Offsets that are not in order raise ValueError at the synchronisation
+        (E = -3 with `max_pairs`)."""
         import torch
         eng = self._engine
         dev = torch.device("cuda", eng.device)
         radius = float(self.diameter if radius is None else radius)
+        _check_batch("pair_tensors", eng.device, points, None, batch, None)
         rows = eng.capacity if points is None else _point_rows(points)
         offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         sync = max_pairs is None
         if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
             torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=half)
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=half, batch=batch)
         if sync:
             eng.synchronize()
             n, total = (int(v) for v in counts.cpu())
+            if total == N.PAIRS_BATCH:
+                raise ValueError(f"pair_tensors: {_BATCH_ORDER}")
             if total < 0:
                 raise ValueError(f"pair_tensors: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
             if points is None:
@@ -346,6 +395,7 @@ class Crate:
             self._count, self._count_known = n, True
         return labels[:n], sizes[:total], roots[:total]
 
+    @_batch_keywords
     def neighbor_tensors(self, k: int, radius: float | None = None, *, points=None, queries=None,
                          squared_distances: bool = False, partner_counts: bool = False, sync: bool = True):
         """The k nearest particles within `radius` (default: `diameter`) of every particle, as a table of fixed shape in
@@ -367,7 +417,13 @@ class Crate:
         row count on are uninitialised, cut is the number of rows that had more than k partners, cut = -1 is the domain
         error (nothing else was written).  The tensors are written on the library's stream, and the library's stream does
         not wait for torch's: read them after `synchronize()`, and have `points` and `queries` ready before the call -- or
-        run the crate on torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        run the crate on torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them.
+
+        `batch=` (a keyword of the wrapper around this method, `_batch_keywords`, as is `query_batch=`) makes `points` B
+        disjoint clouds in one call, as in `pair_tensors`; with `queries` comes `query_batch`,
+        also B + 1 offsets, from 0 to q: query rows ``query_batch[b]:query_batch[b + 1]`` see only the points of cloud b
+        (a cloud may have points and no queries, or queries and no points).  Offsets that are not in order raise
+        ValueError at the synchronisation (cut = -3 with `sync=False`)."""
         import torch
         k = int(k)
         if not 1 <= k <= N.NEAREST_MAX_K:
@@ -375,6 +431,8 @@ class Crate:
         eng = self._engine
         dev = torch.device("cuda", eng.device)
         radius = float(self.diameter if radius is None else radius)
+        batch, query_batch = self._batch_args
+        _check_batch("neighbor_tensors", eng.device, points, queries, batch, query_batch)
         bound = eng.capacity if points is None else _point_rows(points)
         rows = bound if queries is None else _point_rows(queries)
         offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the table reads the workspace)
@@ -385,16 +443,20 @@ class Crate:
         out = tuple(t for t in (neighbors, d2, partners) if t is not None)
         if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
             torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True, batch=batch)
         count_counts = counts
         if queries is not None:  # (the count's n stays readable: with queries the table's row count is q)
             counts = torch.empty(2, dtype=torch.int64, device=dev)
+        if query_batch is not None:
+            eng.pairs_set_query_batch(query_batch)
         eng.pairs_nearest(neighbors, d2, partners, k=k, queries=queries, counts=counts)
         if not sync:
             self._neighbor_temporaries = (offsets, count_counts)  # (held until the next call: the count is still queued)
             return (*out, counts)
         eng.synchronize()
         n, cut = (int(v) for v in counts.cpu())
+        if cut == N.PAIRS_BATCH:
+            raise ValueError(f"neighbor_tensors: {_BATCH_ORDER} (of queries for query_batch)")
         if cut < 0:
             raise ValueError(f"neighbor_tensors: a coordinate of a point or a query lies outside the domain "
                              f"|c| / radius < 2^31 (radius {radius!r})")
@@ -403,7 +465,7 @@ class Crate:
         return tuple(t[:n] for t in out)
 
     def field_tensors(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
-                      points=None, queries=None, weight_sums: bool = False, sync: bool = True):
+                      points=None, queries=None, weight_sums: bool = False, sync: bool = True, batch=None, query_batch=None):
         """What is there within `radius` (default: `diameter`) of every particle: the weighted sums of an SPH
         interpolation, as torch CUDA tensors on the crate's device, summed on the GPU over the pair search's grid
         (sc_pairs_count_device, then sc_pairs_sum_device): ``(sums[, wsum])`` -- float64 (n, C) and (n,).
@@ -430,7 +492,11 @@ class Crate:
         `values`, `points` and `queries` ready before the call -- or run the crate on torch's stream, `engine.set_stream`,
         and everything torch enqueues afterwards sees them.  What the wrapper itself asks of torch -- the contiguous copy,
         the split into eights of more than 8 columns and their concatenation -- runs on torch's stream: with `sync=False`
-        those need the crate on torch's stream."""
+        those need the crate on torch's stream.
+
+        `batch` and `query_batch` make `points` (and `queries`) B disjoint clouds in one call, as in `neighbor_tensors`:
+        the rows of `values` are global, a sum never crosses clouds.  Offsets that are not in order raise ValueError at the
+        synchronisation (status -3 with `sync=False`)."""
         import torch
         eng = self._engine
         dev = torch.device("cuda", eng.device)
@@ -438,6 +504,7 @@ class Crate:
         power = int(power)
         if not 0 <= power <= 3:
             raise ValueError("power must be 0 .. 3")
+        _check_batch("field_tensors", eng.device, points, queries, batch, query_batch)
         flat = False
         if values is not None:
             if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
@@ -458,18 +525,20 @@ class Crate:
         parts = [None if v is None else torch.empty((rows, v.shape[1]), dtype=torch.float64, device=dev) for v in chunks]
         if sync:  # (what torch was asked for above is done, and nothing of torch's touches the new tensors)
             torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True, batch=batch)
         count_counts = counts
         if queries is not None:  # (the count's n stays readable: with queries the sums' row count is q)
             counts = torch.empty(2, dtype=torch.int64, device=dev)
-        for at, (v, part) in enumerate(zip(chunks, parts)):
+        for at, (v, part) in enumerate(zip(chunks, parts)):  # (every launch consumes the query offsets: given each time)
             eng.pairs_sum(v, part, wsum if at == 0 else None, power=power, include_self=include_self, queries=queries,
-                          counts=counts)
+                          counts=counts, query_batch=query_batch)
         if not sync:
             self._field_temporaries = (offsets, count_counts, chunks, parts)  # (held until the next call: still queued)
         else:
             eng.synchronize()
             n, status = (int(v) for v in counts.cpu())
+            if status == N.PAIRS_BATCH:
+                raise ValueError(f"field_tensors: {_BATCH_ORDER} (of queries for query_batch)")
             if status == N.FIELDS_DOMAIN:
                 raise ValueError(f"field_tensors: a coordinate of a point or a query lies outside the domain "
                                  f"|c| / radius < 2^31 (radius {radius!r})")
@@ -486,16 +555,17 @@ class Crate:
         return (*out, counts) if not sync else tuple(t[:n] for t in out)
 
     def field_function(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
-                       points=None, queries=None, weight_sums: bool = False):
+                       points=None, queries=None, weight_sums: bool = False, batch=None, query_batch=None):
         """`field_tensors(..., sync=True)` under torch autograd: the same arguments, the same results bit for bit, attached
         to the graph when `values`, `points` or `queries` requires grad -- `backward()` then gives their gradients from
         the same grid kernels (sc_pairs_sum_device with rows and partners swapped for the values,
         sc_pairs_sum_grad_device for the positions; tests/field_grad_spec.py is the rule).  When nothing requires grad it
         is `field_tensors` and nothing more.  Once differentiable; no gradient with respect to `radius`, no `sync=False`
-        form: `sand_crate_amd.fields.field_function` has the details."""
+        form; `batch` and `query_batch` as in `field_tensors`, and the backward passes them on:
+        `sand_crate_amd.fields.field_function` has the details."""
         from .fields import field_function
         return field_function(self, values, radius, power=power, include_self=include_self, points=points, queries=queries,
-                              weight_sums=weight_sums)
+                              weight_sums=weight_sums, batch=batch, query_batch=query_batch)
 
     def distance_histogram(self, edges, *, points=None, queries=None, per_row: bool = False, totals: bool = True,
                            sync: bool = True):

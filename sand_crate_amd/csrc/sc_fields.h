@@ -33,13 +33,23 @@
 // walk reads; a write-out through LDS as in k_nearest was not built.  No barrier, so a thread with nothing to do returns.
 // No floating-point atomics, no atomic's order reaches the output (the flag is an OR), no workgroup waits for another.
 // With either flag up only counts[1] is written: -1 for the domain (the count's flag or a query), else -2 for the values.
+//
+// On a batched grid (sc_pairs.h) the kernels are the `batched` instantiations: a row carries its record (lo, hi, cloud), a
+// query finds its cloud by binary search over query_ptr, which k_fields_check tests as the count tested ptr (bit 2 of the
+// sum's flag); bad offsets, the count's or the queries', give counts[1] = -3 before anything else.  No LDS is added.
 #pragma once
 #include "sc_pairs.h"
 
 namespace sc {
 
 constexpr int kFieldsMaxChannels = 8;
-constexpr int kFieldsFlagDomain = 1, kFieldsFlagValues = 2;
+constexpr int kFieldsFlagDomain = 1, kFieldsFlagValues = 2, kFieldsFlagBatch = 4;
+
+// counts[1] with a flag up: `flag` the count's, `own` the call's.
+__device__ __forceinline__ long long fields_status(int flag, int own) {
+  if ((flag & kPairsFlagBatch) || (own & kFieldsFlagBatch)) return kPairsStatusBatch;
+  return flag || (own & kFieldsFlagDomain) ? kPairsStatusDomain : -2;
+}
 
 struct FieldsOut {
   double* sums;       // rows x channels, or null (channels 0)
@@ -47,14 +57,17 @@ struct FieldsOut {
   long long* counts;  // [2]: rows, status
 };
 
-// `queries` null: the self form, no point to test.  `values` null: no values to be short of.
+// `queries` null: the self form, no point to test.  `values` null: no values to be short of.  `qptr`: the query offsets of
+// a batched grid, or null; the launch covers its clouds + 1 entries.
 __global__ void __launch_bounds__(kBlock)
     k_fields_check(double radius, const XY* __restrict__ queries, long long n_queries, const double* __restrict__ values,
                    long long values_rows, const long long* __restrict__ words, const int* __restrict__ flag,
-                   int* __restrict__ own_flag, long long* __restrict__ counts) {
+                   int* __restrict__ own_flag, long long* __restrict__ counts, const long long* __restrict__ qptr,
+                   int clouds) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kFieldsFlagBatch);
   if (i == 0) {
-    counts[1] = *flag ? -1 : 0;
+    counts[1] = *flag ? pairs_status(*flag) : 0;
     if (values && values_rows < words[PW_N]) atomicOr(own_flag, kFieldsFlagValues);
   }
   if (!queries || i >= n_queries) return;
@@ -76,13 +89,13 @@ __device__ __forceinline__ double fields_weight(int power, double d2, double r2)
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]); otherwise row i is queries[i] (n_queries rows).
 // `self`: 1 when a point is a partner of its own row (always so for a query that lies on a point).  `values` null: the
 // weight sums only.
-template <int C>
+template <int C, bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_fields_sum(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag,
                  const int* __restrict__ own_flag, const XY* __restrict__ xy, const XY* __restrict__ queries,
                  long long n_queries, int self, int power, int channels, const int* __restrict__ start,
                  const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx,
-                 const double* __restrict__ values, FieldsOut out) {
+                 const double* __restrict__ values, FieldsOut out, PairsBatch bt) {
   __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
   const int tid = (int)threadIdx.x;
   const long long i = (long long)blockIdx.x * blockDim.x + tid;
@@ -90,7 +103,7 @@ __global__ void __launch_bounds__(kBlock)
   const bool up = *flag || own;
   const long long rows = queries ? n_queries : words[PW_N];
   if (i == 0) {
-    if (up) out.counts[1] = *flag || (own & kFieldsFlagDomain) ? -1 : -2;
+    if (up) out.counts[1] = fields_status(*flag, own);
     else out.counts[0] = rows;
   }
   if (up || i >= rows) return;  // (no barrier below: every thread is on its own)
@@ -101,12 +114,13 @@ __global__ void __launch_bounds__(kBlock)
   const XY p = queries ? queries[i] : xy[i];
   if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
     const int me = queries || self ? -1 : (int)i;  // (no j is -1)
+    const PairsRow row = pairs_row<batched>(bt, i);
     const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
     for (int c = 0; c < 9; ++c) {
       const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-      const unsigned b = pairs_bucket(cx, cy, g.mask);
+      const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
       const int end = start[b + 1];
-      const int k = pairs_advance(g, me, p, cx, cy, start[b], end, sxy, scell, sidx);
+      const int k = pairs_advance<batched>(g, row, me, p, cx, cy, start[b], end, sxy, scell, sidx);
       s_cur[c][tid] = k;
       s_end[c][tid] = end;
       s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
@@ -137,7 +151,7 @@ __global__ void __launch_bounds__(kBlock)
       }
       const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
       const int end = s_end[bc][tid];
-      const int next = pairs_advance(g, me, p, cx, cy, k + 1, end, sxy, scell, sidx);
+      const int next = pairs_advance<batched>(g, row, me, p, cx, cy, k + 1, end, sxy, scell, sidx);
       s_cur[bc][tid] = next;
       s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
     }

@@ -29,6 +29,8 @@
 // No barrier, no scratch, no floating-point atomics, no atomic's order reaches the output (the flag is an OR), nothing of
 // the workspace is written.  No j at or beyond part_rows and no row at or beyond row_rows is ever read: with fewer the
 // flag is up and no thread walks.  With either flag up only counts[1] is written: -1 for the domain, else -2.
+// On a batched grid the kernels are the `batched` instantiations, as in sc_fields.h: the row's record, query_ptr tested by
+// the check, -3 for bad offsets, the same 27 KiB of LDS.
 #pragma once
 #include "sc_fields.h"
 
@@ -42,13 +44,16 @@ struct FieldsGradIn {
 };
 
 // `queries` null: the self form, no point to test.  `row_rows` counts row_a and row_s, `part_rows` part_b and part_s.
+// `qptr`: the query offsets of a batched grid, or null; the launch covers its clouds + 1 entries.
 __global__ void __launch_bounds__(kBlock)
     k_fields_grad_check(double radius, const XY* __restrict__ queries, long long n_queries, int has_row, long long row_rows,
                         int has_part, long long part_rows, const long long* __restrict__ words,
-                        const int* __restrict__ flag, int* __restrict__ own_flag, long long* __restrict__ counts) {
+                        const int* __restrict__ flag, int* __restrict__ own_flag, long long* __restrict__ counts,
+                        const long long* __restrict__ qptr, int clouds) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kFieldsFlagBatch);
   if (i == 0) {
-    counts[1] = *flag ? -1 : 0;
+    counts[1] = *flag ? pairs_status(*flag) : 0;
     const long long n = words[PW_N];
     if ((has_row && row_rows < (queries ? n_queries : n)) || (has_part && part_rows < n)) atomicOr(own_flag, kFieldsFlagValues);
   }
@@ -61,13 +66,13 @@ __global__ void __launch_bounds__(kBlock)
 
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]) and never its own partner; otherwise row i is
 // queries[i] (n_queries rows).  `grad`: rows x 2, aligned to 16 bytes.
-template <int C>
+template <int C, bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_fields_grad(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag,
                   const int* __restrict__ own_flag, const XY* __restrict__ xy, const XY* __restrict__ queries,
                   long long n_queries, int power, int channels, const int* __restrict__ start,
                   const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx, FieldsGradIn in,
-                  XY* __restrict__ grad, long long* __restrict__ counts) {
+                  XY* __restrict__ grad, long long* __restrict__ counts, PairsBatch bt) {
   __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
   const int tid = (int)threadIdx.x;
   const long long i = (long long)blockIdx.x * blockDim.x + tid;
@@ -75,7 +80,7 @@ __global__ void __launch_bounds__(kBlock)
   const bool up = *flag || own;
   const long long rows = queries ? n_queries : words[PW_N];
   if (i == 0) {
-    if (up) counts[1] = *flag || (own & kFieldsFlagDomain) ? -1 : -2;
+    if (up) counts[1] = fields_status(*flag, own);
     else counts[0] = rows;
   }
   if (up || i >= rows) return;  // (no barrier below: every thread is on its own)
@@ -92,12 +97,13 @@ __global__ void __launch_bounds__(kBlock)
     double s_row = 0.0;
     if (in.row_s) s_row += in.row_s[i];
     const int me = queries ? -1 : (int)i;  // (no j is -1)
+    const PairsRow row = pairs_row<batched>(bt, i);
     const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
     for (int c = 0; c < 9; ++c) {
       const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-      const unsigned b = pairs_bucket(cx, cy, g.mask);
+      const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
       const int end = start[b + 1];
-      const int k = pairs_advance(g, me, p, cx, cy, start[b], end, sxy, scell, sidx);
+      const int k = pairs_advance<batched>(g, row, me, p, cx, cy, start[b], end, sxy, scell, sidx);
       s_cur[c][tid] = k;
       s_end[c][tid] = end;
       s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
@@ -134,7 +140,7 @@ __global__ void __launch_bounds__(kBlock)
       ay += sm * dy;
       const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
       const int end = s_end[bc][tid];
-      const int next = pairs_advance(g, me, p, cx, cy, k + 1, end, sxy, scell, sidx);
+      const int next = pairs_advance<batched>(g, row, me, p, cx, cy, k + 1, end, sxy, scell, sidx);
       s_cur[bc][tid] = next;
       s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
     }

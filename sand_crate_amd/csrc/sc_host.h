@@ -215,16 +215,35 @@ struct StateIo {
 // the buckets' counts and starts, the members' positions and cells in bucket order, the row lengths, their 64-bit scan
 // with its block sums, the domain flag and the two words (n, E); each grown to the largest bound asked for.
 // `valid`: the workspace holds the grid of a count, and nothing has changed the state since.
+// The batched form (sc_pairs_set_batch_device): `ptr`, the count's copy of the offsets, and `cloud`, every point's cloud;
+// `clouds` > 0 says that the grid is batched.  `next_ptr` / `next_clouds` wait for the next count, `next_qptr` for the
+// next query-form reader: the caller's device memory, read by that call's launches only.
 struct PairsSpace {
   DevBuf<XY> xy, sxy;
   DevBuf<uint2> cell;
   RadixSpace sort;
-  DevBuf<int> bucketCount, bucketStart, bucketSums, rowLen, flag;
-  DevBuf<long long> offs, sums, words;
+  DevBuf<int> bucketCount, bucketStart, bucketSums, rowLen, flag, cloud;
+  DevBuf<long long> offs, sums, words, ptr;
   bool valid = false;
   int64_t m = 0;  // ... the bound its launches were sized by
   int set = 0;    // ... which of the sort's two sets holds the sorted pairs
   PairsGrid grid{};
+  int64_t clouds = 0;
+  const int64_t* next_ptr = nullptr;
+  int64_t next_clouds = 0;
+  const int64_t* next_qptr = nullptr;
+  // The grid as the walking kernels see it; `qptr` null: the self form.
+  PairsBatch batch(const int64_t* qptr) const {
+    return PairsBatch{ptr.get(), (const long long*)qptr, cloud.get(), (int)clouds};
+  }
+  // The offsets a query-form reader of a batched grid was given (consumed); false when there are none.
+  bool take_query_batch(bool query_form, const int64_t** qptr) {
+    *qptr = nullptr;
+    if (!clouds || !query_form) return true;
+    *qptr = next_qptr;
+    next_qptr = nullptr;
+    return *qptr != nullptr;
+  }
   // Room for a search over n points in `buckets` buckets.
   int ensure(int64_t n, int64_t buckets, hipStream_t stream) {
     HIPCHK(flag.grow(1, stream));

@@ -75,10 +75,39 @@ static unsigned pairs_buckets(int64_t m) {
   return t;
 }
 
+int sc_pairs_set_batch_device(sc_ctx* c, const int64_t* dev_ptr, int64_t clouds) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (clouds < 0) return fail(SC_ERR_ARG, "negative number of clouds");
+  if (clouds > kPairsMaxPoints) return fail(SC_ERR_CAPACITY, "%lld clouds, at most %lld", (long long)clouds, (long long)kPairsMaxPoints);
+  const bool set = dev_ptr && clouds > 0;
+  c->pairs.next_ptr = set ? dev_ptr : nullptr;
+  c->pairs.next_clouds = set ? clouds : 0;
+  return SC_OK;
+}
+
+int sc_pairs_set_query_batch_device(sc_ctx* c, const int64_t* dev_query_ptr) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!c->pairs.valid || !c->pairs.clouds)
+    return fail(SC_ERR_ARG, "query offsets without a batched grid: sc_pairs_set_batch_device and sc_pairs_count_device come first");
+  c->pairs.next_qptr = dev_query_ptr;  // (null clears)
+  return SC_OK;
+}
+
+// A reader that is not batched yet (the clusters, the histograms) on a batched grid.
+static int pairs_refuse_batched(sc_ctx* c, const char* who) {
+  if (!c->pairs.clouds) return SC_OK;
+  return fail(SC_ERR_ARG, "%s does not read a batched grid yet: count without sc_pairs_set_batch_device first", who);
+}
 
 int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double radius, int32_t flags, int64_t* dev_offsets,
                           int64_t room_rows, int64_t* dev_counts) {
   if (!c) return fail(SC_ERR_ARG, "null context");
+  const int64_t* batch_ptr = c->pairs.next_ptr;  // consumed here, whatever becomes of the call
+  const int64_t clouds = c->pairs.next_clouds;
+  c->pairs.next_ptr = nullptr;
+  c->pairs.next_clouds = 0;
+  c->pairs.next_qptr = nullptr;
+  if (clouds && !dev_xy) return fail(SC_ERR_ARG, "a batch needs the caller's points: the state is one cloud");
   if (!dev_offsets || !dev_counts) return fail(SC_ERR_ARG, "null offsets or counts pointer");
   if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
   if (flags & ~SC_PAIRS_HALF) return fail(SC_ERR_ARG, "unknown flags %d", flags);
@@ -96,9 +125,14 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
     return fail(SC_ERR_CAPACITY, "offsets hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
   HIPCHK(hipSetDevice(c->device));
   c->pairs.valid = false;
+  c->pairs.clouds = 0;
   const unsigned buckets = pairs_buckets(m);
   int rc = c->pairs.ensure(m, buckets, c->stream);
   if (rc) return rc;
+  if (clouds) {
+    HIPCHK(c->pairs.ptr.grow(clouds + 1, c->stream));
+    HIPCHK(c->pairs.cloud.grow(m, c->stream));
+  }
   PairsGrid g{};
   g.radius = radius;
   g.h = radius * kPairsCellFactor;
@@ -115,9 +149,15 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   HIPCHK(hipMemsetAsync(c->pairs.flag, 0, sizeof(int), c->stream));
   HIPCHK(hipMemsetAsync(c->pairs.bucketCount, 0, (size_t)buckets * sizeof(int), c->stream));
   RadixSpace& w = c->pairs.sort;
-  hipLaunchKernelGGL(k_pairs_key, dim3(grid), dim3(kBlock), 0, c->stream, g, dev_xy ? (const XY*)dev_xy : c->pairs.xy.get(),
-                     c->pairs.xy.get(), dev_xy ? (long long)n : -1LL, c->pairs.words.get(), (int)m, w.keys[0].get(),
-                     w.vals[0].get(), c->pairs.bucketCount.get(), c->pairs.flag.get());
+  c->pairs.clouds = clouds;
+  const PairsBatch bt = c->pairs.batch(nullptr);
+  if (clouds)
+    hipLaunchKernelGGL(k_pairs_batch_check, dim3(grid_for(clouds + 1)), dim3(kBlock), 0, c->stream, (const long long*)batch_ptr,
+                       c->pairs.ptr.get(), (int)clouds, (long long)n, c->pairs.flag.get());
+  hipLaunchKernelGGL(clouds ? k_pairs_key<true> : k_pairs_key<false>, dim3(grid), dim3(kBlock), 0, c->stream, g,
+                     dev_xy ? (const XY*)dev_xy : c->pairs.xy.get(), c->pairs.xy.get(), dev_xy ? (long long)n : -1LL,
+                     c->pairs.words.get(), (int)m, w.keys[0].get(), w.vals[0].get(), c->pairs.bucketCount.get(),
+                     c->pairs.flag.get(), bt, c->pairs.cloud.get());
   // the binning sort: the keys are 0 .. buckets (a dead point's), so as many digits as `buckets` has
   int bits = 1;
   while ((buckets >> bits) != 0) ++bits;
@@ -126,9 +166,9 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   if ((rc = launch_scan(c, c->pairs.bucketCount, c->pairs.bucketStart, buckets, c->pairs.bucketSums, nullptr))) return rc;
   hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, w.keys[in].get(), w.vals[in].get(), (int)m,
                      c->pairs.xy.get(), c->pairs.flag.get(), c->pairs.sxy.get(), c->pairs.cell.get());
-  hipLaunchKernelGGL(k_pairs_count, dim3(grid), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), (int)m,
-                     c->pairs.xy.get(), c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(), w.vals[in].get(),
-                     c->pairs.rowLen.get());
+  hipLaunchKernelGGL(clouds ? k_pairs_count<true> : k_pairs_count<false>, dim3(grid), dim3(kBlock), 0, c->stream, g,
+                     c->pairs.words.get(), c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.bucketStart.get(),
+                     c->pairs.sxy.get(), c->pairs.cell.get(), w.vals[in].get(), c->pairs.rowLen.get(), bt);
   const int nb = (int)(m / kScanPerBlock + 1);  // entry n <= m lies in one of them
   hipLaunchKernelGGL(k_scan64_local, dim3(nb), dim3(kBlock), 0, c->stream, c->pairs.rowLen.get(), c->pairs.offs.get(),
                      c->pairs.words.get(), c->pairs.flag.get(), c->pairs.sums.get());
@@ -152,10 +192,11 @@ int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64
   HIPCHK(hipSetDevice(c->device));
   const int64_t m = c->pairs.m;
   if (room_pairs == 0) return SC_OK;
-  hipLaunchKernelGGL(k_pairs_fill, dim3(grid_for(m)), dim3(kBlock), 0, c->stream, c->pairs.grid, c->pairs.words.get(),
-                     c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.offs.get(), c->pairs.bucketStart.get(),
-                     c->pairs.sxy.get(), c->pairs.cell.get(), c->pairs.sort.vals[c->pairs.set].get(), (long long*)dev_partners, dev_d2,
-                     (long long)room_pairs);
+  hipLaunchKernelGGL(c->pairs.clouds ? k_pairs_fill<true> : k_pairs_fill<false>, dim3(grid_for(m)), dim3(kBlock), 0, c->stream,
+                     c->pairs.grid, c->pairs.words.get(), c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.offs.get(),
+                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), (long long*)dev_partners, dev_d2, (long long)room_pairs,
+                     c->pairs.batch(nullptr));
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -170,6 +211,7 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
   if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_label_device inside a tick");
   if (!c->pairs.valid)
     return fail(SC_ERR_STATE, "no pair count to label from: sc_pairs_count_device comes first, and the state must not change in between");
+  if (const int rc = pairs_refuse_batched(c, "sc_pairs_label_device")) return rc;
   const int64_t m = c->pairs.m;
   if (room_rows < m)
     return fail(SC_ERR_CAPACITY, "labels hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
@@ -208,12 +250,18 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
 }  // extern "C"
 
 template <int K>
-static void nearest_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int k, const NearestOut& out) {
+static void nearest_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int k, const NearestOut& out,
+                           const PairsBatch& bt) {
   const int64_t grid = std::max<int64_t>(1, (rows + kNearestBlock - 1) / kNearestBlock);  // (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_nearest<K>, dim3((unsigned)grid), dim3(kNearestBlock), 0, c->stream, g, c->pairs.words.get(),
-                     c->pairs.flag.get(), c->nearest.flag.get(), c->pairs.xy.get(), queries, (long long)rows, k,
-                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), out);
+  hipLaunchKernelGGL((bt.clouds ? k_nearest<K, true> : k_nearest<K, false>), dim3((unsigned)grid), dim3(kNearestBlock), 0,
+                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->nearest.flag.get(), c->pairs.xy.get(), queries,
+                     (long long)rows, k, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), out, bt);
+}
+
+// The launch of a reader's check kernel: a thread per query, and on a batched grid per entry of query_ptr.
+static int check_grid(int64_t rows, const int64_t* qptr, int64_t clouds) {
+  return grid_for(qptr ? std::max<int64_t>(rows, clouds + 1) : rows);
 }
 
 extern "C" {
@@ -235,6 +283,9 @@ int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_quer
   if (room_rows < rows)
     return fail(SC_ERR_CAPACITY, "the table holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
                 dev_queries ? "queries" : "points");
+  const int64_t* qptr;
+  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
+    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
   HIPCHK(hipSetDevice(c->device));
   const int rc = c->nearest.ensure(c->stream);
   if (rc) return rc;
@@ -244,11 +295,13 @@ int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_quer
   const XY* queries = (const XY*)dev_queries;
   const NearestOut out{(long long*)dev_neighbors, dev_d2, (long long*)dev_partners, (long long*)dev_counts};
   HIPCHK(hipMemsetAsync(c->nearest.flag, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_nearest_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
-                     queries, (long long)n_queries, c->pairs.flag.get(), c->nearest.flag.get(), out.counts);
-  if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, g, queries, rows, k, out);
-  else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, g, queries, rows, k, out);
-  else nearest_launch<kNearestMaxK>(c, g, queries, rows, k, out);
+  const PairsBatch bt = c->pairs.batch(qptr);
+  hipLaunchKernelGGL(k_nearest_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
+                     g.radius, queries, (long long)n_queries, c->pairs.flag.get(), c->nearest.flag.get(), out.counts,
+                     bt.qptr, bt.clouds);
+  if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, g, queries, rows, k, out, bt);
+  else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, g, queries, rows, k, out, bt);
+  else nearest_launch<kNearestMaxK>(c, g, queries, rows, k, out, bt);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -259,11 +312,11 @@ int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_quer
 
 template <int C>
 static void fields_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int self, int power, int channels,
-                          const double* values, const FieldsOut& out) {
-  hipLaunchKernelGGL(k_fields_sum<C>, dim3(grid_for(rows)), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(),
-                     c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries, (long long)rows, self, power,
-                     channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), values, out);
+                          const double* values, const FieldsOut& out, const PairsBatch& bt) {
+  hipLaunchKernelGGL((bt.clouds ? k_fields_sum<C, true> : k_fields_sum<C, false>), dim3(grid_for(rows)), dim3(kBlock), 0,
+                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries,
+                     (long long)rows, self, power, channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(),
+                     c->pairs.cell.get(), c->pairs.sort.vals[c->pairs.set].get(), values, out, bt);
 }
 
 extern "C" {
@@ -291,6 +344,9 @@ int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries,
   if (room_rows < rows)
     return fail(SC_ERR_CAPACITY, "the sums hold %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
                 dev_queries ? "queries" : "points");
+  const int64_t* qptr;
+  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
+    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
   HIPCHK(hipSetDevice(c->device));
   static_assert(kFieldsMaxChannels == SC_FIELDS_MAX_CHANNELS, "the header's bound is the kernel's");
   const int rc = c->fields.ensure(c->stream);
@@ -302,13 +358,14 @@ int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries,
   const FieldsOut out{channels ? dev_sums : nullptr, dev_wsum, (long long*)dev_counts};
   const int self = (flags & SC_FIELDS_SELF) ? 1 : 0;
   HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_fields_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
-                     queries, (long long)n_queries, values, (long long)values_rows, c->pairs.words.get(), c->pairs.flag.get(),
-                     c->fields.flag.get(), out.counts);
-  if (channels <= 1) fields_launch<1>(c, g, queries, rows, self, power, channels, values, out);
-  else if (channels <= 2) fields_launch<2>(c, g, queries, rows, self, power, channels, values, out);
-  else if (channels <= 4) fields_launch<4>(c, g, queries, rows, self, power, channels, values, out);
-  else fields_launch<8>(c, g, queries, rows, self, power, channels, values, out);
+  const PairsBatch bt = c->pairs.batch(qptr);
+  hipLaunchKernelGGL(k_fields_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
+                     g.radius, queries, (long long)n_queries, values, (long long)values_rows, c->pairs.words.get(),
+                     c->pairs.flag.get(), c->fields.flag.get(), out.counts, bt.qptr, bt.clouds);
+  if (channels <= 1) fields_launch<1>(c, g, queries, rows, self, power, channels, values, out, bt);
+  else if (channels <= 2) fields_launch<2>(c, g, queries, rows, self, power, channels, values, out, bt);
+  else if (channels <= 4) fields_launch<4>(c, g, queries, rows, self, power, channels, values, out, bt);
+  else fields_launch<8>(c, g, queries, rows, self, power, channels, values, out, bt);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -319,11 +376,11 @@ int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries,
 
 template <int C>
 static void fields_grad_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int power, int channels,
-                               const FieldsGradIn& in, double* grad, long long* counts) {
-  hipLaunchKernelGGL(k_fields_grad<C>, dim3(grid_for(rows)), dim3(kBlock), 0, c->stream, g, c->pairs.words.get(),
-                     c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries, (long long)rows, power, channels,
-                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), in, (XY*)grad, counts);
+                               const FieldsGradIn& in, double* grad, long long* counts, const PairsBatch& bt) {
+  hipLaunchKernelGGL((bt.clouds ? k_fields_grad<C, true> : k_fields_grad<C, false>), dim3(grid_for(rows)), dim3(kBlock), 0,
+                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries,
+                     (long long)rows, power, channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
+                     c->pairs.sort.vals[c->pairs.set].get(), in, (XY*)grad, counts, bt);
 }
 
 extern "C" {
@@ -351,6 +408,9 @@ int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_que
   if (room_rows < rows)
     return fail(SC_ERR_CAPACITY, "the gradient holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
                 dev_queries ? "queries" : "points");
+  const int64_t* qptr;
+  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
+    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
   HIPCHK(hipSetDevice(c->device));
   const int rc = c->fields.ensure(c->stream);
   if (rc) return rc;
@@ -360,14 +420,15 @@ int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_que
   const FieldsGradIn in{channels ? dev_row_a : nullptr, channels ? dev_part_b : nullptr, dev_row_s, dev_part_s};
   long long* counts = (long long*)dev_counts;
   HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_fields_grad_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, g.radius,
-                     queries, (long long)n_queries, in.row_a || in.row_s ? 1 : 0, (long long)row_a_rows,
+  const PairsBatch bt = c->pairs.batch(qptr);
+  hipLaunchKernelGGL(k_fields_grad_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
+                     g.radius, queries, (long long)n_queries, in.row_a || in.row_s ? 1 : 0, (long long)row_a_rows,
                      in.part_b || in.part_s ? 1 : 0, (long long)part_b_rows, c->pairs.words.get(), c->pairs.flag.get(),
-                     c->fields.flag.get(), counts);
-  if (channels <= 1) fields_grad_launch<1>(c, g, queries, rows, power, channels, in, dev_grad, counts);
-  else if (channels <= 2) fields_grad_launch<2>(c, g, queries, rows, power, channels, in, dev_grad, counts);
-  else if (channels <= 4) fields_grad_launch<4>(c, g, queries, rows, power, channels, in, dev_grad, counts);
-  else fields_grad_launch<8>(c, g, queries, rows, power, channels, in, dev_grad, counts);
+                     c->fields.flag.get(), counts, bt.qptr, bt.clouds);
+  if (channels <= 1) fields_grad_launch<1>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
+  else if (channels <= 2) fields_grad_launch<2>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
+  else if (channels <= 4) fields_grad_launch<4>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
+  else fields_grad_launch<8>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -404,6 +465,7 @@ int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries
   if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_hist_device inside a tick");
   if (!c->pairs.valid)
     return fail(SC_ERR_STATE, "no pair count to take a histogram of: sc_pairs_count_device comes first, and the state must not change in between");
+  if (const int rc = pairs_refuse_batched(c, "sc_pairs_hist_device")) return rc;
   if (!(edges2[bins] <= c->pairs.grid.r2))
     return fail(SC_ERR_ARG, "the last squared edge %.17g lies beyond the count's squared radius %.17g", edges2[bins], c->pairs.grid.r2);
   if (dev_queries && n_queries > kPairsMaxPoints)

@@ -35,6 +35,10 @@
 //
 // counts[1], the number of rows with more partners than k: one integer add per such row, a count does not depend on their
 // order.  With either flag up the kernel writes counts[1] = -1 and nothing else.
+//
+// On a batched grid (sc_pairs.h) the kernels are the `batched` instantiations: a row carries its record (lo, hi, cloud), a
+// query finds its cloud by binary search over query_ptr, which k_nearest_check tests as the count tested ptr; bad offsets
+// give counts[1] = -3.  Rows of several clouds share a workgroup: the write-out does not care whose rows they are.
 #pragma once
 #include "sc_pairs.h"
 
@@ -54,17 +58,20 @@ struct NearestOut {
   long long* counts;     // [2]: rows, cut
 };
 
-// `queries` null: the self form, nothing to test.  Thread 0 prepares counts[1] for the adds of k_nearest.
+// `queries` null: the self form, nothing to test.  Thread 0 prepares counts[1] for the adds of k_nearest.  `qptr`: the
+// query offsets of a batched grid, or null; the launch covers its clouds + 1 entries.
 __global__ void __launch_bounds__(kBlock)
     k_nearest_check(double radius, const XY* __restrict__ queries, long long n_queries, const int* __restrict__ flag,
-                    int* __restrict__ own_flag, long long* __restrict__ counts) {
+                    int* __restrict__ own_flag, long long* __restrict__ counts, const long long* __restrict__ qptr,
+                    int clouds) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) counts[1] = *flag ? -1 : 0;
+  if (i == 0) counts[1] = *flag ? pairs_status(*flag) : 0;
+  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kPairsFlagBatch);
   if (!queries || i >= n_queries) return;
   const XY q = queries[i];
   const double ax = fabs(q.x), ay = fabs(q.y);
   const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-  if ((fx && !(ax / radius < kPairsDomain)) || (fy && !(ay / radius < kPairsDomain))) atomicOr(own_flag, 1);
+  if ((fx && !(ax / radius < kPairsDomain)) || (fy && !(ay / radius < kPairsDomain))) atomicOr(own_flag, kPairsFlagDomain);
 }
 
 __device__ __forceinline__ bool nearest_before(double d2a, int ja, double d2b, int jb) {
@@ -72,12 +79,12 @@ __device__ __forceinline__ bool nearest_before(double d2a, int ja, double d2b, i
 }
 
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]); otherwise row i is queries[i] (n_queries rows).
-template <int K>
+template <int K, bool batched>
 __global__ void __launch_bounds__(kNearestBlock)
     k_nearest(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag,
               const int* __restrict__ own_flag, const XY* __restrict__ xy, const XY* __restrict__ queries,
               long long n_queries, int k, const int* __restrict__ start, const XY* __restrict__ sxy,
-              const uint2* __restrict__ scell, const int* __restrict__ sidx, NearestOut out) {
+              const uint2* __restrict__ scell, const int* __restrict__ sidx, NearestOut out, PairsBatch bt) {
   constexpr int W = kNearestBlock;
   __shared__ double s_d2[K][W + kNearestPad];
   __shared__ int s_j[K][W + kNearestPad];
@@ -87,7 +94,7 @@ __global__ void __launch_bounds__(kNearestBlock)
   const bool up = *flag || *own_flag;
   const long long rows = queries ? n_queries : words[PW_N];
   if (blockIdx.x == 0 && tid == 0) {
-    if (up) out.counts[1] = -1;
+    if (up) out.counts[1] = batched ? pairs_status(*flag | *own_flag) : kPairsStatusDomain;  // (the same bits in both)
     else out.counts[0] = rows;
   }
   int len = 0;  // places of the list in use
@@ -98,16 +105,17 @@ __global__ void __launch_bounds__(kNearestBlock)
     if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
       double worst_d2 = 0;
       int worst_j = 0;
+      const PairsRow row = pairs_row<batched>(bt, i);
       const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
       for (int c = 0; c < 9; ++c) {
         const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-        const unsigned b = pairs_bucket(cx, cy, g.mask);
+        const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
         const int end = start[b + 1];
         for (int s = start[b]; s < end; ++s) {
           const uint2 cell = scell[s];
           const int j = sidx[s];
           double d2;
-          if (!(cell.x == cx && cell.y == cy && pairs_accept(g, self, j, p, sxy[s], d2))) continue;
+          if (!(cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(g, self, j, p, sxy[s], d2))) continue;
           ++count;
           int pos;
           if (len == k) {

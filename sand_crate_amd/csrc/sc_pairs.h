@@ -38,6 +38,20 @@
 // is no larger).  k_pairs_key raises a flag otherwise; every later kernel of the count and of the fill returns at once when
 // it is up, except that E = -1 is written: no host round trip.  Inside the domain |cell| <= 2^31 / (1 + 2^-20), 2047
 // short of the ends of int, so cx +- 1 does not overflow (the cells are kept as unsigned words all the same).
+//
+// The batched form (sc_pairs_set_batch_device before the count): the points are B disjoint clouds, cloud b the rows
+// ptr[b] .. ptr[b + 1] of B + 1 ascending 64-bit offsets, and j is a partner of row i only when both lie in one cloud.
+// Frames of one scene overlap completely in space, and shifting them apart would round dx differently, so the clouds
+// share the one grid.  k_pairs_batch_check copies ptr into the workspace and tests it (first entry 0, no descent, last
+// entry n: otherwise the flag's second bit goes up, and E = -3); k_pairs_key finds every point's cloud by binary search,
+// keeps it as one int per point and mixes it into the bucket hash -- cloud 0 hashes exactly as an unbatched point does --,
+// so that clouds which share a cell land in different buckets, except by collision.  Exactness does not rest on the hash:
+// besides the own-cell test a candidate j must lie in the row's [lo, hi) = [ptr[b], ptr[b + 1]), two compares on the
+// sidx[k] that pairs_accept needs anyway.  A row reads its record (lo, hi, cloud) once, before its nine cells -- a point
+// from the workspace, a query by binary search over query_ptr --, nothing is read per candidate.  The sort, the scans,
+// k_pairs_place and scell are as they are.  Every kernel that walks is a template on `batched`: the unbatched
+// instantiation carries no record at all.  The clusters and the histograms (sc_clusters.h, sc_hist.h) are not batched:
+// their host calls refuse a batched grid.
 #pragma once
 #include "sc_device.h"
 #include "sc_kernels.h"
@@ -48,6 +62,9 @@ namespace sc {
 constexpr int kPairsLoad = 2;               // buckets per point, at least (then rounded up to a power of two)
 constexpr unsigned kPairsMinBuckets = 256;
 constexpr unsigned kPairsHashX = 0x9E3779B1u, kPairsHashY = 0x85EBCA77u, kPairsHashMix = 0x2C1B3C6Du;
+constexpr unsigned kPairsHashCloud = 0xC2B2AE3Du;  // the batched form's third factor
+constexpr int kPairsFlagDomain = 1, kPairsFlagBatch = 2;  // the bits of the count's flag
+constexpr long long kPairsStatusDomain = -1, kPairsStatusBatch = -3;  // (-2: short arrays, sc_fields.h)
 constexpr double kPairsCellFactor = 1.0 + 1.0 / 1048576.0;  // h = radius * (1 + 2^-20)
 constexpr double kPairsDomain = 2147483648.0;                // |c| / radius must stay below 2^31
 
@@ -60,12 +77,64 @@ struct PairsGrid {
   int half;       // keep j > i only
 };
 
-__device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsigned mask) {
-  unsigned v = (cx * kPairsHashX) ^ (cy * kPairsHashY);
+// The batched grid as the kernels see it: the workspace's copy of ptr, the points' clouds, and -- query form -- the
+// caller's query_ptr.  All null and 0 in the unbatched instantiations, which never look.
+struct PairsBatch {
+  const long long* ptr;   // clouds + 1 offsets into the points (the workspace's copy)
+  const long long* qptr;  // clouds + 1 offsets into the queries, or null: the self form
+  const int* cloud;       // the cloud of every point
+  int clouds;
+};
+
+// What a row carries through its walk: its partners are the indices lo <= j < hi, and its cells hash with `cloud`.
+struct PairsRow {
+  int lo, hi;
+  unsigned cloud;
+};
+
+__device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsigned cloud, unsigned mask) {
+  unsigned v = (cx * kPairsHashX) ^ (cy * kPairsHashY) ^ (cloud * kPairsHashCloud);  // (cloud 0: the unbatched hash)
   v ^= v >> 15;
   v *= kPairsHashMix;
   v ^= v >> 13;
   return v & mask;
+}
+
+__device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsigned mask) {
+  return pairs_bucket(cx, cy, 0u, mask);
+}
+
+// The cloud of row i: the last b < clouds with ptr[b] <= i (empty clouds before it are skipped).  Reads entries
+// 0 .. clouds - 1 only, whatever they hold.
+__device__ __forceinline__ int pairs_cloud_of(const long long* __restrict__ ptr, int clouds, long long i) {
+  int lo = 0, hi = clouds;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ptr[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+template <bool batched>
+__device__ __forceinline__ PairsRow pairs_row(const PairsBatch& bt, long long i) {
+  PairsRow r{0, INT_MAX, 0u};
+  if (batched) {
+    const int b = bt.qptr ? pairs_cloud_of(bt.qptr, bt.clouds, i) : bt.cloud[i];
+    r.lo = (int)bt.ptr[b];
+    r.hi = (int)bt.ptr[b + 1];
+    r.cloud = (unsigned)b;
+  }
+  return r;
+}
+
+template <bool batched>
+__device__ __forceinline__ bool pairs_in(const PairsRow& r, int j) {
+  return !batched || (j >= r.lo && j < r.hi);
+}
+
+__device__ __forceinline__ long long pairs_status(int flag) {
+  return (flag & kPairsFlagBatch) ? kPairsStatusBatch : kPairsStatusDomain;
 }
 
 __device__ __forceinline__ unsigned pairs_cell(double c, double h) { return (unsigned)(int)floor(c / h); }
@@ -80,11 +149,31 @@ __global__ void __launch_bounds__(kBlock)
   xy[k] = XY{x[s], y[s]};
 }
 
+// The batched form's offsets: entry k of the caller's `src` goes to `dst`, the workspace, and `bit` of the flag goes up
+// unless src[0] = 0, no entry is below the one before, and src[clouds] = n.  `dst` null: nothing is copied (a query_ptr,
+// which a reader's own check tests against the number of queries, with its own flag).
+__device__ __forceinline__ void pairs_ptr_check(const long long* __restrict__ src, long long* __restrict__ dst, int clouds,
+                                                long long n, long long k, int* __restrict__ flag, int bit) {
+  if (k > clouds) return;
+  const long long v = src[k];
+  if (dst) dst[k] = v;
+  const bool bad = k == 0 ? v != 0 : v < src[k - 1];
+  if (bad || (k == clouds && v != n)) atomicOr(flag, bit);
+}
+
+__global__ void __launch_bounds__(kBlock)
+    k_pairs_batch_check(const long long* __restrict__ src, long long* __restrict__ dst, int clouds, long long n,
+                        int* __restrict__ flag) {
+  pairs_ptr_check(src, dst, clouds, n, (long long)blockIdx.x * blockDim.x + threadIdx.x, flag, kPairsFlagBatch);
+}
+
 // `n_host` >= 0: the caller's points, n is known (and written to words); -1: xy is the workspace, n is words[PW_N].
+// Batched: `bt.ptr` is the workspace's copy (which k_pairs_batch_check has written), the clouds go to `cloud`.
+template <bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_pairs_key(PairsGrid g, const XY* __restrict__ src, XY* __restrict__ xy, long long n_host, long long* __restrict__ words,
                 int m, unsigned* __restrict__ keys, int* __restrict__ index, int* __restrict__ bucketCount,
-                int* __restrict__ flag) {
+                int* __restrict__ flag, PairsBatch bt, int* __restrict__ cloud) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const long long n = n_host >= 0 ? n_host : words[PW_N];
   if (i == 0 && n_host >= 0) words[PW_N] = n_host;
@@ -93,11 +182,16 @@ __global__ void __launch_bounds__(kBlock)
   if (i < n) {
     const XY p = src[i];
     if (src != xy) xy[i] = p;
+    unsigned b = 0u;
+    if (batched) {
+      b = (unsigned)pairs_cloud_of(bt.ptr, bt.clouds, i);
+      cloud[i] = (int)b;
+    }
     const double ax = fabs(p.x), ay = fabs(p.y);
     const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-    if ((fx && !(ax / g.radius < kPairsDomain)) || (fy && !(ay / g.radius < kPairsDomain))) atomicOr(flag, 1);
+    if ((fx && !(ax / g.radius < kPairsDomain)) || (fy && !(ay / g.radius < kPairsDomain))) atomicOr(flag, kPairsFlagDomain);
     else if (fx && fy) {
-      key = pairs_bucket(pairs_cell(p.x, g.h), pairs_cell(p.y, g.h), g.mask);
+      key = pairs_bucket(pairs_cell(p.x, g.h), pairs_cell(p.y, g.h), b, g.mask);
       atomicAdd(&bucketCount[key], 1);
     }
   }
@@ -124,37 +218,43 @@ __device__ __forceinline__ bool pairs_accept(const PairsGrid& g, int i, int j, X
   return j != i && (!g.half || j > i) && d2 <= g.r2;
 }
 
-// The first place from k on, below `end`, whose point lies in cell (cx, cy) and is a partner of i; `end` when none.
-__device__ __forceinline__ int pairs_advance(const PairsGrid& g, int i, XY p, unsigned cx, unsigned cy, int k, int end,
-                                             const XY* __restrict__ sxy, const uint2* __restrict__ scell,
+// The first place from k on, below `end`, whose point lies in cell (cx, cy) -- and, batched, in the row's cloud -- and is
+// a partner of i; `end` when none.
+template <bool batched>
+__device__ __forceinline__ int pairs_advance(const PairsGrid& g, const PairsRow& row, int i, XY p, unsigned cx, unsigned cy,
+                                             int k, int end, const XY* __restrict__ sxy, const uint2* __restrict__ scell,
                                              const int* __restrict__ sidx) {
   for (; k < end; ++k) {
     const uint2 cell = scell[k];
+    const int j = sidx[k];
     double d2;
-    if (cell.x == cx && cell.y == cy && pairs_accept(g, i, sidx[k], p, sxy[k], d2)) break;
+    if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(g, i, j, p, sxy[k], d2)) break;
   }
   return k;
 }
 
+template <bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_pairs_count(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
                   const XY* __restrict__ xy, const int* __restrict__ start, const XY* __restrict__ sxy,
-                  const uint2* __restrict__ scell, const int* __restrict__ sidx, int* __restrict__ rowLen) {
+                  const uint2* __restrict__ scell, const int* __restrict__ sidx, int* __restrict__ rowLen, PairsBatch bt) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= m || *flag) return;
   int count = 0;
   if (i < words[PW_N]) {
     const XY p = xy[i];
     if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
+      const PairsRow row = pairs_row<batched>(bt, i);
       const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
       for (int c = 0; c < 9; ++c) {
         const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-        const unsigned b = pairs_bucket(cx, cy, g.mask);
+        const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
         const int end = start[b + 1];
         for (int k = start[b]; k < end; ++k) {
           const uint2 cell = scell[k];
+          const int j = sidx[k];
           double d2;
-          if (cell.x == cx && cell.y == cy && pairs_accept(g, i, sidx[k], p, sxy[k], d2)) ++count;
+          if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(g, i, j, p, sxy[k], d2)) ++count;
         }
       }
     }
@@ -186,16 +286,17 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ... adds the totals of the workgroups before, writes the caller's copy, and -- the thread that holds entry n -- E and
-// the caller's two words.  With the domain flag up: E = -1 and the caller's words, nothing else.
+// the caller's two words.  With the flag up: E = -1 (the domain) or -3 (the batch offsets) and the caller's words, nothing
+// else.
 __global__ void __launch_bounds__(kBlock)
     k_scan64_fix(long long* __restrict__ out, long long* __restrict__ out_caller, long long* __restrict__ words,
                  const int* __restrict__ flag, const long long* __restrict__ blockSums, long long* __restrict__ counts) {
   const long long n = words[PW_N];
-  if (*flag) {
+  if (const int up = *flag) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      words[PW_E] = -1;
+      words[PW_E] = pairs_status(up);
       counts[0] = n;
-      counts[1] = -1;
+      counts[1] = pairs_status(up);
     }
     return;
   }
@@ -218,11 +319,12 @@ __global__ void __launch_bounds__(kBlock)
 
 // Row i's partners at offs[i], ascending in j: the nine runs are each ascending (the sort is stable), the smallest head
 // goes out next.  Entry e is written only when e < room.
+template <bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_pairs_fill(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
                  const XY* __restrict__ xy, const long long* __restrict__ offs, const int* __restrict__ start,
                  const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx,
-                 long long* __restrict__ partners, double* __restrict__ d2_out, long long room) {
+                 long long* __restrict__ partners, double* __restrict__ d2_out, long long room, PairsBatch bt) {
   __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
   const int tid = (int)threadIdx.x;
   const int i = (int)(blockIdx.x * blockDim.x + tid);
@@ -231,12 +333,13 @@ __global__ void __launch_bounds__(kBlock)
   const long long row_end = offs[i + 1];
   if (e >= room || e == row_end) return;
   const XY p = xy[i];
+  const PairsRow row = pairs_row<batched>(bt, i);
   const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
   for (int c = 0; c < 9; ++c) {
     const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-    const unsigned b = pairs_bucket(cx, cy, g.mask);
+    const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
     const int end = start[b + 1];
-    const int k = pairs_advance(g, i, p, cx, cy, start[b], end, sxy, scell, sidx);
+    const int k = pairs_advance<batched>(g, row, i, p, cx, cy, start[b], end, sxy, scell, sidx);
     s_cur[c][tid] = k;
     s_end[c][tid] = end;
     s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
@@ -260,7 +363,7 @@ __global__ void __launch_bounds__(kBlock)
     ++e;
     const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
     const int end = s_end[bc][tid];
-    const int next = pairs_advance(g, i, p, cx, cy, k + 1, end, sxy, scell, sidx);
+    const int next = pairs_advance<batched>(g, row, i, p, cx, cy, k + 1, end, sxy, scell, sidx);
     s_cur[bc][tid] = next;
     s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
   }

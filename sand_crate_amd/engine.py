@@ -86,6 +86,17 @@ def _state_tensor(t, name: str, dtype: str, tail: tuple, device: int, rows: int 
     return int(shape[0])
 
 
+def _batch_tensor(t, name: str, device: int, entries: int | None = None) -> int:
+    """The entries of the offsets of a batched call, `batch` or `query_batch`: a contiguous 1-D int64 CUDA tensor on
+    `device` of B + 1 >= 2 entries (`entries` of them when given).  ValueError otherwise, before the library is touched."""
+    held = _state_tensor(t, name, "int64", (), device)
+    if held < 2:
+        raise ValueError(f"{name} must hold B + 1 offsets, B at least 1")
+    if entries is not None and held != entries:
+        raise ValueError(f"{name} has {held} entries, batch has {entries}: both count the same clouds")
+    return held
+
+
 class Engine:
     def __init__(self, capacity: int, device: int = 0):
         self._lib = N.load()
@@ -210,13 +221,46 @@ class Engine:
                                                  None if ids is None else N._P(ids.data_ptr()), n))
 
     # -- pair lists in torch's memory (sc_pairs_count_device / sc_pairs_fill_device; the rule is tests/pairs_spec.py)
-    def pairs_count(self, points=None, *, radius: float, offsets, counts, half: bool = False, room: int | None = None):
+    def pairs_set_batch(self, batch=None) -> None:
+        """`batch`, an int64 CUDA tensor of B + 1 ascending offsets (0 .. n), cuts the points of the NEXT `pairs_count`
+        into B clouds that see only themselves (sc_pairs_set_batch_device; tests/batch_spec.py is the rule); None clears a
+        pending one.  The count consumes it and copies it on the context's stream: it must be ready then."""
+        if batch is None:
+            N.check(self._lib.sc_pairs_set_batch_device(self._ctx, None, 0))
+            return
+        entries = _batch_tensor(batch, "batch", self.device)
+        N.check(self._lib.sc_pairs_set_batch_device(self._ctx, N._P(batch.data_ptr()), entries - 1))
+
+    def pairs_set_query_batch(self, query_batch=None) -> None:
+        """`query_batch`, an int64 CUDA tensor of B + 1 ascending offsets (0 .. q), gives the queries of the NEXT query-form
+        reader of a batched grid their clouds (sc_pairs_set_query_batch_device); None clears a pending one.  The reader
+        consumes it; its launches read it on the context's stream."""
+        if query_batch is not None:
+            _batch_tensor(query_batch, "query_batch", self.device)
+        N.check(self._lib.sc_pairs_set_query_batch_device(self._ctx, None if query_batch is None else N._P(query_batch.data_ptr())))
+
+    def _query_batch(self, queries, query_batch) -> None:
+        if query_batch is None:
+            return
+        if queries is None:
+            raise ValueError("query_batch without queries")
+        self.pairs_set_query_batch(query_batch)
+
+    def pairs_count(self, points=None, *, radius: float, offsets, counts, half: bool = False, room: int | None = None,
+                    batch=None):
         """Counts the pairs within `radius` among `points`, a float64 (n, 2) CUDA tensor -- or with None among the state's
         particles in particle-index order -- into `offsets`, int64 (R + 1,): the exclusive scan of the row lengths, entries
         0..n.  `counts`, int64 (2,), receives n and E, the number of pairs (E = -1: a coordinate outside the domain
-        |c| / radius < 2^31).  `half` keeps j > i only.  `room` defaults to R rows.  Enqueued on the context's stream, no
-        synchronisation, with the stream rules of `export_state`.  Returns `counts`."""
+        |c| / radius < 2^31).  `half` keeps j > i only.  `room` defaults to R rows.  `batch`, an int64 CUDA tensor of
+        B + 1 ascending offsets from 0 to n, makes the points B clouds that see only themselves (`pairs_set_batch`; needs
+        `points`): the readers then read a batched grid, `pairs_label` and `pairs_hist` refuse it, and E = -3 says that
+        the offsets are not in order (nothing else is written).  Enqueued on the context's stream, no synchronisation,
+        with the stream rules of `export_state`.  Returns `counts`."""
         n = 0 if points is None else _state_tensor(points, "points", "float64", (2,), self.device)
+        if batch is not None:
+            if points is None:
+                raise ValueError("batch needs points: the state is one cloud")
+            _batch_tensor(batch, "batch", self.device)
         rows = _state_tensor(offsets, "offsets", "int64", (), self.device) - 1
         _state_tensor(counts, "counts", "int64", (), self.device, 2)
         if rows < 0:
@@ -229,6 +273,7 @@ class Engine:
             raise ValueError("radius must be finite and positive")
         # (an empty tensor has no address, and a null address asks for the state: no point is read, any address serves)
         xy = None if points is None else N._P(points.data_ptr() if n else offsets.data_ptr())
+        self.pairs_set_batch(batch)  # (None: a batch left pending by hand does not reach this count)
         N.check(self._lib.sc_pairs_count_device(self._ctx, xy, n, radius,
                                                 N.PAIRS_HALF if half else 0, N._P(offsets.data_ptr()), room,
                                                 N._P(counts.data_ptr())))
@@ -283,8 +328,9 @@ class Engine:
         count's points, or with `queries`, a float64 (q, 2) CUDA tensor, those points of any kind: a query is not its own
         partner's rival, a point it coincides with is a partner at d2 = 0.  `counts`, int64 (2,), receives the row count
         and the number of rows with more than k partners (-1: a point or a query lies outside the domain, nothing else
-        is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.  Returns
-        `counts`."""
+        is written; -3: the offsets of a batched call are not in order).  `room` defaults to R rows.  On a batched grid
+        `queries` need their B + 1 offsets first: `pairs_set_query_batch` right before this call (the parameter list here
+        is as it was).  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
         k = int(k)
         if not 1 <= k <= N.NEAREST_MAX_K:
             raise ValueError(f"k must be 1 .. {N.NEAREST_MAX_K}")
@@ -306,7 +352,7 @@ class Engine:
         return counts
 
     def pairs_sum(self, values=None, sums=None, wsum=None, *, power: int = 3, include_self: bool = True, queries=None,
-                  counts, room: int | None = None, values_rows: int | None = None):
+                  counts, room: int | None = None, values_rows: int | None = None, query_batch=None):
         """The weighted sums over the partners of the last `pairs_count`, whichever `half` it had (sc_pairs_sum_device;
         the rule is tests/field_spec.py): `sums`, float64 (R, C), receives per row the sum of w * values[j, :] over its
         partners j within the count's radius, added in ascending j, and `wsum`, float64 (R,) or None, the sum of the
@@ -315,8 +361,9 @@ class Engine:
         -- `include_self`: point r is a partner of its own row -- or with `queries`, a float64 (q, 2) CUDA tensor, those
         points of any kind.  `counts`, int64 (2,), receives the row count and the status: 0, -1 when a point or a query
         lies outside the domain, -2 when `values` has fewer rows than the count has points (then nothing else is written).
-        `room` defaults to R rows, `values_rows` to V.  Enqueued on the context's stream, no synchronisation.  Returns
-        `counts`."""
+        -3 says that the offsets of a batched call are not in order.  `room` defaults to R rows, `values_rows` to V.  On a
+        batched grid `queries` come with `query_batch`, their B + 1 offsets (`pairs_set_query_batch`).  Enqueued on the
+        context's stream, no synchronisation.  Returns `counts`."""
         power = int(power)
         if not 0 <= power <= 3:
             raise ValueError("power must be 0 .. 3")
@@ -344,13 +391,15 @@ class Engine:
         # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
         # for the self form)
         ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        self._query_batch(queries, query_batch)
         N.check(self._lib.sc_pairs_sum_device(self._ctx, ptr(queries), q, ptr(values), values_rows or 0, channels, power,
                                               N.FIELDS_SELF if include_self else 0, ptr(sums), ptr(wsum), room,
                                               N._P(counts.data_ptr())))
         return counts
 
     def pairs_sum_grad(self, grad, row_a=None, part_b=None, row_s=None, part_s=None, *, power: int = 3, queries=None,
-                       counts, room: int | None = None, row_rows: int | None = None, part_rows: int | None = None):
+                       counts, room: int | None = None, row_rows: int | None = None, part_rows: int | None = None,
+                       query_batch=None):
         """The gradient of the weighted sums with respect to positions, over the partners of the last `pairs_count`
         (sc_pairs_sum_grad_device; the rule is `position_grad` of tests/field_grad_spec.py): `grad`, float64 (R, 2),
         receives per row ``k * sum_j s_rj * t_rj ** (power - 1) * (dx_rj, dy_rj)``, ``k = -2 * power / radius**2``,
@@ -360,8 +409,9 @@ class Engine:
         points -- a point is never its own partner here -- or with `queries`, a float64 (q, 2) CUDA tensor, those points.
         `counts`, int64 (2,), receives the row count and the status: 0, -1 when a point or a query lies outside the
         domain, -2 when the row arrays have fewer rows than there are rows or the partner arrays fewer than the count has
-        points (then nothing else is written).  `room` defaults to R rows, `row_rows` to A, `part_rows` to B.  Enqueued
-        on the context's stream, no synchronisation.  Returns `counts`."""
+        points (then nothing else is written), -3 when the offsets of a batched call are not in order.  `room` defaults
+        to R rows, `row_rows` to A, `part_rows` to B.  On a batched grid `queries` come with `query_batch`, their B + 1
+        offsets (`pairs_set_query_batch`).  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
         power = int(power)
         if not 0 <= power <= 3:
             raise ValueError("power must be 0 .. 3")
@@ -393,6 +443,7 @@ class Engine:
         # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
         # for the self form, or says that an array is absent)
         ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        self._query_batch(queries, query_batch)
         N.check(self._lib.sc_pairs_sum_grad_device(self._ctx, ptr(queries), q, ptr(row_a), row_rows, ptr(part_b), part_rows,
                                                    channels, ptr(row_s), ptr(part_s), power, ptr(grad), room,
                                                    N._P(counts.data_ptr())))

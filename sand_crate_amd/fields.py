@@ -11,6 +11,9 @@ _function = None
 
 
 def _check_status(status: int, radius: float, what: str) -> None:
+    if status == N.PAIRS_BATCH:
+        raise ValueError("field_function: batch offsets must start at 0, not descend and end at the number of points "
+                         "(of queries for query_batch)")
     if status == N.FIELDS_DOMAIN:
         raise ValueError(f"field_function: a coordinate of a point or a query lies outside the domain "
                          f"|c| / radius < 2^31 (radius {radius!r})")
@@ -19,11 +22,12 @@ def _check_status(status: int, radius: float, what: str) -> None:
 
 
 def position_grad(crate, points, radius: float, power: int, row_a=None, part_b=None, row_s=None, part_s=None, *,
-                  queries=None):
+                  queries=None, batch=None, query_batch=None):
     """One use of the position rule (`position_grad_chunked` of tests/field_grad_spec.py) -> float64 (rows, 2): counts
     the pairs among `points`, then launches sc_pairs_sum_grad_device once per eight channels of `row_a` / `part_b`, the
     scalars `row_s` / `part_s` with the first, and adds the results in ascending order.  The rows are the points (the
-    self form) or `queries`.  Synchronises torch's stream before enqueuing and the library's at the end, as
+    self form) or `queries`.  `batch` cuts `points` -- the grid -- into clouds and `query_batch` the `queries`, as in
+    `field_tensors`.  Synchronises torch's stream before enqueuing and the library's at the end, as
     `field_tensors(sync=True)` does."""
     import torch
     eng = crate.engine
@@ -47,10 +51,10 @@ def position_grad(crate, points, radius: float, power: int, row_a=None, part_b=N
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     parts = [torch.empty((rows, 2), dtype=torch.float64, device=dev) for _ in groups]
     torch.cuda.current_stream(dev).synchronize()  # (what torch was asked for above is done)
-    eng.pairs_count(points, radius=radius, offsets=offsets, counts=count_counts, half=True)
+    eng.pairs_count(points, radius=radius, offsets=offsets, counts=count_counts, half=True, batch=batch)
     for at, ((a, b), part) in enumerate(zip(groups, parts)):
         eng.pairs_sum_grad(part, a, b, row_s if at == 0 else None, part_s if at == 0 else None, power=power, queries=queries,
-                           counts=counts)
+                           counts=counts, query_batch=query_batch)
     eng.synchronize()
     _check_status(int(counts[1]), radius, "an upstream gradient or the values")
     total = parts[0]
@@ -67,10 +71,11 @@ def _make_function():
         """(values (n, C) or None, points (n, 2), queries (q, 2) or None) -> the tuple of `field_tensors(sync=True)`."""
 
         @staticmethod
-        def forward(ctx, crate, radius, power, include_self, weight_sums, values, points, queries):
+        def forward(ctx, crate, radius, power, include_self, weight_sums, batch, query_batch, values, points, queries):
             out = crate.field_tensors(values, radius, power=power, include_self=include_self, points=points, queries=queries,
-                                      weight_sums=weight_sums)
+                                      weight_sums=weight_sums, batch=batch, query_batch=query_batch)
             ctx.crate, ctx.radius, ctx.power, ctx.include_self = crate, radius, power, include_self
+            ctx.batch, ctx.query_batch = batch, query_batch
             ctx.has_sums = values is not None
             ctx.save_for_backward(*(t for t in (values, points, queries) if t is not None))
             ctx.set_materialize_grads(False)  # (an output nobody used has no gradient: nothing is launched for it)
@@ -84,18 +89,21 @@ def _make_function():
             points = saved.pop(0)
             queries = saved.pop(0) if saved else None
             crate, radius, power = ctx.crate, ctx.radius, ctx.power
+            batch, query_batch = ctx.batch, ctx.query_batch
             G = grads[0] if ctx.has_sums else None
             gw = grads[-1] if len(grads) > int(ctx.has_sums) else None
             G = None if G is None else G.contiguous()
             gw = None if gw is None else gw.contiguous()
-            need_values, need_points, need_queries = ctx.needs_input_grad[5:8]
+            need_values, need_points, need_queries = ctx.needs_input_grad[7:10]
             g_values = g_points = g_queries = None
             n = int(points.shape[0])
             if need_values and G is not None:
                 if queries is None:
-                    g_values, = crate.field_tensors(G, radius, power=power, include_self=ctx.include_self, points=points)
-                else:
-                    g_values, = crate.field_tensors(G, radius, power=power, points=queries, queries=points)
+                    g_values, = crate.field_tensors(G, radius, power=power, include_self=ctx.include_self, points=points,
+                                                    batch=batch)
+                else:  # (rows and partners swap, and their offsets with them)
+                    g_values, = crate.field_tensors(G, radius, power=power, points=queries, queries=points,
+                                                    batch=query_batch, query_batch=batch)
                 if values.shape[0] > n:  # (rows of values beyond the points were never read)
                     g_values = torch.cat([g_values, g_values.new_zeros((values.shape[0] - n, values.shape[1]))])
             dot = G is not None  # (without G -- or without values, which has no G -- s has no dot product)
@@ -103,18 +111,20 @@ def _make_function():
             if need_points and (dot or gw is not None):
                 if queries is None:
                     g_points = position_grad(crate, points, radius, power, torch.cat([G, V], dim=1) if dot else None,
-                                             torch.cat([V, G], dim=1) if dot else None, gw, gw)
-                else:
-                    g_points = position_grad(crate, queries, radius, power, V, G, None, gw, queries=points)
+                                             torch.cat([V, G], dim=1) if dot else None, gw, gw, batch=batch)
+                else:  # (the grid is over the queries, cut by their offsets; the rows are the points)
+                    g_points = position_grad(crate, queries, radius, power, V, G, None, gw, queries=points,
+                                             batch=query_batch, query_batch=batch)
             if need_queries and (dot or gw is not None):
-                g_queries = position_grad(crate, points, radius, power, G, V, gw, None, queries=queries)
-            return None, None, None, None, None, g_values, g_points, g_queries
+                g_queries = position_grad(crate, points, radius, power, G, V, gw, None, queries=queries, batch=batch,
+                                          query_batch=query_batch)
+            return None, None, None, None, None, None, None, g_values, g_points, g_queries
 
     return FieldFunction
 
 
 def field_function(crate, values=None, radius=None, *, power: int = 3, include_self: bool = True, points=None, queries=None,
-                   weight_sums: bool = False):
+                   weight_sums: bool = False, batch=None, query_batch=None):
     """`crate.field_tensors(values, radius, power=, include_self=, points=, queries=, weight_sums=, sync=True)` attached
     to torch's autograd graph: the same arguments, the same tuple ``(sums[, wsum])``, the same bits -- and when `values`,
     `points` or `queries` requires grad, a backward that gives their gradients, computed on the GPU over the pair
@@ -132,13 +142,16 @@ def field_function(crate, values=None, radius=None, *, power: int = 3, include_s
     forward.  A point is never its own partner in the gradient with respect to the points, whatever `include_self`:
     its weight is constant.
 
+    `batch` and `query_batch` are `field_tensors`' and reach every count of the backward: where rows and partners swap
+    -- the values' gradient and the points' gradient of the query form, whose grid is over the queries -- the two swap too.
+
     Once differentiable: no second derivatives.  No gradient with respect to `radius`, and no `sync=False` form."""
     global _function
     import torch
     tensors = [t for t in (values, points, queries) if t is not None]
     if not torch.is_grad_enabled() or not any(getattr(t, "requires_grad", False) for t in tensors):
         return crate.field_tensors(values, radius, power=power, include_self=include_self, points=points, queries=queries,
-                                   weight_sums=weight_sums)
+                                   weight_sums=weight_sums, batch=batch, query_batch=query_batch)
     power = int(power)
     if not 0 <= power <= 3:
         raise ValueError("power must be 0 .. 3")
@@ -151,9 +164,12 @@ def field_function(crate, values=None, radius=None, *, power: int = 3, include_s
         values = (values.unsqueeze(1) if flat else values).contiguous()
         if values.shape[1] < 1:
             raise ValueError("values must have at least one column")
+    if batch is not None and points is None:
+        raise ValueError("field_function: batch needs points, the state is one cloud")
     if points is None:
         points = crate.state_tensors(pressure=False)[0]
     if _function is None:
         _function = _make_function()
-    out = _function.apply(crate, radius, power, bool(include_self), bool(weight_sums), values, points, queries)
+    out = _function.apply(crate, radius, power, bool(include_self), bool(weight_sums), batch, query_batch, values, points,
+                          queries)
     return (out[0].view(-1), *out[1:]) if flat else out

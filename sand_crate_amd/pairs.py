@@ -5,6 +5,28 @@ weighted sums of `Crate.field_tensors` (sums, wsum) and for the distance histogr
 from __future__ import annotations
 
 
+def batch_ptr(lengths, device=None):
+    """The `batch=` offsets of `Crate.pair_tensors`, `neighbor_tensors`, `field_tensors` and `field_function` from the
+    clouds' sizes: int64 (B + 1,), ``ptr[0] = 0`` and ``ptr[b + 1] = ptr[b] + lengths[b]`` -- the `ptr` of a graph
+    library's batch.  `lengths` is a sequence or an int64 tensor of B >= 1 sizes, none negative."""
+    import torch
+    sizes = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).cpu()
+    if sizes.shape[0] < 1 or bool((sizes < 0).any()):
+        raise ValueError("lengths must hold at least one size, none negative")
+    ptr = torch.zeros(sizes.shape[0] + 1, dtype=torch.int64)
+    ptr[1:] = torch.cumsum(sizes, 0)
+    return ptr if device is None else ptr.to(device)
+
+
+def batch_index(ptr, n=None):
+    """The cloud of every row, the `batch` vector of a graph library: int64 (n,), row i lies in cloud b iff
+    ``ptr[b] <= i < ptr[b + 1]``.  `n` defaults to ``ptr[-1]`` (which then synchronises to read it)."""
+    import torch
+    n = int(ptr[-1]) if n is None else int(n)
+    clouds = torch.arange(ptr.shape[0] - 1, dtype=torch.int64, device=ptr.device)
+    return torch.repeat_interleave(clouds, ptr[1:] - ptr[:-1], output_size=n)
+
+
 def row_lengths(offsets):
     """The number of partners of every row: int64 (n,)."""
     return offsets[1:] - offsets[:-1]
