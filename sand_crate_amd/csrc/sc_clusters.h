@@ -77,28 +77,26 @@ __global__ void __launch_bounds__(kBlock)
   parent[i] = i;
 }
 
-// `g.half` is off (the host clears it): the graph is the full one, and each edge is united from its larger end.  A bucket's
-// members ascend in index (the binning sort is stable), so a run is left at the first j >= i.
-__global__ void __launch_bounds__(kBlock)
-    k_cluster_union(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
-                    const XY* __restrict__ xy, const int* __restrict__ start, const XY* __restrict__ sxy,
-                    const uint2* __restrict__ scell, const int* __restrict__ sidx, int* parent) {
+// `v.g.half` is off (the view's): the graph is the full one, and each edge is united from its larger end.  A bucket's
+// members ascend in index (the binning sort is stable), so a run is left at the first j >= i, before its cell is even read:
+// that early exit is this reader's alone, one more reason why it keeps its own loop over the view (sc_pairs.h).
+__global__ void __launch_bounds__(kBlock) k_cluster_union(PairsView v, int m, int* parent) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i >= m || *flag || i >= words[PW_N]) return;
-  const XY p = xy[i];
+  if (i >= m || *v.flag || i >= v.words[PW_N]) return;
+  const XY p = v.xy[i];
   if (!cluster_finite(p)) return;
-  const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
+  const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
   int root = i;  // an ancestor of i: where the next find starts
   for (int c = 0; c < 9; ++c) {
     const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-    const unsigned b = pairs_bucket(cx, cy, g.mask);
-    const int end = start[b + 1];
-    for (int k = start[b]; k < end; ++k) {
-      const int j = sidx[k];
+    const unsigned b = pairs_bucket(cx, cy, 0u, v.g.mask);  // (never batched: the host refuses)
+    const int end = v.start[b + 1];
+    for (int k = v.start[b]; k < end; ++k) {
+      const int j = v.sidx[k];
       if (j >= i) break;
-      const uint2 cell = scell[k];
+      const uint2 cell = v.scell[k];
       double d2;
-      if (cell.x == cx && cell.y == cy && pairs_accept(g, i, j, p, sxy[k], d2)) root = cluster_unite(parent, root, j);
+      if (cell.x == cx && cell.y == cy && pairs_accept(v.g, i, j, p, v.sxy[k], d2)) root = cluster_unite(parent, root, j);
     }
   }
 }

@@ -15,15 +15,13 @@
 //
 // Everything about the points is read from the workspace the last count left (sc_pairs.h), as sc_nearest.h does, and
 // nothing of it is written: a fill, a label, a table or another sum may follow.
-//   k_fields_check  prepares counts[1] and raises the flag OF THE SUM (the count's stays as the count left it): bit 0 for a
-//                   query outside the domain, bit 1 when the caller's values have fewer rows than the count has points
-//                   (n is known on the device only);
-//   k_fields_sum<C> a thread per row merges its nine runs by always taking the smallest head, exactly as k_pairs_fill does
-//                   -- the cursors in LDS (s_cur / s_end / s_head: a dynamically indexed register array would go to
-//                   scratch) -- and instead of storing the partner adds to wsum and to C channel sums in registers; the
-//                   loops over the channels are unrolled.  C is 1, 2, 4 or 8: a call with 3 channels runs C = 4, the
-//                   loads and the stores guarded.  The merge loop is restated, not shared with k_pairs_fill: that
-//                   kernel stays as it is.
+//   k_reader_check  (sc_pairs.h) prepares counts[1] and raises the flag OF THE READER (the count's stays as the count left
+//                   it): the domain bit for a query outside, the rows bit when the caller's values have fewer rows than
+//                   the count has points (n is known on the device only);
+//   k_fields_sum<C> a thread per row takes its partners from pairs_merge (sc_pairs.h), the merge k_pairs_fill stores its
+//                   list from -- the cursors in the kernel's LDS (s_cur / s_end / s_head) -- and instead of storing the
+//                   partner adds to wsum and to C channel sums in registers; the loops over the channels are unrolled.
+//                   C is 1, 2, 4 or 8: a call with 3 channels runs C = 4, the loads and the stores guarded.
 // The values are gathered by j from the caller's array as they are: values[j, 0 .. channels) is one run of at most 64
 // bytes.  Copying them into bucket order first, next to the sxy[s] the walk reads (16-byte loads at a fixed stride), was
 // built and measured and is 2 to 4 % SLOWER at 1,048,576 points in random index order and 10 % slower for 65,536 probes:
@@ -35,47 +33,21 @@
 // With either flag up only counts[1] is written: -1 for the domain (the count's flag or a query), else -2 for the values.
 //
 // On a batched grid (sc_pairs.h) the kernels are the `batched` instantiations: a row carries its record (lo, hi, cloud), a
-// query finds its cloud by binary search over query_ptr, which k_fields_check tests as the count tested ptr (bit 2 of the
-// sum's flag); bad offsets, the count's or the queries', give counts[1] = -3 before anything else.  No LDS is added.
+// query finds its cloud by binary search over query_ptr, which k_reader_check tests as the count tested ptr (the batch bit
+// of the reader's flag); bad offsets, the count's or the queries', give counts[1] = -3 before anything else.  No LDS is
+// added.
 #pragma once
 #include "sc_pairs.h"
 
 namespace sc {
 
 constexpr int kFieldsMaxChannels = 8;
-constexpr int kFieldsFlagDomain = 1, kFieldsFlagValues = 2, kFieldsFlagBatch = 4;
-
-// counts[1] with a flag up: `flag` the count's, `own` the call's.
-__device__ __forceinline__ long long fields_status(int flag, int own) {
-  if ((flag & kPairsFlagBatch) || (own & kFieldsFlagBatch)) return kPairsStatusBatch;
-  return flag || (own & kFieldsFlagDomain) ? kPairsStatusDomain : -2;
-}
 
 struct FieldsOut {
   double* sums;       // rows x channels, or null (channels 0)
   double* wsum;       // rows, or null
   long long* counts;  // [2]: rows, status
 };
-
-// `queries` null: the self form, no point to test.  `values` null: no values to be short of.  `qptr`: the query offsets of
-// a batched grid, or null; the launch covers its clouds + 1 entries.
-__global__ void __launch_bounds__(kBlock)
-    k_fields_check(double radius, const XY* __restrict__ queries, long long n_queries, const double* __restrict__ values,
-                   long long values_rows, const long long* __restrict__ words, const int* __restrict__ flag,
-                   int* __restrict__ own_flag, long long* __restrict__ counts, const long long* __restrict__ qptr,
-                   int clouds) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kFieldsFlagBatch);
-  if (i == 0) {
-    counts[1] = *flag ? pairs_status(*flag) : 0;
-    if (values && values_rows < words[PW_N]) atomicOr(own_flag, kFieldsFlagValues);
-  }
-  if (!queries || i >= n_queries) return;
-  const XY q = queries[i];
-  const double ax = fabs(q.x), ay = fabs(q.y);
-  const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-  if ((fx && !(ax / radius < kPairsDomain)) || (fy && !(ay / radius < kPairsDomain))) atomicOr(own_flag, kFieldsFlagDomain);
-}
 
 // 1 - d2 / r2 to the power: 1, t, t t, (t t) t.  Power 0 computes no division.
 __device__ __forceinline__ double fields_weight(int power, double d2, double r2) {
@@ -91,19 +63,16 @@ __device__ __forceinline__ double fields_weight(int power, double d2, double r2)
 // weight sums only.
 template <int C, bool batched>
 __global__ void __launch_bounds__(kBlock)
-    k_fields_sum(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag,
-                 const int* __restrict__ own_flag, const XY* __restrict__ xy, const XY* __restrict__ queries,
-                 long long n_queries, int self, int power, int channels, const int* __restrict__ start,
-                 const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx,
-                 const double* __restrict__ values, FieldsOut out, PairsBatch bt) {
+    k_fields_sum(PairsView v, const int* __restrict__ own_flag, const XY* __restrict__ queries, long long n_queries, int self,
+                 int power, int channels, const double* __restrict__ values, FieldsOut out) {
   __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
   const int tid = (int)threadIdx.x;
   const long long i = (long long)blockIdx.x * blockDim.x + tid;
   const int own = *own_flag;
-  const bool up = *flag || own;
-  const long long rows = queries ? n_queries : words[PW_N];
+  const bool up = *v.flag || own;
+  const long long rows = queries ? n_queries : v.words[PW_N];
   if (i == 0) {
-    if (up) out.counts[1] = fields_status(*flag, own);
+    if (up) out.counts[1] = reader_status(*v.flag, own);
     else out.counts[0] = rows;
   }
   if (up || i >= rows) return;  // (no barrier below: every thread is on its own)
@@ -111,50 +80,24 @@ __global__ void __launch_bounds__(kBlock)
   double acc[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) acc[c] = 0.0;
-  const XY p = queries ? queries[i] : xy[i];
+  const XY p = queries ? queries[i] : v.xy[i];
   if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
     const int me = queries || self ? -1 : (int)i;  // (no j is -1)
-    const PairsRow row = pairs_row<batched>(bt, i);
-    const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
-    for (int c = 0; c < 9; ++c) {
-      const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-      const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
-      const int end = start[b + 1];
-      const int k = pairs_advance<batched>(g, row, me, p, cx, cy, start[b], end, sxy, scell, sidx);
-      s_cur[c][tid] = k;
-      s_end[c][tid] = end;
-      s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
-    }
-    for (;;) {
-      int best = INT_MAX, bc = 0;
-#pragma unroll
-      for (int c = 0; c < 9; ++c) {
-        const int h = s_head[c][tid];
-        if (h < best) {
-          best = h;
-          bc = c;
-        }
-      }
-      if (best == INT_MAX) break;  // every run is at its end
-      const int k = s_cur[bc][tid];
+    pairs_merge<batched>(v, pairs_row<batched>(v.bt, i), me, p, s_cur, s_end, s_head, tid, [&](int j, XY q) {
       double d2;
-      (void)pairs_accept(g, me, best, p, sxy[k], d2);
-      const double w = fields_weight(power, d2, g.r2);
+      (void)pairs_accept(v.g, me, j, p, q, d2);
+      const double w = fields_weight(power, d2, v.g.r2);
       wsum += w;
       if (values) {
-        const double* src = values + (long long)best * channels;
-        double v[C];  // (all loads first, then the sums: a load guarded next to its use waits for the one before)
+        const double* src = values + (long long)j * channels;
+        double val[C];  // (all loads first, then the sums: a load guarded next to its use waits for the one before)
 #pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = c < channels ? src[c] : 0.0;
+        for (int c = 0; c < C; ++c) val[c] = c < channels ? src[c] : 0.0;
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] += w * v[c];
+        for (int c = 0; c < C; ++c) acc[c] += w * val[c];
       }
-      const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
-      const int end = s_end[bc][tid];
-      const int next = pairs_advance<batched>(g, row, me, p, cx, cy, k + 1, end, sxy, scell, sidx);
-      s_cur[bc][tid] = next;
-      s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
-    }
+      return true;
+    });
   }
   if (out.wsum) out.wsum[i] = wsum;
   if (out.sums) {

@@ -12,12 +12,14 @@
 // Why the walk and not the merge.  The readers that add floating-point numbers (sc_fields.h) or store a list
 // (k_pairs_fill) merge a row's nine runs into ascending j, because the walk's own order depends on the table's size.  A
 // histogram is integer counts: the order in which a row's partners are met cannot reach it.  So the walk is that of
-// k_pairs_count -- the nine cells in raster order, the own-cell test, pairs_accept -- with no cursors.
+// k_pairs_count -- the nine cells in raster order, the own-cell test, pairs_accept -- with no cursors, written out here
+// (sc_pairs.h says why it is not one function).
 //
 // Everything about the points is read from the workspace the last count left (sc_pairs.h), and nothing of it is written:
 // a fill, a label, a table, a sum or another histogram may follow.
-//   k_hist_check   prepares counts[1] and raises the flag OF THE HISTOGRAM for a query outside the domain (the count's stays
-//                  as the count left it).  The flag and the accumulator of the totals were zeroed on the stream before;
+//   k_reader_check (sc_pairs.h) prepares counts[1] and raises the flag OF THE HISTOGRAM for a query outside the domain (the
+//                  count's stays as the count left it).  The flag and the accumulator of the totals were zeroed on the
+//                  stream before, by one memset: the flag is the word behind the accumulator, not the other readers';
 //   k_hist<NB>     a thread per row walks, places every accepted d2 by a binary search over e2 in LDS and adds one to
 //                  its own counter; then the workgroup writes its block of rows of the table together and adds its
 //                  column sums to the accumulator;
@@ -65,27 +67,12 @@ struct HistOut {
   long long* counts;  // [2]: rows, status
 };
 
-// `queries` null: the self form, no point to test.
-__global__ void __launch_bounds__(kBlock)
-    k_hist_check(double radius, const XY* __restrict__ queries, long long n_queries, const int* __restrict__ flag,
-                 int* __restrict__ own_flag, long long* __restrict__ counts) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) counts[1] = *flag ? -1 : 0;
-  if (!queries || i >= n_queries) return;
-  const XY q = queries[i];
-  const double ax = fabs(q.x), ay = fabs(q.y);
-  const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-  if ((fx && !(ax / radius < kPairsDomain)) || (fy && !(ay / radius < kPairsDomain))) atomicOr(own_flag, 1);
-}
-
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]); otherwise row i is queries[i] (n_queries rows).
-// g.r2 is e2[bins], at most the count's; g.h and g.mask are the count's.
+// v.g.r2 is e2[bins], at most the count's; v.g.h and v.g.mask are the count's.
 template <int NB>
 __global__ void __launch_bounds__(kHistBlock)
-    k_hist(PairsGrid g, HistEdges edges, int bins, const long long* __restrict__ words, const int* __restrict__ flag,
-           const int* __restrict__ own_flag, const XY* __restrict__ xy, const XY* __restrict__ queries, long long n_queries,
-           const int* __restrict__ start, const XY* __restrict__ sxy, const uint2* __restrict__ scell,
-           const int* __restrict__ sidx, long long* __restrict__ acc, HistOut out) {
+    k_hist(PairsView v, HistEdges edges, int bins, const int* __restrict__ own_flag, const XY* __restrict__ queries,
+           long long n_queries, long long* __restrict__ acc, HistOut out) {
   constexpr int W = kHistBlock;
   static_assert(NB <= W, "lane b loads edge b and sums bin b");
   __shared__ double s_e2[NB];
@@ -94,10 +81,10 @@ __global__ void __launch_bounds__(kHistBlock)
   const int tid = (int)threadIdx.x;
   const long long base = (long long)blockIdx.x * W;
   const long long i = base + tid;
-  const bool up = *flag || *own_flag;
-  const long long rows = queries ? n_queries : words[PW_N];
+  const bool up = *v.flag || *own_flag;
+  const long long rows = queries ? n_queries : v.words[PW_N];
   if (blockIdx.x == 0 && tid == 0) {
-    if (up) out.counts[1] = -1;
+    if (up) out.counts[1] = reader_status(*v.flag, *own_flag);
     else out.counts[0] = rows;
   }
   if (up) return;  // (uniform over the launch: nobody is left at the barriers below)
@@ -105,19 +92,19 @@ __global__ void __launch_bounds__(kHistBlock)
   for (int b = 0; b < bins; ++b) s_bins[b][tid] = 0;
   __syncthreads();
   if (i < rows) {
-    const XY p = queries ? queries[i] : xy[i];
+    const XY p = queries ? queries[i] : v.xy[i];
     if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
       const int me = queries ? -1 : (int)i;  // (no j is -1)
       const double first = s_e2[0];
-      const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
+      const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
       for (int c = 0; c < 9; ++c) {
         const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-        const unsigned bk = pairs_bucket(cx, cy, g.mask);
-        const int end = start[bk + 1];
-        for (int k = start[bk]; k < end; ++k) {
-          const uint2 cell = scell[k];
+        const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);  // (never batched: the host refuses)
+        const int end = v.start[bk + 1];
+        for (int k = v.start[bk]; k < end; ++k) {
+          const uint2 cell = v.scell[k];
           double d2;
-          if (!(cell.x == cx && cell.y == cy && pairs_accept(g, me, sidx[k], p, sxy[k], d2))) continue;
+          if (!(cell.x == cx && cell.y == cy && pairs_accept(v.g, me, v.sidx[k], p, v.sxy[k], d2))) continue;
           if (d2 < first) continue;  // below the first edge: in no bin
           int b = 0;                 // the last edge among 1 .. bins - 1 that is at most d2
 #pragma unroll

@@ -218,11 +218,15 @@ struct StateIo {
 // The batched form (sc_pairs_set_batch_device): `ptr`, the count's copy of the offsets, and `cloud`, every point's cloud;
 // `clouds` > 0 says that the grid is batched.  `next_ptr` / `next_clouds` wait for the next count, `next_qptr` for the
 // next query-form reader: the caller's device memory, read by that call's launches only.
+// `readerFlag`: the flag of the reader that runs (sc_nearest.h, sc_fields.h, sc_fields_grad.h) -- a query outside the
+// domain, an array of the caller's with too few rows, bad query offsets.  A flag apart from the count's, which stays as
+// the count left it: a fill or a label after a reader still reads it.  One word for all of them: every reader zeroes it
+// before its check, on the one stream, so no call's verdict reaches the next.
 struct PairsSpace {
   DevBuf<XY> xy, sxy;
   DevBuf<uint2> cell;
   RadixSpace sort;
-  DevBuf<int> bucketCount, bucketStart, bucketSums, rowLen, flag, cloud;
+  DevBuf<int> bucketCount, bucketStart, bucketSums, rowLen, flag, readerFlag, cloud;
   DevBuf<long long> offs, sums, words, ptr;
   bool valid = false;
   int64_t m = 0;  // ... the bound its launches were sized by
@@ -232,9 +236,19 @@ struct PairsSpace {
   const int64_t* next_ptr = nullptr;
   int64_t next_clouds = 0;
   const int64_t* next_qptr = nullptr;
-  // The grid as the walking kernels see it; `qptr` null: the self form.
-  PairsBatch batch(const int64_t* qptr) const {
-    return PairsBatch{ptr.get(), (const long long*)qptr, cloud.get(), (int)clouds};
+  // The workspace as a reader's kernels see it: the full list (`half` off), whichever form the count had.  `qptr`: the
+  // query offsets of a batched grid, null in the self form.
+  PairsView view(const int64_t* qptr) const {
+    PairsView v{grid, words.get(), flag.get(), xy.get(), bucketStart.get(), sxy.get(), cell.get(), sort.vals[set].get(),
+                PairsBatch{ptr.get(), (const long long*)qptr, cloud.get(), (int)clouds}};
+    v.g.half = 0;
+    return v;
+  }
+  // ... and as the count and the fill see it: with the count's `half`.
+  PairsView view_of_count() const {
+    PairsView v = view(nullptr);
+    v.g.half = grid.half;
+    return v;
   }
   // The offsets a query-form reader of a batched grid was given (consumed); false when there are none.
   bool take_query_batch(bool query_form, const int64_t** qptr) {
@@ -247,6 +261,7 @@ struct PairsSpace {
   // Room for a search over n points in `buckets` buckets.
   int ensure(int64_t n, int64_t buckets, hipStream_t stream) {
     HIPCHK(flag.grow(1, stream));
+    HIPCHK(readerFlag.grow(1, stream));
     HIPCHK(words.grow(PW_WORDS, stream));
     if (buckets + 1 > bucketStart.size()) {
       HIPCHK(bucketCount.grow(buckets, stream));
@@ -283,30 +298,9 @@ struct ClusterSpace {
   }
 };
 
-// sc_pairs_nearest_device (sc_nearest.h; sc_host_state.h): the flag a query outside the domain raises -- a flag of its own:
-// the count's stays as the count left it, a fill or a label after the table still reads it.
-struct NearestSpace {
-  DevBuf<int> flag;
-  int ensure(hipStream_t stream) {
-    HIPCHK(flag.grow(1, stream));
-    return SC_OK;
-  }
-};
-
-// sc_pairs_sum_device (sc_fields.h; sc_host_state.h): the flag of the call's own -- a query outside the domain, values
-// with fewer rows than the count has points: the count's flag stays as the count left it.  sc_pairs_sum_grad_device
-// (sc_fields_grad.h) raises the same flag for the same reasons: every call zeroes it first, on the one stream.
-struct FieldsSpace {
-  DevBuf<int> flag;
-  int ensure(hipStream_t stream) {
-    HIPCHK(flag.grow(1, stream));
-    return SC_OK;
-  }
-};
-
 // sc_pairs_hist_device (sc_hist.h; sc_host_state.h): the accumulator of the totals, kHistMaxBins 64-bit words, and behind
 // it the word that holds the flag of the call's own -- a query outside the domain: the count's flag stays as the count
-// left it.  One buffer, so that one memset prepares both.
+// left it.  One buffer, so that one memset prepares both; the readers' check gets the flag's address and nothing else.
 struct HistSpace {
   DevBuf<long long> words;
   int ensure(hipStream_t stream) {
@@ -443,8 +437,6 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   StateIo state;
   PairsSpace pairs;
   ClusterSpace clusters;
-  NearestSpace nearest;
-  FieldsSpace fields;
   HistSpace hist;
   Snapshot snap;
   SlabLink link;

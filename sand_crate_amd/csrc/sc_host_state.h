@@ -150,25 +150,25 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   HIPCHK(hipMemsetAsync(c->pairs.bucketCount, 0, (size_t)buckets * sizeof(int), c->stream));
   RadixSpace& w = c->pairs.sort;
   c->pairs.clouds = clouds;
-  const PairsBatch bt = c->pairs.batch(nullptr);
+  c->pairs.grid = g;
   if (clouds)
     hipLaunchKernelGGL(k_pairs_batch_check, dim3(grid_for(clouds + 1)), dim3(kBlock), 0, c->stream, (const long long*)batch_ptr,
                        c->pairs.ptr.get(), (int)clouds, (long long)n, c->pairs.flag.get());
   hipLaunchKernelGGL(clouds ? k_pairs_key<true> : k_pairs_key<false>, dim3(grid), dim3(kBlock), 0, c->stream, g,
                      dev_xy ? (const XY*)dev_xy : c->pairs.xy.get(), c->pairs.xy.get(), dev_xy ? (long long)n : -1LL,
                      c->pairs.words.get(), (int)m, w.keys[0].get(), w.vals[0].get(), c->pairs.bucketCount.get(),
-                     c->pairs.flag.get(), bt, c->pairs.cloud.get());
+                     c->pairs.flag.get(), c->pairs.ptr.get(), (int)clouds, c->pairs.cloud.get());
   // the binning sort: the keys are 0 .. buckets (a dead point's), so as many digits as `buckets` has
   int bits = 1;
   while ((buckets >> bits) != 0) ++bits;
   int in;
   if ((rc = radix_sort(c, w, RadixStored{}, m, (bits + kRadixDigitBits - 1) / kRadixDigitBits, &in))) return rc;
+  c->pairs.set = in;
   if ((rc = launch_scan(c, c->pairs.bucketCount, c->pairs.bucketStart, buckets, c->pairs.bucketSums, nullptr))) return rc;
   hipLaunchKernelGGL(k_pairs_place, dim3(grid), dim3(kBlock), 0, c->stream, g, w.keys[in].get(), w.vals[in].get(), (int)m,
                      c->pairs.xy.get(), c->pairs.flag.get(), c->pairs.sxy.get(), c->pairs.cell.get());
-  hipLaunchKernelGGL(clouds ? k_pairs_count<true> : k_pairs_count<false>, dim3(grid), dim3(kBlock), 0, c->stream, g,
-                     c->pairs.words.get(), c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.bucketStart.get(),
-                     c->pairs.sxy.get(), c->pairs.cell.get(), w.vals[in].get(), c->pairs.rowLen.get(), bt);
+  hipLaunchKernelGGL(clouds ? k_pairs_count<true> : k_pairs_count<false>, dim3(grid), dim3(kBlock), 0, c->stream,
+                     c->pairs.view_of_count(), (int)m, c->pairs.rowLen.get());
   const int nb = (int)(m / kScanPerBlock + 1);  // entry n <= m lies in one of them
   hipLaunchKernelGGL(k_scan64_local, dim3(nb), dim3(kBlock), 0, c->stream, c->pairs.rowLen.get(), c->pairs.offs.get(),
                      c->pairs.words.get(), c->pairs.flag.get(), c->pairs.sums.get());
@@ -177,8 +177,6 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   HIPCHK(hipGetLastError());
   c->pairs.valid = true;
   c->pairs.m = m;
-  c->pairs.set = in;
-  c->pairs.grid = g;
   return SC_OK;
 }
 
@@ -193,10 +191,8 @@ int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64
   const int64_t m = c->pairs.m;
   if (room_pairs == 0) return SC_OK;
   hipLaunchKernelGGL(c->pairs.clouds ? k_pairs_fill<true> : k_pairs_fill<false>, dim3(grid_for(m)), dim3(kBlock), 0, c->stream,
-                     c->pairs.grid, c->pairs.words.get(), c->pairs.flag.get(), (int)m, c->pairs.xy.get(), c->pairs.offs.get(),
-                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), (long long*)dev_partners, dev_d2, (long long)room_pairs,
-                     c->pairs.batch(nullptr));
+                     c->pairs.view_of_count(), (int)m, c->pairs.offs.get(), (long long*)dev_partners, dev_d2,
+                     (long long)room_pairs);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -218,16 +214,13 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
   HIPCHK(hipSetDevice(c->device));
   int rc = c->clusters.ensure(m, c->stream);
   if (rc) return rc;
-  PairsGrid g = c->pairs.grid;
-  g.half = 0;  // the components are those of the full graph, whichever form the count had
   const int grid = grid_for(m);
   const long long* words = c->pairs.words.get();
   const int* flag = c->pairs.flag.get();
   int* parent = c->clusters.parent.get();
   hipLaunchKernelGGL(k_cluster_init, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
-  hipLaunchKernelGGL(k_cluster_union, dim3(grid), dim3(kBlock), 0, c->stream, g, words, flag, (int)m, c->pairs.xy.get(),
-                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), parent);
+  // (the view's `half` is off: the components are those of the full graph, whichever form the count had)
+  hipLaunchKernelGGL(k_cluster_union, dim3(grid), dim3(kBlock), 0, c->stream, c->pairs.view(nullptr), (int)m, parent);
   // a tree of at most m nodes is at most m - 1 deep, and a round halves (rounding up) every depth
   int rounds = 1;
   while (((int64_t)1 << rounds) < m) ++rounds;
@@ -245,23 +238,82 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
   return SC_OK;
 }
 
-// ---- nearest-k tables (sc_nearest.h) -------------------------------------------------------------
-
 }  // extern "C"
 
-template <int K>
-static void nearest_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int k, const NearestOut& out,
-                           const PairsBatch& bt) {
-  const int64_t grid = std::max<int64_t>(1, (rows + kNearestBlock - 1) / kNearestBlock);  // (one at least: it writes the counts)
-  hipLaunchKernelGGL((bt.clouds ? k_nearest<K, true> : k_nearest<K, false>), dim3((unsigned)grid), dim3(kNearestBlock), 0,
-                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->nearest.flag.get(), c->pairs.xy.get(), queries,
-                     (long long)rows, k, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), out, bt);
+// ---- what the readers with rows of their own share: tables, sums, gradients, histograms -------------------------
+
+// A reader's call as its messages name it.
+struct ReaderCall {
+  const char* who;     // the function
+  const char* verb;    // "no pair count to <verb>"
+  const char* holder;  // "<holder> <room> rows": the caller's array with a row per row, and its verb
+  bool batched_ok;     // reads a batched grid
+  bool holds_rows;     // the caller gave such an array: its room is tested against the rows
+};
+
+// ... and what it launches with.
+struct Reader {
+  int64_t rows;
+  const XY* queries;  // null: the self form
+  PairsView view;
+};
+
+// The checks and the preparation every reader begins with, after the checks of its own arguments.
+static int reader_begin(sc_ctx* c, const ReaderCall& call, const double* dev_queries, int64_t n_queries, int64_t room_rows,
+                        Reader* r) {
+  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
+  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
+  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "%s inside a tick", call.who);
+  if (!c->pairs.valid)
+    return fail(SC_ERR_STATE, "no pair count to %s: sc_pairs_count_device comes first, and the state must not change in between",
+                call.verb);
+  if (!call.batched_ok)
+    if (const int rc = pairs_refuse_batched(c, call.who)) return rc;
+  if (dev_queries && n_queries > kPairsMaxPoints)
+    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
+  r->rows = dev_queries ? n_queries : c->pairs.m;
+  if (call.holds_rows && room_rows < r->rows)
+    return fail(SC_ERR_CAPACITY, "%s %lld rows, up to %lld %s", call.holder, (long long)room_rows, (long long)r->rows,
+                dev_queries ? "queries" : "points");
+  const int64_t* qptr;
+  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
+    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
+  HIPCHK(hipSetDevice(c->device));
+  r->queries = (const XY*)dev_queries;
+  r->view = c->pairs.view(qptr);
+  return SC_OK;
 }
 
-// The launch of a reader's check kernel: a thread per query, and on a batched grid per entry of query_ptr.
-static int check_grid(int64_t rows, const int64_t* qptr, int64_t clouds) {
-  return grid_for(qptr ? std::max<int64_t>(rows, clouds + 1) : rows);
+// The reader's own flag zeroed -- the `zero_bytes` from `zero` on, which hold it --, then k_reader_check: a thread per
+// query, and on a batched grid per entry of query_ptr.  `row_rows` / `part_rows`: the rows of the caller's arrays that go
+// by row / by partner, -1 for none.  The radius is the count's.
+static int reader_check(sc_ctx* c, const Reader& r, int* own_flag, void* zero, size_t zero_bytes, int64_t row_rows,
+                        int64_t part_rows, int64_t* dev_counts) {
+  HIPCHK(hipMemsetAsync(zero, 0, zero_bytes, c->stream));
+  const PairsBatch& bt = r.view.bt;
+  const int grid = !r.queries ? 1 : grid_for(bt.qptr ? std::max<int64_t>(r.rows, (int64_t)bt.clouds + 1) : r.rows);
+  hipLaunchKernelGGL(k_reader_check, dim3(grid), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, r.queries,
+                     (long long)r.rows, (long long)row_rows, (long long)part_rows, r.view.words, r.view.flag, own_flag,
+                     (long long*)dev_counts, bt.qptr, bt.clouds);
+  return SC_OK;
+}
+
+// ... for the readers whose flag is the pairs workspace's.
+static int reader_check(sc_ctx* c, const Reader& r, int64_t row_rows, int64_t part_rows, int64_t* dev_counts) {
+  int* own = c->pairs.readerFlag.get();
+  return reader_check(c, r, own, own, sizeof(int), row_rows, part_rows, dev_counts);
+}
+
+// ---- nearest-k tables (sc_nearest.h) -------------------------------------------------------------
+
+template <int K>
+static void nearest_launch(sc_ctx* c, const Reader& r, int k, const NearestOut& out) {
+  const int64_t grid = std::max<int64_t>(1, (r.rows + kNearestBlock - 1) / kNearestBlock);  // (one at least: it writes the counts)
+  const PairsView& v = r.view;  // (unpacked: k_nearest alone keeps loose arguments, sc_nearest.h says why)
+  hipLaunchKernelGGL((v.bt.clouds ? k_nearest<K, true> : k_nearest<K, false>), dim3((unsigned)grid), dim3(kNearestBlock), 0,
+                     c->stream, v.g, v.words, v.flag, c->pairs.readerFlag.get(), v.xy, r.queries, (long long)r.rows, k, v.start,
+                     v.sxy, v.scell, v.sidx, out, v.bt);
 }
 
 extern "C" {
@@ -271,52 +323,30 @@ int sc_pairs_nearest_device(sc_ctx* c, const double* dev_queries, int64_t n_quer
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_neighbors || !dev_counts) return fail(SC_ERR_ARG, "null neighbors or counts pointer");
   if (k < 1 || k > SC_NEAREST_MAX_K) return fail(SC_ERR_ARG, "k is %d, it must be 1 .. %d", (int)k, (int)SC_NEAREST_MAX_K);
-  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
-  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
-  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_nearest_device inside a tick");
-  if (!c->pairs.valid)
-    return fail(SC_ERR_STATE, "no pair count to search in: sc_pairs_count_device comes first, and the state must not change in between");
-  if (dev_queries && n_queries > kPairsMaxPoints)
-    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
-  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
-  if (room_rows < rows)
-    return fail(SC_ERR_CAPACITY, "the table holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
-                dev_queries ? "queries" : "points");
-  const int64_t* qptr;
-  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
-    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
-  HIPCHK(hipSetDevice(c->device));
-  const int rc = c->nearest.ensure(c->stream);
-  if (rc) return rc;
   static_assert(kNearestMaxK == SC_NEAREST_MAX_K, "the header's bound is the kernel's");
-  PairsGrid g = c->pairs.grid;
-  g.half = 0;  // the table is cut from the full list, whichever form the count had
-  const XY* queries = (const XY*)dev_queries;
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_nearest_device", "search in", "the table holds", true, true}, dev_queries,
+                                  n_queries, room_rows, &r))
+    return rc;
   const NearestOut out{(long long*)dev_neighbors, dev_d2, (long long*)dev_partners, (long long*)dev_counts};
-  HIPCHK(hipMemsetAsync(c->nearest.flag, 0, sizeof(int), c->stream));
-  const PairsBatch bt = c->pairs.batch(qptr);
-  hipLaunchKernelGGL(k_nearest_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
-                     g.radius, queries, (long long)n_queries, c->pairs.flag.get(), c->nearest.flag.get(), out.counts,
-                     bt.qptr, bt.clouds);
-  if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, g, queries, rows, k, out, bt);
-  else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, g, queries, rows, k, out, bt);
-  else nearest_launch<kNearestMaxK>(c, g, queries, rows, k, out, bt);
+  if (const int rc = reader_check(c, r, -1, -1, dev_counts)) return rc;
+  if (k <= kNearestFewK) nearest_launch<kNearestFewK>(c, r, k, out);
+  else if (k <= kNearestMidK) nearest_launch<kNearestMidK>(c, r, k, out);
+  else nearest_launch<kNearestMaxK>(c, r, k, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
 
-// ---- weighted neighbourhood sums (sc_fields.h) ---------------------------------------------------
-
 }  // extern "C"
 
+// ---- weighted neighbourhood sums (sc_fields.h) ---------------------------------------------------
+
 template <int C>
-static void fields_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int self, int power, int channels,
-                          const double* values, const FieldsOut& out, const PairsBatch& bt) {
-  hipLaunchKernelGGL((bt.clouds ? k_fields_sum<C, true> : k_fields_sum<C, false>), dim3(grid_for(rows)), dim3(kBlock), 0,
-                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries,
-                     (long long)rows, self, power, channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(),
-                     c->pairs.cell.get(), c->pairs.sort.vals[c->pairs.set].get(), values, out, bt);
+static void fields_launch(sc_ctx* c, const Reader& r, int self, int power, int channels, const double* values,
+                          const FieldsOut& out) {
+  hipLaunchKernelGGL((r.view.bt.clouds ? k_fields_sum<C, true> : k_fields_sum<C, false>), dim3(grid_for(r.rows)), dim3(kBlock), 0,
+                     c->stream, r.view, c->pairs.readerFlag.get(), r.queries, (long long)r.rows, self, power, channels, values,
+                     out);
 }
 
 extern "C" {
@@ -333,54 +363,34 @@ int sc_pairs_sum_device(sc_ctx* c, const double* dev_queries, int64_t n_queries,
   if (power < 0 || power > 3) return fail(SC_ERR_ARG, "power is %d, it must be 0 .. 3", (int)power);
   if (flags & ~SC_FIELDS_SELF) return fail(SC_ERR_ARG, "unknown flags %d", flags);
   if (room_rows < 0 || values_rows < 0) return fail(SC_ERR_ARG, "negative room or number of value rows");
-  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
-  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_sum_device inside a tick");
-  if (!c->pairs.valid)
-    return fail(SC_ERR_STATE, "no pair count to sum over: sc_pairs_count_device comes first, and the state must not change in between");
-  if (dev_queries && n_queries > kPairsMaxPoints)
-    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
-  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
-  if (room_rows < rows)
-    return fail(SC_ERR_CAPACITY, "the sums hold %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
-                dev_queries ? "queries" : "points");
-  const int64_t* qptr;
-  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
-    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
-  HIPCHK(hipSetDevice(c->device));
   static_assert(kFieldsMaxChannels == SC_FIELDS_MAX_CHANNELS, "the header's bound is the kernel's");
-  const int rc = c->fields.ensure(c->stream);
-  if (rc) return rc;
-  PairsGrid g = c->pairs.grid;
-  g.half = 0;  // the sums run over the full list, whichever form the count had
-  const XY* queries = (const XY*)dev_queries;
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_sum_device", "sum over", "the sums hold", true, true}, dev_queries, n_queries,
+                                  room_rows, &r))
+    return rc;
   const double* values = channels ? dev_values : nullptr;
   const FieldsOut out{channels ? dev_sums : nullptr, dev_wsum, (long long*)dev_counts};
   const int self = (flags & SC_FIELDS_SELF) ? 1 : 0;
-  HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
-  const PairsBatch bt = c->pairs.batch(qptr);
-  hipLaunchKernelGGL(k_fields_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
-                     g.radius, queries, (long long)n_queries, values, (long long)values_rows, c->pairs.words.get(),
-                     c->pairs.flag.get(), c->fields.flag.get(), out.counts, bt.qptr, bt.clouds);
-  if (channels <= 1) fields_launch<1>(c, g, queries, rows, self, power, channels, values, out, bt);
-  else if (channels <= 2) fields_launch<2>(c, g, queries, rows, self, power, channels, values, out, bt);
-  else if (channels <= 4) fields_launch<4>(c, g, queries, rows, self, power, channels, values, out, bt);
-  else fields_launch<8>(c, g, queries, rows, self, power, channels, values, out, bt);
+  if (const int rc = reader_check(c, r, -1, values ? values_rows : -1, dev_counts)) return rc;
+  if (channels <= 1) fields_launch<1>(c, r, self, power, channels, values, out);
+  else if (channels <= 2) fields_launch<2>(c, r, self, power, channels, values, out);
+  else if (channels <= 4) fields_launch<4>(c, r, self, power, channels, values, out);
+  else fields_launch<8>(c, r, self, power, channels, values, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
 
-// ---- the position gradient of the sums (sc_fields_grad.h) -----------------------------------------
-
 }  // extern "C"
 
+// ---- the position gradient of the sums (sc_fields_grad.h) -----------------------------------------
+
 template <int C>
-static void fields_grad_launch(sc_ctx* c, const PairsGrid& g, const XY* queries, int64_t rows, int power, int channels,
-                               const FieldsGradIn& in, double* grad, long long* counts, const PairsBatch& bt) {
-  hipLaunchKernelGGL((bt.clouds ? k_fields_grad<C, true> : k_fields_grad<C, false>), dim3(grid_for(rows)), dim3(kBlock), 0,
-                     c->stream, g, c->pairs.words.get(), c->pairs.flag.get(), c->fields.flag.get(), c->pairs.xy.get(), queries,
-                     (long long)rows, power, channels, c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), in, (XY*)grad, counts, bt);
+static void fields_grad_launch(sc_ctx* c, const Reader& r, int power, int channels, const FieldsGradIn& in, double* grad,
+                               long long* counts) {
+  const PairsView& v = r.view;  // (unpacked, as for k_nearest: sc_fields_grad.h says why)
+  hipLaunchKernelGGL((v.bt.clouds ? k_fields_grad<C, true> : k_fields_grad<C, false>), dim3(grid_for(r.rows)), dim3(kBlock), 0,
+                     c->stream, v.g, v.words, v.flag, c->pairs.readerFlag.get(), v.xy, r.queries, (long long)r.rows, power,
+                     channels, v.start, v.sxy, v.scell, v.sidx, in, (XY*)grad, counts, v.bt);
 }
 
 extern "C" {
@@ -397,54 +407,34 @@ int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_que
   if (channels > 0 && (!dev_row_a || !dev_part_b)) return fail(SC_ERR_ARG, "null row_a or part_b pointer with %d channels", (int)channels);
   if (power < 0 || power > 3) return fail(SC_ERR_ARG, "power is %d, it must be 0 .. 3", (int)power);
   if (room_rows < 0 || row_a_rows < 0 || part_b_rows < 0) return fail(SC_ERR_ARG, "negative room or number of rows");
+  // (reader_begin's check, here as well: it goes before the gradient's alignment, which is tested with the queries')
   if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
   if (((uintptr_t)dev_queries | (uintptr_t)dev_grad) & 15) return fail(SC_ERR_ARG, "the queries and the gradient must be aligned to 16 bytes");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_sum_grad_device inside a tick");
-  if (!c->pairs.valid)
-    return fail(SC_ERR_STATE, "no pair count to sum over: sc_pairs_count_device comes first, and the state must not change in between");
-  if (dev_queries && n_queries > kPairsMaxPoints)
-    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
-  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
-  if (room_rows < rows)
-    return fail(SC_ERR_CAPACITY, "the gradient holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
-                dev_queries ? "queries" : "points");
-  const int64_t* qptr;
-  if (!c->pairs.take_query_batch(dev_queries != nullptr, &qptr))
-    return fail(SC_ERR_ARG, "queries on a batched grid need sc_pairs_set_query_batch_device first");
-  HIPCHK(hipSetDevice(c->device));
-  const int rc = c->fields.ensure(c->stream);
-  if (rc) return rc;
-  PairsGrid g = c->pairs.grid;
-  g.half = 0;  // the gradient runs over the full list, whichever form the count had
-  const XY* queries = (const XY*)dev_queries;
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_sum_grad_device", "sum over", "the gradient holds", true, true}, dev_queries,
+                                  n_queries, room_rows, &r))
+    return rc;
   const FieldsGradIn in{channels ? dev_row_a : nullptr, channels ? dev_part_b : nullptr, dev_row_s, dev_part_s};
   long long* counts = (long long*)dev_counts;
-  HIPCHK(hipMemsetAsync(c->fields.flag, 0, sizeof(int), c->stream));
-  const PairsBatch bt = c->pairs.batch(qptr);
-  hipLaunchKernelGGL(k_fields_grad_check, dim3(queries ? check_grid(rows, qptr, bt.clouds) : 1), dim3(kBlock), 0, c->stream,
-                     g.radius, queries, (long long)n_queries, in.row_a || in.row_s ? 1 : 0, (long long)row_a_rows,
-                     in.part_b || in.part_s ? 1 : 0, (long long)part_b_rows, c->pairs.words.get(), c->pairs.flag.get(),
-                     c->fields.flag.get(), counts, bt.qptr, bt.clouds);
-  if (channels <= 1) fields_grad_launch<1>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
-  else if (channels <= 2) fields_grad_launch<2>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
-  else if (channels <= 4) fields_grad_launch<4>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
-  else fields_grad_launch<8>(c, g, queries, rows, power, channels, in, dev_grad, counts, bt);
+  if (const int rc = reader_check(c, r, in.row_a || in.row_s ? row_a_rows : -1, in.part_b || in.part_s ? part_b_rows : -1, dev_counts))
+    return rc;
+  if (channels <= 1) fields_grad_launch<1>(c, r, power, channels, in, dev_grad, counts);
+  else if (channels <= 2) fields_grad_launch<2>(c, r, power, channels, in, dev_grad, counts);
+  else if (channels <= 4) fields_grad_launch<4>(c, r, power, channels, in, dev_grad, counts);
+  else fields_grad_launch<8>(c, r, power, channels, in, dev_grad, counts);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
 
-// ---- distance histograms (sc_hist.h) --------------------------------------------------------------
-
 }  // extern "C"
 
+// ---- distance histograms (sc_hist.h) --------------------------------------------------------------
+
 template <int NB>
-static void hist_launch(sc_ctx* c, const PairsGrid& g, const HistEdges& edges, int bins, const XY* queries, int64_t rows,
-                        const HistOut& out) {
-  const int64_t grid = std::max<int64_t>(1, (rows + kHistBlock - 1) / kHistBlock);  // (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_hist<NB>, dim3((unsigned)grid), dim3(kHistBlock), 0, c->stream, g, edges, bins, c->pairs.words.get(),
-                     c->pairs.flag.get(), c->hist.flag(), c->pairs.xy.get(), queries, (long long)rows,
-                     c->pairs.bucketStart.get(), c->pairs.sxy.get(), c->pairs.cell.get(),
-                     c->pairs.sort.vals[c->pairs.set].get(), c->hist.acc(), out);
+static void hist_launch(sc_ctx* c, const Reader& r, const HistEdges& edges, int bins, const HistOut& out) {
+  const int64_t grid = std::max<int64_t>(1, (r.rows + kHistBlock - 1) / kHistBlock);  // (one at least: it writes the counts)
+  hipLaunchKernelGGL(k_hist<NB>, dim3((unsigned)grid), dim3(kHistBlock), 0, c->stream, r.view, edges, bins, c->hist.flag(),
+                     r.queries, (long long)r.rows, c->hist.acc(), out);
 }
 
 extern "C" {
@@ -459,40 +449,26 @@ int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries
   if (!(edges2[0] >= 0) || !std::isfinite(edges2[0])) return fail(SC_ERR_ARG, "the first squared edge must be finite and not negative");
   for (int k = 0; k < bins; ++k)
     if (!(edges2[k] < edges2[k + 1])) return fail(SC_ERR_ARG, "the squared edges must be strictly ascending (edge %d is not)", k + 1);
-  if (room_rows < 0) return fail(SC_ERR_ARG, "negative room");
-  if (dev_queries && n_queries < 0) return fail(SC_ERR_ARG, "negative query count");
-  if ((uintptr_t)dev_queries & 15) return fail(SC_ERR_ARG, "the queries must be aligned to 16 bytes");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_hist_device inside a tick");
-  if (!c->pairs.valid)
-    return fail(SC_ERR_STATE, "no pair count to take a histogram of: sc_pairs_count_device comes first, and the state must not change in between");
-  if (const int rc = pairs_refuse_batched(c, "sc_pairs_hist_device")) return rc;
+  static_assert(kHistMaxBins == SC_HIST_MAX_BINS, "the header's bound is the kernel's");
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_hist_device", "take a histogram of", "the table holds", false, dev_table != nullptr},
+                                  dev_queries, n_queries, room_rows, &r))
+    return rc;
   if (!(edges2[bins] <= c->pairs.grid.r2))
     return fail(SC_ERR_ARG, "the last squared edge %.17g lies beyond the count's squared radius %.17g", edges2[bins], c->pairs.grid.r2);
-  if (dev_queries && n_queries > kPairsMaxPoints)
-    return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
-  const int64_t rows = dev_queries ? n_queries : c->pairs.m;
-  if (dev_table && room_rows < rows)
-    return fail(SC_ERR_CAPACITY, "the table holds %lld rows, up to %lld %s", (long long)room_rows, (long long)rows,
-                dev_queries ? "queries" : "points");
-  HIPCHK(hipSetDevice(c->device));
-  static_assert(kHistMaxBins == SC_HIST_MAX_BINS, "the header's bound is the kernel's");
-  const int rc = c->hist.ensure(c->stream);
-  if (rc) return rc;
-  PairsGrid g = c->pairs.grid;
-  g.half = 0;           // the histogram runs over the full list, whichever form the count had
-  g.r2 = edges2[bins];  // ... up to its own last edge: the cells are the count's, which are no smaller
+  if (const int rc = c->hist.ensure(c->stream)) return rc;
+  r.view.g.r2 = edges2[bins];  // the full list up to the histogram's own last edge: the cells are the count's, which are no smaller
   HistEdges edges{};
   std::copy(edges2, edges2 + bins + 1, edges.e2);
-  const XY* queries = (const XY*)dev_queries;
   const HistOut out{(int*)dev_table, (long long*)dev_total, (long long*)dev_counts};
-  HIPCHK(hipMemsetAsync(c->hist.words, 0, (kHistMaxBins + 1) * sizeof(long long), c->stream));  // the accumulator and the flag
-  hipLaunchKernelGGL(k_hist_check, dim3(queries ? grid_for(rows) : 1), dim3(kBlock), 0, c->stream, c->pairs.grid.radius,
-                     queries, (long long)n_queries, c->pairs.flag.get(), c->hist.flag(), out.counts);
-  if (bins <= kHistFewBins) hist_launch<kHistFewBins>(c, g, edges, bins, queries, rows, out);
-  else if (bins <= kHistMidBins) hist_launch<kHistMidBins>(c, g, edges, bins, queries, rows, out);
-  else hist_launch<kHistMaxBins>(c, g, edges, bins, queries, rows, out);
+  // (one memset: the accumulator and, behind it, the flag)
+  if (const int rc = reader_check(c, r, c->hist.flag(), c->hist.words.get(), (kHistMaxBins + 1) * sizeof(long long), -1, -1, dev_counts))
+    return rc;
+  if (bins <= kHistFewBins) hist_launch<kHistFewBins>(c, r, edges, bins, out);
+  else if (bins <= kHistMidBins) hist_launch<kHistMidBins>(c, r, edges, bins, out);
+  else hist_launch<kHistMaxBins>(c, r, edges, bins, out);
   if (dev_total)
-    hipLaunchKernelGGL(k_hist_finish, dim3(1), dim3(kHistBlock), 0, c->stream, (int)bins, c->pairs.flag.get(), c->hist.flag(),
+    hipLaunchKernelGGL(k_hist_finish, dim3(1), dim3(kHistBlock), 0, c->stream, (int)bins, r.view.flag, c->hist.flag(),
                        c->hist.acc(), out.total);
   HIPCHK(hipGetLastError());
   return SC_OK;

@@ -7,12 +7,13 @@
 // Everything about the points is read from the workspace the last count left (sc_pairs.h): the points in index order, the
 // hashed cell table, the members in bucket order with their positions and cells, n and the domain flag.  The caller's
 // points are not read again, and nothing of the workspace is written: a fill, a label or another table may follow.
-//   k_nearest_check   clears the caller's cut counter (or writes -1 there when the count's flag is up) and, query form,
-//                     tests every query against the domain: one outside raises the flag OF THE NEAREST -- the count's
-//                     stays as the count left it, the fill and the label read it;
+//   k_reader_check    (sc_pairs.h) clears the caller's cut counter (or writes the count's status there when its flag is
+//                     up) and, query form, tests every query against the domain: one outside raises the flag OF THE
+//                     READER -- the count's stays as the count left it, the fill and the label read it;
 //   k_nearest<K>      a thread per row walks the buckets of its row's nine cells as k_pairs_count does -- the own-cell
-//                     test, pairs_accept's arithmetic, `half` off, and j != i in the self form only -- and keeps its k best
-//                     so far, ascending in the key (d2, j), then the workgroup writes its block of rows.
+//                     test, pairs_accept's arithmetic, `half` off, and j != i in the self form only (the walk is written
+//                     out here: sc_pairs.h says why) -- and keeps its k best so far, ascending in the key (d2, j), then
+//                     the workgroup writes its block of rows.
 // The key.  d2 alone does not order a row: a lattice has four partners at bit-equal d2, a pile any number at 0.  The
 // smaller j breaks the tie, so the table is the row of the full pair list, stably sorted by d2 and cut at k: a total order
 // on the candidates, nothing left to the order in which they arrive.  Candidates arrive in bucket order -- the nine cells in
@@ -37,7 +38,7 @@
 // order.  With either flag up the kernel writes counts[1] = -1 and nothing else.
 //
 // On a batched grid (sc_pairs.h) the kernels are the `batched` instantiations: a row carries its record (lo, hi, cloud), a
-// query finds its cloud by binary search over query_ptr, which k_nearest_check tests as the count tested ptr; bad offsets
+// query finds its cloud by binary search over query_ptr, which k_reader_check tests as the count tested ptr; bad offsets
 // give counts[1] = -3.  Rows of several clouds share a workgroup: the write-out does not care whose rows they are.
 #pragma once
 #include "sc_pairs.h"
@@ -58,27 +59,15 @@ struct NearestOut {
   long long* counts;     // [2]: rows, cut
 };
 
-// `queries` null: the self form, nothing to test.  Thread 0 prepares counts[1] for the adds of k_nearest.  `qptr`: the
-// query offsets of a batched grid, or null; the launch covers its clouds + 1 entries.
-__global__ void __launch_bounds__(kBlock)
-    k_nearest_check(double radius, const XY* __restrict__ queries, long long n_queries, const int* __restrict__ flag,
-                    int* __restrict__ own_flag, long long* __restrict__ counts, const long long* __restrict__ qptr,
-                    int clouds) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) counts[1] = *flag ? pairs_status(*flag) : 0;
-  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kPairsFlagBatch);
-  if (!queries || i >= n_queries) return;
-  const XY q = queries[i];
-  const double ax = fabs(q.x), ay = fabs(q.y);
-  const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-  if ((fx && !(ax / radius < kPairsDomain)) || (fy && !(ay / radius < kPairsDomain))) atomicOr(own_flag, kPairsFlagDomain);
-}
-
 __device__ __forceinline__ bool nearest_before(double d2a, int ja, double d2b, int jb) {
   return d2a < d2b || (d2a == d2b && ja < jb);
 }
 
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]); otherwise row i is queries[i] (n_queries rows).
+// The one reader whose kernel takes the PairsView unpacked: with the view by value its loops compiled to the same
+// instructions and the table was still MEASURED 1.3 to 5.8 % slower in all seven cases of scripts/nearest_time.py; with
+// the loose arguments it is inside the spread of the parent build (profiles/readers_refactor.txt; only the argument
+// loads of the prologue differ, why that costs time was not found).
 template <int K, bool batched>
 __global__ void __launch_bounds__(kNearestBlock)
     k_nearest(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag,
@@ -94,7 +83,7 @@ __global__ void __launch_bounds__(kNearestBlock)
   const bool up = *flag || *own_flag;
   const long long rows = queries ? n_queries : words[PW_N];
   if (blockIdx.x == 0 && tid == 0) {
-    if (up) out.counts[1] = batched ? pairs_status(*flag | *own_flag) : kPairsStatusDomain;  // (the same bits in both)
+    if (up) out.counts[1] = reader_status(*flag, *own_flag);
     else out.counts[0] = rows;
   }
   int len = 0;  // places of the list in use

@@ -52,6 +52,18 @@
 // k_pairs_place and scell are as they are.  Every kernel that walks is a template on `batched`: the unbatched
 // instantiation carries no record at all.  The clusters and the histograms (sc_clusters.h, sc_hist.h) are not batched:
 // their host calls refuse a batched grid.
+//
+// The readers.  The workspace a count leaves is read by the fill and by the clusters, the nearest-k tables, the weighted
+// sums, their position gradient and the distance histograms (sc_clusters.h, sc_nearest.h, sc_fields.h, sc_fields_grad.h,
+// sc_hist.h).  What they share is here, once: PairsView, the workspace as a reader sees it; pairs_merge, a row's partners
+// ascending in j, for the fill and the sums (the gradient writes the same merge out, sc_fields_grad.h says on what
+// measurement); k_reader_check with the readers' flag bits and reader_status.
+// None of it knows who calls: what a reader does with a partner is the callable it hands in.
+// The plain walk -- the nine cells in raster order, the own-cell test, pairs_in, pairs_accept -- stays written out in
+// k_pairs_count, k_nearest, k_hist and k_cluster_union.  As one function with a callable it was built and MEASURED: the
+// compiler orders the three loads of a candidate (cell, index, position) differently per kernel today -- k_hist issues
+// index and position together, k_pairs_count one after the other -- and gave the shared loop one order for all: k_hist
+// 9 to 15 % and k_nearest 2 to 10 % slower, k_pairs_count 1 % either way (profiles/readers_refactor.txt).
 #pragma once
 #include "sc_device.h"
 #include "sc_kernels.h"
@@ -64,7 +76,9 @@ constexpr unsigned kPairsMinBuckets = 256;
 constexpr unsigned kPairsHashX = 0x9E3779B1u, kPairsHashY = 0x85EBCA77u, kPairsHashMix = 0x2C1B3C6Du;
 constexpr unsigned kPairsHashCloud = 0xC2B2AE3Du;  // the batched form's third factor
 constexpr int kPairsFlagDomain = 1, kPairsFlagBatch = 2;  // the bits of the count's flag
-constexpr long long kPairsStatusDomain = -1, kPairsStatusBatch = -3;  // (-2: short arrays, sc_fields.h)
+// the bits of a reader's own flag: a query outside the domain, an array of the caller's with too few rows, bad query offsets
+constexpr int kReaderFlagDomain = 1, kReaderFlagRows = 2, kReaderFlagBatch = 4;
+constexpr long long kPairsStatusDomain = -1, kPairsStatusRows = -2, kPairsStatusBatch = -3;
 constexpr double kPairsCellFactor = 1.0 + 1.0 / 1048576.0;  // h = radius * (1 + 2^-20)
 constexpr double kPairsDomain = 2147483648.0;                // |c| / radius must stay below 2^31
 
@@ -100,9 +114,20 @@ __device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsig
   return v & mask;
 }
 
-__device__ __forceinline__ unsigned pairs_bucket(unsigned cx, unsigned cy, unsigned mask) {
-  return pairs_bucket(cx, cy, 0u, mask);
-}
+// The workspace as a reader sees it, by value in every kernel that reads the grid (k_nearest and k_fields_grad take it
+// unpacked: sc_nearest.h, sc_fields_grad.h): the grid, n and E, the count's flag,
+// the points in index order, where every bucket starts, and the members in bucket order -- positions, cells, indices.
+struct PairsView {
+  PairsGrid g;
+  const long long* words;
+  const int* flag;
+  const XY* xy;
+  const int* start;
+  const XY* sxy;
+  const uint2* scell;
+  const int* sidx;
+  PairsBatch bt;
+};
 
 // The cloud of row i: the last b < clouds with ptr[b] <= i (empty clouds before it are skipped).  Reads entries
 // 0 .. clouds - 1 only, whatever they hold.
@@ -137,6 +162,21 @@ __device__ __forceinline__ long long pairs_status(int flag) {
   return (flag & kPairsFlagBatch) ? kPairsStatusBatch : kPairsStatusDomain;
 }
 
+// counts[1] of a reader with a flag up: `flag` the count's, `own` the call's.  Bad offsets first, then the domain, then the
+// rows.  A reader that never raises a bit never gets its status: the nearest and the histogram hand k_reader_check no row
+// counts, so -2 is the sums' and the gradient's alone; the clusters and the histograms refuse a batched grid, so neither
+// the count's batch bit nor their own is ever up and -1 is all they report; and on an unbatched grid no reader has query
+// offsets to be wrong.
+__device__ __forceinline__ long long reader_status(int flag, int own) {
+  if ((flag & kPairsFlagBatch) || (own & kReaderFlagBatch)) return kPairsStatusBatch;
+  return flag || (own & kReaderFlagDomain) ? kPairsStatusDomain : kPairsStatusRows;
+}
+
+// The domain rule, for the absolute value of one coordinate: finite, and fl(|c| / radius) not below 2^31.
+__device__ __forceinline__ bool pairs_outside(double c_abs, double radius) {
+  return c_abs < __builtin_inf() && !(c_abs / radius < kPairsDomain);  // (NaN compares false: not outside, just dead)
+}
+
 __device__ __forceinline__ unsigned pairs_cell(double c, double h) { return (unsigned)(int)floor(c / h); }
 
 // The state form: row k is the slot with the k-th smallest id, as in k_state_gather.
@@ -168,12 +208,12 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // `n_host` >= 0: the caller's points, n is known (and written to words); -1: xy is the workspace, n is words[PW_N].
-// Batched: `bt.ptr` is the workspace's copy (which k_pairs_batch_check has written), the clouds go to `cloud`.
+// Batched: `ptr` is the workspace's copy (which k_pairs_batch_check has written), the clouds go to `cloud`.
 template <bool batched>
 __global__ void __launch_bounds__(kBlock)
     k_pairs_key(PairsGrid g, const XY* __restrict__ src, XY* __restrict__ xy, long long n_host, long long* __restrict__ words,
                 int m, unsigned* __restrict__ keys, int* __restrict__ index, int* __restrict__ bucketCount,
-                int* __restrict__ flag, PairsBatch bt, int* __restrict__ cloud) {
+                int* __restrict__ flag, const long long* __restrict__ ptr, int clouds, int* __restrict__ cloud) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const long long n = n_host >= 0 ? n_host : words[PW_N];
   if (i == 0 && n_host >= 0) words[PW_N] = n_host;
@@ -184,13 +224,12 @@ __global__ void __launch_bounds__(kBlock)
     if (src != xy) xy[i] = p;
     unsigned b = 0u;
     if (batched) {
-      b = (unsigned)pairs_cloud_of(bt.ptr, bt.clouds, i);
+      b = (unsigned)pairs_cloud_of(ptr, clouds, i);
       cloud[i] = (int)b;
     }
     const double ax = fabs(p.x), ay = fabs(p.y);
-    const bool fx = ax < __builtin_inf(), fy = ay < __builtin_inf();  // (NaN compares false)
-    if ((fx && !(ax / g.radius < kPairsDomain)) || (fy && !(ay / g.radius < kPairsDomain))) atomicOr(flag, kPairsFlagDomain);
-    else if (fx && fy) {
+    if (pairs_outside(ax, g.radius) || pairs_outside(ay, g.radius)) atomicOr(flag, kPairsFlagDomain);
+    else if (ax < __builtin_inf() && ay < __builtin_inf()) {
       key = pairs_bucket(pairs_cell(p.x, g.h), pairs_cell(p.y, g.h), b, g.mask);
       atomicAdd(&bucketCount[key], 1);
     }
@@ -221,40 +260,75 @@ __device__ __forceinline__ bool pairs_accept(const PairsGrid& g, int i, int j, X
 // The first place from k on, below `end`, whose point lies in cell (cx, cy) -- and, batched, in the row's cloud -- and is
 // a partner of i; `end` when none.
 template <bool batched>
-__device__ __forceinline__ int pairs_advance(const PairsGrid& g, const PairsRow& row, int i, XY p, unsigned cx, unsigned cy,
-                                             int k, int end, const XY* __restrict__ sxy, const uint2* __restrict__ scell,
-                                             const int* __restrict__ sidx) {
+__device__ __forceinline__ int pairs_advance(const PairsView& v, const PairsRow& row, int i, XY p, unsigned cx, unsigned cy,
+                                             int k, int end) {
   for (; k < end; ++k) {
-    const uint2 cell = scell[k];
-    const int j = sidx[k];
+    const uint2 cell = v.scell[k];
+    const int j = v.sidx[k];
     double d2;
-    if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(g, i, j, p, sxy[k], d2)) break;
+    if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(v.g, i, j, p, v.sxy[k], d2)) break;
   }
   return k;
 }
 
+// The merge: a row's partners ascending in j.  The nine runs are each ascending (the sort is stable), the smallest head
+// goes out next: f(j, q) with q the partner's position, until f returns false or every run is at its end.  The cursors
+// live in the kernel's LDS, a column per thread (a dynamically indexed register array would go to scratch); no barrier:
+// every thread is on its own.
+template <bool batched, class F>
+__device__ __forceinline__ void pairs_merge(const PairsView& v, const PairsRow& row, int me, XY p, int (&s_cur)[9][kBlock],
+                                            int (&s_end)[9][kBlock], int (&s_head)[9][kBlock], int tid, F&& f) {
+  const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
+  for (int c = 0; c < 9; ++c) {
+    const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
+    const unsigned b = pairs_bucket(cx, cy, row.cloud, v.g.mask);
+    const int end = v.start[b + 1];
+    const int k = pairs_advance<batched>(v, row, me, p, cx, cy, v.start[b], end);
+    s_cur[c][tid] = k;
+    s_end[c][tid] = end;
+    s_head[c][tid] = k < end ? v.sidx[k] : INT_MAX;
+  }
+  for (;;) {
+    int best = INT_MAX, bc = 0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      const int h = s_head[c][tid];
+      if (h < best) {
+        best = h;
+        bc = c;
+      }
+    }
+    if (best == INT_MAX) break;  // every run is at its end
+    const int k = s_cur[bc][tid];
+    if (!f(best, v.sxy[k])) break;
+    const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
+    const int end = s_end[bc][tid];
+    const int next = pairs_advance<batched>(v, row, me, p, cx, cy, k + 1, end);
+    s_cur[bc][tid] = next;
+    s_head[bc][tid] = next < end ? v.sidx[next] : INT_MAX;
+  }
+}
+
+// `v.g.half` is the count's.
 template <bool batched>
-__global__ void __launch_bounds__(kBlock)
-    k_pairs_count(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
-                  const XY* __restrict__ xy, const int* __restrict__ start, const XY* __restrict__ sxy,
-                  const uint2* __restrict__ scell, const int* __restrict__ sidx, int* __restrict__ rowLen, PairsBatch bt) {
+__global__ void __launch_bounds__(kBlock) k_pairs_count(PairsView v, int m, int* __restrict__ rowLen) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i >= m || *flag) return;
+  if (i >= m || *v.flag) return;
   int count = 0;
-  if (i < words[PW_N]) {
-    const XY p = xy[i];
+  if (i < v.words[PW_N]) {
+    const XY p = v.xy[i];
     if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
-      const PairsRow row = pairs_row<batched>(bt, i);
-      const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
+      const PairsRow row = pairs_row<batched>(v.bt, i);
+      const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
       for (int c = 0; c < 9; ++c) {
         const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-        const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
-        const int end = start[b + 1];
-        for (int k = start[b]; k < end; ++k) {
-          const uint2 cell = scell[k];
-          const int j = sidx[k];
+        const unsigned b = pairs_bucket(cx, cy, row.cloud, v.g.mask);
+        const int end = v.start[b + 1];
+        for (int k = v.start[b]; k < end; ++k) {
+          const uint2 cell = v.scell[k];
+          const int j = v.sidx[k];
           double d2;
-          if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(g, i, j, p, sxy[k], d2)) ++count;
+          if (cell.x == cx && cell.y == cy && pairs_in<batched>(row, j) && pairs_accept(v.g, i, j, p, v.sxy[k], d2)) ++count;
         }
       }
     }
@@ -317,56 +391,54 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-// Row i's partners at offs[i], ascending in j: the nine runs are each ascending (the sort is stable), the smallest head
-// goes out next.  Entry e is written only when e < room.
+// Row i's partners at offs[i], ascending in j (pairs_merge).  Entry e is written only when e < room.  `v.g.half` is the
+// count's.
 template <bool batched>
 __global__ void __launch_bounds__(kBlock)
-    k_pairs_fill(PairsGrid g, const long long* __restrict__ words, const int* __restrict__ flag, int m,
-                 const XY* __restrict__ xy, const long long* __restrict__ offs, const int* __restrict__ start,
-                 const XY* __restrict__ sxy, const uint2* __restrict__ scell, const int* __restrict__ sidx,
-                 long long* __restrict__ partners, double* __restrict__ d2_out, long long room, PairsBatch bt) {
+    k_pairs_fill(PairsView v, int m, const long long* __restrict__ offs, long long* __restrict__ partners,
+                 double* __restrict__ d2_out, long long room) {
   __shared__ int s_cur[9][kBlock], s_end[9][kBlock], s_head[9][kBlock];
   const int tid = (int)threadIdx.x;
   const int i = (int)(blockIdx.x * blockDim.x + tid);
-  if (i >= m || *flag || i >= words[PW_N]) return;  // (no barrier below: every thread is on its own)
+  if (i >= m || *v.flag || i >= v.words[PW_N]) return;  // (no barrier below: every thread is on its own)
   long long e = offs[i];
   const long long row_end = offs[i + 1];
   if (e >= room || e == row_end) return;
-  const XY p = xy[i];
-  const PairsRow row = pairs_row<batched>(bt, i);
-  const unsigned cx0 = pairs_cell(p.x, g.h), cy0 = pairs_cell(p.y, g.h);
-  for (int c = 0; c < 9; ++c) {
-    const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-    const unsigned b = pairs_bucket(cx, cy, row.cloud, g.mask);
-    const int end = start[b + 1];
-    const int k = pairs_advance<batched>(g, row, i, p, cx, cy, start[b], end, sxy, scell, sidx);
-    s_cur[c][tid] = k;
-    s_end[c][tid] = end;
-    s_head[c][tid] = k < end ? sidx[k] : INT_MAX;
-  }
-  while (e < room && e < row_end) {
-    int best = INT_MAX, bc = 0;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) {
-      const int h = s_head[c][tid];
-      if (h < best) {
-        best = h;
-        bc = c;
-      }
-    }
-    if (best == INT_MAX) break;  // (never: the row has row_end - offs[i] partners)
-    const int k = s_cur[bc][tid];
+  const XY p = v.xy[i];
+  pairs_merge<batched>(v, pairs_row<batched>(v.bt, i), i, p, s_cur, s_end, s_head, tid, [&](int j, XY q) {
     double d2;
-    (void)pairs_accept(g, i, best, p, sxy[k], d2);
-    partners[e] = best;
+    (void)pairs_accept(v.g, i, j, p, q, d2);
+    partners[e] = j;
     if (d2_out) d2_out[e] = d2;
     ++e;
-    const unsigned cx = cx0 + (unsigned)(bc % 3 - 1), cy = cy0 + (unsigned)(bc / 3 - 1);
-    const int end = s_end[bc][tid];
-    const int next = pairs_advance<batched>(g, row, i, p, cx, cy, k + 1, end, sxy, scell, sidx);
-    s_cur[bc][tid] = next;
-    s_head[bc][tid] = next < end ? sidx[next] : INT_MAX;
+    return e < room && e < row_end;  // (the runs hold exactly row_end - offs[i] partners)
+  });
+}
+
+// The check every reader but the fill and the clusters launches first, on the same stream, after its own flag was zeroed:
+// thread 0 prepares counts[1] (0, or the count's status) and compares the caller's row counts with what only the device
+// knows -- `row_rows` the rows of the arrays that go by row (at least n_queries, or n in the self form), `part_rows` of
+// those that go by partner (at least n), -1: no such array --; a thread per query tests it against the domain
+// (`queries` null: the self form, nothing to test); and on a batched grid a thread per entry tests `qptr`, the query
+// offsets, as the count tested ptr (null: none; the launch covers its clouds + 1 entries).  What it finds goes up in
+// `own_flag`: the count's flag stays as the count left it, a fill or a label afterwards still reads it.
+__global__ void __launch_bounds__(kBlock)
+    k_reader_check(double radius, const XY* __restrict__ queries, long long n_queries, long long row_rows, long long part_rows,
+                   const long long* __restrict__ words, const int* __restrict__ flag, int* __restrict__ own_flag,
+                   long long* __restrict__ counts, const long long* __restrict__ qptr, int clouds) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (qptr) pairs_ptr_check(qptr, nullptr, clouds, n_queries, i, own_flag, kReaderFlagBatch);
+  if (i == 0) {
+    counts[1] = *flag ? pairs_status(*flag) : 0;
+    if (row_rows >= 0 || part_rows >= 0) {  // (no array of the caller's: n is not even read)
+      const long long n = words[PW_N];
+      if ((row_rows >= 0 && row_rows < (queries ? n_queries : n)) || (part_rows >= 0 && part_rows < n))
+        atomicOr(own_flag, kReaderFlagRows);
+    }
   }
+  if (!queries || i >= n_queries) return;
+  const XY q = queries[i];
+  if (pairs_outside(fabs(q.x), radius) || pairs_outside(fabs(q.y), radius)) atomicOr(own_flag, kReaderFlagDomain);
 }
 
 }  // namespace sc

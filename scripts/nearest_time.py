@@ -188,9 +188,13 @@ def main():
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--big", type=int, default=1048576)
     ap.add_argument("--probes", type=int, default=65536)
+    ap.add_argument("--lib", default=None, help="another build of libsandcrate_hip.so to time")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
+    if args.lib:
+        from sand_crate_amd import _native
+        _native.LIB_PATH = Path(args.lib).resolve()
     import bench
     import sand_crate_amd as sc
 

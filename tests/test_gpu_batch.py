@@ -1,7 +1,8 @@
 """GPU tests of the batched neighbourhood calls (`batch=` / `query_batch=` of `Crate.pair_tensors`, `neighbor_tensors`,
 `field_tensors` and `field_function`; sc_pairs_set_batch_device, sc_pairs_set_query_batch_device): every result against
 the rule of tests/batch_spec.py -- the existing rules cloud by cloud -- bit for bit, floats compared as their 64 bits, on
-the cases of tests/batch_cases.py."""
+the cases of tests/batch_cases.py.  And, unbatched, the readers in a row after one whose own flag went up: they share that
+flag, and no call's verdict may reach the next."""
 import functools
 from pathlib import Path
 
@@ -419,3 +420,47 @@ def test_the_setters_argument_errors(sc, crate):
         crate.cluster_tensors(BK.RADIUS, points=points, batch=good)
     with pytest.raises(TypeError):
         crate.distance_histogram([0.0, BK.RADIUS], points=points, batch=good)
+
+
+# ---- 7. the readers share one flag: no call's verdict reaches the next
+
+def test_a_raised_reader_flag_does_not_reach_the_next_reader(crate):
+    """One count of 70 points -- more than one 64-row workgroup of the nearest and of the histogram -- and 3 queries: a
+    nearest call with a query outside the domain reports -1; the sum, the gradient, the histogram and a clean nearest call
+    after it each report 0 and equal their NumPy rules bit for bit."""
+    import torch
+    import field_grad_spec
+    import field_spec
+    import hist_spec
+    import nearest_spec
+    rs = np.random.RandomState(70)
+    radius, k, power = 0.1, 16, 3                                                   # (no row has 16 partners: the cut count is 0)
+    points = rs.rand(70, 2) * 0.5
+    queries = points[[3, 40, 69]] + 0.01
+    outside = queries.copy()
+    outside[1, 0] = 2.0 ** 32 * radius
+    values, row_a, row_s, part_s = rs.rand(70, 3) - 0.5, rs.rand(3, 3) - 0.5, rs.rand(3) - 0.5, rs.rand(70) - 0.5
+    edges = np.linspace(0.0, radius, 6)
+    eng = crate.engine
+    p, q, far = tensor(points), tensor(queries), tensor(outside)
+    v, a, s, ps = tensor(values), tensor(row_a), tensor(row_s), tensor(part_s)
+    offsets, counts = full(eng.capacity + 1), full(2)
+    status = [full(2) for _ in range(5)]
+    first, neighbors, d2, partners = full((3, k)), full((3, k)), full((3, k), SENTINEL_F), full(3)
+    sums, wsum, grad = full((3, 3), SENTINEL_F), full(3, SENTINEL_F), full((3, 2), SENTINEL_F)
+    table, total = torch.full((3, 5), SENTINEL, dtype=torch.int32, device="cuda"), full(5)
+    eng.pairs_count(p, radius=radius, offsets=offsets, counts=counts)
+    eng.pairs_nearest(first, k=k, queries=far, counts=status[0])
+    eng.pairs_sum(v, sums, wsum, power=power, queries=q, counts=status[1])
+    eng.pairs_sum_grad(grad, a, v, s, ps, power=power, queries=q, counts=status[2])
+    eng.pairs_hist(table, total, edges=edges, queries=q, counts=status[3])
+    eng.pairs_nearest(neighbors, d2, partners, k=k, queries=q, counts=status[4])
+    eng.synchronize()
+    assert counts.cpu().tolist()[0] == 70 and int(counts[1]) > 0
+    assert status[0].cpu().tolist() == [SENTINEL, -1] and untouched(first)
+    want_nearest = nearest_spec.nearest(points, radius, k, queries)
+    assert [t.cpu().tolist() for t in status[1:]] == [[3, 0]] * 4 and int(want_nearest[2].max()) <= k
+    assert same_all((sums, wsum), field_spec.field(points, radius, values, power, True, queries))
+    assert same(grad, field_grad_spec.position_grad(queries, points, radius, power, row_a, values, row_s, part_s))
+    assert same_all((table, total), hist_spec.histogram(points, edges, queries))
+    assert same_all((neighbors, d2, partners), want_nearest) and int(want_nearest[2].sum()) > 0
