@@ -704,6 +704,46 @@ int sc_pairs_set_query_batch_device(sc_ctx* ctx, const int64_t* dev_query_ptr);
 int sc_pairs_label_device(sc_ctx* ctx, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes /* may be NULL */,
                           int64_t* dev_roots /* may be NULL */, int64_t room_clusters, int64_t* dev_counts /* [2]: n, C */);
 
+/* What each cluster carries, in DEVICE memory of the caller: per cluster of the last label the sum, and optionally the
+ * minimum and the maximum, of up to SC_CLUSTER_SUMS_MAX_CHANNELS float64 channels over the cluster's members.
+ * tests/cluster_sums_spec.py is the rule: the members of cluster c are the rows i with label c in ascending i; the sum of a
+ * channel is `tree` of their values in that order -- pairwise summation in groups of 64, and groups of groups, each add
+ * rounded on its own, the padding +0.0, a single member still through one group (so a cluster of -0.0 sums to +0.0);
+ * minima and maxima are NumPy's: a NaN on either side is the result.  A row with label -1 is never read into any result,
+ * whatever its values hold.  The result of a cluster is a pure function of its own members' values: the same bits on every
+ * call, whatever the other clusters, the capacity, the bucket count or the count's flags are.
+ *
+ * sc_pairs_cluster_sums_device  reads what the last sc_pairs_label_device of this context left in its workspace, and n and
+ *     the domain flag of the count it labelled; of the caller's it reads dev_values (values_rows x channels contiguous
+ *     float64, aligned to 16 bytes; row i belongs to point i of the count), nothing else.  Writes dev_sums[c, :] and -- unless
+ *     NULL -- dev_mins[c, :] and dev_maxs[c, :] (float64, room_clusters x channels contiguous) for c < min(C,
+ *     room_clusters) only: rows from the room on are left as they were; dev_counts[0] = n, dev_counts[1] = C.  After a
+ *     count that found a point outside the domain dev_counts[1] = -1 is written and nothing else; with values_rows < n --
+ *     only the device knows n in the state form -- dev_counts[1] = -2 and nothing else: a flag of this call's own, the
+ *     count's verdict stays as the count left it.  Nothing of the count's or the label's workspace is written: a fill, a
+ *     table, a sum, a histogram or another label may follow, and the call may be repeated.
+ * It enqueues on the context's stream only, with the rules of the calls above: nothing synchronises, nothing reaches the
+ * host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches are
+ * not bracketed by the timing events.
+ *     The algorithm: a stable radix sort of (label, index), a dead row's key behind every cluster, brings every cluster's
+ * members together in ascending index; exclusive scans of the sizes and of ceil(size / 64) give the member and chunk
+ * starts; level 0 takes a wave per chunk of 64 consecutive members of ONE cluster, counted from the cluster's start, gathers
+ * values[index] rows and reduces them by the wave's xor butterfly, which is the rule's group of 64; a cluster of one chunk
+ * has its result, larger ones leave a partial per chunk, and ceil(log64(m)) - 1 more levels reduce those the same way, m
+ * the bound.  The number of launches depends on m alone.  No workgroup waits for another and there are no atomics at all
+ * (csrc/sc_cluster_sums.h).  The workspace belongs to the context: under 60 bytes per point of the bound, grown -- which
+ * synchronises once -- to the largest bound asked for.
+ *     SC_ERR_ARG for a null context, null dev_counts or dev_values, null dev_sums with room, channels outside 1 ..
+ * SC_CLUSTER_SUMS_MAX_CHANNELS, values that are not aligned to 16 bytes, or a negative room or number of rows.  SC_ERR_STATE
+ * between sc_step_begin and sc_step_finish, when there is no label, when an sc_pairs_count_device has run since the label
+ * (in either form, batched or not: a batched grid has no label), and when anything has touched the state since (the fill's
+ * rule).  All checked before anything is launched: the arrays are then untouched. */
+enum { SC_CLUSTER_SUMS_MAX_CHANNELS = 8 };
+int sc_pairs_cluster_sums_device(sc_ctx* ctx, const double* dev_values, int64_t values_rows,
+                                 int32_t channels /* 1 .. SC_CLUSTER_SUMS_MAX_CHANNELS */, double* dev_sums,
+                                 double* dev_mins /* may be NULL */, double* dev_maxs /* may be NULL */, int64_t room_clusters,
+                                 int64_t* dev_counts /* [2]: n, C or a status */);
+
 /* Nearest-k neighbour tables of that graph in DEVICE memory of the caller: a table of fixed shape, rows x k, for code that
  * wants neighbors[i, 0 .. k) rather than a CSR list of data-dependent length.  tests/nearest_spec.py is the rule: j is a
  * partner of row r iff fl(fl(dx dx) + fl(dy dy)) <= fl(radius radius), dx = fl(x_r - x_j) -- the arithmetic of the pair list

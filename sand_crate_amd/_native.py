@@ -53,6 +53,11 @@ FIELDS_KERNEL_CHANNELS = (1, 2, 4, 8)
 FIELDS_SELF = 1
 FIELDS_BLOCK = 256
 FIELDS_OK, FIELDS_DOMAIN, FIELDS_VALUES_SHORT = 0, -1, -2
+# the per-cluster sums (csrc/sc_cluster_sums.h): the most channels of one call (SC_CLUSTER_SUMS_MAX_CHANNELS), the members
+# one work item of a level reduces (kCsumGroup: a wave) and the status values of counts[1]
+CLUSTER_SUMS_MAX_CHANNELS = 8
+CLUSTER_SUMS_GROUP = 64
+CLUSTER_SUMS_DOMAIN, CLUSTER_SUMS_VALUES_SHORT = -1, -2
 # the distance histograms (csrc/sc_hist.h): the most bins of one call (SC_HIST_MAX_BINS), the rows per workgroup of its
 # kernel (kHistBlock: one wave), the bins its search is made for -- the smallest of HIST_SLOTS that is at least the call's,
 # `hist_slots(bins)`, each a kernel of its own -- and the status values of counts[1]
@@ -206,6 +211,7 @@ SIGNATURES = {
     "sc_pairs_set_batch_device": (C.c_int, [_P, _P, C.c_int64]),
     "sc_pairs_set_query_batch_device": (C.c_int, [_P, _P]),
     "sc_pairs_label_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "sc_pairs_cluster_sums_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "sc_pairs_nearest_device": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "sc_pairs_sum_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
                                       _P]),

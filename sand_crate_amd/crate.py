@@ -395,6 +395,89 @@ class Crate:
             self._count, self._count_known = n, True
         return labels[:n], sizes[:total], roots[:total]
 
+    def cluster_sums(self, values, radius: float | None = None, *, points=None, extrema: bool = False,
+                     max_clusters: int | None = None):
+        """What each cluster carries: `cluster_tensors` at the same `radius` and `points`, and per cluster the sums --
+        with `extrema` also the minima and maxima -- of `values` over its members, reduced on the GPU in one call (count,
+        label, sc_pairs_cluster_sums_device): ``(labels, sizes, roots, sums[, mins, maxs])``, the last float64 (C, F).
+        `values` is a float64 (n, F) or (n,) CUDA tensor, F 1 .. 8, whose rows are in the order of `state_tensors()` -- or
+        of `points`; (n,) is one channel and still gives (C, 1).  A cluster's sum adds its members' values in ascending
+        index, pairwise in groups of 64 and groups of groups, every add rounded on its own
+        (tests/cluster_sums_spec.py is the rule): a pure function of the cluster's own members, the same bits on every
+        call, no floating-point atomics anywhere.  A row with label -1 is never read, whatever its values are; a NaN among
+        a cluster's values is that cluster's sum, minimum and maximum.  `sand_crate_amd.pairs.cluster_centers` and
+        `cluster_mean_velocities` read the table of `cluster_observables`.
+
+        Synchronisation and `max_clusters` are exactly those of `cluster_tensors`: by default one synchronisation, tensors
+        cut to n and C, ValueError for a coordinate outside the domain and for `values` with fewer rows than there are
+        points; with `max_clusters=K` nothing synchronises, the per-cluster tensors come at K rows and last the int64
+        `counts` tensor (n, C): C > K means that the clusters from K on were not written, C = -1 is the domain error and
+        C = -2 the short `values` (nothing else was written by the reduction).  `values` must be ready when this is
+        called, as `points` must."""
+        import torch
+        eng = self._engine
+        dev = torch.device("cuda", eng.device)
+        radius = float(self.diameter if radius is None else radius)
+        if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
+            raise ValueError("values must be a CUDA float64 tensor of shape (n, F) or (n,)")
+        values = (values.unsqueeze(1) if values.dim() == 1 else values).contiguous()
+        width = int(values.shape[1])
+        if not 1 <= width <= N.CLUSTER_SUMS_MAX_CHANNELS:
+            raise ValueError(f"values must have 1 .. {N.CLUSTER_SUMS_MAX_CHANNELS} columns")
+        rows = eng.capacity if points is None else _point_rows(points)
+        sync = max_clusters is None
+        room = rows if sync else int(max_clusters)
+        if room < 0:
+            raise ValueError("max_clusters must not be negative")
+        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)  # (a temporary: the label reads the workspace)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)          # (n, E) of the count, then (n, C) twice
+        labels = torch.empty(rows, dtype=torch.int64, device=dev)
+        sizes = torch.empty(room, dtype=torch.int64, device=dev)
+        roots = torch.empty(room, dtype=torch.int64, device=dev)
+        tables = tuple(torch.empty((room, width), dtype=torch.float64, device=dev) for _ in range(3 if extrema else 1))
+        if sync:  # (what torch was asked for above is done, and nothing of torch's touches the new tensors)
+            torch.cuda.current_stream(dev).synchronize()
+        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
+        eng.pairs_label(labels, sizes, roots, counts=counts)
+        eng.pairs_cluster_sums(values, *tables, counts=counts)
+        if not sync:
+            self._cluster_sums_temporaries = (offsets, values)  # (held until the next call: still queued)
+            return (labels, sizes, roots, *tables, counts)
+        eng.synchronize()
+        n, total = (int(v) for v in counts.cpu())
+        if total == N.CLUSTER_SUMS_VALUES_SHORT:
+            raise ValueError(f"cluster_sums: values has {values.shape[0]} rows, fewer than there are points")
+        if total < 0:
+            raise ValueError(f"cluster_sums: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
+        if points is None:
+            self._count, self._count_known = n, True
+        return (labels[:n], sizes[:total], roots[:total], *(t[:total] for t in tables))
+
+    def cluster_observables(self, radius: float | None = None, *, max_clusters: int | None = None):
+        """The probe's observables per droplet: ``(labels, roots, table)``, `table` float64 (C, 14) with the columns
+        `sand_crate_amd.pairs.CLUSTER_FIELDS` -- n, sum_x, sum_y, sum_vx, sum_vy, sum_ke, sum_p, min_x, max_x, min_y,
+        max_y, max_speed2, max_p, n_pressed, named as `probe.FIELDS` names them -- for every cluster of the state at
+        `radius` (default: `diameter`).  The channels are built with torch from `state_tensors()` as the probe builds them,
+        each operation rounded on its own and ``vx*vx + vy*vy`` evaluated once, so `max_speed2` and the kinetic energy
+        agree; one `cluster_sums(..., extrema=True)` reduces them, with its synchronisation and `max_clusters` semantics
+        (then `counts` comes last, and the table's rows from min(C, K) on are uninitialised).  Runs on torch's current
+        stream and the crate's: with `max_clusters` the crate must be on torch's stream (`engine.set_stream`)."""
+        import torch
+        from .pairs import CLUSTER_FIELDS, cluster_channels
+        if max_clusters is None:
+            xy, vv, p = self.state_tensors()
+        else:
+            xy, vv, p, _ = self.state_tensors(sync=False)
+        values = cluster_channels(xy, vv, p)
+        out = self.cluster_sums(values, radius, extrema=True, max_clusters=max_clusters)
+        labels, sizes, roots, sums, mins, maxs = out[:6]
+        table = torch.empty((sums.shape[0], len(CLUSTER_FIELDS)), dtype=torch.float64, device=sums.device)
+        table[:, 0] = sizes
+        table[:, 1:7] = sums[:, 0:6]
+        table[:, 7], table[:, 8], table[:, 9], table[:, 10] = mins[:, 0], maxs[:, 0], mins[:, 1], maxs[:, 1]
+        table[:, 11], table[:, 12], table[:, 13] = maxs[:, 6], maxs[:, 5], sums[:, 7]
+        return (labels, roots, table) + tuple(out[6:])
+
     @_batch_keywords
     def neighbor_tensors(self, k: int, radius: float | None = None, *, points=None, queries=None,
                          squared_distances: bool = False, partner_counts: bool = False, sync: bool = True):

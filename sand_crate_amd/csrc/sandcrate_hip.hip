@@ -15,6 +15,7 @@
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_clusters.h"
+#include "sc_cluster_sums.h"
 #include "sc_nearest.h"
 #include "sc_fields.h"
 #include "sc_fields_grad.h"

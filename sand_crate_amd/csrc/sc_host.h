@@ -285,8 +285,11 @@ struct PairsSpace {
 // sc_pairs_label_device (sc_clusters.h; sc_host_state.h): the parents, the root marks, their scan (the dense numbers) with
 // its block sums and the clusters' sizes -- apart from the pairs workspace, which a fill after the labelling still reads;
 // each grown to the largest bound asked for.
+// `valid`: they hold the label of the pairs workspace as it is -- every count clears it --, over the bound `m`.
 struct ClusterSpace {
   DevBuf<int> parent, isRoot, size, sums, dense;
+  bool valid = false;
+  int64_t m = 0;
   int ensure(int64_t m, hipStream_t stream) {
     if (m + 1 <= dense.size()) return SC_OK;
     HIPCHK(parent.grow(m, stream));
@@ -294,6 +297,34 @@ struct ClusterSpace {
     HIPCHK(size.grow(m, stream));
     HIPCHK(sums.grow(m / kScanPerBlock + 2, stream));
     HIPCHK(dense.grow(m + 1, stream));
+    return SC_OK;
+  }
+};
+
+// sc_pairs_cluster_sums_device (sc_cluster_sums.h; sc_host_state.h): the sort of the (label, index) pairs -- a workspace of
+// its own: a fill or a table after the sums still reads the count's --, the per-cluster counts of a level, four scans of
+// them that take turns (member starts, chunk starts, partial starts, and the upper levels' item starts), the scans' block
+// sums, the call's flag, the item lists -- level 0 has up to m items, a level above at most partials(m) -- and the
+// partials of two levels that take turns: sums, minima, maxima.  Each grown to the largest bound asked for.
+struct ClusterSumSpace {
+  RadixSpace sort;
+  DevBuf<int> cnt, st[4], sums, flag;
+  DevBuf<int2> items0, items[2];
+  DevBuf<double> part[2];
+  // A cluster has partials only with more than 64 elements: ceil(s / 64) <= s / 64 + s / 65 < s / 32 of them.
+  static int64_t partials(int64_t m) { return m / 32 + 2; }
+  int ensure(int64_t m, hipStream_t stream) {
+    HIPCHK(flag.grow(1, stream));
+    if (const int rc = sort.ensure(m, stream)) return rc;
+    if (m + 1 <= st[3].size()) return SC_OK;
+    HIPCHK(cnt.grow(m, stream));
+    HIPCHK(sums.grow(m / kScanPerBlock + 2, stream));
+    HIPCHK(items0.grow(m, stream));
+    for (int k = 0; k < 2; ++k) {
+      HIPCHK(items[k].grow(partials(m), stream));
+      HIPCHK(part[k].grow(3 * partials(m) * kClusterSumsMaxChannels, stream));
+    }
+    for (int k = 0; k < 4; ++k) HIPCHK(st[k].grow(m + 1, stream));
     return SC_OK;
   }
 };
@@ -437,6 +468,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   StateIo state;
   PairsSpace pairs;
   ClusterSpace clusters;
+  ClusterSumSpace csums;
   HistSpace hist;
   Snapshot snap;
   SlabLink link;

@@ -5,6 +5,7 @@
 #include "sc_state.h"
 #include "sc_pairs.h"
 #include "sc_clusters.h"
+#include "sc_cluster_sums.h"
 #include "sc_nearest.h"
 #include "sc_fields.h"
 #include "sc_fields_grad.h"
@@ -126,6 +127,7 @@ int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double rad
   HIPCHK(hipSetDevice(c->device));
   c->pairs.valid = false;
   c->pairs.clouds = 0;
+  c->clusters.valid = false;  // (a label belongs to the count it was made from)
   const unsigned buckets = pairs_buckets(m);
   int rc = c->pairs.ensure(m, buckets, c->stream);
   if (rc) return rc;
@@ -234,6 +236,100 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
                      (long long)room_clusters);
   hipLaunchKernelGGL(k_cluster_finish, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->clusters.dense.get(),
                      c->clusters.size.get(), (long long*)dev_sizes, (long long)room_clusters, (long long*)dev_counts);
+  HIPCHK(hipGetLastError());
+  c->clusters.valid = true;
+  c->clusters.m = m;
+  return SC_OK;
+}
+
+}  // extern "C"
+
+// ---- per-cluster sums and extents (sc_cluster_sums.h) ----------------------------------------------
+
+template <int C>
+static void csum_launch(sc_ctx* c, bool first, int grid, const CsumGuard& g, const CsumLevel& lv, const CsumIo& io) {
+  hipLaunchKernelGGL((first ? k_csum_reduce<C, true> : k_csum_reduce<C, false>), dim3(grid), dim3(kBlock), 0, c->stream, g, lv, io,
+                     c->clusters.size.get());
+}
+
+extern "C" {
+
+int sc_pairs_cluster_sums_device(sc_ctx* c, const double* dev_values, int64_t values_rows, int32_t channels, double* dev_sums,
+                                 double* dev_mins, double* dev_maxs, int64_t room_clusters, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_counts) return fail(SC_ERR_ARG, "null counts pointer");
+  if (channels < 1 || channels > SC_CLUSTER_SUMS_MAX_CHANNELS)
+    return fail(SC_ERR_ARG, "%d channels, it must be 1 .. %d", (int)channels, (int)SC_CLUSTER_SUMS_MAX_CHANNELS);
+  static_assert(kClusterSumsMaxChannels == SC_CLUSTER_SUMS_MAX_CHANNELS, "the header's bound is the kernel's");
+  if (room_clusters < 0 || values_rows < 0) return fail(SC_ERR_ARG, "negative room or number of value rows");
+  if (!dev_values || (!dev_sums && room_clusters > 0)) return fail(SC_ERR_ARG, "null values or sums pointer");
+  if ((uintptr_t)dev_values & 15) return fail(SC_ERR_ARG, "the values must be aligned to 16 bytes");
+  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_cluster_sums_device inside a tick");
+  if (!c->pairs.valid || !c->clusters.valid)
+    return fail(SC_ERR_STATE, "no label to sum over: sc_pairs_count_device and sc_pairs_label_device come first, with no "
+                              "count and no change of the state in between");
+  HIPCHK(hipSetDevice(c->device));
+  const int64_t m = c->clusters.m;
+  ClusterSumSpace& w = c->csums;
+  int rc = w.ensure(m, c->stream);
+  if (rc) return rc;
+  const CsumGuard g{c->pairs.words.get(), c->pairs.flag.get(), w.flag.get()};
+  HIPCHK(hipMemsetAsync(w.flag, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_reader_check, dim3(1), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, (const XY*)nullptr, 0LL, -1LL,
+                     (long long)values_rows, g.words, g.flag, w.flag.get(), (long long*)dev_counts, (const long long*)nullptr, 0);
+  if (m > 0) {
+    const int grid = grid_for(m);
+    const int* size = c->clusters.size.get();
+    // the sort: the keys are 0 .. m (a dead row's), so as many digits as m has
+    int bits = 1;
+    while ((m >> bits) != 0) ++bits;
+    int set;
+    const CsumKey key{g.words, g.flag, g.own, c->clusters.parent.get(), c->clusters.isRoot.get(), c->clusters.dense.get(), (int)m};
+    if ((rc = radix_sort(c, w.sort, key, m, (bits + kRadixDigitBits - 1) / kRadixDigitBits, &set))) return rc;
+    int levels = 1;  // 64^levels >= m: the last level leaves every cluster one value
+    for (int64_t reach = kCsumGroup; reach < m; reach *= kCsumGroup) ++levels;
+    // Which of the four scans holds what: the member starts, the partial starts of level 0 (a level above numbers its
+    // partials as its items), and the item starts of level k.  One is overwritten only after its last reader is queued.
+    int* const member_start = w.st[0];
+    int* const part_start = w.st[2];
+    const auto item_start = [&](int k) { return w.st[k == 0 ? 1 : (k + 2) % 4].get(); };
+    const auto count_scan = [&](int level, int as_elems, int* out) {
+      hipLaunchKernelGGL(k_csum_count, dim3(grid), dim3(kBlock), 0, c->stream, g, (int)m, size, level, as_elems, w.cnt.get());
+      return launch_scan(c, w.cnt, out, m, w.sums, nullptr);
+    };
+    if ((rc = launch_scan(c, size, member_start, m, w.sums, nullptr))) return rc;
+    if ((rc = count_scan(0, 0, item_start(0)))) return rc;
+    hipLaunchKernelGGL(k_csum_items, dim3(grid), dim3(kBlock), 0, c->stream, g, (int)m, w.sort.keys[set].get(), member_start,
+                       item_start(0), w.items0.get());
+    if (levels > 1) {
+      if ((rc = count_scan(1, 1, part_start))) return rc;
+      if ((rc = count_scan(1, 0, item_start(1)))) return rc;
+    }
+    const int64_t cap = ClusterSumSpace::partials(m);
+    for (int k = 0; k < levels; ++k) {
+      const bool last = k + 1 == levels;
+      if (k >= 1 && !last)
+        if ((rc = count_scan(k + 1, 0, item_start(k + 1)))) return rc;
+      CsumLevel lv{};
+      lv.level = k;
+      lv.items = k == 0 ? w.items0.get() : w.items[(k - 1) & 1].get();
+      lv.total = item_start(k) + m;
+      lv.in_start = k == 0 ? member_start : k == 1 ? part_start : item_start(k - 1);
+      lv.out_start = k == 0 ? part_start : item_start(k);
+      lv.next_start = last ? nullptr : item_start(k + 1);
+      lv.next_items = w.items[k & 1].get();
+      const CsumIo io{dev_values, w.sort.vals[set].get(), w.part[(k + 1) & 1].get(), w.part[k & 1].get(), (long long)cap,
+                      dev_sums, dev_mins, dev_maxs, (long long)room_clusters, (int)channels};
+      // the items -- at most m at level 0, `cap` above -- in equal shares: a wave each while they last
+      const int64_t bound = k == 0 ? m : cap;
+      const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((bound + kBlock / 64 - 1) / (kBlock / 64), (int64_t)c->num_cus * 8));
+      if (channels <= 1) csum_launch<1>(c, k == 0, blocks, g, lv, io);
+      else if (channels <= 2) csum_launch<2>(c, k == 0, blocks, g, lv, io);
+      else if (channels <= 4) csum_launch<4>(c, k == 0, blocks, g, lv, io);
+      else csum_launch<8>(c, k == 0, blocks, g, lv, io);
+    }
+  }
+  hipLaunchKernelGGL(k_csum_finish, dim3(1), dim3(64), 0, c->stream, g, c->clusters.dense.get(), (int)m, (long long*)dev_counts);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -320,6 +320,34 @@ class Engine:
                                                 N._P(counts.data_ptr())))
         return counts
 
+    def pairs_cluster_sums(self, values, sums, mins=None, maxs=None, *, counts, room_clusters: int | None = None):
+        """What each cluster of the last `pairs_label` carries (sc_pairs_cluster_sums_device; the rule is
+        tests/cluster_sums_spec.py): `sums`, float64 (K, F), receives per cluster the sum of `values[i, :]`, float64 (V, F)
+        with F 1 .. 8, over the cluster's members i in ascending order, added pairwise in groups of 64 and groups of groups
+        -- the same bits on every call --; `mins` and `maxs`, float64 (K, F) or None, the members' minima and maxima (a NaN
+        wins).  A row with label -1 is never read.  `counts`, int64 (2,), receives n and C, or the status in its place:
+        -1 when the count found a coordinate outside the domain, -2 when `values` has fewer rows than the count has
+        points (then nothing else is written).  `room_clusters` defaults to K: clusters from it on are not written.
+        Needs the label of the last `pairs_count`: a count in between is an error.  Enqueued on the context's stream, no
+        synchronisation.  Returns `counts`."""
+        if getattr(values, "is_cuda", False) and values.dim() == 2 and not 1 <= values.shape[1] <= N.CLUSTER_SUMS_MAX_CHANNELS:
+            raise ValueError(f"values must be (points, F) with F 1 .. {N.CLUSTER_SUMS_MAX_CHANNELS}")
+        channels = int(values.shape[1]) if getattr(values, "is_cuda", False) and values.dim() == 2 else 1
+        held = _state_tensor(values, "values", "float64", (channels,), self.device)
+        clusters = _state_tensor(sums, "sums", "float64", (channels,), self.device)
+        for t, name in ((mins, "mins"), (maxs, "maxs")):
+            if t is not None:
+                _state_tensor(t, name, "float64", (channels,), self.device, clusters)
+        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        room_clusters = clusters if room_clusters is None else int(room_clusters)
+        if room_clusters > clusters:
+            raise ValueError(f"room_clusters {room_clusters} exceeds the tensors' {clusters} rows")
+        # (an empty tensor has no address: nothing is read or written there, any address serves)
+        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_pairs_cluster_sums_device(self._ctx, ptr(values), held, channels, ptr(sums), ptr(mins), ptr(maxs),
+                                                       room_clusters, N._P(counts.data_ptr())))
+        return counts
+
     def pairs_nearest(self, neighbors, d2=None, partners=None, *, k: int, queries=None, counts, room: int | None = None):
         """The nearest-k table of the last `pairs_count`, whichever `half` it had (sc_pairs_nearest_device; the rule is
         tests/nearest_spec.py): `neighbors`, int64 (R, k), receives per row the k nearest partners within the count's

@@ -58,6 +58,36 @@ def largest_cluster(sizes):
     return c, int(sizes[c])
 
 
+# The columns of `Crate.cluster_observables`' table: the probe's observables per cluster, named as `probe.FIELDS` names
+# them (a cluster's max_speed2 and max_p are plain maxima over its members: a cluster is never empty).
+CLUSTER_FIELDS = ("n", "sum_x", "sum_y", "sum_vx", "sum_vy", "sum_ke", "sum_p", "min_x", "max_x", "min_y", "max_y",
+                  "max_speed2", "max_p", "n_pressed")
+# ... and the channels they are reduced from (`cluster_channels`), in the order of the table's six sums.
+CLUSTER_CHANNELS = ("x", "y", "vx", "vy", "ke", "p", "speed2", "pressed")
+
+
+def cluster_channels(particles, velocities, pressure):
+    """The float64 (n, 8) channel table `Crate.cluster_observables` reduces, from `state_tensors()`: x, y, vx, vy,
+    ``0.5 * (vx*vx + vy*vy)``, p, ``vx*vx + vy*vy`` and ``p > 0`` as 0 or 1.  Every torch operation is rounded on its own
+    -- two products and a sum, no fused multiply-add --, and the squared speed is evaluated once, so the kinetic energy's
+    terms and `max_speed2` are the probe's (tests/probe_spec.py) bit for bit."""
+    import torch
+    vx, vy = velocities[:, 0], velocities[:, 1]
+    speed2 = torch.add(torch.mul(vx, vx), torch.mul(vy, vy))
+    return torch.stack([particles[:, 0], particles[:, 1], vx, vy, torch.mul(speed2, 0.5), pressure, speed2,
+                        (pressure > 0).to(particles.dtype)], dim=1).contiguous()
+
+
+def cluster_centers(table):
+    """The centre of every cluster of a `Crate.cluster_observables` table: float64 (C, 2), (sum_x / n, sum_y / n)."""
+    return table[:, 1:3] / table[:, 0:1]
+
+
+def cluster_mean_velocities(table):
+    """The mean velocity of every cluster of a `Crate.cluster_observables` table: float64 (C, 2)."""
+    return table[:, 3:5] / table[:, 0:1]
+
+
 def neighbor_mask(neighbors):
     """Which places of a nearest-k table (`Crate.neighbor_tensors`) hold a partner: bool (rows, k); the padding is -1."""
     return neighbors >= 0
