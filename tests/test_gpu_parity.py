@@ -461,10 +461,11 @@ def test_pairs_at_the_edge_of_the_window(sc, origin):
 
 
 def test_buckets_of_many_sorted_chunks_rank_together(sc):
-    """Buckets of 6 and more sorted chunks (k_sort_big sorts 1024 slots at a time) are ranked by the wave together
-    (k_reorder: the first and the last lane's bounds in every other chunk, the keys between them through LDS): 7 chunks,
-    36 chunks (two passes of 32), exact ties in x, near-ties that spread two chunks differently, and buckets whose
-    starts make the waves straddle chunks and buckets.  The order must be the reference's (row, x, id)."""
+    """Buckets of many sorted chunks (k_sort_big sorts 1024 slots at a time): k_reorder takes a particle's rank as its
+    position in its own chunk plus a binary search in each of the others, the searches advancing kRankSide = 4 chunks at
+    a time -- 7 chunks (two groups), 36 chunks (nine groups), exact ties in x, near-ties that spread two chunks
+    differently, and buckets whose starts make the waves straddle chunks and buckets.  The order must be the
+    reference's (row, x, id)."""
     from oracle.neighbors import strip_sort
     rs = np.random.RandomState(5)
     d = 0.05
@@ -806,8 +807,10 @@ def test_tick_reports_a_bad_promise_and_stays_usable(sc):
 
 
 def test_more_big_buckets_than_the_rank_kernel_lists(sc):
-    """k_sort_big sorts the first 4096 big buckets of a tick; the rest is ranked inside the reorder kernel by counting.
-    4400 cells of 100 particles each, with x ties: the sorted order must still be the reference's."""
+    """4400 cells of 100 particles each, with x ties: 4400 one-chunk tasks for k_sort_big, whose list holds
+    kMaxSortTasks = 16,384 tasks (it held 4096 buckets when this test was written, and the rest was ranked inside the
+    reorder kernel by counting: a list that overflows is tests/test_gpu_sort_cases.py's `overflow` now).  The sorted order
+    must be the reference's."""
     from oracle.neighbors import strip_sort
     rs = np.random.RandomState(8)
     d, side, ncell = 0.01, 90, 4400

@@ -671,7 +671,10 @@ def test_bucket_scan_and_task_list_over_many_workgroups(tmp_path):
     """k_scan_cells by itself (scripts/scan_check.hip, compiled here): bucket starts == a host prefix sum and the list
     of k_sort_big's tasks == one task per 1024 slots of every bucket above 96, for 1 .. 2442 workgroups with no, a few
     and thousands of such buckets -- the parity tests' worlds have a handful of scan workgroups, the contract workload
-    140, and a wrong task list (round 3: a wave total read from the wrong lane) shows only with many."""
+    140, and a wrong task list (round 3: a wave total read from the wrong lane) shows only with many.  Then three
+    worlds that fill the list of kMaxSortTasks = 16,384 tasks: 5,462 buckets of three tasks (one bucket is cut, with one
+    task inside the list), 16,384 buckets of one (nothing is cut) and 16,385 (one is left out): every entry is a task of
+    a bucket listed whole or a no-op of the cut bucket, no bucket is listed in part, the counters count everything."""
     import shutil
     import subprocess
     from pathlib import Path
@@ -684,4 +687,5 @@ def test_bucket_scan_and_task_list_over_many_workgroups(tmp_path):
     res = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr
     lines = [ln for ln in res.stdout.splitlines() if "cells," in ln]
-    assert len(lines) == 12 and all("starts ok, tasks ok" in ln for ln in lines), res.stdout
+    assert len(lines) == 15 and all("starts ok, tasks ok" in ln for ln in lines), res.stdout
+    assert [int(ln.rsplit("(", 1)[1].rstrip(")")) for ln in lines[12:]] == [16386, 16384, 16385], res.stdout
