@@ -38,7 +38,6 @@ There is no CPU implementation behind this class: without libsandcrate_hip.so an
 from __future__ import annotations
 
 import copy
-import functools
 import json
 import time
 
@@ -49,6 +48,7 @@ from . import _native as N
 from .engine import Engine
 from .hud_font import default_placement
 from .load_config import WorldConfig
+from .neighbourhood import _Neighbourhood
 from .particle_source import build_particle_sources
 from .probe import FIELDS, as_dict
 from . import track as _track
@@ -97,50 +97,7 @@ def arrow_ends(pairs) -> np.ndarray:
         return np.stack([start, start + d], axis=1)
 
 
-def _point_rows(points) -> int:
-    """The rows of a caller's (n, 2) tensor of points; what is no such tensor is left to the engine's check (0 rows)."""
-    return int(points.shape[0]) if getattr(points, "is_cuda", False) and len(points.shape) == 2 else 0
-
-
-_BATCH_ORDER = "batch offsets must start at 0, not descend and end at the number of points"
-
-
-def _check_batch(who: str, device: int, points, queries, batch, query_batch) -> None:
-    """The `batch=` / `query_batch=` arguments of a neighbourhood call: ValueError before anything is enqueued."""
-    from .engine import _batch_tensor
-    if batch is None:
-        if query_batch is not None:
-            raise ValueError(f"{who}: query_batch without batch")
-        return
-    if points is None:
-        raise ValueError(f"{who}: batch needs points, the state is one cloud")
-    entries = _batch_tensor(batch, "batch", device)
-    if queries is None:
-        if query_batch is not None:
-            raise ValueError(f"{who}: query_batch without queries")
-    elif query_batch is None:
-        raise ValueError(f"{who}: queries of a batched call need query_batch, their clouds")
-    else:
-        _batch_tensor(query_batch, "query_batch", device, entries)
-
-
-def _batch_keywords(method):
-    """`batch=` and `query_batch=` for a method whose own parameter list stays as it is (`neighbor_tensors`: its list is
-    part of the tested surface): the two keywords are taken here and wait in `self._batch_args` for the method, which
-    reads them; `inspect.signature` shows the method's own list."""
-    @functools.wraps(method)
-    def call(self, *args, batch=None, query_batch=None, **kw):
-        self._batch_args = (batch, query_batch)
-        try:
-            return method(self, *args, **kw)
-        finally:
-            self._batch_args = (None, None)
-    return call
-
-
-class Crate:
-    _batch_args = (None, None)
-
+class Crate(_Neighbourhood):
     def __init__(self, world_config: WorldConfig, *, device: int = 0, noise: str = "host", noise_seed: int = 0,
                  capacity: int | None = None) -> None:
         if noise not in _NOISE_MODES:
@@ -288,426 +245,6 @@ class Crate:
         self._engine.import_state(particles, velocities, ids)
         self._cache = None
         self._count, self._count_known = int(particles.shape[0]), True
-
-    def pair_tensors(self, radius: float | None = None, *, points=None, half: bool = False, squared_distances: bool = False,
-                     max_pairs: int | None = None, batch=None):
-        """Which particles lie within `radius` (default: `diameter`) of which, as a CSR edge list in torch CUDA tensors on
-        the crate's device, searched on the GPU (sc_pairs_count_device / sc_pairs_fill_device): ``(offsets, partners[, d2])``
-        -- int64 (n + 1,), int64 (E,), float64 (E,).  Row i's partners are ``partners[offsets[i]:offsets[i + 1]]``, ascending;
-        i and j are rows of `state_tensors()` at the same point of the stream, not ids.  (i, j) is a pair iff i != j and
-        dx*dx + dy*dy <= radius*radius in separately rounded float64 (tests/pairs_spec.py); `half` keeps j > i only;
-        `squared_distances` adds the number that was compared, per pair.  A particle with a coordinate that is not finite
-        has no partners.  `points`, a float64 (n, 2) CUDA tensor, is searched instead of the state.  No cap on a row's
-        length; `sand_crate_amd.pairs.edge_index` turns the result into a (2, E) tensor.
-
-        By default the call synchronises once between counting and filling, reads n and E (16 bytes) and returns tensors
-        cut to them; a coordinate with |c| / radius >= 2^31 raises ValueError.  With `max_pairs=K` nothing synchronises:
-        `offsets` comes at capacity + 1 entries (n + 1 with `points`), `partners` and `d2` at K entries, and last the int64
-        `counts` tensor (n, E): entries of `offsets` past n and of `partners` past min(E, K) are uninitialised, E > K means
-        the list was clipped at K entries, E = -1 is the domain error (nothing else was written).  The tensors are written
-        on the library's stream, and the library's stream does not wait for torch's: read them after `synchronize()`, and
-        have `points` ready before the call -- or run the crate on torch's stream, `engine.set_stream`, and everything
-        torch enqueues afterwards sees them.
-
-        `batch`, an int64 CUDA tensor of B + 1 ascending offsets from 0 to n (`sand_crate_amd.pairs.batch_ptr` makes one
-        from the clouds' sizes), makes `points` B disjoint clouds in one call -- the frames of a minibatch, which may
-        overlap in space completely: cloud b is ``points[batch[b]:batch[b + 1]]``, a pair never crosses clouds, indices are
-        global, and the result is, bit for bit, the per-cloud results concatenated with the partners shifted by
-        ``batch[b]`` (tests/batch_spec.py).  Offsets that are not in order raise ValueError at the synchronisation
-        (E = -3 with `max_pairs`)."""
-        import torch
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(self.diameter if radius is None else radius)
-        _check_batch("pair_tensors", eng.device, points, None, batch, None)
-        rows = eng.capacity if points is None else _point_rows(points)
-        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)
-        sync = max_pairs is None
-        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=half, batch=batch)
-        if sync:
-            eng.synchronize()
-            n, total = (int(v) for v in counts.cpu())
-            if total == N.PAIRS_BATCH:
-                raise ValueError(f"pair_tensors: {_BATCH_ORDER}")
-            if total < 0:
-                raise ValueError(f"pair_tensors: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
-            if points is None:
-                self._count, self._count_known = n, True
-        else:
-            total = int(max_pairs)
-            if total < 0:
-                raise ValueError("max_pairs must not be negative")
-        partners = torch.empty(total, dtype=torch.int64, device=dev)
-        d2 = torch.empty(total, dtype=torch.float64, device=dev) if squared_distances else None
-        eng.pairs_fill(partners, d2)
-        if sync:
-            eng.synchronize()
-            return (offsets[:n + 1], partners) + ((d2,) if squared_distances else ())
-        return (offsets, partners) + ((d2,) if squared_distances else ()) + (counts,)
-
-    def cluster_tensors(self, radius: float | None = None, *, points=None, max_clusters: int | None = None):
-        """What hangs together: the connected components of the graph `pair_tensors` defines at the same `radius` (default:
-        `diameter`), labelled on the GPU from the pair search's grid (sc_pairs_count_device, then sc_pairs_label_device),
-        as torch CUDA tensors on the crate's device: ``(labels, sizes, roots)`` -- int64 (n,), (C,), (C,).  ``labels[i]``
-        is the cluster of row i of `state_tensors()` at the same point of the stream, or -1 for a particle with a
-        coordinate that is not finite: it is in no cluster and bridges none.  Clusters are numbered 0..C-1 in ascending
-        order of their smallest member, ``roots[c]``; ``sizes[c]`` is the member count (tests/cluster_spec.py is the
-        rule; `sand_crate_amd.pairs.largest_cluster` and `cluster_size_of` read the result).  `points`, a float64 (n, 2)
-        CUDA tensor, is labelled instead of the state.
-
-        By default the call synchronises once, reads n and C (16 bytes) and returns tensors cut to them; a coordinate with
-        |c| / radius >= 2^31 raises ValueError.  With `max_clusters=K` nothing synchronises: `labels` comes at capacity
-        entries (n with `points`), `sizes` and `roots` at K entries, and last the int64 `counts` tensor (n, C): entries of
-        `labels` past n and of `sizes` and `roots` past min(C, K) are uninitialised, C > K means that the clusters from K
-        on were not written (`labels` is whole all the same), C = -1 is the domain error (nothing else was written).  The
-        tensors are written on the library's stream, and the library's stream does not wait for torch's: read them after
-        `synchronize()`, and have `points` ready before the call -- or run the crate on torch's stream,
-        `engine.set_stream`, and everything torch enqueues afterwards sees them."""
-        import torch
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(self.diameter if radius is None else radius)
-        rows = eng.capacity if points is None else _point_rows(points)
-        sync = max_clusters is None
-        room = rows if sync else int(max_clusters)
-        if room < 0:
-            raise ValueError("max_clusters must not be negative")
-        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)  # (a temporary: the label reads the workspace)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)          # (n, E) of the count, then (n, C)
-        labels = torch.empty(rows, dtype=torch.int64, device=dev)
-        sizes = torch.empty(room, dtype=torch.int64, device=dev)
-        roots = torch.empty(room, dtype=torch.int64, device=dev)
-        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
-        eng.pairs_label(labels, sizes, roots, counts=counts)
-        if not sync:
-            self._cluster_offsets = offsets  # (held until the next call: the count that writes it is still queued)
-            return labels, sizes, roots, counts
-        eng.synchronize()
-        n, total = (int(v) for v in counts.cpu())
-        if total < 0:
-            raise ValueError(f"cluster_tensors: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
-        if points is None:
-            self._count, self._count_known = n, True
-        return labels[:n], sizes[:total], roots[:total]
-
-    def cluster_sums(self, values, radius: float | None = None, *, points=None, extrema: bool = False,
-                     max_clusters: int | None = None):
-        """What each cluster carries: `cluster_tensors` at the same `radius` and `points`, and per cluster the sums --
-        with `extrema` also the minima and maxima -- of `values` over its members, reduced on the GPU in one call (count,
-        label, sc_pairs_cluster_sums_device): ``(labels, sizes, roots, sums[, mins, maxs])``, the last float64 (C, F).
-        `values` is a float64 (n, F) or (n,) CUDA tensor, F 1 .. 8, whose rows are in the order of `state_tensors()` -- or
-        of `points`; (n,) is one channel and still gives (C, 1).  A cluster's sum adds its members' values in ascending
-        index, pairwise in groups of 64 and groups of groups, every add rounded on its own
-        (tests/cluster_sums_spec.py is the rule): a pure function of the cluster's own members, the same bits on every
-        call, no floating-point atomics anywhere.  A row with label -1 is never read, whatever its values are; a NaN among
-        a cluster's values is that cluster's sum, minimum and maximum.  `sand_crate_amd.pairs.cluster_centers` and
-        `cluster_mean_velocities` read the table of `cluster_observables`.
-
-        Synchronisation and `max_clusters` are exactly those of `cluster_tensors`: by default one synchronisation, tensors
-        cut to n and C, ValueError for a coordinate outside the domain and for `values` with fewer rows than there are
-        points; with `max_clusters=K` nothing synchronises, the per-cluster tensors come at K rows and last the int64
-        `counts` tensor (n, C): C > K means that the clusters from K on were not written, C = -1 is the domain error and
-        C = -2 the short `values` (nothing else was written by the reduction).  `values` must be ready when this is
-        called, as `points` must."""
-        import torch
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(self.diameter if radius is None else radius)
-        if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
-            raise ValueError("values must be a CUDA float64 tensor of shape (n, F) or (n,)")
-        values = (values.unsqueeze(1) if values.dim() == 1 else values).contiguous()
-        width = int(values.shape[1])
-        if not 1 <= width <= N.CLUSTER_SUMS_MAX_CHANNELS:
-            raise ValueError(f"values must have 1 .. {N.CLUSTER_SUMS_MAX_CHANNELS} columns")
-        rows = eng.capacity if points is None else _point_rows(points)
-        sync = max_clusters is None
-        room = rows if sync else int(max_clusters)
-        if room < 0:
-            raise ValueError("max_clusters must not be negative")
-        offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)  # (a temporary: the label reads the workspace)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)          # (n, E) of the count, then (n, C) twice
-        labels = torch.empty(rows, dtype=torch.int64, device=dev)
-        sizes = torch.empty(room, dtype=torch.int64, device=dev)
-        roots = torch.empty(room, dtype=torch.int64, device=dev)
-        tables = tuple(torch.empty((room, width), dtype=torch.float64, device=dev) for _ in range(3 if extrema else 1))
-        if sync:  # (what torch was asked for above is done, and nothing of torch's touches the new tensors)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
-        eng.pairs_label(labels, sizes, roots, counts=counts)
-        eng.pairs_cluster_sums(values, *tables, counts=counts)
-        if not sync:
-            self._cluster_sums_temporaries = (offsets, values)  # (held until the next call: still queued)
-            return (labels, sizes, roots, *tables, counts)
-        eng.synchronize()
-        n, total = (int(v) for v in counts.cpu())
-        if total == N.CLUSTER_SUMS_VALUES_SHORT:
-            raise ValueError(f"cluster_sums: values has {values.shape[0]} rows, fewer than there are points")
-        if total < 0:
-            raise ValueError(f"cluster_sums: a coordinate lies outside the domain |c| / radius < 2^31 (radius {radius!r})")
-        if points is None:
-            self._count, self._count_known = n, True
-        return (labels[:n], sizes[:total], roots[:total], *(t[:total] for t in tables))
-
-    def cluster_observables(self, radius: float | None = None, *, max_clusters: int | None = None):
-        """The probe's observables per droplet: ``(labels, roots, table)``, `table` float64 (C, 14) with the columns
-        `sand_crate_amd.pairs.CLUSTER_FIELDS` -- n, sum_x, sum_y, sum_vx, sum_vy, sum_ke, sum_p, min_x, max_x, min_y,
-        max_y, max_speed2, max_p, n_pressed, named as `probe.FIELDS` names them -- for every cluster of the state at
-        `radius` (default: `diameter`).  The channels are built with torch from `state_tensors()` as the probe builds them,
-        each operation rounded on its own and ``vx*vx + vy*vy`` evaluated once, so `max_speed2` and the kinetic energy
-        agree; one `cluster_sums(..., extrema=True)` reduces them, with its synchronisation and `max_clusters` semantics
-        (then `counts` comes last, and the table's rows from min(C, K) on are uninitialised).  Runs on torch's current
-        stream and the crate's: with `max_clusters` the crate must be on torch's stream (`engine.set_stream`)."""
-        import torch
-        from .pairs import CLUSTER_FIELDS, cluster_channels
-        if max_clusters is None:
-            xy, vv, p = self.state_tensors()
-        else:
-            xy, vv, p, _ = self.state_tensors(sync=False)
-        values = cluster_channels(xy, vv, p)
-        out = self.cluster_sums(values, radius, extrema=True, max_clusters=max_clusters)
-        labels, sizes, roots, sums, mins, maxs = out[:6]
-        table = torch.empty((sums.shape[0], len(CLUSTER_FIELDS)), dtype=torch.float64, device=sums.device)
-        table[:, 0] = sizes
-        table[:, 1:7] = sums[:, 0:6]
-        table[:, 7], table[:, 8], table[:, 9], table[:, 10] = mins[:, 0], maxs[:, 0], mins[:, 1], maxs[:, 1]
-        table[:, 11], table[:, 12], table[:, 13] = maxs[:, 6], maxs[:, 5], sums[:, 7]
-        return (labels, roots, table) + tuple(out[6:])
-
-    @_batch_keywords
-    def neighbor_tensors(self, k: int, radius: float | None = None, *, points=None, queries=None,
-                         squared_distances: bool = False, partner_counts: bool = False, sync: bool = True):
-        """The k nearest particles within `radius` (default: `diameter`) of every particle, as a table of fixed shape in
-        torch CUDA tensors on the crate's device, selected on the GPU from the pair search's grid (sc_pairs_count_device,
-        then sc_pairs_nearest_device): ``(neighbors[, d2][, partners])`` -- int64 (n, k), float64 (n, k), int64 (n,).
-        ``neighbors[i]`` holds the partners of row i of `state_tensors()` at the same point of the stream -- the row of
-        `pair_tensors` -- in ascending order of (squared distance, index), the nearest k of them, and -1 in the places
-        behind (tests/nearest_spec.py is the rule; `sand_crate_amd.pairs.neighbor_mask` and `neighbor_edge_index` read the
-        result).  `squared_distances` adds the numbers that were compared, +inf in the padding; `partner_counts` every
-        row's number of partners without the cap, the row length of `pair_tensors`.  `points`, a float64 (n, 2) CUDA
-        tensor, is searched instead of the state.  With `queries`, a float64 (q, 2) CUDA tensor, the rows are those points
-        instead -- probes, sensors, the cursor: they need not be particles, and one that lies on a particle has it as a
-        partner at distance 0 -- and the tensors have q rows.  `k` is 1 .. 64.
-
-        The shape is known before anything runs, so nothing synchronises between counting and selecting.  `sync=True`
-        synchronises once at the end, reads 16 bytes and returns tensors cut to the row count; a coordinate of a particle
-        or a query with |c| / radius >= 2^31 raises ValueError.  `sync=False` synchronises nothing: the tensors come at
-        capacity rows (n with `points`, q with `queries`) and last the int64 `counts` tensor (rows, cut): rows from the
-        row count on are uninitialised, cut is the number of rows that had more than k partners, cut = -1 is the domain
-        error (nothing else was written).  The tensors are written on the library's stream, and the library's stream does
-        not wait for torch's: read them after `synchronize()`, and have `points` and `queries` ready before the call -- or
-        run the crate on torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them.
-
-        `batch=` (a keyword of the wrapper around this method, `_batch_keywords`, as is `query_batch=`) makes `points` B
-        disjoint clouds in one call, as in `pair_tensors`; with `queries` comes `query_batch`,
-        also B + 1 offsets, from 0 to q: query rows ``query_batch[b]:query_batch[b + 1]`` see only the points of cloud b
-        (a cloud may have points and no queries, or queries and no points).  Offsets that are not in order raise
-        ValueError at the synchronisation (cut = -3 with `sync=False`)."""
-        import torch
-        k = int(k)
-        if not 1 <= k <= N.NEAREST_MAX_K:
-            raise ValueError(f"k must be 1 .. {N.NEAREST_MAX_K}")
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(self.diameter if radius is None else radius)
-        batch, query_batch = self._batch_args
-        _check_batch("neighbor_tensors", eng.device, points, queries, batch, query_batch)
-        bound = eng.capacity if points is None else _point_rows(points)
-        rows = bound if queries is None else _point_rows(queries)
-        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the table reads the workspace)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, cut)
-        neighbors = torch.empty((rows, k), dtype=torch.int64, device=dev)
-        d2 = torch.empty((rows, k), dtype=torch.float64, device=dev) if squared_distances else None
-        partners = torch.empty(rows, dtype=torch.int64, device=dev) if partner_counts else None
-        out = tuple(t for t in (neighbors, d2, partners) if t is not None)
-        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True, batch=batch)
-        count_counts = counts
-        if queries is not None:  # (the count's n stays readable: with queries the table's row count is q)
-            counts = torch.empty(2, dtype=torch.int64, device=dev)
-        if query_batch is not None:
-            eng.pairs_set_query_batch(query_batch)
-        eng.pairs_nearest(neighbors, d2, partners, k=k, queries=queries, counts=counts)
-        if not sync:
-            self._neighbor_temporaries = (offsets, count_counts)  # (held until the next call: the count is still queued)
-            return (*out, counts)
-        eng.synchronize()
-        n, cut = (int(v) for v in counts.cpu())
-        if cut == N.PAIRS_BATCH:
-            raise ValueError(f"neighbor_tensors: {_BATCH_ORDER} (of queries for query_batch)")
-        if cut < 0:
-            raise ValueError(f"neighbor_tensors: a coordinate of a point or a query lies outside the domain "
-                             f"|c| / radius < 2^31 (radius {radius!r})")
-        if points is None:
-            self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
-        return tuple(t[:n] for t in out)
-
-    def field_tensors(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
-                      points=None, queries=None, weight_sums: bool = False, sync: bool = True, batch=None, query_batch=None):
-        """What is there within `radius` (default: `diameter`) of every particle: the weighted sums of an SPH
-        interpolation, as torch CUDA tensors on the crate's device, summed on the GPU over the pair search's grid
-        (sc_pairs_count_device, then sc_pairs_sum_device): ``(sums[, wsum])`` -- float64 (n, C) and (n,).
-        ``sums[i] = sum_j w_ij * values[j]`` over the partners j of row i of `state_tensors()` at the same point of the
-        stream -- the row of `pair_tensors`, and with `include_self` particle i itself --, ``wsum[i] = sum_j w_ij``, with
-        ``w = (1 - d2 / radius**2) ** power``, `power` 0 .. 3 (3: the poly6 shape; 0: w = 1, `wsum` counts the partners).
-        The sums are added in ascending j, every operation rounded on its own: a pure function of the state, the same
-        bits on every call (tests/field_spec.py is the rule; `sand_crate_amd.pairs.normalized` divides the two,
-        `grid_queries` makes a raster of probes).  `values` is a float64 (n, C) or (n,) CUDA tensor whose rows are in the
-        order of `state_tensors()` -- or of `points`, a float64 (n, 2) CUDA tensor that is searched instead of the state;
-        it is made contiguous, any C is served, eight columns per launch against the same count, and (n,) gives sums of
-        shape (n,).  With ``values=None`` only ``(wsum,)`` comes back: the density.  With `queries`, a float64 (q, 2) CUDA
-        tensor, the rows are those points instead -- probes, sensors, the cell centres of an image: they need not be
-        particles, a particle one lies on is a partner at distance 0, `include_self` means nothing -- and the tensors
-        have q rows.  A particle or query with a coordinate that is not finite gives and gets nothing.
-
-        The shape is known before anything runs, so nothing synchronises between counting and summing.  `sync=True`
-        synchronises once at the end, reads 16 bytes and returns tensors cut to the row count; ValueError when a
-        coordinate of a particle or a query has |c| / radius >= 2^31, and when `values` has fewer rows than there are
-        particles.  `sync=False` synchronises nothing: the tensors come at capacity rows (n with `points`, q with
-        `queries`) and last the int64 `counts` tensor (rows, status): rows from the row count on are uninitialised, status
-        -1 is the domain error and -2 the short `values` (nothing else was written).  The tensors are written on the
-        library's stream, and the library's stream does not wait for torch's: read them after `synchronize()`, and have
-        `values`, `points` and `queries` ready before the call -- or run the crate on torch's stream, `engine.set_stream`,
-        and everything torch enqueues afterwards sees them.  What the wrapper itself asks of torch -- the contiguous copy,
-        the split into eights of more than 8 columns and their concatenation -- runs on torch's stream: with `sync=False`
-        those need the crate on torch's stream.
-
-        `batch` and `query_batch` make `points` (and `queries`) B disjoint clouds in one call, as in `neighbor_tensors`:
-        the rows of `values` are global, a sum never crosses clouds.  Offsets that are not in order raise ValueError at the
-        synchronisation (status -3 with `sync=False`)."""
-        import torch
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(self.diameter if radius is None else radius)
-        power = int(power)
-        if not 0 <= power <= 3:
-            raise ValueError("power must be 0 .. 3")
-        _check_batch("field_tensors", eng.device, points, queries, batch, query_batch)
-        flat = False
-        if values is not None:
-            if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
-                raise ValueError("values must be a CUDA float64 tensor of shape (n, C) or (n,)")
-            flat = values.dim() == 1
-            values = (values.unsqueeze(1) if flat else values).contiguous()
-            if values.shape[1] < 1:
-                raise ValueError("values must have at least one column")
-        step = N.FIELDS_MAX_CHANNELS
-        width = 0 if values is None else int(values.shape[1])
-        chunks = [values] if width <= step else [values[:, at:at + step].contiguous() for at in range(0, width, step)]
-        bound = eng.capacity if points is None else _point_rows(points)
-        rows = bound if queries is None else _point_rows(queries)
-        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the sum reads the workspace)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, status)
-        want_wsum = weight_sums or values is None
-        wsum = torch.empty(rows, dtype=torch.float64, device=dev) if want_wsum else None
-        parts = [None if v is None else torch.empty((rows, v.shape[1]), dtype=torch.float64, device=dev) for v in chunks]
-        if sync:  # (what torch was asked for above is done, and nothing of torch's touches the new tensors)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True, batch=batch)
-        count_counts = counts
-        if queries is not None:  # (the count's n stays readable: with queries the sums' row count is q)
-            counts = torch.empty(2, dtype=torch.int64, device=dev)
-        for at, (v, part) in enumerate(zip(chunks, parts)):  # (every launch consumes the query offsets: given each time)
-            eng.pairs_sum(v, part, wsum if at == 0 else None, power=power, include_self=include_self, queries=queries,
-                          counts=counts, query_batch=query_batch)
-        if not sync:
-            self._field_temporaries = (offsets, count_counts, chunks, parts)  # (held until the next call: still queued)
-        else:
-            eng.synchronize()
-            n, status = (int(v) for v in counts.cpu())
-            if status == N.PAIRS_BATCH:
-                raise ValueError(f"field_tensors: {_BATCH_ORDER} (of queries for query_batch)")
-            if status == N.FIELDS_DOMAIN:
-                raise ValueError(f"field_tensors: a coordinate of a point or a query lies outside the domain "
-                                 f"|c| / radius < 2^31 (radius {radius!r})")
-            if status == N.FIELDS_VALUES_SHORT:
-                raise ValueError(f"field_tensors: values has {values.shape[0]} rows, fewer than there are points")
-            if points is None:
-                self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
-        out = ()
-        if values is not None:
-            sums = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
-            out = (sums.view(-1) if flat else sums,)
-        if want_wsum:
-            out += (wsum,)
-        return (*out, counts) if not sync else tuple(t[:n] for t in out)
-
-    def field_function(self, values=None, radius: float | None = None, *, power: int = 3, include_self: bool = True,
-                       points=None, queries=None, weight_sums: bool = False, batch=None, query_batch=None):
-        """`field_tensors(..., sync=True)` under torch autograd: the same arguments, the same results bit for bit, attached
-        to the graph when `values`, `points` or `queries` requires grad -- `backward()` then gives their gradients from
-        the same grid kernels (sc_pairs_sum_device with rows and partners swapped for the values,
-        sc_pairs_sum_grad_device for the positions; tests/field_grad_spec.py is the rule).  When nothing requires grad it
-        is `field_tensors` and nothing more.  Once differentiable; no gradient with respect to `radius`, no `sync=False`
-        form; `batch` and `query_batch` as in `field_tensors`, and the backward passes them on:
-        `sand_crate_amd.fields.field_function` has the details."""
-        from .fields import field_function
-        return field_function(self, values, radius, power=power, include_self=include_self, points=points, queries=queries,
-                              weight_sums=weight_sums, batch=batch, query_batch=query_batch)
-
-    def distance_histogram(self, edges, *, points=None, queries=None, per_row: bool = False, totals: bool = True,
-                           sync: bool = True):
-        """How far apart the particles are: the histogram of the pair distances over the bins `edges` delimits, as torch
-        CUDA tensors on the crate's device, counted on the GPU over the pair search's grid (sc_pairs_count_device at the
-        radius ``edges[-1]``, then sc_pairs_hist_device): ``([table, ]total)`` -- int32 (n, B) with `per_row`, int64 (B,)
-        with `totals`.  `edges` is a host sequence or NumPy array of B + 1 float64 distances, B 1 .. 64, ``0 <= edges[0]
-        < edges[1] < ...`` (`sand_crate_amd.pairs.shell_edges` makes equal-width ones).  ``table[i, b]`` is the number of
-        partners j != i of row i of `state_tensors()` at the same point of the stream with ``edges[b]**2 <= d2 <
-        edges[b + 1]**2``, the last bin closed on top, d2 the separately rounded float64 dx*dx + dy*dy of `pair_tensors`:
-        the squares are compared, no square root is taken (tests/hist_spec.py is the rule).  ``total[b]`` is the sum of
-        the column: it counts ORDERED pairs, each unordered pair twice (`sand_crate_amd.pairs.radial_distribution` turns
-        it into g(r)).  Only integers are added: the same result on every call.  `points`, a float64 (n, 2) CUDA tensor,
-        is searched instead of the state.  With `queries`, a float64 (q, 2) CUDA tensor, the rows are those points
-        instead -- probes, sensors: they need not be particles, a particle one lies on is a partner at distance 0 --
-        and the table has q rows.  A particle or query with a coordinate that is not finite gives and gets nothing.
-
-        The shape is known before anything runs, so nothing synchronises between counting and binning.  `sync=True`
-        synchronises once at the end, reads 16 bytes and returns the table cut to the row count; ValueError when a
-        coordinate of a particle or a query has |c| / edges[-1] >= 2^31.  `sync=False` synchronises nothing: the table
-        comes at capacity rows (n with `points`, q with `queries`) and last the int64 `counts` tensor (rows, status):
-        rows from the row count on are uninitialised, status -1 is the domain error (nothing else was written).  The
-        tensors are written on the library's stream, and the library's stream does not wait for torch's: read them
-        after `synchronize()`, and have `points` and `queries` ready before the call -- or run the crate on torch's
-        stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
-        import torch
-        if not per_row and not totals:
-            raise ValueError("neither per_row nor totals: nothing to return")
-        e = np.array(edges, dtype=np.float64)
-        bins = len(N.hist_squared_edges(e)) - 1
-        if not e[-1] > 0:  # (never: the edges ascend from 0 or more)
-            raise ValueError("the last edge must be positive")
-        eng = self._engine
-        dev = torch.device("cuda", eng.device)
-        radius = float(e[-1])
-        bound = eng.capacity if points is None else _point_rows(points)
-        rows = bound if queries is None else _point_rows(queries)
-        offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the histogram reads the workspace)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)           # (n, E) of the count, then (rows, status)
-        table = torch.empty((rows, bins), dtype=torch.int32, device=dev) if per_row else None
-        total = torch.empty(bins, dtype=torch.int64, device=dev) if totals else None
-        if sync:  # (nothing of torch's touches the new tensors, unless their memory was freed with work still queued)
-            torch.cuda.current_stream(dev).synchronize()
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
-        count_counts = counts
-        if queries is not None:  # (the count's n stays readable: with queries the table's row count is q)
-            counts = torch.empty(2, dtype=torch.int64, device=dev)
-        eng.pairs_hist(table, total, edges=e, queries=queries, counts=counts)
-        if not sync:
-            self._hist_temporaries = (offsets, count_counts)  # (held until the next call: the count is still queued)
-            return (*(t for t in (table, total) if t is not None), counts)
-        eng.synchronize()
-        n, status = (int(v) for v in counts.cpu())
-        if status == N.HIST_DOMAIN:
-            raise ValueError(f"distance_histogram: a coordinate of a point or a query lies outside the domain "
-                             f"|c| / radius < 2^31 (radius {radius!r})")
-        if points is None:
-            self._count, self._count_known = (n if queries is None else int(count_counts[0])), True
-        return (() if table is None else (table[:n],)) + (() if total is None else (total,))
 
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()

@@ -86,6 +86,30 @@ def _state_tensor(t, name: str, dtype: str, tail: tuple, device: int, rows: int 
     return int(shape[0])
 
 
+def _addresses(spare, *tensors) -> list:
+    """The addresses of `tensors` for the library; None for None, which asks for the state or the self form, or says that
+    an array is absent.  An empty tensor has no address: nothing is read or written there, so any address serves --
+    `spare`'s."""
+    return [None if t is None else N._P(t.data_ptr() if t.shape[0] else spare.data_ptr()) for t in tensors]
+
+
+def _room(room, held: int, whose: str, unit: str = "rows") -> int:
+    """`room` of a reader, by default all the `held` rows of its tensors; ValueError for more than they hold."""
+    room = held if room is None else int(room)
+    if room > held:
+        raise ValueError(f"room {room} exceeds {whose} {held} {unit}")
+    return room
+
+
+def _counts_tensor(counts, device: int) -> None:
+    _state_tensor(counts, "counts", "int64", (), device, 2)
+
+
+def _query_rows(queries, device: int) -> int:
+    """The rows of `queries`, float64 (q, 2), or 0 for None: the self form."""
+    return 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), device)
+
+
 def _batch_tensor(t, name: str, device: int, entries: int | None = None) -> int:
     """The entries of the offsets of a batched call, `batch` or `query_batch`: a contiguous 1-D int64 CUDA tensor on
     `device` of B + 1 >= 2 entries (`entries` of them when given).  ValueError otherwise, before the library is touched."""
@@ -262,19 +286,15 @@ class Engine:
                 raise ValueError("batch needs points: the state is one cloud")
             _batch_tensor(batch, "batch", self.device)
         rows = _state_tensor(offsets, "offsets", "int64", (), self.device) - 1
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        _counts_tensor(counts, self.device)
         if rows < 0:
             raise ValueError("offsets must hold at least one entry")
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the offsets' {rows} rows")
+        room = _room(room, rows, "the offsets'")
         radius = float(radius)
         if not (0.0 < radius < float("inf")):
             raise ValueError("radius must be finite and positive")
-        # (an empty tensor has no address, and a null address asks for the state: no point is read, any address serves)
-        xy = None if points is None else N._P(points.data_ptr() if n else offsets.data_ptr())
         self.pairs_set_batch(batch)  # (None: a batch left pending by hand does not reach this count)
-        N.check(self._lib.sc_pairs_count_device(self._ctx, xy, n, radius,
+        N.check(self._lib.sc_pairs_count_device(self._ctx, *_addresses(offsets, points), n, radius,
                                                 N.PAIRS_HALF if half else 0, N._P(offsets.data_ptr()), room,
                                                 N._P(counts.data_ptr())))
         return counts
@@ -286,9 +306,7 @@ class Engine:
         rows = _state_tensor(partners, "partners", "int64", (), self.device)
         if d2 is not None:
             _state_tensor(d2, "d2", "float64", (), self.device, rows)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the tensors' {rows} entries")
+        room = _room(room, rows, "the tensors'", "entries")
         N.check(self._lib.sc_pairs_fill_device(self._ctx, N._P(partners.data_ptr()),
                                                None if d2 is None else N._P(d2.data_ptr()), room))
         return partners
@@ -307,16 +325,13 @@ class Engine:
         for t, name in ((sizes, "sizes"), (roots, "roots")):
             if t is not None:
                 clusters = _state_tensor(t, name, "int64", (), self.device, clusters)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the labels' {rows} rows")
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the labels'")
         room_clusters = (clusters or 0) if room_clusters is None else int(room_clusters)
         if room_clusters > (clusters or 0):
             raise ValueError(f"room_clusters {room_clusters} exceeds the tensors' {clusters or 0} entries")
-        # (an empty tensor has no address: nothing is written there, any address serves)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
-        N.check(self._lib.sc_pairs_label_device(self._ctx, ptr(labels), room, ptr(sizes), ptr(roots), room_clusters,
+        labels_at, sizes_at, roots_at = _addresses(counts, labels, sizes, roots)
+        N.check(self._lib.sc_pairs_label_device(self._ctx, labels_at, room, sizes_at, roots_at, room_clusters,
                                                 N._P(counts.data_ptr())))
         return counts
 
@@ -338,17 +353,17 @@ class Engine:
         for t, name in ((mins, "mins"), (maxs, "maxs")):
             if t is not None:
                 _state_tensor(t, name, "float64", (channels,), self.device, clusters)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
+        _counts_tensor(counts, self.device)
         room_clusters = clusters if room_clusters is None else int(room_clusters)
         if room_clusters > clusters:
             raise ValueError(f"room_clusters {room_clusters} exceeds the tensors' {clusters} rows")
-        # (an empty tensor has no address: nothing is read or written there, any address serves)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
-        N.check(self._lib.sc_pairs_cluster_sums_device(self._ctx, ptr(values), held, channels, ptr(sums), ptr(mins), ptr(maxs),
-                                                       room_clusters, N._P(counts.data_ptr())))
+        values_at, *tables_at = _addresses(counts, values, sums, mins, maxs)
+        N.check(self._lib.sc_pairs_cluster_sums_device(self._ctx, values_at, held, channels, *tables_at, room_clusters,
+                                                       N._P(counts.data_ptr())))
         return counts
 
-    def pairs_nearest(self, neighbors, d2=None, partners=None, *, k: int, queries=None, counts, room: int | None = None):
+    def pairs_nearest(self, neighbors, d2=None, partners=None, *, k: int, queries=None, counts, room: int | None = None,
+                      query_batch=None):
         """The nearest-k table of the last `pairs_count`, whichever `half` it had (sc_pairs_nearest_device; the rule is
         tests/nearest_spec.py): `neighbors`, int64 (R, k), receives per row the k nearest partners within the count's
         radius, ascending in (d2, j) and padded with -1; `d2`, float64 (R, k) or None, their squared distances, padded
@@ -357,8 +372,8 @@ class Engine:
         partner's rival, a point it coincides with is a partner at d2 = 0.  `counts`, int64 (2,), receives the row count
         and the number of rows with more than k partners (-1: a point or a query lies outside the domain, nothing else
         is written; -3: the offsets of a batched call are not in order).  `room` defaults to R rows.  On a batched grid
-        `queries` need their B + 1 offsets first: `pairs_set_query_batch` right before this call (the parameter list here
-        is as it was).  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
+        `queries` come with `query_batch`, their B + 1 offsets (`pairs_set_query_batch`).  Enqueued on the context's stream,
+        no synchronisation.  Returns `counts`."""
         k = int(k)
         if not 1 <= k <= N.NEAREST_MAX_K:
             raise ValueError(f"k must be 1 .. {N.NEAREST_MAX_K}")
@@ -367,16 +382,12 @@ class Engine:
             _state_tensor(d2, "d2", "float64", (k,), self.device, rows)
         if partners is not None:
             _state_tensor(partners, "partners", "int64", (), self.device, rows)
-        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the table's {rows} rows")
-        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
-        # for the self form)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
-        N.check(self._lib.sc_pairs_nearest_device(self._ctx, ptr(queries), q, k, ptr(neighbors), ptr(d2), ptr(partners),
-                                                  room, N._P(counts.data_ptr())))
+        q = _query_rows(queries, self.device)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the table's")
+        self._query_batch(queries, query_batch)
+        queries_at, *table_at = _addresses(counts, queries, neighbors, d2, partners)
+        N.check(self._lib.sc_pairs_nearest_device(self._ctx, queries_at, q, k, *table_at, room, N._P(counts.data_ptr())))
         return counts
 
     def pairs_sum(self, values=None, sums=None, wsum=None, *, power: int = 3, include_self: bool = True, queries=None,
@@ -411,17 +422,13 @@ class Engine:
             rows = _state_tensor(sums, "sums", "float64", (channels,), self.device)
         if wsum is not None:
             rows = _state_tensor(wsum, "wsum", "float64", (), self.device, rows)
-        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the tensors' {rows} rows")
-        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
-        # for the self form)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        q = _query_rows(queries, self.device)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the tensors'")
         self._query_batch(queries, query_batch)
-        N.check(self._lib.sc_pairs_sum_device(self._ctx, ptr(queries), q, ptr(values), values_rows or 0, channels, power,
-                                              N.FIELDS_SELF if include_self else 0, ptr(sums), ptr(wsum), room,
+        queries_at, values_at, sums_at, wsum_at = _addresses(counts, queries, values, sums, wsum)
+        N.check(self._lib.sc_pairs_sum_device(self._ctx, queries_at, q, values_at, values_rows or 0, channels, power,
+                                              N.FIELDS_SELF if include_self else 0, sums_at, wsum_at, room,
                                               N._P(counts.data_ptr())))
         return counts
 
@@ -463,18 +470,13 @@ class Engine:
             raise ValueError(f"row_rows {row_rows} exceeds the row arrays' {held_a or 0} rows")
         if not 0 <= part_rows <= (held_b or 0):
             raise ValueError(f"part_rows {part_rows} exceeds the partner arrays' {held_b or 0} rows")
-        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the gradient's {rows} rows")
-        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
-        # for the self form, or says that an array is absent)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
+        q = _query_rows(queries, self.device)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the gradient's")
         self._query_batch(queries, query_batch)
-        N.check(self._lib.sc_pairs_sum_grad_device(self._ctx, ptr(queries), q, ptr(row_a), row_rows, ptr(part_b), part_rows,
-                                                   channels, ptr(row_s), ptr(part_s), power, ptr(grad), room,
-                                                   N._P(counts.data_ptr())))
+        queries_at, a_at, b_at, row_s_at, part_s_at, grad_at = _addresses(counts, queries, row_a, part_b, row_s, part_s, grad)
+        N.check(self._lib.sc_pairs_sum_grad_device(self._ctx, queries_at, q, a_at, row_rows, b_at, part_rows, channels,
+                                                   row_s_at, part_s_at, power, grad_at, room, N._P(counts.data_ptr())))
         return counts
 
     def pairs_hist(self, table=None, total=None, *, edges, queries=None, counts, room: int | None = None):
@@ -496,15 +498,11 @@ class Engine:
         rows = 0 if table is None else _state_tensor(table, "table", "int32", (bins,), self.device)
         if total is not None:
             _state_tensor(total, "total", "int64", (), self.device, bins)
-        q = 0 if queries is None else _state_tensor(queries, "queries", "float64", (2,), self.device)
-        _state_tensor(counts, "counts", "int64", (), self.device, 2)
-        room = rows if room is None else int(room)
-        if room > rows:
-            raise ValueError(f"room {room} exceeds the table's {rows} rows")
-        # (an empty tensor has no address: nothing is read or written there, any address serves -- but a null one asks
-        # for the self form, or says that an output is absent)
-        ptr = lambda t: None if t is None else N._P(t.data_ptr() if t.shape[0] else counts.data_ptr())  # noqa: E731
-        N.check(self._lib.sc_pairs_hist_device(self._ctx, ptr(queries), q, N.dptr(e2), bins, ptr(table), ptr(total), room,
+        q = _query_rows(queries, self.device)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the table's")
+        queries_at, table_at, total_at = _addresses(counts, queries, table, total)
+        N.check(self._lib.sc_pairs_hist_device(self._ctx, queries_at, q, N.dptr(e2), bins, table_at, total_at, room,
                                                N._P(counts.data_ptr())))
         return counts
 

@@ -6,19 +6,9 @@ distance only, which has the same bits from either end), the positions' gradient
 from __future__ import annotations
 
 from . import _native as N
+from .neighbourhood import _Search, _field_values
 
 _function = None
-
-
-def _check_status(status: int, radius: float, what: str) -> None:
-    if status == N.PAIRS_BATCH:
-        raise ValueError("field_function: batch offsets must start at 0, not descend and end at the number of points "
-                         "(of queries for query_batch)")
-    if status == N.FIELDS_DOMAIN:
-        raise ValueError(f"field_function: a coordinate of a point or a query lies outside the domain "
-                         f"|c| / radius < 2^31 (radius {radius!r})")
-    if status == N.FIELDS_VALUES_SHORT:
-        raise ValueError(f"field_function: {what} has fewer rows than there are points")
 
 
 def position_grad(crate, points, radius: float, power: int, row_a=None, part_b=None, row_s=None, part_s=None, *,
@@ -28,16 +18,14 @@ def position_grad(crate, points, radius: float, power: int, row_a=None, part_b=N
     scalars `row_s` / `part_s` with the first, and adds the results in ascending order.  The rows are the points (the
     self form) or `queries`.  `batch` cuts `points` -- the grid -- into clouds and `query_batch` the `queries`, as in
     `field_tensors`.  Synchronises torch's stream before enqueuing and the library's at the end, as
-    `field_tensors(sync=True)` does."""
+    `field_tensors(sync=True)` does (`neighbourhood._Search`)."""
     import torch
-    eng = crate.engine
-    dev = torch.device("cuda", eng.device)
     points = points.contiguous()
     queries = None if queries is None else queries.contiguous()
-    bound = int(points.shape[0])
-    rows = bound if queries is None else int(queries.shape[0])
+    call = _Search(crate, "field_function", radius, points=points, queries=queries, batch=batch, query_batch=query_batch,
+                   short="an upstream gradient or the values has fewer rows than there are points")
     if power == 0:  # (the weights are constant: nothing runs)
-        return torch.zeros((rows, 2), dtype=torch.float64, device=dev)
+        return torch.zeros((call.rows, 2), dtype=torch.float64, device=call.dev)
     step = N.FIELDS_MAX_CHANNELS
     width = 0 if row_a is None else int(row_a.shape[1])
     if width <= step:
@@ -46,17 +34,12 @@ def position_grad(crate, points, radius: float, power: int, row_a=None, part_b=N
         groups = [(row_a[:, at:at + step].contiguous(), part_b[:, at:at + step].contiguous()) for at in range(0, width, step)]
     row_s = None if row_s is None else row_s.contiguous()
     part_s = None if part_s is None else part_s.contiguous()
-    offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)  # (a temporary: the gradient reads the workspace)
-    count_counts = torch.empty(2, dtype=torch.int64, device=dev)
-    counts = torch.empty(2, dtype=torch.int64, device=dev)
-    parts = [torch.empty((rows, 2), dtype=torch.float64, device=dev) for _ in groups]
-    torch.cuda.current_stream(dev).synchronize()  # (what torch was asked for above is done)
-    eng.pairs_count(points, radius=radius, offsets=offsets, counts=count_counts, half=True, batch=batch)
+    parts = [torch.empty((call.rows, 2), dtype=torch.float64, device=call.dev) for _ in groups]
+    call.count()
     for at, ((a, b), part) in enumerate(zip(groups, parts)):
-        eng.pairs_sum_grad(part, a, b, row_s if at == 0 else None, part_s if at == 0 else None, power=power, queries=queries,
-                           counts=counts, query_batch=query_batch)
-    eng.synchronize()
-    _check_status(int(counts[1]), radius, "an upstream gradient or the values")
+        call.eng.pairs_sum_grad(part, a, b, row_s if at == 0 else None, part_s if at == 0 else None, power=power,
+                                queries=queries, counts=call.counts, query_batch=query_batch)
+    call.read()
     total = parts[0]
     for part in parts[1:]:
         total = total + part
@@ -156,14 +139,7 @@ def field_function(crate, values=None, radius=None, *, power: int = 3, include_s
     if not 0 <= power <= 3:
         raise ValueError("power must be 0 .. 3")
     radius = float(crate.diameter if radius is None else radius)
-    flat = False
-    if values is not None:
-        if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
-            raise ValueError("values must be a CUDA float64 tensor of shape (n, C) or (n,)")
-        flat = values.dim() == 1
-        values = (values.unsqueeze(1) if flat else values).contiguous()
-        if values.shape[1] < 1:
-            raise ValueError("values must have at least one column")
+    values, flat = _field_values(values)
     if batch is not None and points is None:
         raise ValueError("field_function: batch needs points, the state is one cloud")
     if points is None:

@@ -295,11 +295,12 @@ def test_python_surface():
     from sand_crate_amd import Crate
     from sand_crate_amd.engine import Engine
     p = inspect.signature(Engine.pairs_nearest).parameters
-    assert list(p) == ["self", "neighbors", "d2", "partners", "k", "queries", "counts", "room"]
+    assert list(p) == ["self", "neighbors", "d2", "partners", "k", "queries", "counts", "room", "query_batch"]
     assert p["d2"].default is None and p["partners"].default is None and p["queries"].default is None
     assert all(p[name].kind is inspect.Parameter.KEYWORD_ONLY for name in ("k", "queries", "counts", "room"))
     p = inspect.signature(Crate.neighbor_tensors).parameters
-    assert list(p) == ["self", "k", "radius", "points", "queries", "squared_distances", "partner_counts", "sync"]
+    assert list(p) == ["self", "k", "radius", "points", "queries", "squared_distances", "partner_counts", "sync", "batch",
+                       "query_batch"]
     assert p["radius"].default is None and p["sync"].default is True
     assert all(p[name].kind is inspect.Parameter.KEYWORD_ONLY for name in list(p)[3:])
 
