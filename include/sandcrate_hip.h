@@ -567,6 +567,46 @@ int sc_track_disable(sc_ctx* ctx);
 int sc_track_read(sc_ctx* ctx, uint8_t* out, int64_t room, int64_t* n_bytes, int64_t* n_frames, int64_t* dropped);
 int sc_track_load(sc_ctx* ctx, const uint8_t* frame, int64_t n_bytes, int32_t plain);
 
+/* Trajectories: the state at full precision as frames in DEVICE memory of the caller (e.g. torch CUDA tensors), one row
+ * per particle id: row r of a frame is the live particle whose id is id0 + r, whatever slot it is stored in, so the
+ * frames of a run line up by particle without a sort (tests/trajectory_spec.py is the rule, byte for byte, on top of
+ * tests/state_spec.py).  The log is
+ *   dev_states    float64 frames x rows x 4, aligned to 16 bytes: (x, y, vx, vy), the very bits sc_export_state_device
+ *                 delivers for that particle; the row of an id that is not live holds four quiet NaNs, each
+ *                 0x7FF8000000000000.  "Live" is the export's rule -- a stored slot whose x is finite -- so a row is
+ *                 present exactly when its x is finite; -0.0, infinities and NaN in y or the velocity pass unchanged.
+ *   dev_pressure  float64 frames x rows, or NULL: the export's pressure (0 where the last finished tick did not leave
+ *                 the slot live), the same NaN where the row is absent.
+ *   dev_ticks, dev_counts, dev_outside   int64 x frames: the frame's tick (ticks finished by the context), its live
+ *                 particles, and how many of them have an id outside [id0, id0 + rows): counted, not recorded.
+ *   dev_words     int64 x 4: the cursor (frames written), the frames dropped because the log was full, the frame the last
+ *                 reserve chose (-1: none), one spare.
+ * Ids are unique in a state; nothing is said about a state where they are not.
+ *
+ * sc_traj_enable_device  from now on every finished tick (sc_step_finish, so also sc_tick and every tick of sc_step) whose
+ *     count of finished ticks is a multiple of `every` (>= 1) writes one frame at the cursor, on the context's stream after
+ *     the force kernel: three launches, no synchronisation, no host traffic, no allocation.  A tick that finds the log
+ *     full (`frames` frames) writes nothing and the dropped word goes up; an abandoned tick leaves no frame and is not
+ *     counted as dropped.  `reset` != 0 zeroes the words on the stream, a fresh recording; 0 continues where they stand --
+ *     a log may outlive a context and go on in its successor.  The arrays stay the caller's: they must live, and not be
+ *     written elsewhere, until sc_traj_disable and a synchronisation.  Enabling again replaces the log.  While enabled,
+ *     results are bit for bit what they are without it (ticks are then never fused with their successor's wall pass, for
+ *     the probe's reason).
+ * sc_traj_capture        writes one frame of the state as it stands, between ticks: the initial state, or one just loaded.
+ *     Enqueued only.  It takes its place in the log like any frame, or is dropped and counted.
+ * sc_traj_disable        stops recording; the log is left as it is.
+ * SC_ERR_ARG for null pointers (dev_pressure apart), misaligned states, frames < 1, rows < 1, id0 < 0,
+ * id0 + rows > 2^31 - 1 or every < 1.  SC_ERR_STATE between sc_step_begin and sc_step_finish, for sc_traj_capture without
+ * sc_traj_enable_device, for enabling / disabling after sc_set_next_inputs promised the next tick, and for all of them
+ * on a context in slab mode (sc_set_slab); a refused call leaves the log and a recording already running as they were.
+ * Recording reads the state only: no counter, look-ahead promise, RNG position or pending error flag changes, and its
+ * launches are not bracketed by the timing events. */
+int sc_traj_enable_device(sc_ctx* ctx, double* dev_states, double* dev_pressure /* may be NULL */, int64_t* dev_ticks,
+                          int64_t* dev_counts, int64_t* dev_outside, int64_t* dev_words, int64_t frames, int64_t id0,
+                          int64_t rows, int64_t every, int32_t reset);
+int sc_traj_capture(sc_ctx* ctx);
+int sc_traj_disable(sc_ctx* ctx);
+
 /* The state to and from DEVICE memory of the caller (e.g. torch CUDA tensors), in particle-index order: what
  * sc_download_state / sc_upload_state move through the host, without the host.
  *

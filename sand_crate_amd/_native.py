@@ -204,6 +204,9 @@ SIGNATURES = {
     "sc_track_disable": (C.c_int, [_P]),
     "sc_track_read": (C.c_int, [_P, _P, C.c_int64, _I64, _I64, _I64]),
     "sc_track_load": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
+    "sc_traj_enable_device": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "sc_traj_capture": (C.c_int, [_P]),
+    "sc_traj_disable": (C.c_int, [_P]),
     "sc_export_state_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
     "sc_import_state_device": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
     "sc_pairs_count_device": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32, _P, C.c_int64, _P]),

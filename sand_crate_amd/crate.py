@@ -52,6 +52,7 @@ from .neighbourhood import _Neighbourhood
 from .particle_source import build_particle_sources
 from .probe import FIELDS, as_dict
 from . import track as _track
+from .trajectory import Trajectory, check_log, check_window
 from .rigid_body import build_rigid_bodies
 from .utils.geometry_utils import pad_segments
 
@@ -137,6 +138,7 @@ class Crate(_Neighbourhood):
         self._observed = []        # rows read from an engine that is gone, or before the log was switched off
         self._track = None         # (every, capacity_bytes) of the device log of packed frames, or None: not tracking
         self._tracked = []         # (frames, dropped) read from an engine that is gone, or before the log was switched off
+        self._trajectory = None    # the `Trajectory` that records, or None
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -301,6 +303,8 @@ class Crate(_Neighbourhood):
         if getattr(self, "_track", None) is not None:  # ... and so does the log of frames
             self._tracked.append(self._read_track(old))
             self._engine.track_enable(*self._track)
+        if getattr(self, "_trajectory", None) is not None:  # ... and the trajectory: same tensors, the words as they stand
+            self._trajectory._move_to(self._engine)
         old.close()
         if len(snap["ids"]):
             self._engine.upload_with_ids(snap["particles"], snap["velocities"], snap["ids"])
@@ -455,6 +459,44 @@ class Crate(_Neighbourhood):
         if self._track is not None:
             chunks.append(self._read_track(self._engine))
         return [f for c in chunks for f in c[0]], sum(c[1] for c in chunks)
+
+    # ------------------------------------------------------------------ trajectories (sc_traj_*; tests/trajectory_spec.py)
+    def record_trajectory(self, frames: int, *, ids=None, every: int = 1, pressure: bool = False,
+                          initial: bool = True) -> Trajectory:
+        """Record the run at full precision into torch CUDA tensors, one row per particle id: while the returned
+        `Trajectory` records, every tick whose number is a multiple of `every` (`physics_tick` and each tick of `run`)
+        writes one frame -- ``states[t, r]`` is (x, y, vx, vy) of the live particle with id ``lo + r``, exactly what
+        `state_tensors` would deliver for it, and NaN where that id is not live; with `pressure` its pressure too -- into
+        a log of `frames` frames, with no sort, no allocation and no synchronisation until `Trajectory.read()`.  A frame
+        that finds the log full is dropped and counted.  `ids` = (lo, hi) is the window of ids that get a row; the default
+        is (0, `max_particles` of the world's configuration) -- not the capacity: a run does not depend on it -- and live
+        particles outside it are counted per frame, not recorded.  `initial` captures the state as it stands as the first
+        frame.  One recording at a time: a second call stops the first, whose tensors stay readable.
+
+        The log is written on the library's stream, and the library's stream does not wait for torch's: read it after
+        `Trajectory.read()` or `synchronize()` -- or run the crate on torch's stream, `engine.set_stream`, and everything
+        torch enqueues afterwards sees it."""
+        frames, every = check_log(frames, every)
+        id0, rows = check_window(ids, int(self.world_config.coefficients["max_particles"]))
+        self.stop_trajectory()
+        self._trajectory = Trajectory(self._engine, frames, id0, rows, every, bool(pressure))
+        if initial:
+            self._trajectory.capture()
+        return self._trajectory
+
+    def stop_trajectory(self) -> None:
+        """Stops the recording `record_trajectory` started, if any, and synchronises: nothing is queued against its
+        tensors afterwards."""
+        traj, self._trajectory = getattr(self, "_trajectory", None), None
+        if traj is not None:
+            traj.stop()
+
+    def close(self) -> None:
+        """Stops a recording into torch's memory, then frees the GPU context."""
+        try:
+            self.stop_trajectory()
+        finally:
+            self._engine.close()
 
     # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
     def _set_hud(self, hud, width: int) -> None:

@@ -21,6 +21,7 @@
 #include "sc_fields_grad.h"
 #include "sc_hist.h"
 #include "sc_track.h"
+#include "sc_traj.h"
 #include "sc_rccl.h"
 #include "sc_render.h"
 #include "sc_rng.h"
@@ -754,6 +755,7 @@ int sc_set_noise_host(sc_ctx* c, const double* u01, int64_t n_pairs) {
 // what a finished tick appends to the logs that are on (sc_host_logs.h)
 static int probe_launch(sc_ctx* c, bool to_log);
 static int track_launch(sc_ctx* c, bool to_log);
+static int traj_launch(sc_ctx* c, bool on_demand);
 
 int sc_step_finish(sc_ctx* c) {
   if (!c) return fail(SC_ERR_ARG, "null context");
@@ -781,9 +783,10 @@ int sc_step_finish(sc_ctx* c) {
   WallInputs wn;
   std::memset(&wn, 0, sizeof wn);
   const bool slab_ready = !c->slab || c->link.haloL || !(c->link.has_left || c->link.has_right);
-  // (the monitor runs with the plain kernel; the probe's log and the track log record the state sc_download_state
-  // stands for, which a fused tick does not leave in the storage arrays)
-  const bool fused = c->have_next && slab_ready && !c->custom_grid && !c->monitor_on && !c->probe.on && !c->track.on;
+  // (the monitor runs with the plain kernel; the probe's log, the track log and the trajectory log record the state
+  // sc_download_state stands for, which a fused tick does not leave in the storage arrays)
+  const bool fused =
+      c->have_next && slab_ready && !c->custom_grid && !c->monitor_on && !c->probe.on && !c->track.on && !c->traj.on;
   if (fused) {
     World next;
     int rc = build_world(c, next, c->next, c->tick + 1);
@@ -821,7 +824,9 @@ int sc_step_finish(sc_ctx* c) {
   c->stats_live = -1;
   if (c->probe.on && !c->slab && !c->custom_grid)
     if (const int rc = probe_launch(c, true)) return rc;
-  if (c->track.on && !c->slab && !c->custom_grid && c->tick % c->track.every == 0) return track_launch(c, true);
+  if (c->track.on && !c->slab && !c->custom_grid && c->tick % c->track.every == 0)
+    if (const int rc = track_launch(c, true)) return rc;
+  if (c->traj.on && !c->slab && !c->custom_grid && c->tick % c->traj.every == 0) return traj_launch(c, false);
   return SC_OK;
 }
 

@@ -173,6 +173,15 @@ struct TrackState {
   }
 };
 
+// Trajectories (sc_traj.h; sc_host_logs.h): the log of sc_traj_enable_device -- the caller's device memory, not owned:
+// states, pressure (or null), the frames' ticks, counts and outsiders, and the words (cursor, dropped frames, the frame
+// the last reserve chose) -- with its capacity in frames, the window of ids and every how many ticks a frame is taken.
+struct TrajState {
+  TrajLog log{};
+  bool on = false;
+  int64_t frames = 0, id0 = 0, rows = 0, every = 1;
+};
+
 // What every rendered frame is made of and carries (sc_render.h, sc_hud.h, sc_arrows.h; sc_host_frames.h).
 struct FrameState {
   // sc_render: the per-pixel key buffer and (host path) the device frame, grown to the largest frame asked for
@@ -462,6 +471,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
 
   ProbeState probe;
   TrackState track;
+  TrajState traj;
   FrameState frame;
   JpegSpace jpeg;
   GifSpace gif;
@@ -493,8 +503,8 @@ namespace {
 //                       custom_grid and custom_d; side_stream
 //   sc_host_snapshot.h  the whole stored state: rng, upper, next_id, live_hint_from, progress, index_order and
 //                       write_pairs; side_stream (ensure_side_stream of sc_host_slab.h) and link.halo_ring_from
-// The other way round the tick reads probe.on and track.on (a logged tick is not fused) and launches probe_launch and
-// track_launch after pass B, clears pairs.valid where the state changes, and reads `link` as said there.
+// The other way round the tick reads probe.on, track.on and traj.on (a logged tick is not fused) and launches probe_launch,
+// track_launch and traj_launch after pass B, clears pairs.valid where the state changes, and reads `link` as said there.
 
 // In slab mode the stored count changes on the device every tick (halo records arrive without the
 // host knowing how many), so launches cover the capacity; surplus workgroups exit on their first load.

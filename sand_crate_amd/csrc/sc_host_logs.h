@@ -1,8 +1,9 @@
-// Host side of what a run records about itself: the probe, tracking and the force monitor.
+// Host side of what a run records about itself: the probe, tracking, trajectories and the force monitor.
 #pragma once
 #include "sc_host.h"
 #include "sc_probe.h"
 #include "sc_track.h"
+#include "sc_traj.h"
 
 extern "C" {
 
@@ -94,6 +95,77 @@ static int track_refuse(const sc_ctx* c, bool switching) {
   if (c->in_step) return fail(SC_ERR_STATE, switching ? "the track log cannot change inside a tick" : "tracking happens between ticks");
   if (switching && c->prebinned)
     return fail(SC_ERR_STATE, "the track log cannot change after sc_set_next_inputs promised the next tick");
+  return SC_OK;
+}
+
+// ---- trajectories (sc_traj.h) -------------------------------------------------------------------
+
+// Enqueues one frame of the state as it stands into the log's next place: the device decides which, or that the log is
+// full.  `on_demand`: sc_traj_capture, between ticks.
+static int traj_launch(sc_ctx* c, bool on_demand) {
+  TrajArgs a{};
+  a.tick = c->tick;
+  a.frames = c->traj.frames;
+  a.id0 = c->traj.id0;
+  a.rows = c->traj.rows;
+  a.on_demand = on_demand ? 1 : 0;
+  a.pressure_valid = c->normals_valid ? 1 : 0;
+  a.cap = (int)c->cap;
+  hipLaunchKernelGGL(k_traj_reserve, dim3(1), dim3(64), 0, c->stream, a, c->counters, c->traj.log);
+  hipLaunchKernelGGL(k_traj_clear, dim3(grid_for(a.rows)), dim3(kBlock), 0, c->stream, a, c->traj.log);
+  const int64_t bound = slot_bound(c);
+  if (bound > 0)
+    hipLaunchKernelGGL(k_traj_scatter, dim3(grid_for(bound)), dim3(kBlock), 0, c->stream, a, c->counters, c->traj.log, c->x,
+                       c->y, c->vx, c->vy, c->id[0], c->P);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+static int traj_refuse(const sc_ctx* c, bool switching) {
+  if (c->slab) return fail(SC_ERR_STATE, "trajectories are not available in slab mode");
+  if (c->in_step)
+    return fail(SC_ERR_STATE, switching ? "the trajectory log cannot change inside a tick" : "a frame is captured between ticks");
+  if (switching && c->prebinned)
+    return fail(SC_ERR_STATE, "the trajectory log cannot change after sc_set_next_inputs promised the next tick");
+  return SC_OK;
+}
+
+int sc_traj_enable_device(sc_ctx* c, double* dev_states, double* dev_pressure, int64_t* dev_ticks, int64_t* dev_counts,
+                          int64_t* dev_outside, int64_t* dev_words, int64_t frames, int64_t id0, int64_t rows, int64_t every,
+                          int32_t reset) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_states || !dev_ticks || !dev_counts || !dev_outside || !dev_words) return fail(SC_ERR_ARG, "null argument");
+  if ((uintptr_t)dev_states % 16) return fail(SC_ERR_ARG, "the states must be aligned to 16 bytes");
+  if (frames < 1) return fail(SC_ERR_ARG, "a log of %lld frames; at least 1", (long long)frames);
+  if (rows < 1 || id0 < 0 || id0 > (int64_t)std::numeric_limits<int>::max() - rows)
+    return fail(SC_ERR_ARG, "a window of %lld ids from %lld; at least one, within 0..2^31 - 2", (long long)rows, (long long)id0);
+  if (every < 1) return fail(SC_ERR_ARG, "every %lld; at least 1", (long long)every);
+  if (const int rc = traj_refuse(c, true)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (reset) HIPCHK(hipMemsetAsync(dev_words, 0, JW_COUNT * sizeof(int64_t), c->stream));  // (a failure leaves what was)
+  c->traj.log = TrajLog{dev_states, dev_pressure, (long long*)dev_ticks, (long long*)dev_counts, (long long*)dev_outside,
+                        (long long*)dev_words};
+  c->traj.frames = frames;
+  c->traj.id0 = id0;
+  c->traj.rows = rows;
+  c->traj.every = every;
+  c->traj.on = true;
+  return SC_OK;
+}
+
+int sc_traj_capture(sc_ctx* c) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (const int rc = traj_refuse(c, false)) return rc;
+  if (!c->traj.on) return fail(SC_ERR_STATE, "sc_traj_enable_device first");
+  HIPCHK(hipSetDevice(c->device));
+  return traj_launch(c, true);
+}
+
+int sc_traj_disable(sc_ctx* c) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (const int rc = traj_refuse(c, true)) return rc;
+  c->traj.on = false;
+  c->traj.log = TrajLog{};
   return SC_OK;
 }
 

@@ -673,6 +673,7 @@ class Engine:
 
     def synchronize(self) -> None:
         N.check(self._lib.sc_synchronize(self._ctx))
+        self._traj_retired = None  # (nothing is queued any more against the tensors of a recording that was stopped)
 
     def set_scan_patience(self, polls: int) -> None:
         """How often a workgroup of the bucket scan asks for a predecessor's total before the tick is abandoned
@@ -879,6 +880,45 @@ class Engine:
         data = np.frombuffer(bytes(frame), dtype=np.uint8)
         N.check(self._lib.sc_track_load(self._ctx, N._P(data.ctypes.data) if len(data) else None, len(data),
                                         1 if plain else 0))
+
+    # -- trajectories: full-precision frames in torch's memory, a row per id (sc_traj_*; the rule is
+    # tests/trajectory_spec.py, the owner of the tensors trajectory.py)
+    def traj_enable(self, states, pressure, ticks, counts, outside, words, *, id0: int, every: int = 1,
+                    reset: bool = True) -> None:
+        """From now on every tick whose number is a multiple of `every` writes one frame into the caller's CUDA tensors,
+        without synchronising (sc_traj_enable_device): `states` float64 (F, M, 4), `pressure` float64 (F, M) or None,
+        `ticks`, `counts`, `outside` int64 (F,) and `words` int64 (4,); row r of a frame is the particle with id
+        `id0` + r.  `reset` zeroes the words; without it the recording continues where they stand.  The engine keeps the
+        tensors alive until `traj_disable`.  ValueError for tensors that do not fit, before the library is touched."""
+        shape = tuple(getattr(states, "shape", ()))
+        if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"states must be a contiguous CUDA float64 tensor of shape (F, M, 4), F and M at least 1, on cuda:{self.device}")
+        frames, rows = int(shape[0]), int(shape[1])
+        _state_tensor(states, "states", "float64", (rows, 4), self.device, frames)
+        if pressure is not None:
+            _state_tensor(pressure, "pressure", "float64", (rows,), self.device, frames)
+        for t, name in ((ticks, "ticks"), (counts, "counts"), (outside, "outside")):
+            _state_tensor(t, name, "int64", (), self.device, frames)
+        _state_tensor(words, "words", "int64", (), self.device, 4)
+        id0, every = int(id0), int(every)
+        if id0 < 0 or id0 + rows > 2 ** 31 - 1:
+            raise ValueError(f"the window of ids [{id0}, {id0 + rows}) must lie within 0 .. 2^31 - 1")
+        if every < 1:
+            raise ValueError("every must be at least 1")
+        ptr = lambda t: None if t is None else N._P(t.data_ptr())  # noqa: E731
+        N.check(self._lib.sc_traj_enable_device(self._ctx, ptr(states), ptr(pressure), ptr(ticks), ptr(counts), ptr(outside),
+                                                ptr(words), frames, id0, rows, every, 1 if reset else 0))
+        self._traj_log = (states, pressure, ticks, counts, outside, words)
+
+    def traj_capture(self) -> None:
+        """One frame of the state as it stands, now, into the log (sc_traj_capture); enqueued only."""
+        N.check(self._lib.sc_traj_capture(self._ctx))
+
+    def traj_disable(self) -> None:
+        """Stops recording (sc_traj_disable).  Launches may still be queued against the tensors: the engine lets go of
+        them at the next `synchronize()`."""
+        N.check(self._lib.sc_traj_disable(self._ctx))
+        self._traj_retired, self._traj_log = getattr(self, "_traj_log", None), None
 
     # -- force monitor
     def enable_force_monitor(self, on: bool = True) -> None:

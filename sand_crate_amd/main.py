@@ -28,6 +28,10 @@ read every 4096 ticks and written as ``observables.npz`` next to ``config.yaml``
 into nine bytes per particle in a log in device memory -- no download and no synchronisation in the tick loop -- which is
 read when the host's bound of the particle count says the next frames may no longer fit, and streamed into ``track.sctk``
 (`track.TrackWriter`); ``python -m sand_crate_amd.replay`` turns that file into frames or videos at any view.
+``--trajectory [EVERY]`` records the run at full precision (`Crate.record_trajectory`): every EVERY-th tick the device writes
+positions and velocities as float64 into a log in device memory, one row per particle id -- no sort, no download and no
+synchronisation in the tick loop; the log holds a frame for the initial state and for every EVERY-th of the variant's ticks,
+is read once at the end of the variant and written as ``trajectory.npz`` (states, ticks, counts, outside, dropped, id0).
 ``--checkpoint-every K`` also writes resumable checkpoints
 (``checkpoint_<tick>.npz``: `Crate.begin_checkpoint` captures the state on the device and sends it to pinned host
 memory on a side stream while the following ticks run); ``--resume FILE`` continues such a run.
@@ -95,7 +99,7 @@ class HeadlessPlayback:
                  record_every: int = 10, device: int = 0, checkpoint_every: int = 0,
                  resume: Optional[Path] = None, frames: bool = False, video: bool = False,
                  video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
-                 observe: Optional[int] = None, track: int = 0) -> None:
+                 observe: Optional[int] = None, track: int = 0, trajectory: int = 0) -> None:
         self.config = config
         if recording_dir_path is None:
             stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -124,6 +128,8 @@ class HeadlessPlayback:
         self.track = max(int(track or 0), 0)  # a packed frame every this-many-th tick into track.sctk; 0: none
         self.track_frames = 0
         self.track_dropped = 0
+        self.trajectory = max(int(trajectory or 0), 0)  # a full-precision frame every this-many-th tick; 0: none
+        self.recorded: Optional[dict] = None  # what trajectory.npz holds, once the variant has run
         self.done = False
         self.seconds = 0.0
 
@@ -143,8 +149,12 @@ class HeadlessPlayback:
                                 arrows=self.arrows > 0)
             if getattr(self, "track", 0):
                 self._track_begin()
+            if getattr(self, "trajectory", 0):  # the initial state and every `trajectory`-th of the n ticks
+                self.crate.record_trajectory(int(n) // self.trajectory + 2, every=self.trajectory)
             self._run(int(n), avi, gif)
+            self._trajectory_end()
         finally:
+            self.crate.stop_trajectory()
             self._track_end()
             if avi is not None:
                 self.video_frames = avi.frames
@@ -231,6 +241,15 @@ class HeadlessPlayback:
             writer.close()
             self._track_writer = None
 
+    def _trajectory_end(self) -> None:
+        """--trajectory: the log is read once, when the variant has run."""
+        recording = getattr(self.crate, "_trajectory", None)
+        if recording is None:
+            return
+        got = recording.read()
+        self.recorded = {name: got[name].cpu().numpy() for name in ("states", "ticks", "counts", "outside")}
+        self.recorded.update(dropped=np.int64(got["dropped"]), id0=np.int64(recording.id0))
+
     def _collect_checkpoint(self) -> None:
         if self._checkpoint_tick is None:
             return
@@ -255,6 +274,9 @@ class HeadlessPlayback:
         if observables is not None:
             np.savez_compressed(out_dir / "observables.npz", fields=np.array(FIELDS), x_range=np.array([0.0, 1.0]),
                                 dt=np.float64(self.crate.dt), **observables)
+        recorded = getattr(self, "recorded", None)
+        if recorded is not None:
+            np.savez_compressed(out_dir / "trajectory.npz", **recorded)
         if self.render_frames:
             write_frames(out_dir, self.images, arrays["ticks"], gif=not self.gif)
 
@@ -280,7 +302,7 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
          ticks: Optional[int] = None, noise: str = "host", record_every: int = 10, checkpoint_every: int = 0,
          resume: Optional[Path] = None, frames: bool = False, video: bool = False,
          video_quality: int = 95, gif: bool = False, hud: bool = False, arrows: int = 0,
-         observe: Optional[int] = None, track: int = 0) -> list[dict]:
+         observe: Optional[int] = None, track: int = 0, trajectory: int = 0) -> list[dict]:
     config = load_config(config_file_path=config_file_path)
     summary = []
     for k, variant in enumerate(config_options(options, config)):
@@ -291,7 +313,8 @@ def main(config_file_path, play_recording: Optional[Path] = None, *, variants: O
                                     checkpoint_every=checkpoint_every, resume=resume if k == 0 else None, frames=frames,
                                     video=video, video_quality=video_quality, gif=gif, hud=hud, arrows=arrows,
                                     **({} if observe is None else {"observe": observe}),
-                                    **({"track": track} if track else {}))
+                                    **({"track": track} if track else {}),
+                                    **({"trajectory": trajectory} if trajectory else {}))
         playback.run_live_simulation(ticks)
         summary.append({"variant": k, "ticks": playback.crate.tick, "particles": playback.crate.particle_count,
                         "seconds": playback.seconds,
@@ -336,6 +359,9 @@ def argument_parser() -> argparse.ArgumentParser:
     ap.add_argument("--track", type=int, nargs="?", const=1, default=0, metavar="EVERY", help="record every EVERY-th tick "
                     "(default: every one) as a packed frame on the GPU, nine bytes per particle, streamed into track.sctk; "
                     "python -m sand_crate_amd.replay draws it at any view")
+    ap.add_argument("--trajectory", type=int, nargs="?", const=1, default=0, metavar="EVERY", help="record every EVERY-th "
+                    "tick (default: every one) at full precision on the GPU, float64 positions and velocities in one row "
+                    "per particle id, read once at the end and written as trajectory.npz")
     return ap
 
 
@@ -344,4 +370,4 @@ if __name__ == "__main__":
     main(a.config_file_path, a.play_recording, variants=a.variants, ticks=a.ticks, noise=a.noise,
          record_every=a.record_every, checkpoint_every=a.checkpoint_every, resume=a.resume, frames=a.frames,
          video=a.video, video_quality=a.video_quality, gif=a.gif, hud=a.hud, arrows=a.arrows, observe=a.observe,
-         track=a.track)
+         track=a.track, trajectory=a.trajectory)
