@@ -700,8 +700,8 @@ int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* m
  *     count copies dev_ptr into the workspace on the context's stream -- it must be ready then, as the points must --
  *     and the readers never read it again.  clouds = 0 or dev_ptr NULL clears a pending batch.  The grid the count
  *     leaves is batched, which the context knows on the host: sc_pairs_fill_device, sc_pairs_nearest_device,
- *     sc_pairs_sum_device and sc_pairs_sum_grad_device read it as such.  sc_pairs_label_device and sc_pairs_hist_device
- *     are NOT batched yet: on a batched grid they return SC_ERR_ARG and write nothing.
+ *     sc_pairs_sum_device and sc_pairs_sum_grad_device read it as such.  sc_pairs_label_device, sc_pairs_hist_device and
+ *     sc_pairs_rays_device are NOT batched yet: on a batched grid they return SC_ERR_ARG and write nothing.
  * sc_pairs_set_query_batch_device  with queries a second array, dev_query_ptr, also clouds + 1 entries ending at
  *     n_queries: query rows query_ptr[b] .. query_ptr[b + 1] see the points of cloud b only; a cloud may have points and
  *     no queries, or queries and no points (rows without partners).  Applies to the next query-form reader of the batched
@@ -983,6 +983,58 @@ int sc_pairs_hist_device(sc_ctx* ctx, const double* dev_queries /* NULL: the poi
                          const double* edges2 /* HOST, bins + 1 */, int32_t bins,
                          int32_t* dev_table /* rows x bins, may be NULL */, int64_t* dev_total /* bins, may be NULL */,
                          int64_t room_rows, int64_t* dev_counts /* [2]: rows, status */);
+
+/* Ray sensors over the points of that grid and a list of wall segments, in DEVICE memory of the caller: what a sensor
+ * sees along a line -- a range finder on a stirring body, the height of the free surface under a probe, the particle
+ * under the cursor.  tests/ray_spec.py is the rule, by brute force: ray r has the origin o = dev_origins[r] and the
+ * direction d = dev_directions[r], which nobody normalises -- the parameter t is in units of |d|, the distance for a unit
+ * direction.  Every point with finite coordinates carries a disc of radius disc_radius, rho2 = fl(rho rho).  With
+ * f = o - c: a = fl(fl(dx dx) + fl(dy dy)), b = fl(fl(fx dx) + fl(fy dy)), cc = fl(fl(fl(fx fx) + fl(fy fy)) - rho2);
+ * cc <= 0 (the origin inside or on the disc): t = +0; else b >= 0: no hit; else disc = fl(fl(b b) - fl(a cc)) < 0: no
+ * hit; else t = fl(cc / fl(-b + sqrt(disc))), a form without cancellation; a hit iff t <= max_t.  Wall s from A to B,
+ * e = B - A, g = A - o: den = fl(fl(dx ey) - fl(dy ex)), 0: no hit (parallel and collinear rays miss);
+ * t = fl(fl(fl(gx ey) - fl(gy ex)) / den), u = fl(fl(fl(gx dy) - fl(gy dx)) / den); a hit iff 0 <= t <= max_t and
+ * 0 <= u <= 1, from either face -- a sensor, not the physics' one-sided crossing test --, a t of -0 reported as +0.
+ * The result of a ray is the hit with the smallest key (t, kind, index), walls before discs: dev_hit[r] = j >= 0 for
+ * the disc of point j of the count, -2 - s for wall s, -1 for none, with dev_t[r] = +inf.  A ray whose origin or
+ * direction is not finite, or whose a is 0, is dead: t = NaN, hit = -1.  The result is a pure function of the points,
+ * the walls, the rays, disc_radius and max_t: the same on every call and for every capacity.
+ *
+ * sc_pairs_rays_device  sends n_rays rays through the grid of the last sc_pairs_count_device of this context, unbatched,
+ *     with any flags: it reads the workspace that count left and leaves it as it is -- fills, labels, tables, sums,
+ *     histograms and further rays may follow.  dev_origins and dev_directions are n_rays x 2 interleaved float64,
+ *     aligned to 16 bytes.  disc_radius must be at most HALF the count's radius (count at twice the disc radius: the
+ *     cell is then one disc diameter wide and a ray that advances a cell width per step meets, in the 3 x 3 cells round
+ *     the step's midpoint, every disc it can touch); 0 skips the discs: walls only.  max_t is finite and not negative.
+ *     `segments` is HOST memory, n_segments x 2 x 2 (A.x, A.y, B.x, B.y), read before the call returns, at most
+ *     SC_MAX_SEGMENTS; NULL with 0.  Writes dev_t (float64) and dev_hit (int64) for every ray, rows from n_rays on are
+ *     left as they were; `room_rows`, their room in rows, must be at least n_rays.  dev_counts[0] = n_rays,
+ *     dev_counts[1] = the status: 0 when all is well; -1 after a count that found a point outside the domain
+ *     fl(|c| / radius) < 2^31 (the count's radius), or with an origin outside it, or -- when discs are looked for -- a
+ *     live ray's end point fl(o + fl(max_t d)) outside it or not finite; -4 when a live ray would have to walk more
+ *     than 8192 cells: with dt = fl(radius / sqrt(a)) and t_end = min(max_t, the ray's nearest wall hit) it needs
+ *     fl(8192 dt) > t_end -- in a closed crate every ray ends at a wall, in an open scene shorten max_t.  With a status
+ *     below 0 only dev_counts[1] is written.
+ * It enqueues on the context's stream only, with the rules of sc_pairs_sum_device: nothing synchronises, nothing reaches
+ * the host, no counter, look-ahead promise, RNG position, pending error flag or particle array changes, and the launches
+ * are not bracketed by the timing events.
+ *     The algorithm: the readers' check pass over the origins, a pass over the rays for the end points and the range,
+ *     then the walls -- passed by value -- and the walk: step k covers t in [fl(k dt), fl((k + 1) dt)] and tests the
+ *     members of the nine cells round its midpoint by the rule above, keeping the smallest key, so the order in which
+ *     candidates are met cannot reach the output; the nearest wall caps the walk, which ends after the first step with
+ *     best t < fl((k + 1) dt) (csrc/sc_rays.h has the argument and its rounding margin).  A wave per ray: the lanes
+ *     take the (step, cell) pairs of seven steps at a time and the wave the minimum key; a thread per ray was measured
+ *     slower at every size (scripts/rays_time.py, profiles/rays_time.txt).  No atomics beyond the flag's.
+ *     SC_ERR_ARG for a null context or a null origins, directions, t, hit or counts pointer, a negative n_rays or room,
+ *     misaligned origins or directions, a max_t or disc_radius that is negative or not finite, a disc_radius above half
+ *     the count's radius, a null `segments` with n_segments > 0, and on a batched grid; SC_ERR_CAPACITY for more than
+ *     SC_MAX_SEGMENTS segments (or fewer than 0), more than 2^28 rays and too few rows; SC_ERR_STATE as for
+ *     sc_pairs_sum_device.  All checked before anything is launched: the arrays are then untouched. */
+int sc_pairs_rays_device(sc_ctx* ctx, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                         double disc_radius /* 0: walls only */, double max_t,
+                         const double* segments /* HOST, may be NULL */, int32_t n_segments,
+                         double* dev_t, int64_t* dev_hit, int64_t room_rows,
+                         int64_t* dev_counts /* [2]: rays, status */);
 
 #ifdef __cplusplus
 }

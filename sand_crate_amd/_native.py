@@ -65,6 +65,14 @@ HIST_MAX_BINS = 64
 HIST_BLOCK = 64
 HIST_SLOTS = (16, 32, 64)
 HIST_OK, HIST_DOMAIN = 0, -1
+# the ray sensors (csrc/sc_rays.h): the most steps -- cells -- a ray may walk (kRayMaxSteps), the lanes of the wave that
+# walks a ray (kRayBlock), the steps it takes at a time (kRayWaveSteps), the status values of counts[1] -- PAIRS_RANGE is
+# the new one: a ray that would walk more than RAY_MAX_STEPS cells -- and the values of `hit` that are no particle: none,
+# and wall s as RAY_WALL - s
+RAY_MAX_STEPS = 8192
+RAY_BLOCK, RAY_WAVE_STEPS = 64, 7
+PAIRS_RANGE = -4
+RAY_NONE, RAY_WALL = -1, -2
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -221,6 +229,7 @@ SIGNATURES = {
     "sc_pairs_sum_grad_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, _P, C.c_int32,
                                            _P, C.c_int64, _P]),
     "sc_pairs_hist_device": (C.c_int, [_P, _P, C.c_int64, _D, C.c_int32, _P, _P, C.c_int64, _P]),
+    "sc_pairs_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, _D, C.c_int32, _P, _P, C.c_int64, _P]),
 }
 
 

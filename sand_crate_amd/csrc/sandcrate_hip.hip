@@ -20,6 +20,7 @@
 #include "sc_fields.h"
 #include "sc_fields_grad.h"
 #include "sc_hist.h"
+#include "sc_rays.h"
 #include "sc_track.h"
 #include "sc_traj.h"
 #include "sc_rccl.h"

@@ -227,7 +227,7 @@ struct StateIo {
 // The batched form (sc_pairs_set_batch_device): `ptr`, the count's copy of the offsets, and `cloud`, every point's cloud;
 // `clouds` > 0 says that the grid is batched.  `next_ptr` / `next_clouds` wait for the next count, `next_qptr` for the
 // next query-form reader: the caller's device memory, read by that call's launches only.
-// `readerFlag`: the flag of the reader that runs (sc_nearest.h, sc_fields.h, sc_fields_grad.h) -- a query outside the
+// `readerFlag`: the flag of the reader that runs (sc_nearest.h, sc_fields.h, sc_fields_grad.h, sc_rays.h) -- a query outside the
 // domain, an array of the caller's with too few rows, bad query offsets.  A flag apart from the count's, which stays as
 // the count left it: a fill or a label after a reader still reads it.  One word for all of them: every reader zeroes it
 // before its check, on the one stream, so no call's verdict reaches the next.

@@ -1,5 +1,5 @@
 // Host side of the state in the caller's device memory: export and import, pair lists, clusters, nearest-k tables,
-// weighted neighbourhood sums with their position gradient, and distance histograms.
+// weighted neighbourhood sums with their position gradient, distance histograms, and ray sensors.
 #pragma once
 #include "sc_host.h"
 #include "sc_state.h"
@@ -10,6 +10,7 @@
 #include "sc_fields.h"
 #include "sc_fields_grad.h"
 #include "sc_hist.h"
+#include "sc_rays.h"
 
 extern "C" {
 
@@ -566,6 +567,49 @@ int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries
   if (dev_total)
     hipLaunchKernelGGL(k_hist_finish, dim3(1), dim3(kHistBlock), 0, c->stream, (int)bins, r.view.flag, c->hist.flag(),
                        c->hist.acc(), out.total);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+}  // extern "C"
+
+// ---- ray sensors (sc_rays.h) ----------------------------------------------------------------------
+
+extern "C" {
+
+int sc_pairs_rays_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, double disc_radius,
+                         double max_t, const double* segments, int32_t n_segments, double* dev_t, int64_t* dev_hit,
+                         int64_t room_rows, int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_counts)
+    return fail(SC_ERR_ARG, "null origins, directions, t, hit or counts pointer");
+  if (n_rays < 0) return fail(SC_ERR_ARG, "negative ray count");
+  if ((uintptr_t)dev_directions & 15) return fail(SC_ERR_ARG, "the directions must be aligned to 16 bytes");
+  if (!(max_t >= 0) || !std::isfinite(max_t)) return fail(SC_ERR_ARG, "max_t must be finite and not negative");
+  if (!(disc_radius >= 0) || !std::isfinite(disc_radius)) return fail(SC_ERR_ARG, "the disc radius must be finite and not negative");
+  if (n_segments < 0 || n_segments > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", (int)n_segments, kMaxSeg);
+  if (n_segments > 0 && !segments) return fail(SC_ERR_ARG, "null segment array");
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_rays_device", "send rays through", "t and hit hold", false, true}, dev_origins,
+                                  n_rays, room_rows, &r))
+    return rc;
+  if (!(disc_radius <= c->pairs.grid.radius / 2))
+    return fail(SC_ERR_ARG, "the disc radius %.17g is more than half the count's radius %.17g: count at twice the disc radius",
+                disc_radius, c->pairs.grid.radius);
+  RayWalls walls{};
+  walls.n = n_segments;
+  if (n_segments) std::memcpy(walls.s, segments, sizeof(double) * 4 * (size_t)n_segments);
+  const int discs = disc_radius > 0;
+  const XY* dirs = (const XY*)dev_directions;
+  const RayOut out{dev_t, (long long*)dev_hit, (long long*)dev_counts};
+  if (const int rc = reader_check(c, r, -1, -1, dev_counts)) return rc;
+  int* own = c->pairs.readerFlag.get();
+  if (discs)
+    hipLaunchKernelGGL(k_rays_check, dim3(grid_for(r.rows)), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, walls, max_t,
+                       r.queries, dirs, (long long)r.rows, own);
+  const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
+  hipLaunchKernelGGL(k_rays, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, discs, disc_radius * disc_radius,
+                     max_t, own, r.queries, dirs, (long long)r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -1,0 +1,232 @@
+// Ray sensors on the device (sc_pairs_rays_device): for every ray -- an origin and a direction -- the first thing it
+// meets among the discs of radius rho round the points of the last count and up to SC_MAX_SEGMENTS wall segments: the
+// ray's parameter t and what was hit.  A range finder, the height of the free surface under a probe, the particle under
+// the cursor.  The rule is specified in NumPy, by brute force, in tests/ray_spec.py; the result is a pure function of
+// the points, the walls, the rays, rho and max_t.  Included once by sandcrate_hip.hip, after sc_hist.h.
+//
+// The rule (ray_disc, ray_walls below: every operation rounded on its own, -ffp-contract=off).  Disc with centre c:
+// f = o - c, a = fl(fl(dx dx) + fl(dy dy)), b = fl(fl(fx dx) + fl(fy dy)), cc = fl(fl(fl(fx fx) + fl(fy fy)) - rho2);
+// cc <= 0: t = +0; else b >= 0: none; else disc = fl(fl(b b) - fl(a cc)) < 0: none; else t = fl(cc / fl(-b + sqrt(disc)));
+// a hit iff t <= max_t.  Wall A -> B, e = B - A, g = A - o: den = fl(fl(dx ey) - fl(dy ex)), 0: none;
+// t = fl(fl(fl(gx ey) - fl(gy ex)) / den), u = fl(fl(fl(gx dy) - fl(gy dx)) / den); a hit iff 0 <= t <= max_t and
+// 0 <= u <= 1, from either face, -0 reported as +0.  The result is the smallest key (t, kind, index), walls before
+// discs: hit = j for disc j, -2 - s for wall s, -1 and t = +inf for none; a ray with an origin or a direction that is
+// not finite, or with a = 0, is dead: t = NaN, hit = -1.  sqrt and / are correctly rounded here, as the host's are.
+//
+// Everything about the points is read from the workspace the last count left (sc_pairs.h), through PairsView, and
+// nothing of it is written: any other reader may follow.
+//   k_reader_check (sc_pairs.h) prepares counts[1] and raises the domain bit of the readers' flag for an origin outside
+//                  the domain: the origins are the queries;
+//   k_rays_check   a thread per ray: the domain bit for a live ray's end point fl(o + fl(max_t d)) that fails
+//                  pairs_outside's rule or is not finite, and kRayFlagRange for a live ray whose walk would take more
+//                  than kRayMaxSteps steps (below).  Not launched for walls alone;
+//   k_rays         a wave per ray: the walls, the walk, the result -- unless a flag is up: then counts[1] = -1 (the
+//                  domain) or -4 (the range) is all that is written.
+//
+// The walk.  s is the count's radius and the host requires rho <= s / 2; the cells are h = fl(s (1 + 2^-20)) wide.  With
+// dt = fl(s / sqrt(a)), step k covers t in [fl(k dt), fl((k + 1) dt)] -- consecutive steps share their border, so the
+// steps tile t >= 0 -- and looks at the 3 x 3 cells round the cell of its midpoint M = fl(o + fl(tm d)),
+// tm = fl((k + 0.5) dt).  A candidate is a member of a bucket of those nine whose stored cell is the cell looked for,
+// the own-cell test of every reader: it is tested by the rule, and the smallest key (t, j) is kept, so the order in
+// which candidates are met does not reach the output.  The walls are tested first; t_end = min(max_t, the nearest wall's
+// t) caps the walk: step k is walked iff fl(k dt) <= t_end.  The walk ends after the first step k with
+// best t < fl((k + 1) dt).  A disc that would win has t* <= best t; its own step k* (the one whose piece holds t*) is
+// then at most k, and -- the claim below -- the disc was a candidate of step k*.  The kernel takes kRayWaveSteps steps
+// at a time, lane L the cell L % 9 of step k0 + L / 9, takes the minimum key over the wave, and ends after the first
+// batch with best t < fl((k0 + kRayWaveSteps) dt): the same argument with the batch's last step for k.
+//
+// The claim: the disc hit at t* in step k has its centre c in the 3 x 3 block of M's cell, in computed cells.  With
+// u = 2^-53 and |f| the distance from the origin to c:
+//   * the point P = o + t* d (exact, at the COMPUTED t*) is at most sqrt(rho^2 + 18 u |f|^2) from c.  The computed a, b,
+//     cc are those of an exact problem whose coefficients are off by 2u a, 2u |f| |d| and 3u |f|^2; t* solves that
+//     problem up to the roundings of disc (3u b^2, seen through t / q <= t / |b|), of sqrt, the sum and the quotient
+//     (3u t), and t* |d| <= |f| for a hit on the near side: put into |P - c|^2 - rho^2 = a t^2 + 2 b t + cc the terms add
+//     up to at most 18 u |f|^2.  A walk has at most kRayMaxSteps = 2^13 steps, so |f| <= (2^13 + 1.5) s and, at
+//     rho = s / 2 where it is worst, |P - c| <= s / 2 + 2^-22.8 s;
+//   * |P - M'| <= s / 2 (1 + 2^-35) for the exact midpoint M' = o + tm d: dt |d| = s (1 + 3u), and fl(k dt), tm and
+//     fl((k + 1) dt) are each off by at most u 2^13 dt;
+//   * the computed M is off M' by at most u (|M| + |tm d|) <= 2^-22 s (1 + 2^-17) per axis inside the domain
+//     |c| / s < 2^31, which holds the origin and the end point (k_reader_check, k_rays_check) and so every M between.
+//     The last step walked has fl(k dt) <= t_end <= max_t, so its midpoint may lie up to half a cell BEYOND the end
+//     point: |M| / s < 2^31 + 1/2 then, and M / h still below 2^31 by some 2^11 cells, because h > s (sc_pairs.h: 2047
+//     cells short of the ends of int) -- the (int) conversion in pairs_cell is defined, and cx +- 1 does not overflow;
+//   * the two divisions by h are each off by at most 2^-22 cells there (sc_pairs.h).
+// So per axis the computed quotients of c and M differ by at most
+//   (1 + 2^-22.8 + 2^-22 + 2^-34) / (1 + 2^-20) + 2^-21 < 1 - 2^-20 (1 - 0.15 - 0.25 - 0.5) < 1,
+// and two numbers less than 1 apart have floors at most 1 apart.  The margin of 2^-20 is thus used up to nine tenths at
+// the far corner of the domain, at the last step, for a grazed disc of the largest radius; 2^14 steps would not fit:
+// the cap is the largest power of two the margin of sc_pairs.h carries.  An origin inside a disc (cc <= 0, t = 0) has c
+// within rho (1 + 2u) of o, which lies in step 0's piece: the same bound with room to spare.
+//
+// The cap.  A live ray needs fl(kRayMaxSteps dt) > t_end, else kRayFlagRange goes up and the call ends as status -4: a
+// max_t of 1e12 in an open scene is a status, not a kernel that walks for minutes.  (An a that overflowed gives dt = 0
+// and the same status.)  With the flag down every walk ends by step kRayMaxSteps: fl(k dt) is monotone in k.
+//
+// The form (profiles/rays_time.txt).  What every other reader does, a thread per row in workgroups of one wave, was
+// built too -- the same ray_scan, the eighteen `start` loads of a step's nine buckets issued together -- and MEASURED
+// slower at every size: a lane walks its steps one after the other, each a chain of dependent loads (6.8 us a step where
+// the cells are mostly empty), and the lanes of a wave wait for its longest ray.  Over 1,048,576 particles the wave per
+// ray took 25 us against 42 us for a fan of 256 rays and 0.79 ms against 2.52 ms for 262,144 rays looking down; over
+// every 256th of those particles, where a ray walks some sixty cells, 74 against 758 us and 1.04 against 1.79 ms.
+#pragma once
+#include "sc_pairs.h"
+
+namespace sc {
+
+constexpr int kRayMaxSteps = 8192;      // 2^13: see "the claim" (mirrored by sand_crate_amd/_native.py: RAY_MAX_STEPS)
+constexpr int kRayBlock = 64;           // a workgroup: the one wave of a ray
+constexpr int kRayWaveSteps = 7;        // steps per batch: 63 (step, cell) pairs, one lane idle
+constexpr int kRayFlagRange = 8;        // a bit of the readers' flag, beside kReaderFlag* (sc_pairs.h)
+constexpr long long kRayStatusRange = -4;
+constexpr int kRayNoDisc = INT_MAX;     // the index of "no disc yet": behind every j
+
+struct RayWalls {
+  double s[kMaxSeg][4];  // A.x, A.y, B.x, B.y: the caller's (S, 2, 2)
+  int n;
+};
+
+struct RayOut {
+  double* t;
+  long long* hit;
+  long long* counts;  // [2]: rays, status
+};
+
+__device__ __forceinline__ long long ray_status(int flag, int own) {
+  return flag || (own & kReaderFlagDomain) ? kPairsStatusDomain : kRayStatusRange;
+}
+
+// Is the ray alive; a = fl(fl(dx dx) + fl(dy dy)).
+__device__ __forceinline__ bool ray_live(XY o, XY d, double& a) {
+  a = d.x * d.x + d.y * d.y;
+  const double inf = __builtin_inf();
+  return fabs(o.x) < inf && fabs(o.y) < inf && fabs(d.x) < inf && fabs(d.y) < inf && a != 0;
+}
+
+// The nearest wall hit: (t, s), the lowest s among equals; (+inf, -1) for none.
+__device__ __forceinline__ void ray_walls(const RayWalls& w, XY o, XY d, double max_t, double& best, int& who) {
+  best = __builtin_inf();
+  who = -1;
+  for (int s = 0; s < w.n; ++s) {
+    const double ax = w.s[s][0], ay = w.s[s][1];
+    const double ex = w.s[s][2] - ax, ey = w.s[s][3] - ay;
+    const double gx = ax - o.x, gy = ay - o.y;
+    const double den = d.x * ey - d.y * ex;
+    const double t = (gx * ey - gy * ex) / den, u = (gx * d.y - gy * d.x) / den;
+    if (den != 0 && t >= 0 && t <= max_t && u >= 0 && u <= 1 && t < best) {
+      best = t == 0 ? 0.0 : t;  // (-0 is +0)
+      who = s;
+    }
+  }
+}
+
+// The disc round c: is it hit, and at which t.
+__device__ __forceinline__ bool ray_disc(XY o, XY d, double a, XY c, double rho2, double max_t, double& t) {
+  const double fx = o.x - c.x, fy = o.y - c.y;
+  const double b = fx * d.x + fy * d.y;
+  const double cc = (fx * fx + fy * fy) - rho2;
+  if (cc <= 0) {
+    t = 0.0;
+  } else {
+    if (!(b < 0)) return false;
+    const double disc = b * b - a * cc;
+    if (!(disc >= 0)) return false;
+    t = cc / (-b + sqrt(disc));
+  }
+  return t <= max_t;
+}
+
+// The candidates of one bucket, places lo .. hi - 1: those whose own cell is (cx, cy), by the rule, into the best key.
+__device__ __forceinline__ void ray_scan(const PairsView& v, XY o, XY d, double a, double rho2, double max_t, unsigned cx,
+                                         unsigned cy, int lo, int hi, double& best, int& who) {
+  for (int k = lo; k < hi; ++k) {
+    const uint2 cell = v.scell[k];
+    if (cell.x != cx || cell.y != cy) continue;
+    const int j = v.sidx[k];
+    double t;
+    if (!ray_disc(o, d, a, v.sxy[k], rho2, max_t, t)) continue;
+    if (t < best || (t == best && j < who)) {
+      best = t;
+      who = j;
+    }
+  }
+}
+
+// The result of a live ray from its nearest wall (tw, sw) and its nearest disc (td, jd): a wall wins a tie.
+__device__ __forceinline__ void ray_write(const RayOut& out, long long r, double tw, int sw, double td, int jd) {
+  const bool disc = td < tw;
+  out.t[r] = disc ? td : tw;
+  out.hit[r] = disc ? (long long)jd : sw >= 0 ? -2LL - sw : -1LL;
+}
+
+// After k_reader_check on the same stream, when discs are looked for: what only the rays can say.
+__global__ void __launch_bounds__(kBlock)
+    k_rays_check(double radius, RayWalls walls, double max_t, const XY* __restrict__ origins, const XY* __restrict__ dirs,
+                 long long n_rays, int* __restrict__ own_flag) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays) return;
+  const XY o = origins[r], d = dirs[r];
+  double a;
+  if (!ray_live(o, d, a)) return;
+  const double ex = fabs(o.x + max_t * d.x), ey = fabs(o.y + max_t * d.y);
+  if (!(ex / radius < kPairsDomain) || !(ey / radius < kPairsDomain)) atomicOr(own_flag, kReaderFlagDomain);  // (inf too)
+  double tw;
+  int sw;
+  ray_walls(walls, o, d, max_t, tw, sw);
+  const double dt = radius / sqrt(a);
+  if ((double)kRayMaxSteps * dt <= fmin(max_t, tw)) atomicOr(own_flag, kRayFlagRange);
+}
+
+// A wave per ray: workgroup r is ray r.  Every lane computes the ray and its walls (uniform: scalar work); lane L < 63
+// takes cell L % 9 of step k0 + L / 9 of the batch.  `discs` 0: walls alone.  v.g.radius and v.g.h are the count's.
+__global__ void __launch_bounds__(kRayBlock)
+    k_rays(PairsView v, RayWalls walls, int discs, double rho2, double max_t, const int* __restrict__ own_flag,
+           const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayOut out) {
+  static_assert(9 * kRayWaveSteps <= kRayBlock && kRayBlock == 64, "a lane per (step, cell) pair of a batch, one wave");
+  const long long r = blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  const bool up = *v.flag || *own_flag;
+  if (r == 0 && lane == 0) {
+    if (up) out.counts[1] = ray_status(*v.flag, *own_flag);
+    else out.counts[0] = n_rays;
+  }
+  if (up || r >= n_rays) return;
+  const XY o = origins[r], d = dirs[r];
+  double a;
+  if (!ray_live(o, d, a)) {
+    if (lane == 0) {
+      out.t[r] = __builtin_nan("");
+      out.hit[r] = -1;
+    }
+    return;
+  }
+  double tw, best = __builtin_inf();
+  int sw, who = kRayNoDisc;
+  ray_walls(walls, o, d, max_t, tw, sw);
+  if (discs) {
+    const double t_end = fmin(max_t, tw), dt = v.g.radius / sqrt(a);
+    const int step = lane / 9, c = lane % 9;
+    for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
+      const int k = k0 + step;
+      if (step < kRayWaveSteps && (double)k * dt <= t_end) {
+        const double tm = ((double)k + 0.5) * dt;
+        const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
+        const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
+        const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);
+        ray_scan(v, o, d, a, rho2, max_t, cx, cy, v.start[bk], v.start[bk + 1], best, who);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave, in every lane
+        const double t2 = __shfl_xor(best, off, 64);
+        const int j2 = __shfl_xor(who, off, 64);
+        if (t2 < best || (t2 == best && j2 < who)) {
+          best = t2;
+          who = j2;
+        }
+      }
+      if (best < (double)(k0 + kRayWaveSteps) * dt) break;
+    }
+  }
+  if (lane == 0) ray_write(out, r, tw, sw, best, who);
+}
+
+}  // namespace sc

@@ -506,6 +506,39 @@ class Engine:
                                                N._P(counts.data_ptr())))
         return counts
 
+    def pairs_rays(self, t, hit, *, origins, directions, disc_radius: float, max_t: float, segments=None, counts,
+                   room: int | None = None):
+        """Ray sensors over the points of the last `pairs_count` and a list of walls (sc_pairs_rays_device; the rule is
+        tests/ray_spec.py): `t`, float64 (R,), receives per ray the parameter of the first thing it meets -- in units of
+        the direction's length, +inf for nothing, NaN for a dead ray --, `hit`, int64 (R,), what that is: j >= 0 the disc
+        of radius `disc_radius` round point j of the count, -2 - s wall s, -1 nothing.  `origins` and `directions` are
+        float64 (q, 2) CUDA tensors with the same q; the directions are not normalised.  `disc_radius` may be at most
+        half the count's radius, 0 looks at the walls alone; `max_t` is a finite host float >= 0.  `segments` is a host
+        array (S, 2, 2), S at most 16, or None.  A wall wins a tie with a disc, the lower index a tie of two of a kind.
+        `counts`, int64 (2,), receives the ray count and the status: 0, -1 when a point, an origin or a ray's end point
+        ``origin + max_t * direction`` lies outside the domain, -4 when a ray would walk more than 8192 cells (then
+        nothing else is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.
+        Returns `counts`."""
+        disc_radius, max_t = float(disc_radius), float(max_t)  # (the host's numbers first: they need no device)
+        if not (0 <= disc_radius < float("inf")):
+            raise ValueError("disc_radius must be finite and not negative")
+        if not (0 <= max_t < float("inf")):
+            raise ValueError("max_t must be finite and not negative")
+        seg = np.zeros((0, 2, 2)) if segments is None else np.ascontiguousarray(segments, dtype=np.float64)
+        if seg.ndim != 3 or seg.shape[1:] != (2, 2) or len(seg) > N.MAX_SEGMENTS:
+            raise ValueError(f"segments must be (S, 2, 2) with S at most {N.MAX_SEGMENTS}")
+        rows = _state_tensor(t, "t", "float64", (), self.device)
+        _state_tensor(hit, "hit", "int64", (), self.device, rows)
+        q = _state_tensor(origins, "origins", "float64", (2,), self.device)
+        _state_tensor(directions, "directions", "float64", (2,), self.device, q)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the tensors'")
+        origins_at, directions_at, t_at, hit_at = _addresses(counts, origins, directions, t, hit)
+        N.check(self._lib.sc_pairs_rays_device(self._ctx, origins_at, directions_at, q, disc_radius, max_t,
+                                               N.dptr(seg) if len(seg) else None, len(seg), t_at, hit_at, room,
+                                               N._P(counts.data_ptr())))
+        return counts
+
     # -- frames
     @staticmethod
     def view(width: int, height: int, particle_radius: float, *, zoom: float = 1.0, center=None,

@@ -1,13 +1,14 @@
 """The neighbourhood calls of `Crate` -- `pair_tensors`, `cluster_tensors`, `cluster_sums`, `cluster_observables`,
-`neighbor_tensors`, `field_tensors`, `field_function` and `distance_histogram` -- as a mixin `Crate` inherits (crate.py is
-the reference's surface plus recording and rendering), and the protocol all of them follow, written once: `_Search`.
+`neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram` and `ray_tensors` -- as a mixin `Crate`
+inherits (crate.py is the reference's surface plus recording and rendering), and the protocol all of them follow,
+written once: `_Search`.
 
 Every call counts the pairs on the grid (`Engine.pairs_count`) and then runs one or more readers of that grid
-(`pairs_fill`, `pairs_label`, `pairs_cluster_sums`, `pairs_nearest`, `pairs_sum`, `pairs_sum_grad`, `pairs_hist`), all on
-the library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either it then synchronises,
-reads the counts, raises what the status says and cuts the tensors, or it returns the tensors as they are with `counts`
-last.  The C side of the same sharing is `reader_begin` / `reader_check` (csrc/sc_host_state.h).  torch is imported on
-first use."""
+(`pairs_fill`, `pairs_label`, `pairs_cluster_sums`, `pairs_nearest`, `pairs_sum`, `pairs_sum_grad`, `pairs_hist`,
+`pairs_rays`), all on the library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either
+it then synchronises, reads the counts, raises what the status says and cuts the tensors, or it returns the tensors as
+they are with `counts` last.  The C side of the same sharing is `reader_begin` / `reader_check`
+(csrc/sc_host_state.h).  torch is imported on first use."""
 from __future__ import annotations
 
 import numpy as np
@@ -29,8 +30,10 @@ _STATUS = {
     N.PAIRS_BATCH: "{who}: " + _BATCH_ORDER + "{of_queries}",
     N.PAIRS_DOMAIN: "{who}: a coordinate{of_either} lies outside the domain |c| / radius < 2^31 (radius {radius!r})",
     N.FIELDS_VALUES_SHORT: "{who}: {short}",
+    N.PAIRS_RANGE: "{who}: {far}",
 }
-_QUERY_CALLS = ("neighbor_tensors", "field_tensors", "field_function", "distance_histogram")
+_QUERY_CALLS = ("neighbor_tensors", "field_tensors", "field_function", "distance_histogram", "ray_tensors")
+_OF_EITHER = {"ray_tensors": " of a point, an origin or a ray's end point origin + max_t * direction"}
 
 
 def _check_batch(who: str, device: int, points, queries, batch, query_batch) -> None:
@@ -78,13 +81,14 @@ class _Search:
     offsets  int64 (bound + 1,): the count's scan, which only `pair_tensors` returns
     counts   int64 (2,): (n, E) of the count, then (rows, status) of each reader -- with `queries` a second pair, so that
              the count's n, the number of particles, stays readable; both pairs are one allocation and one host copy
-    short    the sentence of status -2, the caller's arrays having too few rows"""
+    short    the sentence of status -2, the caller's arrays having too few rows
+    far      the sentence of status -4, a ray that would walk beyond the cap"""
 
     def __init__(self, crate, who: str, radius=None, *, points=None, queries=None, batch=None, query_batch=None,
-                 sync: bool = True, short: str = ""):
+                 sync: bool = True, short: str = "", far: str = ""):
         import torch
         eng = crate._engine
-        self.crate, self.who, self.eng, self.sync, self.short = crate, who, eng, sync, short
+        self.crate, self.who, self.eng, self.sync, self.short, self.far = crate, who, eng, sync, short, far
         self.points, self.queries, self.batch = points, queries, batch
         self.dev = torch.device("cuda", eng.device)
         self.radius = float(crate.diameter if radius is None else radius)
@@ -114,8 +118,9 @@ class _Search:
         if status < 0:
             queries = self.who in _QUERY_CALLS
             raise ValueError(_STATUS.get(status, _STATUS[N.PAIRS_DOMAIN]).format(
-                who=self.who, radius=self.radius, short=self.short, of_either=" of a point or a query" if queries else "",
-                of_queries=" (of queries for query_batch)" if queries else ""))
+                who=self.who, radius=self.radius, short=self.short,
+                of_either=_OF_EITHER.get(self.who, " of a point or a query") if queries else "",
+                of_queries=" (of queries for query_batch)" if queries else "", far=self.far))
         if self.points is None:
             self.crate._count, self.crate._count_known = got[0], True
         return n, status
@@ -138,8 +143,9 @@ class _Search:
 
 
 class _Neighbourhood:
-    """`Crate`'s neighbourhood calls.  Uses of the crate: `_engine`, `diameter`, `state_tensors`, and `_count` /
-    `_count_known`, which a synchronising search of the state brings up to date."""
+    """`Crate`'s neighbourhood calls.  Uses of the crate: `_engine`, `diameter`, `state_tensors`, `segments` and
+    `rigid_bodies` (the walls of `ray_tensors`), and `_count` / `_count_known`, which a synchronising search of the state
+    brings up to date."""
 
     def pair_tensors(self, radius: float | None = None, *, points=None, half: bool = False, squared_distances: bool = False,
                      max_pairs: int | None = None, batch=None):
@@ -434,3 +440,63 @@ class _Neighbourhood:
         call.count()
         call.eng.pairs_hist(table, total, edges=e, queries=queries, counts=call.counts)
         return call.end(rows=(table,), whole=(total,))
+
+    def ray_tensors(self, origins, directions, max_t: float, *, disc_radius: float | None = None, walls=True,
+                    particles: bool = True, points=None, sync: bool = True):
+        """What a sensor sees along a line: for every ray the first thing it meets among the particles -- discs of radius
+        `disc_radius` (default: the crate's particle radius, ``diameter / 2``) -- and the walls, as torch CUDA tensors on
+        the crate's device, walked on the GPU through the pair search's grid (sc_pairs_count_device at the radius
+        ``2 * disc_radius``, then sc_pairs_rays_device): ``(t, hit)`` -- float64 (R,) and int64 (R,).  `origins` and
+        `directions` are float64 (R, 2) CUDA tensors; a direction is not normalised, ``t`` is in units of its length (with
+        unit directions, `sand_crate_amd.pairs.ray_fan`, the distance), and only hits with ``0 <= t <= max_t`` count;
+        `max_t` is a finite host float.  ``hit[r]`` is j >= 0 for particle j -- the row of `state_tensors()` at the same
+        point of the stream, or of `points`, a float64 (n, 2) CUDA tensor that is searched instead of the state --,
+        ``-2 - s`` for wall s and -1 for nothing, with ``t = +inf`` (`sand_crate_amd.pairs.hit_particles`, `hit_walls`
+        and `ray_points` read the result).  An origin inside or on a disc hits it at t = 0; a wall counts from either
+        face, a ray parallel to it misses; of equal t a wall comes before a particle and a lower index before a higher
+        one.  A ray with a number that is not finite, or with a zero direction, has t = NaN and hit = -1; a particle
+        with a coordinate that is not finite is never hit.  Every operation is rounded on its own and the smallest
+        (t, kind, index) is taken: a pure function of the state and the rays, the same on every call
+        (tests/ray_spec.py is the rule).
+
+        `walls=True` are the crate's current `segments`, an (S, 2, 2) host array the caller's own (at most 16), `False`
+        none; `particles=False` looks at the walls alone (the origins must still lie in the domain).  In an open scene
+        keep `max_t` short: a ray may walk at most 8192 cells of one particle diameter before it meets a wall.
+
+        `sync=True` synchronises once at the end and reads 32 bytes; ValueError when a coordinate of a particle, of an
+        origin or of an end point ``origin + max_t * direction`` has |c| / (2 disc_radius) >= 2^31, and when a ray would
+        walk further than the cap.  `sync=False` synchronises nothing and returns ``(t, hit, counts)``, the int64
+        `counts` tensor (rays, status) last: status -1 is the domain error, -4 the cap (nothing else was written).  The
+        tensors are written on the library's stream, and the library's stream does not wait for torch's: read them after
+        `synchronize()`, and have `origins`, `directions` and `points` ready before the call -- or run the crate on
+        torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        import torch
+        rho = float(self.diameter / 2 if disc_radius is None else disc_radius)
+        if not 0 < rho < float("inf"):
+            raise ValueError("disc_radius must be finite and positive")
+        max_t = float(max_t)
+        if not 0 <= max_t < float("inf"):
+            raise ValueError("max_t must be finite and not negative")
+        if walls is True:
+            segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
+        elif walls is False or walls is None:
+            segments = np.zeros((0, 2, 2))
+        else:
+            segments = np.ascontiguousarray(walls, dtype=np.float64)
+        if segments.ndim != 3 or segments.shape[1:] != (2, 2) or len(segments) > N.MAX_SEGMENTS:
+            raise ValueError(f"walls must be True, False or an (S, 2, 2) array with S at most {N.MAX_SEGMENTS}")
+        for tensor, name in ((origins, "origins"), (directions, "directions")):
+            if not getattr(tensor, "is_cuda", False) or tensor.dtype != torch.float64 or tensor.dim() != 2 or \
+                    tensor.shape[1] != 2 or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous CUDA float64 tensor of shape (R, 2)")
+        if origins.shape[0] != directions.shape[0]:
+            raise ValueError("origins and directions must have the same number of rows")
+        far = (f"max_t {max_t!r} lets a ray walk more than the cap of {N.RAY_MAX_STEPS} cells of width {2 * rho!r} before "
+               "it meets a wall: shorten max_t, or close the scene with walls")
+        call = _Search(self, "ray_tensors", 2 * rho, points=points, queries=origins, sync=sync, far=far)
+        t = torch.empty(call.rows, dtype=torch.float64, device=call.dev)
+        hit = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
+        call.count()
+        call.eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho if particles else 0.0, max_t=max_t,
+                            segments=segments, counts=call.counts)
+        return call.end(rows=(t, hit), held=(origins, directions))

@@ -1,7 +1,7 @@
 """Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
 `Crate.cluster_tensors` (labels, sizes), for the nearest-k tables of `Crate.neighbor_tensors` (neighbors), for the
-weighted sums of `Crate.field_tensors` (sums, wsum) and for the distance histograms of `Crate.distance_histogram`
-(edges, total)."""
+weighted sums of `Crate.field_tensors` (sums, wsum), for the distance histograms of `Crate.distance_histogram`
+(edges, total) and for the ray sensors of `Crate.ray_tensors` (origins, directions, t, hit)."""
 from __future__ import annotations
 
 
@@ -150,3 +150,43 @@ def grid_queries(x0, x1, y0, y1, nx, ny, device=None):
     x = x0 + (torch.arange(nx, dtype=torch.float64, device=device) + 0.5) * ((x1 - x0) / nx if nx else 0.0)
     y = y0 + (torch.arange(ny, dtype=torch.float64, device=device) + 0.5) * ((y1 - y0) / ny if ny else 0.0)
     return torch.stack([x.repeat(ny), y.repeat_interleave(nx)], dim=1)
+
+
+def ray_fan(origin, count, start_angle, stop_angle, device=None):
+    """`count` rays from one point for `Crate.ray_tensors`: ``(origins, directions)``, float64 (count, 2) each -- every
+    origin is `origin`, direction k is ``(cos a_k, sin a_k)`` with ``a_k = start_angle + k * (stop_angle - start_angle) /
+    (count - 1)``, both ends included (one ray looks along `start_angle`), in radians, counter-clockwise from +x.  The
+    angles, cosines and sines are NumPy's float64; the directions are unit up to rounding, so t is the distance."""
+    import numpy as np
+    import torch
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must not be negative")
+    start_angle, stop_angle = float(start_angle), float(stop_angle)
+    step = (stop_angle - start_angle) / (count - 1) if count > 1 else 0.0
+    angles = start_angle + np.arange(count, dtype=np.float64) * step
+    directions = torch.from_numpy(np.stack([np.cos(angles), np.sin(angles)], axis=1))
+    at = np.array([float(origin[0]), float(origin[1])], dtype=np.float64)
+    origins = torch.from_numpy(np.tile(at, (count, 1)))
+    return (origins, directions) if device is None else (origins.to(device), directions.to(device))
+
+
+def ray_points(origins, directions, t):
+    """Where the rays of `Crate.ray_tensors` ended: float64 (R, 2), ``origins + t[:, None] * directions`` -- product
+    and sum rounded on their own --, NaN in both columns where nothing was hit (t = +inf) and for a dead ray (t = NaN)."""
+    import torch
+    seen = torch.isfinite(t).unsqueeze(1)
+    ends = torch.add(origins, torch.mul(t.unsqueeze(1), directions))
+    return torch.where(seen, ends, torch.full_like(ends, float("nan")))
+
+
+def hit_particles(hit):
+    """The particle every ray of `Crate.ray_tensors` hit: int64 (R,), the row of `state_tensors()`, -1 for a wall or nothing."""
+    import torch
+    return torch.where(hit >= 0, hit, torch.full_like(hit, -1))
+
+
+def hit_walls(hit):
+    """The wall segment every ray of `Crate.ray_tensors` hit: int64 (R,), the row of `segments`, -1 for a particle or nothing."""
+    import torch
+    return torch.where(hit <= -2, -2 - hit, torch.full_like(hit, -1))
