@@ -8,14 +8,15 @@ from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
 import arrow_cases as K
 import arrow_spec as A
 import gif_spec as G
+import gpu_support as U
 import jpeg_spec as J
 import render_spec as R
 import text_spec as T
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,30 +27,12 @@ WALLS = dict(segment_width=20)  # thick walls: the frame's edge is white ten pix
 
 
 @pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def spread_world(sc, n):
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * n)))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
-    wc.particle_sources = []
-    return wc
-
-
-@pytest.fixture(scope="module")
 def crate(sc):
     """400 particles all over the wave_machine world after one tick (so they have pressures), discs of a few pixels at
     the frame sizes used here."""
     n = 400
     rs = np.random.RandomState(77)
-    crate = sc.Crate(spread_world(sc, n), noise="counter", noise_seed=1, capacity=n + 1024)
+    crate = sc.Crate(U.spread_world(sc, n), noise="counter", noise_seed=1, capacity=n + 1024)
     crate.particles = rs.rand(n, 2) * 0.96 + 0.02
     crate.particle_velocities = (rs.rand(n, 2) - 0.5) * 0.1
     crate.physics_tick()
@@ -82,21 +65,6 @@ def first_frames(crate, state):
     return {name: crate.render(c.width, c.height, **c.view, **WALLS) for name, c in CASES.items() if name in ("axes", "layers")}
 
 
-def same(got: bytes, want: bytes):
-    if got != want:
-        n = min(len(got), len(want))
-        first = next((k for k in range(n) if got[k] != want[k]), n)
-        raise AssertionError(f"{len(got)} bytes vs {len(want)}, first difference at byte {first}")
-
-
-def same_frame(got, want):
-    assert got.shape == want.shape and got.dtype == want.dtype
-    if not np.array_equal(got, want):
-        bad = np.argwhere((got != want).any(axis=-1)) if got.ndim == 3 else np.argwhere(got != want)
-        raise AssertionError(f"{len(bad)} pixels differ, the first at row {bad[0][0]}, column {bad[0][1]}: "
-                             f"{got[tuple(bad[0])]} vs {want[tuple(bad[0])]}")
-
-
 def green(frame):
     return (frame[..., 0] == 0) & (frame[..., 1] == 255) & (frame[..., 2] == 0)
 
@@ -121,7 +89,7 @@ def banded(got, base, ends, width, height, zoom, center):
 def test_frames_before_any_arrows(first_frames, state):
     for name, frame in first_frames.items():
         c = CASES[name]
-        same_frame(frame, base_of(state, c.width, c.height, c.zoom, c.center))
+        U.same_frame(frame, base_of(state, c.width, c.height, c.zoom, c.center))
 
 
 def test_the_layers_scene_puts_discs_and_a_wall_under_the_arrows(state):
@@ -145,11 +113,11 @@ def test_every_case(crate, state, first_frames, name):
     want = A.draw(base, c.ends, c.zoom, c.center)
     if c.hud is not None:
         want = T.draw(want, c.hud, T.MARGIN, T.MARGIN, T.default_scale(c.width))
-    same_frame(got, want)
+    U.same_frame(got, want)
     assert green(got).any()
     data = crate.render_gif(c.width, c.height, **c.view, **WALLS, arrows=c.pairs, hud=hud)
-    same(data, G.image_data(A.indices(want)))
-    same_frame(crate.render(c.width, c.height, **c.view, **WALLS), base)  # arrows=None after an arrow frame: none
+    U.same_stream(data, G.image_data(A.indices(want)))
+    U.same_frame(crate.render(c.width, c.height, **c.view, **WALLS), base)  # arrows=None after an arrow frame: none
 
 
 def test_engine_list_is_start_and_end(crate, state):
@@ -163,17 +131,17 @@ def test_engine_list_is_start_and_end(crate, state):
         got = crate.engine.render(crate.engine.view(c.width, c.height, crate.particle_radius, **WALLS), crate.segments)
     finally:
         crate.engine.set_arrows(N.ARROWS_OFF)
-    same_frame(got, A.draw(base_of(state, c.width, c.height), ends))
+    U.same_frame(got, A.draw(base_of(state, c.width, c.height), ends))
 
 
 def test_debug_arrows_true(sc):
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     for _ in range(5):
         crate.physics_tick()
     assert crate.debug_arrows == []
     w, h = 200, 150
     base = crate.render(w, h)
-    same_frame(crate.render(w, h, arrows=True), base)                  # an empty list
+    U.same_frame(crate.render(w, h, arrows=True), base)                  # an empty list
     rs = np.random.RandomState(9)
     pairs = [(rs.rand(2), (rs.rand(2) - 0.5) * 0.4) for _ in range(25)]
     pairs.append((np.array([np.nan, 0.5]), np.array([0.1, 0.1])))      # playback.py:97 skips these
@@ -187,15 +155,15 @@ def test_debug_arrows_true(sc):
             d = direction / np.power(np.sqrt(dx * dx + dy * dy) + 0.001, 0.3)
         ends.append([start, start + d])
     want = A.draw(base, np.array(ends))
-    same_frame(got, want)
+    U.same_frame(got, want)
     assert green(got).sum() > 200
-    same_frame(crate.render(w, h, arrows=np.array([[s, d] for s, d in pairs])), want)  # the same list as an array
-    same_frame(crate.render(w, h, arrows=[[list(s), list(d)] for s, d in pairs]), want)
+    U.same_frame(crate.render(w, h, arrows=np.array([[s, d] for s, d in pairs])), want)  # the same list as an array
+    U.same_frame(crate.render(w, h, arrows=[[list(s), list(d)] for s, d in pairs]), want)
     crate.physics_tick()                                               # crate.py:94: the tick empties the list
     assert crate.debug_arrows == []
     after = crate.render(w, h, arrows=True)
     assert not green(after).any()
-    same_frame(after, crate.render(w, h))
+    U.same_frame(after, crate.render(w, h))
 
 
 # ---- velocity mode
@@ -205,7 +173,7 @@ def uploaded(sc):
     """The velocity cases' state set through the `Crate` setters, no tick: ids are 0 .. n - 1."""
     v = next(iter(VELOCITY.values()))
     n = len(v.xy)
-    wc = spread_world(sc, n)
+    wc = U.spread_world(sc, n)
     crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 64)
     crate.particles = v.xy
     crate.particle_velocities = v.vxy
@@ -218,12 +186,12 @@ def test_velocity_of_an_uploaded_state(uploaded, name):
     base = uploaded.render(v.width, v.height, **v.view)
     got = uploaded.render(v.width, v.height, **v.view, arrows="velocity", arrow_every=v.every, arrow_scale=v.scale)
     banded(got, base, v.ends, v.width, v.height, v.zoom, v.center)
-    same_frame(uploaded.render(v.width, v.height, **v.view), base)
+    U.same_frame(uploaded.render(v.width, v.height, **v.view), base)
 
 
 def test_velocity_after_ticks(sc):
     """512 particles at most, 20 ticks with the scene's source running: slots are cell-sorted, ids are not slot numbers."""
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
+    wc = copy.deepcopy(U.scene(sc, "wave_machine"))
     wc.coefficients.update(max_particles=512)
     crate = sc.Crate(wc, noise="counter", noise_seed=3)
     rs = np.random.RandomState(31)
@@ -241,7 +209,7 @@ def test_velocity_after_ticks(sc):
         ends = A.velocity_ends(xy, vxy, ids, crate.dt if scale is None else scale, every)
         assert len(ends) == (ids % every == 0).sum()
         banded(got, base, ends, w, h, view["zoom"], view["center"])
-    same_frame(crate.render(w, h, **view), base)
+    U.same_frame(crate.render(w, h, **view), base)
 
 
 # ---- where the frame lives, and the encoders
@@ -258,22 +226,22 @@ def test_unaligned_device_frame(crate, state):
     base = base_of(state, w, h, c.zoom, c.center)
     assert crate.render(w, h, out=out, arrows=c.pairs, **c.view, **WALLS) is out
     crate.synchronize()
-    same_frame(out.cpu().numpy(), A.draw(base, c.ends, c.zoom, c.center))
+    U.same_frame(out.cpu().numpy(), A.draw(base, c.ends, c.zoom, c.center))
     got = buf.cpu().numpy()
     assert got[0] == 0 and not got[1 + 3 * w * h:].any()  # nothing outside the frame
     assert crate.render(w, h, out=out, **c.view, **WALLS) is out  # and without: the plain frame again
     crate.synchronize()
-    same_frame(out.cpu().numpy(), base)
+    U.same_frame(out.cpu().numpy(), base)
 
 
 def test_render_jpeg_with_arrows(crate, state):
     c = CASES["random_zoomed"]
     w, h = c.width, c.height
     frame = crate.render(w, h, **c.view, **WALLS, arrows=c.pairs)
-    same_frame(frame, A.draw(base_of(state, w, h, c.zoom, c.center), c.ends, c.zoom, c.center))
+    U.same_frame(frame, A.draw(base_of(state, w, h, c.zoom, c.center), c.ends, c.zoom, c.center))
     for q in (95, 50):
-        same(crate.render_jpeg(w, h, quality=q, **c.view, **WALLS, arrows=c.pairs), J.encode(frame, q))
-    same(crate.render_jpeg(w, h, **c.view, **WALLS), J.encode(base_of(state, w, h, c.zoom, c.center), 95))
+        U.same_stream(crate.render_jpeg(w, h, quality=q, **c.view, **WALLS, arrows=c.pairs), J.encode(frame, q))
+    U.same_stream(crate.render_jpeg(w, h, **c.view, **WALLS), J.encode(base_of(state, w, h, c.zoom, c.center), 95))
 
 
 def test_render_gif_with_arrows(crate, state, tmp_path):
@@ -285,14 +253,14 @@ def test_render_gif_with_arrows(crate, state, tmp_path):
     want = A.indices(frame)
     assert (want == 1).any() and (want == 255).any() and want[(want > 1) & (want < 255)].min() >= 2
     data = crate.render_gif(w, h, **WALLS, arrows=c.pairs)
-    same(data, G.image_data(want))
+    U.same_stream(data, G.image_data(want))
     frames, _, _, _ = G.decode(G.header(w, h) + G.frame(w, h, data) + b"\x3B")
     assert np.array_equal(frames[0] == 1, A.mask(c.ends, w, h) & (want == 1))
     # velocity arrows reach the encoder too: index 1 appears, and only there does the frame differ in kind
     vel = G.decode(G.header(w, h) + G.frame(w, h, crate.render_gif(w, h, **WALLS, arrows="velocity", arrow_scale=2.0)) + b"\x3B")[0][0]
     assert (vel == 1).any() and np.array_equal(vel[vel != 1], A.indices(base)[vel != 1])
     # without arrows: today's bytes, max(c, 1)
-    same(crate.render_gif(w, h, **WALLS), G.image_data(G.indices(base)))
+    U.same_stream(crate.render_gif(w, h, **WALLS), G.image_data(G.indices(base)))
     path = tmp_path / "arrows.gif"
     with GifWriter(path, w, h, arrows=True) as gif:
         gif.write(data)
@@ -307,14 +275,14 @@ def test_render_gif_with_arrows(crate, state, tmp_path):
     except ImportError:
         return
     with Image.open(path) as im:
-        same_frame(np.array(im.convert("RGB")), lossy)
+        U.same_frame(np.array(im.convert("RGB")), lossy)
 
 
 # ---- the simulation is left alone
 
 def test_drawing_is_read_only(sc):
     def trajectory(draw):
-        crate = sc.Crate(scene(sc, "wave_machine"))
+        crate = sc.Crate(U.scene(sc, "wave_machine"))
         for k in range(10):
             crate.physics_tick()
             if draw:
@@ -357,35 +325,35 @@ def test_argument_errors(crate, state):
         return eng.render(eng.view(c.width, c.height, crate.particle_radius, **WALLS), crate.segments)
 
     crate.render(c.width, c.height, **WALLS)  # (the crate knows of no arrows)
-    same_frame(frame(), base)
+    U.same_frame(frame(), base)
     bads = (dict(mode=3), dict(mode=-1), dict(n=-1), dict(n=N.MAX_ARROWS + 1), dict(arrows=None), dict(every=0),
             dict(every=-5), dict(scale=float("nan")), dict(scale=float("inf")), dict(mode=N.ARROWS_VELOCITY, every=0),
             dict(mode=N.ARROWS_VELOCITY, scale=float("-inf")), dict(ctx=None))
     for bad in bads:
         assert call(**bad) == N.ERR_ARG, bad
         assert lib.sc_last_error()
-    same_frame(frame(), base)                                  # none of them set anything
+    U.same_frame(frame(), base)                                  # none of them set anything
     try:
         assert call() == 0
-        same_frame(frame(), with_arrows)
+        U.same_frame(frame(), with_arrows)
         for bad in bads:
             assert call(**bad) == N.ERR_ARG, bad
-        same_frame(frame(), with_arrows)                       # a refused call leaves the arrows that were there
+        U.same_frame(frame(), with_arrows)                       # a refused call leaves the arrows that were there
         with pytest.raises(N.NativeError) as err:
             eng.set_arrows(N.ARROWS_VELOCITY, None, 1.0, 0)
         assert err.value.code == N.ERR_ARG
-        same_frame(frame(), with_arrows)
+        U.same_frame(frame(), with_arrows)
         assert call(arrows=None, n=0) == 0                     # an empty list is no arrows; the list may then be null
-        same_frame(frame(), base)
+        U.same_frame(frame(), base)
         assert call() == 0 and call(mode=N.ARROWS_OFF, arrows=None, n=0) == 0
-        same_frame(frame(), base)
+        U.same_frame(frame(), base)
     finally:
         eng.set_arrows(N.ARROWS_OFF)
 
 
 def test_no_arrows_inside_a_tick(sc):
     from sand_crate_amd import _native as N
-    crate = sc.Crate(scene(sc, "wave_machine"), noise="host-sync")
+    crate = sc.Crate(U.scene(sc, "wave_machine"), noise="host-sync")
     crate.physics_tick()
     eng = crate.engine
     crate._send_tick_inputs()
@@ -416,7 +384,7 @@ def test_a_new_context_has_no_arrows(sc, crate):
 
 def test_arrows_survive_a_grown_engine(sc):
     n = 50
-    crate = sc.Crate(spread_world(sc, n), noise="counter", noise_seed=1, capacity=n)
+    crate = sc.Crate(U.spread_world(sc, n), noise="counter", noise_seed=1, capacity=n)
     rs = np.random.RandomState(2)
     crate.particles = rs.rand(n, 2) * 0.9 + 0.05
     pairs = CASES["axes"].pairs
@@ -434,19 +402,9 @@ def test_arrows_survive_a_grown_engine(sc):
 
 # ---- the driver
 
-def small_screen_config(tmp_path, width=160, height=120) -> Path:
-    with open(ROOT / "config" / "wave_machine.yaml") as f:
-        cfg = yaml.safe_load(f)
-    cfg["playback"].update(screen_x=width, screen_y=height)
-    path = tmp_path / "small_screen.yaml"
-    with open(path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    return path
-
-
 def test_headless_driver_with_arrows(tmp_path):
     from sand_crate_amd.main import main
-    cfg = small_screen_config(tmp_path)
+    cfg = U.small_screen_config(tmp_path)
     first = {}
     for arrows in (0, 4):
         out = tmp_path / f"arrows{arrows}"

@@ -4,38 +4,23 @@ the rule of tests/batch_spec.py -- the existing rules cloud by cloud -- bit for 
 the cases of tests/batch_cases.py.  And, unbatched, the readers in a row after one whose own flag went up: they share that
 flag, and no call's verdict may reach the next."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import batch_cases as BK
 import batch_spec as BS
+import gpu_support as U
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
-SENTINEL_F = -1.5
 ALL_CASES = BK.SELF_CASES + BK.QUERY_CASES
 BATCH_ORDER = "batch offsets must start at 0, not descend and end at the number of points"
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    return sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config, noise="none", capacity=256)
-
-
 def tensor(a, tail=None, requires_grad=False):
+    """Not U.tensor: this one keeps the array's own dtype, for the batch offsets are int64."""
     import torch
     if a is None:
         return None
@@ -45,37 +30,8 @@ def tensor(a, tail=None, requires_grad=False):
     return t.requires_grad_() if requires_grad else t
 
 
-def full(shape, value=SENTINEL):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), value,
-                      dtype=torch.int64 if isinstance(value, int) else torch.float64, device="cuda")
-
-
-def untouched(*tensors):
-    return all(bool((t == (SENTINEL_F if t.dtype.is_floating_point else SENTINEL)).all()) for t in tensors)
-
-
-def same(got, want):
-    """torch.equal, floats as their bits."""
-    import torch
-    want = torch.from_numpy(np.ascontiguousarray(want)).cuda()
-    got = got.detach()
-    if got.dtype != want.dtype or got.shape != want.shape:
-        return False
-    if got.dtype == torch.float64:
-        got, want = got.contiguous().view(torch.int64), want.view(torch.int64)
-    return torch.equal(got, want)
-
-
 def same_all(got, want):
-    return len(got) == len(want) and all(same(g, w) for g, w in zip(got, want))
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
+    return len(got) == len(want) and all(U.same_bits_on_device(g, w) for g, w in zip(got, want))
 
 
 def forms(name):
@@ -188,8 +144,9 @@ def test_self_form_gradients_are_the_per_cloud_rule(crate, name, width, power):
     """5 channels make [G | V] ten wide: two launches of the position kernel, added up as the rule adds them."""
     case = BK.cases()[name]
     got, G, gw = gradients(crate, name, width, power, False, ("values", "points"))
-    assert same(got["values"], BS.values_grad(case.points, case.radius, case.ptr, G, power))
-    assert same(got["points"], BS.self_points_grad(case.points, case.radius, case.ptr, values_of(name, width), power, G, gw))
+    assert U.same_bits_on_device(got["values"], BS.values_grad(case.points, case.radius, case.ptr, G, power))
+    assert U.same_bits_on_device(got["points"], BS.self_points_grad(case.points, case.radius, case.ptr, values_of(name, width),
+                                                                    power, G, gw))
 
 
 @pytest.mark.parametrize("width,power", [(3, 3), (5, 2)])
@@ -198,9 +155,10 @@ def test_query_form_gradients_are_the_per_cloud_rule(crate, width, power):
     case = BK.cases()[name]
     got, G, gw = gradients(crate, name, width, power, True, ("values", "points", "queries"))
     args = (case.points, case.radius, case.ptr, values_of(name, width), power, case.queries, case.query_ptr)
-    assert same(got["values"], BS.values_grad(case.points, case.radius, case.ptr, G, power, True, case.queries, case.query_ptr))
-    assert same(got["queries"], BS.query_queries_grad(*args, G=G, gw=gw))
-    assert same(got["points"], BS.query_points_grad(*args, G=G, gw=gw))
+    assert U.same_bits_on_device(got["values"], BS.values_grad(case.points, case.radius, case.ptr, G, power, True, case.queries,
+                                                               case.query_ptr))
+    assert U.same_bits_on_device(got["queries"], BS.query_queries_grad(*args, G=G, gw=gw))
+    assert U.same_bits_on_device(got["points"], BS.query_points_grad(*args, G=G, gw=gw))
 
 
 # ---- 3. one cloud, the setter's life, the forms that do not synchronise
@@ -286,22 +244,22 @@ def test_label_and_histogram_refuse_a_batched_grid(crate):
     eng = crate.engine
     kw = inputs("triplets")
     n = len(BK.cases()["triplets"].points)
-    offsets, counts = full(n + 1), full(2)
+    offsets, counts = U.full(n + 1, "cuda"), U.full(2, "cuda")
     eng.pairs_count(kw["points"], radius=BK.RADIUS, offsets=offsets, counts=counts, batch=kw["batch"])
-    labels, sizes, roots, label_counts = full(n), full(n), full(n), full(2)
-    assert code_of(eng.pairs_label, labels, sizes, roots, counts=label_counts) == N.ERR_ARG
-    table, total, hist_counts = full((n, 4)).to(torch.int32), full(4), full(2)
-    assert code_of(eng.pairs_hist, table, total, edges=[0.0, 0.01, 0.02, 0.03, 0.04], counts=hist_counts) == N.ERR_ARG
-    assert code_of(eng.pairs_hist, table, total, edges=[0.0, 0.01, 0.02, 0.03, 0.04], queries=kw["points"],
-                   counts=hist_counts) == N.ERR_ARG
+    labels, sizes, roots, label_counts = U.full(n, "cuda"), U.full(n, "cuda"), U.full(n, "cuda"), U.full(2, "cuda")
+    assert U.code_of(eng.pairs_label, labels, sizes, roots, counts=label_counts) == N.ERR_ARG
+    table, total, hist_counts = U.full((n, 4), "cuda").to(torch.int32), U.full(4, "cuda"), U.full(2, "cuda")
+    assert U.code_of(eng.pairs_hist, table, total, edges=[0.0, 0.01, 0.02, 0.03, 0.04], counts=hist_counts) == N.ERR_ARG
+    assert U.code_of(eng.pairs_hist, table, total, edges=[0.0, 0.01, 0.02, 0.03, 0.04], queries=kw["points"],
+                     counts=hist_counts) == N.ERR_ARG
     eng.synchronize()
-    assert untouched(labels, sizes, roots, label_counts, table, total, hist_counts)
+    assert U.untouched(labels, sizes, roots, label_counts, table, total, hist_counts)
     assert counts.tolist() == [n, int(pairs_spec_of("triplets", False)[0][-1])]     # (the count itself went through)
     # the grid is still there for the readers that are batched
-    partners = full(int(counts[1]))
+    partners = U.full(int(counts[1]), "cuda")
     eng.pairs_fill(partners)
     eng.synchronize()
-    assert same(partners, pairs_spec_of("triplets", False)[1])
+    assert U.same_bits_on_device(partners, pairs_spec_of("triplets", False)[1])
 
 
 # ---- 5. offsets out of order
@@ -327,27 +285,28 @@ def test_offsets_out_of_order_write_nothing_and_raise(crate, which, key):
     eng = crate.engine
     values = tensor(values_of("queries", 3))
     rows = q if query_form else n
-    offsets, counts = full(n + 1), full(2)
+    offsets, counts = U.full(n + 1, "cuda"), U.full(2, "cuda")
     eng.pairs_count(kw["points"], radius=BK.RADIUS, offsets=offsets, counts=counts, half=True, batch=kw["batch"])
-    partners, d2 = full(64), full(64, SENTINEL_F)
+    partners, d2 = U.full(64, "cuda"), U.full(64, "cuda", U.SENTINEL_F)
     eng.pairs_fill(partners, d2)
     reader = dict(queries=kw.get("queries"), query_batch=kw.get("query_batch"))
-    neighbors, nd2, ncount, nearest_counts = full((rows, 4)), full((rows, 4), SENTINEL_F), full(rows), full(2)
+    neighbors, nd2 = U.full((rows, 4), "cuda"), U.full((rows, 4), "cuda", U.SENTINEL_F)
+    ncount, nearest_counts = U.full(rows, "cuda"), U.full(2, "cuda")
     if query_form:                                                                  # (pairs_nearest has no such keyword)
         eng.pairs_set_query_batch(kw["query_batch"])
     eng.pairs_nearest(neighbors, nd2, ncount, k=4, counts=nearest_counts, queries=reader["queries"])
-    sums, wsum, sum_counts = full((rows, 3), SENTINEL_F), full(rows, SENTINEL_F), full(2)
+    sums, wsum, sum_counts = U.full((rows, 3), "cuda", U.SENTINEL_F), U.full(rows, "cuda", U.SENTINEL_F), U.full(2, "cuda")
     eng.pairs_sum(values, sums, wsum, counts=sum_counts, **reader)
-    grad, grad_counts = full((rows, 2), SENTINEL_F), full(2)
+    grad, grad_counts = U.full((rows, 2), "cuda", U.SENTINEL_F), U.full(2, "cuda")
     row_a = tensor(np.ones((rows, 3)))
     eng.pairs_sum_grad(grad, row_a, values, counts=grad_counts, **reader)
     eng.synchronize()
     if query_form:                                                                  # (the count and the fill were in order)
-        assert counts.tolist()[0] == n and counts.tolist()[1] >= 0 and not untouched(offsets)
+        assert counts.tolist()[0] == n and counts.tolist()[1] >= 0 and not U.untouched(offsets)
     else:
-        assert counts.tolist() == [n, N.PAIRS_BATCH] and untouched(offsets, partners, d2)
+        assert counts.tolist() == [n, N.PAIRS_BATCH] and U.untouched(offsets, partners, d2)
     assert int(nearest_counts[1]) == int(sum_counts[1]) == int(grad_counts[1]) == N.PAIRS_BATCH == -3
-    assert untouched(neighbors, nd2, ncount, sums, wsum, grad)
+    assert U.untouched(neighbors, nd2, ncount, sums, wsum, grad)
     calls = [lambda: crate.neighbor_tensors(4, BK.RADIUS, **kw),
              lambda: crate.field_tensors(values, BK.RADIUS, **kw),
              lambda: crate.field_function(values, BK.RADIUS, **kw),
@@ -370,7 +329,7 @@ def test_the_setters_argument_errors(sc, crate):
     eng = crate.engine
     kw = inputs("queries", True)
     n, q = kw["points"].shape[0], kw["queries"].shape[0]
-    offsets, counts = full(max(n, eng.capacity) + 1), full(2)
+    offsets, counts = U.full(max(n, eng.capacity) + 1, "cuda"), U.full(2, "cuda")
     lib, ctx = eng._lib, eng._ctx
     assert lib.sc_pairs_set_batch_device(ctx, N._P(kw["batch"].data_ptr()), -1) == N.ERR_ARG
     assert lib.sc_pairs_set_batch_device(None, N._P(kw["batch"].data_ptr()), 2) == N.ERR_ARG
@@ -384,20 +343,21 @@ def test_the_setters_argument_errors(sc, crate):
     assert state_count() == 0
     eng.pairs_count(None, radius=BK.RADIUS, offsets=offsets, counts=counts)
     # query offsets on an unbatched grid
-    assert code_of(eng.pairs_set_query_batch, kw["query_batch"]) == N.ERR_ARG
+    assert U.code_of(eng.pairs_set_query_batch, kw["query_batch"]) == N.ERR_ARG
     eng.pairs_count(kw["points"], radius=BK.RADIUS, offsets=offsets, counts=counts)
-    assert code_of(eng.pairs_set_query_batch, kw["query_batch"]) == N.ERR_ARG
+    assert U.code_of(eng.pairs_set_query_batch, kw["query_batch"]) == N.ERR_ARG
     # a query-form reader of a batched grid without them -- each of the three -- and with them; they are consumed
     eng.pairs_count(kw["points"], radius=BK.RADIUS, offsets=offsets, counts=counts, batch=kw["batch"])
-    neighbors, wsum, grad, reader_counts = full((q, 2)), full(q, SENTINEL_F), full((q, 2), SENTINEL_F), full(2)
-    assert code_of(eng.pairs_nearest, neighbors, k=2, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
-    assert code_of(eng.pairs_sum, None, None, wsum, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
-    assert code_of(eng.pairs_sum_grad, grad, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
+    neighbors, wsum = U.full((q, 2), "cuda"), U.full(q, "cuda", U.SENTINEL_F)
+    grad, reader_counts = U.full((q, 2), "cuda", U.SENTINEL_F), U.full(2, "cuda")
+    assert U.code_of(eng.pairs_nearest, neighbors, k=2, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
+    assert U.code_of(eng.pairs_sum, None, None, wsum, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
+    assert U.code_of(eng.pairs_sum_grad, grad, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
     eng.pairs_set_query_batch(kw["query_batch"])
     eng.pairs_nearest(neighbors, k=2, queries=kw["queries"], counts=reader_counts)
-    assert code_of(eng.pairs_nearest, neighbors, k=2, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
+    assert U.code_of(eng.pairs_nearest, neighbors, k=2, queries=kw["queries"], counts=reader_counts) == N.ERR_ARG
     eng.synchronize()
-    assert same(neighbors, nearest_spec_of("queries", 2, True)[0]) and untouched(wsum, grad)
+    assert U.same_bits_on_device(neighbors, nearest_spec_of("queries", 2, True)[0]) and U.untouched(wsum, grad)
     # the wrappers' own checks, before anything is enqueued
     good, points, queries = kw["batch"], kw["points"], kw["queries"]
     wrong = [dict(points=points, batch=good.to(torch.int32)), dict(points=points, batch=good.cpu()),
@@ -444,11 +404,12 @@ def test_a_raised_reader_flag_does_not_reach_the_next_reader(crate):
     eng = crate.engine
     p, q, far = tensor(points), tensor(queries), tensor(outside)
     v, a, s, ps = tensor(values), tensor(row_a), tensor(row_s), tensor(part_s)
-    offsets, counts = full(eng.capacity + 1), full(2)
-    status = [full(2) for _ in range(5)]
-    first, neighbors, d2, partners = full((3, k)), full((3, k)), full((3, k), SENTINEL_F), full(3)
-    sums, wsum, grad = full((3, 3), SENTINEL_F), full(3, SENTINEL_F), full((3, 2), SENTINEL_F)
-    table, total = torch.full((3, 5), SENTINEL, dtype=torch.int32, device="cuda"), full(5)
+    offsets, counts = U.full(eng.capacity + 1, "cuda"), U.full(2, "cuda")
+    status = [U.full(2, "cuda") for _ in range(5)]
+    first, neighbors = U.full((3, k), "cuda"), U.full((3, k), "cuda")
+    d2, partners = U.full((3, k), "cuda", U.SENTINEL_F), U.full(3, "cuda")
+    sums, wsum, grad = U.full((3, 3), "cuda", U.SENTINEL_F), U.full(3, "cuda", U.SENTINEL_F), U.full((3, 2), "cuda", U.SENTINEL_F)
+    table, total = torch.full((3, 5), U.SENTINEL, dtype=torch.int32, device="cuda"), U.full(5, "cuda")
     eng.pairs_count(p, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_nearest(first, k=k, queries=far, counts=status[0])
     eng.pairs_sum(v, sums, wsum, power=power, queries=q, counts=status[1])
@@ -457,10 +418,11 @@ def test_a_raised_reader_flag_does_not_reach_the_next_reader(crate):
     eng.pairs_nearest(neighbors, d2, partners, k=k, queries=q, counts=status[4])
     eng.synchronize()
     assert counts.cpu().tolist()[0] == 70 and int(counts[1]) > 0
-    assert status[0].cpu().tolist() == [SENTINEL, -1] and untouched(first)
+    assert status[0].cpu().tolist() == [U.SENTINEL, -1] and U.untouched(first)
     want_nearest = nearest_spec.nearest(points, radius, k, queries)
     assert [t.cpu().tolist() for t in status[1:]] == [[3, 0]] * 4 and int(want_nearest[2].max()) <= k
     assert same_all((sums, wsum), field_spec.field(points, radius, values, power, True, queries))
-    assert same(grad, field_grad_spec.position_grad(queries, points, radius, power, row_a, values, row_s, part_s))
+    assert U.same_bits_on_device(grad, field_grad_spec.position_grad(queries, points, radius, power, row_a, values, row_s,
+                                                                     part_s))
     assert same_all((table, total), hist_spec.histogram(points, edges, queries))
     assert same_all((neighbors, d2, partners), want_nearest) and int(want_nearest[2].sum()) > 0

@@ -5,7 +5,6 @@ the state after ticks, in a twin of eight times the capacity and after a load wi
 repeated, after a half and a full count and after another reader, a fill after the reduction, a room below the cluster
 count, the statuses, the error codes and the path that does not synchronise."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,60 +12,22 @@ import pytest
 import cluster_cases as CK
 import cluster_sums_cases as SK
 import cluster_sums_spec as SS
+import gpu_support as U
 import pairs_cases as K
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
 MARK = -1.25                        # what the float tensors hold before a call
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine reduces the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(a, width=2):
-    import torch
-    t = torch.from_numpy(np.array(a, dtype=np.float64).reshape(-1, width)).cuda()   # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
-    return t
-
-
-def full(shape, device, value=SENTINEL, dtype=None):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), value, dtype=dtype or torch.int64, device=device)
-
-
 def marked(shape, device):
-    import torch
-    return full(shape, device, MARK, torch.float64)
+    return U.full(shape, device, MARK)
 
 
 def host(t):
     return t if isinstance(t, np.ndarray) else t.cpu().numpy()
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,16 +57,16 @@ def reduce(eng, points, radius, values, *, half=True, extrema=True, room=None, r
     dev = torch.device("cuda", eng.device)
     n, width = len(points), values.shape[1]
     room = n if room is None else room
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    labels = full(n, dev)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    labels = U.full(n, dev)
     tables = [marked((room + 4, width), dev) for _ in range(3 if extrema else 1)]
-    t, v = tensor(points), tensor(values, width)
+    t, v = U.tensor(points), U.tensor(values, width)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts, half=half)
     eng.pairs_label(labels, counts=counts)
     for k in range(repeat):
         if between is not None and k:
             between()
-        out = full(2, dev)
+        out = U.full(2, dev)
         assert eng.pairs_cluster_sums(v, *tables, counts=out, room_clusters=room) is out
     eng.synchronize()
     return (*tables, out)
@@ -117,25 +78,25 @@ def reduce(eng, points, radius, values, *, half=True, extrema=True, room=None, r
 def test_ladder_equals_the_spec(crate, width, extrema):
     case = SK.cases()["ladder"]
     pts, values = case[0], case[1][:, 3:4] if width == 1 else case[1]               # (one channel: the one that shows the order)
-    got = crate.cluster_sums(tensor(values, width), SK.RADIUS, points=tensor(pts), extrema=extrema)
+    got = crate.cluster_sums(U.tensor(values, width), SK.RADIUS, points=U.tensor(pts), extrema=extrema)
     assert len(got) == (6 if extrema else 4) and all(t.is_cuda for t in got)
     assert_label(got[:3], case)
     want = SS.cluster_sums(case[2], values, clusters=len(case[3])) if width == 1 else spec("ladder", 8)
     assert_tables(got[3:], want[:3 if extrema else 1])
-    flat = crate.cluster_sums(tensor(values, width)[:, 0].contiguous(), SK.RADIUS, points=tensor(pts))   # (n,): one channel
+    flat = crate.cluster_sums(U.tensor(values, width)[:, 0].contiguous(), SK.RADIUS, points=U.tensor(pts))   # (n,): one channel
     assert flat[3].shape == (len(case[3]), 1) and SS.same(host(flat[3]), want[0][:, :1])
 
 
 def test_chain4_reaches_the_fourth_level(crate):
     case = SK.cases()["chain4"]
-    got = crate.cluster_sums(tensor(case[1]), SK.RADIUS, points=tensor(case[0]), extrema=True)
+    got = crate.cluster_sums(U.tensor(case[1]), SK.RADIUS, points=U.tensor(case[0]), extrema=True)
     assert_label(got[:3], case)
     assert_tables(got[3:], spec("chain4", 2))
 
 
 def test_isolated_with_dead_rows_never_reads_them(crate):
     case = SK.cases()["isolated_dead"]
-    got = crate.cluster_sums(tensor(case[1], 3), SK.RADIUS, points=tensor(case[0]), extrema=True)
+    got = crate.cluster_sums(U.tensor(case[1], 3), SK.RADIUS, points=U.tensor(case[0]), extrema=True)
     assert_label(got[:3], case)
     assert_tables(got[3:], spec("isolated_dead", 3))
     assert not np.isnan(host(got[3])).any() and np.isnan(case[1][case[2] < 0]).all()
@@ -143,7 +104,8 @@ def test_isolated_with_dead_rows_never_reads_them(crate):
 
 def test_special_values(crate):
     case = SK.cases()["special"]
-    sums, mins, maxs = (host(t) for t in crate.cluster_sums(tensor(case[1]), SK.RADIUS, points=tensor(case[0]), extrema=True)[3:])
+    got = crate.cluster_sums(U.tensor(case[1]), SK.RADIUS, points=U.tensor(case[0]), extrema=True)
+    sums, mins, maxs = (host(t) for t in got[3:])
     assert_tables((sums, mins, maxs), spec("special", 2))
     assert sums[0, 0] == 0.0 and not np.signbit(sums[0, 0]) and np.signbit(mins[0, 0])    # -0.0 only: +0.0 by the rule
     assert np.isnan([sums[1, 0], mins[1, 0], maxs[1, 0]]).all()
@@ -154,7 +116,7 @@ def test_special_values(crate):
 def test_wide_with_the_devices_own_labels(crate):
     points, radius = CK.cases()["wide"]
     values = SK.table(96, len(points), 3)
-    got = crate.cluster_sums(tensor(values, 3), radius, points=tensor(points), extrema=True)
+    got = crate.cluster_sums(U.tensor(values, 3), radius, points=U.tensor(points), extrema=True)
     labels, sizes = host(got[0]), host(got[1])
     assert 100 < len(sizes) < len(points) // 4 and sizes.max() > 1000                # big and small ones: two levels at least
     assert np.array_equal(np.bincount(labels[labels >= 0]), sizes)
@@ -171,7 +133,7 @@ def state_of(crate):
 def test_observables_after_ticks_in_a_twin_and_after_a_load_with_permuted_ids(sc):
     import torch
     from sand_crate_amd import pairs
-    first = sc.Crate(world(sc), noise="host", noise_seed=3)
+    first = sc.Crate(U.scene(sc), noise="host", noise_seed=3)
     for _ in range(200):
         first.physics_tick()
     xy, vv, p, _ = state_of(first)
@@ -185,7 +147,7 @@ def test_observables_after_ticks_in_a_twin_and_after_a_load_with_permuted_ids(sc
     centers = pairs.cluster_centers(table)
     assert centers.shape == (len(roots), 2) and bool((centers[:, 0] >= table[:, 7]).all()) and bool((centers[:, 0] <= table[:, 8]).all())
     assert pairs.cluster_mean_velocities(table).shape == (len(roots), 2)
-    twin = sc.Crate(world(sc), noise="host", noise_seed=3, capacity=8 * first.engine.capacity)
+    twin = sc.Crate(U.scene(sc), noise="host", noise_seed=3, capacity=8 * first.engine.capacity)
     for _ in range(200):
         twin.physics_tick()
     assert all(torch.equal(a, b) for a, b in zip(state_of(twin), state_of(first)))
@@ -207,7 +169,7 @@ def test_observables_after_ticks_in_a_twin_and_after_a_load_with_permuted_ids(sc
     # a load with permuted ids: the rows are those of that crate's export
     ids = torch.from_numpy(np.random.RandomState(7).permutation(n) * 3 + 5).cuda()
     torch.cuda.synchronize()
-    other = sc.Crate(world(sc), noise="none", capacity=n + 100)
+    other = sc.Crate(U.scene(sc), noise="none", capacity=n + 100)
     other.load_state_tensors(xy, vv, ids)
     order = np.argsort(host(ids))
     labels, roots, table = other.cluster_observables(1.5 * other.diameter)
@@ -217,7 +179,7 @@ def test_observables_after_ticks_in_a_twin_and_after_a_load_with_permuted_ids(sc
 
 
 def test_state_of_an_empty_crate(sc):
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     labels, roots, table = crate.cluster_observables()                              # before the first tick: n = 0
     assert labels.shape == roots.shape == (0,) and table.shape == (0, 14)
 
@@ -233,7 +195,7 @@ def test_same_bytes_repeated_after_half_and_full_and_after_another_reader(crate)
     want, total = spec("ladder", 8), len(case[3])
 
     def another_reader():                                                           # a table and a sum in between
-        crate.engine.pairs_nearest(full((len(pts), 4), dev), k=4, counts=full(2, dev))
+        crate.engine.pairs_nearest(U.full((len(pts), 4), dev), k=4, counts=U.full(2, dev))
 
     results = [reduce(eng, pts, SK.RADIUS, values, half=True), reduce(eng, pts, SK.RADIUS, values, half=False),
                reduce(eng, pts, SK.RADIUS, values, half=True, repeat=3, between=another_reader)]
@@ -250,12 +212,12 @@ def test_a_fill_after_the_reduction_gives_the_list_it_gave_before(crate):
     dev = torch.device("cuda", eng.device)
     n = len(points)
     want = S.pairs(points, radius, False)
-    offsets, counts, other, third = full(n + 1, dev), full(2, dev), full(2, dev), full(2, dev)
-    labels, again = full(n, dev), full(n, dev)
-    partners = full(len(want[1]), dev)
-    values = tensor(SK.table(97, n, 2))
+    offsets, counts, other, third = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev), U.full(2, dev)
+    labels, again = U.full(n, dev), U.full(n, dev)
+    partners = U.full(len(want[1]), dev)
+    values = U.tensor(SK.table(97, n, 2))
     sums = marked((n, 2), dev)
-    t = tensor(points)
+    t = U.tensor(points)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts, half=False)
     eng.pairs_label(labels, counts=other)
     eng.pairs_cluster_sums(values, sums, counts=third)
@@ -284,7 +246,7 @@ def test_room_below_the_cluster_count(crate, room):
 def test_max_clusters_does_not_synchronise_and_equals_the_default(crate, monkeypatch):
     import torch
     case = SK.cases()["ladder"]
-    t, v = tensor(case[0]), tensor(case[1], 8)
+    t, v = U.tensor(case[0]), U.tensor(case[1], 8)
     default = crate.cluster_sums(v, SK.RADIUS, points=t, extrema=True)
     n, total = len(case[0]), len(case[3])
 
@@ -318,16 +280,16 @@ def test_too_few_value_rows_and_the_domain(crate):
     case = SK.cases()["special"]
     pts, values = case[0], case[1]
     n = len(pts)
-    t, v = tensor(pts), tensor(values)
+    t, v = U.tensor(pts), U.tensor(values)
     with pytest.raises(ValueError, match="fewer"):
         crate.cluster_sums(v[:n - 1].contiguous(), SK.RADIUS, points=t)
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    labels, sums, mins = full(n, dev), marked((n, 2), dev), marked((n, 2), dev)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    labels, sums, mins = U.full(n, dev), marked((n, 2), dev), marked((n, 2), dev)
     eng.pairs_count(t, radius=SK.RADIUS, offsets=offsets, counts=counts)
     eng.pairs_label(labels, counts=counts)
     eng.pairs_cluster_sums(v[:n - 1].contiguous(), sums, mins, counts=out)
     eng.synchronize()
-    assert out.cpu().tolist() == [SENTINEL, -2] and bool((sums == MARK).all()) and bool((mins == MARK).all())
+    assert out.cpu().tolist() == [U.SENTINEL, -2] and bool((sums == MARK).all()) and bool((mins == MARK).all())
     eng.pairs_cluster_sums(v, sums, mins, counts=out)                               # the call's own flag: gone with the call
     eng.synchronize()
     assert out.cpu().tolist() == [n, 4] and SS.same(host(sums[:4]), spec("special", 2)[0])
@@ -336,48 +298,48 @@ def test_too_few_value_rows_and_the_domain(crate):
     assert int(short[-1][1]) == -2
     # a coordinate outside the domain: -1, nothing else
     points, radius = K.outside_domain()
-    t, v = tensor(points), tensor(SK.table(98, len(points), 2))
+    t, v = U.tensor(points), U.tensor(SK.table(98, len(points), 2))
     with pytest.raises(ValueError, match="domain"):
         crate.cluster_sums(v, radius, points=t)
-    offsets, out = full(len(points) + 1, dev), full(2, dev)
-    labels, sums = full(len(points), dev), marked((len(points), 2), dev)
+    offsets, out = U.full(len(points) + 1, dev), U.full(2, dev)
+    labels, sums = U.full(len(points), dev), marked((len(points), 2), dev)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_label(labels, counts=counts)
     eng.pairs_cluster_sums(v, sums, counts=out)
     eng.synchronize()
-    assert out.cpu().tolist() == [SENTINEL, -1] and bool((sums == MARK).all())
+    assert out.cpu().tolist() == [U.SENTINEL, -1] and bool((sums == MARK).all())
 
 
 def test_state_and_argument_errors(sc):
     import torch
     from sand_crate_amd import _native as N
     from sand_crate_amd import pairs
-    crate = sc.Crate(world(sc), noise="none", capacity=512)
+    crate = sc.Crate(U.scene(sc), noise="none", capacity=512)
     eng = crate.engine
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
     points, radius = K.cases()["n_65"]
     n = len(points)
-    t, v = tensor(points), tensor(SK.table(99, n, 2))
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    labels, sums, mins, maxs = full(n, dev), marked((n, 2), dev), marked((n, 2), dev), marked((n, 2), dev)
+    t, v = U.tensor(points), U.tensor(SK.table(99, n, 2))
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    labels, sums, mins, maxs = U.full(n, dev), marked((n, 2), dev), marked((n, 2), dev), marked((n, 2), dev)
     torch.cuda.synchronize()
     args = (v, sums, mins, maxs)
 
     def untouched():
         eng.synchronize()
-        return bool((counts == SENTINEL).all()) and all(bool((a == MARK).all()) for a in (sums, mins, maxs))
+        return bool((counts == U.SENTINEL).all()) and all(bool((a == MARK).all()) for a in (sums, mins, maxs))
 
-    assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # no count, no label
-    other = full(2, dev)
+    assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # no count, no label
+    other = U.full(2, dev)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=other)
-    assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a count, no label
+    assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a count, no label
     eng.pairs_label(labels, counts=other)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=other)
-    assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a count since the label
+    assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a count since the label
     eng.pairs_label(labels, counts=other)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=other, batch=pairs.batch_ptr([30, n - 30], dev))
-    assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a batched count: no label to read
+    assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE     # a batched count: no label to read
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=other)
     eng.pairs_label(labels, counts=other)
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
@@ -391,20 +353,20 @@ def test_state_and_argument_errors(sc):
     assert fn(ctx, ptr(v), n, 2, ptr(sums), None, None, n, None) == N.ERR_ARG
     assert lib.sc_last_error() and untouched()
     crate.particles = points                                                        # an upload since the label
-    assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=other)
     eng.pairs_label(labels, counts=other)
     crate._send_tick_inputs()                                                       # inside a tick
     eng.step_begin()
     try:
-        assert code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE
+        assert U.code_of(eng.pairs_cluster_sums, *args, counts=counts) == N.ERR_STATE
     finally:
         eng.step_finish()
     assert untouched()
     # no points at all: n = 0, C = 0, nothing written
-    empty = tensor(np.zeros((0, 2)))
-    eng.pairs_count(empty, radius=radius, offsets=full(1, dev), counts=other)
-    eng.pairs_label(full(0, dev), counts=other)
-    eng.pairs_cluster_sums(tensor(np.zeros((0, 2))), sums, mins, maxs, counts=counts)
+    empty = U.tensor(np.zeros((0, 2)))
+    eng.pairs_count(empty, radius=radius, offsets=U.full(1, dev), counts=other)
+    eng.pairs_label(U.full(0, dev), counts=other)
+    eng.pairs_cluster_sums(U.tensor(np.zeros((0, 2))), sums, mins, maxs, counts=counts)
     eng.synchronize()
     assert counts.cpu().tolist() == [0, 0] and all(bool((a == MARK).all()) for a in (sums, mins, maxs))

@@ -4,50 +4,18 @@ against the spec's label propagation over the device's own pair list, on the sta
 ids --, the same bytes after a half and a full count and when repeated, a fill after the label, a room below the cluster
 count, the domain error, the error codes and the path that does not synchronise."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import cluster_cases as CK
 import cluster_spec as CS
+import gpu_support as U
 import pairs_cases as K
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine labels the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(points):
-    import torch
-    t = torch.from_numpy(np.array(points, dtype=np.float64).reshape(-1, 2)).cuda()   # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
-    return t
-
-
-def full(shape, device):
-    import torch
-    return torch.full((shape,), SENTINEL, dtype=torch.int64, device=device)
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,22 +31,15 @@ def assert_same(got, want):
         assert g.dtype == w.dtype == np.int64 and g.shape == w.shape and g.tobytes() == w.tobytes()
 
 
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
-
-
 def label(eng, points, radius, *, half, rooms=None, twice=False):
     """count + label through the engine into sentinel-filled tensors -> (labels, sizes, roots, counts), synchronised."""
     import torch
     dev = torch.device("cuda", eng.device)
     n = len(points)
     room = n if rooms is None else rooms
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    labels, sizes, roots = full(n + 8, dev), full(room + 8, dev), full(room + 8, dev)
-    t = tensor(points)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    labels, sizes, roots = U.full(n + 8, dev), U.full(room + 8, dev), U.full(room + 8, dev)
+    t = U.tensor(points)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts, half=half)
     for _ in range(2 if twice else 1):
         assert eng.pairs_label(labels, sizes, roots, counts=counts, room=n, room_clusters=room) is counts
@@ -91,14 +52,14 @@ def label(eng, points, radius, *, half, rooms=None, twice=False):
 @pytest.mark.parametrize("name", list(CK.small_cases()))
 def test_case_equals_the_spec(crate, name):
     points, radius = CK.cases()[name]
-    got = crate.cluster_tensors(radius, points=tensor(points))
+    got = crate.cluster_tensors(radius, points=U.tensor(points))
     assert all(t.is_cuda for t in got)
     assert_same(got, spec(name))
 
 
 def test_wide_equals_the_propagation_over_the_device_list(crate):
     points, radius = CK.cases()["wide"]
-    t = tensor(points)
+    t = U.tensor(points)
     offsets, partners = crate.pair_tensors(radius, points=t, half=True)
     want = CS.components(len(points), offsets.cpu().numpy(), partners.cpu().numpy())
     assert 100 < len(want[1]) < len(points) // 4 and want[1].max() > 1000        # near percolation: big and small ones
@@ -117,7 +78,7 @@ def test_half_full_and_repeated_give_the_same_bytes(crate, name):
     for labels, sizes, roots, counts in results:
         assert counts.cpu().tolist() == [n, total]
         assert_same((labels[:n], sizes[:total], roots[:total]), want)
-        assert (labels[n:] == SENTINEL).all() and (sizes[total:] == SENTINEL).all() and (roots[total:] == SENTINEL).all()
+        assert (labels[n:] == U.SENTINEL).all() and (sizes[total:] == U.SENTINEL).all() and (roots[total:] == U.SENTINEL).all()
 
 
 def test_a_fill_after_the_label_still_matches(crate):
@@ -128,11 +89,11 @@ def test_a_fill_after_the_label_still_matches(crate):
     n = len(points)
     for half in (False, True):
         want = S.pairs(points, radius, half)
-        offsets, counts, other = full(n + 1, dev), full(2, dev), full(2, dev)
-        labels = full(n, dev)
-        partners = full(len(want[1]), dev)
+        offsets, counts, other = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+        labels = U.full(n, dev)
+        partners = U.full(len(want[1]), dev)
         d2 = torch.full((len(want[1]),), -1.5, dtype=torch.float64, device=dev)
-        t = tensor(points)
+        t = U.tensor(points)
         eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts, half=half)
         eng.pairs_label(labels, counts=other)                                       # without sizes and roots
         eng.pairs_fill(partners, d2)
@@ -155,30 +116,30 @@ def test_room_below_the_cluster_count(crate, room):
     labels, sizes, roots, counts = label(crate.engine, points, radius, half=True, rooms=room)
     assert counts.cpu().tolist() == [n, total]
     assert_same((labels[:n], sizes[:room], roots[:room]), (want[0], want[1][:room], want[2][:room]))
-    assert (labels[n:] == SENTINEL).all() and (sizes[room:] == SENTINEL).all() and (roots[room:] == SENTINEL).all()
+    assert (labels[n:] == U.SENTINEL).all() and (sizes[room:] == U.SENTINEL).all() and (roots[room:] == U.SENTINEL).all()
 
 
 # ---- 4. the domain
 
 def test_outside_the_domain(crate):
     points, radius = K.outside_domain()
-    t = tensor(points)
+    t = U.tensor(points)
     with pytest.raises(ValueError, match="domain"):
         crate.cluster_tensors(radius, points=t)
     labels, sizes, roots, counts = label(crate.engine, points, radius, half=True)
     assert counts.cpu().tolist() == [len(points), -1]                               # (n is the count's; the label wrote -1)
-    assert (labels == SENTINEL).all() and (sizes == SENTINEL).all() and (roots == SENTINEL).all()
+    assert (labels == U.SENTINEL).all() and (sizes == U.SENTINEL).all() and (roots == U.SENTINEL).all()
     import torch
-    alone = full(2, torch.device("cuda", crate.engine.device))
+    alone = U.full(2, torch.device("cuda", crate.engine.device))
     crate.engine.pairs_label(labels, sizes, roots, counts=alone)                    # counts[1] = -1 and nothing else
     crate.engine.synchronize()
-    assert alone.cpu().tolist() == [SENTINEL, -1] and (labels == SENTINEL).all()
+    assert alone.cpu().tolist() == [U.SENTINEL, -1] and (labels == U.SENTINEL).all()
     out = crate.cluster_tensors(radius, points=t, max_clusters=16)
     crate.synchronize()
     assert int(out[-1][1]) == -1
     inside = points.copy()
     inside[33, 1] = np.nextafter(inside[33, 1], 0)                                  # one ulp inside: fine
-    assert_same(crate.cluster_tensors(radius, points=tensor(inside)), CS.clusters(inside, radius))
+    assert_same(crate.cluster_tensors(radius, points=U.tensor(inside)), CS.clusters(inside, radius))
 
 
 # ---- 5. the state form
@@ -186,7 +147,7 @@ def test_outside_the_domain(crate):
 def test_state_after_ticks_and_a_load_with_permuted_ids(sc):
     import torch
     from sand_crate_amd import pairs
-    first = sc.Crate(world(sc))
+    first = sc.Crate(U.scene(sc))
     for _ in range(40):
         first.physics_tick()
     particles, velocities = first.state_tensors(pressure=False)
@@ -196,7 +157,7 @@ def test_state_after_ticks_and_a_load_with_permuted_ids(sc):
     assert_same(first.cluster_tensors(), CS.clusters(points, first.diameter))       # radius defaults to the diameter
     ids = torch.from_numpy(np.random.RandomState(7).permutation(n) * 3 + 5).cuda()  # row k gets id ids[k]: sparse, shuffled
     torch.cuda.synchronize()
-    other = sc.Crate(world(sc), noise="none", capacity=n + 100)
+    other = sc.Crate(U.scene(sc), noise="none", capacity=n + 100)
     other.load_state_tensors(particles, velocities, ids)
     exported, _, exported_ids = other.state_tensors(pressure=False, ids=True)
     order = np.argsort(ids.cpu().numpy())
@@ -214,7 +175,7 @@ def test_state_after_ticks_and_a_load_with_permuted_ids(sc):
 
 
 def test_state_of_an_empty_crate(sc):
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     labels, sizes, roots = crate.cluster_tensors()                                  # before the first tick
     assert labels.shape == sizes.shape == roots.shape == (0,)
     out = crate.cluster_tensors(max_clusters=4)
@@ -224,7 +185,7 @@ def test_state_of_an_empty_crate(sc):
 
 def test_labelling_changes_nothing(sc):
     def trajectory(labelling):
-        crate = sc.Crate(world(sc))
+        crate = sc.Crate(U.scene(sc))
         for _ in range(30):
             crate.physics_tick()
             if labelling:
@@ -247,39 +208,39 @@ def test_labelling_changes_nothing(sc):
 def test_state_errors(sc):
     import torch
     from sand_crate_amd import _native as N
-    crate = sc.Crate(world(sc), noise="none", capacity=512)
+    crate = sc.Crate(U.scene(sc), noise="none", capacity=512)
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     points, radius = K.cases()["n_65"]
-    t = tensor(points)
+    t = U.tensor(points)
     offsets = torch.zeros(eng.capacity + 1, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    labels, sizes, roots = full(eng.capacity, dev), full(eng.capacity, dev), full(eng.capacity, dev)
+    labels, sizes, roots = U.full(eng.capacity, dev), U.full(eng.capacity, dev), U.full(eng.capacity, dev)
     torch.cuda.synchronize()
     args = (labels, sizes, roots)
-    assert code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE            # no count yet
+    assert U.code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE            # no count yet
     eng.synchronize()
-    assert (labels == SENTINEL).all() and (sizes == SENTINEL).all() and (roots == SENTINEL).all()
+    assert (labels == U.SENTINEL).all() and (sizes == U.SENTINEL).all() and (roots == U.SENTINEL).all()
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_label(*args, counts=counts)                                           # ... with one: fine, and again
     eng.pairs_label(*args, counts=counts)
     crate.particles = points                                                        # an upload since the count
-    assert code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
     eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_label(*args, counts=counts)
     eng.append(points[:3] + 2.0, np.zeros((3, 2)))                                  # an append since the count
-    assert code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
     crate.particles = points
     eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_label(*args, counts=counts)
     crate.physics_tick()                                                            # a tick since the count
-    assert code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
     eng.synchronize()
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     crate._send_tick_inputs()                                                       # inside a tick
     eng.step_begin()
     try:
-        assert code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
+        assert U.code_of(eng.pairs_label, *args, counts=counts) == N.ERR_STATE
     finally:
         eng.step_finish()
 
@@ -292,9 +253,9 @@ def test_argument_and_capacity_errors(sc):
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
     points = np.random.RandomState(3).rand(n, 2)
-    t = tensor(points)
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    labels, sizes, roots, out = full(n, dev), full(n, dev), full(n, dev), full(2, dev)
+    t = U.tensor(points)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    labels, sizes, roots, out = U.full(n, dev), U.full(n, dev), U.full(n, dev), U.full(2, dev)
     torch.cuda.synchronize()
     eng.pairs_count(t, radius=0.05, offsets=offsets, counts=counts)
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
@@ -305,11 +266,11 @@ def test_argument_and_capacity_errors(sc):
     assert fn(ctx, ptr(labels), -1, ptr(sizes), ptr(roots), n, ptr(out)) == N.ERR_ARG
     assert fn(ctx, ptr(labels), n, ptr(sizes), ptr(roots), -1, ptr(out)) == N.ERR_ARG
     assert fn(ctx, ptr(labels), n - 1, ptr(sizes), ptr(roots), n, ptr(out)) == N.ERR_CAPACITY      # short labels
-    assert code_of(eng.pairs_label, labels[:n - 1], sizes, roots, counts=out) == N.ERR_CAPACITY
+    assert U.code_of(eng.pairs_label, labels[:n - 1], sizes, roots, counts=out) == N.ERR_CAPACITY
     assert lib.sc_last_error()
     eng.synchronize()
     for a in (labels, sizes, roots, out):
-        assert (a == SENTINEL).all()
+        assert (a == U.SENTINEL).all()
     eng.pairs_label(labels, None, roots, counts=out)                                # sizes or roots alone: fine
     eng.pairs_label(labels, sizes, None, counts=out)
     eng.synchronize()
@@ -323,7 +284,7 @@ def test_max_clusters_does_not_synchronise_and_equals_the_default(crate, monkeyp
     import torch
     name = "n_2049_partners_4.5"
     points, radius = CK.cases()[name]
-    t = tensor(points)
+    t = U.tensor(points)
     labels, sizes, roots = crate.cluster_tensors(radius, points=t)
     n, total = len(points), len(sizes)
     assert_same((labels, sizes, roots), spec(name))

@@ -11,77 +11,20 @@ The raster's bound.  values.grad[j] = sum_r w_rj G_r with G_r = target_r / wsum_
 tests/test_field_grad_cpu.py, (Q_j + 2C + 16) 2^-53 sum_r |w_rj G_r| with Q_j the queries that reach point j -- and G_r
 itself differs between the two routes by the error of wsum_r, a sum of P_r positive weights (relative error at most
 (P_r + 3) 2^-53 on each side) and one division: so the factor is (Q_j + 2 max_r P_r + 2C + 24)."""
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import field_cases as FK
 import field_grad_cases as GK
 import field_grad_spec as GS
+import gpu_support as U
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
-SENTINEL_F = -1.5
 CASES = [name for name in GK.cases() if name not in GK.OUTSIDE]
 GROUP = GS.GROUP
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(a, tail=None, requires_grad=False):
-    import torch
-    if a is None:
-        return None
-    a = np.array(a, dtype=np.float64)                                               # (a copy: the cases are read-only)
-    t = torch.from_numpy(a if tail is None else a.reshape(-1, tail)).cuda()
-    torch.cuda.synchronize()
-    return t.requires_grad_() if requires_grad else t
-
-
-def full(shape, device, value=SENTINEL):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), value,
-                      dtype=torch.int64 if isinstance(value, int) else torch.float64, device=device)
-
-
-def same(got, want):
-    """Bit for bit, every element; a NaN of the rule is any NaN at the same place."""
-    g = got.detach().cpu().numpy()
-    if g.dtype != want.dtype or g.shape != want.shape:
-        return False
-    nan = np.isnan(want)
-    return bool((np.isnan(g) == nan).all()) and g[~nan].tobytes() == want[~nan].tobytes()
-
-
-def untouched(*tensors):
-    return all(bool((t == (SENTINEL_F if t.dtype.is_floating_point else SENTINEL)).all()) for t in tensors)
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
 
 
 def groups_of(use):
@@ -101,9 +44,10 @@ def through_the_engine(eng, use, radius, power, *, half=False, spare=8, row_rows
     dev = torch.device("cuda", eng.device)
     n = len(pts)
     rows = n if self_form else len(rows_xy)
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    grad = full((rows + spare, 2), dev, SENTINEL_F)
-    held = [tensor(pts, 2), None if self_form else tensor(rows_xy, 2), tensor(a), tensor(b), tensor(row_s), tensor(part_s)]
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    grad = U.full((rows + spare, 2), dev, U.SENTINEL_F)
+    held = [U.tensor(pts, 2), None if self_form else U.tensor(rows_xy, 2),
+            U.tensor(a, None), U.tensor(b, None), U.tensor(row_s, None), U.tensor(part_s, None)]
     eng.pairs_count(held[0], radius=radius, offsets=offsets, counts=counts, half=half)
     assert eng.pairs_sum_grad(grad, held[2], held[3], held[4], held[5], power=power, queries=held[1], counts=out,
                               row_rows=row_rows, part_rows=part_rows) is out
@@ -115,19 +59,19 @@ def run_function(crate, case, needs, *, weight_sums=None, state=False):
     """`field_function` of a case with `needs` (a subset of "values", "points", "queries") requiring grad, then the
     gradients of the case's upstream G and gw -> (outputs, {name: gradient or None})."""
     import torch
-    values = tensor(case.values, requires_grad="values" in needs)
-    points = tensor(case.points, 2, requires_grad="points" in needs)
-    queries = tensor(case.queries, 2, requires_grad="queries" in needs)
+    values = U.tensor(case.values, None, requires_grad="values" in needs)
+    points = U.tensor(case.points, 2, requires_grad="points" in needs)
+    queries = U.tensor(case.queries, 2, requires_grad="queries" in needs)
     want_wsum = case.gw is not None if weight_sums is None else weight_sums
     out = crate.field_function(values, case.radius, power=case.power, include_self=case.include_self,
                                points=None if state else points, queries=queries, weight_sums=want_wsum)
     inputs = {name: t for name, t in (("values", values), ("points", points), ("queries", queries)) if name in needs}
     pairs = []
     if case.values is not None and case.G is not None:
-        G = tensor(case.G)
+        G = U.tensor(case.G, None)
         pairs.append((out[0], G.view(-1) if out[0].dim() == 1 else G))
     if case.gw is not None:
-        pairs.append((out[-1], tensor(case.gw)))
+        pairs.append((out[-1], U.tensor(case.gw, None)))
     grads = torch.autograd.grad([o for o, _ in pairs], list(inputs.values()), [g for _, g in pairs], allow_unused=True)
     return out, dict(zip(inputs, grads))
 
@@ -145,9 +89,9 @@ def check_gradients(case, want, grads):
         if name == "values" and case.values.ndim == 1:
             rule = rule[:, 0]
         if case.power == 0 and name != "values":
-            assert got is None or same(got, rule)
+            assert got is None or U.same_bits_or_nan(got, rule)
             continue
-        assert got is not None and same(got, rule), name
+        assert got is not None and U.same_bits_or_nan(got, rule), name
 
 
 # ---- 1. the kernel against the rule: every case, every use, every group
@@ -163,9 +107,9 @@ def test_engine_equals_the_spec(crate, name):
                 want = GS.position_grad(group[0], group[1], case.radius, case.power, *group[2:])
             grad, counts = through_the_engine(crate.engine, group, case.radius, case.power, half=bool(at))
             assert counts.cpu().tolist() == [rows, 0]
-            assert same(grad[:rows], want) and untouched(grad[rows:])
+            assert U.same_bits_or_nan(grad[:rows], want) and U.untouched(grad[rows:])
             total = grad[:rows] if total is None else total + grad[:rows]
-        assert same(total, GK.spec(name)[key])                                      # the groups add up to the chunked rule
+        assert U.same_bits_or_nan(total, GK.spec(name)[key])                        # the groups add up to the chunked rule
 
 
 def test_two_calls_give_identical_bits(crate):
@@ -185,7 +129,7 @@ def test_outside_the_domain_writes_the_status_only(crate, name):
     case = GK.cases()[name]
     for key, use in GK.uses(case).items():
         grad, counts = through_the_engine(crate.engine, use, case.radius, case.power)
-        assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(grad)
+        assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(grad)
     with pytest.raises(ValueError, match="domain"):
         run_function(crate, case, needs_of(case))
 
@@ -197,23 +141,23 @@ def test_short_arrays_write_the_status_only(crate):
         use = GK.uses(case)[key]
         for kw in (dict(row_rows=rows - 1), dict(part_rows=partners - 1)):
             grad, counts = through_the_engine(crate.engine, use, case.radius, case.power, **kw)
-            assert counts.cpu().tolist() == [SENTINEL, -2] and untouched(grad)
+            assert counts.cpu().tolist() == [U.SENTINEL, -2] and U.untouched(grad)
         grad, counts = through_the_engine(crate.engine, use, case.radius, case.power, row_rows=rows, part_rows=partners)
-        assert counts.cpu().tolist() == [rows, 0] and same(grad[:rows], GK.spec("queries_65")[key])
+        assert counts.cpu().tolist() == [rows, 0] and U.same_bits_or_nan(grad[:rows], GK.spec("queries_65")[key])
     case = GK.cases()["channels_3"]
     n = len(case.points)
     use = GK.uses(case)["points"]
     for kw in (dict(row_rows=n - 1), dict(part_rows=n - 1)):
         grad, counts = through_the_engine(crate.engine, use, case.radius, case.power, **kw)
-        assert counts.cpu().tolist() == [SENTINEL, -2] and untouched(grad)
+        assert counts.cpu().tolist() == [U.SENTINEL, -2] and U.untouched(grad)
     # the scalars alone are counted too, and the domain wins over the rows
     only = GK.uses(GK.cases()["density"])["points"]
     grad, counts = through_the_engine(crate.engine, only, case.radius, case.power, part_rows=n - 1)
-    assert counts.cpu().tolist() == [SENTINEL, -2] and untouched(grad)
+    assert counts.cpu().tolist() == [U.SENTINEL, -2] and U.untouched(grad)
     outside = GK.cases()[GK.OUTSIDE[1]]
     grad, counts = through_the_engine(crate.engine, GK.uses(outside)["queries"], outside.radius, outside.power,
                                       part_rows=len(outside.points) - 1)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(grad)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(grad)
 
 
 # ---- 3. the workspace is left as it is
@@ -227,11 +171,12 @@ def test_the_pair_list_is_the_same_before_and_after(crate):
     n = len(points)
     want = S.pairs(points, radius)
     total = len(want[1])
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    before, after = [full(total, dev), full(total, dev, SENTINEL_F)], [full(total, dev), full(total, dev, SENTINEL_F)]
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    before, after = [U.full(total, dev), U.full(total, dev, U.SENTINEL_F)], [U.full(total, dev), U.full(total, dev, U.SENTINEL_F)]
     _, _, a, b, row_s, part_s, _ = GK.uses(case)["points"]
-    held = [tensor(points, 2), tensor(a), tensor(b), tensor(row_s), tensor(points[:40] + 0.25 * radius, 2)]
-    grad, probe_grad = full((n, 2), dev, SENTINEL_F), full((40, 2), dev, SENTINEL_F)
+    held = [U.tensor(points, 2), U.tensor(a, None), U.tensor(b, None), U.tensor(row_s, None),
+            U.tensor(points[:40] + 0.25 * radius, 2)]
+    grad, probe_grad = U.full((n, 2), dev, U.SENTINEL_F), U.full((40, 2), dev, U.SENTINEL_F)
     eng.pairs_count(held[0], radius=radius, offsets=offsets, counts=counts)
     eng.pairs_fill(*before)
     eng.pairs_sum_grad(grad, held[1], held[2], held[3], held[3], power=3, counts=out)
@@ -239,9 +184,10 @@ def test_the_pair_list_is_the_same_before_and_after(crate):
     eng.pairs_fill(*after)
     eng.synchronize()
     assert all(torch.equal(x, y) for x, y in zip(before, after))
-    assert same(after[0], want[1]) and same(after[1], want[2])
-    assert same(grad, GS.position_grad(None, points, radius, 3, a, b, row_s, part_s, True))
-    assert same(probe_grad, GS.position_grad(points[:40] + 0.25 * radius, points, radius, 2, None, None, None, part_s))
+    assert U.same_bits_or_nan(after[0], want[1]) and U.same_bits_or_nan(after[1], want[2])
+    assert U.same_bits_or_nan(grad, GS.position_grad(None, points, radius, 3, a, b, row_s, part_s, True))
+    assert U.same_bits_or_nan(probe_grad,
+                              GS.position_grad(points[:40] + 0.25 * radius, points, radius, 2, None, None, None, part_s))
 
 
 # ---- 4. errors
@@ -254,17 +200,18 @@ def test_argument_state_and_capacity_errors(sc):
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
     points = np.random.RandomState(3).rand(n, 2)
-    t = tensor(points, 2)
-    a, b, s = tensor(FK.make_values(4, n, width)), tensor(FK.make_values(5, n, width)), tensor(FK.make_values(6, n))
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    grad, out = full((n, 2), dev, SENTINEL_F), full(2, dev)
+    t = U.tensor(points, 2)
+    a, b = U.tensor(FK.make_values(4, n, width), None), U.tensor(FK.make_values(5, n, width), None)
+    s = U.tensor(FK.make_values(6, n), None)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    grad, out = U.full((n, 2), dev, U.SENTINEL_F), U.full(2, dev)
     torch.cuda.synchronize()
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
     fn = lib.sc_pairs_sum_grad_device
     args = lambda **kw: tuple({**dict(ctx=ctx, q=None, nq=0, a=ptr(a), arows=n, b=ptr(b), brows=n, c=width, rs=ptr(s),  # noqa: E731
                                       ps=ptr(s), power=3, grad=ptr(grad), room=n, counts=ptr(out)), **kw}.values())
     assert fn(*args()) == N.ERR_STATE                                               # no count yet
-    assert code_of(eng.pairs_sum_grad, grad, a, b, counts=out) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum_grad, grad, a, b, counts=out) == N.ERR_STATE
     eng.pairs_count(t, radius=0.05, offsets=offsets, counts=counts)
     assert fn(*args(ctx=None)) == N.ERR_ARG
     assert fn(*args(counts=None)) == N.ERR_ARG
@@ -284,7 +231,7 @@ def test_argument_state_and_capacity_errors(sc):
     assert fn(*args(room=n - 1)) == N.ERR_CAPACITY                                  # a short gradient, self form
     assert fn(*args(q=ptr(t), nq=n, room=n - 1)) == N.ERR_CAPACITY                  # ... and for the queries
     assert fn(*args(q=ptr(t), nq=(1 << 28) + 1, room=(1 << 28) + 1)) == N.ERR_CAPACITY
-    assert code_of(eng.pairs_sum_grad, grad[:n - 1], a, b, counts=out) == N.ERR_CAPACITY
+    assert U.code_of(eng.pairs_sum_grad, grad[:n - 1], a, b, counts=out) == N.ERR_CAPACITY
     assert lib.sc_last_error()
     for call in (lambda: eng.pairs_sum_grad(grad, a, b, power=4, counts=out), lambda: eng.pairs_sum_grad(grad, a, None, counts=out),
                  lambda: eng.pairs_sum_grad(grad, a, b[:, :2], counts=out), lambda: eng.pairs_sum_grad(grad, a, b, s[:n - 1], counts=out),
@@ -293,14 +240,14 @@ def test_argument_state_and_capacity_errors(sc):
         with pytest.raises(ValueError):
             call()
     eng.synchronize()
-    assert untouched(grad, out)
+    assert U.untouched(grad, out)
     assert fn(*args()) == 0                                                         # and as it should be: fine
     eng.synchronize()
     A, B, sv = a.cpu().numpy(), b.cpu().numpy(), s.cpu().numpy()
-    assert out.cpu().tolist() == [n, 0] and same(grad, GS.position_grad(None, points, 0.05, 3, A, B, sv, sv, True))
+    assert out.cpu().tolist() == [n, 0] and U.same_bits_or_nan(grad, GS.position_grad(None, points, 0.05, 3, A, B, sv, sv, True))
     assert fn(*args(q=ptr(t), nq=10, room=10, a=None, b=None, c=0, ps=None)) == 0   # row_s alone, few queries
     eng.synchronize()
-    assert same(grad[:10], GS.position_grad(points[:10], points, 0.05, 3, None, None, sv, None))
+    assert U.same_bits_or_nan(grad[:10], GS.position_grad(points[:10], points, 0.05, 3, None, None, sv, None))
     eng.upload(points, np.zeros_like(points))                                       # an upload since the count
     assert fn(*args()) == N.ERR_STATE
     eng.close()
@@ -313,10 +260,10 @@ def test_argument_state_and_capacity_errors(sc):
 def test_forward_is_field_tensors_bit_for_bit(crate, name):
     import torch
     case = GK.cases()[name]
-    kw = dict(power=case.power, include_self=case.include_self, points=tensor(case.points, 2), queries=tensor(case.queries, 2),
-              weight_sums=True)
-    want = crate.field_tensors(tensor(case.values), case.radius, **kw)
-    plain = crate.field_function(tensor(case.values), case.radius, **kw)
+    kw = dict(power=case.power, include_self=case.include_self, points=U.tensor(case.points, 2),
+              queries=U.tensor(case.queries, 2), weight_sums=True)
+    want = crate.field_tensors(U.tensor(case.values, None), case.radius, **kw)
+    plain = crate.field_function(U.tensor(case.values, None), case.radius, **kw)
     assert all(t.grad_fn is None and not t.requires_grad for t in plain)            # requires_grad nowhere: no graph
     out, _ = run_function(crate, case, needs_of(case), weight_sums=True)
     assert all(t.requires_grad for t in out)
@@ -324,10 +271,11 @@ def test_forward_is_field_tensors_bit_for_bit(crate, name):
         assert len(got) == len(want)
         assert all(a.shape == b.shape and torch.equal(a.detach().view(torch.int64), b.view(torch.int64)) for a, b in zip(got, want))
     with torch.no_grad():
-        quiet = crate.field_function(tensor(case.values, requires_grad=case.values is not None), case.radius, **kw)
+        quiet = crate.field_function(U.tensor(case.values, None, requires_grad=case.values is not None), case.radius, **kw)
     assert all(t.grad_fn is None for t in quiet)
     with pytest.raises(ValueError, match="power"):
-        crate.field_function(tensor(case.values), case.radius, power=4, points=tensor(case.points, 2, requires_grad=True))
+        crate.field_function(U.tensor(case.values, None), case.radius, power=4,
+                             points=U.tensor(case.points, 2, requires_grad=True))
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -350,12 +298,12 @@ def test_include_self_plays_no_part_in_the_position_gradient(crate):
     case = GK.cases()[GK.ORDER]
     a = run_function(crate, case, ("points",))[1]["points"]
     b = run_function(crate, case._replace(include_self=True), ("points",))[1]["points"]
-    assert same(a, b.cpu().numpy()) and same(a, GK.spec(GK.ORDER)["points"])
+    assert U.same_bits_or_nan(a, b.cpu().numpy()) and U.same_bits_or_nan(a, GK.spec(GK.ORDER)["points"])
 
 
 def test_state_form_and_a_tick_between_forward_and_backward(sc):
     import torch
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     for _ in range(40):
         crate.physics_tick()
     particles, velocities = crate.state_tensors(pressure=False)
@@ -373,22 +321,23 @@ def test_state_form_and_a_tick_between_forward_and_backward(sc):
         forward = [t.detach().clone() for t in out]
         if tick:
             crate.physics_tick()
-        grad, = torch.autograd.grad(list(out), [values], [tensor(G), tensor(gw)])
+        grad, = torch.autograd.grad(list(out), [values], [U.tensor(G, None), U.tensor(gw, None)])
         return forward, grad
 
     forward, grad = run(False)
     assert all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in zip(forward, want_forward))
-    assert same(grad, GS.values_grad(points, radius, G, 2, True))
+    assert U.same_bits_or_nan(grad, GS.values_grad(points, radius, G, 2, True))
     forward_t, grad_t = run(True)
     assert all(torch.equal(a, b) for a, b in zip(forward, forward_t)) and torch.equal(grad, grad_t)
     assert not torch.equal(crate.state_tensors(pressure=False)[0], particles)   # the tick did move them
     # probes over the state, the gradient with respect to the probes
-    probes = tensor(points[:50] + 0.3 * crate.diameter, 2, requires_grad=True)
+    probes = U.tensor(points[:50] + 0.3 * crate.diameter, 2, requires_grad=True)
     crate_points = crate.state_tensors(pressure=False)[0].cpu().numpy()
     vel = crate.state_tensors(pressure=False)[1]
     sums, wsum = crate.field_function(vel, radius, queries=probes, weight_sums=True)
-    g, = torch.autograd.grad([sums, wsum], [probes], [tensor(G[:50]), tensor(gw[:50])])
-    assert same(g, GS.query_queries_grad(crate_points, radius, vel.cpu().numpy(), 3, probes.detach().cpu().numpy(), G[:50], gw[:50]))
+    g, = torch.autograd.grad([sums, wsum], [probes], [U.tensor(G[:50], None), U.tensor(gw[:50], None)])
+    assert U.same_bits_or_nan(g, GS.query_queries_grad(crate_points, radius, vel.cpu().numpy(), 3, probes.detach().cpu().numpy(),
+                                                       G[:50], gw[:50]))
 
 
 def test_raster_through_normalized_back_to_the_values(crate):
@@ -400,10 +349,10 @@ def test_raster_through_normalized_back_to_the_values(crate):
     nx, ny = 16, 12
     target = np.random.RandomState(21).randn(ny * nx, C)
     grid = pairs.grid_queries(0.0, 1.0, 0.0, 1.0, nx, ny, "cuda")
-    values = tensor(case.values, requires_grad=True)
-    sums, wsum = crate.field_function(values, radius, points=tensor(points, 2), queries=grid, weight_sums=True)
+    values = U.tensor(case.values, None, requires_grad=True)
+    sums, wsum = crate.field_function(values, radius, points=U.tensor(points, 2), queries=grid, weight_sums=True)
     image = pairs.normalized(sums, wsum)
-    (image * tensor(target)).sum().backward()
+    (image * U.tensor(target, None)).sum().backward()
     got = values.grad.cpu().numpy()
     assert np.isfinite(got).all() and (got != 0).any()
     # torch's dense float64 autograd of the same raster, on the CPU

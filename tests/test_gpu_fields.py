@@ -5,7 +5,6 @@ bits; the domain error and short values write the status and nothing else; the w
 rows past the row count stay untouched; the state form after ticks, the invalidation rule, the error codes and the path
 that does not synchronise."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,50 +12,15 @@ import pytest
 import cluster_spec as CS
 import field_cases as FK
 import field_spec as FS
+import gpu_support as U
 import nearest_spec as NS
 import pairs_cases as K
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
-SENTINEL_F = -1.5
 CASES = [name for name in FK.cases() if name not in FK.OUTSIDE]
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(a, tail=None):
-    import torch
-    if a is None:
-        return None
-    a = np.array(a, dtype=np.float64)                                               # (a copy: the cases are read-only)
-    t = torch.from_numpy(a if tail is None else a.reshape(-1, tail)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def full(shape, device, value=SENTINEL):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), value,
-                      dtype=torch.int64 if isinstance(value, int) else torch.float64, device=device)
 
 
 def two_dimensional(case):
@@ -70,29 +34,9 @@ def spec(name):
         return FS.field(case.points, case.radius, two_dimensional(case), case.power, case.include_self, case.queries)
 
 
-def same(got, want):
-    """Bit for bit, every element; a NaN of the rule is any NaN at the same place."""
-    g = got.cpu().numpy()
-    if g.dtype != want.dtype or g.shape != want.shape:
-        return False
-    nan = np.isnan(want)
-    return bool((np.isnan(g) == nan).all()) and g[~nan].tobytes() == want[~nan].tobytes()
-
-
-def untouched(*tensors):
-    return all(bool((t == (SENTINEL_F if t.dtype.is_floating_point else SENTINEL)).all()) for t in tensors)
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
-
-
 def through_the_crate(crate, case, **kw):
-    return crate.field_tensors(tensor(case.values), case.radius, power=case.power, include_self=case.include_self,
-                               points=tensor(case.points, 2), queries=tensor(case.queries, 2), **kw)
+    return crate.field_tensors(U.tensor(case.values, None), case.radius, power=case.power, include_self=case.include_self,
+                               points=U.tensor(case.points, 2), queries=U.tensor(case.queries, 2), **kw)
 
 
 def through_the_engine(eng, case, *, weight_sums=True, half=False, spare=8, values_rows=None):
@@ -102,11 +46,11 @@ def through_the_engine(eng, case, *, weight_sums=True, half=False, spare=8, valu
     dev = torch.device("cuda", eng.device)
     n = len(case.points)
     rows = n if case.queries is None else len(case.queries)
-    values = tensor(two_dimensional(case))
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    sums = None if values is None else full((rows + spare, values.shape[1]), dev, SENTINEL_F)
-    wsum = full(rows + spare, dev, SENTINEL_F) if weight_sums or values is None else None
-    t, q = tensor(case.points, 2), tensor(case.queries, 2)                          # (alive until the synchronisation)
+    values = U.tensor(two_dimensional(case), None)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    sums = None if values is None else U.full((rows + spare, values.shape[1]), dev, U.SENTINEL_F)
+    wsum = U.full(rows + spare, dev, U.SENTINEL_F) if weight_sums or values is None else None
+    t, q = U.tensor(case.points, 2), U.tensor(case.queries, 2)                          # (alive until the synchronisation)
     eng.pairs_count(t, radius=case.radius, offsets=offsets, counts=counts, half=half)
     assert eng.pairs_sum(values, sums, wsum, power=case.power, include_self=case.include_self, queries=q, counts=out,
                          values_rows=values_rows) is out
@@ -124,22 +68,22 @@ def test_case_equals_the_spec(crate, name):
     got = through_the_crate(crate, case, weight_sums=True)
     assert all(t.is_cuda for t in got)
     if case.values is None:
-        assert len(got) == 1 and same(got[0], want_wsum)
-        assert same(through_the_crate(crate, case)[0], want_wsum)
+        assert len(got) == 1 and U.same_bits_or_nan(got[0], want_wsum)
+        assert U.same_bits_or_nan(through_the_crate(crate, case)[0], want_wsum)
     else:
         shaped = want_sums[:, 0] if case.values.ndim == 1 else want_sums
-        assert len(got) == 2 and same(got[0], shaped) and same(got[1], want_wsum)
+        assert len(got) == 2 and U.same_bits_or_nan(got[0], shaped) and U.same_bits_or_nan(got[1], want_wsum)
         only = through_the_crate(crate, case)
-        assert len(only) == 1 and same(only[0], shaped)
+        assert len(only) == 1 and U.same_bits_or_nan(only[0], shaped)
     if want_sums.shape[1] > 8:
         return
     for weight_sums in (True, False):
         sums, wsum, counts = through_the_engine(crate.engine, case, weight_sums=weight_sums, half=not weight_sums)
         assert counts.cpu().tolist() == [rows, 0]
         if sums is not None:
-            assert same(sums[:rows], want_sums) and untouched(sums[rows:])
+            assert U.same_bits_or_nan(sums[:rows], want_sums) and U.untouched(sums[rows:])
         if wsum is not None:
-            assert same(wsum[:rows], want_wsum) and untouched(wsum[rows:])
+            assert U.same_bits_or_nan(wsum[:rows], want_wsum) and U.untouched(wsum[rows:])
 
 
 def test_two_calls_give_identical_bits(crate):
@@ -159,7 +103,7 @@ def test_outside_the_domain_writes_the_status_only(crate, name):
     with pytest.raises(ValueError, match="domain"):
         through_the_crate(crate, case)
     sums, wsum, counts = through_the_engine(crate.engine, case)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(sums, wsum)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(sums, wsum)
     out = through_the_crate(crate, case, sync=False)
     crate.synchronize()
     assert int(out[-1][1]) == -1
@@ -172,21 +116,21 @@ def test_a_query_outside_leaves_the_counts_flag_as_it_was(crate):
     dev = torch.device("cuda", eng.device)
     n = len(case.points)
     want = S.pairs(case.points, case.radius)
-    t, q, values = tensor(case.points, 2), tensor(case.queries, 2), tensor(two_dimensional(case))
-    offsets, counts, out, again = full(n + 1, dev), full(2, dev), full(2, dev), full(2, dev)
-    sums = full((len(case.queries), values.shape[1]), dev, SENTINEL_F)
-    own = full((n, values.shape[1]), dev, SENTINEL_F)
-    partners, d2 = full(len(want[1]), dev), full(len(want[1]), dev, SENTINEL_F)
+    t, q, values = U.tensor(case.points, 2), U.tensor(case.queries, 2), U.tensor(two_dimensional(case), None)
+    offsets, counts, out, again = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev), U.full(2, dev)
+    sums = U.full((len(case.queries), values.shape[1]), dev, U.SENTINEL_F)
+    own = U.full((n, values.shape[1]), dev, U.SENTINEL_F)
+    partners, d2 = U.full(len(want[1]), dev), U.full(len(want[1]), dev, U.SENTINEL_F)
     eng.pairs_count(t, radius=case.radius, offsets=offsets, counts=counts)
     eng.pairs_sum(values, sums, power=case.power, queries=q, counts=out)
     eng.pairs_fill(partners, d2)                                                    # the count's flag is still down
     eng.pairs_sum(values, own, power=case.power, counts=again)                      # ... and so is the next sum's own
     eng.synchronize()
-    assert out.cpu().tolist() == [SENTINEL, -1] and untouched(sums)
-    assert same(partners, want[1]) and same(d2, want[2])
+    assert out.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(sums)
+    assert U.same_bits_or_nan(partners, want[1]) and U.same_bits_or_nan(d2, want[2])
     with np.errstate(all="ignore"):
         rule = FS.field(case.points, case.radius, two_dimensional(case), case.power, True)
-    assert again.cpu().tolist() == [n, 0] and same(own, rule[0])
+    assert again.cpu().tolist() == [n, 0] and U.same_bits_or_nan(own, rule[0])
 
 
 def test_values_one_row_short_and_one_row_long(crate):
@@ -195,22 +139,22 @@ def test_values_one_row_short_and_one_row_long(crate):
     n = len(case.points)
     want_sums, want_wsum = spec("channels_3")
     sums, wsum, counts = through_the_engine(crate.engine, case, values_rows=n - 1)
-    assert counts.cpu().tolist() == [SENTINEL, -2] and untouched(sums, wsum)
-    points = tensor(case.points, 2)
-    short = tensor(case.values[:n - 1])
+    assert counts.cpu().tolist() == [U.SENTINEL, -2] and U.untouched(sums, wsum)
+    points = U.tensor(case.points, 2)
+    short = U.tensor(case.values[:n - 1], None)
     with pytest.raises(ValueError, match="rows"):
         crate.field_tensors(short, case.radius, points=points)
     out = crate.field_tensors(short, case.radius, points=points, sync=False)
     crate.synchronize()
     assert int(out[-1][1]) == -2
-    long = torch.cat([tensor(case.values), full((1, 3), points.device, float("nan"))])
+    long = torch.cat([U.tensor(case.values, None), U.full((1, 3), points.device, float("nan"))])
     torch.cuda.synchronize()
     got = crate.field_tensors(long, case.radius, points=points, weight_sums=True)
-    assert same(got[0], want_sums) and same(got[1], want_wsum)
+    assert U.same_bits_or_nan(got[0], want_sums) and U.same_bits_or_nan(got[1], want_wsum)
     # the status wins over the queries' rows, and the domain over the values
     outside = FK.cases()[FK.OUTSIDE[1]]
     sums, wsum, counts = through_the_engine(crate.engine, outside, values_rows=len(outside.points) - 1)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(sums, wsum)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(sums, wsum)
 
 
 # ---- 3. the workspace is left as it is
@@ -225,14 +169,14 @@ def test_lists_labels_and_tables_are_the_same_before_and_after(crate, half):
     n, k = len(points), 5
     want = S.pairs(points, radius, half)
     total = len(want[1])
-    offsets, counts, other, third = full(n + 1, dev), full(2, dev), full(2, dev), full(2, dev)
-    before = [full(total, dev), full(total, dev, SENTINEL_F), full(n, dev), full((n, k), dev)]
-    after = [full(total, dev), full(total, dev, SENTINEL_F), full(n, dev), full((n, k), dev)]
-    values = tensor(two_dimensional(case))
-    sums, wsum = full((n, values.shape[1]), dev, SENTINEL_F), full(n, dev, SENTINEL_F)
-    probes = tensor(points[:40] + 0.25 * radius, 2)
-    probe_sums = full((40, values.shape[1]), dev, SENTINEL_F)
-    t = tensor(points, 2)
+    offsets, counts, other, third = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev), U.full(2, dev)
+    before = [U.full(total, dev), U.full(total, dev, U.SENTINEL_F), U.full(n, dev), U.full((n, k), dev)]
+    after = [U.full(total, dev), U.full(total, dev, U.SENTINEL_F), U.full(n, dev), U.full((n, k), dev)]
+    values = U.tensor(two_dimensional(case), None)
+    sums, wsum = U.full((n, values.shape[1]), dev, U.SENTINEL_F), U.full(n, dev, U.SENTINEL_F)
+    probes = U.tensor(points[:40] + 0.25 * radius, 2)
+    probe_sums = U.full((40, values.shape[1]), dev, U.SENTINEL_F)
+    t = U.tensor(points, 2)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts, half=half)
     for partners, d2, labels, table in (before, after):
         eng.pairs_fill(partners, d2)
@@ -244,18 +188,21 @@ def test_lists_labels_and_tables_are_the_same_before_and_after(crate, half):
             eng.pairs_sum(None, None, wsum, power=0, counts=third)                  # ... and repeated, without values
     eng.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(before, after))
-    assert same(after[0], want[1]) and same(after[1], want[2]) and same(after[2], CS.clusters(points, radius)[0])
-    assert same(after[3], NS.nearest(points, radius, k)[0])
+    assert U.same_bits_or_nan(after[0], want[1]) and U.same_bits_or_nan(after[1], want[2]) and \
+        U.same_bits_or_nan(after[2], CS.clusters(points, radius)[0])
+    assert U.same_bits_or_nan(after[3], NS.nearest(points, radius, k)[0])
     with np.errstate(all="ignore"):
-        assert other.cpu().tolist() == [n, 0] and same(sums, FS.field(points, radius, two_dimensional(case), 2, False)[0])
-        assert same(probe_sums, FS.field(points, radius, two_dimensional(case), 1, True, points[:40] + 0.25 * radius)[0])
-        assert same(wsum, FS.field(points, radius, None, 0, True)[1])
+        assert other.cpu().tolist() == [n, 0] and \
+            U.same_bits_or_nan(sums, FS.field(points, radius, two_dimensional(case), 2, False)[0])
+        assert U.same_bits_or_nan(probe_sums,
+                                  FS.field(points, radius, two_dimensional(case), 1, True, points[:40] + 0.25 * radius)[0])
+        assert U.same_bits_or_nan(wsum, FS.field(points, radius, None, 0, True)[1])
 
 
 def test_the_crates_other_tensors_are_the_same_before_and_after(crate):
     import torch
     case = FK.cases()["channels_9"]
-    points = tensor(case.points, 2)
+    points = U.tensor(case.points, 2)
     before = (crate.pair_tensors(case.radius, points=points, squared_distances=True),
               crate.neighbor_tensors(7, case.radius, points=points), crate.cluster_tensors(case.radius, points=points))
     through_the_crate(crate, case, weight_sums=True)
@@ -270,7 +217,7 @@ def test_state_after_ticks_with_queries_and_the_stale_count(sc):
     import torch
     from sand_crate_amd import _native as N
     from sand_crate_amd import pairs
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     for _ in range(40):
         crate.physics_tick()
     particles, velocities = crate.state_tensors(pressure=False)
@@ -282,10 +229,10 @@ def test_state_after_ticks_with_queries_and_the_stale_count(sc):
         got = crate.field_tensors(velocities, None if factor == 1.0 else radius, power=power, include_self=include_self,
                                   weight_sums=True)
         want = FS.field(points, radius, v, power, include_self)
-        assert same(got[0], want[0]) and same(got[1], want[1])
+        assert U.same_bits_or_nan(got[0], want[0]) and U.same_bits_or_nan(got[1], want[1])
     assert crate.particle_count == n
     density, = crate.field_tensors()
-    assert same(density, FS.field(points, crate.diameter)[1])
+    assert U.same_bits_or_nan(density, FS.field(points, crate.diameter)[1])
     offsets, _ = crate.pair_tensors()
     count, = crate.field_tensors(power=0, include_self=False)
     assert torch.equal(count, pairs.row_lengths(offsets).double())                  # power 0 counts the partners
@@ -294,24 +241,24 @@ def test_state_after_ticks_with_queries_and_the_stale_count(sc):
     torch.cuda.synchronize()
     sums, wsum = crate.field_tensors(velocities, 2 * crate.diameter, queries=grid, weight_sums=True)
     want = FS.field(points, 2 * crate.diameter, v, 3, True, grid.cpu().numpy())
-    assert same(sums, want[0]) and same(wsum, want[1]) and crate.particle_count == n
+    assert U.same_bits_or_nan(sums, want[0]) and U.same_bits_or_nan(wsum, want[1]) and crate.particle_count == n
     image = pairs.normalized(sums, wsum).reshape(12, 16, 2)
     assert bool(torch.isfinite(image).all()) and bool((wsum > 0).any())
     # a tick since the count: the grid is stale
     eng = crate.engine
-    out, counts = torch.zeros((eng.capacity, 2), dtype=torch.float64, device=particles.device), full(2, particles.device)
+    out, counts = torch.zeros((eng.capacity, 2), dtype=torch.float64, device=particles.device), U.full(2, particles.device)
     torch.cuda.synchronize()
     values = torch.zeros((eng.capacity, 2), dtype=torch.float64, device=particles.device)
     torch.cuda.synchronize()
     eng.pairs_sum(values, out, counts=counts)
     crate.physics_tick()
-    assert code_of(eng.pairs_sum, values, out, counts=counts) == N.ERR_STATE
-    assert code_of(eng.pairs_sum, values, out[:16], queries=grid[:16], counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum, values, out, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum, values, out[:16], queries=grid[:16], counts=counts) == N.ERR_STATE
 
 
 def test_state_of_an_empty_crate_and_rows_past_the_row_count(sc):
     import torch
-    crate = sc.Crate(world(sc), noise="none", capacity=512)
+    crate = sc.Crate(U.scene(sc), noise="none", capacity=512)
     wsum, = crate.field_tensors()                                                   # before the first tick
     assert wsum.shape == (0,)
     eng = crate.engine
@@ -320,33 +267,33 @@ def test_state_of_an_empty_crate_and_rows_past_the_row_count(sc):
     sums, wsum = crate.field_tensors(empty, weight_sums=True)
     assert sums.shape == (0, 3) and wsum.shape == (0,)
     queries = np.array([[0.5, 0.5], [np.nan, 1.0]])
-    sums, wsum = crate.field_tensors(empty, queries=tensor(queries, 2), weight_sums=True)
+    sums, wsum = crate.field_tensors(empty, queries=U.tensor(queries, 2), weight_sums=True)
     assert sums.cpu().tolist() == [[0.0] * 3] * 2 and wsum.cpu().tolist() == [0.0, 0.0]
     case = FK.cases()["rows_65"]
     crate.particles = case.points
     room, n = eng.capacity, len(case.points)
-    offsets, counts = full(room + 1, dev), full(2, dev)
-    values = torch.cat([tensor(case.values), full((room - n, 2), dev, float("nan"))])
-    sums, wsum = full((room, 2), dev, SENTINEL_F), full(room, dev, SENTINEL_F)
+    offsets, counts = U.full(room + 1, dev), U.full(2, dev)
+    values = torch.cat([U.tensor(case.values, None), U.full((room - n, 2), dev, float("nan"))])
+    sums, wsum = U.full((room, 2), dev, U.SENTINEL_F), U.full(room, dev, U.SENTINEL_F)
     torch.cuda.synchronize()
     eng.pairs_count(None, radius=case.radius, offsets=offsets, counts=counts)
     eng.pairs_sum(values, sums, wsum, counts=counts)
     eng.synchronize()
     want = spec("rows_65")
     assert counts.cpu().tolist() == [n, 0]
-    assert same(sums[:n], want[0]) and same(wsum[:n], want[1]) and untouched(sums[n:], wsum[n:])
+    assert U.same_bits_or_nan(sums[:n], want[0]) and U.same_bits_or_nan(wsum[:n], want[1]) and U.untouched(sums[n:], wsum[n:])
     # values with fewer rows than the STATE has particles: only the device knows
     eng.pairs_sum(values[:n - 1], sums, wsum, counts=counts, room=room)
     eng.synchronize()
-    assert counts.cpu().tolist() == [n, -2] and same(sums[:n], want[0]) and untouched(sums[n:], wsum[n:])
+    assert counts.cpu().tolist() == [n, -2] and U.same_bits_or_nan(sums[:n], want[0]) and U.untouched(sums[n:], wsum[n:])
     with pytest.raises(ValueError, match="rows"):
         crate.field_tensors(values[:n - 1])
 
 
 def test_summing_changes_nothing(sc):
     def trajectory(summing):
-        crate = sc.Crate(world(sc))
-        probes = tensor(np.random.RandomState(9).rand(50, 2), 2) if summing else None
+        crate = sc.Crate(U.scene(sc))
+        probes = U.tensor(np.random.RandomState(9).rand(50, 2), 2) if summing else None
         for _ in range(30):
             crate.physics_tick()
             if summing:
@@ -369,47 +316,47 @@ def test_summing_changes_nothing(sc):
 def test_state_errors_and_the_slab(sc):
     import torch
     from sand_crate_amd import _native as N
-    crate = sc.Crate(world(sc), noise="none", capacity=512)
+    crate = sc.Crate(U.scene(sc), noise="none", capacity=512)
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     points, radius = K.cases()["n_65"]
-    t = tensor(points, 2)
+    t = U.tensor(points, 2)
     offsets = torch.zeros(eng.capacity + 1, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     values = torch.zeros((eng.capacity, 2), dtype=torch.float64, device=dev)
-    sums, out = full((eng.capacity, 2), dev, SENTINEL_F), full(2, dev)
+    sums, out = U.full((eng.capacity, 2), dev, U.SENTINEL_F), U.full(2, dev)
     torch.cuda.synchronize()
-    assert code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE          # no count yet
-    assert code_of(eng.pairs_sum, values, sums, queries=t, counts=out) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE          # no count yet
+    assert U.code_of(eng.pairs_sum, values, sums, queries=t, counts=out) == N.ERR_STATE
     eng.synchronize()
-    assert untouched(sums, out)
+    assert U.untouched(sums, out)
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_sum(values, sums, counts=out)                                         # ... with one: fine, and again
     eng.pairs_sum(values, sums, queries=t, counts=out)
     crate.particles = points                                                        # an upload since the count
-    assert code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
     eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_sum(values, sums, counts=out)
     eng.append(points[:3] + 2.0, np.zeros((3, 2)))                                  # an append since the count
-    assert code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
+    assert U.code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
     eng.synchronize()
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     crate._send_tick_inputs()                                                       # inside a tick
     eng.step_begin()
     try:
-        assert code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
+        assert U.code_of(eng.pairs_sum, values, sums, counts=out) == N.ERR_STATE
     finally:
         eng.step_finish()
     # a slab context has no state form -- the count refuses it, as before --, but sums over a caller's points
     slab = sc.Engine(capacity=256)
     slab.set_slab(0, 50, 3, False, True)
-    assert code_of(slab.pairs_count, None, radius=radius, offsets=offsets[:257], counts=counts) == N.ERR_STATE
-    assert code_of(slab.pairs_sum, values, sums, counts=out) == N.ERR_STATE
-    own = tensor(FK.make_values(3, 65, 2))
+    assert U.code_of(slab.pairs_count, None, radius=radius, offsets=offsets[:257], counts=counts) == N.ERR_STATE
+    assert U.code_of(slab.pairs_sum, values, sums, counts=out) == N.ERR_STATE
+    own = U.tensor(FK.make_values(3, 65, 2), None)
     slab.pairs_count(t, radius=radius, offsets=offsets[:66], counts=counts)
     slab.pairs_sum(own, sums[:65], counts=out)
     slab.synchronize()
-    assert same(sums[:65], FS.field(points, radius, own.cpu().numpy())[0])
+    assert U.same_bits_or_nan(sums[:65], FS.field(points, radius, own.cpu().numpy())[0])
     slab.close()
 
 
@@ -421,10 +368,10 @@ def test_argument_and_capacity_errors(sc):
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
     points = np.random.RandomState(3).rand(n, 2)
-    t = tensor(points, 2)
-    values = tensor(FK.make_values(4, n, width))
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    sums, wsum, out = full((n, width), dev, SENTINEL_F), full(n, dev, SENTINEL_F), full(2, dev)
+    t = U.tensor(points, 2)
+    values = U.tensor(FK.make_values(4, n, width), None)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    sums, wsum, out = U.full((n, width), dev, U.SENTINEL_F), U.full(n, dev, U.SENTINEL_F), U.full(2, dev)
     torch.cuda.synchronize()
     eng.pairs_count(t, radius=0.05, offsets=offsets, counts=counts)
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
@@ -449,7 +396,7 @@ def test_argument_and_capacity_errors(sc):
     assert fn(*args(room=n - 1)) == N.ERR_CAPACITY                                  # short sums, self form
     assert fn(*args(q=ptr(t), nq=n, room=n - 1)) == N.ERR_CAPACITY                  # ... and for the queries
     assert fn(*args(q=ptr(t), nq=(1 << 28) + 1, room=(1 << 28) + 1)) == N.ERR_CAPACITY
-    assert code_of(eng.pairs_sum, values, sums[:n - 1], counts=out) == N.ERR_CAPACITY
+    assert U.code_of(eng.pairs_sum, values, sums[:n - 1], counts=out) == N.ERR_CAPACITY
     assert lib.sc_last_error()
     for call in (lambda: eng.pairs_sum(values, sums, power=4, counts=out), lambda: eng.pairs_sum(values, None, wsum, counts=out),
                  lambda: eng.pairs_sum(None, None, None, counts=out), lambda: eng.pairs_sum(values, sums[:, :2], counts=out),
@@ -457,13 +404,13 @@ def test_argument_and_capacity_errors(sc):
         with pytest.raises(ValueError):
             call()
     eng.synchronize()
-    assert untouched(sums, wsum, out)
+    assert U.untouched(sums, wsum, out)
     assert fn(*args(wsum=None)) == 0                                                # without the weight sums: fine
     assert fn(*args(q=ptr(t), nq=10, room=10, sums=None, v=None, c=0, flags=N.FIELDS_SELF)) == 0   # wsum alone, few queries
     eng.synchronize()
     want = FS.field(points, 0.05, values.cpu().numpy(), 3, False)
-    assert same(sums, want[0])
-    assert same(wsum[:10], FS.field(points, 0.05, None, 3, True, points[:10])[1]) and untouched(wsum[10:])
+    assert U.same_bits_or_nan(sums, want[0])
+    assert U.same_bits_or_nan(wsum[:10], FS.field(points, 0.05, None, 3, True, points[:10])[1]) and U.untouched(wsum[10:])
     eng.close()
 
 
@@ -473,7 +420,7 @@ def test_argument_and_capacity_errors(sc):
 def test_sync_false_does_not_synchronise_and_equals_the_default(crate, monkeypatch, name):
     import torch
     case = FK.cases()[name]
-    values, points, queries = tensor(case.values), tensor(case.points, 2), tensor(case.queries, 2)
+    values, points, queries = U.tensor(case.values, None), U.tensor(case.points, 2), U.tensor(case.queries, 2)
     kw = dict(power=case.power, include_self=case.include_self, points=points, queries=queries, weight_sums=True)
     want = crate.field_tensors(values, case.radius, **kw)
     rows = len(want[-1])

@@ -18,18 +18,13 @@ import pytest
 
 import force_cases as fc
 import test_force_cases_cpu as premises
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 COEF = ("dt", "particle_radius", "wall_collision_decay", "pressure_amplifier", "ignored_pressure",
         "collider_noise_level", "viscosity", "surface_smoothing", "target_pressure")
 PHASES = ("tension", "gravity", "pressure", "viscosity", "wall_bounce", "continuous_collision")
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 class Blocks:

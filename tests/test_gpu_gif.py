@@ -7,22 +7,17 @@ from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
 import gif_cases as K
 import gif_spec as G
+import gpu_support as U
 import render_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 CASES = K.cases()
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 @pytest.fixture(scope="module")
@@ -32,48 +27,17 @@ def engine(sc):
     eng.close()
 
 
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def m2_crate(sc, n, xy=None):
-    """bench.py's M2 inputs: n uniform particles (or those at `xy`) in the wave_machine world, spacing scaled to n, no
-    sources."""
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * n)))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
-    wc.particle_sources = []
-    rs = np.random.RandomState(1234)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles = rs.rand(n, 2) * 0.96 + 0.02 if xy is None else xy
-    crate.particle_velocities = (rs.rand(n, 2) - 0.5) * 0.1
-    return crate
-
-
-def same(got: bytes, want: bytes):
-    if got != want:
-        n = min(len(got), len(want))
-        first = next((k for k in range(n) if got[k] != want[k]), n)
-        raise AssertionError(f"{len(got)} bytes vs {len(want)}, first difference at byte {first}")
-
-
-def spec_frame(crate, width, height, **kw):
-    xy, _, pressure, ids = crate.engine.download()
-    seg = crate.segments if crate.rigid_bodies else np.zeros((0, 2, 2))
-    return S.render(xy, pressure, ids, seg, width, height, crate.particle_radius, **kw)
-
-
 def spec_data(crate, width, height, **kw):
-    return G.image_data(G.indices(spec_frame(crate, width, height, **kw)))
+    return G.image_data(G.indices(U.spec_frame(crate, width, height, **kw)))
 
 
 @pytest.fixture(scope="module")
 def wave(sc):
     """The wave_machine scene after 40 ticks, and the specification's indices of its frame at three sizes."""
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     for _ in range(40):
         crate.physics_tick()
-    idx = {size: G.indices(spec_frame(crate, *size)) for size in ((200, 150), (300, 200), (1000, 1000))}
+    idx = {size: G.indices(U.spec_frame(crate, *size)) for size in ((200, 150), (300, 200), (1000, 1000))}
     for a in idx.values():
         a.setflags(write=False)
     return crate, idx
@@ -84,9 +48,9 @@ def test_every_case(engine, name):
     import torch
     idx = CASES[name]
     want = G.image_data(idx)
-    same(engine.encode_gif(np.array(idx)), want)
+    U.same_stream(engine.encode_gif(np.array(idx)), want)
     t = torch.from_numpy(np.array(idx)).cuda()
-    same(engine.encode_gif(t), want)
+    U.same_stream(engine.encode_gif(t), want)
 
 
 def test_rendered_index_images(engine, wave):
@@ -96,10 +60,10 @@ def test_rendered_index_images(engine, wave):
         a = idx[size]
         assert a.shape == (size[1], size[0]) and len(np.unique(a)) > 2
         want = G.image_data(a)
-        same(engine.encode_gif(np.array(a)), want)
-        same(engine.encode_gif(torch.from_numpy(np.array(a)).cuda()), want)
+        U.same_stream(engine.encode_gif(np.array(a)), want)
+        U.same_stream(engine.encode_gif(torch.from_numpy(np.array(a)).cuda()), want)
     # back to a small frame: the workspace and the host buffer stay at the largest size asked for
-    same(engine.encode_gif(np.array(CASES["size_1x1"])), G.image_data(CASES["size_1x1"]))
+    U.same_stream(engine.encode_gif(np.array(CASES["size_1x1"])), G.image_data(CASES["size_1x1"]))
     with pytest.raises(ValueError):
         engine.encode_gif(np.zeros((4, 4, 3), dtype=np.uint8))
     with pytest.raises(ValueError):
@@ -108,11 +72,11 @@ def test_rendered_index_images(engine, wave):
 
 def test_wave_machine_render_gif(wave):
     crate, idx = wave
-    same(crate.render_gif(200, 150), G.image_data(idx[(200, 150)]))
-    same(crate.render_gif(1000, 1000), G.image_data(idx[(1000, 1000)]))
+    U.same_stream(crate.render_gif(200, 150), G.image_data(idx[(200, 150)]))
+    U.same_stream(crate.render_gif(1000, 1000), G.image_data(idx[(1000, 1000)]))
     # zoomed and off centre, a frame whose pixel count is not a multiple of four
     kw = dict(zoom=2.5, center=(50.0, 120.0), segment_width=3)
-    same(crate.render_gif(211, 151, **kw), spec_data(crate, 211, 151, **kw))
+    U.same_stream(crate.render_gif(211, 151, **kw), spec_data(crate, 211, 151, **kw))
     # and what comes out is a GIF of that frame
     frames, pal, _, _ = G.decode(G.header(200, 150) + G.frame(200, 150, crate.render_gif(200, 150)) + b"\x3B")
     want = crate.render(200, 150)
@@ -121,23 +85,23 @@ def test_wave_machine_render_gif(wave):
 
 
 def test_stirring_cup_render_gif(sc):
-    crate = sc.Crate(scene(sc, "stirring_cup"))
+    crate = sc.Crate(U.scene(sc, "stirring_cup"))
     for _ in range(30):
         crate.physics_tick()
-    same(crate.render_gif(200, 150), spec_data(crate, 200, 150))
+    U.same_stream(crate.render_gif(200, 150), spec_data(crate, 200, 150))
 
 
 def test_empty_crate(sc):
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
+    wc = copy.deepcopy(U.scene(sc, "wave_machine"))
     wc.particle_sources = []
     crate = sc.Crate(wc)
     crate.physics_tick()
     assert crate.particle_count == 0
-    same(crate.render_gif(200, 150), spec_data(crate, 200, 150))
+    U.same_stream(crate.render_gif(200, 150), spec_data(crate, 200, 150))
     wc.rigid_bodies = []
     bare = sc.Crate(wc)
     data = bare.render_gif(64, 48)
-    same(data, G.image_data(np.zeros((48, 64), dtype=np.uint8)))
+    U.same_stream(data, G.image_data(np.zeros((48, 64), dtype=np.uint8)))
 
 
 def test_pressures_of_one_and_above(sc):
@@ -148,19 +112,19 @@ def test_pressures_of_one_and_above(sc):
     rs = np.random.RandomState(8)
     xy = rs.rand(n, 2) * 0.96 + 0.02
     xy[: n // 2] = 0.35 + 0.3 * rs.rand(n // 2, 2)  # half of them ten times as dense
-    crate = m2_crate(sc, n, xy)
+    crate = U.m2_crate(sc, n, xy)
     crate.physics_tick()
     pressure = crate.engine.download()[2]
     assert (pressure >= 1.0).any() and (pressure < 1.0 / 255).any()
-    frame = spec_frame(crate, 200, 150)
+    frame = U.spec_frame(crate, 200, 150)
     idx = G.indices(frame)
     assert ((frame[..., 0] == 0) & (frame[..., 2] == 255)).any() and (idx == 1).any()
-    same(crate.render_gif(200, 150), G.image_data(idx))
+    U.same_stream(crate.render_gif(200, 150), G.image_data(idx))
 
 
 def test_encoding_is_read_only(sc):
     def trajectory(encode):
-        crate = sc.Crate(scene(sc, "wave_machine"))
+        crate = sc.Crate(U.scene(sc, "wave_machine"))
         for _ in range(20):
             crate.physics_tick()
             if encode:
@@ -214,7 +178,7 @@ def test_capacity_and_argument_errors(sc, engine):
     assert lib.sc_gif_encode_device(None, N._P(dev.data_ptr()), w, h, N._P(buf.ctypes.data), len(buf), ctypes.byref(n)) == \
         N.ERR_ARG
 
-    crate = m2_crate(sc, 4096)
+    crate = U.m2_crate(sc, 4096)
     crate.physics_tick()
     eng = crate.engine
     view = eng.view(64, 64, crate.particle_radius)
@@ -238,21 +202,11 @@ def test_capacity_and_argument_errors(sc, engine):
     assert render(len(out)) == 0 and out[:n.value].tobytes() == crate.render_gif(64, 64)
 
 
-def small_screen_config(tmp_path, width=160, height=120) -> Path:
-    with open(ROOT / "config" / "wave_machine.yaml") as f:
-        cfg = yaml.safe_load(f)
-    cfg["playback"].update(screen_x=width, screen_y=height)
-    path = tmp_path / "small_screen.yaml"
-    with open(path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    return path
-
-
 def check_video_gif(sc, out: Path, ticks, width=160, height=120):
     frames, pal, delays, loop = G.decode((out / "video.gif").read_bytes())
     assert len(frames) == len(ticks) and delays == [1] * len(ticks) and loop == 0
     assert np.array_equal(pal, G.palette())
-    r = scene(sc, "wave_machine").coefficients["particle_radius"]
+    r = U.scene(sc, "wave_machine").coefficients["particle_radius"]
     want = []
     with np.load(out / "state.npz") as st:
         assert st["ticks"].tolist() == ticks
@@ -266,7 +220,7 @@ def check_video_gif(sc, out: Path, ticks, width=160, height=120):
 
 def test_headless_driver_streams_video_gif(sc, tmp_path):
     from sand_crate_amd.main import main
-    cfg = small_screen_config(tmp_path)
+    cfg = U.small_screen_config(tmp_path)
     ticks = [10, 20, 30, 40]
     main(cfg, tmp_path / "gif", variants=1, ticks=40, record_every=10, gif=True)
     out = tmp_path / "gif" / "variant_00"

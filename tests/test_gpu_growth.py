@@ -13,8 +13,10 @@ import numpy as np
 import pytest
 
 import force_cases as fc
+import gpu_support as U
 import growth_cases as G
 from conftest import load_golden
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +24,6 @@ CASES = G.cases()
 NOISES = ("none", "counter", "host-sync")
 HUD = "grown\ncrate"
 ARROWS = [[[0.2, 0.2], [0.3, 0.0]], [[0.8, 0.7], [0.0, -0.3]]]
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def make_crate(sc, case, noise, capacity):
@@ -57,11 +53,6 @@ def set_flows(sources, case, tick, since=None):
 def tick(crate, case):
     set_flows(crate.particle_sources, case, crate.tick)
     crate.physics_tick()
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def final_state(crate):
@@ -134,7 +125,7 @@ def test_every_capacity_matches_the_oracle_and_the_ample_one(sc, name, noise):
     assert len(finals[-1][0]) > 200
     for got in finals[:-1]:
         for a, b in zip(got, finals[-1]):
-            same_bytes(a, b)
+            U.same_bytes(a, b)
 
 
 # ------------------------------------------------------------------ against the reference
@@ -211,7 +202,7 @@ def test_add_ons_across_two_growths(sc, spy):
     # observe: the tick column runs on; the whole log is the twin's
     assert grown["obs"]["tick"].tolist() == list(range(1, case.ticks + 1)) and grown["obs"]["dropped"] == 0
     for name in (*probe_spec.FIELDS, "count", "top"):
-        same_bytes(grown["obs"][name], twin["obs"][name])
+        U.same_bytes(grown["obs"][name], twin["obs"][name])
     # track(every=3): the phase runs on; the frames are the twin's
     frames, dropped = grown["tracked"]
     assert dropped == 0 and [track_spec.header(f)["tick"] for f in frames] == list(range(3, case.ticks + 1, 3))
@@ -228,14 +219,14 @@ def test_add_ons_across_two_growths(sc, spy):
     # show_kernel_times: the new contexts time their launches
     assert len(grown["launches"]) == case.ticks and all(n > 0 for n in grown["launches"])
     # the HUD and the arrows are on a frame rendered after the growths
-    same_bytes(grown["frame"], twin["frame"])
-    same_bytes(grown["bare"], twin["bare"])
+    U.same_bytes(grown["frame"], twin["frame"])
+    U.same_bytes(grown["bare"], twin["bare"])
     green = (grown["frame"] == (0, 255, 0)).all(axis=-1)
     assert green.sum() > 20 and not (grown["bare"] == (0, 255, 0)).all(axis=-1).any()
     white = (grown["frame"] == 255).all(axis=-1) & ~(grown["bare"] == 255).all(axis=-1)
     assert white.sum() > 40                                       # the text's ink
     for a, b in zip(final_state(grown["crate"]), final_state(twin["crate"])):
-        same_bytes(a, b)
+        U.same_bytes(a, b)
 
 
 # ------------------------------------------------------------------ checkpoints
@@ -269,7 +260,7 @@ def test_checkpoint_after_the_second_growth_continues_the_run(sc, tmp_path):
             tick(again, case)
         assert again.measure()["tick"] == crate.measure()["tick"] == second + 7
         for a, b in zip(want, final_state(again)):
-            same_bytes(a, b)
+            U.same_bytes(a, b)
 
 
 def test_checkpoint_begun_before_a_growth_is_finished_after_it(sc, tmp_path):
@@ -292,7 +283,7 @@ def test_checkpoint_begun_before_a_growth_is_finished_after_it(sc, tmp_path):
     assert meta == twin_meta and meta["tick"] == meta["engine_tick"] == first
     assert sorted(arrays) == sorted(twin_arrays) and len(arrays["ids"]) > 8
     for name in arrays:
-        same_bytes(arrays[name], twin_arrays[name])
+        U.same_bytes(arrays[name], twin_arrays[name])
 
 
 # ------------------------------------------------------------------ crate.particles = more than the capacity
@@ -314,7 +305,7 @@ def test_set_state_growth_equals_a_crate_with_the_room(sc):
     assert last == twin_last == case.ticks_before + case.ticks_after   # the tick comes from the old context, as without a growth
     for got, want in zip(states, twin_states):
         for a, b in zip(got, want):
-            same_bytes(a, b)
+            U.same_bytes(a, b)
     # the first tick after the replacement starts from a state the oracle knows exactly
     t, out, _ = list(G.run_set_state(case))[case.ticks_before]
     gp, gv, gpr, gids = states[0]
@@ -345,7 +336,7 @@ def test_load_state_tensors_growth_equals_a_crate_with_the_room(sc):
         assert crate.measure()["tick"] == case.ticks_before + 2
         finals.append(final_state(crate))
     for a, b in zip(*finals):
-        same_bytes(a, b)
+        U.same_bytes(a, b)
 
 
 # ------------------------------------------------------------------ what the engine was told
@@ -386,4 +377,4 @@ def test_engine_settings_hold_after_a_growth(sc, monkeypatch):
             crate.engine.use_own_stream()
     assert crate.engine.stream is None and n == len(case.second)
     for a, b in zip(got, crate.engine.download()):
-        same_bytes(a, b)
+        U.same_bytes(a, b)

@@ -5,74 +5,25 @@ the other readers; the state form after ticks and the invalidation rule; capacit
 the status and nothing else; the workspace of the count is left as it is; the half flag is ignored; a last edge below the
 count's radius; the error codes."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as U
 import hist_cases as HK
 import hist_spec as HS
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
 CASES = sorted(HK.cases())
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(a):
-    import torch
-    if a is None:
-        return None
-    t = torch.from_numpy(np.array(a, dtype=np.float64).reshape(-1, 2)).cuda()      # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
-    return t
-
-
-def full(shape, device, dtype=None):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), SENTINEL, dtype=dtype or torch.int64, device=device)
-
-
-def untouched(*tensors):
-    return all(bool((t == SENTINEL).all()) for t in tensors)
-
-
-def same(got, want):
-    g = got.cpu().numpy()
-    return g.dtype == want.dtype and g.shape == want.shape and np.array_equal(g, want)
 
 
 @functools.lru_cache(maxsize=None)
 def spec(name, query_form):
     case = HK.cases()[name]
     return HS.histogram(case.points, case.edges, HK.queries_of(case) if query_form else case.queries)
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
 
 
 def through_the_engine(eng, points, edges, queries=None, *, radius=None, half=False, spare=8, table=True, total=True):
@@ -83,10 +34,10 @@ def through_the_engine(eng, points, edges, queries=None, *, radius=None, half=Fa
     n = len(points)
     rows = n if queries is None else len(queries)
     bins = len(edges) - 1
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    tb = full((rows + spare, bins), dev, torch.int32) if table else None
-    tt = full(bins, dev) if total else None
-    t, q = tensor(points), tensor(queries)                                          # (alive until the synchronisation)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    tb = U.full((rows + spare, bins), dev, dtype=torch.int32) if table else None
+    tt = U.full(bins, dev) if total else None
+    t, q = U.tensor(points), U.tensor(queries)                                          # (alive until the synchronisation)
     eng.pairs_count(t, radius=float(edges[-1]) if radius is None else radius, offsets=offsets, counts=counts, half=half)
     assert eng.pairs_hist(tb, tt, edges=edges, queries=q, counts=out) is out
     eng.synchronize()
@@ -103,22 +54,22 @@ def test_case_equals_the_spec(crate, name, query_form):
     queries = HK.queries_of(case) if query_form else case.queries
     want_table, want_total = spec(name, query_form)
     rows = len(want_table)
-    points, q = tensor(case.points), tensor(queries)
+    points, q = U.tensor(case.points), U.tensor(queries)
     table, total = crate.distance_histogram(case.edges, points=points, queries=q, per_row=True)
-    assert table.is_cuda and total.is_cuda and same(table, want_table) and same(total, want_total)
+    assert table.is_cuda and total.is_cuda and U.same_bits(table, want_table) and U.same_bits(total, want_total)
     assert torch.equal(total, table.sum(0))
     only, = crate.distance_histogram(case.edges, points=points, queries=q)
-    assert same(only, want_total)
+    assert U.same_bits(only, want_total)
     rows_only, = crate.distance_histogram(list(case.edges), points=points, queries=q, per_row=True, totals=False)
-    assert same(rows_only, want_table)
+    assert U.same_bits(rows_only, want_table)
     out = crate.distance_histogram(case.edges, points=points, queries=q, per_row=True, sync=False)
     crate.synchronize()
     assert len(out) == 3 and out[2].cpu().tolist() == [rows, 0]
-    assert same(out[0][:rows], want_table) and same(out[1], want_total)
+    assert U.same_bits(out[0][:rows], want_table) and U.same_bits(out[1], want_total)
     for half in (False, True):
         tb, tt, counts = through_the_engine(crate.engine, case.points, case.edges, queries, half=half, total=half)
         assert counts.cpu().tolist() == [rows, 0]
-        assert same(tb[:rows], want_table) and untouched(tb[rows:]) and (tt is None or same(tt, want_total))
+        assert U.same_bits(tb[:rows], want_table) and U.untouched(tb[rows:]) and (tt is None or U.same_bits(tt, want_total))
 
 
 def test_totals_beyond_32_bits(sc):
@@ -126,9 +77,9 @@ def test_totals_beyond_32_bits(sc):
     n = HK.BEYOND_32_BITS
     want = HK.coincident_total(n)
     assert int(want[0]) > 2 ** 32
-    crate = sc.Crate(world(sc), noise="none", capacity=16)
-    total, = crate.distance_histogram([0.0, 0.1], points=tensor(HK.coincident(n)))
-    assert same(total, want)
+    crate = sc.Crate(U.scene(sc), noise="none", capacity=16)
+    total, = crate.distance_histogram([0.0, 0.1], points=U.tensor(HK.coincident(n)))
+    assert U.same_bits(total, want)
 
 
 # ---- 2. one bin is what the other readers count
@@ -137,7 +88,7 @@ def test_one_bin_is_the_partner_count_of_the_table_and_the_list(crate):
     import torch
     from sand_crate_amd import pairs
     case = HK.cases()["bins_16"]
-    points, radius = tensor(case.points), float(case.edges[-1])
+    points, radius = U.tensor(case.points), float(case.edges[-1])
     table, total = crate.distance_histogram([0.0, radius], points=points, per_row=True)
     _, partners = crate.neighbor_tensors(4, radius, points=points, partner_counts=True)
     offsets, listed = crate.pair_tensors(radius, points=points)
@@ -151,7 +102,7 @@ def test_state_after_ticks_and_the_stale_count(sc):
     import torch
     from sand_crate_amd import _native as N
     from sand_crate_amd import pairs
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     for _ in range(50):
         crate.physics_tick()
     edges = pairs.shell_edges(3 * crate.diameter, 24)
@@ -162,39 +113,39 @@ def test_state_after_ticks_and_the_stale_count(sc):
     as_points = crate.distance_histogram(edges, points=particles, per_row=True)
     assert torch.equal(table, as_points[0]) and torch.equal(total, as_points[1])
     want = HS.histogram(particles.cpu().numpy(), edges)
-    assert same(table, want[0]) and same(total, want[1]) and int(total.sum()) > 0
+    assert U.same_bits(table, want[0]) and U.same_bits(total, want[1]) and int(total.sum()) > 0
     g = pairs.radial_distribution(total, edges, n, 1.0)
     assert g.shape == (24,) and bool(torch.isfinite(g).all())
     # a tick since the count: the grid is stale
     eng = crate.engine
     dev = particles.device
-    out, counts = full(24, dev), full(2, dev)
-    offsets = full(eng.capacity + 1, dev)
+    out, counts = U.full(24, dev), U.full(2, dev)
+    offsets = U.full(eng.capacity + 1, dev)
     torch.cuda.synchronize()
     eng.pairs_count(None, radius=float(edges[-1]), offsets=offsets, counts=counts)
     eng.pairs_hist(None, out, edges=edges, counts=counts)
     eng.synchronize()
-    assert same(out, want[1])
+    assert U.same_bits(out, want[1])
     crate.physics_tick()
-    assert code_of(eng.pairs_hist, None, out, edges=edges, counts=counts) == N.ERR_STATE
-    assert code_of(eng.pairs_hist, None, out, edges=edges, queries=particles[:16].contiguous(), counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_hist, None, out, edges=edges, counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_hist, None, out, edges=edges, queries=particles[:16].contiguous(), counts=counts) == N.ERR_STATE
     slab = sc.Engine(capacity=256)
     slab.set_slab(0, 50, 3, False, True)
-    assert code_of(slab.pairs_count, None, radius=0.1, offsets=offsets[:257], counts=counts) == N.ERR_STATE
-    assert code_of(slab.pairs_hist, None, out, edges=edges, counts=counts) == N.ERR_STATE
+    assert U.code_of(slab.pairs_count, None, radius=0.1, offsets=offsets[:257], counts=counts) == N.ERR_STATE
+    assert U.code_of(slab.pairs_hist, None, out, edges=edges, counts=counts) == N.ERR_STATE
     slab.close()
 
 
 def test_the_capacity_does_not_reach_the_result(sc):
     import torch
     case = HK.cases()["far_cells"]
-    points = tensor(case.points)
+    points = U.tensor(case.points)
     results = []
     for capacity in (16, 100_000):
-        crate = sc.Crate(world(sc), noise="none", capacity=capacity)
+        crate = sc.Crate(U.scene(sc), noise="none", capacity=capacity)
         results.append(crate.distance_histogram(case.edges, points=points, per_row=True))
     assert all(torch.equal(a, b) for a, b in zip(*results))
-    assert same(results[0][0], spec("far_cells", False)[0])
+    assert U.same_bits(results[0][0], spec("far_cells", False)[0])
 
 
 # ---- 4. the status
@@ -205,18 +156,18 @@ def test_a_query_outside_writes_the_status_only(crate):
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     tb, tt, counts = through_the_engine(eng, case.points, case.edges, case.queries)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(tb, tt)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(tb, tt)
     # the count's own verdict is unchanged: a fill afterwards succeeds, and so does the next histogram
     want = S.pairs(case.points, case.edges[-1])
-    partners, again = full(len(want[1]), dev), full(2, dev)
+    partners, again = U.full(len(want[1]), dev), U.full(2, dev)
     eng.pairs_fill(partners)
-    tb = full((len(case.points), 3), dev, torch.int32)
+    tb = U.full((len(case.points), 3), dev, dtype=torch.int32)
     eng.pairs_hist(tb, tt, edges=case.edges, counts=again)
     eng.synchronize()
     rule = HS.histogram(case.points, case.edges)
-    assert same(partners, want[1]) and again.cpu().tolist() == [len(case.points), 0]
-    assert same(tb, rule[0]) and same(tt, rule[1])
-    points, q = tensor(case.points), tensor(case.queries)
+    assert U.same_bits(partners, want[1]) and again.cpu().tolist() == [len(case.points), 0]
+    assert U.same_bits(tb, rule[0]) and U.same_bits(tt, rule[1])
+    points, q = U.tensor(case.points), U.tensor(case.queries)
     with pytest.raises(ValueError, match="domain"):
         crate.distance_histogram(case.edges, points=points, queries=q)
     out = crate.distance_histogram(case.edges, points=points, queries=q, per_row=True, sync=False)
@@ -226,7 +177,7 @@ def test_a_query_outside_writes_the_status_only(crate):
     far = case.points.copy()
     far[7, 1] = -(2.0 ** 32) * case.edges[-1]
     tb, tt, counts = through_the_engine(eng, far, case.edges)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(tb, tt)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(tb, tt)
 
 
 # ---- 5. the workspace is left as it is; the half flag; a shorter last edge
@@ -240,13 +191,13 @@ def test_fill_hist_fill(crate, half):
     n = len(case.points)
     want = S.pairs(case.points, case.edges[-1], half)
     k = len(want[1])
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    before, after = (full(k, dev), torch.full((k,), -1.5, dtype=torch.float64, device=dev)), \
-                    (full(k, dev), torch.full((k,), -1.5, dtype=torch.float64, device=dev))
-    tb, tt = full((n, 33), dev, torch.int32), full(33, dev)
-    probes = tensor(case.points[:40] + 0.01)
-    probe_table = full((40, 33), dev, torch.int32)
-    t = tensor(case.points)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    before, after = (U.full(k, dev), torch.full((k,), -1.5, dtype=torch.float64, device=dev)), \
+                    (U.full(k, dev), torch.full((k,), -1.5, dtype=torch.float64, device=dev))
+    tb, tt = U.full((n, 33), dev, dtype=torch.int32), U.full(33, dev)
+    probes = U.tensor(case.points[:40] + 0.01)
+    probe_table = U.full((40, 33), dev, dtype=torch.int32)
+    t = U.tensor(case.points)
     eng.pairs_count(t, radius=float(case.edges[-1]), offsets=offsets, counts=counts, half=half)
     eng.pairs_fill(*before)
     eng.pairs_hist(tb, tt, edges=case.edges, counts=out)
@@ -255,16 +206,16 @@ def test_fill_hist_fill(crate, half):
     eng.pairs_fill(*after)
     eng.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(before, after))
-    assert same(after[0], want[1]) and same(after[1], want[2])
+    assert U.same_bits(after[0], want[1]) and U.same_bits(after[1], want[2])
     rule = spec("bins_33", False)
-    assert same(tb, rule[0]) and same(tt, rule[1])                                  # the half flag is ignored
-    assert same(probe_table, HS.histogram(case.points, case.edges, case.points[:40] + 0.01)[0])
+    assert U.same_bits(tb, rule[0]) and U.same_bits(tt, rule[1])                                  # the half flag is ignored
+    assert U.same_bits(probe_table, HS.histogram(case.points, case.edges, case.points[:40] + 0.01)[0])
 
 
 def test_pair_tensors_are_the_same_before_and_after(crate):
     import torch
     case = HK.cases()["bins_17"]
-    points, radius = tensor(case.points), float(case.edges[-1])
+    points, radius = U.tensor(case.points), float(case.edges[-1])
     before = crate.pair_tensors(radius, points=points, squared_distances=True)
     crate.distance_histogram(case.edges, points=points, per_row=True)
     after = crate.pair_tensors(radius, points=points, squared_distances=True)
@@ -279,10 +230,10 @@ def test_a_last_edge_below_the_counts_radius(crate):
     want = HS.histogram(pts, edges)
     assert want[1].sum() > 0
     for tb, tt, counts in (wide, own):
-        assert counts.cpu().tolist() == [400, 0] and same(tb[:400], want[0]) and same(tt, want[1])
+        assert counts.cpu().tolist() == [400, 0] and U.same_bits(tb[:400], want[0]) and U.same_bits(tt, want[1])
     probes = pts[:70] * 0.5 + 0.2
     wide = through_the_engine(crate.engine, pts, edges, probes, radius=0.1)
-    assert same(wide[0][:70], HS.histogram(pts, edges, probes)[0])
+    assert U.same_bits(wide[0][:70], HS.histogram(pts, edges, probes)[0])
 
 
 # ---- 6. errors
@@ -295,9 +246,9 @@ def test_argument_and_capacity_errors(sc):
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
     points = np.random.RandomState(3).rand(n, 2)
-    t = tensor(points)
-    offsets, counts = full(n + 1, dev), full(2, dev)
-    table, total, out = full((n, bins), dev, torch.int32), full(bins, dev), full(2, dev)
+    t = U.tensor(points)
+    offsets, counts = U.full(n + 1, dev), U.full(2, dev)
+    table, total, out = U.full((n, bins), dev, dtype=torch.int32), U.full(bins, dev), U.full(2, dev)
     edges = np.linspace(0.0, 0.05, bins + 1)
     torch.cuda.synchronize()
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
@@ -328,7 +279,7 @@ def test_argument_and_capacity_errors(sc):
     assert fn(*args(room=n - 1)) == N.ERR_CAPACITY                                  # a short table, self form
     assert fn(*args(q=ptr(t), nq=n, room=n - 1)) == N.ERR_CAPACITY                  # ... and for the queries
     assert fn(*args(q=ptr(t), nq=(1 << 28) + 1, room=(1 << 28) + 1)) == N.ERR_CAPACITY
-    assert code_of(eng.pairs_hist, table[:n - 1], total, edges=edges, counts=out) == N.ERR_CAPACITY
+    assert U.code_of(eng.pairs_hist, table[:n - 1], total, edges=edges, counts=out) == N.ERR_CAPACITY
     assert lib.sc_last_error()
     for call in (lambda: eng.pairs_hist(None, None, edges=edges, counts=out), lambda: eng.pairs_hist(table, total[:4], edges=edges, counts=out),
                  lambda: eng.pairs_hist(table[:, :4], total, edges=edges, counts=out), lambda: eng.pairs_hist(table.long(), total, edges=edges, counts=out),
@@ -337,17 +288,17 @@ def test_argument_and_capacity_errors(sc):
         with pytest.raises(ValueError):
             call()
     eng.synchronize()
-    assert untouched(table, total, out)
+    assert U.untouched(table, total, out)
     assert fn(*args(total=None)) == 0                                               # the table alone: fine
     assert fn(*args(table=None, room=0)) == 0                                       # the totals alone need no room
     eng.synchronize()
     want = HS.histogram(points, edges)
-    assert same(table, want[0]) and same(total, want[1]) and out.cpu().tolist() == [n, 0]
+    assert U.same_bits(table, want[0]) and U.same_bits(total, want[1]) and out.cpu().tolist() == [n, 0]
     eng.close()
 
 
 def test_wrapper_errors(crate):
-    points = tensor(HK.cases()["rows_65"].points)
+    points = U.tensor(HK.cases()["rows_65"].points)
     for call in (lambda: crate.distance_histogram([0.0, 0.1], points=points, totals=False),
                  lambda: crate.distance_histogram([0.1, 0.0], points=points), lambda: crate.distance_histogram([0.0], points=points),
                  lambda: crate.distance_histogram(np.linspace(0, 1, 66), points=points),

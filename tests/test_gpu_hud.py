@@ -2,17 +2,17 @@
 `render_gif`, `main --hud`): a frame with a HUD equals tests/text_spec.py's `draw` of the frame without one bit for bit,
 its JPEG and GIF equal tests/jpeg_spec.py and tests/gif_spec.py of that frame byte for byte, clearing brings the plain
 frame back, and drawing changes nothing in the simulation."""
-import copy
 from pathlib import Path
 
 import numpy as np
 import pytest
-import yaml
 
 import gif_spec as G
+import gpu_support as U
 import hud_cases as K
 import jpeg_spec as J
 import text_spec as T
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,26 +22,12 @@ VIEW = dict(segment_width=20)  # thick walls: the frame's edge is white ten pixe
 
 
 @pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-@pytest.fixture(scope="module")
 def crate(sc):
     """400 particles all over the wave_machine world after one tick (so they have pressures), discs of a few pixels
     at the frame sizes used here."""
     n = 400
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * n)))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
-    wc.particle_sources = []
     rs = np.random.RandomState(77)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
+    crate = sc.Crate(U.spread_world(sc, n), noise="counter", noise_seed=1, capacity=n + 1024)
     crate.particles = rs.rand(n, 2) * 0.96 + 0.02
     crate.particle_velocities = (rs.rand(n, 2) - 0.5) * 0.1
     crate.physics_tick()
@@ -56,20 +42,6 @@ def plain(crate):
     for f in frames.values():
         f.setflags(write=False)
     return frames
-
-
-def same(got: bytes, want: bytes):
-    if got != want:
-        n = min(len(got), len(want))
-        first = next((k for k in range(n) if got[k] != want[k]), n)
-        raise AssertionError(f"{len(got)} bytes vs {len(want)}, first difference at byte {first}")
-
-
-def same_frame(got, want):
-    assert got.shape == want.shape and got.dtype == want.dtype
-    if not np.array_equal(got, want):
-        bad = np.argwhere((got != want).any(axis=-1))
-        raise AssertionError(f"{len(bad)} pixels differ, the first at row {bad[0][0]}, column {bad[0][1]}")
 
 
 def test_the_scene_puts_something_under_the_text(plain):
@@ -96,11 +68,11 @@ def test_every_case(crate, plain, name):
     finally:
         eng.set_hud(None)
     want = T.draw(base, c.text, c.x, c.y, c.scale)
-    same_frame(got, want)
-    same(data, G.image_data(G.indices(want)))
+    U.same_frame(got, want)
+    U.same_stream(data, G.image_data(G.indices(want)))
     if c.box == (0, 0):
-        same_frame(got, base)
-    same_frame(crate.render(c.width, c.height, **VIEW), base)  # cleared
+        U.same_frame(got, base)
+    U.same_frame(crate.render(c.width, c.height, **VIEW), base)  # cleared
 
 
 def test_unaligned_device_frame(crate, plain):
@@ -115,12 +87,12 @@ def test_unaligned_device_frame(crate, plain):
     text = c.text.decode()
     assert crate.render(w, h, out=out, hud=text, **VIEW) is out
     crate.synchronize()
-    same_frame(out.cpu().numpy(), T.draw(plain[(w, h)], c.text, 6, 6, 1))
+    U.same_frame(out.cpu().numpy(), T.draw(plain[(w, h)], c.text, 6, 6, 1))
     got = buf.cpu().numpy()
     assert got[0] == 0 and not got[1 + 3 * w * h:].any()  # nothing outside the frame
     assert crate.render(w, h, out=out, **VIEW) is out  # and without: the plain frame again
     crate.synchronize()
-    same_frame(out.cpu().numpy(), plain[(w, h)])
+    U.same_frame(out.cpu().numpy(), plain[(w, h)])
 
 
 def test_render_gif_with_hud(crate, plain):
@@ -129,25 +101,25 @@ def test_render_gif_with_hud(crate, plain):
     text = c.text.decode()
     want = G.indices(T.draw(plain[(w, h)], c.text, 6, 6, 1))
     data = crate.render_gif(w, h, hud=text, **VIEW)
-    same(data, G.image_data(want))
+    U.same_stream(data, G.image_data(want))
     frames, _, _, _ = G.decode(G.header(w, h) + G.frame(w, h, data) + b"\x3B")
     ink = T.ink(c.text, 6, 6, 1, w, h)
     assert (frames[0][ink] == 255).all()
     assert np.array_equal(frames[0] == 255, ink | (G.indices(plain[(w, h)]) == 255))  # index 255: the ink and the walls
-    same(crate.render_gif(w, h, **VIEW), G.image_data(G.indices(plain[(w, h)])))
+    U.same_stream(crate.render_gif(w, h, **VIEW), G.image_data(G.indices(plain[(w, h)])))
 
 
 def test_render_jpeg_with_hud(crate, plain):
     c = CASES["odd"]
     w, h = c.width, c.height
     for q in (95, 50):
-        same(crate.render_jpeg(w, h, quality=q, hud=c.text.decode(), **VIEW),
-             J.encode(T.draw(plain[(w, h)], c.text, 6, 6, 1), q))
-    same(crate.render_jpeg(w, h, **VIEW), J.encode(plain[(w, h)], 95))
+        U.same_stream(crate.render_jpeg(w, h, quality=q, hud=c.text.decode(), **VIEW),
+                      J.encode(T.draw(plain[(w, h)], c.text, 6, 6, 1), q))
+    U.same_stream(crate.render_jpeg(w, h, **VIEW), J.encode(plain[(w, h)], 95))
 
 
 def test_hud_true_draws_debug_prints(sc):
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     crate.show_forces()
     for _ in range(5):
         crate.physics_tick()
@@ -157,19 +129,19 @@ def test_hud_true_draws_debug_prints(sc):
         base = crate.render(w, h)
         got = crate.render(w, h, hud=True)
         want = T.draw(base, text.encode("ascii", "replace"), 6, 6, T.default_scale(w))
-        same_frame(got, want)
+        U.same_frame(got, want)
         assert (got != base).any()
-        same_frame(crate.render(w, h), base)
+        U.same_frame(crate.render(w, h), base)
     assert T.default_scale(1440) == 2
     crate.physics_tick()  # the text follows the tick
     base = crate.render(200, 150)
     assert crate.debug_prints.startswith("Tick: 6\n")
-    same_frame(crate.render(200, 150, hud=True), T.draw(base, crate.debug_prints.encode("ascii", "replace"), 6, 6, 1))
+    U.same_frame(crate.render(200, 150, hud=True), T.draw(base, crate.debug_prints.encode("ascii", "replace"), 6, 6, 1))
 
 
 def test_drawing_is_read_only(sc):
     def trajectory(draw):
-        crate = sc.Crate(scene(sc, "wave_machine"))
+        crate = sc.Crate(U.scene(sc, "wave_machine"))
         for _ in range(20):
             crate.physics_tick()
             if draw:
@@ -207,16 +179,16 @@ def test_argument_errors(crate, plain):
     with pytest.raises(N.NativeError) as err:
         eng.set_hud(b"ok", scale=0)
     assert err.value.code == N.ERR_ARG
-    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # none of them set anything
+    U.same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # none of them set anything
     # the edges of the ranges are valid, and a valid call afterwards works
     assert call(t=big, n=65536, x=16384, y=16384, scale=64) == 0
-    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # (an origin outside the frame)
+    U.same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])  # (an origin outside the frame)
     assert call(x=0, y=0) == 0
-    same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))
+    U.same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))
     assert call(x=-1) == N.ERR_ARG
-    same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))  # a refused call changes nothing
+    U.same_frame(crate.render(64, 48, **VIEW), T.draw(plain[(64, 48)], text, 0, 0, 1))  # a refused call changes nothing
     assert call(t=None, n=0) == 0  # clears; the text may be null
-    same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])
+    U.same_frame(crate.render(64, 48, **VIEW), plain[(64, 48)])
 
 
 def test_a_new_context_has_no_hud(sc, crate):
@@ -230,19 +202,9 @@ def test_a_new_context_has_no_hud(sc, crate):
         crate.engine.set_hud(None)
 
 
-def small_screen_config(tmp_path, width=160, height=120) -> Path:
-    with open(ROOT / "config" / "wave_machine.yaml") as f:
-        cfg = yaml.safe_load(f)
-    cfg["playback"].update(screen_x=width, screen_y=height)
-    path = tmp_path / "small_screen.yaml"
-    with open(path, "w") as f:
-        yaml.safe_dump(cfg, f)
-    return path
-
-
 def test_headless_driver_with_hud(tmp_path):
     from sand_crate_amd.main import main
-    cfg = small_screen_config(tmp_path)
+    cfg = U.small_screen_config(tmp_path)
     first = {}
     for hud in (False, True):
         out = tmp_path / ("hud" if hud else "plain")

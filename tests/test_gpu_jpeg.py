@@ -1,7 +1,6 @@
 """GPU tests of the JPEG encoder (sc_jpeg_encode_device, sc_render_jpeg, `Crate.render_jpeg`, `main --video`): every file
 equals tests/jpeg_spec.py byte for byte, of the frame tests/render_spec.py draws from what sc_download_state returns at
 the same moment, and encoding changes nothing."""
-import copy
 import ctypes
 import io
 import struct
@@ -10,18 +9,14 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import gpu_support as U
 import jpeg_spec as J
 import render_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 @pytest.fixture(scope="module")
@@ -31,41 +26,11 @@ def engine(sc):
     eng.close()
 
 
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def m2_crate(sc, n):
-    """bench.py's M2 inputs: n uniform particles in the wave_machine world, spacing scaled to n, no sources."""
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * n)))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
-    wc.particle_sources = []
-    rs = np.random.RandomState(1234)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles = rs.rand(n, 2) * 0.96 + 0.02
-    crate.particle_velocities = (rs.rand(n, 2) - 0.5) * 0.1
-    return crate
-
-
-def same(got: bytes, want: bytes):
-    if got != want:
-        n = min(len(got), len(want))
-        first = next((k for k in range(n) if got[k] != want[k]), n)
-        raise AssertionError(f"{len(got)} bytes vs {len(want)}, first difference at byte {first}")
-
-
-def spec_frame(crate, width, height, **kw):
-    xy, _, pressure, ids = crate.engine.download()
-    seg = crate.segments if crate.rigid_bodies else np.zeros((0, 2, 2))
-    return S.render(xy, pressure, ids, seg, width, height, crate.particle_radius, **kw)
-
-
 def test_random_images_at_odd_sizes(engine):
     rs = np.random.RandomState(1)
     for h, w in ((1, 1), (7, 9), (8, 8), (9, 7), (17, 1), (1, 130), (64, 64), (333, 777), (1001, 999)):
         img = rs.randint(0, 256, (h, w, 3)).astype(np.uint8)
-        same(engine.encode_jpeg(img, 75), J.encode(img, 75))
+        U.same_stream(engine.encode_jpeg(img, 75), J.encode(img, 75))
 
 
 def test_noise_at_quality_100(engine):
@@ -75,7 +40,7 @@ def test_noise_at_quality_100(engine):
         img = rs.randint(0, 256, (h, w, 3)).astype(np.uint8)
         data = engine.encode_jpeg(img, 100)
         assert len(data) > 3 * h * w
-        same(data, J.encode(img, 100))
+        U.same_stream(data, J.encode(img, 100))
 
 
 def test_flat_and_extreme_images(engine):
@@ -83,12 +48,12 @@ def test_flat_and_extreme_images(engine):
         img = np.empty((40, 56, 3), dtype=np.uint8)
         img[:] = value
         for q in (1, 100):
-            same(engine.encode_jpeg(img, q), J.encode(img, q))
+            U.same_stream(engine.encode_jpeg(img, q), J.encode(img, q))
     # the largest DC steps: black and white blocks in turn, at quality 100
     img = np.zeros((16, 64, 3), dtype=np.uint8)
     img[:, 8::16] = 255
     img[:, 9:16] = 255
-    same(engine.encode_jpeg(img, 100), J.encode(img, 100))
+    U.same_stream(engine.encode_jpeg(img, 100), J.encode(img, 100))
 
 
 def test_quality_sweep(engine):
@@ -98,52 +63,52 @@ def test_quality_sweep(engine):
     noisy = np.clip(smooth + rs.randint(-20, 21, smooth.shape), 0, 255).astype(np.uint8)
     for q in (1, 2, 10, 25, 49, 50, 51, 75, 90, 95, 99, 100):
         for img in (smooth, noisy):
-            same(engine.encode_jpeg(img, q), J.encode(img, q))
+            U.same_stream(engine.encode_jpeg(img, q), J.encode(img, q))
 
 
 def test_cuda_tensor_input(engine):
     import torch
     img = np.random.RandomState(4).randint(0, 256, (300, 200, 3)).astype(np.uint8)
     t = torch.from_numpy(img).cuda()
-    same(engine.encode_jpeg(t, 90), J.encode(img, 90))
+    U.same_stream(engine.encode_jpeg(t, 90), J.encode(img, 90))
     with pytest.raises(ValueError):
         engine.encode_jpeg(t[:, :, :2].contiguous(), 90)
 
 
 def test_wave_machine_render_jpeg(sc):
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     for _ in range(60):
         crate.physics_tick()
     for q in (95, 50):
-        same(crate.render_jpeg(1000, 1000, quality=q), J.encode(spec_frame(crate, 1000, 1000), q))
-    same(crate.render_jpeg(640, 481, zoom=2.0, center=(100.0, 300.0)),
-         J.encode(spec_frame(crate, 640, 481, zoom=2.0, center=(100.0, 300.0)), 95))
+        U.same_stream(crate.render_jpeg(1000, 1000, quality=q), J.encode(U.spec_frame(crate, 1000, 1000), q))
+    U.same_stream(crate.render_jpeg(640, 481, zoom=2.0, center=(100.0, 300.0)),
+                  J.encode(U.spec_frame(crate, 640, 481, zoom=2.0, center=(100.0, 300.0)), 95))
 
 
 def test_million_particles_at_1000_and_4096(sc):
-    crate = m2_crate(sc, 1048576)
+    crate = U.m2_crate(sc, 1048576)
     crate.physics_tick()
     crate.physics_tick()
     for side in (1000, 4096):
-        same(crate.render_jpeg(side, side), J.encode(spec_frame(crate, side, side), 95))
+        U.same_stream(crate.render_jpeg(side, side), J.encode(U.spec_frame(crate, side, side), 95))
 
 
 def test_device_frame_from_render(sc):
     """sc_jpeg_encode_device on a frame sc_render_device wrote: what Crate.render_jpeg gives."""
     import torch
-    crate = sc.Crate(scene(sc, "stirring_cup"))
+    crate = sc.Crate(U.scene(sc, "stirring_cup"))
     for _ in range(30):
         crate.physics_tick()
     out = torch.zeros((480, 640, 3), dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     crate.render(640, 480, out=out)
     crate.synchronize()
-    same(crate.engine.encode_jpeg(out, 95), crate.render_jpeg(640, 480))
+    U.same_stream(crate.engine.encode_jpeg(out, 95), crate.render_jpeg(640, 480))
 
 
 def test_encoding_is_read_only(sc):
     def trajectory(encode):
-        crate = sc.Crate(scene(sc, "wave_machine"), noise="counter", noise_seed=5)
+        crate = sc.Crate(U.scene(sc, "wave_machine"), noise="counter", noise_seed=5)
         for _ in range(20):
             crate.physics_tick()
             if encode:
@@ -190,7 +155,7 @@ def test_capacity_and_argument_errors(sc, engine):
     assert lib.sc_jpeg_encode_device(ctx, N._P(dev.data_ptr()), 70, 50, 80, N._P(buf.ctypes.data), len(buf), None) == \
         N.ERR_ARG
 
-    crate = m2_crate(sc, 4096)
+    crate = U.m2_crate(sc, 4096)
     crate.physics_tick()
     eng = crate.engine
     view = eng.view(64, 64, crate.particle_radius)
@@ -231,13 +196,13 @@ def test_headless_driver_writes_video(sc, tmp_path):
     out = tmp_path / "variant_00"
     frames = avi_frames(out / "video.avi")
     assert len(frames) == 20
-    r = scene(sc, "wave_machine").coefficients["particle_radius"]
+    r = U.scene(sc, "wave_machine").coefficients["particle_radius"]
     with np.load(out / "state.npz") as st:
         assert st["ticks"].tolist() == list(range(10, 201, 10))
         for k, f in enumerate(frames):
             xy = st[f"particles_{k}"]
             img = S.render(xy, st[f"pressure_{k}"], np.arange(len(xy)), st[f"segments_{k}"], 1000, 1000, r)
-            same(f, J.encode(img, 95))
+            U.same_stream(f, J.encode(img, 95))
     try:
         from PIL import Image
     except ImportError:

@@ -7,9 +7,9 @@ import ctypes
 import numpy as np
 import pytest
 
+import gpu_support as U
 import jpeg_cases as K
 import jpeg_spec as J
-from test_gpu_jpeg import same
 
 pytestmark = pytest.mark.gpu
 
@@ -36,10 +36,10 @@ def test_every_case(engine, want, name):
     from sand_crate_amd import _native as N
     img, q = CASES[name]
     h, w = img.shape[:2]
-    same(engine.encode_jpeg(np.array(img), q), want[name])
+    U.same_stream(engine.encode_jpeg(np.array(img), q), want[name])
     dev = torch.from_numpy(np.array(img)).cuda()
-    same(engine.encode_jpeg(dev, q), want[name])
-    same(engine.encode_jpeg(dev, q), want[name])  # the same device tensor again
+    U.same_stream(engine.encode_jpeg(dev, q), want[name])
+    U.same_stream(engine.encode_jpeg(dev, q), want[name])  # the same device tensor again
     bound, n = ctypes.c_int64(0), ctypes.c_int64(-1)
     assert engine._lib.sc_jpeg_bound(w, h, ctypes.byref(bound)) == 0 and bound.value >= len(want[name])
     torch.cuda.synchronize()
@@ -54,4 +54,4 @@ def test_the_window_and_workspace_are_reused(engine, want, first, second):
     the rows' bit buffers and the output buffer is not the second's."""
     for name in (first, second, first):
         img, q = CASES[name]
-        same(engine.encode_jpeg(np.array(img), q), want[name])
+        U.same_stream(engine.encode_jpeg(np.array(img), q), want[name])

@@ -18,6 +18,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from gpu_support import sc  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -27,14 +29,6 @@ PROBES = np.array([[1.5, 2.0], [4.0, 2.25], [7.75, 2.0]])           # 3 queries
 CLOUDS, PROBE_CLOUDS = [0, 4, 8], [0, 2, 3]                         # two clouds of 4 points; their queries
 CAPACITY = 64
 READS = ("cpu", "item", "tolist", "__int__", "__index__", "__float__", "__bool__")
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 @pytest.fixture(scope="module")

@@ -3,45 +3,15 @@
 on every named case of tests/pairs_cases.py with and without `half`, on the state after real ticks, after a load and on an
 empty crate --, a pair count beyond 31 bits against the closed form, searching changes nothing, `max_pairs` clips and
 writes nothing past the room, the domain error and the error codes."""
-from pathlib import Path
-
 import numpy as np
 import pytest
 
+import gpu_support as U
 import pairs_cases as K
 import pairs_spec as S
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL_I, SENTINEL_F = -777, -12345.5
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    wc = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-    return sc.Crate(wc, noise="none", capacity=256)
-
-
-def tensor(points):
-    import torch
-    t = torch.from_numpy(np.array(points, dtype=np.float64).reshape(-1, 2)).cuda()   # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
-    return t
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def assert_is_spec(got, points, radius, half):
@@ -50,14 +20,7 @@ def assert_is_spec(got, points, radius, half):
     assert offsets.dtype == partners.dtype == torch.int64 and d2.dtype == torch.float64
     want = S.pairs(points, radius, half)
     for g, w in zip((offsets, partners, d2), want):
-        same_bytes(g.cpu().numpy(), w)
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
+        U.same_bytes(g.cpu().numpy(), w)
 
 
 # ---- 1. every case on the points= path
@@ -66,20 +29,20 @@ def code_of(call, *args, **kw):
 @pytest.mark.parametrize("name", list(K.cases()))
 def test_case_equals_the_spec(crate, name, half):
     points, radius = K.cases()[name]
-    got = crate.pair_tensors(radius, points=tensor(points), half=half, squared_distances=True)
+    got = crate.pair_tensors(radius, points=U.tensor(points), half=half, squared_distances=True)
     assert len(got) == 3 and len(got[0]) == len(points) + 1
     assert_is_spec(got, points, radius, half)
-    plain = crate.pair_tensors(radius, points=tensor(points), half=half)            # without the distances: the same list
+    plain = crate.pair_tensors(radius, points=U.tensor(points), half=half)            # without the distances: the same list
     assert len(plain) == 2
-    same_bytes(plain[0].cpu().numpy(), got[0].cpu().numpy())
-    same_bytes(plain[1].cpu().numpy(), got[1].cpu().numpy())
+    U.same_bytes(plain[0].cpu().numpy(), got[0].cpu().numpy())
+    U.same_bytes(plain[1].cpu().numpy(), got[1].cpu().numpy())
 
 
 def test_edge_index_of_a_case(crate):
     import torch
     from sand_crate_amd import pairs
     points, radius = K.cases()["n_257"]
-    offsets, partners = crate.pair_tensors(radius, points=tensor(points))
+    offsets, partners = crate.pair_tensors(radius, points=U.tensor(points))
     e = pairs.edge_index(offsets, partners)
     want = S.pairs(points, radius)
     assert e.shape == (2, len(want[1])) and e.is_cuda
@@ -91,7 +54,7 @@ def test_edge_index_of_a_case(crate):
 
 @pytest.fixture(scope="module")
 def ticked(sc):
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
+    crate = sc.Crate(U.scene(sc))
     for _ in range(200):
         crate.physics_tick()
     return crate
@@ -111,8 +74,8 @@ def test_state_after_ticks(ticked, factor):
     if factor == 1:
         default = crate.pair_tensors()                                              # radius defaults to the diameter
         want = S.pairs(points, crate.diameter)
-        same_bytes(default[0].cpu().numpy(), want[0])
-        same_bytes(default[1].cpu().numpy(), want[1])
+        U.same_bytes(default[0].cpu().numpy(), want[0])
+        U.same_bytes(default[1].cpu().numpy(), want[1])
         assert int(want[0][-1]) > len(points)                                       # a packed bed: some partners each
 
 
@@ -122,19 +85,19 @@ def test_state_right_after_a_load(sc, ticked):
     n = len(particles)
     order = torch.from_numpy(np.random.RandomState(5).permutation(n)).cuda()
     sparse = ids * 1000 + 17                                                        # sparse ids, shuffled storage order
-    wc = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
+    wc = U.scene(sc)
     other = sc.Crate(wc, noise="none", capacity=n + 100)
     p, v, i = particles[order].contiguous(), velocities[order].contiguous(), sparse[order].contiguous()
     torch.cuda.synchronize()
     other.load_state_tensors(p, v, i)
     points = other.state_tensors(pressure=False)[0].cpu().numpy()
-    same_bytes(points, particles.cpu().numpy())                                     # index order is id order again
+    U.same_bytes(points, particles.cpu().numpy())                                     # index order is id order again
     radius = 3 * other.diameter
     assert_is_spec(other.pair_tensors(radius, squared_distances=True), points, radius, False)
 
 
 def test_state_of_an_empty_crate(sc):
-    wc = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
+    wc = U.scene(sc)
     crate = sc.Crate(wc)
     offsets, partners, d2 = crate.pair_tensors(squared_distances=True)              # before the first tick
     assert offsets.cpu().tolist() == [0] and partners.shape == d2.shape == (0,)
@@ -147,7 +110,7 @@ def test_state_of_an_empty_crate(sc):
 
 def test_searching_changes_nothing(sc):
     def trajectory(searching):
-        crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
+        crate = sc.Crate(U.scene(sc))
         for _ in range(50):
             crate.physics_tick()
             if searching:
@@ -161,7 +124,7 @@ def test_searching_changes_nothing(sc):
     (a, rng_a), (b, rng_b) = trajectory(False), trajectory(True)
     assert len(a[0]) > 100
     for x, y in zip(a, b):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     assert np.array_equal(rng_a[0], rng_b[0]) and rng_a[1] == rng_b[1]
 
 
@@ -170,7 +133,7 @@ def test_searching_changes_nothing(sc):
 def test_max_pairs_not_clipped_equals_the_default(crate):
     import torch
     points, radius = K.cases()["long_rows"]
-    t = tensor(points)
+    t = U.tensor(points)
     offsets, partners, d2 = crate.pair_tensors(radius, points=t, squared_distances=True)
     total = len(partners)
     out = crate.pair_tensors(radius, points=t, squared_distances=True, max_pairs=total + 50)
@@ -192,19 +155,19 @@ def test_clipped_list_is_right_below_the_room_and_untouched_beyond(crate, room):
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     n = len(points)
-    offsets = torch.full((n + 1,), SENTINEL_I, dtype=torch.int64, device=dev)
-    counts = torch.full((2,), SENTINEL_I, dtype=torch.int64, device=dev)
-    partners = torch.full((room + 64,), SENTINEL_I, dtype=torch.int64, device=dev)
-    d2 = torch.full((room + 64,), SENTINEL_F, dtype=torch.float64, device=dev)
-    t = tensor(points)
+    offsets = torch.full((n + 1,), U.SENTINEL, dtype=torch.int64, device=dev)
+    counts = torch.full((2,), U.SENTINEL, dtype=torch.int64, device=dev)
+    partners = torch.full((room + 64,), U.SENTINEL, dtype=torch.int64, device=dev)
+    d2 = torch.full((room + 64,), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
+    t = U.tensor(points)
     assert eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts) is counts
     eng.pairs_fill(partners, d2, room=room)
     eng.synchronize()
     assert counts.cpu().tolist() == [n, int(want[0][-1])]
-    same_bytes(offsets.cpu().numpy(), want[0])
-    same_bytes(partners[:room].cpu().numpy(), want[1][:room])
-    same_bytes(d2[:room].cpu().numpy(), want[2][:room])
-    assert (partners[room:] == SENTINEL_I).all() and (d2[room:] == SENTINEL_F).all()
+    U.same_bytes(offsets.cpu().numpy(), want[0])
+    U.same_bytes(partners[:room].cpu().numpy(), want[1][:room])
+    U.same_bytes(d2[:room].cpu().numpy(), want[2][:room])
+    assert (partners[room:] == U.SENTINEL).all() and (d2[room:] == U.SENTINEL_FAR).all()
 
 
 # ---- 5. a pair count beyond 31 bits
@@ -219,8 +182,8 @@ def test_big_pile_against_the_closed_form(sc):
     for half in (False, True):
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        partners = torch.full((room + 64,), SENTINEL_I, dtype=torch.int64, device=dev)
-        d2 = torch.full((room + 64,), SENTINEL_F, dtype=torch.float64, device=dev)
+        partners = torch.full((room + 64,), U.SENTINEL, dtype=torch.int64, device=dev)
+        d2 = torch.full((room + 64,), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
         torch.cuda.synchronize()
         eng.pairs_count(points, radius=0.01, offsets=offsets, counts=counts, half=half)
         eng.pairs_fill(partners, d2, room=room)
@@ -229,9 +192,9 @@ def test_big_pile_against_the_closed_form(sc):
         assert counts.cpu().tolist() == [n, int(want[n])]
         if not half:
             assert int(want[n]) == 4294901760 and int(want[7]) == 7 * 65535
-        same_bytes(offsets.cpu().numpy(), want)
-        same_bytes(partners[:room].cpu().numpy(), S.coincident_partners(n, 0, room, half))
-        assert not d2[:room].any() and (partners[room:] == SENTINEL_I).all() and (d2[room:] == SENTINEL_F).all()
+        U.same_bytes(offsets.cpu().numpy(), want)
+        U.same_bytes(partners[:room].cpu().numpy(), S.coincident_partners(n, 0, room, half))
+        assert not d2[:room].any() and (partners[room:] == U.SENTINEL).all() and (d2[room:] == U.SENTINEL_FAR).all()
     eng.close()
 
 
@@ -240,28 +203,28 @@ def test_big_pile_against_the_closed_form(sc):
 def test_outside_the_domain(crate):
     import torch
     points, radius = K.outside_domain()
-    t = tensor(points)
+    t = U.tensor(points)
     with pytest.raises(ValueError, match="domain"):
         crate.pair_tensors(radius, points=t)
     # on the path that does not synchronise: E = -1, and nothing else is written
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
-    offsets = torch.full((len(points) + 1,), SENTINEL_I, dtype=torch.int64, device=dev)
-    counts = torch.full((2,), SENTINEL_I, dtype=torch.int64, device=dev)
-    partners = torch.full((100,), SENTINEL_I, dtype=torch.int64, device=dev)
-    d2 = torch.full((100,), SENTINEL_F, dtype=torch.float64, device=dev)
+    offsets = torch.full((len(points) + 1,), U.SENTINEL, dtype=torch.int64, device=dev)
+    counts = torch.full((2,), U.SENTINEL, dtype=torch.int64, device=dev)
+    partners = torch.full((100,), U.SENTINEL, dtype=torch.int64, device=dev)
+    d2 = torch.full((100,), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_fill(partners, d2)
     eng.synchronize()
     assert counts.cpu().tolist() == [len(points), -1]
-    assert (offsets == SENTINEL_I).all() and (partners == SENTINEL_I).all() and (d2 == SENTINEL_F).all()
+    assert (offsets == U.SENTINEL).all() and (partners == U.SENTINEL).all() and (d2 == U.SENTINEL_FAR).all()
     out = crate.pair_tensors(radius, points=t, max_pairs=100)
     crate.synchronize()
     assert int(out[-1][1]) == -1
     inside = points.copy()
     inside[33, 1] = np.nextafter(inside[33, 1], 0)                                  # one ulp inside: fine
-    assert_is_spec(crate.pair_tensors(radius, points=tensor(inside), squared_distances=True), inside, radius, False)
+    assert_is_spec(crate.pair_tensors(radius, points=U.tensor(inside), squared_distances=True), inside, radius, False)
 
 
 # ---- 7. errors
@@ -269,44 +232,44 @@ def test_outside_the_domain(crate):
 def test_state_errors(sc):
     import torch
     from sand_crate_amd import _native as N
-    wc = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
+    wc = U.scene(sc)
     crate = sc.Crate(wc, noise="none", capacity=512)
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     points, radius = K.cases()["n_65"]
-    t = tensor(points)
+    t = U.tensor(points)
     offsets = torch.zeros(eng.capacity + 1, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    partners = torch.full((4096,), SENTINEL_I, dtype=torch.int64, device=dev)
+    partners = torch.full((4096,), U.SENTINEL, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
-    assert code_of(eng.pairs_fill, partners) == N.ERR_STATE                         # no count yet
+    assert U.code_of(eng.pairs_fill, partners) == N.ERR_STATE                         # no count yet
     eng.pairs_count(t, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_fill(partners)                                                        # ... with one: fine, and again
     eng.pairs_fill(partners)
     crate.particles = points                                                        # an upload since the count
-    assert code_of(eng.pairs_fill, partners) == N.ERR_STATE
+    assert U.code_of(eng.pairs_fill, partners) == N.ERR_STATE
     eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
     eng.pairs_fill(partners)
     crate.physics_tick()                                                            # a tick since the count
-    assert code_of(eng.pairs_fill, partners) == N.ERR_STATE
+    assert U.code_of(eng.pairs_fill, partners) == N.ERR_STATE
     eng.synchronize()
     # inside a tick
     crate._send_tick_inputs()
     eng.step_begin()
     try:
-        assert code_of(eng.pairs_count, t, radius=radius, offsets=offsets, counts=counts) == N.ERR_STATE
-        assert code_of(eng.pairs_fill, partners) == N.ERR_STATE
+        assert U.code_of(eng.pairs_count, t, radius=radius, offsets=offsets, counts=counts) == N.ERR_STATE
+        assert U.code_of(eng.pairs_fill, partners) == N.ERR_STATE
     finally:
         eng.step_finish()
     # a slab context has no state form, but searches a caller's points
     slab = sc.Engine(capacity=256)
     slab.set_slab(0, 50, 3, False, True)
-    assert code_of(slab.pairs_count, None, radius=radius, offsets=offsets[:257], counts=counts) == N.ERR_STATE
+    assert U.code_of(slab.pairs_count, None, radius=radius, offsets=offsets[:257], counts=counts) == N.ERR_STATE
     slab.pairs_count(t, radius=radius, offsets=offsets[:66], counts=counts)
     slab.pairs_fill(partners)
     slab.synchronize()
     want = S.pairs(points, radius)
-    same_bytes(partners[:len(want[1])].cpu().numpy(), want[1])
+    U.same_bytes(partners[:len(want[1])].cpu().numpy(), want[1])
     slab.close()
 
 
@@ -319,10 +282,10 @@ def test_argument_and_capacity_errors(sc):
     eng.upload(rs.rand(n, 2), np.zeros((n, 2)))
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
-    t = tensor(rs.rand(n, 2))
-    offsets = torch.full((n + 1,), SENTINEL_I, dtype=torch.int64, device=dev)
-    counts = torch.full((2,), SENTINEL_I, dtype=torch.int64, device=dev)
-    partners = torch.full((64,), SENTINEL_I, dtype=torch.int64, device=dev)
+    t = U.tensor(rs.rand(n, 2))
+    offsets = torch.full((n + 1,), U.SENTINEL, dtype=torch.int64, device=dev)
+    counts = torch.full((2,), U.SENTINEL, dtype=torch.int64, device=dev)
+    partners = torch.full((64,), U.SENTINEL, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
     count = lib.sc_pairs_count_device
@@ -343,13 +306,13 @@ def test_argument_and_capacity_errors(sc):
     assert fill(None, ptr(partners), None, 64) == N.ERR_ARG
     assert fill(ctx, ptr(partners), None, 64) == N.ERR_STATE                                               # nothing was counted
     eng.synchronize()
-    assert (offsets == SENTINEL_I).all() and (counts == SENTINEL_I).all() and (partners == SENTINEL_I).all()
+    assert (offsets == U.SENTINEL).all() and (counts == U.SENTINEL).all() and (partners == U.SENTINEL).all()
     eng.pairs_count(t, radius=0.1, offsets=offsets, counts=counts)                                         # with the room: fine
     assert fill(ctx, None, None, 64) == N.ERR_ARG
     assert fill(ctx, ptr(partners), None, -1) == N.ERR_ARG
     eng.pairs_fill(partners)
     eng.synchronize()
     want = S.pairs(t.cpu().numpy(), 0.1)
-    same_bytes(offsets.cpu().numpy(), want[0])
-    same_bytes(partners.cpu().numpy(), want[1][:64])
+    U.same_bytes(offsets.cpu().numpy(), want[0])
+    U.same_bytes(partners.cpu().numpy(), want[1][:64])
     eng.close()

@@ -15,16 +15,11 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 # ------------------------------------------------------------------ (1) golden: neighbor search

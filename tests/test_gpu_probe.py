@@ -3,15 +3,16 @@
 downloaded state -- the six sums within the spec's tolerance, every other field and both profile arrays equal --, the log
 holds byte for byte what measuring after every tick returns, a full log drops and counts, the log survives a grown
 engine, logging changes no result, and measuring changes nothing in the simulation."""
-import copy
 import ctypes as C
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as U
 import probe_cases as K
 import probe_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,27 +29,9 @@ def launch_sizes():
 CASES = K.cases(*launch_sizes())
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def spread_world(sc, n):
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * max(n, 1))))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=max(n, 1))
-    wc.particle_sources = []
-    return wc
-
-
 def world_of(sc, case, **kw):
     n = len(case.xy)
-    crate = sc.Crate(spread_world(sc, n), noise=kw.pop("noise", "counter"), noise_seed=1, capacity=n + 64, **kw)
+    crate = sc.Crate(U.spread_world(sc, n), noise=kw.pop("noise", "counter"), noise_seed=1, capacity=n + 64, **kw)
     crate.particles = case.xy
     crate.particle_velocities = case.vxy
     return crate
@@ -56,11 +39,6 @@ def world_of(sc, case, **kw):
 
 def row_of(measured):
     return np.array([measured[name] for name in S.FIELDS], dtype=np.float64)
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 # ---- a measurement is the spec's
@@ -84,10 +62,10 @@ def test_every_case(sc, name):
     else:
         assert got["n_pressed"] == 0 and got["sum_p"] == 0 and got["max_p"] == 0   # right after an upload: zeros
     again = crate.measure(c.bins, c.x_range)                                     # measuring twice: identical bytes
-    same_bytes(row_of(again), row_of(got))
+    U.same_bytes(row_of(again), row_of(got))
     if c.bins:
-        same_bytes(again["count"], got["count"])
-        same_bytes(again["top"], got["top"])
+        U.same_bytes(again["count"], got["count"])
+        U.same_bytes(again["top"], got["top"])
     if "bin" in c.claims:
         assert got["count"][c.claims["bin"]] == len(c.xy) and got["top"][c.claims["bin"]] == c.claims["top"]
     if "bins" in c.claims:
@@ -126,9 +104,9 @@ def test_log_equals_measuring_after_every_tick(world400):
     assert obs["tick"].tolist() == list(range(1, 9)) and obs["dropped"] == 0
     assert obs["count"].shape == obs["top"].shape == (8, 32) and obs["count"].dtype == np.int32
     for t, m in enumerate(measured):
-        same_bytes(np.array([obs[name][t] for name in S.FIELDS]), row_of(m))
-        same_bytes(obs["count"][t], m["count"])
-        same_bytes(obs["top"][t], m["top"])
+        U.same_bytes(np.array([obs[name][t] for name in S.FIELDS]), row_of(m))
+        U.same_bytes(obs["count"][t], m["count"])
+        U.same_bytes(obs["top"][t], m["top"])
     assert len(set(obs["sum_ke"].tolist())) == 8                       # (the state moves)
     assert crate.observations()["tick"].shape == (0,)                  # read and cleared
     crate.physics_tick()
@@ -149,11 +127,11 @@ def test_log_through_run_changes_nothing(world400):
     a, b = logged.observations(), single.observations()
     assert a["tick"].tolist() == list(range(1, 9)) and a["dropped"] == b["dropped"] == 0
     for name in (*S.FIELDS, "count", "top"):
-        same_bytes(a[name], b[name])
+        U.same_bytes(a[name], b[name])
     for x, y in zip(logged.engine.download(), plain.engine.download()):   # the log changes no result
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     for x, y in zip(logged.engine.download(), single.engine.download()):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     xy, vxy, pressure, _ = logged.engine.download()
     S.compare_row(np.array([a[name][-1] for name in S.FIELDS]), xy, vxy, pressure, 8, 32)
     count, top = S.profile(xy, 32, 0.0, 1.0)
@@ -184,7 +162,7 @@ def test_a_full_log_drops_and_counts(world400):
 
 def test_grow_keeps_the_log(sc):
     n = 50
-    crate = sc.Crate(spread_world(sc, 4 * n + 2000), noise="counter", noise_seed=1, capacity=n)   # (discs sized for the crowd)
+    crate = sc.Crate(U.spread_world(sc, 4 * n + 2000), noise="counter", noise_seed=1, capacity=n)   # (discs sized for the crowd)
     xy, vxy = K.cloud(2, n, 0.05, 0.95)
     crate.particles = xy
     crate.particle_velocities = vxy
@@ -201,17 +179,10 @@ def test_grow_keeps_the_log(sc):
     assert obs["n"][:3].tolist() == [n] * 3 and obs["n"][3] == len(more) >= obs["n"][4] > n   # before and after, in order
     assert obs["tick"].tolist() == [1.0, 2.0, 3.0, 4.0, 5.0]          # (the new context counts on: the tick goes over)
     assert obs["count"].shape == (5, 8) and obs["dropped"] == 0
-    same_bytes(np.array([obs[name][-1] for name in S.FIELDS]), row_of(crate.measure(8)))
+    U.same_bytes(np.array([obs[name][-1] for name in S.FIELDS]), row_of(crate.measure(8)))
 
 
 # ---- errors
-
-def code_of(call, *args):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args)
-    return err.value.code
-
 
 def test_argument_errors(sc):
     from sand_crate_amd import _native as N
@@ -221,12 +192,12 @@ def test_argument_errors(sc):
     nan, inf = float("nan"), float("inf")
     good = eng.probe_now(4)[0]
     for bad in ((-1, 0.0, 1.0), (1025, 0.0, 1.0), (4, nan, 1.0), (4, 0.0, inf), (4, -inf, 1.0), (4, 0.5, 0.5), (4, 0.75, 0.25)):
-        assert code_of(eng.probe_now, *bad) == N.ERR_ARG, bad
-        assert code_of(eng.probe_enable, 8, *bad) == N.ERR_ARG, bad
-        same_bytes(eng.probe_now(4)[0], good)                          # a valid call still works
+        assert U.code_of(eng.probe_now, *bad) == N.ERR_ARG, bad
+        assert U.code_of(eng.probe_enable, 8, *bad) == N.ERR_ARG, bad
+        U.same_bytes(eng.probe_now(4)[0], good)                          # a valid call still works
     for capacity in (0, -3, (1 << 20) + 1):
-        assert code_of(eng.probe_enable, capacity) == N.ERR_ARG
-    assert code_of(eng.probe_read, 4) == N.ERR_STATE                    # (none of them switched the log on)
+        assert U.code_of(eng.probe_enable, capacity) == N.ERR_ARG
+    assert U.code_of(eng.probe_read, 4) == N.ERR_STATE                    # (none of them switched the log on)
     eng.probe_now(0, nan, nan)                                          # without bins the range is not looked at
     row = np.zeros(16)
     counts, tops = np.zeros(4, dtype=np.int32), np.zeros(4)
@@ -246,28 +217,28 @@ def test_argument_errors(sc):
     assert lib.sc_probe_read(ctx, N.dptr(rows), N.i32ptr(many_counts), N.dptr(many_tops), 8, None, C.byref(dropped)) == N.ERR_ARG
     assert lib.sc_probe_read(ctx, N.dptr(rows), N.i32ptr(many_counts), N.dptr(many_tops), 8, C.byref(n), None) == N.ERR_ARG
     assert lib.sc_probe_read(None, N.dptr(rows), N.i32ptr(many_counts), N.dptr(many_tops), 8, C.byref(n), C.byref(dropped)) == N.ERR_ARG
-    assert code_of(eng.probe_read, -1) == N.ERR_ARG
+    assert U.code_of(eng.probe_read, -1) == N.ERR_ARG
     assert lib.sc_last_error()
     got, _, _, dropped_now = eng.probe_read()                           # none of the refused reads took the row
     assert got[:, 0].tolist() == [1.0] and dropped_now == 0
     eng.probe_disable()
-    assert code_of(eng.probe_read) == N.ERR_STATE
+    assert U.code_of(eng.probe_read) == N.ERR_STATE
     eng.probe_disable()                                                 # (off twice is fine)
 
 
 def test_state_errors_inside_a_tick_and_after_a_promise(sc):
     from sand_crate_amd import _native as N
-    crate = sc.Crate(scene(sc, "wave_machine"), noise="host-sync")
+    crate = sc.Crate(U.scene(sc, "wave_machine"), noise="host-sync")
     crate.physics_tick()
     eng = crate.engine
     eng.probe_enable(8)
     crate._send_tick_inputs()
     eng.step_begin()
     try:
-        assert code_of(eng.probe_now) == N.ERR_STATE
-        assert code_of(eng.probe_read) == N.ERR_STATE
-        assert code_of(eng.probe_enable, 8) == N.ERR_STATE
-        assert code_of(eng.probe_disable) == N.ERR_STATE
+        assert U.code_of(eng.probe_now) == N.ERR_STATE
+        assert U.code_of(eng.probe_read) == N.ERR_STATE
+        assert U.code_of(eng.probe_enable, 8) == N.ERR_STATE
+        assert U.code_of(eng.probe_disable) == N.ERR_STATE
         stats = eng.step_stats()
         eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
     finally:
@@ -286,9 +257,9 @@ def test_state_errors_inside_a_tick_and_after_a_promise(sc):
         body.apply_velocity(crate.dt)
     nxt = crate._pack_tick_inputs()
     eng.tick(now, nxt)
-    assert code_of(eng.probe_enable, 8) == N.ERR_STATE
-    assert code_of(eng.probe_disable) == N.ERR_STATE
-    assert code_of(eng.probe_read) == N.ERR_STATE                       # (it is not on)
+    assert U.code_of(eng.probe_enable, 8) == N.ERR_STATE
+    assert U.code_of(eng.probe_disable) == N.ERR_STATE
+    assert U.code_of(eng.probe_read) == N.ERR_STATE                       # (it is not on)
     eng.tick(nxt)
     eng.probe_enable(8)                                                 # the promise is kept: now it can
     eng.tick(nxt)
@@ -303,7 +274,7 @@ def test_slab_contexts_refuse(sc):
     assert eng.probe_now()[0][1] == 20
     eng.set_slab(0, 10, 3, False, False)
     for call, args in ((eng.probe_now, ()), (eng.probe_enable, (8,)), (eng.probe_disable, ()), (eng.probe_read, ())):
-        assert code_of(call, *args) == N.ERR_STATE
+        assert U.code_of(call, *args) == N.ERR_STATE
         assert eng.count() == 20                                        # the context is fine
     eng.close()
 
@@ -312,7 +283,7 @@ def test_slab_contexts_refuse(sc):
 
 def test_measuring_is_read_only(sc):
     def trajectory(measure):
-        crate = sc.Crate(scene(sc, "wave_machine"))                      # noise="host": the device holds the stream
+        crate = sc.Crate(U.scene(sc, "wave_machine"))                      # noise="host": the device holds the stream
         for _ in range(10):
             crate.physics_tick()
             if measure:
@@ -320,14 +291,14 @@ def test_measuring_is_read_only(sc):
                 assert crate.measure(64)["tick"] == crate.tick and crate.measure()["n"] == len(before[0][0])
                 after = crate.engine.download(), crate.engine.rng_get_state()
                 for x, y in zip(before[0], after[0]):
-                    same_bytes(x, y)
+                    U.same_bytes(x, y)
                 assert np.array_equal(before[1][0], after[1][0]) and before[1][1] == after[1][1]
         assert crate.tick == 10
         return (*crate.engine.download(), crate.engine.rng_get_state())
 
     a, b = trajectory(False), trajectory(True)
     for x, y in zip(a[:4], b[:4]):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     assert np.array_equal(a[4][0], b[4][0]) and a[4][1] == b[4][1]
 
 

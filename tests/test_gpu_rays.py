@@ -4,59 +4,17 @@ synchronising and not --; the state form after ticks; a fan from inside the
 closed box always ends somewhere; capacity independence; a raised status writes counts[1] and nothing else; the
 workspace of the count is left as it is; the error codes."""
 import functools
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as U
 import pairs_spec as S
 import ray_cases as K
 import ray_spec as RS
+from gpu_support import crate, sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = -777
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def world(sc):
-    return sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-
-
-@pytest.fixture(scope="module")
-def crate(sc):
-    """One small crate whose engine searches the callers' points."""
-    return sc.Crate(world(sc), noise="none", capacity=256)
-
-
-def tensor(a):
-    import torch
-    t = torch.from_numpy(np.array(a, dtype=np.float64).reshape(-1, 2)).cuda()      # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
-    return t
-
-
-def full(shape, device, dtype=None):
-    import torch
-    return torch.full(shape if isinstance(shape, tuple) else (shape,), SENTINEL, dtype=dtype or torch.int64, device=device)
-
-
-def untouched(*tensors):
-    return all(bool((t == SENTINEL).all()) for t in tensors)
-
-
-def same(got, want):
-    g = got.cpu().numpy()
-    return g.dtype == want.dtype and g.shape == want.shape and np.array_equal(g, want, equal_nan=True) and \
-        np.array_equal(np.signbit(g), np.signbit(want))
 
 
 @functools.lru_cache(maxsize=None)
@@ -65,22 +23,15 @@ def spec(name):
     return RS.rays(c.points, c.walls, c.origins, c.directions, c.rho, c.max_t)
 
 
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
-
-
 def through_the_engine(eng, c, *, spare=8, rho=None, walls=True):
     """count + rays through the engine into sentinel-filled tensors with `spare` rows of room beyond the rays ->
-    (t, hit, counts), synchronised."""
+    (t, hit, counts), synchronised.  The float t holds the integer sentinel too: `U.untouched(..., sentinel=U.SENTINEL)`."""
     import torch
     dev = torch.device("cuda", eng.device)
     n, rays = len(c.points), len(c.origins)
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    t, hit = full(rays + spare, dev, torch.float64), full(rays + spare, dev)
-    p, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)                # (alive until the synchronisation)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    t, hit = U.full(rays + spare, dev, dtype=torch.float64), U.full(rays + spare, dev)
+    p, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)                # (alive until the synchronisation)
     eng.pairs_count(p, radius=float(2 * c.rho if c.radius is None else c.radius), offsets=offsets, counts=counts)
     assert eng.pairs_rays(t, hit, origins=o, directions=d, disc_radius=c.rho if rho is None else rho, max_t=c.max_t,
                           segments=c.walls if walls else None, counts=out) is out
@@ -97,23 +48,25 @@ def test_case_equals_the_spec(crate, name):
     rays = len(want_t)
     t, hit, counts = through_the_engine(crate.engine, c)
     assert counts.cpu().tolist() == [rays, 0]
-    assert same(t[:rays], want_t) and same(hit[:rays], want_hit) and untouched(t[rays:], hit[rays:])
+    assert U.same_values_signs(t[:rays], want_t) and U.same_values_signs(hit[:rays], want_hit) and \
+        U.untouched(t[rays:], hit[rays:], sentinel=U.SENTINEL)
     if c.radius is not None:
         return                                                                      # (the crate counts at 2 rho)
-    points, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
+    points, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
     t, hit = crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, points=points)
-    assert t.is_cuda and hit.is_cuda and same(t, want_t) and same(hit, want_hit)
+    assert t.is_cuda and hit.is_cuda and U.same_values_signs(t, want_t) and U.same_values_signs(hit, want_hit)
     out = crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, points=points, sync=False)
     crate.synchronize()
-    assert len(out) == 3 and out[2].cpu().tolist() == [rays, 0] and same(out[0], want_t) and same(out[1], want_hit)
+    assert len(out) == 3 and out[2].cpu().tolist() == [rays, 0] and U.same_values_signs(out[0], want_t) and \
+        U.same_values_signs(out[1], want_hit)
     # walls alone and particles alone are the spec's, too
     alone = RS.rays(None, c.walls, c.origins, c.directions, c.rho, c.max_t)
     t, hit = crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, particles=False, points=points)
-    assert same(t, alone[0]) and same(hit, alone[1])
+    assert U.same_values_signs(t, alone[0]) and U.same_values_signs(hit, alone[1])
     if RS.status(c.points, None, c.origins, c.directions, c.rho, c.max_t) == 0:
         alone = RS.rays(c.points, None, c.origins, c.directions, c.rho, c.max_t)
         t, hit = crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=False, points=points)
-        assert same(t, alone[0]) and same(hit, alone[1])
+        assert U.same_values_signs(t, alone[0]) and U.same_values_signs(hit, alone[1])
 
 
 # ---- 2. the state form, and a fan in the closed box
@@ -122,7 +75,7 @@ def test_state_after_ticks_and_a_fan_in_the_box(sc):
     import torch
     from sand_crate_amd import _native as N
     from sand_crate_amd import pairs
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     for _ in range(40):
         crate.physics_tick()
     particles, = crate.state_tensors(pressure=False)[:1]
@@ -136,7 +89,7 @@ def test_state_after_ticks_and_a_fan_in_the_box(sc):
     t, hit = crate.ray_tensors(o, d, reach)
     assert n > 100 and crate.particle_count == n and t.shape == hit.shape == (257,)
     want = RS.rays(host, walls, o.cpu().numpy(), d.cpu().numpy(), crate.diameter / 2, reach)
-    assert same(t, want[0]) and same(hit, want[1])
+    assert U.same_values_signs(t, want[0]) and U.same_values_signs(hit, want[1])
     assert int((hit == -1).sum()) == 0 and bool(torch.isfinite(t).all())         # the box is closed
     assert int((pairs.hit_walls(hit) >= 0).sum()) + int((pairs.hit_particles(hit) >= 0).sum()) == 257
     as_points = crate.ray_tensors(o, d, reach, points=particles)
@@ -145,32 +98,33 @@ def test_state_after_ticks_and_a_fan_in_the_box(sc):
     assert (ends >= lo - 1e-9).all() and (ends <= hi + 1e-9).all()
     # looking down on the surface from the top of the box (gravity points along +y): a particle or the floor
     xs = np.linspace(0.01, 0.99, 64)
-    down_o = tensor(np.stack([xs, np.full(64, 0.01)], axis=1))
-    down_d = tensor(np.tile([0.0, 1.0], (64, 1)))
+    down_o = U.tensor(np.stack([xs, np.full(64, 0.01)], axis=1))
+    down_d = U.tensor(np.tile([0.0, 1.0], (64, 1)))
     t, hit = crate.ray_tensors(down_o, down_d, reach)
     want = RS.rays(host, walls, down_o.cpu().numpy(), down_d.cpu().numpy(), crate.diameter / 2, reach)
-    assert same(t, want[0]) and same(hit, want[1]) and int((hit >= 0).sum()) > 0 and int((hit == -1).sum()) == 0
+    assert U.same_values_signs(t, want[0]) and U.same_values_signs(hit, want[1]) and int((hit >= 0).sum()) > 0 and \
+        int((hit == -1).sum()) == 0
     # a tick since the count: the grid is stale
     eng = crate.engine
     dev = particles.device
-    out_t, out_hit, counts = full(64, dev, torch.float64), full(64, dev), full(2, dev)
+    out_t, out_hit, counts = U.full(64, dev, dtype=torch.float64), U.full(64, dev), U.full(2, dev)
     crate.physics_tick()
-    assert code_of(eng.pairs_rays, out_t, out_hit, origins=down_o, directions=down_d, disc_radius=crate.diameter / 2, max_t=1.0,
-                   counts=counts) == N.ERR_STATE
+    assert U.code_of(eng.pairs_rays, out_t, out_hit, origins=down_o, directions=down_d, disc_radius=crate.diameter / 2,
+                     max_t=1.0, counts=counts) == N.ERR_STATE
     eng.synchronize()
-    assert untouched(out_t, out_hit, counts)
+    assert U.untouched(out_t, out_hit, counts, sentinel=U.SENTINEL)
 
 
 def test_the_capacity_does_not_reach_the_result(sc):
     import torch
     c = K.cases()["dense"]
-    points, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
+    points, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
     results = []
     for capacity in (256, 100_000):
-        crate = sc.Crate(world(sc), noise="none", capacity=capacity)
+        crate = sc.Crate(U.scene(sc), noise="none", capacity=capacity)
         results.append(crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, points=points))
-    assert all(torch.equal(a, b) or same(a, b.cpu().numpy()) for a, b in zip(*results))
-    assert same(results[0][0], spec("dense")[0]) and same(results[0][1], spec("dense")[1])
+    assert all(torch.equal(a, b) or U.same_values_signs(a, b.cpu().numpy()) for a, b in zip(*results))
+    assert U.same_values_signs(results[0][0], spec("dense")[0]) and U.same_values_signs(results[0][1], spec("dense")[1])
 
 
 # ---- 3. the status
@@ -180,8 +134,8 @@ def test_a_status_writes_counts_1_and_nothing_else(crate, name):
     c = K.cases()[name]
     status = c.claims["status"]
     t, hit, counts = through_the_engine(crate.engine, c)
-    assert counts.cpu().tolist() == [SENTINEL, status] and untouched(t, hit)
-    points, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
+    assert counts.cpu().tolist() == [U.SENTINEL, status] and U.untouched(t, hit, sentinel=U.SENTINEL)
+    points, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
     with pytest.raises(ValueError, match="max_t" if status == -4 else "domain"):
         crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, points=points)
     out = crate.ray_tensors(o, d, c.max_t, disc_radius=c.rho, walls=c.walls, points=points, sync=False)
@@ -197,7 +151,7 @@ def test_a_point_outside_is_the_counts_flag(crate):
     far = c.points.copy()
     far[7, 1] = -(2.0 ** 32) * 2 * c.rho
     t, hit, counts = through_the_engine(crate.engine, c._replace(points=far))
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(t, hit)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(t, hit, sentinel=U.SENTINEL)
 
 
 def test_walls_alone_need_no_range(crate):
@@ -207,7 +161,7 @@ def test_walls_alone_need_no_range(crate):
     t, hit, counts = through_the_engine(crate.engine, c._replace(walls=walls, max_t=6000.0), rho=0.0)
     assert counts.cpu().tolist() == [1, 0] and t[:1].cpu().tolist() == [5000.0] and hit[:1].cpu().tolist() == [-2]
     t, hit, counts = through_the_engine(crate.engine, K.cases()["origin_outside"], rho=0.0)
-    assert counts.cpu().tolist() == [SENTINEL, -1] and untouched(t, hit)
+    assert counts.cpu().tolist() == [U.SENTINEL, -1] and U.untouched(t, hit, sentinel=U.SENTINEL)
 
 
 # ---- 4. the workspace is left as it is
@@ -220,10 +174,10 @@ def test_fill_rays_fill(crate):
     n, rays = len(c.points), len(c.origins)
     want = S.pairs(c.points, 2 * c.rho)
     k = len(want[1])
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    before, after = full(k, dev), full(k, dev)
-    t, hit = full(rays, dev, torch.float64), full(rays, dev)
-    p, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    before, after = U.full(k, dev), U.full(k, dev)
+    t, hit = U.full(rays, dev, dtype=torch.float64), U.full(rays, dev)
+    p, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
     eng.pairs_count(p, radius=2 * c.rho, offsets=offsets, counts=counts)
     eng.pairs_fill(before)
     eng.pairs_rays(t, hit, origins=o, directions=d, disc_radius=c.rho, max_t=c.max_t, segments=c.walls, counts=out)
@@ -231,8 +185,9 @@ def test_fill_rays_fill(crate):
     eng.pairs_rays(t, hit, origins=o, directions=d, disc_radius=c.rho, max_t=c.max_t, segments=c.walls, counts=out)
     eng.pairs_fill(after)
     eng.synchronize()
-    assert torch.equal(before, after) and same(after, want[1]) and k > 0
-    assert same(t, spec("dense")[0]) and same(hit, spec("dense")[1]) and out.cpu().tolist() == [rays, 0]
+    assert torch.equal(before, after) and U.same_values_signs(after, want[1]) and k > 0
+    assert U.same_values_signs(t, spec("dense")[0]) and U.same_values_signs(hit, spec("dense")[1]) and \
+        out.cpu().tolist() == [rays, 0]
 
 
 # ---- 5. errors
@@ -245,9 +200,9 @@ def test_argument_and_capacity_errors(sc):
     eng = sc.Engine(capacity=n + 64)
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
-    p, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
-    offsets, counts, out = full(n + 1, dev), full(2, dev), full(2, dev)
-    t, hit = full(rays, dev, torch.float64), full(rays, dev)
+    p, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
+    offsets, counts, out = U.full(n + 1, dev), U.full(2, dev), U.full(2, dev)
+    t, hit = U.full(rays, dev, dtype=torch.float64), U.full(rays, dev)
     walls = np.ascontiguousarray(c.walls)
     torch.cuda.synchronize()
     ptr = lambda x: N._P(x.data_ptr())  # noqa: E731
@@ -281,42 +236,43 @@ def test_argument_and_capacity_errors(sc):
     eng.pairs_count(p, radius=2 * c.rho, offsets=offsets, counts=counts, batch=ptr_b)
     assert fn(*args()) == N.ERR_ARG and b"batched" in lib.sc_last_error()
     eng.synchronize()
-    assert untouched(t, hit, out)
+    assert U.untouched(t, hit, out, sentinel=U.SENTINEL)
     eng.pairs_count(p, radius=2 * c.rho, offsets=offsets, counts=counts)
     assert fn(*args(seg=None, ns=0)) == 0                                           # no walls: fine
     assert fn(*args()) == 0
     eng.synchronize()
-    assert same(t, spec("dense")[0]) and same(hit, spec("dense")[1]) and out.cpu().tolist() == [rays, 0]
+    assert U.same_values_signs(t, spec("dense")[0]) and U.same_values_signs(hit, spec("dense")[1]) and \
+        out.cpu().tolist() == [rays, 0]
     eng.close()
 
 
 def test_inside_a_tick(sc):
     import torch
     from sand_crate_amd import _native as N
-    crate = sc.Crate(world(sc))
+    crate = sc.Crate(U.scene(sc))
     for _ in range(3):
         crate.physics_tick()
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
-    o, d = tensor([[0.5, 0.5]]), tensor([[1.0, 0.0]])
-    offsets, counts = full(eng.capacity + 1, dev), full(2, dev)
-    t, hit = full(1, dev, torch.float64), full(1, dev)
+    o, d = U.tensor([[0.5, 0.5]]), U.tensor([[1.0, 0.0]])
+    offsets, counts = U.full(eng.capacity + 1, dev), U.full(2, dev)
+    t, hit = U.full(1, dev, dtype=torch.float64), U.full(1, dev)
     eng.pairs_count(None, radius=crate.diameter, offsets=offsets, counts=counts)
     crate._send_tick_inputs()
     eng.step_begin()
     try:
-        assert code_of(eng.pairs_rays, t, hit, origins=o, directions=d, disc_radius=crate.diameter / 2, max_t=1.0,
-                       counts=counts) == N.ERR_STATE
+        assert U.code_of(eng.pairs_rays, t, hit, origins=o, directions=d, disc_radius=crate.diameter / 2, max_t=1.0,
+                         counts=counts) == N.ERR_STATE
         assert b"inside a tick" in eng._lib.sc_last_error()
     finally:
         eng.step_finish()
     eng.synchronize()
-    assert untouched(t, hit)
+    assert U.untouched(t, hit, sentinel=U.SENTINEL)
 
 
 def test_wrapper_errors(crate):
     c = K.cases()["rays_65"]
-    points, o, d = tensor(c.points), tensor(c.origins), tensor(c.directions)
+    points, o, d = U.tensor(c.points), U.tensor(c.origins), U.tensor(c.directions)
     for call in (lambda: crate.ray_tensors(o, d[:-1], 1.0, points=points), lambda: crate.ray_tensors(o.float(), d, 1.0, points=points),
                  lambda: crate.ray_tensors(o, d, -1.0, points=points), lambda: crate.ray_tensors(o, d, float("inf"), points=points),
                  lambda: crate.ray_tensors(o, d, 1.0, disc_radius=0.0, points=points),

@@ -11,9 +11,11 @@ import copy
 import numpy as np
 import pytest
 
+import gpu_support as U
 import probe_spec
 import recovery_cases as rc
 import track_spec
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,19 +24,6 @@ PATIENCE = 1 << 22  # the default (sc_kernels.h: kScanMaxPolls)
 # the oracle's worlds, built once and before any crate: an OracleCrate seeds np.random as the reference does (crate.py:22),
 # and the crate of the "host-sync" test draws from that very generator between its ticks
 ORACLES = {id(coef): rc.oracle(coef) for coef in (rc.COEF, rc.PILE_COEF)}
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def make_crate(sc, state, noise, capacity, coef=rc.COEF):
@@ -119,10 +108,10 @@ def abandon(crate, path, k=rc.ABANDONED):
 
 def assert_state_as_found(before, after, coef=rc.COEF):
     """Velocities, ids, count and pressures exactly; positions exactly but for the wall fix, applied once."""
-    same_bytes(after[1], before[1])
-    same_bytes(after[3], before[3])
-    same_bytes(after[2], before[2])
-    same_bytes(after[0], wall_fixed(before[0], coef))
+    U.same_bytes(after[1], before[1])
+    U.same_bytes(after[3], before[3])
+    U.same_bytes(after[2], before[2])
+    U.same_bytes(after[0], wall_fixed(before[0], coef))
 
 
 # ---------------------------------------------------------------- every reader, every tick path
@@ -147,7 +136,7 @@ def test_every_reader_recovers_on_every_tick_path(sc, world, reader, path):
     after = eng.download()
     assert_state_as_found(before, after)
     if world == "quiet":
-        same_bytes(after[0], before[0])
+        U.same_bytes(after[0], before[0])
     else:
         assert (after[0] != before[0]).any(axis=1).sum() == len(band[0])
     state = (after[0], after[1], after[3])
@@ -173,7 +162,7 @@ def recovered_pile(sc, reader):
     expect_error_once(crate, reader, N.ERR_HIP, "bucket scan", "skipped")
     after = crate.engine.download()
     assert_state_as_found(before, after, rc.PILE_COEF)
-    same_bytes(after[0], before[0])
+    U.same_bytes(after[0], before[0])
     return crate, (after[0], after[1], after[3])
 
 
@@ -232,8 +221,8 @@ def test_device_stream_does_not_move_for_abandoned_ticks(sc, world, reader):
     key1, pos1 = a.engine.rng_get_state()  # (before the reader, too)
     expect_error_once(a, reader, N.ERR_HIP, "bucket scan", "skipped")
     key2, pos2 = a.engine.rng_get_state()
-    same_bytes(key1, key0)
-    same_bytes(key2, key0)
+    U.same_bytes(key1, key0)
+    U.same_bytes(key2, key0)
     assert pos0 == pos1 == pos2
     assert_state_as_found(found, a.engine.download())  # (dense has particles at the walls by now: the fix, once)
     run_ticks(a, "physics_tick", 2)
@@ -242,10 +231,10 @@ def test_device_stream_does_not_move_for_abandoned_ticks(sc, world, reader):
     got, want = a.engine.download(), b.engine.download()
     assert not np.array_equal(want[0], found[0])
     for x, y in zip(got, want):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     ka, pa = a.engine.rng_get_state()
     kb, pb = b.engine.rng_get_state()
-    same_bytes(ka, kb)
+    U.same_bytes(ka, kb)
     assert pa == pb and (pa != pos0 or not np.array_equal(ka, key0))
 
 
@@ -284,7 +273,7 @@ def test_host_sync_draws_nothing_for_an_abandoned_tick(sc):
     expect_error_once(crate, "particles", N.ERR_HIP, "bucket scan", "skipped")
     after = crate.engine.download()
     assert_state_as_found(before, after)
-    same_bytes(np.random.get_state()[1], host.get_state()[1])  # the two streams stand at the same place
+    U.same_bytes(np.random.get_state()[1], host.get_state()[1])  # the two streams stand at the same place
     assert np.random.get_state()[2] == host.get_state()[2]
     for _ in range(rc.GOOD_AFTER):
         state = good_tick(state)
@@ -317,7 +306,7 @@ def test_export_before_the_first_reader(sc, world):
     assert_state_as_found(before, exported)
     expect_error_once(crate, "download", N.ERR_HIP, "bucket scan", "skipped")  # ... and it was still there to be read
     for x, y in zip(crate.engine.download(), exported):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     assert_export_is_download(crate.engine)
     crate.physics_tick()
     got = assert_export_is_download(crate.engine)

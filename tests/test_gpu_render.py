@@ -1,56 +1,23 @@
 """GPU tests of the frame renderer (sc_render / sc_render_device, `Crate.render`): every frame equals tests/render_spec.py
 applied to what sc_download_state returns at the same moment, bit for bit, and rendering changes nothing."""
-import copy
 import ctypes
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import gpu_support as U
 import render_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def scene(sc, name):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def m2_world(sc, n):
-    """bench.py's M2 inputs: n uniform particles in the wave_machine world, spacing scaled to n, no sources."""
-    wc = copy.deepcopy(scene(sc, "wave_machine"))
-    d = float(np.sqrt(12.0 / (np.pi * n)))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=n)
-    wc.particle_sources = []
-    rs = np.random.RandomState(1234)
-    return wc, rs.rand(n, 2) * 0.96 + 0.02, (rs.rand(n, 2) - 0.5) * 0.1
-
-
-def m2_crate(sc, n, **kw):
-    wc, p, v = m2_world(sc, n)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024, **kw)
-    crate.particles = p
-    crate.particle_velocities = v
-    return crate
-
-
-def spec_of(crate, width, height, **kw):
-    xy, _, pressure, ids = crate.engine.download()
-    seg = crate.segments if crate.rigid_bodies else np.zeros((0, 2, 2))
-    return S.render(xy, pressure, ids, seg, width, height, crate.particle_radius, **kw)
-
-
 def check(crate, width, height, **kw):
     img = crate.render(width, height, **kw)
-    want = spec_of(crate, width, height, **kw)
+    want = U.spec_frame(crate, width, height, **kw)
     assert img.shape == want.shape and img.dtype == np.uint8
     if not np.array_equal(img, want):
         bad = np.argwhere((img != want).any(axis=2))
@@ -60,7 +27,7 @@ def check(crate, width, height, **kw):
 
 
 def test_wave_machine_with_its_source_at_1000(sc):
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     for _ in range(60):
         crate.physics_tick()
     assert S.disc_radius(1000, crate.particle_radius, 1.0) == 5  # the one-wave-per-disc path
@@ -71,7 +38,7 @@ def test_wave_machine_with_its_source_at_1000(sc):
 
 
 def test_stirring_cup_with_moving_walls(sc):
-    crate = sc.Crate(scene(sc, "stirring_cup"))
+    crate = sc.Crate(U.scene(sc, "stirring_cup"))
     for _ in range(100):
         crate.physics_tick()
     check(crate, 1000, 1000)
@@ -80,7 +47,7 @@ def test_stirring_cup_with_moving_walls(sc):
 
 
 def test_million_particles_at_1000_and_2048(sc):
-    crate = m2_crate(sc, 1048576)
+    crate = U.m2_crate(sc, 1048576)
     crate.physics_tick()
     crate.physics_tick()
     assert S.disc_radius(1000, crate.particle_radius, 1.0) == 0
@@ -91,7 +58,7 @@ def test_million_particles_at_1000_and_2048(sc):
 
 
 def test_zoomed_view_cut_by_the_frame_edges(sc):
-    crate = sc.Crate(scene(sc, "wave_machine"))
+    crate = sc.Crate(U.scene(sc, "wave_machine"))
     for _ in range(40):
         crate.physics_tick()
     for center in ((120.0, 880.0), (905.5, 60.25)):
@@ -102,7 +69,7 @@ def test_zoomed_view_cut_by_the_frame_edges(sc):
 
 def test_pile_up_highest_id_wins(sc):
     """Thousands of particles per pixel: the frame keeps the last-drawn (highest id) one of each."""
-    crate = m2_crate(sc, 262144)
+    crate = U.m2_crate(sc, 262144)
     crate.physics_tick()
     eng = crate.engine
     xy, _, pressure, ids = eng.download()
@@ -115,7 +82,7 @@ def test_pile_up_highest_id_wins(sc):
 
 
 def test_after_upload_every_particle_is_white(sc):
-    crate = m2_crate(sc, 65536)
+    crate = U.m2_crate(sc, 65536)
     img = check(crate, 1000, 1000)
     drawn = img.any(axis=2) & ~(img == 255).all(axis=2)
     assert not drawn.any()  # nothing but white discs (and white walls) on black
@@ -124,7 +91,7 @@ def test_after_upload_every_particle_is_white(sc):
 
 def test_rendering_is_read_only_for_physics_tick(sc):
     def trajectory(render):
-        crate = sc.Crate(scene(sc, "wave_machine"))
+        crate = sc.Crate(U.scene(sc, "wave_machine"))
         for _ in range(20):
             crate.physics_tick()
             if render:
@@ -141,7 +108,7 @@ def test_rendering_is_read_only_for_physics_tick(sc):
 
 def test_rendering_is_read_only_for_run(sc):
     def trajectory(render):
-        crate = m2_crate(sc, 16384)
+        crate = U.m2_crate(sc, 16384)
         for _ in range(4):
             crate.run(5)
             if render:
@@ -154,7 +121,7 @@ def test_rendering_is_read_only_for_run(sc):
 
 def test_device_path_equals_host_path(sc):
     import torch
-    crate = sc.Crate(scene(sc, "stirring_cup"))
+    crate = sc.Crate(U.scene(sc, "stirring_cup"))
     for _ in range(30):
         crate.physics_tick()
     host = crate.render(1000, 1000)
@@ -174,7 +141,7 @@ def test_device_path_equals_host_path(sc):
 
 def test_error_codes(sc):
     from sand_crate_amd import _native as N
-    crate = m2_crate(sc, 4096)
+    crate = U.m2_crate(sc, 4096)
     crate.physics_tick()
     eng = crate.engine
     lib, ctx = eng._lib, eng._ctx
@@ -212,7 +179,7 @@ def test_headless_driver_writes_frames(sc, tmp_path):
     from sand_crate_amd.main import main
     main(ROOT / "config" / "wave_machine.yaml", tmp_path, variants=1, ticks=20, record_every=10, frames=True)
     out = tmp_path / "variant_00"
-    r = scene(sc, "wave_machine").coefficients["particle_radius"]
+    r = U.scene(sc, "wave_machine").coefficients["particle_radius"]
     with np.load(out / "frames.npz") as z, np.load(out / "state.npz") as st:
         frames, ticks = z["frames"], z["ticks"]
         assert frames.shape == (2, 1000, 1000, 3) and ticks.tolist() == [10, 20] == st["ticks"].tolist()

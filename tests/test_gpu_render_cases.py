@@ -13,17 +13,12 @@ import pytest
 import gif_spec as G
 import render_cases as K
 import render_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 COEF = ("dt", "particle_radius", "wall_collision_decay", "pressure_amplifier", "ignored_pressure",
         "collider_noise_level", "viscosity", "surface_smoothing", "target_pressure")
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 @pytest.fixture(scope="module")

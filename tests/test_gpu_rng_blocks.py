@@ -14,19 +14,15 @@ import json
 import numpy as np
 import pytest
 
+import gpu_support as U
 import rng_block_cases as K
+from gpu_support import sc  # noqa: F401
 from test_gpu_parity import wave_world
 from test_gpu_rng_stream import check_emission
 
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-9, dict(particles=1e-12, velocities=1e-11, pressure=1e-12)  # test_gpu_rng_stream.host_noise_ticks
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def engine_ticks(sc, world: K.World, start: int, ticks: int, device_stream: bool):
@@ -180,16 +176,12 @@ def seed_key():
     return np.random.RandomState(0).get_state()[1]
 
 
-def scene(sc):
-    return sc.load_config("config/wave_machine.yaml").world_config
-
-
 def test_a_run_from_an_odd_position_equals_the_host_drawn_stream(sc):
     """config/wave_machine.yaml for 30 ticks, emission and collider noise: the device stream from (key, 623) against
     noise="host-sync" with np.random set to the same state.  Every double of the run straddles a pair of words NumPy's
     even-position runs never pair up."""
     ticks = 30
-    dev = sc.Crate(scene(sc), noise="host")
+    dev = sc.Crate(U.scene(sc), noise="host")
     dev.engine.rng_set_state(seed_key(), ODD)
     for _ in range(ticks):
         dev.physics_tick()
@@ -197,7 +189,7 @@ def test_a_run_from_an_odd_position_equals_the_host_drawn_stream(sc):
     _, pos = dev.engine.rng_get_state()
     dev.sync_host_rng()
     after_dev = np.random.rand(4)
-    ref = sc.Crate(scene(sc), noise="host-sync")  # seeds np.random again
+    ref = sc.Crate(U.scene(sc), noise="host-sync")  # seeds np.random again
     np.random.set_state(("MT19937", seed_key(), ODD))
     for _ in range(ticks):
         ref.physics_tick()
@@ -213,7 +205,7 @@ def test_a_run_from_an_odd_position_equals_the_host_drawn_stream(sc):
 
 def test_a_checkpoint_at_an_odd_position_resumes_the_same_run(sc, tmp_path):
     def started():
-        crate = sc.Crate(scene(sc), noise="host")
+        crate = sc.Crate(U.scene(sc), noise="host")
         crate.engine.rng_set_state(seed_key(), ODD)
         return crate
 

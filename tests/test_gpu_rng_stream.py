@@ -9,6 +9,7 @@ import time
 import numpy as np
 import pytest
 
+from gpu_support import sc  # noqa: F401
 from rng_cases import CALLS, SWEEP, mixed_sources, numpy_emit, seed_of, source
 from test_gpu_parity import bench_like_crate, synthetic, wave_world
 from test_gpu_round2 import pile_up_state
@@ -16,12 +17,6 @@ from test_gpu_round2 import pile_up_state
 pytestmark = pytest.mark.gpu
 
 SMALL_IDS = 1 << 16  # sc_rng.h kSmallIds: the host's id bound up to which one launch takes the noise offsets and draws
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def assert_same_state(eng, rs):

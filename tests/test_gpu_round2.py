@@ -5,15 +5,11 @@ import copy
 import numpy as np
 import pytest
 
+import gpu_support as U
+from gpu_support import sc  # noqa: F401
 from test_gpu_parity import synthetic, wave_world
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def test_upload_with_ids_twice_within_one_staging_allocation(sc):
@@ -80,22 +76,18 @@ def test_run_equals_ticks_with_a_free_body(sc):
 
 
 # ------------------------------------------------------------------ NumPy's global stream on the device (N2)
-def scene(sc, name):
-    return sc.load_config(f"config/{name}.yaml").world_config
-
-
 @pytest.mark.parametrize("name,ticks", [("stirring_cup", 120), ("wave_machine", 90)])
 def test_device_stream_equals_host_drawn_stream(sc, name, ticks):
     """noise="host" (sources and collider noise drawn on the device from NumPy's MT19937 state) against
     noise="host-sync" (the host draws the same stream with np.random): the same particles, bit for bit, tick
     after tick -- and the stream handed back to np.random stands where the host-drawn one stands."""
-    dev = sc.Crate(scene(sc, name), noise="host")
+    dev = sc.Crate(U.scene(sc, name), noise="host")
     for _ in range(ticks):
         dev.physics_tick()
     pd, vd, prd, idd = dev.engine.download()
     dev.sync_host_rng()
     after_dev = np.random.rand(5)
-    ref = sc.Crate(scene(sc, name), noise="host-sync")  # seeds np.random again (crate.py:22)
+    ref = sc.Crate(U.scene(sc, name), noise="host-sync")  # seeds np.random again (crate.py:22)
     for _ in range(ticks):
         ref.physics_tick()
     pr, vr, prr, idr = ref.engine.download()
@@ -167,7 +159,7 @@ def test_resume_from_checkpoint_is_bit_equal(sc, tmp_path, noise):
     """40 ticks in one go against 20 ticks, save, a NEW crate from the file, 20 more: particles, ids, pressure, walls
     and -- for the MT19937 modes -- the random stream continue exactly (wave_machine.yaml: a particle source that
     is still emitting and a motored wall)."""
-    a = sc.Crate(scene(sc, "wave_machine"), noise=noise, noise_seed=3)
+    a = sc.Crate(U.scene(sc, "wave_machine"), noise=noise, noise_seed=3)
     for _ in range(40):
         a.physics_tick()
     want = a.engine.download()
@@ -176,7 +168,7 @@ def test_resume_from_checkpoint_is_bit_equal(sc, tmp_path, noise):
         a.sync_host_rng()
         want_draw = np.random.rand(3)
 
-    b = sc.Crate(scene(sc, "wave_machine"), noise=noise, noise_seed=3)
+    b = sc.Crate(U.scene(sc, "wave_machine"), noise=noise, noise_seed=3)
     for _ in range(20):
         b.physics_tick()
     b.gravity = np.array([0.0, 9.8])  # coefficients travel as they stand (here unchanged)
@@ -609,7 +601,7 @@ def test_checkpoint_is_refused_while_a_promised_tick_is_pending(sc):
 
 
 def big_flow_world(sc):
-    wc = scene(sc, "wave_machine")
+    wc = U.scene(sc, "wave_machine")
     wc.particle_sources = [dict(radius=0.3, position=[0.05, 0.95], velocity=[3, 0.0], flow=20000, noise=0.0, active_ticks=500)]
     return wc  # flow * dt = 40 > 30: NumPy's legacy binomial takes its BTPE branch (particle_source.py:18)
 

@@ -6,19 +6,12 @@ noise; without halo overlap everywhere, with it where the particles stay within 
 import pytest
 
 import slab_cases
+from gpu_support import sc  # noqa: F401
 from slab_cases import CASES, EQUAL
 from test_gpu_slabs import assert_chain_equals_single, single_domain
 
 pytestmark = pytest.mark.gpu
 TICKS = 3
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 _single = {}

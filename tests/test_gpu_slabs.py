@@ -8,15 +8,9 @@ import copy
 import numpy as np
 import pytest
 
+from gpu_support import sc  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def bench_world(n):

@@ -18,6 +18,7 @@ import time
 import numpy as np
 import pytest
 
+import gpu_support as U
 import recovery_cases as rc
 import sort_cases as cases
 
@@ -33,11 +34,6 @@ def lib():
     torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
     import sand_crate_amd
     return sand_crate_amd
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def make_crate(lib, name):
@@ -73,8 +69,8 @@ def bring_to_route(crate, name, route):
     gp, gv, _, gids = eng.download()
     if name != "wall_pile":  # no time has passed
         order = np.argsort(ids)
-        same_bytes(gp, p[order])
-        same_bytes(gv, v[order])
+        U.same_bytes(gp, p[order])
+        U.same_bytes(gv, v[order])
     return (gp, gv, gids), True
 
 
@@ -96,7 +92,7 @@ def tap(crate, state, fixed_already, route, neighbors=True):
     assert np.array_equal(rows, np.floor(q[order, 1] / d).astype(np.int64))
     assert np.array_equal(sorted_ids, ids[order])
     if neighbors:
-        same_bytes(fixed_xy, q[order])
+        U.same_bytes(fixed_xy, q[order])
     return got
 
 
@@ -118,8 +114,8 @@ def check_world(lib, name, route):
         assert out["wall_count"].sum() > 1500 and out["pressure"].max() > 1.0  # wall slots and a pile's pressures
         assert_tick(got, out, ids[by_id])
     else:  # no forces, no time: what K4 moved to the sorted arrays is what comes back
-        same_bytes(got[0], p[by_id])
-        same_bytes(got[1], v[by_id])
+        U.same_bytes(got[0], p[by_id])
+        U.same_bytes(got[1], v[by_id])
     crate.engine.close()
 
 

@@ -4,14 +4,14 @@
 blocks begin and end, with sparse and shuffled ids, after real ticks (emitting sources, fused ticks, a removal), after an
 append, in slab mode --, exporting changes nothing, importing equals uploading, and the error codes."""
 import copy
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import gpu_support as U
+from gpu_support import sc  # noqa: F401
 
-ROOT = Path(__file__).resolve().parent.parent
+pytestmark = pytest.mark.gpu
 
 
 def launch_widths():
@@ -31,40 +31,17 @@ def edge_sizes():
     return sorted(sizes)
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
 def cloud(seed, n, lo=0.05, hi=0.95):
     rs = np.random.RandomState(seed)
     return lo + (hi - lo) * rs.rand(n, 2), 0.2 * (rs.rand(n, 2) - 0.5)
 
 
-def scene(sc, name="wave_machine"):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
-def spread_world(sc, n):
-    wc = copy.deepcopy(scene(sc))
-    d = float(np.sqrt(12.0 / (np.pi * max(n, 1))))
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=max(n, 1))
-    wc.particle_sources = []
-    return wc
-
-
 def spread_crate(sc, n, seed=3, noise="none", capacity=None):
-    crate = sc.Crate(spread_world(sc, n), noise=noise, noise_seed=1, capacity=capacity or n + 64)
+    crate = sc.Crate(U.spread_world(sc, n), noise=noise, noise_seed=1, capacity=capacity or n + 64)
     p, v = cloud(seed, n)
     crate.particles = p
     crate.particle_velocities = v
     return crate
-
-
-SENTINEL_F, SENTINEL_I = -12345.5, -777
 
 
 def export(eng, room=None, extra=0):
@@ -74,39 +51,27 @@ def export(eng, room=None, extra=0):
     room = eng.capacity if room is None else room
     dev = torch.device("cuda", eng.device)
     rows = room + extra
-    p = torch.full((rows, 2), SENTINEL_F, dtype=torch.float64, device=dev)
-    v = torch.full((rows, 2), SENTINEL_F, dtype=torch.float64, device=dev)
-    pr = torch.full((rows,), SENTINEL_F, dtype=torch.float64, device=dev)
-    ids = torch.full((rows,), SENTINEL_I, dtype=torch.int64, device=dev)
-    count = torch.full((1,), SENTINEL_I, dtype=torch.int64, device=dev)
+    p = torch.full((rows, 2), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
+    v = torch.full((rows, 2), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
+    pr = torch.full((rows,), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
+    ids = torch.full((rows,), U.SENTINEL, dtype=torch.int64, device=dev)
+    count = torch.full((1,), U.SENTINEL, dtype=torch.int64, device=dev)
     torch.cuda.synchronize(dev)
     assert eng.export_state(p, v, pr, ids, count=count, room=room) is count
     eng.synchronize()
     n = int(count.item())
     assert 0 <= n <= room
-    assert (p[n:] == SENTINEL_F).all() and (v[n:] == SENTINEL_F).all() and (pr[n:] == SENTINEL_F).all()
-    assert (ids[n:] == SENTINEL_I).all()
+    assert (p[n:] == U.SENTINEL_FAR).all() and (v[n:] == U.SENTINEL_FAR).all() and (pr[n:] == U.SENTINEL_FAR).all()
+    assert (ids[n:] == U.SENTINEL).all()
     return tuple(t[:n].cpu().numpy() for t in (p, v, pr, ids))
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def assert_export_is_download(eng, **kw):
     got = export(eng, **kw)
     want = eng.download()
     for g, w in zip(got, want):
-        same_bytes(g, w)
+        U.same_bytes(g, w)
     return got
-
-
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
 
 
 # ---- 1. sizes at the edges
@@ -119,12 +84,12 @@ def test_sizes_at_the_edges(sc, n):
     eng.upload_with_ids(p[order], v[order], order.astype(np.int64))
     gp, gv, gpr, gids = assert_export_is_download(eng, extra=3)
     assert len(gids) == n and np.array_equal(gids, np.arange(n)) and not gpr.any()
-    same_bytes(gp, p)
-    same_bytes(gv, v)
+    U.same_bytes(gp, p)
+    U.same_bytes(gv, v)
     eng.upload(p, v)                                            # a fresh upload: particle i gets id i
     gp, _, gpr, gids = assert_export_is_download(eng)
     assert np.array_equal(gids, np.arange(n)) and not gpr.any()
-    same_bytes(gp, p)
+    U.same_bytes(gp, p)
     eng.close()
 
 
@@ -140,15 +105,15 @@ def test_sparse_ids_in_shuffled_storage_order(sc, top):
     eng.upload_with_ids(p[order], v[order], ids[order])
     gp, gv, _, gids = assert_export_is_download(eng)
     assert np.array_equal(gids, ids)
-    same_bytes(gp, p)
-    same_bytes(gv, v)
+    U.same_bytes(gp, p)
+    U.same_bytes(gv, v)
     eng.close()
 
 
 # ---- 3. after real ticks
 
 def test_after_ticks_with_emitting_sources(sc):
-    crate = sc.Crate(scene(sc), noise="host")                  # the sources emit on the device: ids grow, storage is cell-sorted
+    crate = sc.Crate(U.scene(sc), noise="host")                # the sources emit on the device: ids grow, storage is cell-sorted
     counts = []
     for tick in range(1, 41):
         crate.physics_tick()
@@ -159,9 +124,9 @@ def test_after_ticks_with_emitting_sources(sc):
             assert (pr > 0).any() or tick == 1
     assert counts[0] < counts[1] < counts[2]
     p, v, pr = crate.state_tensors()                            # the crate's own form: the attributes, on the device
-    same_bytes(p.cpu().numpy(), crate.particles)
-    same_bytes(v.cpu().numpy(), crate.particle_velocities)
-    same_bytes(pr.cpu().numpy(), crate.particles_pressure)
+    U.same_bytes(p.cpu().numpy(), crate.particles)
+    U.same_bytes(v.cpu().numpy(), crate.particle_velocities)
+    U.same_bytes(pr.cpu().numpy(), crate.particles_pressure)
     assert crate.particle_count == len(p)
 
 
@@ -175,7 +140,7 @@ def test_after_fused_ticks(sc):
 def test_after_a_removal_the_ids_have_a_gap(sc):
     from oracle.tick import remove_outside
     n = 500
-    crate = sc.Crate(spread_world(sc, n), noise="none", capacity=n + 64)
+    crate = sc.Crate(U.spread_world(sc, n), noise="none", capacity=n + 64)
     p, v = cloud(8, n)
     r = crate.particle_radius
     p[123] = (0.5, 1.0 + 1.5 * r)                               # crate.py:152: a coordinate above 1 + r is removed
@@ -197,7 +162,7 @@ def test_appended_slots_carry_no_pressure(sc):
     crate.engine.append(more, more_v)
     gp, _, pr, ids = assert_export_is_download(crate.engine)
     assert np.array_equal(ids, np.arange(703)) and not pr[700:].any() and (pr[:700] > 0).any()
-    same_bytes(gp[700:], more)
+    U.same_bytes(gp[700:], more)
 
 
 # ---- 5. slabs
@@ -235,7 +200,7 @@ def test_exporting_changes_nothing(sc):
         return crate.engine.download()
 
     for a, b in zip(trajectory(False), trajectory(True)):
-        same_bytes(a, b)
+        U.same_bytes(a, b)
     crate = spread_crate(sc, 1500, noise="counter")
     crate.run(3)
     first = crate.state_tensors(ids=True)
@@ -260,8 +225,8 @@ def test_load_state_tensors_equals_upload(sc):
     ids = np.sort(np.random.RandomState(12).choice(50000, n, replace=False)).astype(np.int64)
     order = np.random.RandomState(13).permutation(n)
     for with_ids in (False, True):
-        a = sc.Crate(spread_world(sc, n), noise="none", capacity=n + 64)
-        b = sc.Crate(spread_world(sc, n), noise="none", capacity=n + 64)
+        a = sc.Crate(U.spread_world(sc, n), noise="none", capacity=n + 64)
+        b = sc.Crate(U.spread_world(sc, n), noise="none", capacity=n + 64)
         if with_ids:
             a.engine.upload_with_ids(p[order], v[order], ids[order])
             b.load_state_tensors(*tensors(p[order], v[order], ids[order]))
@@ -270,14 +235,14 @@ def test_load_state_tensors_equals_upload(sc):
             b.load_state_tensors(*tensors(p, v))
         assert b.particle_count == n
         for x, y in zip(a.engine.download(), b.engine.download()):
-            same_bytes(x, y)
+            U.same_bytes(x, y)
         for crate in (a, b):
             crate._cache = None
             crate._count_known = False
             crate.physics_tick()
         for x, y in zip(a.engine.download(), b.engine.download()):
-            same_bytes(x, y)
-        same_bytes(b.particles, a.engine.download()[0])
+            U.same_bytes(x, y)
+        U.same_bytes(b.particles, a.engine.download()[0])
 
 
 def test_round_trip_into_a_fresh_crate(sc):
@@ -286,7 +251,7 @@ def test_round_trip_into_a_fresh_crate(sc):
     for _ in range(5):
         a.physics_tick()
     p, v, ids = a.state_tensors(pressure=False, ids=True)
-    b = sc.Crate(spread_world(sc, n), noise="none", capacity=n + 64)
+    b = sc.Crate(U.spread_world(sc, n), noise="none", capacity=n + 64)
     for body_a, body_b in zip(a.rigid_bodies, b.rigid_bodies):   # the walls where crate A has them
         body_b.__dict__.update(copy.deepcopy(body_a.__dict__))
     b.load_state_tensors(p, v, ids)
@@ -296,7 +261,7 @@ def test_round_trip_into_a_fresh_crate(sc):
         a.physics_tick()
         b.physics_tick()
     for x, y in zip(a.engine.download(), b.engine.download()):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
 
 
 def test_import_refuses_ids_out_of_range(sc):
@@ -309,9 +274,9 @@ def test_import_refuses_ids_out_of_range(sc):
     for bad in (2 ** 31 - 1, -1, 2 ** 40):
         ids = np.arange(70, dtype=np.int64)
         ids[69] = bad
-        assert code_of(crate.engine.import_state, *tensors(p, v, ids)) == N.ERR_ARG
+        assert U.code_of(crate.engine.import_state, *tensors(p, v, ids)) == N.ERR_ARG
         for x, y in zip(before, crate.engine.download()):       # the context still holds its old state, pressures included
-            same_bytes(x, y)
+            U.same_bytes(x, y)
     ids[69] = 2 ** 31 - 2                                        # the largest id there is
     crate.engine.import_state(*tensors(p, v, ids))
     assert crate.engine.download()[3].tolist() == ids.tolist()
@@ -322,15 +287,15 @@ def test_import_beyond_the_capacity(sc):
     crate = spread_crate(sc, 100, capacity=128)
     before = crate.engine.download()
     p, v = cloud(15, 129)
-    assert code_of(crate.engine.import_state, *tensors(p, v)) == N.ERR_CAPACITY
+    assert U.code_of(crate.engine.import_state, *tensors(p, v)) == N.ERR_CAPACITY
     for x, y in zip(before, crate.engine.download()):
-        same_bytes(x, y)
+        U.same_bytes(x, y)
     old = crate.engine
     crate.load_state_tensors(*tensors(p, v))                    # the crate grows into a larger context
     assert crate.engine is not old and crate.engine.capacity >= 129 and crate.particle_count == 129
-    same_bytes(crate.particles, p)
-    same_bytes(crate.particle_velocities, v)
-    same_bytes(crate.state_tensors()[0].cpu().numpy(), p)
+    U.same_bytes(crate.particles, p)
+    U.same_bytes(crate.particle_velocities, v)
+    U.same_bytes(crate.state_tensors()[0].cpu().numpy(), p)
 
 
 # ---- 8. errors
@@ -338,7 +303,7 @@ def test_import_beyond_the_capacity(sc):
 def test_state_error_inside_a_tick(sc):
     import torch
     from sand_crate_amd import _native as N
-    crate = sc.Crate(scene(sc), noise="host-sync")
+    crate = sc.Crate(U.scene(sc), noise="host-sync")
     crate.physics_tick()
     eng = crate.engine
     count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -346,8 +311,8 @@ def test_state_error_inside_a_tick(sc):
     crate._send_tick_inputs()
     eng.step_begin()
     try:
-        assert code_of(eng.export_state, count=count, room=eng.capacity) == N.ERR_STATE
-        assert code_of(eng.import_state, p, v) == N.ERR_STATE
+        assert U.code_of(eng.export_state, count=count, room=eng.capacity) == N.ERR_STATE
+        assert U.code_of(eng.import_state, p, v) == N.ERR_STATE
         stats = eng.step_stats()
         eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
     finally:
@@ -363,9 +328,9 @@ def test_argument_and_capacity_errors(sc):
     eng.upload(*cloud(17, n))
     lib, ctx = eng._lib, eng._ctx
     dev = torch.device("cuda", eng.device)
-    p = torch.full((n, 2), SENTINEL_F, dtype=torch.float64, device=dev)
-    ids = torch.full((n,), SENTINEL_I, dtype=torch.int64, device=dev)
-    count = torch.full((1,), SENTINEL_I, dtype=torch.int64, device=dev)
+    p = torch.full((n, 2), U.SENTINEL_FAR, dtype=torch.float64, device=dev)
+    ids = torch.full((n,), U.SENTINEL, dtype=torch.int64, device=dev)
+    count = torch.full((1,), U.SENTINEL, dtype=torch.int64, device=dev)
     torch.cuda.synchronize(dev)
     ptr = lambda t: N._P(t.data_ptr())  # noqa: E731
     assert lib.sc_export_state_device(ctx, ptr(p), None, None, ptr(ids), n, None) == N.ERR_ARG        # no count pointer
@@ -376,12 +341,12 @@ def test_argument_and_capacity_errors(sc):
     assert lib.sc_import_state_device(ctx, ptr(p), None, None, n) == N.ERR_ARG
     assert lib.sc_import_state_device(ctx, ptr(p), ptr(p), None, -1) == N.ERR_ARG
     # room one below the bound of the stored count: refused before anything is launched
-    assert code_of(eng.export_state, p[:n - 1], ids=ids[:n - 1], count=count) == N.ERR_CAPACITY
+    assert U.code_of(eng.export_state, p[:n - 1], ids=ids[:n - 1], count=count) == N.ERR_CAPACITY
     assert lib.sc_last_error()
     eng.synchronize()
-    assert (p == SENTINEL_F).all() and (ids == SENTINEL_I).all() and int(count.item()) == SENTINEL_I
+    assert (p == U.SENTINEL_FAR).all() and (ids == U.SENTINEL).all() and int(count.item()) == U.SENTINEL
     eng.export_state(p, ids=ids, count=count)                                                         # with the room: fine
     eng.synchronize()
     assert int(count.item()) == n and np.array_equal(ids.cpu().numpy(), np.arange(n))
-    same_bytes(p.cpu().numpy(), eng.download()[0])
+    U.same_bytes(p.cpu().numpy(), eng.download()[0])
     eng.close()

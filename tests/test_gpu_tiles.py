@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import tile_cases as tc
+from gpu_support import sc  # noqa: F401
 from test_gpu_parity import wave_world
 
 pytestmark = pytest.mark.gpu
@@ -22,12 +23,6 @@ BIG = {f"lone{n}": functools.partial(tc.lone_bucket, n) for n in tc.LONE_BIG_SIZ
 # the worlds around 960 and 4095, lone and three-range: the DENS-only launch of host noise reads rows with its own slots_fit
 HOST_WORLDS = [f"{kind}{t + k}" for kind in ("lone", "ranges") for t in (960, 4095) for k in (-1, 0, 1, 2)]
 FUSED_WORLDS = [f"{kind}{t}" for kind in ("lone", "ranges") for t in tc.EDGES] + ["reach960", "reach4095"]
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 @functools.lru_cache(maxsize=None)

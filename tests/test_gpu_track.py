@@ -9,7 +9,6 @@ states, by particles appended behind them, and by a round trip of all 256 colour
 pressures of track_cases.py (NaN, the infinities, the neighbours of k / 255) are the spec's business in
 test_track_cpu.py.  Coordinates that are not finite cannot be downloaded (sc_download_state skips them): those cases are
 compared with the spec applied to the uploaded arrays, which is what a download would return."""
-import copy
 import struct
 from pathlib import Path
 
@@ -17,34 +16,24 @@ import numpy as np
 import pytest
 
 import gif_spec as G
+import gpu_support as U
 import jpeg_spec as J
 import render_spec as R
 import text_spec as T
 import track_cases as K
 import track_spec as S
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 
 
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def scene(sc, name="wave_machine"):
-    return sc.load_config(ROOT / "config" / f"{name}.yaml").world_config
-
-
 def world(sc, n, bodies=None, sources=False):
     """wave_machine's coefficients with discs sized for n particles; `bodies` replaces its walls."""
-    wc = copy.deepcopy(scene(sc))
-    d = float(np.sqrt(12.0 / (np.pi * max(n, 64))))                        # (a handful of particles keep sensible discs)
-    wc.coefficients.update(particle_radius=d / 2, dt=0.002 * (d / 0.01), max_particles=max(n, 1))
-    if not sources:
-        wc.particle_sources = []
+    wc = U.spread_world(sc, n, least=64)                                   # (a handful of particles keep sensible discs)
+    if sources:
+        wc.particle_sources = U.scene(sc).particle_sources                # (a fresh load: nobody else's)
     if bodies is not None:
         wc.rigid_bodies = bodies
     return wc
@@ -62,7 +51,7 @@ def segments_of(crate):
     return crate.segments if crate.rigid_bodies else np.zeros((0, 2, 2))
 
 
-def spec_frame(crate, valid_slots=None):
+def spec_pack(crate, valid_slots=None):
     """track_spec.pack of what the engine downloads and the walls as they stand."""
     xy, _, pressure, ids = crate.engine.download()
     return S.pack(crate.tick, xy, pressure, ids, segments_of(crate), pressure_valid=crate.tick > 0, valid_slots=valid_slots)
@@ -70,7 +59,7 @@ def spec_frame(crate, valid_slots=None):
 
 def check_capture(crate, want=None):
     got = crate.capture_frame()
-    want = spec_frame(crate) if want is None else want
+    want = spec_pack(crate) if want is None else want
     assert len(got) == len(want) == crate.engine.track_bound(S.header(got)["n"], S.header(got)["n_segments"])
     assert S.canonical(got) == S.canonical(want)
     assert crate.capture_frame() == got                                     # the same state twice: the same bytes
@@ -147,7 +136,7 @@ def test_appended_behind_ticked_ones(sc):
     crate._cache, crate._count_known = None, False
     _, _, pressure, ids = crate.engine.download()
     assert (pressure[ids < 300] > 0).any() and (pressure[ids >= 300] == 0).all()
-    p = S.parse(check_capture(crate, spec_frame(crate, valid_slots=ids < 300)))
+    p = S.parse(check_capture(crate, spec_pack(crate, valid_slots=ids < 300)))
     assert p["n"] == 370 and p["flags"] == 1 and (p["c"][p["ids"] >= 300] == 255).all() and (p["c"][p["ids"] < 300] < 255).any()
 
 
@@ -222,7 +211,7 @@ def test_log_equals_capturing_after_every_tick_and_changes_nothing(sc, noise):
     counts = [S.header(f)["n"] for f in frames]
     assert counts[-1] > counts[0] >= 300                                    # (the source is active)
     assert len({S.parse(f)["segments"].tobytes() for f in frames}) == 12    # (the wall moves)
-    assert S.canonical(frames[-1]) == S.canonical(spec_frame(logged))
+    assert S.canonical(frames[-1]) == S.canonical(spec_pack(logged))
     plain, _ = ticked(sc, noise)
     same_state(logged, plain)                                              # the log changes no result
     assert logged.tracked() == ([], 0)                                     # read and rewound
@@ -316,7 +305,7 @@ def test_grow_keeps_the_log(sc):
 def recorded(sc):
     """One frame of a ticked scene, its parsed form, and the particle radius that goes with it."""
     from sand_crate_amd import track
-    crate = sc.Crate(scene(sc), noise="counter", noise_seed=2)
+    crate = sc.Crate(U.scene(sc), noise="counter", noise_seed=2)
     for _ in range(60):
         crate.physics_tick()
     frame = crate.capture_frame()

@@ -9,26 +9,14 @@ import copy
 import numpy as np
 import pytest
 
+import gpu_support as U
 import growth_cases as G
 import recovery_cases as rc
 import trajectory_cases as K
 import trajectory_spec as T
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import torch
-    torch.cuda.init()  # torch's HIP runtime must come up before the library's in a process that uses both
-    import sand_crate_amd
-    return sand_crate_amd
-
-
-def same_bytes(a, b, where=""):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, where
-    assert a.tobytes() == b.tobytes(), where
 
 
 def world(sc, max_particles=3000):
@@ -54,9 +42,9 @@ def numpy_of(got):
 def check_frame(got, k, crate, window, tick, where=""):
     """Frame k of what `read()` gave against the spec fed by the crate's download, as the state stands."""
     states, press, count, outside = T.frame_of_export(*crate.engine.download(), window[0], window[1] - window[0])
-    same_bytes(got["states"][k], states, where)
+    U.same_bytes(got["states"][k], states, where)
     if "pressure" in got:
-        same_bytes(got["pressure"][k], press, where)
+        U.same_bytes(got["pressure"][k], press, where)
     assert (got["ticks"][k], got["counts"][k], got["outside"][k]) == (tick, count, outside), where
     return states, count, outside
 
@@ -67,7 +55,7 @@ def check_log(got, log, where=""):
     assert got["dropped"] == want["dropped"] and len(got["ticks"]) == len(want["ticks"]), where
     for name in ("states", "pressure", "ticks", "counts", "outside"):
         if name in want:
-            same_bytes(got[name], want[name], f"{where}: {name}")
+            U.same_bytes(got[name], want[name], f"{where}: {name}")
 
 
 # ---------------------------------------------------------------- 1. rows at the edges
@@ -90,13 +78,13 @@ def test_rows_at_the_edges(sc, rows):
             assert T.present(states).tolist() == [True] + [False] * (rows - 1) and outside == 0
         if n > 1:
             assert outside > 0 and T.present(states)[[0, -1]].all()
-            same_bytes(got["pressure"][0][T.present(states)], np.zeros(n - outside))   # just loaded: no pressure yet
+            U.same_bytes(got["pressure"][0][T.present(states)], np.zeros(n - outside))   # just loaded: no pressure yet
         crate.physics_tick()
         got = numpy_of(rec.read())
         assert got["states"].shape[0] == 2
         check_frame(got, 1, crate, window, crate.tick, f"n {n}, after a tick")
-        same_bytes(got["positions"], got["states"][:, :, 0:2])
-        same_bytes(got["velocities"], got["states"][:, :, 2:4])
+        U.same_bytes(got["positions"], got["states"][:, :, 0:2])
+        U.same_bytes(got["velocities"], got["states"][:, :, 2:4])
     crate.close()
 
 
@@ -144,8 +132,8 @@ def test_values_that_are_not_numbers(sc):
     assert (count, outside) == (int(live.sum()), 0) and T.present(got["states"][0]).tolist() == live.tolist()
     # ... and against the spec from the arrays as they were stored
     want = T.frame(xy[:, 0], xy[:, 1], vxy[:, 0], vxy[:, 1], np.zeros(n), np.arange(n), n, 0, False, 0, n)
-    same_bytes(got["states"][0], want[0])
-    same_bytes(got["pressure"][0], want[1])
+    U.same_bytes(got["states"][0], want[0])
+    U.same_bytes(got["pressure"][0], want[1])
     absent = got["states"][0][~live]
     assert (np.ascontiguousarray(absent).view(np.uint64) == T.FILL_BITS).all()
     assert (np.ascontiguousarray(got["pressure"][0][~live]).view(np.uint64) == T.FILL_BITS).all()
@@ -236,7 +224,7 @@ def test_a_run_with_gaps_in_the_ids(sc, every, no_reads):
         no_reads[0] = False
     twin_got = numpy_of(twin_rec.read())
     for name in ("states", "pressure", "ticks", "counts", "outside"):
-        same_bytes(twin_got[name], got[name], f"twin, every {every}: {name}")
+        U.same_bytes(twin_got[name], got[name], f"twin, every {every}: {name}")
     assert twin_got["dropped"] == 0
     twin_final = final_state(twin)
     twin.close()
@@ -245,8 +233,8 @@ def test_a_run_with_gaps_in_the_ids(sc, every, no_reads):
     for _ in range(K.RUN_TICKS):
         run_tick(plain, case)
     for a, b, c in zip(final_state(plain), twin_final, want_final):
-        same_bytes(a, b)
-        same_bytes(a, c)
+        U.same_bytes(a, b)
+        U.same_bytes(a, c)
     plain.close()
 
 
@@ -269,9 +257,9 @@ def test_recording_through_run(sc):
         logs.append((got, crate.engine.download()))
         crate.close()
     for name in ("states", "ticks", "counts", "outside"):
-        same_bytes(logs[0][0][name], logs[1][0][name], name)
+        U.same_bytes(logs[0][0][name], logs[1][0][name], name)
     for a, b in zip(logs[0][1], logs[1][1]):
-        same_bytes(a, b)
+        U.same_bytes(a, b)
 
 
 # ---------------------------------------------------------------- 5. the log's bounds
@@ -292,7 +280,7 @@ def test_a_full_log_drops_and_counts_and_restarts(sc):
     again = numpy_of(rec.read())                                     # reading does not restart
     assert again["dropped"] == 2
     for name in ("states", "pressure", "ticks", "counts", "outside"):
-        same_bytes(again[name], got[name], name)
+        U.same_bytes(again[name], got[name], name)
     rec.capture()                                                    # on demand into a full log: dropped as well
     assert rec.read()["dropped"] == 3 and len(rec.read()["ticks"]) == 3
     rec.restart()
@@ -392,19 +380,12 @@ def test_growth_keeps_the_recording(sc):
     assert grown["ticks"].tolist() == list(range(0, case.ticks + 1, 3)) and grown["dropped"] == twin["dropped"] == 0
     assert grown["counts"][-1] > 200
     for name in ("states", "pressure", "ticks", "counts", "outside"):
-        same_bytes(grown[name], twin[name], name)
+        U.same_bytes(grown[name], twin[name], name)
     for a, b in zip(final, twin_final):
-        same_bytes(a, b)
+        U.same_bytes(a, b)
 
 
 # ---------------------------------------------------------------- 7. refusals
-def code_of(call, *args, **kw):
-    from sand_crate_amd import _native as N
-    with pytest.raises(N.NativeError) as err:
-        call(*args, **kw)
-    return err.value.code
-
-
 def log_tensors(sc, frames, rows, device=0, sentinel=-7):
     import torch
     dev = torch.device("cuda", device)
@@ -419,10 +400,10 @@ def enable(eng, t, **kw):
     eng.traj_enable(t["states"], t["pressure"], t["ticks"], t["counts"], t["outside"], t["words"], **kw)
 
 
-def untouched(t, sentinel=-7):
+def log_untouched(t, sentinel=-7):
     import torch
     torch.cuda.synchronize()
-    return all(bool((v == sentinel).all()) for v in t.values() if v is not None)
+    return U.untouched(*(v for v in t.values() if v is not None), sentinel=sentinel)
 
 
 def test_refused_inside_a_tick_and_the_recording_goes_on(sc):
@@ -437,16 +418,16 @@ def test_refused_inside_a_tick_and_the_recording_goes_on(sc):
     crate._send_tick_inputs()
     eng.step_begin()
     try:
-        assert code_of(enable, eng, other, id0=0) == N.ERR_STATE
-        assert code_of(eng.traj_capture) == N.ERR_STATE
-        assert code_of(eng.traj_disable) == N.ERR_STATE
+        assert U.code_of(enable, eng, other, id0=0) == N.ERR_STATE
+        assert U.code_of(eng.traj_capture) == N.ERR_STATE
+        assert U.code_of(eng.traj_disable) == N.ERR_STATE
         stats = eng.step_stats()
         eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
     finally:
         eng.step_finish()
     crate._cache = None
     got = numpy_of(rec.read())                                       # the refused calls left the recording on, into its log
-    assert got["ticks"].tolist() == [2] and untouched(other)
+    assert got["ticks"].tolist() == [2] and log_untouched(other)
     check_frame(got, 0, crate, (0, 64), 2)
     crate.close()
 
@@ -466,10 +447,10 @@ def test_refused_after_a_promised_tick_and_in_slab_mode(sc):
     log = log_tensors(sc, 2, 8)
     torch.cuda.synchronize()
     eng.tick(now, nxt)
-    assert code_of(enable, eng, log, id0=0) == N.ERR_STATE
-    assert code_of(eng.traj_disable) == N.ERR_STATE
-    assert code_of(eng.traj_capture) == N.ERR_STATE                  # (it is not on)
-    assert untouched(log)
+    assert U.code_of(enable, eng, log, id0=0) == N.ERR_STATE
+    assert U.code_of(eng.traj_disable) == N.ERR_STATE
+    assert U.code_of(eng.traj_capture) == N.ERR_STATE                  # (it is not on)
+    assert log_untouched(log)
     eng.tick(nxt)
     enable(eng, log, id0=0)                                          # the promise is kept: now it can
     eng.tick(nxt)
@@ -491,7 +472,7 @@ def test_refused_after_a_promised_tick_and_in_slab_mode(sc):
         args[k] = None
         assert lib.sc_traj_enable_device(ctx, *args, 2, 0, 8, 1, 1) == N.ERR_ARG, k
     assert lib.sc_traj_enable_device(ctx, N._P(t["states"].data_ptr() + 8), *ok[1:], 1, 0, 8, 1, 1) == N.ERR_ARG
-    assert code_of(eng.traj_capture) == N.ERR_STATE                  # none of them switched it on
+    assert U.code_of(eng.traj_capture) == N.ERR_STATE                  # none of them switched it on
     crate.close()
     # slab mode
     eng = sc.Engine(capacity=64)
@@ -502,10 +483,10 @@ def test_refused_after_a_promised_tick_and_in_slab_mode(sc):
     enable(eng, log, id0=0)
     eng.set_slab(0, 10, 3, False, False)
     for call, args, kw in ((enable, (eng, log), dict(id0=0)), (eng.traj_capture, (), {}), (eng.traj_disable, (), {})):
-        assert code_of(call, *args, **kw) == N.ERR_STATE
+        assert U.code_of(call, *args, **kw) == N.ERR_STATE
         assert eng.count() == 20                                     # the context is fine
     eng.synchronize()
-    assert log["words"].cpu().tolist() == [0, 0, 0, 0] and untouched({k: v for k, v in log.items() if k != "words"})
+    assert log["words"].cpu().tolist() == [0, 0, 0, 0] and log_untouched({k: v for k, v in log.items() if k != "words"})
     eng.close()
 
 
@@ -523,4 +504,4 @@ def test_driver_writes_trajectory_npz(sc, tmp_path):
         for k in range(4):                                           # state.npz holds the same ticks' positions, by rank
             live = T.present(z["states"][k + 1])
             assert int(state["ticks"][k]) == z["ticks"][k + 1] and live.sum() == z["counts"][k + 1]
-            same_bytes(z["states"][k + 1][live][:, 0:2], state[f"particles_{k}"])
+            U.same_bytes(z["states"][k + 1][live][:, 0:2], state[f"particles_{k}"])

@@ -14,6 +14,7 @@ import pytest
 
 import test_wall_cases_cpu as premises
 import wall_cases as wc
+from gpu_support import sc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,12 +22,6 @@ COEF = ("dt", "particle_radius", "wall_collision_decay", "pressure_amplifier", "
         "collider_noise_level", "viscosity", "surface_smoothing", "target_pressure")
 TICKS = 3
 SEED = 11
-
-
-@pytest.fixture(scope="module")
-def sc():
-    import sand_crate_amd
-    return sand_crate_amd
 
 
 def _bodies(states):
