@@ -37,22 +37,18 @@ There is no CPU implementation behind this class: without libsandcrate_hip.so an
 """
 from __future__ import annotations
 
-import copy
-import json
 import time
 
 import numpy as np
 import yaml
 
 from . import _native as N
+from .addons import FRAMES, OBSERVABLES, DeviceLog, Overlay, PendingCheckpoint, _Checkpoints, _Frames, _Logs
+from .addons import arrow_ends  # noqa: F401  (part of this module's surface)
 from .engine import Engine
-from .hud_font import default_placement
 from .load_config import WorldConfig
 from .neighbourhood import _Neighbourhood
 from .particle_source import build_particle_sources
-from .probe import FIELDS, as_dict
-from . import track as _track
-from .trajectory import Trajectory, check_log, check_window
 from .rigid_body import build_rigid_bodies
 from .utils.geometry_utils import pad_segments
 
@@ -85,20 +81,7 @@ def tick_geometry(rigid_bodies, particle_radius, cache):
     return seg, np.concatenate(plus + minus), bodies
 
 
-def arrow_ends(pairs) -> np.ndarray:
-    """K x 2 x 2 (start, end) of the reference's debug arrows, an array-like K x 2 x 2 of (start, direction), as
-    Playback.draw_debug_arrows draws them (playback.py:95-107): entries with a NaN are dropped (:97), the direction is
-    compressed, d / (|d| + 0.001) ^ 0.3 (:99), and the arrow ends at start + that."""
-    a = np.asarray(pairs, dtype=np.float64).reshape(-1, 2, 2)
-    a = a[~np.isnan(a).any(axis=(1, 2))]
-    start, d = a[:, 0], a[:, 1]
-    with np.errstate(all="ignore"):
-        norm = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
-        d = d / np.power(norm + 0.001, 0.3)[:, None]
-        return np.stack([start, start + d], axis=1)
-
-
-class Crate(_Neighbourhood):
+class Crate(_Frames, _Logs, _Checkpoints, _Neighbourhood):
     def __init__(self, world_config: WorldConfig, *, device: int = 0, noise: str = "host", noise_seed: int = 0,
                  capacity: int | None = None) -> None:
         if noise not in _NOISE_MODES:
@@ -121,24 +104,21 @@ class Crate(_Neighbourhood):
         self._engine.set_noise_mode(_NOISE_MODES[noise], noise_seed)
         if noise == "host":        # the device takes over the global stream the reference draws from
             self._hand_rng_to_device()
-        self._count = 0            # particles on the device after the last tick / upload
-        self._count_known = True
-        self._cache = None         # (particles, velocities, pressure) downloaded for this tick
-        self._empty()
+        self._host_rng_mark = None  # where `sync_host_rng` left np.random, until the next emission has looked at it
+        # (_count: the particles on the device, if _count_known; _cache: what was downloaded for this tick, or None)
+        self._state_changed(0, (np.zeros((0, 2)), np.zeros((0, 2)), np.zeros((0,))))
         self._tick_seconds = 0.0   # EMA of wall time per tick, for debug_prints
         self._pad_cache = {}
         self._hud_kernels = False
         self._kernel_seconds = {}
         self._hud_forces = False
         self._force_ema = {}
-        self._pending_checkpoint = None
-        self._hud_sent = None      # (text bytes, x, y, scale) the engine draws on frames, or None: no HUD
-        self._arrows_sent = None   # ("list", bytes of the K x 2 x 2 ends) or ("velocity", scale, every), or None: no arrows
-        self._observe = None       # (capacity, bins, x0, x1) of the device log of observables, or None: not logging
-        self._observed = []        # rows read from an engine that is gone, or before the log was switched off
-        self._track = None         # (every, capacity_bytes) of the device log of packed frames, or None: not tracking
-        self._tracked = []         # (frames, dropped) read from an engine that is gone, or before the log was switched off
-        self._trajectory = None    # the `Trajectory` that records, or None
+        self._overlay = Overlay()
+        self._observed = DeviceLog(*OBSERVABLES)
+        self._tracked = DeviceLog(*FRAMES)
+        self._checkpoint = PendingCheckpoint()
+        self._trajectory = None    # the `Trajectory` that records, or None; it is listed in `_addons` while it does
+        self._addons = [self._overlay, self._observed, self._tracked, self._checkpoint]  # what `_grow` moves: addons.py
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference accessors
@@ -156,19 +136,22 @@ class Crate(_Neighbourhood):
     @property
     def particle_count(self) -> int:
         if not self._count_known:
-            self._count = self._engine.count()
-            self._count_known = True
+            self._state_changed(self._engine.count(), self._cache)  # (the state is the same: only its count was learned)
         return self._count
 
     # ------------------------------------------------------------------ state attributes
-    def _empty(self) -> None:
-        self._cache = (np.zeros((0, 2)), np.zeros((0, 2)), np.zeros((0,)))
+    def _state_changed(self, count: int | None = None, cache=None) -> None:
+        """The device state changed: the particle count is `count`, or not known, and what was downloaded is stale --
+        `cache` where the caller has the new state on the host (or, the state being the same, the cache that stands)."""
+        self._cache = cache
+        self._count_known = count is not None
+        if count is not None:
+            self._count = count
 
     def _state(self):
         if self._cache is None:
             p, v, pr, _ = self._engine.download()
-            self._cache = (p, v, pr)
-            self._count, self._count_known = len(p), True
+            self._state_changed(len(p), (p, v, pr))
         return self._cache
 
     @property
@@ -203,8 +186,7 @@ class Crate(_Neighbourhood):
         if len(particles) > self._engine.capacity:
             self._grow(len(particles))
         self._engine.upload(particles, velocities)
-        self._cache = (particles, velocities, np.zeros(len(particles)))
-        self._count, self._count_known = len(particles), True
+        self._state_changed(len(particles), (particles, velocities, np.zeros(len(particles))))
 
     def state_tensors(self, *, pressure: bool = True, ids: bool = False, sync: bool = True):
         """The state as torch CUDA tensors on the crate's device, without crossing to the host: ``(particles,
@@ -232,7 +214,7 @@ class Crate(_Neighbourhood):
             return (*(t for t in out if t is not None), count)
         eng.synchronize()
         n = int(count.item())
-        self._count, self._count_known = n, True
+        self._state_changed(n, self._cache)  # (the state is the same: only its count was learned)
         return tuple(t[:n] for t in out if t is not None)
 
     def load_state_tensors(self, particles, velocities, ids=None) -> None:
@@ -245,8 +227,7 @@ class Crate(_Neighbourhood):
         if n > self._engine.capacity:
             self._grow(n)
         self._engine.import_state(particles, velocities, ids)
-        self._cache = None
-        self._count, self._count_known = int(particles.shape[0]), True
+        self._state_changed(int(particles.shape[0]))
 
     def _hand_rng_to_device(self) -> None:
         name, key, pos, _, _ = np.random.get_state()
@@ -279,38 +260,29 @@ class Crate(_Neighbourhood):
         had the room from the start: a run does not depend on the capacity.  The state goes over through the old
         context's snapshot (sc_checkpoint_begin / sc_checkpoint_finish) -- particles and velocities with their ids, the
         tick number, the next id to hand out, the device's generator -- so counter noise, exported ids, the logs' tick
-        numbers and the phase of `track(every=)` continue; noise mode and seed, the logs, and what the old engine was
-        told (`Engine.adopt_settings`: stream, scan patience, timing, force monitor) are set again; HUD text and arrows
-        are sent again with the next frame.  Pressures are not part of a snapshot: as after any upload they are zero
-        until the next tick -- the callers grow right before one, or replace the state anyway.  `engine.timing()` counts
-        the launches of the context that is there.  Costs a synchronisation and a copy of the state through the host."""
+        numbers and the phase of the frame log continue; noise mode and seed and what the old engine was told
+        (`Engine.adopt_settings`: stream, scan patience, timing, force monitor) are set again; every add-on saves what
+        lives only in the old context (`leave`) and sets itself up in the new one (`enter`: addons.py).  Pressures are
+        not part of a snapshot: as after any upload they are zero until the next tick -- the callers grow right before
+        one, or replace the state anyway.  `engine.timing()` counts the launches of the context that is there.  Costs a
+        synchronisation and a copy of the state through the host."""
         old = self._engine
-        pending = getattr(self, "_pending_checkpoint", None)
-        if pending is not None and "snapshot" not in pending:  # begin_checkpoint's capture lives in the old context
-            pending["snapshot"] = old.checkpoint_finish()
+        for addon in self._addons:
+            addon.leave(old)
         old.checkpoint_begin()
         snap = old.checkpoint_finish()
-        self._engine = Engine(int(needed * 1.5) + 1024, device=old.device)
-        self._engine.set_noise_mode(_NOISE_MODES[self._noise], self._noise_seed)
-        self._engine.adopt_settings(old)
-        self._hud_sent = None  # (a new context has no HUD)
-        self._arrows_sent = None  # (... and no arrows)
+        new = self._engine = Engine(int(needed * 1.5) + 1024, device=old.device)
+        new.set_noise_mode(_NOISE_MODES[self._noise], self._noise_seed)
+        new.adopt_settings(old)
         if self._noise == "host" and snap["rng"] is not None:
-            self._engine.rng_set_state(*snap["rng"])
-        if getattr(self, "_observe", None) is not None:  # the log moves on: what the old context holds is kept
-            self._observed.append(old.probe_read())
-            self._engine.probe_enable(*self._observe)
-        if getattr(self, "_track", None) is not None:  # ... and so does the log of frames
-            self._tracked.append(self._read_track(old))
-            self._engine.track_enable(*self._track)
-        if getattr(self, "_trajectory", None) is not None:  # ... and the trajectory: same tensors, the words as they stand
-            self._trajectory._move_to(self._engine)
+            new.rng_set_state(*snap["rng"])
+        for addon in self._addons:
+            addon.enter(new)
         old.close()
         if len(snap["ids"]):
-            self._engine.upload_with_ids(snap["particles"], snap["velocities"], snap["ids"])
-        self._engine.restore_counters(snap["tick"], snap["next_id"])
-        self._count, self._count_known = len(snap["ids"]), True
-        self._cache = None
+            new.upload_with_ids(snap["particles"], snap["velocities"], snap["ids"])
+        new.restore_counters(snap["tick"], snap["next_id"])
+        self._state_changed(len(snap["ids"]))
 
     # ------------------------------------------------------------------ the tick
     def physics_tick(self) -> None:
@@ -320,9 +292,9 @@ class Crate(_Neighbourhood):
         for body in self.rigid_bodies:  # crate.py:363-365
             body.apply_velocity(self.dt)
         eng = self._engine
+        count = None                 # the particles after the tick, where the host learns them
         if self._noise == "host":    # the stream lives on the device: nothing comes back, nothing goes up --
             eng.tick(self._pack_tick_inputs())  # ... and the whole tick is one library call
-            self._count_known = False
             self.last_stats = None
         elif self._noise == "host-sync":
             self._send_tick_inputs()
@@ -334,16 +306,16 @@ class Crate(_Neighbourhood):
                 # where it stands -- and the count is the one the crate had
                 eng.set_noise_host(np.zeros((0, 2)))
                 eng.step_finish()
+                count = self._count if self._count_known else None
             else:
                 # crate.py:165-170 draws rand(C_i, 2) particle by particle; one block is the same stream
                 eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
                 eng.step_finish()
-                self._count, self._count_known = stats.particles, True
+                count = stats.particles
         else:
             eng.tick(self._pack_tick_inputs())
-            self._count_known = False
         self._accelerate_free_bodies()
-        self._cache = None
+        self._state_changed(count)
         self.tick += 1
         if self._hud_kernels:  # the HUD's phase split (timer.py:37-48), from HIP events; synchronises the tick
             eng.synchronize()
@@ -378,322 +350,12 @@ class Crate(_Neighbourhood):
         self._force_ema = {}
         self._engine.enable_force_monitor(self._hud_forces)
 
-    # ------------------------------------------------------------------ observables (sc_probe_*; tests/probe_spec.py)
-    def measure(self, bins: int = 0, x_range=(0.0, 1.0)) -> dict:
-        """The state as it stands, reduced on the device to the sixteen numbers of `probe.FIELDS` -- {name: value} -- and,
-        with `bins`, the profile of the free surface over `x_range`: `count` (bins,) int32 particles per column and
-        `top` (bins,) the smallest y in each (gravity points to +y), +inf where a column is empty.  Nothing but these
-        numbers is downloaded; synchronises.  The simulation is left alone."""
-        row, counts, tops = self._engine.probe_now(bins, float(x_range[0]), float(x_range[1]))
-        return as_dict(row, counts, tops)
-
-    def observe(self, on: bool = True, *, capacity: int = 4096, bins: int = 0, x_range=(0.0, 1.0)) -> None:
-        """Switch the device log: while on, every tick (`physics_tick` and each tick of `run`) appends what `measure`
-        would return to a log of `capacity` rows in device memory, with no synchronisation and no download until
-        `observations()` reads it.  A tick that finds the log full is dropped and counted.  Switching the log (on again
-        with other settings, or off) keeps what was logged so far for the next `observations()`."""
-        if self._observe is not None:
-            self._observed.append(self._engine.probe_read())
-        if on:
-            want = (int(capacity), int(bins), float(x_range[0]), float(x_range[1]))
-            self._observe = None
-            self._engine.probe_enable(*want)
-            self._observe = want
-        elif self._observe is not None:
-            self._observe = None
-            self._engine.probe_disable()
-
-    def observations(self) -> dict:
-        """What was logged since the last call, oldest first: a T-long float64 array per name of `probe.FIELDS`, `count`
-        (T x bins, int32) and `top` (T x bins) when the log has bins, and `dropped`, the ticks that found the log
-        full.  T = 0 when nothing was logged.  Synchronises.  (`tick` counts the ticks of the GPU context, and goes on
-        counting when the crate had to grow into a larger one: `_grow`.)"""
-        chunks, self._observed = self._observed, []
-        if self._observe is not None:
-            chunks.append(self._engine.probe_read())
-        bins = self._observe[1] if self._observe is not None else (chunks[-1][1].shape[1] if chunks else 0)
-        if any(c[1].shape[1] != bins for c in chunks):  # the bins changed between reads: the profiles of the last setting
-            chunks = [c if c[1].shape[1] == bins else (c[0], np.zeros((len(c[0]), bins), dtype=np.int32),
-                                                      np.full((len(c[0]), bins), np.inf), c[3]) for c in chunks]
-        rows = np.concatenate([c[0] for c in chunks]) if chunks else np.zeros((0, len(FIELDS)))
-        counts = np.concatenate([c[1] for c in chunks]) if chunks else np.zeros((0, bins), dtype=np.int32)
-        tops = np.concatenate([c[2] for c in chunks]) if chunks else np.zeros((0, bins))
-        return as_dict(rows, counts, tops, dropped=sum(c[3] for c in chunks))
-
-    # ------------------------------------------------------------------ packed frames (sc_track_*; tests/track_spec.py)
-    def capture_frame(self) -> bytes:
-        """The state as it stands as one packed frame (`track.parse` reads it, `track.Player` draws it): nine bytes per
-        particle -- id, position on a 16-bit grid over [-0.25, 1.25], the colour byte `render` would give it -- behind the
-        tick number and the walls as they stand.  Packed on the device; only the frame is downloaded.  Synchronises; the
-        simulation is left alone."""
-        self._send_tick_inputs()  # (the walls as they stand: before the first tick the engine has seen none)
-        return self._engine.track_capture()
-
-    def track(self, on: bool = True, *, every: int = 1, capacity_bytes: int = 1 << 26) -> None:
-        """Switch the device log of frames: while on, every tick whose number is a multiple of `every` (`physics_tick`
-        and each tick of `run`) appends what `capture_frame` would return to a log of `capacity_bytes` in device memory,
-        with no synchronisation and no download until `tracked()` reads it.  A frame that does not fit is dropped whole
-        and counted.  Switching the log (on again with other settings, or off) keeps what was logged so far for the next
-        `tracked()`."""
-        if self._track is not None:
-            self._tracked.append(self._read_track(self._engine))
-        if on:
-            want = (int(every), int(capacity_bytes))
-            self._track = None
-            self._engine.track_enable(*want)
-            self._track = want
-        elif self._track is not None:
-            self._track = None
-            self._engine.track_disable()
-
-    @staticmethod
-    def _read_track(engine):
-        blob, _, dropped = engine.track_read()
-        return _track.split(blob), dropped
-
-    def tracked(self) -> tuple[list[bytes], int]:
-        """-> (the frames logged since the last call, oldest first; how many were dropped because the log was full).
-        Synchronises.  (A frame's tick counts the ticks of the GPU context, and goes on counting when the crate had to
-        grow into a larger one: `_grow`.)"""
-        chunks, self._tracked = self._tracked, []
-        if self._track is not None:
-            chunks.append(self._read_track(self._engine))
-        return [f for c in chunks for f in c[0]], sum(c[1] for c in chunks)
-
-    # ------------------------------------------------------------------ trajectories (sc_traj_*; tests/trajectory_spec.py)
-    def record_trajectory(self, frames: int, *, ids=None, every: int = 1, pressure: bool = False,
-                          initial: bool = True) -> Trajectory:
-        """Record the run at full precision into torch CUDA tensors, one row per particle id: while the returned
-        `Trajectory` records, every tick whose number is a multiple of `every` (`physics_tick` and each tick of `run`)
-        writes one frame -- ``states[t, r]`` is (x, y, vx, vy) of the live particle with id ``lo + r``, exactly what
-        `state_tensors` would deliver for it, and NaN where that id is not live; with `pressure` its pressure too -- into
-        a log of `frames` frames, with no sort, no allocation and no synchronisation until `Trajectory.read()`.  A frame
-        that finds the log full is dropped and counted.  `ids` = (lo, hi) is the window of ids that get a row; the default
-        is (0, `max_particles` of the world's configuration) -- not the capacity: a run does not depend on it -- and live
-        particles outside it are counted per frame, not recorded.  `initial` captures the state as it stands as the first
-        frame.  One recording at a time: a second call stops the first, whose tensors stay readable.
-
-        The log is written on the library's stream, and the library's stream does not wait for torch's: read it after
-        `Trajectory.read()` or `synchronize()` -- or run the crate on torch's stream, `engine.set_stream`, and everything
-        torch enqueues afterwards sees it."""
-        frames, every = check_log(frames, every)
-        id0, rows = check_window(ids, int(self.world_config.coefficients["max_particles"]))
-        self.stop_trajectory()
-        self._trajectory = Trajectory(self._engine, frames, id0, rows, every, bool(pressure))
-        if initial:
-            self._trajectory.capture()
-        return self._trajectory
-
-    def stop_trajectory(self) -> None:
-        """Stops the recording `record_trajectory` started, if any, and synchronises: nothing is queued against its
-        tensors afterwards."""
-        traj, self._trajectory = getattr(self, "_trajectory", None), None
-        if traj is not None:
-            traj.stop()
-
     def close(self) -> None:
         """Stops a recording into torch's memory, then frees the GPU context."""
         try:
             self.stop_trajectory()
         finally:
             self._engine.close()
-
-    # ------------------------------------------------------------------ frames (Playback.draw_scene, playback.py:75-85)
-    def _set_hud(self, hud, width: int) -> None:
-        """The `hud` argument of `render`, `render_jpeg` and `render_gif`: True draws `debug_prints` (what
-        Playback.draw_debug_text shows, playback.py:215-219), a str draws that string, None or False nothing.  The text
-        goes at the reference's margin in the built-in bitmap font, scaled for a frame this wide
-        (hud_font.default_placement); characters outside ASCII become ``?``.  The engine is told only when the text or
-        its placement changed since the last frame."""
-        want = None
-        if hud is not None and hud is not False:
-            text = self.debug_prints if hud is True else hud
-            if not isinstance(text, str):
-                raise TypeError("hud must be None, a bool or a str")
-            data = text.encode("ascii", "replace")
-            if data:
-                want = (data, *default_placement(width))
-        if want != self._hud_sent:
-            self._hud_sent = None
-            if want is None:
-                self._engine.set_hud(None)
-            else:
-                self._engine.set_hud(*want)
-            self._hud_sent = want
-
-    def _set_arrows(self, arrows, every: int, scale) -> None:
-        """The `arrows`, `arrow_every` and `arrow_scale` arguments of `render`, `render_jpeg` and `render_gif`: the debug
-        arrows of Playback.draw_debug_arrows (playback.py:95-107), green, over the walls and under the HUD text.  None or
-        False draws none; True draws `debug_arrows`, the reference's list of (start, direction) in world units; an
-        array-like K x 2 x 2 of (start, direction) is drawn the same way (`arrow_ends`: NaN entries dropped, the
-        direction compressed on the host); "velocity" draws, without downloading anything, one arrow for every particle
-        whose index is a multiple of `every`, along velocity * `scale` compressed the same way on the device -- `scale`
-        defaults to `dt`, the step the particle is about to take.  Anything else is a TypeError.  The engine is told only
-        when the request changed since the last frame."""
-        want = None
-        if arrows is None or arrows is False:
-            pass
-        elif isinstance(arrows, str):
-            if arrows != "velocity":
-                raise TypeError('arrows must be None, a bool, "velocity" or an array-like K x 2 x 2 of (start, direction)')
-            want = ("velocity", float(self.dt if scale is None else scale), int(every))
-        else:
-            try:
-                ends = arrow_ends(self.debug_arrows if arrows is True else arrows)
-            except (TypeError, ValueError):
-                raise TypeError('arrows must be None, a bool, "velocity" or an array-like K x 2 x 2 of (start, direction)') \
-                    from None
-            if len(ends):
-                want = ("list", ends.tobytes())
-        if want != getattr(self, "_arrows_sent", None):
-            self._arrows_sent = None
-            if want is None:
-                self._engine.set_arrows(N.ARROWS_OFF)
-            elif want[0] == "list":
-                self._engine.set_arrows(N.ARROWS_LIST, np.frombuffer(want[1], dtype=np.float64))
-            else:
-                self._engine.set_arrows(N.ARROWS_VELOCITY, None, want[1], want[2])
-            self._arrows_sent = want
-
-    def render(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None, segment_width: int = 2,
-               out=None, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None):
-        """The frame the reference's viewer draws after `physics_tick()`, rendered on the GPU: every particle a disc of
-        ``int(width * particle_radius) * zoom`` pixels coloured by its pressure (white at 0, blue at 1 and above), the
-        walls (`segments`) on top in white, black elsewhere; ``height x width x 3`` uint8, row 0 at the top.
-
-        It shows the device state as `sc_download_state` would return it: the pressure is that of the last finished
-        tick, so right after the particles were set -- or after `from_checkpoint`, before the first tick -- every
-        particle is white.  `center` is in screen pixels (default: the frame's centre).  With `out` a CUDA uint8 tensor
-        of shape (height, width, 3) the frame is written there on the library's stream and the call returns without
-        synchronising: the library's stream does not wait for torch's, so the tensor must be ready when this is called
-        and read after `synchronize()` (or run the crate on torch's stream, `engine.set_stream`).  Otherwise it returns a
-        NumPy array.  `hud=True` writes the HUD text (`debug_prints`) over the frame at the top left, `hud` a str that
-        string (`_set_hud`); telling the engine a new text synchronises.  `arrows` draws the viewer's debug arrows
-        between the walls and the text: True the list `debug_arrows`, an array of (start, direction) that, "velocity" one
-        per `arrow_every`-th particle along its velocity times `arrow_scale` (`_set_arrows`).
-        The pixel rule, bit for bit: tests/render_spec.py, tests/arrow_spec.py for the arrows and tests/text_spec.py for
-        the text."""
-        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
-        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
-        self._set_hud(hud, width)
-        self._set_arrows(arrows, arrow_every, arrow_scale)
-        return self._engine.render(view, segments, out)
-
-    def render_jpeg(self, width: int = 1000, height: int = 1000, *, quality: int = 95, zoom: float = 1.0, center=None,
-                    segment_width: int = 2, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None) -> bytes:
-        """`render`'s frame as a JPEG file, encoded on the GPU: only the compressed bytes leave it.  Baseline JPEG, 4:4:4,
-        the standard tables at `quality` (1..100; 95 is cv2's default, what the reference's AVI writer uses).  `hud`,
-        `arrows`, `arrow_every` and `arrow_scale` as in `render`: text and arrows are on the frame before it is encoded.
-        The bitstream, byte for byte: tests/jpeg_spec.py applied to `render`'s frame."""
-        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
-        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
-        self._set_hud(hud, width)
-        self._set_arrows(arrows, arrow_every, arrow_scale)
-        return self._engine.render_jpeg(view, segments, quality)
-
-    def render_gif(self, width: int = 1000, height: int = 1000, *, zoom: float = 1.0, center=None,
-                   segment_width: int = 2, hud=None, arrows=None, arrow_every: int = 1, arrow_scale=None) -> bytes:
-        """`render`'s frame as the image data of one GIF frame, compressed on the GPU: only the LZW bytes leave it;
-        `gif.GifWriter` strings such frames into ``video.gif``.  The frame has a GIF's worth of colours by construction
-        -- black and (c, c, 255) -- so nothing is quantised: palette entry 0 is black, entry k is (k, k, 255).  The one
-        loss: (0, 0, 255), a pressure of 1 and above, is stored as entry 1, (1, 1, 255).  `hud` as in `render`: the text
-        is white like the walls, entry 255.  `arrows`, `arrow_every` and `arrow_scale` as in `render`: a frame with arrows
-        keeps entry 1 for them -- (0, 255, 0) in `gif.palette(arrows=True)` -- and stores a disc of colour byte c as
-        max(c, 2), so there (0, 0, 255) and (1, 1, 255) both become (2, 2, 255).
-        The bitstream, byte for byte: tests/gif_spec.py (`image_data(indices(frame))`) applied to `render`'s frame."""
-        view = Engine.view(width, height, self.particle_radius, zoom=zoom, center=center, segment_width=segment_width)
-        segments = self.segments if self.rigid_bodies else np.zeros((0, 2, 2))
-        self._set_hud(hud, width)
-        self._set_arrows(arrows, arrow_every, arrow_scale)
-        return self._engine.render_gif(view, segments)
-
-    # ------------------------------------------------------------------ checkpoint (the reference's commented zarr dump,
-    # playback.py:109-118, grown into something a run can resume from)
-    def begin_checkpoint(self) -> None:
-        """Capture the whole simulation state as of now.  Returns at once: the particle state is copied on the device
-        and travels to pinned host memory on a side stream while later ticks run; `finish_checkpoint` collects it."""
-        if self._pending_checkpoint is not None:
-            raise RuntimeError("a checkpoint is already under way")
-        self._engine.checkpoint_begin()
-        bodies = []
-        for body in self.rigid_bodies:
-            bodies.append({"segments": body.segments.tolist(), "position": [float(x) for x in body.position],
-                           "center_velocity": np.asarray(body.center_velocity, dtype=np.float64).tolist(),
-                           "angular_clockwise_velocity": float(body.angular_clockwise_velocity),
-                           "time_from_start": float(getattr(body, "time_from_start", 0.0))})
-        coefficients = {}
-        for name in self.editable_coefficients():
-            value = getattr(self, name)
-            coefficients[name] = value.tolist() if isinstance(value, np.ndarray) else value
-        host_rng = None
-        if self._noise != "host":  # the host owns the global stream (the device's copy travels with the particles)
-            _, key, pos, has_gauss, cached = np.random.get_state()
-            host_rng = {"key": key.tolist(), "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
-        wc = self.world_config
-        self._pending_checkpoint = {
-            "format": 1, "tick": int(self.tick), "noise": self._noise, "noise_seed": int(self._noise_seed),
-            "world_config": {"rigid_bodies": copy.deepcopy(wc.rigid_bodies), "particle_sources": copy.deepcopy(wc.particle_sources),
-                             "coefficients": coefficients},
-            "bodies": bodies, "host_rng": host_rng, "pressure": self._cache[2] if self._cache is not None else None}
-
-    def finish_checkpoint(self, path) -> None:
-        """Wait for the transfer `begin_checkpoint` started (not for later ticks) and write the .npz file."""
-        if self._pending_checkpoint is None:
-            raise RuntimeError("begin_checkpoint first")
-        meta, self._pending_checkpoint = self._pending_checkpoint, None
-        snap = meta.pop("snapshot", None)  # (collected already when the crate grew out of the context that took it)
-        if snap is None:
-            snap = self._engine.checkpoint_finish()
-        pressure = meta.pop("pressure")
-        meta["next_id"] = int(snap["next_id"])
-        meta["engine_tick"] = int(snap["tick"])
-        arrays = {"particles": snap["particles"], "velocities": snap["velocities"], "ids": snap["ids"]}
-        if pressure is not None and len(pressure) == len(snap["ids"]):
-            arrays["pressure"] = pressure
-        # the stream to restore is the one the run draws from: the device's in noise mode "host", else the host's (a crate
-        # that fell back from "host" to "host-sync" still has a -- stale -- device state: it is not written)
-        if snap["rng"] is not None and meta["noise"] == "host":
-            arrays["rng_key"] = snap["rng"][0]
-            meta["rng_pos"] = int(snap["rng"][1])
-        np.savez(path, meta=np.array(json.dumps(meta)), **arrays)
-
-    def save_checkpoint(self, path) -> None:
-        self.begin_checkpoint()
-        self.finish_checkpoint(path)
-
-    @classmethod
-    def from_checkpoint(cls, path, *, device: int = 0, capacity: int | None = None) -> "Crate":
-        """A crate that continues the run `save_checkpoint` captured: same particles (and ids), velocities, tick,
-        wall positions and motor clocks, coefficients as edited, and the random stream where it stood."""
-        with np.load(path, allow_pickle=False) as z:
-            meta = json.loads(str(z["meta"]))
-            arrays = {k: z[k] for k in z.files if k != "meta"}
-        wc = meta["world_config"]
-        crate = cls(WorldConfig(rigid_bodies=wc["rigid_bodies"], particle_sources=wc["particle_sources"],
-                                coefficients=wc["coefficients"]),
-                    device=device, noise=meta["noise"], noise_seed=meta["noise_seed"], capacity=capacity)
-        for body, saved in zip(crate.rigid_bodies, meta["bodies"]):
-            body.segments = np.array(saved["segments"], dtype=np.float64)
-            body.position = list(saved["position"])
-            body.center_velocity = np.array(saved["center_velocity"], dtype=np.float64)
-            body.angular_clockwise_velocity = saved["angular_clockwise_velocity"]
-            if hasattr(body, "time_from_start"):
-                body.time_from_start = saved["time_from_start"]
-        n = len(arrays["ids"])
-        if n > crate._engine.capacity:
-            crate._grow(n)
-        eng = crate._engine
-        eng.upload_with_ids(arrays["particles"], arrays["velocities"], arrays["ids"])
-        eng.restore_counters(meta["engine_tick"], meta["next_id"])
-        crate.tick = meta["tick"]
-        crate._count, crate._count_known = n, True
-        crate._cache = (arrays["particles"], arrays["velocities"], arrays.get("pressure", np.zeros(n)))
-        if meta["noise"] == "host" and "rng_key" in arrays:
-            eng.rng_set_state(arrays["rng_key"], meta["rng_pos"])
-        elif meta["host_rng"] is not None:
-            h = meta["host_rng"]
-            np.random.set_state(("MT19937", np.array(h["key"], dtype=np.uint32), h["pos"], h["has_gauss"], h["cached_gaussian"]))
-        return crate
 
     def run(self, n_ticks: int) -> None:
         """`n_ticks` ticks back to back without touching the host state in between (no sources
@@ -721,8 +383,7 @@ class Crate(_Neighbourhood):
             eng.tick(now, nxt)
             self.tick += 1
             now = nxt
-        self._cache = None
-        self._count_known = False
+        self._state_changed()
 
     def _accelerate_free_bodies(self) -> None:
         """crate.py:311-314: gravity accelerates bodies that are neither fixed nor motored.  (Each body owns its
@@ -741,7 +402,7 @@ class Crate(_Neighbourhood):
             active = [s for s in self.particle_sources if s.active_ticks > self.tick]
             if not active:
                 return
-            mark = getattr(self, "_host_rng_mark", None)
+            mark = self._host_rng_mark
             if mark is not None:  # sync_host_rng() was used: has the host drawn from the stream since?
                 _, key, pos, _, _ = np.random.get_state()
                 if pos != mark[1] or not np.array_equal(key, mark[0]):
@@ -749,17 +410,13 @@ class Crate(_Neighbourhood):
                 self._host_rng_mark = None
             try:
                 self._engine.emit_particles(active, self.dt, int(self.max_particles))
-                self._cache = None
-                self._count_known = False
-                return
+                return self._state_changed()
             except N.NativeError as err:
                 # (sc_emit_particles takes any number of sources: ERR_CAPACITY is the context's capacity)
                 if err.code == N.ERR_CAPACITY:
                     self._grow(max(self._engine.capacity, int(self.max_particles)) + 1024)
                     self._engine.emit_particles(active, self.dt, int(self.max_particles))
-                    self._cache = None
-                    self._count_known = False
-                    return
+                    return self._state_changed()
                 if err.code != N.ERR_DOMAIN:
                     raise
                 self._fall_back_to_host_stream()  # binomial(n, p) with p > 0.5: the host draws from here on
@@ -771,25 +428,21 @@ class Crate(_Neighbourhood):
                 if self._count + len(new_p) > self._engine.capacity:
                     self._grow(self._count + len(new_p))
                 self._engine.append(new_p, new_v)
-                self._count += len(new_p)
-                self._cache = None
+                self._state_changed(self._count + len(new_p))  # (`particle_count` above made the count known)
+
+    def _tick_inputs(self):
+        """-> (coef, segments, padded, bodies) of the tick: the coefficients by name, and `tick_geometry`."""
+        coef = {name: getattr(self, name) for name in _TICK_COEFFICIENTS}
+        return (coef, *tick_geometry(self.rigid_bodies, self.particle_radius, self._pad_cache))
 
     def _pack_tick_inputs(self):
-        coef = {name: getattr(self, name) for name in _TICK_COEFFICIENTS}
-        seg, pad, bodies = tick_geometry(self.rigid_bodies, self.particle_radius, self._pad_cache)
-        return self._engine.pack_inputs(coef, self.gravity, seg, pad, bodies)
+        coef, *geometry = self._tick_inputs()
+        return self._engine.pack_inputs(coef, self.gravity, *geometry)
 
     def _send_tick_inputs(self) -> None:
-        coef = {name: getattr(self, name) for name in _TICK_COEFFICIENTS}
+        coef, *geometry = self._tick_inputs()
         self._engine.set_params(gravity=self.gravity, **coef)
-        bodies = self.rigid_bodies
-        if bodies:
-            seg = self.segments
-            self._engine.set_segments(
-                seg, pad_segments(seg, self.particle_radius),
-                [(b.position, b.center_velocity, b.angular_clockwise_velocity, len(b)) for b in bodies])
-        else:
-            self._engine.set_segments(np.zeros((0, 2, 2)), np.zeros((0, 2, 2)), [])
+        self._engine.set_segments(*geometry)
 
     # ------------------------------------------------------------------ HUD text (crate.py:131-136)
     @property
@@ -819,12 +472,13 @@ class Crate(_Neighbourhood):
             self.debug_prints += f"\n\n{yaml.dump({'Forces': rounded})}"
         self.debug_prints += f"\n\n{self.get_coefficient_debug()}"
 
+    def _coefficients(self) -> dict:
+        """The editable coefficients as they stand, arrays as lists: for the HUD text and for a checkpoint."""
+        values = ((name, getattr(self, name)) for name in self.editable_coefficients())
+        return {name: val.tolist() if isinstance(val, np.ndarray) else val for name, val in values}
+
     def get_coefficient_debug(self) -> str:
-        rows = []
-        for name in self.editable_coefficients():
-            val = getattr(self, name)
-            rows.append({name: val.tolist() if isinstance(val, np.ndarray) else val})
-        return yaml.dump(rows)
+        return yaml.dump([{name: val} for name, val in self._coefficients().items()])
 
     def kernel_timing(self):
         return self._engine.timing()

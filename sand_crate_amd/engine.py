@@ -134,6 +134,9 @@ class Engine:
         self.scan_patience = None     # what `set_scan_patience` was given, or None: the library's default
         self.timing_on = False
         self.force_monitor_on = False
+        # set on use: the host buffer `_fetch_bytes` keeps; (capacity, bins) of the log of observables while it is on; the
+        # tensors of a recording while it runs and, stopped, until the next `synchronize()`
+        self._fetch_buf = self._probe_log = self._traj_log = self._traj_retired = None
 
     def adopt_settings(self, other: "Engine") -> None:
         """The settings `other` was given become this context's: the stream, the scan's patience, timing and the force
@@ -566,7 +569,7 @@ class Engine:
     def _fetch_bytes(self, call, guess: int) -> bytes:
         """Runs call(out, room, n_out) -- an encoder, or a reader of tracked frames -- into a host buffer kept between
         calls, of at least `guess` bytes, and once more into a larger one when the library asks for more than it holds."""
-        buf = getattr(self, "_fetch_buf", None)
+        buf = self._fetch_buf
         if buf is None or len(buf) < guess:
             buf = self._fetch_buf = np.empty(max(int(guess), 1), dtype=np.uint8)
         n = C.c_int64(0)
@@ -862,7 +865,7 @@ class Engine:
         """-> (rows (T, 16), counts (T, bins), tops (T, bins), dropped): what was logged since the last read, oldest
         first, at most `room` rows (default: the log's capacity), and the ticks that found the log full
         (sc_probe_read); synchronises."""
-        capacity, bins = getattr(self, "_probe_log", None) or (0, 0)
+        capacity, bins = self._probe_log or (0, 0)
         room = capacity if room is None else int(room)
         rows = np.zeros((max(room, 0), N.PROBE_FIELDS))
         counts = np.zeros((max(room, 0), bins), dtype=np.int32)
@@ -893,11 +896,9 @@ class Engine:
         device memory, without synchronising; a frame that does not fit is dropped whole and counted
         (sc_track_enable)."""
         N.check(self._lib.sc_track_enable(self._ctx, int(every), int(capacity_bytes)))
-        self._track_log = int(capacity_bytes)
 
     def track_disable(self) -> None:
         N.check(self._lib.sc_track_disable(self._ctx))
-        self._track_log = None
 
     def track_read(self):
         """-> (bytes: the frames logged since the last read, oldest first, back to back; how many; dropped frames)
@@ -951,7 +952,7 @@ class Engine:
         """Stops recording (sc_traj_disable).  Launches may still be queued against the tensors: the engine lets go of
         them at the next `synchronize()`."""
         N.check(self._lib.sc_traj_disable(self._ctx))
-        self._traj_retired, self._traj_log = getattr(self, "_traj_log", None), None
+        self._traj_retired, self._traj_log = self._traj_log, None
 
     # -- force monitor
     def enable_force_monitor(self, on: bool = True) -> None:

@@ -128,6 +128,7 @@ class HeadlessPlayback:
         self.track = max(int(track or 0), 0)  # a packed frame every this-many-th tick into track.sctk; 0: none
         self.track_frames = 0
         self.track_dropped = 0
+        self._track_writer = None  # the TrackWriter of track.sctk while a variant with --track runs
         self.trajectory = max(int(trajectory or 0), 0)  # a full-precision frame every this-many-th tick; 0: none
         self.recorded: Optional[dict] = None  # what trajectory.npz holds, once the variant has run
         self.done = False
@@ -177,7 +178,7 @@ class HeadlessPlayback:
             self.crate.observe(capacity=max(min(n, OBSERVE_EVERY), 1), bins=observe, x_range=(0.0, 1.0))
         for k in range(n):
             self.crate.physics_tick()
-            if getattr(self, "_track_writer", None) is not None and self.crate.tick % self.track == 0:
+            if self._track_writer is not None and self.crate.tick % self.track == 0:
                 self._track_tick()
             if observe is not None and (k + 1) % OBSERVE_EVERY == 0:
                 self.observed.append(self.crate.observations())
@@ -230,7 +231,7 @@ class HeadlessPlayback:
             self._track_drain()
 
     def _track_end(self) -> None:
-        writer = getattr(self, "_track_writer", None)
+        writer = self._track_writer
         if writer is None:
             return
         try:

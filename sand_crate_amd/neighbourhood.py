@@ -1,6 +1,6 @@
 """The neighbourhood calls of `Crate` -- `pair_tensors`, `cluster_tensors`, `cluster_sums`, `cluster_observables`,
 `neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram` and `ray_tensors` -- as a mixin `Crate`
-inherits (crate.py is the reference's surface plus recording and rendering), and the protocol all of them follow,
+inherits (crate.py is the reference's surface, the tick and growth), and the protocol all of them follow,
 written once: `_Search`.
 
 Every call counts the pairs on the grid (`Engine.pairs_count`) and then runs one or more readers of that grid
@@ -122,7 +122,7 @@ class _Search:
                 of_either=_OF_EITHER.get(self.who, " of a point or a query") if queries else "",
                 of_queries=" (of queries for query_batch)" if queries else "", far=self.far))
         if self.points is None:
-            self.crate._count, self.crate._count_known = got[0], True
+            self.crate._state_changed(got[0], self.crate._cache)  # (the state is the same: only its count was learned)
         return n, status
 
     def park(self, *held) -> None:
@@ -144,8 +144,8 @@ class _Search:
 
 class _Neighbourhood:
     """`Crate`'s neighbourhood calls.  Uses of the crate: `_engine`, `diameter`, `state_tensors`, `segments` and
-    `rigid_bodies` (the walls of `ray_tensors`), and `_count` / `_count_known`, which a synchronising search of the state
-    brings up to date."""
+    `rigid_bodies` (the walls of `ray_tensors`), and `_state_changed`, through which a synchronising search of the state
+    brings the particle count up to date."""
 
     def pair_tensors(self, radius: float | None = None, *, points=None, half: bool = False, squared_distances: bool = False,
                      max_pairs: int | None = None, batch=None):

@@ -322,6 +322,7 @@ class SlabCrate:
         self.gravity = np.array(world_config.coefficients["gravity"], dtype=np.float64)
         self.tick = 0
         self._pad_cache = {}
+        self._xchg_events = None  # the event pairs of `time_exchanges`, or None: not timing
 
         p = np.ascontiguousarray(particles, dtype=np.float64).reshape(-1, 2)
         v = np.ascontiguousarray(velocities, dtype=np.float64).reshape(-1, 2)
@@ -525,7 +526,7 @@ class SlabCrate:
             sl, rl, sr, rr = self._sizes
             out.update(records_to_left=int(sl) if self.left is not None else 0, records_from_left=int(rl) if self.left is not None else 0,
                        records_to_right=int(sr) if self.right is not None else 0, records_from_right=int(rr) if self.right is not None else 0)
-        ev = getattr(self, "_xchg_events", None)
+        ev = self._xchg_events
         if ev:
             out["exchange_us_mean"] = round(1000.0 * sum(a.elapsed_time(b) for a, b in ev) / len(ev), 2)
             out["exchanges_timed"] = len(ev)
@@ -537,7 +538,7 @@ class SlabCrate:
         """One message each way with each existing neighbor, of the sizes agreed for this tick."""
         if self.world == 1 or self._chained:
             return
-        ev = getattr(self, "_xchg_events", None)
+        ev = self._xchg_events
         if ev is None:
             return self._exchange_now()
         torch = self.backend.torch

@@ -244,13 +244,14 @@ class Player:
     engine grows to the largest frame seen)."""
 
     def __init__(self, capacity: int | None = None, device: int = 0, particle_radius: float | None = None) -> None:
+        from .addons import Overlay
         from .engine import Engine
         self._Engine = Engine
         self.device = int(device)
         self.particle_radius = particle_radius
         self._fixed = capacity is not None
         self._engine = Engine(max(int(capacity or 1024), 1), device=self.device)
-        self._hud_sent = None
+        self._overlay = Overlay()  # (the HUD text the engine was last told to draw)
 
     @property
     def engine(self):
@@ -266,29 +267,18 @@ class Player:
         if len(frame) >= HEADER and frame[:4] == MAGIC and n > self._engine.capacity and not self._fixed:
             self._engine.close()
             self._engine = self._Engine(int(n * 1.25) + 1024, device=self.device)
-            self._hud_sent = None
+            self._overlay.enter(self._engine)  # (a new context has no HUD)
         self._engine.track_load(frame, plain)
         seg = np.frombuffer(frame, dtype="<f8", count=4 * nseg, offset=HEADER).reshape(nseg, 2, 2)
         return dict(tick=tick, n=n, flags=flags, segments=seg)
 
     def _prepare(self, frame, width, zoom, center, segment_width, hud, plain, particle_radius, height):
-        from .hud_font import default_placement
+        from .addons import hud_request
         radius = self.particle_radius if particle_radius is None else particle_radius
         if radius is None:
             raise TrackError("the frame does not carry the particle radius: give particle_radius to Player or to the call")
         info = self.load(frame, plain)
-        want = None
-        if hud is not None and hud is not False:
-            text = hud_text(frame) if hud is True else hud
-            if not isinstance(text, str):
-                raise TypeError("hud must be None, a bool or a str")
-            data = text.encode("ascii", "replace")
-            if data:
-                want = (data, *default_placement(width))
-        if want != self._hud_sent:
-            self._hud_sent = None
-            self._engine.set_hud(*(want or (None,)))
-            self._hud_sent = want
+        self._overlay.send(self._engine, "hud", hud_request(hud, hud_text(frame) if hud is True else None, width))
         view = self._Engine.view(width, height, radius, zoom=zoom, center=center, segment_width=segment_width)
         return view, info["segments"]
 

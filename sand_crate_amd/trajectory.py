@@ -50,7 +50,7 @@ def complete_rows(states):
 
 class Trajectory:
     """The log of one recording: the tensors, and the engine that writes into them (`Crate._grow` moves it to the new
-    one).  Made by `Crate.record_trajectory`."""
+    one: `leave`, `enter`).  Made by `Crate.record_trajectory`."""
 
     def __init__(self, engine, frames: int, id0: int, rows: int, every: int = 1, pressure: bool = False):
         import torch
@@ -81,10 +81,13 @@ class Trajectory:
         self._engine.traj_enable(self.states, self.pressure, self.ticks, self.counts, self.outside, self.words,
                                  id0=self._id0, every=self._every, reset=reset)
 
-    def _move_to(self, engine) -> None:
-        """The recording goes on in `engine`, the context that replaces the one it ran in, where the words stand."""
+    def leave(self, old_engine) -> None:
+        """An add-on of the crate (addons.py) whose log is torch's: nothing lives in the context that goes."""
+
+    def enter(self, new_engine) -> None:
+        """... and the recording goes on in the one that replaces it, where the words stand."""
         if self._engine is not None:
-            self._engine = engine
+            self._engine = new_engine
             self._enable(reset=False)
 
     def _need_engine(self):

@@ -373,10 +373,10 @@ class RecordingEngine:
 
 def recording_crate():
     from sand_crate_amd import Crate
+    from sand_crate_amd.addons import Overlay
     crate = object.__new__(Crate)  # (no GPU context: only what the frame calls touch)
     crate._engine = RecordingEngine()
-    crate._hud_sent = None
-    crate._arrows_sent = None
+    crate._overlay = Overlay()
     crate._debug_prints = ""
     crate.debug_arrows = []
     crate.particle_radius = 0.01
@@ -421,9 +421,30 @@ def test_crate_sends_the_arrows_only_when_they_change():
 
 
 def test_grow_forgets_what_was_sent():
-    from sand_crate_amd import Crate
-    src = inspect.getsource(Crate._grow)
-    assert "_arrows_sent = None" in src and "_hud_sent = None" in src
+    """The overlay across a growth (`leave` the old context, `enter` the new one): a HUD and arrows that were sent are
+    both sent again, to the new engine, with the next frame -- once -- and the old engine hears nothing more."""
+    from sand_crate_amd import _native as N
+
+    class Both(RecordingEngine):
+        def set_hud(self, text, x=6, y=6, scale=1):
+            self.calls.append(("hud", text, x, y, scale))
+
+    crate = recording_crate()
+    crate._engine = old = Both()
+    new = Both()
+    crate.render(64, 48, hud="grown", arrows="velocity", arrow_every=4)
+    sent = [("hud", b"grown", 6, 6, 1), (N.ARROWS_VELOCITY, None, 0.002, 4)]
+    assert old.calls == sent
+    crate._overlay.leave(old)
+    crate._engine = new
+    crate._overlay.enter(new)
+    assert old.calls == sent and new.calls == []              # (nothing until a frame asks for it)
+    crate.render_gif(64, 48, hud="grown", arrows="velocity", arrow_every=4)
+    crate.render(64, 48, hud="grown", arrows="velocity", arrow_every=4)
+    assert new.calls == sent and old.calls == sent
+    crate._overlay.enter(new)                                  # a context that draws nothing is not told to draw nothing
+    crate.render(64, 48)
+    assert new.calls == sent
 
 
 def test_engine_binding_lists_the_call():

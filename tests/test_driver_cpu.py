@@ -82,3 +82,63 @@ def test_host_body_motion_and_tick_geometry_match_the_reference():
                 assert np.array_equal(seg, g[f"segments_t{t}"]), (scene, t)
                 assert np.array_equal(pad, pad_segments(seg, r))
                 assert [n for *_, n in packed] == [len(b) for b in bodies]
+
+
+def test_both_tick_input_routes_send_the_same_bits():
+    """`_send_tick_inputs` hands the engine the geometry `_pack_tick_inputs` packs -- `tick_geometry` with its cache of
+    padded halves -- where it used to pad the stacked segments: bit for bit the same arrays, for the bodies of both
+    scenes as they move, for a world without bodies, and for a body edited in place between two calls."""
+    from sand_crate_amd import Crate
+    from sand_crate_amd.load_config import load_config
+    from sand_crate_amd.rigid_body import build_rigid_bodies
+    from sand_crate_amd.utils.geometry_utils import pad_segments
+
+    class Engine:
+        def set_params(self, **coef):
+            self.coef = coef
+
+        def set_segments(self, segments, padded, bodies):
+            self.sent = (segments, padded, bodies)
+
+        def pack_inputs(self, coef, gravity, segments, padded, bodies):
+            return coef, (segments, padded, bodies)
+
+    def stacked(crate):                                          # the route `_send_tick_inputs` took before
+        if not crate.rigid_bodies:
+            return np.zeros((0, 2, 2)), np.zeros((0, 2, 2)), []
+        seg = crate.segments
+        return seg, pad_segments(seg, crate.particle_radius), [
+            (b.position, b.center_velocity, b.angular_clockwise_velocity, len(b)) for b in crate.rigid_bodies]
+
+    def check(crate):
+        want = stacked(crate)
+        crate._send_tick_inputs()
+        coef, packed = crate._pack_tick_inputs()
+        for got in (crate._engine.sent, packed):
+            assert got[0].dtype == want[0].dtype == got[1].dtype == want[1].dtype == np.float64
+            assert got[0].shape == want[0].shape and got[0].tobytes() == want[0].tobytes()
+            assert got[1].shape == want[1].shape and got[1].tobytes() == want[1].tobytes()
+            assert len(got[2]) == len(want[2])
+            for a, b in zip(got[2], want[2]):
+                assert a[0] is b[0] and a[1] is b[1] and a[2:] == b[2:]
+        assert crate._engine.coef == {"gravity": crate.gravity, **coef}
+
+    for scene in ("stirring_cup", "wave_machine", None):
+        wc = load_config(ROOT / "config" / f"{scene or 'stirring_cup'}.yaml").world_config
+        crate = object.__new__(Crate)  # (no GPU context: only what the tick inputs touch)
+        crate._engine, crate._pad_cache = Engine(), {}
+        crate.rigid_bodies = build_rigid_bodies(wc.rigid_bodies) if scene else []
+        for name, value in wc.coefficients.items():
+            setattr(crate, name, value)
+        check(crate)
+        for _ in range(3):                                       # moving bodies get new arrays, fixed ones hit the cache
+            for body in crate.rigid_bodies:
+                body.apply_velocity(crate.dt)
+            check(crate)
+        if scene:
+            assert len(crate._pad_cache) == len(crate.rigid_bodies)
+            for body in crate.rigid_bodies:                      # the same array, other contents: the cache must notice
+                body.segments[0, 1] += 0.03125
+                check(crate)
+            crate.particle_radius *= 1.5                         # ... and another pad distance
+            check(crate)

@@ -286,6 +286,68 @@ def test_checkpoint_begun_before_a_growth_is_finished_after_it(sc, tmp_path):
         U.same_bytes(arrays[name], twin_arrays[name])
 
 
+# ------------------------------------------------------------------ every add-on at once
+def everything_run(sc, case, capacity, path, ticks_after=4):
+    """Every add-on of the crate on at once, a checkpoint begun right before the tick of the first growth, a handful of
+    ticks across it -> what each add-on delivers afterwards."""
+    first = G.TWO_GROWTHS[0][0]
+    crate = make_crate(sc, case, "counter", capacity)
+    crate.observe(capacity=64, bins=8)
+    crate.track(every=2, capacity_bytes=1 << 22)
+    recording = crate.record_trajectory(first + ticks_after + 2, initial=True)
+    crate.show_kernel_times(True)
+    crate.show_forces(True)
+    look = dict(hud=HUD, arrows="velocity", arrow_every=3, arrow_scale=0.05)
+    crate.render(96, 80, **look)                                  # the text and the arrows are set before the growth
+    while crate.tick < first:
+        tick(crate, case)
+    engine = crate.engine
+    crate.begin_checkpoint()
+    for _ in range(ticks_after):
+        tick(crate, case)
+    crate.finish_checkpoint(path)
+    log = recording.read()
+    out = dict(grew=crate.engine is not engine, obs=crate.observations(), tracked=crate.tracked(),
+               trajectory={name: log[name].cpu().numpy() for name in ("states", "ticks", "counts", "outside")},
+               trajectory_dropped=log["dropped"], frame=crate.render(96, 80, **look), bare=crate.render(96, 80),
+               checkpoint=meta_of(path), final=final_state(crate))
+    crate.close()
+    return out
+
+
+def test_every_add_on_at_once_across_a_growth(sc, tmp_path):
+    """The rule that moves the add-ons to a grown context (`leave` / `enter`, sand_crate_amd/addons.py), all of them
+    subject to it in one growth: both logs, a trajectory, the two HUD meters, text and velocity arrows on the frames and
+    a checkpoint under way deliver, byte for byte, what they deliver in a twin that had the room."""
+    import probe_spec
+    import track_spec
+    case = CASES["sources_two_growths"]
+    first, ticks = G.TWO_GROWTHS[0][0], G.TWO_GROWTHS[0][0] + 4
+    grown, twin = (everything_run(sc, case, capacity, tmp_path / f"all_{capacity}.npz") for capacity in case.capacities)
+    assert grown["grew"] and not twin["grew"]
+    assert grown["obs"]["tick"].tolist() == list(range(1, ticks + 1)) and grown["obs"]["dropped"] == 0
+    for name in (*probe_spec.FIELDS, "count", "top"):
+        U.same_bytes(grown["obs"][name], twin["obs"][name], name)
+    frames, dropped = grown["tracked"]
+    assert dropped == 0 and [track_spec.header(f)["tick"] for f in frames] == list(range(2, ticks + 1, 2))
+    assert (frames, dropped) == twin["tracked"]
+    assert grown["trajectory"]["ticks"].tolist() == list(range(ticks + 1)) and grown["trajectory_dropped"] == 0
+    assert grown["trajectory"]["counts"][-1] > 16 and grown["trajectory_dropped"] == twin["trajectory_dropped"]
+    for name, log in grown["trajectory"].items():
+        U.same_bytes(log, twin["trajectory"][name], name)
+    U.same_bytes(grown["frame"], twin["frame"])
+    U.same_bytes(grown["bare"], twin["bare"])
+    assert (grown["frame"] == (0, 255, 0)).all(axis=-1).any() and not (grown["bare"] == (0, 255, 0)).all(axis=-1).any()
+    assert ((grown["frame"] == 255).all(axis=-1) & ~(grown["bare"] == 255).all(axis=-1)).any()   # ... and the text's ink
+    (meta, arrays), (twin_meta, twin_arrays) = grown["checkpoint"], twin["checkpoint"]
+    assert meta == twin_meta and meta["tick"] == meta["engine_tick"] == first
+    assert sorted(arrays) == sorted(twin_arrays) and len(arrays["ids"]) > 8
+    for name in arrays:
+        U.same_bytes(arrays[name], twin_arrays[name], name)
+    for a, b in zip(grown["final"], twin["final"]):
+        U.same_bytes(a, b)
+
+
 # ------------------------------------------------------------------ crate.particles = more than the capacity
 def set_state_run(sc, case, capacity):
     crate = ticked_set_state_crate(sc, case, capacity)

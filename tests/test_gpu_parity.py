@@ -541,7 +541,7 @@ def test_pile_up_state_ticks_with_bucket_sort(sc):
         ref = live_ids[np.lexsort((live_ids, pos[:, 0], r))]
         assert np.array_equal(sorted_ids, ref), f"tick {t}"
         eng.step_finish()
-        crate._cache = None
+        crate._state_changed()
 
 
 # ------------------------------------------------------------------ C-ABI contract: errors and edge cases

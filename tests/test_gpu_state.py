@@ -237,8 +237,7 @@ def test_load_state_tensors_equals_upload(sc):
         for x, y in zip(a.engine.download(), b.engine.download()):
             U.same_bytes(x, y)
         for crate in (a, b):
-            crate._cache = None
-            crate._count_known = False
+            crate._state_changed()
             crate.physics_tick()
         for x, y in zip(a.engine.download(), b.engine.download()):
             U.same_bytes(x, y)

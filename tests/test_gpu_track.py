@@ -119,7 +119,7 @@ def test_sparse_ids(sc):
     ids = K.sparse_ids(4, n)
     crate = crate_of(sc, xy, vxy)
     crate.engine.upload_with_ids(xy, vxy, ids)
-    crate._cache = None
+    crate._state_changed()
     p = S.parse(check_capture(crate))
     assert p["ids"].tolist() == ids.tolist() and p["ids"].max() == 1_000_000 and (p["ids"] > 65_536).sum() > 200
     crate.physics_tick()
@@ -133,7 +133,7 @@ def test_appended_behind_ticked_ones(sc):
     crate.physics_tick()
     more, more_v = K.cloud(13, 70)
     crate.engine.append(more, more_v)
-    crate._cache, crate._count_known = None, False
+    crate._state_changed()
     _, _, pressure, ids = crate.engine.download()
     assert (pressure[ids < 300] > 0).any() and (pressure[ids >= 300] == 0).all()
     p = S.parse(check_capture(crate, spec_pack(crate, valid_slots=ids < 300)))

@@ -425,7 +425,7 @@ def test_refused_inside_a_tick_and_the_recording_goes_on(sc):
         eng.set_noise_host(np.random.rand(stats.neighbor_slots, 2))
     finally:
         eng.step_finish()
-    crate._cache = None
+    crate._state_changed()
     got = numpy_of(rec.read())                                       # the refused calls left the recording on, into its log
     assert got["ticks"].tolist() == [2] and log_untouched(other)
     check_frame(got, 0, crate, (0, 64), 2)

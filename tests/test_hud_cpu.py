@@ -183,11 +183,14 @@ class RecordingEngine:
 
 def recording_crate():
     from sand_crate_amd import Crate
+    from sand_crate_amd.addons import Overlay
     crate = object.__new__(Crate)  # (no GPU context: only what the frame calls touch)
     crate._engine = RecordingEngine()
-    crate._hud_sent = None
+    crate._overlay = Overlay()
     crate._debug_prints = "Tick: 3\nParticles: 5\n"
+    crate.debug_arrows = []
     crate.particle_radius = 0.01
+    crate.dt = 0.002
     crate.rigid_bodies = []
     return crate
 
@@ -215,6 +218,67 @@ def test_crate_sends_the_hud_only_when_it_changes():
     assert len(calls) == 5
     with pytest.raises(TypeError):
         crate.render(64, 48, hud=7)
+
+
+def test_player_sends_the_hud_only_when_it_changes():
+    """`track.Player` shares the crate's overlay code: the same call sequence, with the frame's own two lines for True,
+    and again from the start in the engine a larger frame makes it open."""
+    import track_spec
+    from sand_crate_amd.addons import Overlay
+    from sand_crate_amd.engine import Engine
+    from sand_crate_amd.track import Player
+
+    class PlayerEngine(RecordingEngine):
+        capacity = 8
+
+        def track_load(self, frame, plain=False):
+            pass
+
+        def close(self):
+            pass
+
+    made = []
+
+    class Opened(PlayerEngine):                               # what `load` opens for a frame beyond the capacity
+        view = staticmethod(Engine.view)
+
+        def __init__(self, capacity, device=0):
+            super().__init__()
+            self.capacity = capacity
+            made.append(self)
+
+    def frame(tick, n):
+        xy = np.full((n, 2), 0.5)
+        return track_spec.pack(tick, xy, np.zeros(n), np.arange(n), np.zeros((0, 2, 2)))
+
+    player = object.__new__(Player)  # (no GPU context: only what the frame calls touch)
+    player._Engine, player._engine, player._overlay = Opened, PlayerEngine(), Overlay()
+    player.device, player.particle_radius, player._fixed = 0, 0.01, False
+    calls = player._engine.calls
+    small = frame(3, 5)
+    assert player.render(small, 64, 48) == "frame" and player.render_gif(small, 64, 48, hud=False) == b"gif" and not calls
+    player.render(small, 64, 48, hud=True)
+    assert calls == [(b"Tick: 3\nParticles: 5", 6, 6, 1)]
+    player.render_jpeg(small, 64, 48, hud=True)
+    player.render_gif(small, 64, 48, hud="Tick: 3\nParticles: 5")
+    assert len(calls) == 1                                  # the same text, placement and scale
+    player.render_gif(small, 1440, 48, hud=True)
+    assert calls[-1] == (b"Tick: 3\nParticles: 5", 6, 6, 2) and len(calls) == 2  # the scale follows the width
+    player.render(small, 64, 48, hud="café ☃")
+    assert calls[-1] == (b"caf? ?", 6, 6, 1) and len(calls) == 3  # encode("ascii", "replace")
+    player.render(frame(4, 5), 64, 48, hud=True)
+    assert calls[-1][0] == b"Tick: 4\nParticles: 5" and len(calls) == 4
+    player.render(small, 64, 48)                             # a call without one clears it, once
+    player.render_jpeg(small, 64, 48, hud=None)
+    assert calls[-1][0] is None and len(calls) == 5
+    player.render(small, 64, 48, hud="")                     # nothing to draw is no HUD
+    assert len(calls) == 5
+    with pytest.raises(TypeError):
+        player.render(small, 64, 48, hud=7)
+    player.render(small, 64, 48, hud="kept")
+    assert len(calls) == 6 and not made
+    player.render(frame(5, 9), 64, 48, hud="kept")           # nine particles: a new engine, which has no HUD yet
+    assert len(made) == 1 and player.engine is made[0] and made[0].calls == [(b"kept", 6, 6, 1)] and len(calls) == 6
 
 
 def test_engine_binding_lists_the_call():

@@ -212,7 +212,7 @@ def test_crate_surface():
     p = inspect.signature(Crate.observe).parameters
     assert (p["on"].default, p["capacity"].default, p["bins"].default, p["x_range"].default) == (True, 4096, 0, (0.0, 1.0))
     assert p["capacity"].kind is inspect.Parameter.KEYWORD_ONLY
-    assert callable(Crate.observations) and "probe_enable" in inspect.getsource(Crate._grow)
+    assert callable(Crate.observations)      # (that a growth keeps the log: tests/test_addons_cpu.py, by behaviour)
 
 
 def test_concatenate_and_as_dict():
