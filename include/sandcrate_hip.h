@@ -324,8 +324,8 @@ int sc_restore_counters(sc_ctx* ctx, int64_t tick, int64_t next_id);
  * 624-word key and the position of `np.random.get_state()` -- and from then on
  *   sc_emit_particles  runs ParticleSource.generate_particles (particle_source.py:17-24) for the given sources,
  *                      any number of them, in order on the device: binomial(flow, dt) new particles each (the legacy
- *                      inversion branch up to flow * dt = 30, BTPE beyond; SC_ERR_DOMAIN if flow < 1, dt <= 0 or
- *                      dt > 0.5), rand(n, 2) position jitter, rand(n, 2) velocity noise, capped at max_particles minus
+ *                      inversion branch up to flow * dt = 30, BTPE beyond; a flow of 0 draws its one double and emits
+ *                      nothing; SC_ERR_DOMAIN if flow < 0, dt <= 0 or dt > 0.5), rand(n, 2) position jitter, rand(n, 2) velocity noise, capped at max_particles minus
  *                      the count the previous sources left (a source capped at 0 or less draws its binomial only),
  *                      appended with the next ids;
  *   sc_step_finish     in SC_NOISE_HOST mode without a sc_set_noise_host call draws the tick's rand(sum C_i, 2)

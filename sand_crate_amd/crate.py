@@ -287,6 +287,7 @@ class Crate(_Frames, _Logs, _Checkpoints, _Neighbourhood):
     # ------------------------------------------------------------------ the tick
     def physics_tick(self) -> None:
         t0 = time.perf_counter()
+        self._check_walls()
         self._create_new_particles()
         self.debug_arrows = []
         for body in self.rigid_bodies:  # crate.py:363-365
@@ -366,6 +367,7 @@ class Crate(_Frames, _Logs, _Checkpoints, _Neighbourhood):
             raise RuntimeError("Crate.run cannot interleave particle sources; use physics_tick()")
         if n_ticks <= 0:
             return
+        self._check_walls()
         eng = self._engine
         # One library call per tick (sc_tick).  Nobody can edit coefficients inside run(), so every tick
         # also promises the next tick's inputs and its removal / wall pass rides on this tick's force
@@ -384,6 +386,16 @@ class Crate(_Frames, _Logs, _Checkpoints, _Neighbourhood):
             self.tick += 1
             now = nxt
         self._state_changed()
+
+    def _check_walls(self) -> None:
+        """The library's capacity error for more walls than a tick takes (load_walls: SC_MAX_SEGMENTS, SC_MAX_BODIES),
+        raised before the tick has changed anything: the library refuses them only after the sources have emitted and
+        the bodies have moved, and a caller who takes the body away again would go on from a world one step ahead."""
+        segments = sum(len(body) for body in self.rigid_bodies)
+        if segments > N.MAX_SEGMENTS:
+            raise N.NativeError(N.ERR_CAPACITY, f"{segments} segments, at most {N.MAX_SEGMENTS}")
+        if len(self.rigid_bodies) > N.MAX_BODIES:
+            raise N.NativeError(N.ERR_CAPACITY, f"{len(self.rigid_bodies)} bodies, at most {N.MAX_BODIES}")
 
     def _accelerate_free_bodies(self) -> None:
         """crate.py:311-314: gravity accelerates bodies that are neither fixed nor motored.  (Each body owns its

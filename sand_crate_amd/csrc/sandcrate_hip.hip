@@ -330,6 +330,15 @@ int put_from_device(sc_ctx* c, const double* dev_xy, const double* dev_vxy, cons
                     bool reset) {
   if (c->prebinned && reset)
     if (const int rc = abandon_promise(c)) return rc;
+  if (!reset && c->ids_bounded) {
+    // the device has handed out ids since the host last knew the counter: what the host holds is a bound, and ids taken
+    // from it would leave a gap that a host that emitted everything itself does not have.  Ask the device -- one
+    // synchronisation, on the rare path of a host append behind a device emission (a crate whose dt passed one half)
+    int h[C_COUNT];
+    if (const int rc = read_counters(c, h)) return rc;
+    c->next_id = h[C_NEXT_ID];
+  }
+  c->ids_bounded = false;
   const int64_t base = reset ? 0 : c->upper;
   c->pairs.valid = false;
   if (reset) {
@@ -1213,8 +1222,10 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
     const sc_source& s = sources[i];
     const double p = dt;
     // the legacy binomial for p <= 0.5: inversion up to n p = 30 (both YAML scenes: n p = 4 and 14), BTPE beyond;
-    // p > 0.5 (a time step above one half) is not on the device
-    if (!(p > 0.0 && p <= 0.5) || s.flow < 1)
+    // p > 0.5 (a time step above one half) is not on the device.  flow = 0 (a flow slider at its stop) is: NumPy spends
+    // one double on binomial(0, p) and returns 0, and so does the inversion loop -- qn = exp(0) = 1, bound = 0, no U
+    // exceeds it.  Only a negative flow, which NumPy refuses, is refused here
+    if (!(p > 0.0 && p <= 0.5) || s.flow < 0)
       return fail(SC_ERR_DOMAIN, "binomial(%lld, %g): the device draws NumPy's legacy binomial for 0 < p <= 0.5 only",
                   (long long)s.flow, p);
     SourcesK& g = groups[i / kMaxSources];
@@ -1280,6 +1291,7 @@ int sc_emit_particles(sc_ctx* c, const sc_source* sources, int32_t n_sources, do
   HIPCHK(hipGetLastError());
   c->upper = upper;
   c->next_id += most;  // an upper bound from here on: the device counts the ids it hands out (C_NEXT_ID)
+  c->ids_bounded = true;
   return SC_OK;
 }
 

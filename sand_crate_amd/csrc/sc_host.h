@@ -443,6 +443,7 @@ struct __attribute__((visibility("hidden"))) sc_ctx {
   int64_t tick = 0;
   int64_t upper = 0;    // host-side upper bound of the stored particle count
   int64_t next_id = 0;
+  bool ids_bounded = false;  // the device has handed out ids since (sc_emit_particles): next_id is an upper bound, C_NEXT_ID the counter
   bool in_step = false;
   int64_t normals_valid = 0;
   bool custom_grid = false;  // sc_neighbor_search: grid from the data, no walls, no removal

@@ -346,11 +346,25 @@ def one_ulp(seed, groups=()):
     return nudge
 
 
+def tick_sensitivity(a, b, d):
+    """Two outputs of tick_core for one tick, `b` from inputs one ulp away: -> (the largest change of a compared output in
+    units of its tolerance, whether the decisions -- sort, lists, contacts, NaN rows -- are the same)."""
+    from oracle.neighbors import strip_sort
+    same = np.array_equal(a["neighbor_table"], b["neighbor_table"]) and np.array_equal(a["wall_count"], b["wall_count"])
+    same &= all(np.array_equal(x, y) for x, y in zip(strip_sort(a["fixed_positions"], d), strip_sort(b["fixed_positions"], d)))
+    worst = 0.0
+    for key, atol in ATOL.items():
+        x, y = a[key], b[key]
+        same &= np.array_equal(np.isnan(x), np.isnan(y))
+        fin = ~(np.isnan(x) | np.isnan(y))
+        worst = max(worst, float((np.abs(x - y)[fin] / (atol + RTOL * np.abs(x[fin]))).max(initial=0.0)))
+    return worst, bool(same)
+
+
 def conditioning(case, noise, ticks=TICKS):
     """The worst ratio, over the ticks of the oracle's run and the outputs the device is compared on, of the change that
     one ulp in every input makes to the tolerance the device is given -- and whether the decisions (sort, lists,
     contacts, NaN rows) stayed the same.  Measured on the oracle alone."""
-    from oracle.neighbors import strip_sort
     groups = [case.ids[k] for k in piles_of(case)]
     worst, same = 0.0, True
     host_a, host_b = np.random.RandomState(HOST_SEED), np.random.RandomState(HOST_SEED)
@@ -358,13 +372,8 @@ def conditioning(case, noise, ticks=TICKS):
     for t in range(ticks):
         st, a = oracle_tick(case, noise, t, state, host_a)
         _, b = oracle_tick(case, noise, t, state, host_b, nudge=one_ulp(1000 + t, groups))
-        same &= np.array_equal(a["neighbor_table"], b["neighbor_table"]) and np.array_equal(a["wall_count"], b["wall_count"])
-        same &= all(np.array_equal(x, y) for x, y in zip(strip_sort(a["fixed_positions"], case.d), strip_sort(b["fixed_positions"], case.d)))
-        for key, atol in ATOL.items():
-            x, y = a[key], b[key]
-            same &= np.array_equal(np.isnan(x), np.isnan(y))
-            fin = ~(np.isnan(x) | np.isnan(y))
-            worst = max(worst, float((np.abs(x - y)[fin] / (atol + RTOL * np.abs(x[fin]))).max(initial=0.0)))
+        tick_worst, tick_same = tick_sensitivity(a, b, case.d)
+        worst, same = max(worst, tick_worst), same and tick_same
         keep = ~np.isnan(a["particles"]).any(axis=1)
         state = (a["particles"][keep], a["velocities"][keep], st[2][keep])
     return worst, bool(same)

@@ -137,10 +137,12 @@ def cases() -> dict:
 
 # ------------------------------------------------------------------ the oracle side of a run
 class Stage:
-    """The host side of a world as the oracle has it: bodies, coefficients, and the emission rule."""
+    """The host side of a world as the oracle has it: bodies, coefficients, and the emission rule.  `coef`, `bodies`
+    and `sources` are read afresh by every call, so they may be edited between ticks (tests/edit_cases.py): a
+    coefficient replaced, the gravity written in place, a body or a source changed, appended or removed."""
 
     def __init__(self, bodies, coef, sources=()):
-        self.bodies = build_bodies(bodies)
+        self.bodies = build_bodies(bodies)                       # (a list: it may grow and shrink)
         self.sources = build_sources(copy.deepcopy(list(sources)))
         self.coef = dict(coef)
         self.coef["gravity"] = np.array(self.coef["gravity"], dtype=np.float64)
@@ -176,6 +178,12 @@ class Stage:
     def advance(self) -> None:
         for b in self.bodies:
             b.advance(self.coef["dt"])
+
+    def accelerate(self) -> None:
+        """crate.py:311-314, behind the tick: gravity accelerates the bodies that are neither fixed nor motored."""
+        for b in self.bodies:
+            if b.kind == "free":
+                b.center_velocity = b.center_velocity + self.coef["dt"] * np.asarray(self.coef["gravity"], dtype=np.float64)
 
     def remove(self, p, v, ids):
         return remove_outside(p, v, self.coef["particle_radius"], ids)

@@ -98,19 +98,29 @@ def test_many_sources_in_one_call(sc, n_sources):
 
 
 def test_emission_argument_errors(sc):
-    """flow < 1, dt <= 0 and dt > 0.5 are outside the device's binomial (SC_ERR_DOMAIN, nothing drawn); dt = 0.5 is
-    inside."""
+    """flow < 0, dt <= 0 and dt > 0.5 are outside the device's binomial (SC_ERR_DOMAIN, nothing drawn); dt = 0.5 is
+    inside, and so is a flow of 0 -- a flow slider at its stop: one double, no particle, as NumPy draws binomial(0, p)."""
     from sand_crate_amd import _native as N
     rs = np.random.RandomState(3)
     eng = fresh_engine(sc, rs, 4096)
-    for flows, dt in (([0], 0.002), ([-3], 0.002), ([7000, 0], 0.002), ([10], 0.0), ([10], -0.1), ([10], 0.5000001),
-                      ([10] * 9, 0.75)):
+    for flows, dt in (([-1], 0.002), ([-3], 0.002), ([7000, -1], 0.002), ([10], 0.0), ([10], -0.1), ([10], 0.5000001),
+                      ([0], 0.75), ([10] * 9, 0.75)):
         with pytest.raises(N.NativeError) as err:
             eng.emit_particles([source(f) for f in flows], dt, 10 ** 6)
         assert err.value.code == N.ERR_DOMAIN
     assert eng.count() == 0
     assert_same_state(eng, rs)
-    stored, next_id, _ = check_emission(eng, rs, [source(13), source(2000)], 0.5, 10 ** 6, 0, 0)
+    one_double = np.random.RandomState()
+    one_double.set_state(rs.get_state())
+    one_double.random_sample()
+    stored, next_id, spec = check_emission(eng, rs, [source(0)], 0.002, 10 ** 6, 0, 0)
+    assert (stored, next_id) == (0, 0) and spec[0][0] == 0
+    assert rs.get_state()[2] == one_double.get_state()[2] and np.array_equal(rs.get_state()[1], one_double.get_state()[1])
+    assert_same_state(eng, rs)
+    stored, next_id, spec = check_emission(eng, rs, [source(7000), source(0), source(90)], 0.002, 10 ** 6, 0, 0)
+    assert stored > 0 and spec[1][1] is None
+    assert_same_state(eng, rs)
+    stored, next_id, _ = check_emission(eng, rs, [source(13), source(0), source(2000)], 0.5, 10 ** 6, stored, next_id)
     check_emission(eng, rs, mixed_sources(12), 0.002, 10 ** 6, stored, next_id)
     assert_same_state(eng, rs)
     eng.close()
