@@ -1036,6 +1036,55 @@ int sc_pairs_rays_device(sc_ctx* ctx, const double* dev_origins, const double* d
                          double* dev_t, int64_t* dev_hit, int64_t room_rows,
                          int64_t* dev_counts /* [2]: rays, status */);
 
+/* ---- Ray paths: hit points, normals and specular bounces ----------------------------------------------------------
+ * The rays above, followed through `bounces` specular reflections: L = bounces + 1 legs per ray, each with its t, what
+ * it hit, the hit point and the surface normal there.  Sonar and light multipath in a closed crate, the facet a range
+ * finder sees, the slope of the free surface under a probe.  The rule is specified in NumPy in tests/ray_path_spec.py;
+ * every operation is a float64 operation rounded on its own, and the directions are never normalised.
+ *
+ * Leg k has an origin o, a direction d, a budget m and an excluded object.  Leg 0 has the caller's origin and direction,
+ * m = max_t and nothing excluded: its t and hit are sc_pairs_rays_device's, bit for bit.  A leg k >= 1 is hit by the same
+ * rule, 0 <= t <= m, the smallest key (t, kind, index), with two changes: the object the leg before it hit -- disc j or
+ * wall s -- takes no part, and a disc with cc <= 0 (the origin inside or on it) is hit at t = +0 only if b < 0, the ray
+ * heading inward; otherwise the ray is leaving it and it is not hit.  A leg starts ON what it has just left, and that is
+ * named, not nudged away from: the continuation needs no epsilon and its bits depend on none.
+ * A leg that hit has P = (fl(ox + fl(t dx)), fl(oy + fl(t dy))) and the normal n: for a disc with centre c,
+ * g = (fl(Px - cx), fl(Py - cy)), len = sqrt(fl(fl(gx gx) + fl(gy gy))), n = (fl(gx / len), fl(gy / len)); for a wall
+ * A -> B, e = B - A, len = sqrt(fl(fl(ex ex) + fl(ey ey))), n0 = (fl(ey / len), fl(-ex / len)),
+ * q = fl(fl(dx n0x) + fl(dy n0y)), n = -n0 if q > 0, else n0: the normal faces the side the ray came from.
+ * The next leg: dn = fl(fl(dx nx) + fl(dy ny)); dn < 0: k2 = fl(2 dn), d' = (fl(dx - fl(k2 nx)), fl(dy - fl(k2 ny)));
+ * otherwise d' = d (the ray leaves already: a leg 0 that began inside a disc, pointing outward).  o' = P, m' = fl(m - t).
+ * dev_end[r] says how the path of ray r ended: 0, all L legs hit something; 1, a leg met nothing within its budget --
+ * that leg has t = +inf, hit = -1, P = n = NaN; 2, leg 0 is dead (t = NaN, hit = -1), or a normal has a component that is
+ * not finite (len = 0, a hit from the disc's own centre: the leg is written as computed), or the next leg would be dead
+ * (a number of o' or d' not finite, a' = 0); and, only when discs are looked for, the two tests of the call's status
+ * made on (o', d', m'): -1, a coordinate c of o' or of the end point fl(o' + fl(m' d')) fails fl(|c| / radius) < 2^31 or
+ * that end point is not finite -- tested first --, -4, fl(8192 dt) <= t_end with dt = fl(radius / sqrt(a')) and
+ * t_end = min(m', the next leg's nearest wall hit, the excluded wall left out).  The tests of a next leg are made only
+ * when there is one.  Every leg after the last one written is t = NaN, hit = -1, P = n = NaN: the call writes all L rows
+ * of every ray itself, the caller's arrays need no clear.
+ *
+ * sc_pairs_ray_paths_device  is sc_pairs_rays_device in its arguments, rules of the stream, refusals and statuses, with
+ *     `bounces`, 0 .. SC_RAY_MAX_BOUNCES, and the wider outputs: dev_t and dev_hit n_rays x L, dev_points and dev_normals
+ *     n_rays x L x 2 float64, aligned to 16 bytes, dev_end n_rays int64; `room_rows` is their room in rays.  The statuses
+ *     in dev_counts[1] are about leg 0, the caller's input, and refuse the whole call: -1 and -4 as above, nothing else
+ *     written.  Later legs are data: their failures end that ray alone, in dev_end.
+ *     The algorithm: the two check passes of the rays on leg 0, then a wave per ray that keeps the ray, leg after leg:
+ *     the walls with the excluded one skipped, the walk of sc_pairs_rays_device from step 0 with the leg's own dt, the
+ *     place of the best candidate in the sorted arrays carried through the wave's minimum so that its centre is read,
+ *     not searched again; every lane computes the normal, the reflection and the next leg's tests, so the wave stays
+ *     uniform (csrc/sc_rays.h extends the walk's argument to later legs).  No LDS, no atomics beyond the flag's.
+ *     SC_ERR_ARG, SC_ERR_CAPACITY and SC_ERR_STATE as for sc_pairs_rays_device, and SC_ERR_ARG for `bounces` outside
+ *     0 .. SC_RAY_MAX_BOUNCES, a null points, normals or end pointer and misaligned points or normals.  All checked before
+ *     anything is launched. */
+#define SC_RAY_MAX_BOUNCES 15
+int sc_pairs_ray_paths_device(sc_ctx* ctx, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                              int32_t bounces, double disc_radius /* 0: walls only */, double max_t,
+                              const double* segments /* HOST, may be NULL */, int32_t n_segments,
+                              double* dev_t /* n_rays x L */, int64_t* dev_hit /* n_rays x L */,
+                              double* dev_points /* n_rays x L x 2 */, double* dev_normals /* n_rays x L x 2 */,
+                              int64_t* dev_end /* n_rays */, int64_t room_rows, int64_t* dev_counts /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,10 @@ RAY_MAX_STEPS = 8192
 RAY_BLOCK, RAY_WAVE_STEPS = 64, 7
 PAIRS_RANGE = -4
 RAY_NONE, RAY_WALL = -1, -2
+# the ray paths: the most bounces (SC_RAY_MAX_BOUNCES), and the values of `end` that are no status: every leg hit, a leg
+# met nothing, the ray or its next leg is dead; PAIRS_DOMAIN and PAIRS_RANGE are the other two
+RAY_MAX_BOUNCES = 15
+RAY_END_ALL_HIT, RAY_END_NOTHING, RAY_END_DEAD = 0, 1, 2
 ERR_ARG = -1
 ERR_HIP = -2
 ERR_CAPACITY = -3
@@ -230,6 +234,8 @@ SIGNATURES = {
                                            _P, C.c_int64, _P]),
     "sc_pairs_hist_device": (C.c_int, [_P, _P, C.c_int64, _D, C.c_int32, _P, _P, C.c_int64, _P]),
     "sc_pairs_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, _D, C.c_int32, _P, _P, C.c_int64, _P]),
+    "sc_pairs_ray_paths_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, _D, C.c_int32, _P, _P,
+                                            _P, _P, _P, C.c_int64, _P]),
 }
 
 

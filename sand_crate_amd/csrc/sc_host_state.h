@@ -575,6 +575,34 @@ int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries
 
 // ---- ray sensors (sc_rays.h) ----------------------------------------------------------------------
 
+// What the rays and the ray paths ask of their common arguments, before the reader's own checks.
+static int rays_arguments(const double* dev_directions, int64_t n_rays, double disc_radius, double max_t, const double* segments,
+                          int32_t n_segments) {
+  if (n_rays < 0) return fail(SC_ERR_ARG, "negative ray count");
+  if ((uintptr_t)dev_directions & 15) return fail(SC_ERR_ARG, "the directions must be aligned to 16 bytes");
+  if (!(max_t >= 0) || !std::isfinite(max_t)) return fail(SC_ERR_ARG, "max_t must be finite and not negative");
+  if (!(disc_radius >= 0) || !std::isfinite(disc_radius)) return fail(SC_ERR_ARG, "the disc radius must be finite and not negative");
+  if (n_segments < 0 || n_segments > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", (int)n_segments, kMaxSeg);
+  if (n_segments > 0 && !segments) return fail(SC_ERR_ARG, "null segment array");
+  return SC_OK;
+}
+
+// ... and after them: the disc radius against the count's, the walls by value, and the check passes over leg 0.
+static int rays_check(sc_ctx* c, const Reader& r, double disc_radius, double max_t, const double* segments, int32_t n_segments,
+                      const XY* dirs, int64_t* dev_counts, RayWalls* walls) {
+  if (!(disc_radius <= c->pairs.grid.radius / 2))
+    return fail(SC_ERR_ARG, "the disc radius %.17g is more than half the count's radius %.17g: count at twice the disc radius",
+                disc_radius, c->pairs.grid.radius);
+  *walls = RayWalls{};
+  walls->n = n_segments;
+  if (n_segments) std::memcpy(walls->s, segments, sizeof(double) * 4 * (size_t)n_segments);
+  if (const int rc = reader_check(c, r, -1, -1, dev_counts)) return rc;
+  if (disc_radius > 0)
+    hipLaunchKernelGGL(k_rays_check, dim3(grid_for(r.rows)), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, *walls, max_t,
+                       r.queries, dirs, (long long)r.rows, c->pairs.readerFlag.get());
+  return SC_OK;
+}
+
 extern "C" {
 
 int sc_pairs_rays_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, double disc_radius,
@@ -583,33 +611,46 @@ int sc_pairs_rays_device(sc_ctx* c, const double* dev_origins, const double* dev
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_counts)
     return fail(SC_ERR_ARG, "null origins, directions, t, hit or counts pointer");
-  if (n_rays < 0) return fail(SC_ERR_ARG, "negative ray count");
-  if ((uintptr_t)dev_directions & 15) return fail(SC_ERR_ARG, "the directions must be aligned to 16 bytes");
-  if (!(max_t >= 0) || !std::isfinite(max_t)) return fail(SC_ERR_ARG, "max_t must be finite and not negative");
-  if (!(disc_radius >= 0) || !std::isfinite(disc_radius)) return fail(SC_ERR_ARG, "the disc radius must be finite and not negative");
-  if (n_segments < 0 || n_segments > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", (int)n_segments, kMaxSeg);
-  if (n_segments > 0 && !segments) return fail(SC_ERR_ARG, "null segment array");
+  if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
   Reader r;
   if (const int rc = reader_begin(c, {"sc_pairs_rays_device", "send rays through", "t and hit hold", false, true}, dev_origins,
                                   n_rays, room_rows, &r))
     return rc;
-  if (!(disc_radius <= c->pairs.grid.radius / 2))
-    return fail(SC_ERR_ARG, "the disc radius %.17g is more than half the count's radius %.17g: count at twice the disc radius",
-                disc_radius, c->pairs.grid.radius);
-  RayWalls walls{};
-  walls.n = n_segments;
-  if (n_segments) std::memcpy(walls.s, segments, sizeof(double) * 4 * (size_t)n_segments);
-  const int discs = disc_radius > 0;
   const XY* dirs = (const XY*)dev_directions;
   const RayOut out{dev_t, (long long*)dev_hit, (long long*)dev_counts};
-  if (const int rc = reader_check(c, r, -1, -1, dev_counts)) return rc;
-  int* own = c->pairs.readerFlag.get();
-  if (discs)
-    hipLaunchKernelGGL(k_rays_check, dim3(grid_for(r.rows)), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, walls, max_t,
-                       r.queries, dirs, (long long)r.rows, own);
+  RayWalls walls;
+  if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
   const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_rays, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, discs, disc_radius * disc_radius,
-                     max_t, own, r.queries, dirs, (long long)r.rows, out);
+  hipLaunchKernelGGL(k_rays, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, (int)(disc_radius > 0),
+                     disc_radius * disc_radius, max_t, c->pairs.readerFlag.get(), r.queries, dirs, (long long)r.rows, out);
+  HIPCHK(hipGetLastError());
+  return SC_OK;
+}
+
+int sc_pairs_ray_paths_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, int32_t bounces,
+                              double disc_radius, double max_t, const double* segments, int32_t n_segments, double* dev_t,
+                              int64_t* dev_hit, double* dev_points, double* dev_normals, int64_t* dev_end, int64_t room_rows,
+                              int64_t* dev_counts) {
+  if (!c) return fail(SC_ERR_ARG, "null context");
+  if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_points || !dev_normals || !dev_end || !dev_counts)
+    return fail(SC_ERR_ARG, "null origins, directions, t, hit, points, normals, end or counts pointer");
+  if (bounces < 0 || bounces > SC_RAY_MAX_BOUNCES)
+    return fail(SC_ERR_ARG, "%d bounces, it must be 0 .. %d", (int)bounces, (int)SC_RAY_MAX_BOUNCES);
+  static_assert(kRayMaxLegs == SC_RAY_MAX_BOUNCES + 1, "the header's bound is the kernel's");
+  if (((uintptr_t)dev_points | (uintptr_t)dev_normals) & 15) return fail(SC_ERR_ARG, "the points and the normals must be aligned to 16 bytes");
+  if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
+  Reader r;
+  if (const int rc = reader_begin(c, {"sc_pairs_ray_paths_device", "send rays through", "the paths hold", false, true}, dev_origins,
+                                  n_rays, room_rows, &r))
+    return rc;
+  const XY* dirs = (const XY*)dev_directions;
+  const RayPathOut out{dev_t, (long long*)dev_hit, (XY*)dev_points, (XY*)dev_normals, (long long*)dev_end, (long long*)dev_counts};
+  RayWalls walls;
+  if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
+  const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
+  hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, (int)(disc_radius > 0),
+                     disc_radius * disc_radius, max_t, (int)bounces + 1, c->pairs.readerFlag.get(), r.queries, dirs,
+                     (long long)r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -21,7 +21,8 @@
 //                  pairs_outside's rule or is not finite, and kRayFlagRange for a live ray whose walk would take more
 //                  than kRayMaxSteps steps (below).  Not launched for walls alone;
 //   k_rays         a wave per ray: the walls, the walk, the result -- unless a flag is up: then counts[1] = -1 (the
-//                  domain) or -4 (the range) is all that is written.
+//                  domain) or -4 (the range) is all that is written;
+//   k_ray_paths    (sc_pairs_ray_paths_device) the same wave, kept for bounces + 1 legs: "Paths" below.
 //
 // The walk.  s is the count's radius and the host requires rho <= s / 2; the cells are h = fl(s (1 + 2^-20)) wide.  With
 // dt = fl(s / sqrt(a)), step k covers t in [fl(k dt), fl((k + 1) dt)] -- consecutive steps share their border, so the
@@ -61,6 +62,33 @@
 // The cap.  A live ray needs fl(kRayMaxSteps dt) > t_end, else kRayFlagRange goes up and the call ends as status -4: a
 // max_t of 1e12 in an open scene is a status, not a kernel that walks for minutes.  (An a that overflowed gives dt = 0
 // and the same status.)  With the flag down every walk ends by step kRayMaxSteps: fl(k dt) is monotone in k.
+//
+// Paths (sc_pairs_ray_paths_device, k_ray_paths; the rule is tests/ray_path_spec.py).  The ray stays in its wave for
+// L = bounces + 1 legs.  A leg has o, d, a budget m and the object the leg before it hit, which takes no part in it; a
+// disc with cc <= 0 is hit (at t = +0) by a later leg only if b < 0 -- the ray heads inward --, else the ray is leaving
+// it.  A leg therefore starts ON the surface it has left and names it: no epsilon moves the origin, and no bit depends on
+// one.  A leg that hit has P = fl(o + fl(t d)) and the normal n -- g = P - c, n = g / sqrt(fl(fl(gx gx) + fl(gy gy)))
+// for a disc; n0 = (ey, -ex) / sqrt(fl(fl(ex ex) + fl(ey ey))) for a wall, negated if fl(fl(dx n0x) + fl(dy n0y)) > 0 --;
+// the next leg has o' = P, m' = fl(m - t) and, with dn = fl(fl(dx nx) + fl(dy ny)) < 0, d' = fl(d - fl(fl(2 dn) n)),
+// else d' = d.  How a path ends is `end`: 0 all legs hit, 1 a leg met nothing, 2 dead (leg 0, a normal that is not
+// finite, the next leg), -1 and -4 the next leg fails the two tests below.  Leg 0 is tested by the two check kernels
+// and refuses the call; a later leg is data and ends its ray alone.
+//
+// The claim, for later legs.  Before leg k >= 1 is walked every lane has tested (o', d', m') as k_rays_check tests leg 0:
+//   * the domain: o' and the end point fl(o' + fl(m' d')) are finite and have |c| / s < 2^31.  Every midpoint of the leg's
+//     walk lies between the two, up to the half cell beyond the end point that the last step may reach: the third bullet
+//     above holds word for word, the conversions in pairs_cell are defined and cx +- 1 does not overflow;
+//   * the range: fl(kRayMaxSteps dt) > t_end with the leg's OWN dt = fl(s / sqrt(a')) and its own walls -- the excluded
+//     one left out, as in the walk.  The walk starts again at step 0, so |f| <= (2^13 + 1.5) s for every disc it can
+//     hit, and the first bullet's 18 u |f|^2 is the same number: a, b and cc are computed from (o', d') exactly as from
+//     (o, d), whatever roundings made o' and d'.  The leg is a ray of its own; that its origin is a computed point
+//     changes nothing in the bound, which never assumed an exact origin.
+// The excluded disc is skipped by its index before the rule is asked, so it cannot win; skipping a candidate removes a
+// key from a minimum and leaves the argument for the others as it was.  A disc with cc <= 0 that is hit (b < 0) has its
+// centre within rho (1 + 2u) of o', which lies in step 0's piece: the bound of the last sentence of the claim.  A disc
+// with cc <= 0 that is NOT hit (b >= 0) is not a candidate at all, in the rule as in the walk.  The stop test is the
+// walk's: after the first batch with best t < fl((k0 + kRayWaveSteps) dt), per leg.  The path is finite because every
+// leg, a t = 0 leg included, uses up one of L.
 //
 // The form (profiles/rays_time.txt).  What every other reader does, a thread per row in workgroups of one wave, was
 // built too -- the same ray_scan, the eighteen `start` loads of a step's nine buckets issued together -- and MEASURED
@@ -102,11 +130,13 @@ __device__ __forceinline__ bool ray_live(XY o, XY d, double& a) {
   return fabs(o.x) < inf && fabs(o.y) < inf && fabs(d.x) < inf && fabs(d.y) < inf && a != 0;
 }
 
-// The nearest wall hit: (t, s), the lowest s among equals; (+inf, -1) for none.
-__device__ __forceinline__ void ray_walls(const RayWalls& w, XY o, XY d, double max_t, double& best, int& who) {
+// The nearest wall hit: (t, s), the lowest s among equals; (+inf, -1) for none.  kPath: wall `skip` takes no part.
+template <bool kPath = false>
+__device__ __forceinline__ void ray_walls(const RayWalls& w, XY o, XY d, double max_t, double& best, int& who, int skip = -1) {
   best = __builtin_inf();
   who = -1;
   for (int s = 0; s < w.n; ++s) {
+    if (kPath && s == skip) continue;
     const double ax = w.s[s][0], ay = w.s[s][1];
     const double ex = w.s[s][2] - ax, ey = w.s[s][3] - ay;
     const double gx = ax - o.x, gy = ay - o.y;
@@ -119,12 +149,15 @@ __device__ __forceinline__ void ray_walls(const RayWalls& w, XY o, XY d, double 
   }
 }
 
-// The disc round c: is it hit, and at which t.
-__device__ __forceinline__ bool ray_disc(XY o, XY d, double a, XY c, double rho2, double max_t, double& t) {
+// The disc round c: is it hit, and at which t.  kPath and `later`, a leg >= 1 of a path: a disc the origin lies in or
+// on is hit only by a ray that heads inward.
+template <bool kPath = false>
+__device__ __forceinline__ bool ray_disc(XY o, XY d, double a, XY c, double rho2, double max_t, double& t, bool later = false) {
   const double fx = o.x - c.x, fy = o.y - c.y;
   const double b = fx * d.x + fy * d.y;
   const double cc = (fx * fx + fy * fy) - rho2;
   if (cc <= 0) {
+    if (kPath && later && !(b < 0)) return false;
     t = 0.0;
   } else {
     if (!(b < 0)) return false;
@@ -227,6 +260,157 @@ __global__ void __launch_bounds__(kRayBlock)
     }
   }
   if (lane == 0) ray_write(out, r, tw, sw, best, who);
+}
+
+// ---- ray paths (sc_pairs_ray_paths_device): the ray stays in its wave, leg after leg ---------------
+
+constexpr int kRayMaxLegs = 16;  // bounces 0 .. 15 (include/sandcrate_hip.h: SC_RAY_MAX_BOUNCES + 1)
+constexpr long long kRayEndNothing = 1, kRayEndDead = 2;  // `end`; 0: every leg hit; kPairsStatusDomain, kRayStatusRange
+
+struct RayPathOut {
+  double* t;       // n_rays x legs
+  long long* hit;  // n_rays x legs
+  XY* points;      // n_rays x legs
+  XY* normals;     // n_rays x legs
+  long long* end;  // n_rays
+  long long* counts;  // [2]: rays, status
+};
+
+// ray_scan for a leg of a path: disc `skip` takes no part, `later` is ray_disc's, and the place in the sorted arrays of
+// the best candidate rides along with its key, for the normal.
+__device__ __forceinline__ void ray_scan_path(const PairsView& v, XY o, XY d, double a, double rho2, double max_t, bool later,
+                                              int skip, unsigned cx, unsigned cy, int lo, int hi, double& best, int& who,
+                                              int& place) {
+  for (int k = lo; k < hi; ++k) {
+    const uint2 cell = v.scell[k];
+    if (cell.x != cx || cell.y != cy) continue;
+    const int j = v.sidx[k];
+    double t;
+    if (j == skip || !ray_disc<true>(o, d, a, v.sxy[k], rho2, max_t, t, later)) continue;
+    if (t < best || (t == best && j < who)) {
+      best = t;
+      who = j;
+      place = k;
+    }
+  }
+}
+
+__device__ __forceinline__ void ray_path_write(const RayPathOut& out, long long at, double t, long long hit, XY p, XY n) {
+  out.t[at] = t;
+  out.hit[at] = hit;
+  out.points[at] = p;
+  out.normals[at] = n;
+}
+
+// A wave per ray, as k_rays: workgroup r is ray r, and the leg loop runs here.  Every lane holds the leg -- o, d, a, the
+// budget m and the excluded wall and disc -- and computes the walls, the normal, the reflection and the tests of the next
+// leg: all uniform over the wave.  The walk of a leg is k_rays', from step 0 with the leg's own dt.  Lane 0 writes the
+// legs; the lanes share the rows the path never reached.  Leg 0's own domain and range are the call's (the flags); a
+// later leg's end the ray only.
+__global__ void __launch_bounds__(kRayBlock)
+    k_ray_paths(PairsView v, RayWalls walls, int discs, double rho2, double max_t, int legs, const int* __restrict__ own_flag,
+                const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayPathOut out) {
+  const long long r = blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  const bool up = *v.flag || *own_flag;
+  if (r == 0 && lane == 0) {
+    if (up) out.counts[1] = ray_status(*v.flag, *own_flag);
+    else out.counts[0] = n_rays;
+  }
+  if (up || r >= n_rays) return;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+  const XY none{nan, nan};
+  const long long row = r * legs;
+  XY o = origins[r], d = dirs[r];
+  double a, m = max_t;
+  int skip_wall = -1, skip_disc = -1;  // (no wall and no disc has these indices)
+  long long end = 0;
+  int leg = 0;
+  if (!ray_live(o, d, a)) end = kRayEndDead;
+  while (end == 0 && leg < legs) {
+    double tw, best = inf;
+    int sw, who = kRayNoDisc, place = 0;
+    ray_walls<true>(walls, o, d, m, tw, sw, skip_wall);
+    if (discs) {
+      const double t_end = fmin(m, tw), dt = v.g.radius / sqrt(a);
+      if ((double)kRayMaxSteps * dt <= t_end) {  // (never leg 0: k_rays_check has raised the flag for it)
+        end = kRayStatusRange;
+        break;
+      }
+      const int step = lane / 9, c = lane % 9;
+      for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
+        const int k = k0 + step;
+        if (step < kRayWaveSteps && (double)k * dt <= t_end) {
+          const double tm = ((double)k + 0.5) * dt;
+          const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
+          const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
+          const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);
+          ray_scan_path(v, o, d, a, rho2, m, leg > 0, skip_disc, cx, cy, v.start[bk], v.start[bk + 1], best, who, place);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave and its place, in every lane
+          const double t2 = __shfl_xor(best, off, 64);
+          const int j2 = __shfl_xor(who, off, 64);
+          const int p2 = __shfl_xor(place, off, 64);
+          if (t2 < best || (t2 == best && j2 < who)) {
+            best = t2;
+            who = j2;
+            place = p2;
+          }
+        }
+        if (best < (double)(k0 + kRayWaveSteps) * dt) break;
+      }
+    }
+    const bool disc = best < tw;  // (a wall wins a tie)
+    if (!disc && sw < 0) {
+      if (lane == 0) ray_path_write(out, row + leg, inf, -1, none, none);
+      ++leg;
+      end = kRayEndNothing;
+      break;
+    }
+    const double t = disc ? best : tw;
+    const XY p{o.x + t * d.x, o.y + t * d.y};
+    XY n;
+    if (disc) {
+      const XY c = v.sxy[place];
+      const double gx = p.x - c.x, gy = p.y - c.y;
+      const double len = sqrt(gx * gx + gy * gy);
+      n = XY{gx / len, gy / len};
+    } else {
+      const double ex = walls.s[sw][2] - walls.s[sw][0], ey = walls.s[sw][3] - walls.s[sw][1];
+      const double len = sqrt(ex * ex + ey * ey);
+      n = XY{ey / len, -ex / len};
+      if (d.x * n.x + d.y * n.y > 0) n = -n;  // the side the ray came from
+    }
+    if (lane == 0) ray_path_write(out, row + leg, t, disc ? (long long)who : -2LL - sw, p, n);
+    ++leg;
+    if (!(fabs(n.x) < inf && fabs(n.y) < inf)) {
+      end = kRayEndDead;
+      break;
+    }
+    if (leg == legs) break;
+    // the next leg, and whether it may be walked
+    const double dn = d.x * n.x + d.y * n.y;
+    if (dn < 0) {
+      const double k2 = 2.0 * dn;
+      d = XY{d.x - k2 * n.x, d.y - k2 * n.y};
+    }
+    o = p;
+    m = m - t;
+    skip_wall = disc ? -1 : sw;
+    skip_disc = disc ? who : -1;
+    if (!ray_live(o, d, a)) {
+      end = kRayEndDead;
+    } else if (discs) {
+      const double ex = fabs(o.x + m * d.x), ey = fabs(o.y + m * d.y), s = v.g.radius;
+      if (!(fabs(o.x) / s < kPairsDomain) || !(fabs(o.y) / s < kPairsDomain) || !(ex / s < kPairsDomain) ||
+          !(ey / s < kPairsDomain))  // (inf too)
+        end = kPairsStatusDomain;
+    }
+  }
+  // the legs the path never reached -- for a dead ray all of them: its leg 0 is t = NaN, hit = -1 as well
+  for (int k = leg + lane; k < legs; k += kRayBlock) ray_path_write(out, row + k, nan, -1, none, none);
+  if (lane == 0) out.end[r] = end;
 }
 
 }  // namespace sc

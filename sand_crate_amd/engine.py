@@ -101,6 +101,20 @@ def _room(room, held: int, whose: str, unit: str = "rows") -> int:
     return room
 
 
+def _ray_numbers(disc_radius, max_t, segments):
+    """The host's numbers of `pairs_rays` and `pairs_ray_paths`, checked first -- they need no device --:
+    -> (disc_radius, max_t, segments as float64 (S, 2, 2)).  ValueError otherwise."""
+    disc_radius, max_t = float(disc_radius), float(max_t)
+    if not (0 <= disc_radius < float("inf")):
+        raise ValueError("disc_radius must be finite and not negative")
+    if not (0 <= max_t < float("inf")):
+        raise ValueError("max_t must be finite and not negative")
+    seg = np.zeros((0, 2, 2)) if segments is None else np.ascontiguousarray(segments, dtype=np.float64)
+    if seg.ndim != 3 or seg.shape[1:] != (2, 2) or len(seg) > N.MAX_SEGMENTS:
+        raise ValueError(f"segments must be (S, 2, 2) with S at most {N.MAX_SEGMENTS}")
+    return disc_radius, max_t, seg
+
+
 def _counts_tensor(counts, device: int) -> None:
     _state_tensor(counts, "counts", "int64", (), device, 2)
 
@@ -522,14 +536,7 @@ class Engine:
         ``origin + max_t * direction`` lies outside the domain, -4 when a ray would walk more than 8192 cells (then
         nothing else is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.
         Returns `counts`."""
-        disc_radius, max_t = float(disc_radius), float(max_t)  # (the host's numbers first: they need no device)
-        if not (0 <= disc_radius < float("inf")):
-            raise ValueError("disc_radius must be finite and not negative")
-        if not (0 <= max_t < float("inf")):
-            raise ValueError("max_t must be finite and not negative")
-        seg = np.zeros((0, 2, 2)) if segments is None else np.ascontiguousarray(segments, dtype=np.float64)
-        if seg.ndim != 3 or seg.shape[1:] != (2, 2) or len(seg) > N.MAX_SEGMENTS:
-            raise ValueError(f"segments must be (S, 2, 2) with S at most {N.MAX_SEGMENTS}")
+        disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
         rows = _state_tensor(t, "t", "float64", (), self.device)
         _state_tensor(hit, "hit", "int64", (), self.device, rows)
         q = _state_tensor(origins, "origins", "float64", (2,), self.device)
@@ -540,6 +547,39 @@ class Engine:
         N.check(self._lib.sc_pairs_rays_device(self._ctx, origins_at, directions_at, q, disc_radius, max_t,
                                                N.dptr(seg) if len(seg) else None, len(seg), t_at, hit_at, room,
                                                N._P(counts.data_ptr())))
+        return counts
+
+    def pairs_ray_paths(self, t, hit, points, normals, end, *, origins, directions, bounces: int, disc_radius: float,
+                        max_t: float, segments=None, counts, room: int | None = None):
+        """`pairs_rays` followed through `bounces` specular reflections, 0 .. 15 (sc_pairs_ray_paths_device; the rule is
+        tests/ray_path_spec.py): L = bounces + 1 legs per ray.  `t`, float64 (R, L), and `hit`, int64 (R, L), are
+        `pairs_rays`' per leg; `points` and `normals`, float64 (R, L, 2), receive the hit point and the surface normal
+        there, facing the side the ray came from; `end`, int64 (R,), how the path ended: 0 every leg hit something, 1 a leg
+        met nothing within what was left of `max_t` (t = +inf, hit = -1), 2 the ray or its next leg is dead or a normal is
+        not finite, -1 and -4 the next leg fails the domain or the cap.  Legs a path never reached are t = NaN, hit = -1,
+        NaN points and normals.  A leg >= 1 does not see what the leg before it hit, and a disc its origin lies in or on
+        only when it heads inward.  `origins`, `directions`, `disc_radius`, `max_t` and `segments` as in `pairs_rays`.
+        `counts`, int64 (2,), receives the ray count and the status of leg 0: 0, -1 or -4 as `pairs_rays` (then nothing
+        else is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.  Returns
+        `counts`."""
+        disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
+        bounces = int(bounces)
+        if not 0 <= bounces <= N.RAY_MAX_BOUNCES:
+            raise ValueError(f"bounces must be 0 .. {N.RAY_MAX_BOUNCES}")
+        legs = bounces + 1
+        rows = _state_tensor(t, "t", "float64", (legs,), self.device)
+        _state_tensor(hit, "hit", "int64", (legs,), self.device, rows)
+        _state_tensor(points, "points", "float64", (legs, 2), self.device, rows)
+        _state_tensor(normals, "normals", "float64", (legs, 2), self.device, rows)
+        _state_tensor(end, "end", "int64", (), self.device, rows)
+        q = _state_tensor(origins, "origins", "float64", (2,), self.device)
+        _state_tensor(directions, "directions", "float64", (2,), self.device, q)
+        _counts_tensor(counts, self.device)
+        room = _room(room, rows, "the tensors'")
+        origins_at, directions_at, *out_at = _addresses(counts, origins, directions, t, hit, points, normals, end)
+        N.check(self._lib.sc_pairs_ray_paths_device(self._ctx, origins_at, directions_at, q, bounces, disc_radius, max_t,
+                                                    N.dptr(seg) if len(seg) else None, len(seg), *out_at, room,
+                                                    N._P(counts.data_ptr())))
         return counts
 
     # -- frames

@@ -1,11 +1,11 @@
 """The neighbourhood calls of `Crate` -- `pair_tensors`, `cluster_tensors`, `cluster_sums`, `cluster_observables`,
-`neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram` and `ray_tensors` -- as a mixin `Crate`
+`neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram`, `ray_tensors` and `ray_paths` -- as a mixin `Crate`
 inherits (crate.py is the reference's surface, the tick and growth), and the protocol all of them follow,
 written once: `_Search`.
 
 Every call counts the pairs on the grid (`Engine.pairs_count`) and then runs one or more readers of that grid
 (`pairs_fill`, `pairs_label`, `pairs_cluster_sums`, `pairs_nearest`, `pairs_sum`, `pairs_sum_grad`, `pairs_hist`,
-`pairs_rays`), all on the library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either
+`pairs_rays`, `pairs_ray_paths`), all on the library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either
 it then synchronises, reads the counts, raises what the status says and cuts the tensors, or it returns the tensors as
 they are with `counts` last.  The C side of the same sharing is `reader_begin` / `reader_check`
 (csrc/sc_host_state.h).  torch is imported on first use."""
@@ -32,8 +32,8 @@ _STATUS = {
     N.FIELDS_VALUES_SHORT: "{who}: {short}",
     N.PAIRS_RANGE: "{who}: {far}",
 }
-_QUERY_CALLS = ("neighbor_tensors", "field_tensors", "field_function", "distance_histogram", "ray_tensors")
-_OF_EITHER = {"ray_tensors": " of a point, an origin or a ray's end point origin + max_t * direction"}
+_QUERY_CALLS = ("neighbor_tensors", "field_tensors", "field_function", "distance_histogram", "ray_tensors", "ray_paths")
+_OF_EITHER = dict.fromkeys(("ray_tensors", "ray_paths"), " of a point, an origin or a ray's end point origin + max_t * direction")
 
 
 def _check_batch(who: str, device: int, points, queries, batch, query_batch) -> None:
@@ -471,6 +471,19 @@ class _Neighbourhood:
         `synchronize()`, and have `origins`, `directions` and `points` ready before the call -- or run the crate on
         torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
         import torch
+        rho, max_t, segments, far = self._ray_arguments(origins, directions, max_t, disc_radius, walls)
+        call = _Search(self, "ray_tensors", 2 * rho, points=points, queries=origins, sync=sync, far=far)
+        t = torch.empty(call.rows, dtype=torch.float64, device=call.dev)
+        hit = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
+        call.count()
+        call.eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho if particles else 0.0, max_t=max_t,
+                            segments=segments, counts=call.counts)
+        return call.end(rows=(t, hit), held=(origins, directions))
+
+    def _ray_arguments(self, origins, directions, max_t, disc_radius, walls):
+        """The arguments `ray_tensors` and `ray_paths` share, checked: -> (rho, max_t, segments, the sentence of status
+        -4).  ValueError before anything is enqueued."""
+        import torch
         rho = float(self.diameter / 2 if disc_radius is None else disc_radius)
         if not 0 < rho < float("inf"):
             raise ValueError("disc_radius must be finite and positive")
@@ -493,10 +506,49 @@ class _Neighbourhood:
             raise ValueError("origins and directions must have the same number of rows")
         far = (f"max_t {max_t!r} lets a ray walk more than the cap of {N.RAY_MAX_STEPS} cells of width {2 * rho!r} before "
                "it meets a wall: shorten max_t, or close the scene with walls")
-        call = _Search(self, "ray_tensors", 2 * rho, points=points, queries=origins, sync=sync, far=far)
-        t = torch.empty(call.rows, dtype=torch.float64, device=call.dev)
-        hit = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
+        return rho, max_t, segments, far
+
+    def ray_paths(self, origins, directions, max_t: float, bounces: int = 1, *, disc_radius: float | None = None, walls=True,
+                  particles: bool = True, points=None, sync: bool = True):
+        """Where a signal goes: `ray_tensors` followed through `bounces` specular reflections, 0 .. 15, in one launch
+        (sc_pairs_count_device at the radius ``2 * disc_radius``, then sc_pairs_ray_paths_device): the named tuple
+        ``RayPaths(t, hit, points, normals, end)`` -- float64 (R, L), int64 (R, L), float64 (R, L, 2), float64 (R, L, 2)
+        and int64 (R,), L = bounces + 1 legs per ray.  The arguments are `ray_tensors`'; `max_t` is the budget of the
+        whole path, in units of the first direction's length, which a reflection keeps up to rounding.
+
+        Leg 0 is `ray_tensors`' result, bit for bit.  ``points[r, k]`` is where leg k hit, ``origin + t * direction`` of
+        that leg, and ``normals[r, k]`` the unit normal of the surface there, facing the side the ray came from: from the
+        particle's centre to the point, or the wall's normal.  The next leg starts at that point with the direction
+        mirrored about the normal, ``d - 2 (d . n) n``, and with what is left of the budget.  It does not see what the
+        leg before it hit, and a disc its origin lies in or on only when it heads inward: the continuation names the thing
+        it stands on and needs no epsilon, so the bits depend on none.  A leg 0 that starts inside a disc hits it at
+        t = 0; it is reflected when it points inward and kept when it points outward.  ``end[r]`` says how the path ended:
+        0 every leg hit something; 1 a leg met nothing within the budget, that leg has t = +inf and hit = -1; 2 the ray is
+        dead, as in `ray_tensors`, or a normal is not finite -- a hit from a disc's own centre --, or the next leg would be
+        dead; -1 and -4 the next leg would leave the domain or walk past the cap of 8192 cells: for a later leg these end
+        that ray only.  Legs a path never reached have t = NaN, hit = -1 and NaN points and normals.  Every operation is
+        rounded on its own: a pure function of the state and the rays, the same on every call (tests/ray_path_spec.py is
+        the rule; `sand_crate_amd.pairs.path_legs` and `path_arrows` read the result).
+
+        `sync=True` synchronises once at the end and raises `ray_tensors`' ValueErrors for leg 0, the caller's input: a
+        coordinate outside the domain, a first leg beyond the cap.  `sync=False` synchronises nothing and returns
+        ``(t, hit, points, normals, end, counts)``, the int64 `counts` tensor (rays, status) last, with the stream rules of
+        `ray_tensors`."""
+        import torch
+        from .pairs import RayPaths
+        bounces = int(bounces)
+        if not 0 <= bounces <= N.RAY_MAX_BOUNCES:
+            raise ValueError(f"bounces must be 0 .. {N.RAY_MAX_BOUNCES}")
+        rho, max_t, segments, far = self._ray_arguments(origins, directions, max_t, disc_radius, walls)
+        call = _Search(self, "ray_paths", 2 * rho, points=points, queries=origins, sync=sync, far=far)
+        legs = bounces + 1
+        t = torch.empty((call.rows, legs), dtype=torch.float64, device=call.dev)
+        hit = torch.empty((call.rows, legs), dtype=torch.int64, device=call.dev)
+        at = torch.empty((call.rows, legs, 2), dtype=torch.float64, device=call.dev)
+        normals = torch.empty((call.rows, legs, 2), dtype=torch.float64, device=call.dev)
+        end = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
         call.count()
-        call.eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho if particles else 0.0, max_t=max_t,
-                            segments=segments, counts=call.counts)
-        return call.end(rows=(t, hit), held=(origins, directions))
+        call.eng.pairs_ray_paths(t, hit, at, normals, end, origins=origins, directions=directions, bounces=bounces,
+                                 disc_radius=rho if particles else 0.0, max_t=max_t, segments=segments, counts=call.counts)
+        out = call.end(rows=(t, hit, at, normals, end), held=(origins, directions))
+        return RayPaths(*out) if sync else out

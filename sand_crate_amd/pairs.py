@@ -1,8 +1,11 @@
 """Small torch helpers for the CSR pair lists of `Crate.pair_tensors` (offsets, partners) and for the clusters of
 `Crate.cluster_tensors` (labels, sizes), for the nearest-k tables of `Crate.neighbor_tensors` (neighbors), for the
 weighted sums of `Crate.field_tensors` (sums, wsum), for the distance histograms of `Crate.distance_histogram`
-(edges, total) and for the ray sensors of `Crate.ray_tensors` (origins, directions, t, hit)."""
+(edges, total), for the ray sensors of `Crate.ray_tensors` (origins, directions, t, hit) and for the ray paths of
+`Crate.ray_paths` (hit, points)."""
 from __future__ import annotations
+
+import collections
 
 
 def batch_ptr(lengths, device=None):
@@ -190,3 +193,24 @@ def hit_walls(hit):
     """The wall segment every ray of `Crate.ray_tensors` hit: int64 (R,), the row of `segments`, -1 for a particle or nothing."""
     import torch
     return torch.where(hit <= -2, -2 - hit, torch.full_like(hit, -1))
+
+
+RayPaths = collections.namedtuple("RayPaths", "t hit points normals end")  # what `Crate.ray_paths` returns
+
+
+def path_legs(hit):
+    """How many legs of every path of `Crate.ray_paths` hit something: int64 (R,) from `hit`, int64 (R, L).  The legs
+    that hit come first: ``hit[r, :path_legs(hit)[r]]`` are they, and a leg is -1 when it met nothing or was never reached."""
+    return (hit != -1).sum(dim=1)
+
+
+def path_arrows(origins, points, hit):
+    """The travelled legs of the paths of `Crate.ray_paths` as the (start, direction) pairs `render(arrows=...)` draws: a
+    host float64 array (K, 2, 2), ray by ray and leg by leg.  Leg k of a ray that hit goes from the point of leg k - 1
+    -- from the origin for k = 0 -- to ``points[r, k]``, and its direction is the difference of the two; a leg that met
+    nothing has no end point and gives no arrow.  Synchronises: it copies the three tensors to the host."""
+    import numpy as np
+    import torch
+    starts = torch.cat([origins.unsqueeze(1), points[:, :-1]], dim=1)
+    pairs = torch.stack([starts, points - starts], dim=2)
+    return np.ascontiguousarray(pairs[hit != -1].cpu().numpy()).reshape(-1, 2, 2)
