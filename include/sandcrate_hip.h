@@ -700,8 +700,11 @@ int sc_pairs_fill_device(sc_ctx* ctx, int64_t* dev_partners, double* dev_d2 /* m
  *     count copies dev_ptr into the workspace on the context's stream -- it must be ready then, as the points must --
  *     and the readers never read it again.  clouds = 0 or dev_ptr NULL clears a pending batch.  The grid the count
  *     leaves is batched, which the context knows on the host: sc_pairs_fill_device, sc_pairs_nearest_device,
- *     sc_pairs_sum_device and sc_pairs_sum_grad_device read it as such.  sc_pairs_label_device, sc_pairs_hist_device and
- *     sc_pairs_rays_device are NOT batched yet: on a batched grid they return SC_ERR_ARG and write nothing.
+ *     sc_pairs_sum_device and sc_pairs_sum_grad_device read it as such.  sc_pairs_label_device, sc_pairs_hist_device,
+ *     sc_pairs_rays_device and sc_pairs_ray_paths_device do NOT read a batched grid: on one they return SC_ERR_ARG and
+ *     write nothing.  Their batched forms have outputs of other shapes and are calls of their own, at the end of this
+ *     header: sc_pairs_label_batch_device, sc_pairs_hist_batch_device, sc_pairs_rays_batch_device and
+ *     sc_pairs_ray_paths_batch_device, which in turn return SC_ERR_ARG on an unbatched grid.
  * sc_pairs_set_query_batch_device  with queries a second array, dev_query_ptr, also clouds + 1 entries ending at
  *     n_queries: query rows query_ptr[b] .. query_ptr[b + 1] see the points of cloud b only; a cloud may have points and
  *     no queries, or queries and no points (rows without partners).  Applies to the next query-form reader of the batched
@@ -1084,6 +1087,53 @@ int sc_pairs_ray_paths_device(sc_ctx* ctx, const double* dev_origins, const doub
                               double* dev_t /* n_rays x L */, int64_t* dev_hit /* n_rays x L */,
                               double* dev_points /* n_rays x L x 2 */, double* dev_normals /* n_rays x L x 2 */,
                               int64_t* dev_end /* n_rays */, int64_t room_rows, int64_t* dev_counts /* [2] */);
+
+/* ---- The batched forms of the four calls above: clusters, histograms, rays and ray paths of a minibatch -------------
+ * Each reads the grid that a count after sc_pairs_set_batch_device has left -- B clouds, cloud b the rows
+ * ptr[b] .. ptr[b + 1] -- and returns SC_ERR_ARG on an unbatched grid, as its unbatched twin does on a batched one.  Each
+ * obeys the count-then-read protocol of its twin, with the same arguments, alignment rules, dev_counts[2], rules of the
+ * stream, refusals and status codes, and one more status: dev_counts[1] = -3 when the count's offsets, or the call's own
+ * query offsets, were not in order -- found on the device, nothing else is written.  tests/batch_readers_spec.py is the
+ * rule: there is no new arithmetic, every result is the twin's rule cloud by cloud, concatenated in cloud order, indices
+ * global.  The kernels are the twins' with the row's record (its cloud and index range) read once per row: the cloud
+ * goes into the bucket hash, the range decides (csrc/sc_pairs.h).
+ *
+ * sc_pairs_label_batch_device  sc_pairs_label_device plus dev_cluster_ptr, int64, clouds + 1 entries, always written
+ *     whole.  A cluster never crosses clouds.  Labels and roots are global; clusters are numbered by their smallest
+ *     member, so cloud b's clusters are the contiguous range dev_cluster_ptr[b] .. dev_cluster_ptr[b + 1], and
+ *     dev_cluster_ptr[clouds] = C.  A cloud without a finite point has no cluster: its two entries are equal.  The label
+ *     it leaves is an ordinary one: sc_pairs_cluster_sums_device reads it unchanged.  SC_ERR_ARG also for a null
+ *     dev_cluster_ptr.
+ * sc_pairs_hist_batch_device  sc_pairs_hist_device with totals per cloud: dev_table as before, rows x bins int32;
+ *     dev_cloud_total int64, clouds x bins contiguous, row b the column sums of the table over the rows of cloud b (all
+ *     zero for a cloud without rows); `room_clouds`, its room in clouds, must be at least the grid's clouds.  With
+ *     dev_queries, sc_pairs_set_query_batch_device comes first, as for every query-form reader of a batched grid.  The
+ *     context's accumulator grows with clouds x bins: SC_ERR_CAPACITY beyond SC_HIST_BATCH_MAX_CELLS words, and for too
+ *     small a room_clouds.
+ * sc_pairs_rays_batch_device, sc_pairs_ray_paths_batch_device  the unbatched argument lists.  Rays are always the query
+ *     form, so sc_pairs_set_query_batch_device comes first with the rays' offsets: ray r of ray-cloud b meets the discs
+ *     of cloud b only, a ray-cloud over an empty cloud sees the walls alone.  The walls go in by value and are shared by
+ *     all clouds.  dev_hit is the global row, and so is the disc a path's next leg leaves out. */
+enum { SC_HIST_BATCH_MAX_CELLS = 1 << 24 };
+int sc_pairs_label_batch_device(sc_ctx* ctx, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes /* may be NULL */,
+                                int64_t* dev_roots /* may be NULL */, int64_t room_clusters,
+                                int64_t* dev_cluster_ptr /* clouds + 1 */, int64_t* dev_counts /* [2]: n, C */);
+int sc_pairs_hist_batch_device(sc_ctx* ctx, const double* dev_queries /* NULL: the points themselves */, int64_t n_queries,
+                               const double* edges2 /* HOST, bins + 1 */, int32_t bins,
+                               int32_t* dev_table /* rows x bins, may be NULL */,
+                               int64_t* dev_cloud_total /* clouds x bins, may be NULL */, int64_t room_rows,
+                               int64_t room_clouds, int64_t* dev_counts /* [2]: rows, status */);
+int sc_pairs_rays_batch_device(sc_ctx* ctx, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                               double disc_radius /* 0: walls only */, double max_t,
+                               const double* segments /* HOST, may be NULL */, int32_t n_segments,
+                               double* dev_t, int64_t* dev_hit, int64_t room_rows,
+                               int64_t* dev_counts /* [2]: rays, status */);
+int sc_pairs_ray_paths_batch_device(sc_ctx* ctx, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                                    int32_t bounces, double disc_radius /* 0: walls only */, double max_t,
+                                    const double* segments /* HOST, may be NULL */, int32_t n_segments,
+                                    double* dev_t /* n_rays x L */, int64_t* dev_hit /* n_rays x L */,
+                                    double* dev_points /* n_rays x L x 2 */, double* dev_normals /* n_rays x L x 2 */,
+                                    int64_t* dev_end /* n_rays */, int64_t room_rows, int64_t* dev_counts /* [2] */);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,7 @@ HIST_MAX_BINS = 64
 HIST_BLOCK = 64
 HIST_SLOTS = (16, 32, 64)
 HIST_OK, HIST_DOMAIN = 0, -1
+HIST_BATCH_MAX_CELLS = 1 << 24  # clouds x bins of one batched histogram (SC_HIST_BATCH_MAX_CELLS)
 # the ray sensors (csrc/sc_rays.h): the most steps -- cells -- a ray may walk (kRayMaxSteps), the lanes of the wave that
 # walks a ray (kRayBlock), the steps it takes at a time (kRayWaveSteps), the status values of counts[1] -- PAIRS_RANGE is
 # the new one: a ray that would walk more than RAY_MAX_STEPS cells -- and the values of `hit` that are no particle: none,
@@ -236,6 +237,13 @@ SIGNATURES = {
     "sc_pairs_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, _D, C.c_int32, _P, _P, C.c_int64, _P]),
     "sc_pairs_ray_paths_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, _D, C.c_int32, _P, _P,
                                             _P, _P, _P, C.c_int64, _P]),
+    # the batched forms: the label's with cluster_ptr before the counts, the histogram's with room_clouds behind room_rows
+    "sc_pairs_label_batch_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "sc_pairs_hist_batch_device": (C.c_int, [_P, _P, C.c_int64, _D, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
+    "sc_pairs_rays_batch_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_double, _D, C.c_int32, _P, _P, C.c_int64,
+                                             _P]),
+    "sc_pairs_ray_paths_batch_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, _D, C.c_int32, _P,
+                                                  _P, _P, _P, _P, C.c_int64, _P]),
 }
 
 

@@ -32,6 +32,14 @@
 // the finds need no depth guarantee to be correct, and no later thread walks a chain.
 //
 // With the domain flag up every kernel returns at once, except that counts[1] = -1 is written.
+//
+// The batched form (sc_pairs_label_batch_device, on the grid of a count after sc_pairs_set_batch_device): an edge never
+// crosses clouds.  k_cluster_union<true> reads its row's record once (pairs_row, sc_pairs.h), hashes with the row's
+// cloud and skips a candidate below the cloud's first row; everything after the union is the unbatched label -- labels
+// and roots are global, and because a cloud is a range of rows and clusters are numbered by their smallest member, cloud
+// b's clusters are a contiguous range: k_cluster_ptr reads its ends out of the scan the label makes anyway.  Bad batch
+// offsets were found by the count: counts[1] = -3 and nothing else.  The label is left valid, so
+// sc_pairs_cluster_sums_device reads it as it reads any other.
 #pragma once
 #include "sc_pairs.h"
 
@@ -80,20 +88,25 @@ __global__ void __launch_bounds__(kBlock)
 // `v.g.half` is off (the view's): the graph is the full one, and each edge is united from its larger end.  A bucket's
 // members ascend in index (the binning sort is stable), so a run is left at the first j >= i, before its cell is even read:
 // that early exit is this reader's alone, one more reason why it keeps its own loop over the view (sc_pairs.h).
+// Batched: the row's record (lo, hi, cloud) comes from pairs_row, the buckets hash with the row's cloud, and of pairs_in
+// only j >= lo is left to test -- j < i < hi already.  The unbatched instantiation carries no record.
+template <bool batched>
 __global__ void __launch_bounds__(kBlock) k_cluster_union(PairsView v, int m, int* parent) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= m || *v.flag || i >= v.words[PW_N]) return;
   const XY p = v.xy[i];
   if (!cluster_finite(p)) return;
+  const PairsRow row = pairs_row<batched>(v.bt, i);
   const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
   int root = i;  // an ancestor of i: where the next find starts
   for (int c = 0; c < 9; ++c) {
     const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-    const unsigned b = pairs_bucket(cx, cy, 0u, v.g.mask);  // (never batched: the host refuses)
+    const unsigned b = pairs_bucket(cx, cy, row.cloud, v.g.mask);
     const int end = v.start[b + 1];
     for (int k = v.start[b]; k < end; ++k) {
       const int j = v.sidx[k];
       if (j >= i) break;
+      if (batched && j < row.lo) continue;  // (another cloud's member, met by collision)
       const uint2 cell = v.scell[k];
       double d2;
       if (cell.x == cx && cell.y == cy && pairs_accept(v.g, i, j, p, v.sxy[k], d2)) root = cluster_unite(parent, root, j);
@@ -147,15 +160,15 @@ __global__ void __launch_bounds__(kBlock)
   if (d >= 0 && run.is_head) atomicAdd(&sizeW[d], run.len);
 }
 
-// ... the sizes widened into the caller's array, below the room, and the two words.  With the domain flag up:
-// counts[1] = -1, nothing else.
+// ... the sizes widened into the caller's array, below the room, and the two words.  With the count's flag up:
+// counts[1] = -1 (the domain) or -3 (the offsets of a batched count), nothing else.
 __global__ void __launch_bounds__(kBlock)
     k_cluster_finish(const long long* __restrict__ words, const int* __restrict__ flag, int m, const int* __restrict__ dense,
                      const int* __restrict__ sizeW, long long* __restrict__ sizes, long long room_clusters,
                      long long* __restrict__ counts) {
   const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (*flag) {
-    if (c == 0) counts[1] = -1;
+  if (const int up = *flag) {
+    if (c == 0) counts[1] = pairs_status(up);
     return;
   }
   const int total = dense[m];
@@ -164,6 +177,18 @@ __global__ void __launch_bounds__(kBlock)
     counts[1] = total;
   }
   if (sizes && c < total && c < room_clusters) sizes[c] = sizeW[c];
+}
+
+// The batched label's offset table, a thread per entry: cluster_ptr[b] is the number of roots below ptr[b], which is
+// dense[ptr[b]] -- clusters are numbered by their smallest member and a cloud is a range of rows, so cloud b's clusters
+// are cluster_ptr[b] .. cluster_ptr[b + 1].  ptr[b] <= n <= m, and the scan has written dense[0 .. m]: isRoot is 0 from n
+// on, so the last entry, dense[n], is C even when n = m.  With the flag up nothing is written.
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_ptr(const int* __restrict__ flag, const long long* __restrict__ ptr, int clouds, const int* __restrict__ dense,
+                  long long* __restrict__ cluster_ptr) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b > clouds || *flag) return;
+  cluster_ptr[b] = dense[ptr[b]];
 }
 
 }  // namespace sc

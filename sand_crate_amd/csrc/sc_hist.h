@@ -44,6 +44,17 @@
 // The totals.  Lane b adds up bin b over the workgroup's 64 rows in 64 bits (64 rows of up to 2^28 partners do not fit
 // 32) and issues one 64-bit integer atomicAdd when the sum is not zero.  Integer adds commute: no atomic's order reaches
 // the output.  No floating-point atomics, no workgroup waits for another, no workspace beyond the flag and the 64 words.
+//
+// The batched form (sc_pairs_hist_batch_device, on the grid of a count after sc_pairs_set_batch_device; the rule is
+// tests/batch_readers_spec.py): k_hist<NB, true>.  The row reads its record (lo, hi, cloud) once -- pairs_row,
+// sc_pairs.h: a point's from the workspace, a query's by binary search over query_ptr --, hashes its nine cells with its
+// cloud and counts a candidate only when pairs_in says its index lies in the cloud.  The table is as before.  The totals
+// are per cloud, clouds x bins words in the context's accumulator: a workgroup's 64 rows may hold several clouds, but rows
+// ascend, so clouds ascend -- every row leaves its cloud in LDS (64 ints more, in this instantiation only), and lane b
+// sums bin b over each run of equal cloud and issues one 64-bit integer atomicAdd per non-zero (run, bin).  The counters
+// still take kHistLines lines whatever the clouds: the occupancy argument above is the walk's and has not changed.
+// k_hist_finish copies clouds x bins words, and only with no flag up.  The unbatched instantiation carries no record and
+// no s_cloud.
 #pragma once
 #include "sc_pairs.h"
 
@@ -63,13 +74,13 @@ struct HistEdges {
 
 struct HistOut {
   int* table;         // rows x bins, or null
-  long long* total;   // bins, or null
+  long long* total;   // bins -- batched: clouds x bins --, or null
   long long* counts;  // [2]: rows, status
 };
 
 // `queries` null: row i is point i of the count (n rows, n = words[PW_N]); otherwise row i is queries[i] (n_queries rows).
-// v.g.r2 is e2[bins], at most the count's; v.g.h and v.g.mask are the count's.
-template <int NB>
+// v.g.r2 is e2[bins], at most the count's; v.g.h and v.g.mask are the count's.  `batched`: `acc` holds clouds x bins words.
+template <int NB, bool batched>
 __global__ void __launch_bounds__(kHistBlock)
     k_hist(PairsView v, HistEdges edges, int bins, const int* __restrict__ own_flag, const XY* __restrict__ queries,
            long long n_queries, long long* __restrict__ acc, HistOut out) {
@@ -78,6 +89,7 @@ __global__ void __launch_bounds__(kHistBlock)
   __shared__ double s_e2[NB];
   static_assert(NB <= kHistLines, "a line of counters per bin");
   __shared__ int s_bins[kHistLines][W + kHistPad];
+  __shared__ int s_cloud[batched ? W : 1];  // the cloud of every row of the workgroup (batched only)
   const int tid = (int)threadIdx.x;
   const long long base = (long long)blockIdx.x * W;
   const long long i = base + tid;
@@ -93,18 +105,22 @@ __global__ void __launch_bounds__(kHistBlock)
   __syncthreads();
   if (i < rows) {
     const XY p = queries ? queries[i] : v.xy[i];
+    const PairsRow row = pairs_row<batched>(v.bt, i);  // (a dead row has a cloud too: its zeros are credited there)
+    if (batched) s_cloud[tid] = (int)row.cloud;
     if (fabs(p.x) < __builtin_inf() && fabs(p.y) < __builtin_inf()) {
       const int me = queries ? -1 : (int)i;  // (no j is -1)
       const double first = s_e2[0];
       const unsigned cx0 = pairs_cell(p.x, v.g.h), cy0 = pairs_cell(p.y, v.g.h);
       for (int c = 0; c < 9; ++c) {
         const unsigned cx = cx0 + (unsigned)(c % 3 - 1), cy = cy0 + (unsigned)(c / 3 - 1);
-        const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);  // (never batched: the host refuses)
+        const unsigned bk = pairs_bucket(cx, cy, row.cloud, v.g.mask);
         const int end = v.start[bk + 1];
         for (int k = v.start[bk]; k < end; ++k) {
           const uint2 cell = v.scell[k];
           double d2;
-          if (!(cell.x == cx && cell.y == cy && pairs_accept(v.g, me, v.sidx[k], p, v.sxy[k], d2))) continue;
+          if (!(cell.x == cx && cell.y == cy && pairs_in<batched>(row, v.sidx[k]) &&
+                pairs_accept(v.g, me, v.sidx[k], p, v.sxy[k], d2)))
+            continue;
           if (d2 < first) continue;  // below the first edge: in no bin
           int b = 0;                 // the last edge among 1 .. bins - 1 that is at most d2
 #pragma unroll
@@ -128,17 +144,32 @@ __global__ void __launch_bounds__(kHistBlock)
   }
   if (out.total && tid < bins) {
     long long sum = 0;
-    for (int t = 0; t < mine; ++t) sum += s_bins[tid][t];
-    if (sum) atomicAdd((unsigned long long*)&acc[tid], (unsigned long long)sum);
+    if (batched) {
+      // the rows ascend, so their clouds ascend: one add per run of equal cloud, into that cloud's line
+      int cur = mine > 0 ? s_cloud[0] : 0;
+      for (int t = 0; t < mine; ++t) {
+        const int cl = s_cloud[t];
+        if (cl != cur) {
+          if (sum) atomicAdd((unsigned long long*)&acc[(long long)cur * bins + tid], (unsigned long long)sum);
+          sum = 0;
+          cur = cl;
+        }
+        sum += s_bins[tid][t];
+      }
+      if (sum) atomicAdd((unsigned long long*)&acc[(long long)cur * bins + tid], (unsigned long long)sum);
+    } else {
+      for (int t = 0; t < mine; ++t) sum += s_bins[tid][t];
+      if (sum) atomicAdd((unsigned long long*)&acc[tid], (unsigned long long)sum);
+    }
   }
 }
 
-// After k_hist on the same stream: the totals go to the caller unless a flag is up.
+// After k_hist on the same stream: the `cells` totals -- bins, batched clouds x bins -- go to the caller unless a flag is up.
 __global__ void __launch_bounds__(kHistBlock)
-    k_hist_finish(int bins, const int* __restrict__ flag, const int* __restrict__ own_flag,
+    k_hist_finish(long long cells, const int* __restrict__ flag, const int* __restrict__ own_flag,
                   const long long* __restrict__ acc, long long* __restrict__ total) {
-  const int b = (int)threadIdx.x;
-  if (*flag || *own_flag || b >= bins) return;
+  const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (*flag || *own_flag || b >= cells) return;
   total[b] = acc[b];
 }
 

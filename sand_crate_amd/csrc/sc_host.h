@@ -341,14 +341,17 @@ struct ClusterSumSpace {
 // sc_pairs_hist_device (sc_hist.h; sc_host_state.h): the accumulator of the totals, kHistMaxBins 64-bit words, and behind
 // it the word that holds the flag of the call's own -- a query outside the domain: the count's flag stays as the count
 // left it.  One buffer, so that one memset prepares both; the readers' check gets the flag's address and nothing else.
+// sc_pairs_hist_batch_device: its accumulator, `cells` = clouds x bins words, lies BEHIND the flag -- again one memset,
+// from the flag on -- and the buffer is grown to the largest one asked for.
 struct HistSpace {
   DevBuf<long long> words;
-  int ensure(hipStream_t stream) {
-    HIPCHK(words.grow(kHistMaxBins + 1, stream));
+  int ensure(hipStream_t stream, int64_t cells = 0) {
+    HIPCHK(words.grow(kHistMaxBins + 1 + cells, stream));
     return SC_OK;
   }
   long long* acc() const { return words.get(); }
   int* flag() const { return (int*)(words.get() + kHistMaxBins); }
+  long long* batch_acc() const { return words.get() + kHistMaxBins + 1; }
 };
 
 // The checkpoint (sc_checkpoint_begin / _finish; sc_host_snapshot.h): device-side snapshot, pinned host copy, and the

@@ -95,10 +95,13 @@ int sc_pairs_set_query_batch_device(sc_ctx* c, const int64_t* dev_query_ptr) {
   return SC_OK;
 }
 
-// A reader that is not batched yet (the clusters, the histograms) on a batched grid.
-static int pairs_refuse_batched(sc_ctx* c, const char* who) {
-  if (!c->pairs.clouds) return SC_OK;
-  return fail(SC_ERR_ARG, "%s does not read a batched grid yet: count without sc_pairs_set_batch_device first", who);
+// The clusters, the histograms, the rays and the ray paths come in two calls each, `who` and `twin`, which share a host
+// body: the unbatched one refuses a batched grid and the batched one an unbatched grid, each naming the other.
+static int pairs_grid_is(sc_ctx* c, bool batched, const char* who, const char* twin) {
+  if ((c->pairs.clouds != 0) == batched) return SC_OK;
+  if (batched)
+    return fail(SC_ERR_ARG, "%s reads a batched grid only: sc_pairs_set_batch_device and a count come first, or call %s", who, twin);
+  return fail(SC_ERR_ARG, "%s does not read a batched grid: call %s, or count without sc_pairs_set_batch_device first", who, twin);
 }
 
 int sc_pairs_count_device(sc_ctx* c, const double* dev_xy, int64_t n, double radius, int32_t flags, int64_t* dev_offsets,
@@ -202,15 +205,18 @@ int sc_pairs_fill_device(sc_ctx* c, int64_t* dev_partners, double* dev_d2, int64
 
 // ---- clusters (sc_clusters.h) --------------------------------------------------------------------
 
-int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
-                          int64_t room_clusters, int64_t* dev_counts) {
+// sc_pairs_label_device and sc_pairs_label_batch_device: `batched` says which, and `dev_cluster_ptr` is the second one's.
+static int pairs_label(sc_ctx* c, bool batched, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
+                       int64_t room_clusters, int64_t* dev_cluster_ptr, int64_t* dev_counts) {
+  const char* who = batched ? "sc_pairs_label_batch_device" : "sc_pairs_label_device";
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_labels || !dev_counts) return fail(SC_ERR_ARG, "null labels or counts pointer");
+  if (batched && !dev_cluster_ptr) return fail(SC_ERR_ARG, "null cluster_ptr pointer");
   if (room_rows < 0 || room_clusters < 0) return fail(SC_ERR_ARG, "negative room");
-  if (c->in_step) return fail(SC_ERR_STATE, "sc_pairs_label_device inside a tick");
+  if (c->in_step) return fail(SC_ERR_STATE, "%s inside a tick", who);
   if (!c->pairs.valid)
     return fail(SC_ERR_STATE, "no pair count to label from: sc_pairs_count_device comes first, and the state must not change in between");
-  if (const int rc = pairs_refuse_batched(c, "sc_pairs_label_device")) return rc;
+  if (const int rc = pairs_grid_is(c, batched, who, batched ? "sc_pairs_label_device" : "sc_pairs_label_batch_device")) return rc;
   const int64_t m = c->pairs.m;
   if (room_rows < m)
     return fail(SC_ERR_CAPACITY, "labels hold %lld rows, up to %lld points", (long long)room_rows, (long long)m);
@@ -223,7 +229,8 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
   int* parent = c->clusters.parent.get();
   hipLaunchKernelGGL(k_cluster_init, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, parent);
   // (the view's `half` is off: the components are those of the full graph, whichever form the count had)
-  hipLaunchKernelGGL(k_cluster_union, dim3(grid), dim3(kBlock), 0, c->stream, c->pairs.view(nullptr), (int)m, parent);
+  hipLaunchKernelGGL(batched ? k_cluster_union<true> : k_cluster_union<false>, dim3(grid), dim3(kBlock), 0, c->stream,
+                     c->pairs.view(nullptr), (int)m, parent);
   // a tree of at most m nodes is at most m - 1 deep, and a round halves (rounding up) every depth
   int rounds = 1;
   while (((int64_t)1 << rounds) < m) ++rounds;
@@ -237,10 +244,23 @@ int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int
                      (long long)room_clusters);
   hipLaunchKernelGGL(k_cluster_finish, dim3(grid), dim3(kBlock), 0, c->stream, words, flag, (int)m, c->clusters.dense.get(),
                      c->clusters.size.get(), (long long*)dev_sizes, (long long)room_clusters, (long long*)dev_counts);
+  if (batched)
+    hipLaunchKernelGGL(k_cluster_ptr, dim3(grid_for(c->pairs.clouds + 1)), dim3(kBlock), 0, c->stream, flag, c->pairs.ptr.get(),
+                       (int)c->pairs.clouds, c->clusters.dense.get(), (long long*)dev_cluster_ptr);
   HIPCHK(hipGetLastError());
   c->clusters.valid = true;
   c->clusters.m = m;
   return SC_OK;
+}
+
+int sc_pairs_label_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
+                          int64_t room_clusters, int64_t* dev_counts) {
+  return pairs_label(c, false, dev_labels, room_rows, dev_sizes, dev_roots, room_clusters, nullptr, dev_counts);
+}
+
+int sc_pairs_label_batch_device(sc_ctx* c, int64_t* dev_labels, int64_t room_rows, int64_t* dev_sizes, int64_t* dev_roots,
+                                int64_t room_clusters, int64_t* dev_cluster_ptr, int64_t* dev_counts) {
+  return pairs_label(c, true, dev_labels, room_rows, dev_sizes, dev_roots, room_clusters, dev_cluster_ptr, dev_counts);
 }
 
 }  // extern "C"
@@ -346,6 +366,8 @@ struct ReaderCall {
   const char* holder;  // "<holder> <room> rows": the caller's array with a row per row, and its verb
   bool batched_ok;     // reads a batched grid
   bool holds_rows;     // the caller gave such an array: its room is tested against the rows
+  const char* twin = nullptr;  // with `batched_ok` off: the call that reads a batched grid; on: the one `who` is the
+                               // batched form of, which makes `who` refuse an unbatched grid
 };
 
 // ... and what it launches with.
@@ -365,8 +387,8 @@ static int reader_begin(sc_ctx* c, const ReaderCall& call, const double* dev_que
   if (!c->pairs.valid)
     return fail(SC_ERR_STATE, "no pair count to %s: sc_pairs_count_device comes first, and the state must not change in between",
                 call.verb);
-  if (!call.batched_ok)
-    if (const int rc = pairs_refuse_batched(c, call.who)) return rc;
+  if (!call.batched_ok || call.twin)
+    if (const int rc = pairs_grid_is(c, call.batched_ok, call.who, call.twin)) return rc;
   if (dev_queries && n_queries > kPairsMaxPoints)
     return fail(SC_ERR_CAPACITY, "%lld queries, at most %lld", (long long)n_queries, (long long)kPairsMaxPoints);
   r->rows = dev_queries ? n_queries : c->pairs.m;
@@ -528,16 +550,16 @@ int sc_pairs_sum_grad_device(sc_ctx* c, const double* dev_queries, int64_t n_que
 // ---- distance histograms (sc_hist.h) --------------------------------------------------------------
 
 template <int NB>
-static void hist_launch(sc_ctx* c, const Reader& r, const HistEdges& edges, int bins, const HistOut& out) {
+static void hist_launch(sc_ctx* c, const Reader& r, const HistEdges& edges, int bins, long long* acc, const HistOut& out) {
   const int64_t grid = std::max<int64_t>(1, (r.rows + kHistBlock - 1) / kHistBlock);  // (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_hist<NB>, dim3((unsigned)grid), dim3(kHistBlock), 0, c->stream, r.view, edges, bins, c->hist.flag(),
-                     r.queries, (long long)r.rows, c->hist.acc(), out);
+  hipLaunchKernelGGL((r.view.bt.clouds ? k_hist<NB, true> : k_hist<NB, false>), dim3((unsigned)grid), dim3(kHistBlock), 0,
+                     c->stream, r.view, edges, bins, c->hist.flag(), r.queries, (long long)r.rows, acc, out);
 }
 
-extern "C" {
-
-int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* edges2, int32_t bins,
-                         int32_t* dev_table, int64_t* dev_total, int64_t room_rows, int64_t* dev_counts) {
+// sc_pairs_hist_device and sc_pairs_hist_batch_device: `batched` says which; `dev_total` holds bins words, or -- batched --
+// `room_clouds` x bins.
+static int pairs_hist(sc_ctx* c, bool batched, const double* dev_queries, int64_t n_queries, const double* edges2, int32_t bins,
+                      int32_t* dev_table, int64_t* dev_total, int64_t room_rows, int64_t room_clouds, int64_t* dev_counts) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_counts) return fail(SC_ERR_ARG, "null counts pointer");
   if (!dev_table && !dev_total) return fail(SC_ERR_ARG, "neither a table nor totals to write");
@@ -547,28 +569,54 @@ int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries
   for (int k = 0; k < bins; ++k)
     if (!(edges2[k] < edges2[k + 1])) return fail(SC_ERR_ARG, "the squared edges must be strictly ascending (edge %d is not)", k + 1);
   static_assert(kHistMaxBins == SC_HIST_MAX_BINS, "the header's bound is the kernel's");
+  if (batched && room_clouds < 0) return fail(SC_ERR_ARG, "negative room");
   Reader r;
-  if (const int rc = reader_begin(c, {"sc_pairs_hist_device", "take a histogram of", "the table holds", false, dev_table != nullptr},
-                                  dev_queries, n_queries, room_rows, &r))
-    return rc;
+  const ReaderCall call = batched ? ReaderCall{"sc_pairs_hist_batch_device", "take a histogram of", "the table holds", true,
+                                               dev_table != nullptr, "sc_pairs_hist_device"}
+                                  : ReaderCall{"sc_pairs_hist_device", "take a histogram of", "the table holds", false,
+                                               dev_table != nullptr, "sc_pairs_hist_batch_device"};
+  if (const int rc = reader_begin(c, call, dev_queries, n_queries, room_rows, &r)) return rc;
   if (!(edges2[bins] <= c->pairs.grid.r2))
     return fail(SC_ERR_ARG, "the last squared edge %.17g lies beyond the count's squared radius %.17g", edges2[bins], c->pairs.grid.r2);
-  if (const int rc = c->hist.ensure(c->stream)) return rc;
+  const int64_t cells = batched ? c->pairs.clouds * bins : 0;  // the batched accumulator: a line of bins per cloud
+  if (cells > SC_HIST_BATCH_MAX_CELLS)
+    return fail(SC_ERR_CAPACITY, "%lld clouds x %d bins, at most %lld words of totals", (long long)c->pairs.clouds, (int)bins,
+                (long long)SC_HIST_BATCH_MAX_CELLS);
+  if (batched && dev_total && room_clouds < c->pairs.clouds)
+    return fail(SC_ERR_CAPACITY, "the totals hold %lld clouds, the grid has %lld", (long long)room_clouds, (long long)c->pairs.clouds);
+  if (const int rc = c->hist.ensure(c->stream, cells)) return rc;
   r.view.g.r2 = edges2[bins];  // the full list up to the histogram's own last edge: the cells are the count's, which are no smaller
   HistEdges edges{};
   std::copy(edges2, edges2 + bins + 1, edges.e2);
   const HistOut out{(int*)dev_table, (long long*)dev_total, (long long*)dev_counts};
-  // (one memset: the accumulator and, behind it, the flag)
-  if (const int rc = reader_check(c, r, c->hist.flag(), c->hist.words.get(), (kHistMaxBins + 1) * sizeof(long long), -1, -1, dev_counts))
-    return rc;
-  if (bins <= kHistFewBins) hist_launch<kHistFewBins>(c, r, edges, bins, out);
-  else if (bins <= kHistMidBins) hist_launch<kHistMidBins>(c, r, edges, bins, out);
-  else hist_launch<kHistMaxBins>(c, r, edges, bins, out);
-  if (dev_total)
-    hipLaunchKernelGGL(k_hist_finish, dim3(1), dim3(kHistBlock), 0, c->stream, (int)bins, r.view.flag, c->hist.flag(),
-                       c->hist.acc(), out.total);
+  // (one memset: the accumulator and, behind it, the flag -- batched: the flag and, behind it, the clouds' accumulator)
+  long long* acc = batched ? c->hist.batch_acc() : c->hist.acc();
+  void* zero = batched ? (void*)c->hist.flag() : (void*)c->hist.words.get();
+  const size_t zero_words = batched ? (size_t)cells + 1 : (size_t)kHistMaxBins + 1;
+  if (const int rc = reader_check(c, r, c->hist.flag(), zero, zero_words * sizeof(long long), -1, -1, dev_counts)) return rc;
+  if (bins <= kHistFewBins) hist_launch<kHistFewBins>(c, r, edges, bins, acc, out);
+  else if (bins <= kHistMidBins) hist_launch<kHistMidBins>(c, r, edges, bins, acc, out);
+  else hist_launch<kHistMaxBins>(c, r, edges, bins, acc, out);
+  if (dev_total) {
+    const long long words = batched ? (long long)cells : (long long)bins;
+    hipLaunchKernelGGL(k_hist_finish, dim3((unsigned)((words + kHistBlock - 1) / kHistBlock)), dim3(kHistBlock), 0, c->stream,
+                       words, r.view.flag, c->hist.flag(), acc, out.total);
+  }
   HIPCHK(hipGetLastError());
   return SC_OK;
+}
+
+extern "C" {
+
+int sc_pairs_hist_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* edges2, int32_t bins,
+                         int32_t* dev_table, int64_t* dev_total, int64_t room_rows, int64_t* dev_counts) {
+  return pairs_hist(c, false, dev_queries, n_queries, edges2, bins, dev_table, dev_total, room_rows, 0, dev_counts);
+}
+
+int sc_pairs_hist_batch_device(sc_ctx* c, const double* dev_queries, int64_t n_queries, const double* edges2, int32_t bins,
+                               int32_t* dev_table, int64_t* dev_cloud_total, int64_t room_rows, int64_t room_clouds,
+                               int64_t* dev_counts) {
+  return pairs_hist(c, true, dev_queries, n_queries, edges2, bins, dev_table, dev_cloud_total, room_rows, room_clouds, dev_counts);
 }
 
 }  // extern "C"
@@ -603,34 +651,37 @@ static int rays_check(sc_ctx* c, const Reader& r, double disc_radius, double max
   return SC_OK;
 }
 
-extern "C" {
-
-int sc_pairs_rays_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, double disc_radius,
-                         double max_t, const double* segments, int32_t n_segments, double* dev_t, int64_t* dev_hit,
-                         int64_t room_rows, int64_t* dev_counts) {
+// sc_pairs_rays_device and sc_pairs_rays_batch_device: `batched` says which.
+static int pairs_rays(sc_ctx* c, bool batched, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                      double disc_radius, double max_t, const double* segments, int32_t n_segments, double* dev_t,
+                      int64_t* dev_hit, int64_t room_rows, int64_t* dev_counts) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_counts)
     return fail(SC_ERR_ARG, "null origins, directions, t, hit or counts pointer");
   if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
   Reader r;
-  if (const int rc = reader_begin(c, {"sc_pairs_rays_device", "send rays through", "t and hit hold", false, true}, dev_origins,
-                                  n_rays, room_rows, &r))
-    return rc;
+  const ReaderCall call = batched ? ReaderCall{"sc_pairs_rays_batch_device", "send rays through", "t and hit hold", true, true,
+                                               "sc_pairs_rays_device"}
+                                  : ReaderCall{"sc_pairs_rays_device", "send rays through", "t and hit hold", false, true,
+                                               "sc_pairs_rays_batch_device"};
+  if (const int rc = reader_begin(c, call, dev_origins, n_rays, room_rows, &r)) return rc;
   const XY* dirs = (const XY*)dev_directions;
   const RayOut out{dev_t, (long long*)dev_hit, (long long*)dev_counts};
   RayWalls walls;
   if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
   const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_rays, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, (int)(disc_radius > 0),
-                     disc_radius * disc_radius, max_t, c->pairs.readerFlag.get(), r.queries, dirs, (long long)r.rows, out);
+  hipLaunchKernelGGL(batched ? k_rays<true> : k_rays<false>, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls,
+                     (int)(disc_radius > 0), disc_radius * disc_radius, max_t, c->pairs.readerFlag.get(), r.queries, dirs,
+                     (long long)r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
 
-int sc_pairs_ray_paths_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, int32_t bounces,
-                              double disc_radius, double max_t, const double* segments, int32_t n_segments, double* dev_t,
-                              int64_t* dev_hit, double* dev_points, double* dev_normals, int64_t* dev_end, int64_t room_rows,
-                              int64_t* dev_counts) {
+// sc_pairs_ray_paths_device and sc_pairs_ray_paths_batch_device: `batched` says which.
+static int pairs_ray_paths(sc_ctx* c, bool batched, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                           int32_t bounces, double disc_radius, double max_t, const double* segments, int32_t n_segments,
+                           double* dev_t, int64_t* dev_hit, double* dev_points, double* dev_normals, int64_t* dev_end,
+                           int64_t room_rows, int64_t* dev_counts) {
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_points || !dev_normals || !dev_end || !dev_counts)
     return fail(SC_ERR_ARG, "null origins, directions, t, hit, points, normals, end or counts pointer");
@@ -640,19 +691,53 @@ int sc_pairs_ray_paths_device(sc_ctx* c, const double* dev_origins, const double
   if (((uintptr_t)dev_points | (uintptr_t)dev_normals) & 15) return fail(SC_ERR_ARG, "the points and the normals must be aligned to 16 bytes");
   if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
   Reader r;
-  if (const int rc = reader_begin(c, {"sc_pairs_ray_paths_device", "send rays through", "the paths hold", false, true}, dev_origins,
-                                  n_rays, room_rows, &r))
-    return rc;
+  const ReaderCall call = batched ? ReaderCall{"sc_pairs_ray_paths_batch_device", "send rays through", "the paths hold", true, true,
+                                               "sc_pairs_ray_paths_device"}
+                                  : ReaderCall{"sc_pairs_ray_paths_device", "send rays through", "the paths hold", false, true,
+                                               "sc_pairs_ray_paths_batch_device"};
+  if (const int rc = reader_begin(c, call, dev_origins, n_rays, room_rows, &r)) return rc;
   const XY* dirs = (const XY*)dev_directions;
   const RayPathOut out{dev_t, (long long*)dev_hit, (XY*)dev_points, (XY*)dev_normals, (long long*)dev_end, (long long*)dev_counts};
   RayWalls walls;
   if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
   const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
-  hipLaunchKernelGGL(k_ray_paths, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls, (int)(disc_radius > 0),
-                     disc_radius * disc_radius, max_t, (int)bounces + 1, c->pairs.readerFlag.get(), r.queries, dirs,
-                     (long long)r.rows, out);
+  hipLaunchKernelGGL(batched ? k_ray_paths<true> : k_ray_paths<false>, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view,
+                     walls, (int)(disc_radius > 0), disc_radius * disc_radius, max_t, (int)bounces + 1,
+                     c->pairs.readerFlag.get(), r.queries, dirs, (long long)r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
+}
+
+extern "C" {
+
+int sc_pairs_rays_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, double disc_radius,
+                         double max_t, const double* segments, int32_t n_segments, double* dev_t, int64_t* dev_hit,
+                         int64_t room_rows, int64_t* dev_counts) {
+  return pairs_rays(c, false, dev_origins, dev_directions, n_rays, disc_radius, max_t, segments, n_segments, dev_t, dev_hit,
+                    room_rows, dev_counts);
+}
+
+int sc_pairs_rays_batch_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                               double disc_radius, double max_t, const double* segments, int32_t n_segments, double* dev_t,
+                               int64_t* dev_hit, int64_t room_rows, int64_t* dev_counts) {
+  return pairs_rays(c, true, dev_origins, dev_directions, n_rays, disc_radius, max_t, segments, n_segments, dev_t, dev_hit,
+                    room_rows, dev_counts);
+}
+
+int sc_pairs_ray_paths_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays, int32_t bounces,
+                              double disc_radius, double max_t, const double* segments, int32_t n_segments, double* dev_t,
+                              int64_t* dev_hit, double* dev_points, double* dev_normals, int64_t* dev_end, int64_t room_rows,
+                              int64_t* dev_counts) {
+  return pairs_ray_paths(c, false, dev_origins, dev_directions, n_rays, bounces, disc_radius, max_t, segments, n_segments, dev_t,
+                         dev_hit, dev_points, dev_normals, dev_end, room_rows, dev_counts);
+}
+
+int sc_pairs_ray_paths_batch_device(sc_ctx* c, const double* dev_origins, const double* dev_directions, int64_t n_rays,
+                                    int32_t bounces, double disc_radius, double max_t, const double* segments,
+                                    int32_t n_segments, double* dev_t, int64_t* dev_hit, double* dev_points, double* dev_normals,
+                                    int64_t* dev_end, int64_t room_rows, int64_t* dev_counts) {
+  return pairs_ray_paths(c, true, dev_origins, dev_directions, n_rays, bounces, disc_radius, max_t, segments, n_segments, dev_t,
+                         dev_hit, dev_points, dev_normals, dev_end, room_rows, dev_counts);
 }
 
 }  // extern "C"

@@ -50,8 +50,11 @@
 // sidx[k] that pairs_accept needs anyway.  A row reads its record (lo, hi, cloud) once, before its nine cells -- a point
 // from the workspace, a query by binary search over query_ptr --, nothing is read per candidate.  The sort, the scans,
 // k_pairs_place and scell are as they are.  Every kernel that walks is a template on `batched`: the unbatched
-// instantiation carries no record at all.  The clusters and the histograms (sc_clusters.h, sc_hist.h) are not batched:
-// their host calls refuse a batched grid.
+// instantiation carries no record at all.  The clusters, the histograms, the rays and the ray paths (sc_clusters.h,
+// sc_hist.h, sc_rays.h) read a batched grid through entry points of their own (sc_pairs_label_batch_device,
+// sc_pairs_hist_batch_device, sc_pairs_rays_batch_device, sc_pairs_ray_paths_batch_device): their outputs have other
+// shapes -- a cluster offset table, totals per cloud -- and the unbatched calls keep refusing a batched grid.  Each pair
+// shares one host body and one kernel template.
 //
 // The readers.  The workspace a count leaves is read by the fill and by the clusters, the nearest-k tables, the weighted
 // sums, their position gradient and the distance histograms (sc_clusters.h, sc_nearest.h, sc_fields.h, sc_fields_grad.h,
@@ -164,9 +167,9 @@ __device__ __forceinline__ long long pairs_status(int flag) {
 
 // counts[1] of a reader with a flag up: `flag` the count's, `own` the call's.  Bad offsets first, then the domain, then the
 // rows.  A reader that never raises a bit never gets its status: the nearest and the histogram hand k_reader_check no row
-// counts, so -2 is the sums' and the gradient's alone; the clusters and the histograms refuse a batched grid, so neither
-// the count's batch bit nor their own is ever up and -1 is all they report; and on an unbatched grid no reader has query
-// offsets to be wrong.
+// counts, so -2 is the sums' and the gradient's alone; the unbatched histogram refuses a batched grid, so neither the
+// count's batch bit nor its own is ever up and -1 is all it reports (the batched one reports -3 too); and on an unbatched
+// grid no reader has query offsets to be wrong.
 __device__ __forceinline__ long long reader_status(int flag, int own) {
   if ((flag & kPairsFlagBatch) || (own & kReaderFlagBatch)) return kPairsStatusBatch;
   return flag || (own & kReaderFlagDomain) ? kPairsStatusDomain : kPairsStatusRows;

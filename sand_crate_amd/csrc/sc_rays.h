@@ -96,6 +96,16 @@
 // the cells are mostly empty), and the lanes of a wave wait for its longest ray.  Over 1,048,576 particles the wave per
 // ray took 25 us against 42 us for a fan of 256 rays and 0.79 ms against 2.52 ms for 262,144 rays looking down; over
 // every 256th of those particles, where a ray walks some sixty cells, 74 against 758 us and 1.04 against 1.79 ms.
+//
+// The batched form (sc_pairs_rays_batch_device, sc_pairs_ray_paths_batch_device, on the grid of a count after
+// sc_pairs_set_batch_device; the rule is tests/batch_readers_spec.py).  Rays are always the query form, so their clouds
+// come as query offsets (sc_pairs_set_query_batch_device): ray r of ray-cloud b meets the discs of cloud b only.  The
+// wave reads its ray's record (lo, hi, cloud) once -- pairs_row over query_ptr, uniform and so scalar --, hashes every
+// step's cells with the cloud and drops a candidate whose index is outside [lo, hi) (pairs_in): the hash is for speed,
+// the range for exactness, as in sc_pairs.h.  The walls go in by value and are shared by all clouds; `hit`, and a path's
+// excluded disc, are global indices.  Nothing in the walk's claim changes: it speaks of the candidates that are met, and
+// a cloud's discs lie in the buckets of its own hash.  k_rays_check is unchanged.  Offsets out of order -- the
+// count's or the rays' -- are status -3.  The unbatched instantiations carry no record.
 #pragma once
 #include "sc_pairs.h"
 
@@ -119,7 +129,10 @@ struct RayOut {
   long long* counts;  // [2]: rays, status
 };
 
+// counts[1] with a flag up: batched, offsets out of order -- the count's or the rays' own -- come first (-3).
+template <bool batched>
 __device__ __forceinline__ long long ray_status(int flag, int own) {
+  if (batched && ((flag & kPairsFlagBatch) || (own & kReaderFlagBatch))) return kPairsStatusBatch;
   return flag || (own & kReaderFlagDomain) ? kPairsStatusDomain : kRayStatusRange;
 }
 
@@ -168,15 +181,18 @@ __device__ __forceinline__ bool ray_disc(XY o, XY d, double a, XY c, double rho2
   return t <= max_t;
 }
 
-// The candidates of one bucket, places lo .. hi - 1: those whose own cell is (cx, cy), by the rule, into the best key.
-__device__ __forceinline__ void ray_scan(const PairsView& v, XY o, XY d, double a, double rho2, double max_t, unsigned cx,
-                                         unsigned cy, int lo, int hi, double& best, int& who) {
+// The candidates of one bucket, places lo .. hi - 1: those whose own cell is (cx, cy) -- and, batched, whose index lies
+// in the ray's cloud --, by the rule, into the best key.  (`row` by value: by reference the compiler scheduled the
+// unbatched k_rays differently from the kernel without a record; by value it is that kernel, instruction for instruction.)
+template <bool batched>
+__device__ __forceinline__ void ray_scan(const PairsView& v, const PairsRow row, XY o, XY d, double a, double rho2,
+                                         double max_t, unsigned cx, unsigned cy, int lo, int hi, double& best, int& who) {
   for (int k = lo; k < hi; ++k) {
     const uint2 cell = v.scell[k];
     if (cell.x != cx || cell.y != cy) continue;
     const int j = v.sidx[k];
     double t;
-    if (!ray_disc(o, d, a, v.sxy[k], rho2, max_t, t)) continue;
+    if (!pairs_in<batched>(row, j) || !ray_disc(o, d, a, v.sxy[k], rho2, max_t, t)) continue;
     if (t < best || (t == best && j < who)) {
       best = t;
       who = j;
@@ -211,6 +227,9 @@ __global__ void __launch_bounds__(kBlock)
 
 // A wave per ray: workgroup r is ray r.  Every lane computes the ray and its walls (uniform: scalar work); lane L < 63
 // takes cell L % 9 of step k0 + L / 9 of the batch.  `discs` 0: walls alone.  v.g.radius and v.g.h are the count's.
+// Batched: the ray's record (lo, hi, cloud) comes from pairs_row over query_ptr -- the rays are queries --, uniform over
+// the wave and so scalar work; the cells hash with the ray's cloud and ray_scan tests pairs_in.  `who` stays global.
+template <bool batched>
 __global__ void __launch_bounds__(kRayBlock)
     k_rays(PairsView v, RayWalls walls, int discs, double rho2, double max_t, const int* __restrict__ own_flag,
            const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayOut out) {
@@ -219,7 +238,7 @@ __global__ void __launch_bounds__(kRayBlock)
   const int lane = (int)threadIdx.x;
   const bool up = *v.flag || *own_flag;
   if (r == 0 && lane == 0) {
-    if (up) out.counts[1] = ray_status(*v.flag, *own_flag);
+    if (up) out.counts[1] = ray_status<batched>(*v.flag, *own_flag);
     else out.counts[0] = n_rays;
   }
   if (up || r >= n_rays) return;
@@ -236,6 +255,7 @@ __global__ void __launch_bounds__(kRayBlock)
   int sw, who = kRayNoDisc;
   ray_walls(walls, o, d, max_t, tw, sw);
   if (discs) {
+    const PairsRow row = pairs_row<batched>(v.bt, r);
     const double t_end = fmin(max_t, tw), dt = v.g.radius / sqrt(a);
     const int step = lane / 9, c = lane % 9;
     for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
@@ -244,8 +264,8 @@ __global__ void __launch_bounds__(kRayBlock)
         const double tm = ((double)k + 0.5) * dt;
         const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
         const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
-        const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);
-        ray_scan(v, o, d, a, rho2, max_t, cx, cy, v.start[bk], v.start[bk + 1], best, who);
+        const unsigned bk = pairs_bucket(cx, cy, row.cloud, v.g.mask);
+        ray_scan<batched>(v, row, o, d, a, rho2, max_t, cx, cy, v.start[bk], v.start[bk + 1], best, who);
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave, in every lane
@@ -277,16 +297,17 @@ struct RayPathOut {
 };
 
 // ray_scan for a leg of a path: disc `skip` takes no part, `later` is ray_disc's, and the place in the sorted arrays of
-// the best candidate rides along with its key, for the normal.
-__device__ __forceinline__ void ray_scan_path(const PairsView& v, XY o, XY d, double a, double rho2, double max_t, bool later,
-                                              int skip, unsigned cx, unsigned cy, int lo, int hi, double& best, int& who,
-                                              int& place) {
+// the best candidate rides along with its key, for the normal.  `skip` is a global index, as j is, batched or not.
+template <bool batched>
+__device__ __forceinline__ void ray_scan_path(const PairsView& v, const PairsRow row, XY o, XY d, double a, double rho2,
+                                              double max_t, bool later, int skip, unsigned cx, unsigned cy, int lo, int hi,
+                                              double& best, int& who, int& place) {
   for (int k = lo; k < hi; ++k) {
     const uint2 cell = v.scell[k];
     if (cell.x != cx || cell.y != cy) continue;
     const int j = v.sidx[k];
     double t;
-    if (j == skip || !ray_disc<true>(o, d, a, v.sxy[k], rho2, max_t, t, later)) continue;
+    if (j == skip || !pairs_in<batched>(row, j) || !ray_disc<true>(o, d, a, v.sxy[k], rho2, max_t, t, later)) continue;
     if (t < best || (t == best && j < who)) {
       best = t;
       who = j;
@@ -306,7 +327,9 @@ __device__ __forceinline__ void ray_path_write(const RayPathOut& out, long long 
 // budget m and the excluded wall and disc -- and computes the walls, the normal, the reflection and the tests of the next
 // leg: all uniform over the wave.  The walk of a leg is k_rays', from step 0 with the leg's own dt.  Lane 0 writes the
 // legs; the lanes share the rows the path never reached.  Leg 0's own domain and range are the call's (the flags); a
-// later leg's end the ray only.
+// later leg's end the ray only.  Batched: the ray's record once, before leg 0, as in k_rays; every leg stays in the
+// ray's cloud.
+template <bool batched>
 __global__ void __launch_bounds__(kRayBlock)
     k_ray_paths(PairsView v, RayWalls walls, int discs, double rho2, double max_t, int legs, const int* __restrict__ own_flag,
                 const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayPathOut out) {
@@ -314,7 +337,7 @@ __global__ void __launch_bounds__(kRayBlock)
   const int lane = (int)threadIdx.x;
   const bool up = *v.flag || *own_flag;
   if (r == 0 && lane == 0) {
-    if (up) out.counts[1] = ray_status(*v.flag, *own_flag);
+    if (up) out.counts[1] = ray_status<batched>(*v.flag, *own_flag);
     else out.counts[0] = n_rays;
   }
   if (up || r >= n_rays) return;
@@ -326,6 +349,7 @@ __global__ void __launch_bounds__(kRayBlock)
   int skip_wall = -1, skip_disc = -1;  // (no wall and no disc has these indices)
   long long end = 0;
   int leg = 0;
+  const PairsRow rec = pairs_row<batched>(v.bt, r);  // the ray's cloud
   if (!ray_live(o, d, a)) end = kRayEndDead;
   while (end == 0 && leg < legs) {
     double tw, best = inf;
@@ -344,8 +368,9 @@ __global__ void __launch_bounds__(kRayBlock)
           const double tm = ((double)k + 0.5) * dt;
           const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
           const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
-          const unsigned bk = pairs_bucket(cx, cy, 0u, v.g.mask);
-          ray_scan_path(v, o, d, a, rho2, m, leg > 0, skip_disc, cx, cy, v.start[bk], v.start[bk + 1], best, who, place);
+          const unsigned bk = pairs_bucket(cx, cy, rec.cloud, v.g.mask);
+          ray_scan_path<batched>(v, rec, o, d, a, rho2, m, leg > 0, skip_disc, cx, cy, v.start[bk], v.start[bk + 1], best, who,
+                                 place);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave and its place, in every lane

@@ -294,7 +294,8 @@ class Engine:
         0..n.  `counts`, int64 (2,), receives n and E, the number of pairs (E = -1: a coordinate outside the domain
         |c| / radius < 2^31).  `half` keeps j > i only.  `room` defaults to R rows.  `batch`, an int64 CUDA tensor of
         B + 1 ascending offsets from 0 to n, makes the points B clouds that see only themselves (`pairs_set_batch`; needs
-        `points`): the readers then read a batched grid, `pairs_label` and `pairs_hist` refuse it, and E = -3 says that
+        `points`): the readers then read a batched grid -- the clusters, histograms and rays through `pairs_label_batch`,
+        `pairs_hist_batch`, `pairs_rays_batch` and `pairs_ray_paths_batch` --, and E = -3 says that
         the offsets are not in order (nothing else is written).  Enqueued on the context's stream, no synchronisation,
         with the stream rules of `export_state`.  Returns `counts`."""
         n = 0 if points is None else _state_tensor(points, "points", "float64", (2,), self.device)
@@ -336,7 +337,21 @@ class Engine:
         cluster's member count and smallest member; clusters are numbered 0..C-1 ascending in that member.  `counts`,
         int64 (2,), receives n and C (C = -1: the count found a coordinate outside the domain, nothing else is written).
         `room` defaults to R rows, `room_clusters` to K (0 without `sizes` and `roots`): clusters from it on are not
-        written.  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
+        written.  Refuses a batched grid: `pairs_label_batch` reads one.  Enqueued on the context's stream, no
+        synchronisation.  Returns `counts`."""
+        return self._label(labels, sizes, roots, None, counts, room, room_clusters)
+
+    def pairs_label_batch(self, labels, sizes=None, roots=None, *, cluster_ptr, counts, room: int | None = None,
+                          room_clusters: int | None = None):
+        """`pairs_label` of a batched grid -- the last `pairs_count` had `batch` -- (sc_pairs_label_batch_device; the rule
+        is tests/batch_readers_spec.py): a cluster never crosses clouds, labels and roots are global, and `cluster_ptr`,
+        int64 (B + 1,), receives the offsets of the clouds into the clusters: cloud b's are
+        ``cluster_ptr[b]:cluster_ptr[b + 1]``, always whole.  C = -3 says that the count's offsets were not in order
+        (nothing else is written).  `pairs_cluster_sums` reads the label as any other.  Refuses an unbatched grid."""
+        _state_tensor(cluster_ptr, "cluster_ptr", "int64", (), self.device)
+        return self._label(labels, sizes, roots, cluster_ptr, counts, room, room_clusters)
+
+    def _label(self, labels, sizes, roots, cluster_ptr, counts, room, room_clusters):
         rows = _state_tensor(labels, "labels", "int64", (), self.device)
         clusters = None
         for t, name in ((sizes, "sizes"), (roots, "roots")):
@@ -348,8 +363,12 @@ class Engine:
         if room_clusters > (clusters or 0):
             raise ValueError(f"room_clusters {room_clusters} exceeds the tensors' {clusters or 0} entries")
         labels_at, sizes_at, roots_at = _addresses(counts, labels, sizes, roots)
-        N.check(self._lib.sc_pairs_label_device(self._ctx, labels_at, room, sizes_at, roots_at, room_clusters,
-                                                N._P(counts.data_ptr())))
+        if cluster_ptr is None:
+            N.check(self._lib.sc_pairs_label_device(self._ctx, labels_at, room, sizes_at, roots_at, room_clusters,
+                                                    N._P(counts.data_ptr())))
+        else:
+            N.check(self._lib.sc_pairs_label_batch_device(self._ctx, labels_at, room, sizes_at, roots_at, room_clusters,
+                                                          N._P(cluster_ptr.data_ptr()), N._P(counts.data_ptr())))
         return counts
 
     def pairs_cluster_sums(self, values, sums, mins=None, maxs=None, *, counts, room_clusters: int | None = None):
@@ -506,21 +525,41 @@ class Engine:
         ``edges[-1]`` may be at most the count's radius.  The rows are the count's points -- a point is never its own
         partner -- or with `queries`, a float64 (q, 2) CUDA tensor, those points of any kind.  `counts`, int64 (2,),
         receives the row count and the status: 0, or -1 when a point or a query lies outside the domain (then nothing
-        else is written).  `room` defaults to R rows (0 without a table).  Enqueued on the context's stream, no
-        synchronisation.  Returns `counts`."""
+        else is written).  `room` defaults to R rows (0 without a table).  Refuses a batched grid: `pairs_hist_batch`
+        reads one.  Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
+        return self._hist(table, total, False, edges, queries, None, counts, room)
+
+    def pairs_hist_batch(self, table=None, cloud_total=None, *, edges, queries=None, query_batch=None, counts,
+                         room: int | None = None):
+        """`pairs_hist` of a batched grid -- the last `pairs_count` had `batch` -- (sc_pairs_hist_batch_device; the rule is
+        tests/batch_readers_spec.py): a row counts the partners of its own cloud only, `table` is as before and
+        `cloud_total`, int64 (B, bins) or None, receives the column sums per cloud.  `queries` come with `query_batch`,
+        their B + 1 offsets (`pairs_set_query_batch`).  Status -3 says that offsets were not in order (nothing else is
+        written).  Refuses an unbatched grid."""
+        return self._hist(table, cloud_total, True, edges, queries, query_batch, counts, room)
+
+    def _hist(self, table, total, batched, edges, queries, query_batch, counts, room):
         e2 = N.hist_squared_edges(edges)
         bins = len(e2) - 1
         if table is None and total is None:
             raise ValueError("neither table nor total to write")
         rows = 0 if table is None else _state_tensor(table, "table", "int32", (bins,), self.device)
-        if total is not None:
+        clouds = 0
+        if total is not None and batched:
+            clouds = _state_tensor(total, "cloud_total", "int64", (bins,), self.device)
+        elif total is not None:
             _state_tensor(total, "total", "int64", (), self.device, bins)
         q = _query_rows(queries, self.device)
         _counts_tensor(counts, self.device)
         room = _room(room, rows, "the table's")
         queries_at, table_at, total_at = _addresses(counts, queries, table, total)
-        N.check(self._lib.sc_pairs_hist_device(self._ctx, queries_at, q, N.dptr(e2), bins, table_at, total_at, room,
-                                               N._P(counts.data_ptr())))
+        if batched:
+            self._query_batch(queries, query_batch)
+            N.check(self._lib.sc_pairs_hist_batch_device(self._ctx, queries_at, q, N.dptr(e2), bins, table_at, total_at, room,
+                                                         clouds, N._P(counts.data_ptr())))
+        else:
+            N.check(self._lib.sc_pairs_hist_device(self._ctx, queries_at, q, N.dptr(e2), bins, table_at, total_at, room,
+                                                   N._P(counts.data_ptr())))
         return counts
 
     def pairs_rays(self, t, hit, *, origins, directions, disc_radius: float, max_t: float, segments=None, counts,
@@ -534,8 +573,22 @@ class Engine:
         array (S, 2, 2), S at most 16, or None.  A wall wins a tie with a disc, the lower index a tie of two of a kind.
         `counts`, int64 (2,), receives the ray count and the status: 0, -1 when a point, an origin or a ray's end point
         ``origin + max_t * direction`` lies outside the domain, -4 when a ray would walk more than 8192 cells (then
-        nothing else is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.
-        Returns `counts`."""
+        nothing else is written).  `room` defaults to R rows.  Refuses a batched grid: `pairs_rays_batch` reads one.
+        Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
+        return self._rays("sc_pairs_rays_device", None, t, hit, origins, directions, disc_radius, max_t, segments,
+                          counts, room)
+
+    def pairs_rays_batch(self, t, hit, *, origins, directions, ray_batch, disc_radius: float, max_t: float, segments=None,
+                         counts, room: int | None = None):
+        """`pairs_rays` of a batched grid -- the last `pairs_count` had `batch` -- (sc_pairs_rays_batch_device; the rule is
+        tests/batch_readers_spec.py): `ray_batch`, int64 (B + 1,), cuts the rays as `batch` cut the points
+        (`pairs_set_query_batch`: the rays are queries), rays ``ray_batch[b]:ray_batch[b + 1]`` meet the discs of cloud b
+        only, the walls are shared, and `hit` is the global row.  Status -3 says that offsets were not in order (nothing
+        else is written).  Refuses an unbatched grid."""
+        return self._rays("sc_pairs_rays_batch_device", ray_batch, t, hit, origins, directions, disc_radius, max_t,
+                          segments, counts, room)
+
+    def _rays(self, fn, ray_batch, t, hit, origins, directions, disc_radius, max_t, segments, counts, room):
         disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
         rows = _state_tensor(t, "t", "float64", (), self.device)
         _state_tensor(hit, "hit", "int64", (), self.device, rows)
@@ -544,9 +597,9 @@ class Engine:
         _counts_tensor(counts, self.device)
         room = _room(room, rows, "the tensors'")
         origins_at, directions_at, t_at, hit_at = _addresses(counts, origins, directions, t, hit)
-        N.check(self._lib.sc_pairs_rays_device(self._ctx, origins_at, directions_at, q, disc_radius, max_t,
-                                               N.dptr(seg) if len(seg) else None, len(seg), t_at, hit_at, room,
-                                               N._P(counts.data_ptr())))
+        self._query_batch(origins, ray_batch)
+        N.check(getattr(self._lib, fn)(self._ctx, origins_at, directions_at, q, disc_radius, max_t,
+                                       N.dptr(seg) if len(seg) else None, len(seg), t_at, hit_at, room, N._P(counts.data_ptr())))
         return counts
 
     def pairs_ray_paths(self, t, hit, points, normals, end, *, origins, directions, bounces: int, disc_radius: float,
@@ -560,8 +613,20 @@ class Engine:
         NaN points and normals.  A leg >= 1 does not see what the leg before it hit, and a disc its origin lies in or on
         only when it heads inward.  `origins`, `directions`, `disc_radius`, `max_t` and `segments` as in `pairs_rays`.
         `counts`, int64 (2,), receives the ray count and the status of leg 0: 0, -1 or -4 as `pairs_rays` (then nothing
-        else is written).  `room` defaults to R rows.  Enqueued on the context's stream, no synchronisation.  Returns
-        `counts`."""
+        else is written).  `room` defaults to R rows.  Refuses a batched grid: `pairs_ray_paths_batch` reads one.  Enqueued
+        on the context's stream, no synchronisation.  Returns `counts`."""
+        return self._ray_paths("sc_pairs_ray_paths_device", None, t, hit, points, normals, end, origins, directions,
+                               bounces, disc_radius, max_t, segments, counts, room)
+
+    def pairs_ray_paths_batch(self, t, hit, points, normals, end, *, origins, directions, ray_batch, bounces: int,
+                              disc_radius: float, max_t: float, segments=None, counts, room: int | None = None):
+        """`pairs_ray_paths` of a batched grid (sc_pairs_ray_paths_batch_device): `ray_batch` and everything about the
+        clouds as in `pairs_rays_batch`; every leg of a path stays in its ray's cloud."""
+        return self._ray_paths("sc_pairs_ray_paths_batch_device", ray_batch, t, hit, points, normals, end, origins,
+                               directions, bounces, disc_radius, max_t, segments, counts, room)
+
+    def _ray_paths(self, fn, ray_batch, t, hit, points, normals, end, origins, directions, bounces, disc_radius, max_t, segments,
+                   counts, room):
         disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
         bounces = int(bounces)
         if not 0 <= bounces <= N.RAY_MAX_BOUNCES:
@@ -577,9 +642,9 @@ class Engine:
         _counts_tensor(counts, self.device)
         room = _room(room, rows, "the tensors'")
         origins_at, directions_at, *out_at = _addresses(counts, origins, directions, t, hit, points, normals, end)
-        N.check(self._lib.sc_pairs_ray_paths_device(self._ctx, origins_at, directions_at, q, bounces, disc_radius, max_t,
-                                                    N.dptr(seg) if len(seg) else None, len(seg), *out_at, room,
-                                                    N._P(counts.data_ptr())))
+        self._query_batch(origins, ray_batch)
+        N.check(getattr(self._lib, fn)(self._ctx, origins_at, directions_at, q, bounces, disc_radius, max_t,
+                                       N.dptr(seg) if len(seg) else None, len(seg), *out_at, room, N._P(counts.data_ptr())))
         return counts
 
     # -- frames

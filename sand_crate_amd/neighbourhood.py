@@ -1,11 +1,13 @@
-"""The neighbourhood calls of `Crate` -- `pair_tensors`, `cluster_tensors`, `cluster_sums`, `cluster_observables`,
-`neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram`, `ray_tensors` and `ray_paths` -- as a mixin `Crate`
+"""The neighbourhood calls of `Crate` -- `pair_tensors`, `cluster_tensors`, `cluster_tensors_batch`, `cluster_sums`,
+`cluster_sums_batch`, `cluster_observables`, `neighbor_tensors`, `field_tensors`, `field_function`, `distance_histogram`,
+`distance_histogram_batch`, `ray_tensors` and `ray_paths` -- as a mixin `Crate`
 inherits (crate.py is the reference's surface, the tick and growth), and the protocol all of them follow,
 written once: `_Search`.
 
 Every call counts the pairs on the grid (`Engine.pairs_count`) and then runs one or more readers of that grid
 (`pairs_fill`, `pairs_label`, `pairs_cluster_sums`, `pairs_nearest`, `pairs_sum`, `pairs_sum_grad`, `pairs_hist`,
-`pairs_rays`, `pairs_ray_paths`), all on the library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either
+`pairs_rays`, `pairs_ray_paths`, and the `_batch` forms of label, histogram, rays and paths on a batched grid), all on the
+library's stream, into tensors of torch's that it allocates at a size known beforehand.  Either
 it then synchronises, reads the counts, raises what the status says and cuts the tensors, or it returns the tensors as
 they are with `counts` last.  The C side of the same sharing is `reader_begin` / `reader_check`
 (csrc/sc_host_state.h).  torch is imported on first use."""
@@ -36,22 +38,23 @@ _QUERY_CALLS = ("neighbor_tensors", "field_tensors", "field_function", "distance
 _OF_EITHER = dict.fromkeys(("ray_tensors", "ray_paths"), " of a point, an origin or a ray's end point origin + max_t * direction")
 
 
-def _check_batch(who: str, device: int, points, queries, batch, query_batch) -> None:
-    """The `batch=` / `query_batch=` arguments of a neighbourhood call: ValueError before anything is enqueued."""
+def _check_batch(who: str, device: int, points, queries, batch, query_batch, second: str = "query_batch") -> None:
+    """The `batch=` / `query_batch=` arguments of a neighbourhood call: ValueError before anything is enqueued.  `second`
+    is the name the call gives its second offsets (`ray_batch` for the rays, which are the queries)."""
     if batch is None:
         if query_batch is not None:
-            raise ValueError(f"{who}: query_batch without batch")
+            raise ValueError(f"{who}: {second} without batch")
         return
     if points is None:
         raise ValueError(f"{who}: batch needs points, the state is one cloud")
     entries = _batch_tensor(batch, "batch", device)
     if queries is None:
         if query_batch is not None:
-            raise ValueError(f"{who}: query_batch without queries")
+            raise ValueError(f"{who}: {second} without queries")
     elif query_batch is None:
-        raise ValueError(f"{who}: queries of a batched call need query_batch, their clouds")
+        raise ValueError(f"{who}: {'rays' if second == 'ray_batch' else 'queries'} of a batched call need {second}, their clouds")
     else:
-        _batch_tensor(query_batch, "query_batch", device, entries)
+        _batch_tensor(query_batch, second, device, entries)
 
 
 def _field_values(values):
@@ -85,14 +88,15 @@ class _Search:
     far      the sentence of status -4, a ray that would walk beyond the cap"""
 
     def __init__(self, crate, who: str, radius=None, *, points=None, queries=None, batch=None, query_batch=None,
-                 sync: bool = True, short: str = "", far: str = ""):
+                 sync: bool = True, short: str = "", far: str = "", second: str = "query_batch"):
         import torch
         eng = crate._engine
         self.crate, self.who, self.eng, self.sync, self.short, self.far = crate, who, eng, sync, short, far
         self.points, self.queries, self.batch = points, queries, batch
         self.dev = torch.device("cuda", eng.device)
         self.radius = float(crate.diameter if radius is None else radius)
-        _check_batch(who, eng.device, points, queries, batch, query_batch)
+        _check_batch(who, eng.device, points, queries, batch, query_batch, second)
+        self.clouds = 0 if batch is None else int(batch.shape[0]) - 1
         self.bound = eng.capacity if points is None else _point_rows(points)
         self.rows = self.bound if queries is None else _point_rows(queries)
 
@@ -120,7 +124,8 @@ class _Search:
             raise ValueError(_STATUS.get(status, _STATUS[N.PAIRS_DOMAIN]).format(
                 who=self.who, radius=self.radius, short=self.short,
                 of_either=_OF_EITHER.get(self.who, " of a point or a query") if queries else "",
-                of_queries=" (of queries for query_batch)" if queries else "", far=self.far))
+                of_queries=f" (of {'rays for ray_batch' if self.who in _OF_EITHER else 'queries for query_batch'})"
+                if queries else "", far=self.far))
         if self.points is None:
             self.crate._state_changed(got[0], self.crate._cache)  # (the state is the same: only its count was learned)
         return n, status
@@ -205,19 +210,52 @@ class _Neighbourhood:
         on were not written (`labels` is whole all the same), C = -1 is the domain error (nothing else was written).  The
         tensors are written on the library's stream, and the library's stream does not wait for torch's: read them after
         `synchronize()`, and have `points` ready before the call -- or run the crate on torch's stream,
-        `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        `engine.set_stream`, and everything torch enqueues afterwards sees them.
+
+        The clusters of a minibatch of clouds in one call: `cluster_tensors_batch`."""
+        return self._clusters("cluster_tensors", radius, points, None, max_clusters)
+
+    def cluster_tensors_batch(self, radius: float | None = None, *, points, batch, max_clusters: int | None = None):
+        """`cluster_tensors` of B disjoint clouds in one call (sc_pairs_label_batch_device): `batch`, an int64 CUDA tensor
+        of B + 1 ascending offsets from 0 to n as in `pair_tensors`, cuts `points` into clouds that may overlap in space
+        completely, and a cluster never crosses clouds.  ``(labels, sizes, roots, cluster_ptr)``: labels and roots are
+        global, and because clusters are numbered by their smallest member, cloud b's clusters are the contiguous range
+        ``cluster_ptr[b]:cluster_ptr[b + 1]`` of `sizes` and `roots` -- `cluster_ptr`, int64 (B + 1,), ends at C; a cloud
+        without a finite point has none (`sand_crate_amd.pairs.cluster_cloud` gives every cluster's cloud).  The result
+        is, bit for bit, `cluster_tensors` cloud by cloud, the labels shifted by the clusters before and the roots by
+        ``batch[b]`` (tests/batch_readers_spec.py).  `max_clusters` as in `cluster_tensors`: `counts` stays last and
+        `cluster_ptr` is always whole.  Offsets that are not in order raise ValueError at the synchronisation (C = -3
+        with `max_clusters`).  (A method of its own and not `batch=` of `cluster_tensors`: the result has one tensor
+        more, as `cluster_sums_batch`'s has.)"""
+        return self._clusters("cluster_tensors", radius, points, batch, max_clusters, batched=True)
+
+    def _clusters(self, who, radius, points, batch, max_clusters, values=None, extrema=False, batched=False):
+        """`cluster_tensors`, `cluster_sums` and their `_batch` forms: count, label and -- with `values` -- reduce."""
         import torch
         sync = max_clusters is None
         if not sync and int(max_clusters) < 0:
             raise ValueError("max_clusters must not be negative")
-        call = _Search(self, "cluster_tensors", radius, points=points, sync=sync)
+        if batched and batch is None:
+            raise ValueError(f"{who}: batch must be the clouds' offsets")
+        short = "" if values is None else f"values has {values.shape[0]} rows, fewer than there are points"
+        call = _Search(self, who, radius, points=points, batch=batch, sync=sync, short=short)
         room = call.rows if sync else int(max_clusters)
         labels = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
         sizes = torch.empty(room, dtype=torch.int64, device=call.dev)
         roots = torch.empty(room, dtype=torch.int64, device=call.dev)
-        call.count()  # (one `counts` for the count and the label: (n, E), then (n, C))
-        call.eng.pairs_label(labels, sizes, roots, counts=call.counts)
-        return call.end(rows=(labels,), items=(sizes, roots))
+        width = 0 if values is None else int(values.shape[1])
+        tables = tuple(torch.empty((room, width), dtype=torch.float64, device=call.dev)
+                       for _ in range(0 if values is None else 3 if extrema else 1))
+        cluster_ptr = None if batch is None else torch.empty(call.clouds + 1, dtype=torch.int64, device=call.dev)
+        call.count()  # (one `counts` for all: (n, E) of the count, then (n, C) of the label and of the sums)
+        if batch is None:
+            call.eng.pairs_label(labels, sizes, roots, counts=call.counts)
+        else:
+            call.eng.pairs_label_batch(labels, sizes, roots, cluster_ptr=cluster_ptr, counts=call.counts)
+        if values is not None:
+            call.eng.pairs_cluster_sums(values, *tables, counts=call.counts)
+        return call.end(rows=(labels,), items=(sizes, roots, *tables), whole=(cluster_ptr,),
+                        held=() if values is None else (values,))
 
     def cluster_sums(self, values, radius: float | None = None, *, points=None, extrema: bool = False,
                      max_clusters: int | None = None):
@@ -237,7 +275,25 @@ class _Neighbourhood:
         points; with `max_clusters=K` nothing synchronises, the per-cluster tensors come at K rows and last the int64
         `counts` tensor (n, C): C > K means that the clusters from K on were not written, C = -1 is the domain error and
         C = -2 the short `values` (nothing else was written by the reduction).  `values` must be ready when this is
-        called, as `points` must."""
+        called, as `points` must.
+
+        The sums of a minibatch of clouds in one call: `cluster_sums_batch`."""
+        return self._clusters("cluster_sums", radius, points, None, max_clusters, self._cluster_values(values), extrema)
+
+    def cluster_sums_batch(self, values, radius: float | None = None, *, points, batch, extrema: bool = False,
+                           max_clusters: int | None = None):
+        """`cluster_sums` of B disjoint clouds in one call: the clusters are `cluster_tensors_batch`'s, the rows of `values`
+        are global, and the reduction is `cluster_sums`' own, which reads the batched label as any other
+        (sc_pairs_label_batch_device, then sc_pairs_cluster_sums_device).
+        ``(labels, sizes, roots, sums[, mins, maxs], cluster_ptr)``: `cluster_ptr` comes after the tables and is always
+        whole, `counts` stays last with `max_clusters`.  Bit for bit `cluster_sums` cloud by cloud
+        (tests/batch_readers_spec.py)."""
+        return self._clusters("cluster_sums", radius, points, batch, max_clusters, self._cluster_values(values), extrema,
+                              batched=True)
+
+    @staticmethod
+    def _cluster_values(values):
+        """`values` of `cluster_sums` as the kernel takes it: contiguous float64 (n, F).  ValueError for anything else."""
         import torch
         if not getattr(values, "is_cuda", False) or values.dtype != torch.float64 or values.dim() not in (1, 2):
             raise ValueError("values must be a CUDA float64 tensor of shape (n, F) or (n,)")
@@ -245,20 +301,7 @@ class _Neighbourhood:
         width = int(values.shape[1])
         if not 1 <= width <= N.CLUSTER_SUMS_MAX_CHANNELS:
             raise ValueError(f"values must have 1 .. {N.CLUSTER_SUMS_MAX_CHANNELS} columns")
-        sync = max_clusters is None
-        if not sync and int(max_clusters) < 0:
-            raise ValueError("max_clusters must not be negative")
-        call = _Search(self, "cluster_sums", radius, points=points, sync=sync,
-                       short=f"values has {values.shape[0]} rows, fewer than there are points")
-        room = call.rows if sync else int(max_clusters)
-        labels = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
-        sizes = torch.empty(room, dtype=torch.int64, device=call.dev)
-        roots = torch.empty(room, dtype=torch.int64, device=call.dev)
-        tables = tuple(torch.empty((room, width), dtype=torch.float64, device=call.dev) for _ in range(3 if extrema else 1))
-        call.count()  # (one `counts` for all three: (n, E) of the count, then (n, C) twice)
-        call.eng.pairs_label(labels, sizes, roots, counts=call.counts)
-        call.eng.pairs_cluster_sums(values, *tables, counts=call.counts)
-        return call.end(rows=(labels,), items=(sizes, roots, *tables), held=(values,))
+        return values
 
     def cluster_observables(self, radius: float | None = None, *, max_clusters: int | None = None):
         """The probe's observables per droplet: ``(labels, roots, table)``, `table` float64 (C, 14) with the columns
@@ -426,7 +469,26 @@ class _Neighbourhood:
         rows from the row count on are uninitialised, status -1 is the domain error (nothing else was written).  The
         tensors are written on the library's stream, and the library's stream does not wait for torch's: read them
         after `synchronize()`, and have `points` and `queries` ready before the call -- or run the crate on torch's
-        stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        stream, `engine.set_stream`, and everything torch enqueues afterwards sees them.
+
+        The histograms of a minibatch of clouds in one call: `distance_histogram_batch`."""
+        return self._histogram(edges, points, queries, None, None, per_row, totals, sync)
+
+    def distance_histogram_batch(self, edges, *, points, batch, queries=None, query_batch=None, per_row: bool = False,
+                                 totals: bool = True, sync: bool = True):
+        """`distance_histogram` of B disjoint clouds in one call (sc_pairs_hist_batch_device): `batch` cuts `points` and,
+        with `queries`, `query_batch` cuts them, as in `neighbor_tensors` -- a row counts the partners of its own cloud
+        only.  ``([table, ]total)``: `table` as before, one row per point or query, and `total` int64 (B, bins), row b the
+        column sums over the rows of cloud b -- g(r) per frame through `sand_crate_amd.pairs.radial_distribution` with
+        the clouds' sizes.  Bit for bit `distance_histogram` cloud by cloud, the tables concatenated and the totals
+        stacked (tests/batch_readers_spec.py).  `sync` as in `distance_histogram`; offsets that are not in order raise
+        ValueError at the synchronisation (status -3 with `sync=False`).  (A method of its own and not `batch=` of
+        `distance_histogram`: `total` has another shape.)"""
+        if batch is None:
+            raise ValueError("distance_histogram: batch must be the clouds' offsets")
+        return self._histogram(edges, points, queries, batch, query_batch, per_row, totals, sync)
+
+    def _histogram(self, edges, points, queries, batch, query_batch, per_row, totals, sync):
         import torch
         if not per_row and not totals:
             raise ValueError("neither per_row nor totals: nothing to return")
@@ -434,15 +496,22 @@ class _Neighbourhood:
         bins = len(N.hist_squared_edges(e)) - 1
         if not e[-1] > 0:  # (never: the edges ascend from 0 or more)
             raise ValueError("the last edge must be positive")
-        call = _Search(self, "distance_histogram", e[-1], points=points, queries=queries, sync=sync)
+        call = _Search(self, "distance_histogram", e[-1], points=points, queries=queries, batch=batch, query_batch=query_batch,
+                       sync=sync)
+        if call.clouds * bins > N.HIST_BATCH_MAX_CELLS:
+            raise ValueError(f"distance_histogram: {call.clouds} clouds x {bins} bins, at most {N.HIST_BATCH_MAX_CELLS} totals")
         table = torch.empty((call.rows, bins), dtype=torch.int32, device=call.dev) if per_row else None
-        total = torch.empty(bins, dtype=torch.int64, device=call.dev) if totals else None
+        shape = bins if batch is None else (call.clouds, bins)
+        total = torch.empty(shape, dtype=torch.int64, device=call.dev) if totals else None
         call.count()
-        call.eng.pairs_hist(table, total, edges=e, queries=queries, counts=call.counts)
-        return call.end(rows=(table,), whole=(total,))
+        if batch is None:
+            call.eng.pairs_hist(table, total, edges=e, queries=queries, counts=call.counts)
+        else:
+            call.eng.pairs_hist_batch(table, total, edges=e, queries=queries, query_batch=query_batch, counts=call.counts)
+        return call.end(rows=(table,), whole=(total,), held=() if query_batch is None else (query_batch,))
 
     def ray_tensors(self, origins, directions, max_t: float, *, disc_radius: float | None = None, walls=True,
-                    particles: bool = True, points=None, sync: bool = True):
+                    particles: bool = True, points=None, sync: bool = True, batch=None, ray_batch=None):
         """What a sensor sees along a line: for every ray the first thing it meets among the particles -- discs of radius
         `disc_radius` (default: the crate's particle radius, ``diameter / 2``) -- and the walls, as torch CUDA tensors on
         the crate's device, walked on the GPU through the pair search's grid (sc_pairs_count_device at the radius
@@ -469,16 +538,28 @@ class _Neighbourhood:
         `counts` tensor (rays, status) last: status -1 is the domain error, -4 the cap (nothing else was written).  The
         tensors are written on the library's stream, and the library's stream does not wait for torch's: read them after
         `synchronize()`, and have `origins`, `directions` and `points` ready before the call -- or run the crate on
-        torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them."""
+        torch's stream, `engine.set_stream`, and everything torch enqueues afterwards sees them.
+
+        `batch` and `ray_batch`, both int64 CUDA tensors of B + 1 ascending offsets, come together and make the call B
+        scenes at once (sc_pairs_rays_batch_device): `batch` cuts `points` into clouds as in `pair_tensors`, `ray_batch`
+        cuts the rays, and rays ``ray_batch[b]:ray_batch[b + 1]`` meet the particles of cloud b only -- a sensor fan per
+        recorded frame.  The walls are shared by all clouds, ``hit`` is the global row of `points`, and the result is,
+        bit for bit, the per-cloud results concatenated (tests/batch_readers_spec.py).  Offsets that are not in order
+        raise ValueError at the synchronisation (status -3 with `sync=False`)."""
         import torch
         rho, max_t, segments, far = self._ray_arguments(origins, directions, max_t, disc_radius, walls)
-        call = _Search(self, "ray_tensors", 2 * rho, points=points, queries=origins, sync=sync, far=far)
+        call = _Search(self, "ray_tensors", 2 * rho, points=points, queries=origins, batch=batch, query_batch=ray_batch,
+                       sync=sync, far=far, second="ray_batch")
         t = torch.empty(call.rows, dtype=torch.float64, device=call.dev)
         hit = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
         call.count()
-        call.eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho if particles else 0.0, max_t=max_t,
-                            segments=segments, counts=call.counts)
-        return call.end(rows=(t, hit), held=(origins, directions))
+        common = dict(origins=origins, directions=directions, disc_radius=rho if particles else 0.0, max_t=max_t,
+                      segments=segments, counts=call.counts)
+        if batch is None:
+            call.eng.pairs_rays(t, hit, **common)
+        else:
+            call.eng.pairs_rays_batch(t, hit, ray_batch=ray_batch, **common)
+        return call.end(rows=(t, hit), held=(origins, directions, ray_batch))
 
     def _ray_arguments(self, origins, directions, max_t, disc_radius, walls):
         """The arguments `ray_tensors` and `ray_paths` share, checked: -> (rho, max_t, segments, the sentence of status
@@ -509,7 +590,7 @@ class _Neighbourhood:
         return rho, max_t, segments, far
 
     def ray_paths(self, origins, directions, max_t: float, bounces: int = 1, *, disc_radius: float | None = None, walls=True,
-                  particles: bool = True, points=None, sync: bool = True):
+                  particles: bool = True, points=None, sync: bool = True, batch=None, ray_batch=None):
         """Where a signal goes: `ray_tensors` followed through `bounces` specular reflections, 0 .. 15, in one launch
         (sc_pairs_count_device at the radius ``2 * disc_radius``, then sc_pairs_ray_paths_device): the named tuple
         ``RayPaths(t, hit, points, normals, end)`` -- float64 (R, L), int64 (R, L), float64 (R, L, 2), float64 (R, L, 2)
@@ -533,14 +614,16 @@ class _Neighbourhood:
         `sync=True` synchronises once at the end and raises `ray_tensors`' ValueErrors for leg 0, the caller's input: a
         coordinate outside the domain, a first leg beyond the cap.  `sync=False` synchronises nothing and returns
         ``(t, hit, points, normals, end, counts)``, the int64 `counts` tensor (rays, status) last, with the stream rules of
-        `ray_tensors`."""
+        `ray_tensors`.  `batch` and `ray_batch` as in `ray_tensors` (sc_pairs_ray_paths_batch_device): every leg of a
+        path stays among the particles of its ray's cloud."""
         import torch
         from .pairs import RayPaths
         bounces = int(bounces)
         if not 0 <= bounces <= N.RAY_MAX_BOUNCES:
             raise ValueError(f"bounces must be 0 .. {N.RAY_MAX_BOUNCES}")
         rho, max_t, segments, far = self._ray_arguments(origins, directions, max_t, disc_radius, walls)
-        call = _Search(self, "ray_paths", 2 * rho, points=points, queries=origins, sync=sync, far=far)
+        call = _Search(self, "ray_paths", 2 * rho, points=points, queries=origins, batch=batch, query_batch=ray_batch,
+                       sync=sync, far=far, second="ray_batch")
         legs = bounces + 1
         t = torch.empty((call.rows, legs), dtype=torch.float64, device=call.dev)
         hit = torch.empty((call.rows, legs), dtype=torch.int64, device=call.dev)
@@ -548,7 +631,11 @@ class _Neighbourhood:
         normals = torch.empty((call.rows, legs, 2), dtype=torch.float64, device=call.dev)
         end = torch.empty(call.rows, dtype=torch.int64, device=call.dev)
         call.count()
-        call.eng.pairs_ray_paths(t, hit, at, normals, end, origins=origins, directions=directions, bounces=bounces,
-                                 disc_radius=rho if particles else 0.0, max_t=max_t, segments=segments, counts=call.counts)
-        out = call.end(rows=(t, hit, at, normals, end), held=(origins, directions))
+        common = dict(origins=origins, directions=directions, bounces=bounces, disc_radius=rho if particles else 0.0,
+                      max_t=max_t, segments=segments, counts=call.counts)
+        if batch is None:
+            call.eng.pairs_ray_paths(t, hit, at, normals, end, **common)
+        else:
+            call.eng.pairs_ray_paths_batch(t, hit, at, normals, end, ray_batch=ray_batch, **common)
+        out = call.end(rows=(t, hit, at, normals, end), held=(origins, directions, ray_batch))
         return RayPaths(*out) if sync else out

@@ -9,8 +9,8 @@ import collections
 
 
 def batch_ptr(lengths, device=None):
-    """The `batch=` offsets of `Crate.pair_tensors`, `neighbor_tensors`, `field_tensors` and `field_function` from the
-    clouds' sizes: int64 (B + 1,), ``ptr[0] = 0`` and ``ptr[b + 1] = ptr[b] + lengths[b]`` -- the `ptr` of a graph
+    """The `batch=` offsets of `Crate.pair_tensors`, `neighbor_tensors`, `field_tensors`, `field_function` and the other
+    batched neighbourhood calls from the clouds' sizes: int64 (B + 1,), ``ptr[0] = 0`` and ``ptr[b + 1] = ptr[b] + lengths[b]`` -- the `ptr` of a graph
     library's batch.  `lengths` is a sequence or an int64 tensor of B >= 1 sizes, none negative."""
     import torch
     sizes = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).cpu()
@@ -131,15 +131,31 @@ def radial_distribution(total, edges, n, area):
     torch tensor: ``g[b] = total[b] / (n * (n / area) * pi * (edges[b + 1]**2 - edges[b]**2))`` -- the partners counted
     in the shell over the partners an ideal gas of the same density, n particles on `area`, would have there.  `total`
     counts ORDERED pairs, each unordered pair twice, as the self form of the histogram does: every one of the n
-    particles looks around.  Edge effects are not corrected: particles near the boundary of `area` see fewer partners."""
+    particles looks around.  Edge effects are not corrected: particles near the boundary of `area` see fewer partners.
+
+    Per cloud: with the (B, bins) `total` of `Crate.distance_histogram_batch`, `n` is the clouds' sizes -- a sequence or
+    tensor of B numbers, ``batch[1:] - batch[:-1]`` -- and the result is (B, bins), row b the g(r) of cloud b by the same
+    formula (an empty cloud's row is NaN: 0 / 0)."""
     import math
 
     import torch
     e = torch.as_tensor(edges, dtype=torch.float64, device=total.device)
-    if e.dim() != 1 or e.shape[0] != total.shape[0] + 1:
-        raise ValueError("edges must have one entry more than total")
+    if e.dim() != 1 or e.shape[0] != total.shape[-1] + 1:
+        raise ValueError("edges must have one entry more than total has bins")
     shell = math.pi * (e[1:] ** 2 - e[:-1] ** 2)
-    return total.to(torch.float64) / (float(n) * (float(n) / float(area)) * shell)
+    if total.dim() == 1:
+        return total.to(torch.float64) / (float(n) * (float(n) / float(area)) * shell)
+    sizes = torch.as_tensor(n, dtype=torch.float64, device=total.device).reshape(-1)
+    if total.dim() != 2 or sizes.shape[0] != total.shape[0]:
+        raise ValueError("a (B, bins) total needs the B sizes of its clouds")
+    return total.to(torch.float64) / ((sizes * (sizes / float(area)))[:, None] * shell[None, :])
+
+
+def cluster_cloud(cluster_ptr, clusters=None):
+    """The cloud of every cluster of `Crate.cluster_tensors_batch` and `cluster_sums_batch`: int64 (C,), cluster c
+    lies in cloud b iff ``cluster_ptr[b] <= c < cluster_ptr[b + 1]`` -- `batch_index` over the clusters.  `clusters`
+    defaults to ``cluster_ptr[-1]`` (which then synchronises to read it)."""
+    return batch_index(cluster_ptr, clusters)
 
 
 def grid_queries(x0, x1, y0, y1, nx, ny, device=None):
