@@ -33,58 +33,11 @@ microseconds.
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+from timing_support import alternate, bench_crate, bits_equal, device_times, median, record, stats, use_library, viewer_crate
 
 BINS, FAN, BOUNCES = 16, 64, 3
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
-
-
-def bits_equal(a, b):
-    import torch
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.dtype == torch.float64:
-        a, b = a.contiguous().view(torch.int64), b.contiguous().view(torch.int64)
-    return torch.equal(a, b)
-
-
-def record(crate, clouds, ticks):
-    """-> the frames, float64 (n_b, 2) CUDA tensors: the state after `ticks` ticks and after each of the next ones."""
-    for _ in range(ticks):
-        crate.physics_tick()
-    frames = []
-    for _ in range(clouds):
-        frames.append(crate.state_tensors(pressure=False)[0].clone())
-        crate.physics_tick()
-    crate.synchronize()
-    return frames
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def joined(name, parts, ptr):
@@ -109,9 +62,9 @@ def joined(name, parts, ptr):
     return tuple(out)
 
 
-def batch_mode(args, sc, pairs, torch):
+def batch_mode(args, pairs, torch):
     import numpy as np
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
+    crate = viewer_crate(0)
     frames = record(crate, args.clouds, args.ticks)
     radius = crate.diameter
     walls = crate.segments
@@ -148,23 +101,16 @@ def batch_mode(args, sc, pairs, torch):
         got, want = batched(), joined(name, loop(), ptr)
         if len(got) != len(want) or not all(bits_equal(g, w) for g, w in zip(got, want)):
             raise SystemExit(f"{name}: the batched call differs from the loop")
-        times = alternate({"loop": loop, "batched": batched}, args.reps)
-        med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+        times = alternate({"loop": loop, "batched": batched}, args.reps, WARMUP)
+        med = {key: median(t) for key, t in times.items()}
         print(json.dumps({**base, "case": name, **stats(times["batched"], "batched_wall_"), **stats(times["loop"], "loop_wall_"),
                           "single_call_wall_us": round(med["loop"] / args.clouds, 2),
                           "batched_over_loop": round(med["batched"] / med["loop"], 4),
                           "batched_over_single": round(med["batched"] * args.clouds / med["loop"], 2)}), flush=True)
 
 
-def unbatched_mode(args, sc, pairs, torch):
-    import bench
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+def unbatched_mode(args, pairs, torch):
+    crate = bench_crate(args.big, 3)
     eng = crate.engine
     dev = torch.device("cuda", eng.device)
     points = crate.state_tensors(pressure=False)[0].contiguous()
@@ -185,32 +131,19 @@ def unbatched_mode(args, sc, pairs, torch):
     path = (f64(rays, legs), i64(rays, legs), f64(rays, legs, 2), f64(rays, legs, 2), i64(rays))
     edges = pairs.shell_edges(radius, BINS)
     ray_args = dict(origins=origins, directions=down, disc_radius=radius / 2, max_t=2.0, segments=walls, counts=other)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
     torch.cuda.synchronize()
-    calls = (("count", lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts)),
-             ("label", lambda: eng.pairs_label(labels, sizes, roots, counts=other)),
-             ("hist", lambda: eng.pairs_hist(table, total, edges=edges, counts=other)),
-             ("rays", lambda: eng.pairs_rays(t, hit, **ray_args)),
-             ("ray_paths", lambda: eng.pairs_ray_paths(*path, bounces=BOUNCES, **ray_args)))
-    times = {name: [] for name, _ in calls}
-    for rep in range(args.reps + 3):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(calls) + 1)]
-        for mark, (_, call) in zip(ev, calls):
-            mark.record(stream)
-            call()
-        ev[-1].record(stream)
-        ev[-1].synchronize()
-        if rep >= 3:
-            for at, (name, _) in enumerate(calls):
-                times[name].append(1000.0 * ev[at].elapsed_time(ev[at + 1]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts),
+        "label": lambda: eng.pairs_label(labels, sizes, roots, counts=other),
+        "hist": lambda: eng.pairs_hist(table, total, edges=edges, counts=other),
+        "rays": lambda: eng.pairs_rays(t, hit, **ray_args),
+        "ray_paths": lambda: eng.pairs_ray_paths(*path, bounces=BOUNCES, **ray_args)}, args.reps, WARMUP)
     if other.tolist() != [rays, 0]:
         raise SystemExit(f"the last reader reports {other.tolist()}")
     out = {"case": "unbatched kernels", "lib": args.lib or "this build", "points": n, "rays": rays, "bins": BINS,
            "bounces": BOUNCES, "clusters": int(labels.max()) + 1, "pairs_in_bins": int(total.sum()), "hits": int((hit >= 0).sum())}
-    for name, _ in calls:
-        out.update(stats(times[name], f"{name}_device_"))
+    for name, series in times.items():
+        out.update(stats(series, f"{name}_device_"))
     print(json.dumps(out), flush=True)
 
 
@@ -225,18 +158,17 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
+    lib = use_library(args.lib)
+    if lib:
         import ctypes
-        other = ctypes.CDLL(str(_native.LIB_PATH))                                 # (an older build lacks the newest calls)
+        from sand_crate_amd import _native
+        other = ctypes.CDLL(str(lib))                                              # (an older build lacks the newest calls)
         for name in [name for name in _native.SIGNATURES if not hasattr(other, name)]:
             del _native.SIGNATURES[name]
-    import sand_crate_amd as sc
     from sand_crate_amd import pairs
     if args.reps is None:
         args.reps = 15 if args.unbatched else 20
-    (unbatched_mode if args.unbatched else batch_mode)(args, sc, pairs, torch)
+    (unbatched_mode if args.unbatched else batch_mode)(args, pairs, torch)
 
 
 if __name__ == "__main__":

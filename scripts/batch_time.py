@@ -23,58 +23,11 @@ case, microseconds.
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+from timing_support import alternate, bits_equal, device_times, median, record, stats, use_library, viewer_crate
 
 K = 16
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
-
-
-def bits_equal(a, b):
-    import torch
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    if a.dtype == torch.float64:
-        a, b = a.contiguous().view(torch.int64), b.contiguous().view(torch.int64)
-    return torch.equal(a, b)
-
-
-def record(crate, clouds, ticks):
-    """-> the frames, float64 (n_b, 2) CUDA tensors: the state after `ticks` ticks and after each of the next ones."""
-    for _ in range(ticks):
-        crate.physics_tick()
-    frames = []
-    for _ in range(clouds):
-        frames.append(crate.state_tensors(pressure=False)[0].clone())
-        crate.physics_tick()
-    crate.synchronize()
-    return frames
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def functions(crate, radius):
@@ -129,28 +82,14 @@ def kernels(crate, radius, points, values, ptr, reps):
     table_d2 = torch.empty((n, K), dtype=torch.float64, device=dev)
     sums = torch.empty((n, int(values.shape[1])), dtype=torch.float64, device=dev)
     wsum = torch.empty(n, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    calls = (lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, batch=ptr),
-             lambda: eng.pairs_fill(partners, d2),
-             lambda: eng.pairs_nearest(table, table_d2, k=K, counts=other),
-             lambda: eng.pairs_sum(values, sums, wsum, counts=other),
-             lambda: None)
-    names = ("count", "fill", "table", "sum")
-    times = {name: [] for name in names}
-    for rep in range(reps + 3):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in calls]
-        for mark, call in zip(ev, calls):
-            mark.record(stream)
-            call()
-        ev[-1].synchronize()
-        if rep >= 3:
-            for k, name in enumerate(names):
-                times[name].append(1000.0 * ev[k].elapsed_time(ev[k + 1]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, batch=ptr),
+        "fill": lambda: eng.pairs_fill(partners, d2),
+        "table": lambda: eng.pairs_nearest(table, table_d2, k=K, counts=other),
+        "sum": lambda: eng.pairs_sum(values, sums, wsum, counts=other)}, reps, WARMUP)
     out = {"points": n, "pairs": total}
-    for name in names:
-        out.update(stats(times[name], f"{name}_device_"))
+    for name, series in times.items():
+        out.update(stats(series, f"{name}_device_"))
     return out
 
 
@@ -163,13 +102,10 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import sand_crate_amd as sc
+    use_library(args.lib)
     from sand_crate_amd import pairs
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
+    crate = viewer_crate(0)
     frames = record(crate, args.clouds, args.ticks)
     radius = crate.diameter
     points = torch.cat(frames)
@@ -187,8 +123,8 @@ def main():
         got, want = batched(), joined(name, loop(), ptr)
         if len(got) != len(want) or not all(bits_equal(g, w) for g, w in zip(got, want)):
             raise SystemExit(f"{name}: the batched call differs from the loop")
-        times = alternate({"loop": loop, "batched": batched}, args.reps)
-        med = {key: sorted(t)[len(t) // 2] for key, t in times.items()}
+        times = alternate({"loop": loop, "batched": batched}, args.reps, WARMUP)
+        med = {key: median(t) for key, t in times.items()}
         print(json.dumps({**base, "case": name, **stats(times["batched"], "batched_wall_"), **stats(times["loop"], "loop_wall_"),
                           "single_call_wall_us": round(med["loop"] / args.clouds, 2),
                           "batched_over_loop": round(med["batched"] / med["loop"], 4),

@@ -29,38 +29,12 @@ median and min over the repetitions, in microseconds.
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, viewer_crate
 
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=2):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 2                            # rounds before anything is recorded, wall and device alike
 
 
 def reduce_launches(bound):
@@ -152,31 +126,10 @@ def reduce_device(eng, points, radius, rows, values, reps):
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     labels, sizes, roots = (torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(3))
     tables = [torch.empty((rows, values.shape[1]), dtype=torch.float64, device=dev) for _ in range(3)]
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-
-    def once(events=None):
-        marks = events or [None] * 4
-        for mark, call in zip(marks, (
-                lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True),
-                lambda: eng.pairs_label(labels, sizes, roots, counts=counts),
-                lambda: eng.pairs_cluster_sums(values, *tables, counts=counts), None)):
-            if mark is not None:
-                mark.record(stream)
-            if call is not None:
-                call()
-
-    for _ in range(2):
-        once()
-    torch.cuda.synchronize(dev)
-    times = {"count": [], "label": [], "reduce": []}
-    for _ in range(reps):
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        once(events)
-        events[3].synchronize()
-        for k, name in enumerate(times):
-            times[name].append(1000.0 * events[k].elapsed_time(events[k + 1]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True),
+        "label": lambda: eng.pairs_label(labels, sizes, roots, counts=counts),
+        "reduce": lambda: eng.pairs_cluster_sums(values, *tables, counts=counts)}, reps, WARMUP)
     n, total = (int(v) for v in counts.cpu())
     out = {"n": n, "C": total}
     for name, t in times.items():
@@ -202,11 +155,11 @@ def measure(crate, base, radius, points, values, rows, reps):
     if len(first) == 2:
         base["index_add_equals_segment_reduce"] = bool(torch.equal(*first.values()))
     sides["cluster_sums"] = lambda: crate.cluster_sums(values, radius, points=points, extrema=True)
-    times = alternate(sides, reps)
+    times = alternate(sides, reps, WARMUP)
     for name, t in times.items():
         print(json.dumps({**base, "case": name, **stats(t, "wall_")}), flush=True)
     print(json.dumps({**base, "case": "reduce", **reduce_device(crate.engine, points, radius, rows, values, reps)}), flush=True)
-    med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+    med = {name: median(t) for name, t in times.items()}
     print(json.dumps({**base, "case": "verdict", **{f"cluster_sums_over_{name}": round(med["cluster_sums"] / t, 4)
                                                   for name, t in med.items() if name != "cluster_sums"}}), flush=True)
     torch.cuda.synchronize()
@@ -247,26 +200,19 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
-    import sand_crate_amd as sc
 
     big_reps = max(5, args.reps // 3)
     if args.only != "points":
-        crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-        for _ in range(args.ticks):
-            crate.physics_tick()
-        crate.synchronize()
+        crate = viewer_crate(args.ticks)
         measure_state(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps)
         crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    if args.only != "points":
-        p, v = bench.synthetic_state(args.big)
-        crate.particles = p
-        crate.particle_velocities = v
-        crate.run(3)
-        crate.synchronize()
+    if args.only == "points":                                                       # (an empty crate: the points come through `points=`)
+        import bench
+        import sand_crate_amd as sc
+        crate = sc.Crate(bench.world_for(args.big)[0], noise="counter", noise_seed=1, capacity=args.big + 1024)
+    else:
+        crate = bench_crate(args.big, 3)
         measure_state(crate, {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}, big_reps)
     if args.only != "states":
         measure_points(crate, args.big, big_reps)

@@ -28,38 +28,12 @@ and min over the repetitions, in microseconds.
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, viewer_crate, with_wall
 
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def label_launches(bound):
@@ -76,29 +50,13 @@ def label_device(eng, points, radius, rows, reps):
     offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     labels, sizes, roots = (torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(3))
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    for _ in range(3):
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
-        eng.pairs_label(labels, sizes, roots, counts=counts)
-    torch.cuda.synchronize(dev)
-    count_t, label_t, wall = [], [], []
-    for _ in range(reps):
-        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        a.record(stream)
-        eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True)
-        b.record(stream)
-        t0 = time.perf_counter()
-        eng.pairs_label(labels, sizes, roots, counts=counts)
-        wall.append(1e6 * (time.perf_counter() - t0))
-        c.record(stream)
-        c.synchronize()
-        count_t.append(1000.0 * a.elapsed_time(b))
-        label_t.append(1000.0 * b.elapsed_time(c))
-    eng.use_own_stream()
+    wall = []
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts, half=True),
+        "label": with_wall(lambda: eng.pairs_label(labels, sizes, roots, counts=counts), wall)}, reps, WARMUP)
     n, total = (int(v) for v in counts.cpu())
-    out = {**stats(count_t, "count_device_"), **stats(label_t, "label_device_"), **stats(wall, "label_enqueue_wall_"),
-           "n": n, "C": total, **label_launches(n)}
+    out = {**stats(times["count"], "count_device_"), **stats(times["label"], "label_device_"),
+           **stats(wall[-reps:], "label_enqueue_wall_"), "n": n, "C": total, **label_launches(n)}
     return out, (labels[:n], sizes[:total], roots[:total])
 
 
@@ -124,12 +82,12 @@ def measure_state(crate, base, reps, small):
         raise SystemExit("cluster_tensors differs from the rule")
     base = {**base, "C": len(got[1]), "largest": int(got[1].max()) if len(got[1]) else 0}
     times = alternate({"download": eng.download, "pair_tensors": lambda: crate.pair_tensors(half=True),
-                       "cluster_tensors": crate.cluster_tensors}, reps)
+                       "cluster_tensors": crate.cluster_tensors}, reps, WARMUP)
     for name, t in times.items():
         print(json.dumps({**base, "case": name, **stats(t, "wall_")}), flush=True)
     dev, _ = label_device(eng, None, crate.diameter, eng.capacity, reps)
     print(json.dumps({**base, "case": "label", **dev}), flush=True)
-    med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+    med = {name: median(t) for name, t in times.items()}
     print(json.dumps({**base, "case": "verdict", "cluster_tensors_over_pair_tensors": round(med["cluster_tensors"] / med["pair_tensors"], 4),
                       "cluster_tensors_over_download": round(med["cluster_tensors"] / med["download"], 4)}), flush=True)
     torch.cuda.synchronize()
@@ -175,26 +133,19 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
-    import sand_crate_amd as sc
 
     big_reps = max(5, args.reps // 3)
     if args.only != "points":
-        crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-        for _ in range(args.ticks):
-            crate.physics_tick()
-        crate.synchronize()
+        crate = viewer_crate(args.ticks)
         measure_state(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, True)
         crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    if args.only != "points":
-        p, v = bench.synthetic_state(args.big)
-        crate.particles = p
-        crate.particle_velocities = v
-        crate.run(3)
-        crate.synchronize()
+    if args.only == "points":                                                       # (an empty crate: the points come through `points=`)
+        import bench
+        import sand_crate_amd as sc
+        crate = sc.Crate(bench.world_for(args.big)[0], noise="counter", noise_seed=1, capacity=args.big + 1024)
+    else:
+        crate = bench_crate(args.big, 3)
         measure_state(crate, {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}, big_reps, False)
     if args.only != "states":
         measure_points(crate, args.big, big_reps)

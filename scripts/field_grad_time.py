@@ -35,40 +35,15 @@ so the list route has no bits to compare -- and on the small state `field_functi
 """
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, use_library, viewer_crate
+
+WARMUP = 2                            # rounds before anything is recorded, wall and device alike
 
 POWER = 3
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=2):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
 
 
 def field_route(crate, values, points, radius, G, gw, with_points, queries=None):
@@ -125,38 +100,19 @@ def kernels(crate, points, radius, values, G, gw, reps, total, queries=None):
     grad = torch.empty((rows, 2), dtype=torch.float64, device=dev)
     partners = torch.empty(total, dtype=torch.int64, device=dev)
     d2 = torch.empty(total, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    calls = (lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts),
-             lambda: eng.pairs_sum(values, sums, wsum, power=POWER, queries=queries, counts=other),
-             lambda: eng.pairs_sum_grad(grad, G, values, gw, gw if queries is None else None, power=POWER, queries=queries,
-                                        counts=third),
-             lambda: eng.pairs_fill(partners, d2), lambda: None)
-
-    def once(events=None):
-        for mark, call in zip(events or [None] * len(calls), calls):
-            if mark is not None:
-                mark.record(stream)
-            call()
-
-    for _ in range(2):
-        once()
-    torch.cuda.synchronize(dev)
-    spans = [[] for _ in range(4)]
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in calls]
-        once(ev)
-        ev[-1].synchronize()
-        for k, span in enumerate(spans):
-            span.append(1000.0 * ev[k].elapsed_time(ev[k + 1]))
-    eng.use_own_stream()
+    spans = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=radius, offsets=offsets, counts=counts),
+        "sum": lambda: eng.pairs_sum(values, sums, wsum, power=POWER, queries=queries, counts=other),
+        "grad": lambda: eng.pairs_sum_grad(grad, G, values, gw, gw if queries is None else None, power=POWER, queries=queries,
+                                           counts=third),
+        "fill": lambda: eng.pairs_fill(partners, d2)}, reps, WARMUP)
     for name, c in (("sum", other), ("grad", third)):
         if int(c[1]) != 0:
             raise SystemExit(f"kernels: {name} status {int(c[1])}")
-    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
-    return {**stats(spans[0], "count_device_"), **stats(spans[1], "sum_device_"), **stats(spans[2], "grad_device_"),
-            **stats(spans[3], "fill_device_"), "rows": int(third[0]), "grad_bytes": 16 * rows, "list_bytes": 16 * total,
-            "grad_over_sum": round(med(spans[2]) / med(spans[1]), 3), "grad_over_fill": round(med(spans[2]) / med(spans[3]), 3)}
+    return {**stats(spans["count"], "count_device_"), **stats(spans["sum"], "sum_device_"), **stats(spans["grad"], "grad_device_"),
+            **stats(spans["fill"], "fill_device_"), "rows": int(third[0]), "grad_bytes": 16 * rows, "list_bytes": 16 * total,
+            "grad_over_sum": round(median(spans["grad"]) / median(spans["sum"]), 3),
+            "grad_over_fill": round(median(spans["grad"]) / median(spans["fill"]), 3)}
 
 
 def agree(got, want, what):
@@ -193,11 +149,12 @@ def measure(crate, base, reps, shapes, check_rule):
             del got
             part = []
             times = alternate({"list route": lambda: list_route(crate, values, particles, radius, G, gw, with_points, part),
-                               "field_function": lambda: field_route(crate, values, particles, radius, G, gw, with_points)}, reps)
+                               "field_function": lambda: field_route(crate, values, particles, radius, G, gw, with_points)},
+                              reps, WARMUP)
             print(json.dumps({**case, "wrt": wrt, "case": "list route", **stats(times["list route"], "wall_"),
                               **stats(part[-reps:], "pair_tensors_part_wall_")}), flush=True)
             print(json.dumps({**case, "wrt": wrt, "case": "field_function", **stats(times["field_function"], "wall_")}), flush=True)
-            med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+            med = {name: median(t) for name, t in times.items()}
             print(json.dumps({**case, "wrt": wrt, "case": "verdict",
                               "field_function_over_list_route": round(med["field_function"] / med["list route"], 4)}), flush=True)
             torch.cuda.empty_cache()
@@ -226,7 +183,8 @@ def measure_queries(crate, base, reps, name, queries):
     del diff, dist, t, w, want, got
     times = alternate({"field_tensors": lambda: (crate.field_tensors(velocities, radius, power=POWER, points=points, queries=queries,
                                                                      weight_sums=True), torch.cuda.synchronize()),
-                       "field_function": lambda: field_route(crate, velocities, points, radius, G, gw, False, queries)}, reps)
+                       "field_function": lambda: field_route(crate, velocities, points, radius, G, gw, False, queries)},
+                      reps, WARMUP)
     case = {**base, "channels": 2, "radius_in_diameters": 1.0, "queries": q, "wrt": "values+queries"}
     print(json.dumps({**case, "case": f"{name}: forward alone (field_tensors)", **stats(times["field_tensors"], "wall_")}), flush=True)
     print(json.dumps({**case, "case": f"{name}: field_function", **stats(times["field_function"], "wall_")}), flush=True)
@@ -246,28 +204,15 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import bench
-    import sand_crate_amd as sc
+    use_library(args.lib)
     from sand_crate_amd import pairs
 
     shapes = [(2, 1.0), (8, 1.0), (2, 2.0), (8, 2.0)]
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, shapes, True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     base = {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}
     big_reps = max(5, args.reps // 4)
     measure(crate, base, big_reps, shapes, False)

@@ -31,40 +31,15 @@ draws: an index says nothing about the place.  One JSON line per case: median an
 """
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, use_library, viewer_crate
+
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 POWER = 3
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
 
 
 def sums_from_list(offsets, partners, d2, values, radius):
@@ -95,37 +70,16 @@ def kernels(crate, radius, values, reps, total, queries=None):
     wsum = torch.empty(rows, dtype=torch.float64, device=dev)
     partners = torch.empty(total, dtype=torch.int64, device=dev)
     d2 = torch.empty(total, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-
-    def once(events=None):
-        marks = events or [None] * 4
-        for mark, call in zip(marks, (lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
-                                      lambda: eng.pairs_sum(values, sums, wsum, power=POWER, queries=queries, counts=other),
-                                      lambda: eng.pairs_fill(partners, d2), lambda: None)):
-            if mark is not None:
-                mark.record(stream)
-            call()
-
-    for _ in range(3):
-        once()
-    torch.cuda.synchronize(dev)
-    count_t, sum_t, fill_t = [], [], []
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        once(ev)
-        ev[3].synchronize()
-        count_t.append(1000.0 * ev[0].elapsed_time(ev[1]))
-        sum_t.append(1000.0 * ev[1].elapsed_time(ev[2]))
-        fill_t.append(1000.0 * ev[2].elapsed_time(ev[3]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
+        "sum": lambda: eng.pairs_sum(values, sums, wsum, power=POWER, queries=queries, counts=other),
+        "fill": lambda: eng.pairs_fill(partners, d2)}, reps, WARMUP)
     n_rows, status = (int(v) for v in other.cpu())
     if status != 0:
         raise SystemExit(f"kernels: status {status}")
-    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
-    return {**stats(count_t, "count_device_"), **stats(sum_t, "sum_device_"), **stats(fill_t, "fill_device_"),
+    return {**stats(times["count"], "count_device_"), **stats(times["sum"], "sum_device_"), **stats(times["fill"], "fill_device_"),
             "rows": n_rows, "sums_bytes": 8 * n_rows * (width + 1), "list_bytes": 16 * total,
-            "sum_over_fill": round(med(sum_t) / med(fill_t), 3)}
+            "sum_over_fill": round(median(times["sum"]) / median(times["fill"]), 3)}
 
 
 def close(got, want, scale):
@@ -170,12 +124,13 @@ def measure(crate, base, reps, shapes, check_rule):
             torch.cuda.synchronize()
 
         times = alternate({"list route": list_route,
-                           "field_tensors": lambda: crate.field_tensors(values, radius, power=POWER, weight_sums=True)}, reps)
+                           "field_tensors": lambda: crate.field_tensors(values, radius, power=POWER, weight_sums=True)},
+                          reps, WARMUP)
         print(json.dumps({**case, "case": "list route", **stats(times["list route"], "wall_"),
                           **stats(part[-reps:], "pair_tensors_part_wall_")}), flush=True)
         print(json.dumps({**case, "case": "field_tensors", **stats(times["field_tensors"], "wall_")}), flush=True)
         print(json.dumps({**case, "case": "kernels", **kernels(crate, radius, values, reps, total)}), flush=True)
-        med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+        med = {name: median(t) for name, t in times.items()}
         print(json.dumps({**case, "case": "verdict",
                           "field_tensors_over_list_route": round(med["field_tensors"] / med["list route"], 4)}), flush=True)
         del offsets, partners, d2
@@ -198,7 +153,7 @@ def measure_queries(crate, base, reps, name, queries):
         raise SystemExit(f"{name}: the sums differ from the brute force")
     del d, dist, t, w
     times = alternate({"field_tensors": lambda: crate.field_tensors(velocities, queries=queries, power=POWER,
-                                                                    weight_sums=True)}, reps)
+                                                                    weight_sums=True)}, reps, WARMUP)
     case = {**base, "channels": 2, "radius_in_diameters": 1.0, "queries": int(queries.shape[0]),
             "rows_with_partners": int((got[1] > 0).sum())}
     print(json.dumps({**case, "case": f"{name}: field_tensors", **stats(times["field_tensors"], "wall_")}), flush=True)
@@ -218,28 +173,15 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import bench
-    import sand_crate_amd as sc
+    use_library(args.lib)
     from sand_crate_amd import pairs
 
     shapes = [(2, 1.0), (8, 1.0), (2, 2.0), (8, 2.0)]
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, shapes, True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     base = {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}
     big_reps = max(5, args.reps // 3)
     measure(crate, base, big_reps, shapes, False)

@@ -2,8 +2,9 @@
 library that is in place then) is uploaded again before every measured tick, so variants that change the physics
 (ablations) are still timed on identical inputs.   python scripts/frozen_time.py <tag> [particles] [reps]"""
 import copy, os, sys
-sys.path.insert(0, ".")
 import numpy as np
+from timing_support import use_library
+use_library()  # $SAND_CRATE_LIB: a variant build (scripts/run_variants.sh), else the package's own library
 import bench, sand_crate_amd as sc
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 1048576

@@ -19,38 +19,21 @@ and min over the repetitions, in microseconds, and the size of a frame.
 import argparse
 import io
 import json
-import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
+from timing_support import device_times, median, stats, viewer_crate, with_wall
 
 
 def time_gpu(crate, fn, reps):
-    import torch
-    stream = torch.cuda.current_stream()
-    crate.engine.set_stream(stream.cuda_stream)
-    for _ in range(3):  # first-use costs: workspace growth, code object load
+    data, wall = None, []
+
+    def call():
+        nonlocal data
         data = fn()
-    torch.cuda.synchronize()
-    device, wall = [], []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        t0 = time.perf_counter()
-        data = fn()
-        wall.append(1e6 * (time.perf_counter() - t0))
-        b.record(stream)
-        b.synchronize()
-        device.append(1000.0 * a.elapsed_time(b))
-    crate.engine.use_own_stream()
-    return {**stats(device, "device_"), **stats(wall, "wall_"), "bytes": len(data)}
+
+    # 3 rounds of warm-up for the first-use costs: workspace growth, code object load
+    device = device_times(crate.engine, {"call": with_wall(call, wall)}, reps, 3)["call"]
+    return {**stats(device, "device_"), **stats(wall[-reps:], "wall_"), "bytes": len(data)}
 
 
 def time_host_gif(crate, side, frames, reps):
@@ -70,7 +53,7 @@ def time_host_gif(crate, side, frames, reps):
         buf = io.BytesIO()
         images[0].save(buf, format="GIF", append_images=images[1:], save_all=True, duration=10, loop=0)
         save.append(1e6 * (time.perf_counter() - t0) / frames)
-    median_render = sorted(render)[len(render) // 2]
+    median_render = median(render)
     both = [median_render + s for s in save]
     return {**stats(both, "wall_"), **stats(render, "render_wall_"), **stats(save, "pil_save_wall_"),
             "bytes": buf.tell() // frames}
@@ -84,13 +67,9 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import sand_crate_amd as sc
 
     side = 1000
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     base = {"scene": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count, "frame": f"{side}x{side}"}
     print(json.dumps({**base, "case": "render_gif", **time_gpu(crate, lambda: crate.render_gif(side, side), args.reps)}),
           flush=True)

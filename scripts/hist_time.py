@@ -31,40 +31,15 @@ per case: median and min over the repetitions, microseconds.
 """
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, use_library, viewer_crate
+
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 BINS = (16, 64)
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
 
 
 def counts_from_list(offsets, partners, d2, e2, per_row):
@@ -96,38 +71,18 @@ def kernels(crate, edges, per_row, reps, total_pairs, queries=None):
     wsum = torch.empty(rows, dtype=torch.float64, device=dev)
     partners = torch.empty(total_pairs, dtype=torch.int64, device=dev)
     d2 = torch.empty(total_pairs, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    calls = (lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
-             lambda: eng.pairs_hist(table, total, edges=edges, queries=queries, counts=other),
-             lambda: eng.pairs_sum(None, None, wsum, power=3, queries=queries, counts=third),
-             lambda: eng.pairs_fill(partners, d2), lambda: None)
-
-    def once(events=None):
-        for mark, call in zip(events or [None] * len(calls), calls):
-            if mark is not None:
-                mark.record(stream)
-            call()
-
-    for _ in range(3):
-        once()
-    torch.cuda.synchronize(dev)
-    times = [[] for _ in range(len(calls) - 1)]
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in calls]
-        once(ev)
-        ev[-1].synchronize()
-        for k, t in enumerate(times):
-            t.append(1000.0 * ev[k].elapsed_time(ev[k + 1]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
+        "hist": lambda: eng.pairs_hist(table, total, edges=edges, queries=queries, counts=other),
+        "wsum": lambda: eng.pairs_sum(None, None, wsum, power=3, queries=queries, counts=third),
+        "fill": lambda: eng.pairs_fill(partners, d2)}, reps, WARMUP)
     n_rows, status = (int(v) for v in other.cpu())
     if status != 0:
         raise SystemExit(f"kernels: status {status}")
-    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
-    return {**stats(times[0], "count_device_"), **stats(times[1], "hist_device_"), **stats(times[2], "wsum_device_"),
-            **stats(times[3], "fill_device_"), "rows": n_rows, "hist_bytes": 8 * bins + (4 * n_rows * bins if per_row else 0),
-            "list_bytes": 16 * total_pairs, "hist_over_count": round(med(times[1]) / med(times[0]), 3),
-            "hist_over_wsum": round(med(times[1]) / med(times[2]), 3)}
+    return {**stats(times["count"], "count_device_"), **stats(times["hist"], "hist_device_"), **stats(times["wsum"], "wsum_device_"),
+            **stats(times["fill"], "fill_device_"), "rows": n_rows, "hist_bytes": 8 * bins + (4 * n_rows * bins if per_row else 0),
+            "list_bytes": 16 * total_pairs, "hist_over_count": round(median(times["hist"]) / median(times["count"]), 3),
+            "hist_over_wsum": round(median(times["hist"]) / median(times["wsum"]), 3)}
 
 
 def measure(crate, base, reps, check_rule):
@@ -165,12 +120,13 @@ def measure(crate, base, reps, check_rule):
                     torch.cuda.synchronize()
 
                 times = alternate({"list route": list_route,
-                                   "distance_histogram": lambda: crate.distance_histogram(edges, per_row=per_row)}, reps)
+                                   "distance_histogram": lambda: crate.distance_histogram(edges, per_row=per_row)},
+                                  reps, WARMUP)
                 print(json.dumps({**case, "case": "list route", **stats(times["list route"], "wall_"),
                                   **stats(part[-reps:], "pair_tensors_part_wall_")}), flush=True)
                 print(json.dumps({**case, "case": "distance_histogram", **stats(times["distance_histogram"], "wall_")}), flush=True)
                 print(json.dumps({**case, "case": "kernels", **kernels(crate, edges, per_row, reps, total_pairs)}), flush=True)
-                med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+                med = {name: median(t) for name, t in times.items()}
                 print(json.dumps({**case, "case": "verdict", "distance_histogram_over_list_route":
                                   round(med["distance_histogram"] / med["list route"], 4)}), flush=True)
         del offsets, partners, d2
@@ -196,7 +152,8 @@ def measure_queries(crate, base, reps, queries):
         if not (torch.equal(table[:64], want) and torch.equal(total, table.sum(0))):
             raise SystemExit("probes: the table differs from the brute force")
         del dx, dy, dist, idx, inside
-        times = alternate({"distance_histogram": lambda: crate.distance_histogram(edges, queries=queries, per_row=True)}, reps)
+        times = alternate({"distance_histogram": lambda: crate.distance_histogram(edges, queries=queries, per_row=True)},
+                          reps, WARMUP)
         case = {**base, "bins": bins, "radius_in_diameters": 1.0, "table": True, "queries": int(queries.shape[0]),
                 "partners": int(total.sum())}
         print(json.dumps({**case, "case": "probes: distance_histogram", **stats(times["distance_histogram"], "wall_")}), flush=True)
@@ -215,26 +172,13 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import bench
-    import sand_crate_amd as sc
+    use_library(args.lib)
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     base = {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}
     big_reps = max(5, args.reps // 3)
     measure(crate, base, big_reps, False)

@@ -13,36 +13,21 @@ min over the repetitions, in microseconds, and the file's size.
 import argparse
 import io
 import json
-import sys
 import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-
-def stats(times):
-    times = sorted(times)
-    return {"median_us": round(times[len(times) // 2], 2), "min_us": round(times[0], 2)}
+from timing_support import bench_crate, device_times, stats, viewer_crate
 
 
 def time_gpu(crate, fn, reps):
-    import torch
-    stream = torch.cuda.current_stream()
-    crate.engine.set_stream(stream.cuda_stream)
-    for _ in range(3):  # first-use costs: workspace growth, code object load
+    data = None
+
+    def call():
+        nonlocal data
         data = fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        data = fn()
-        b.record(stream)
-        b.synchronize()
-        times.append(1000.0 * a.elapsed_time(b))
-    crate.engine.use_own_stream()
-    return {**stats(times), "bytes": len(data)}
+
+    # 3 rounds of warm-up for the first-use costs: workspace growth, code object load
+    times = device_times(crate.engine, {"call": call}, reps, 3)
+    return {**stats(times["call"]), "bytes": len(data)}
 
 
 def time_pil(img, reps):
@@ -82,22 +67,12 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
-    import sand_crate_amd as sc
 
-    n = 1048576
-    wc, _ = bench.world_for(n)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles, crate.particle_velocities = bench.synthetic_state(n)
-    crate.run(5)
-    crate.synchronize()
+    crate = bench_crate(1048576, 5)
     cases(crate, "M2", (1000, 4096), args.reps, True)
     del crate
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(200):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(200)
     cases(crate, "wave_machine", (1000,), args.reps, False)
 
 

@@ -1,7 +1,8 @@
 """The contract workload beyond the uniform regime: per-kernel times over tick windows.  python scripts/late_time.py [particles]"""
 import copy, sys, time
-sys.path.insert(0, ".")
-import numpy as np, bench, sand_crate_amd as sc
+from timing_support import use_library
+use_library()  # $SAND_CRATE_LIB: a variant build (scripts/run_variants.sh), else the package's own library
+import bench, sand_crate_amd as sc
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
 wc, d = bench.world_for(n); p, v = bench.synthetic_state(n)
 s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024); s.particles = p; s.particle_velocities = v

@@ -23,38 +23,13 @@ with the NumPy rule (tests/nearest_spec.py).  One JSON line per case: median and
 """
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, use_library, viewer_crate
 
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def table_from_list(offsets, partners, d2, k):
@@ -88,35 +63,14 @@ def kernels(crate, radius, k, reps, total, queries=None):
     table_d2 = torch.empty((rows, k), dtype=torch.float64, device=dev)
     partners = torch.empty(total, dtype=torch.int64, device=dev)
     d2 = torch.empty(total, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-
-    def once(events=None):
-        marks = events or [None] * 4
-        for mark, call in zip(marks, (lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
-                                      lambda: eng.pairs_nearest(neighbors, table_d2, k=k, queries=queries, counts=other),
-                                      lambda: eng.pairs_fill(partners, d2), lambda: None)):
-            if mark is not None:
-                mark.record(stream)
-            call()
-
-    for _ in range(3):
-        once()
-    torch.cuda.synchronize(dev)
-    count_t, table_t, fill_t = [], [], []
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        once(ev)
-        ev[3].synchronize()
-        count_t.append(1000.0 * ev[0].elapsed_time(ev[1]))
-        table_t.append(1000.0 * ev[1].elapsed_time(ev[2]))
-        fill_t.append(1000.0 * ev[2].elapsed_time(ev[3]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts),
+        "table": lambda: eng.pairs_nearest(neighbors, table_d2, k=k, queries=queries, counts=other),
+        "fill": lambda: eng.pairs_fill(partners, d2)}, reps, WARMUP)
     n_rows, cut = (int(v) for v in other.cpu())
-    med = lambda t: sorted(t)[len(t) // 2]  # noqa: E731
-    return {**stats(count_t, "count_device_"), **stats(table_t, "table_device_"), **stats(fill_t, "fill_device_"),
+    return {**stats(times["count"], "count_device_"), **stats(times["table"], "table_device_"), **stats(times["fill"], "fill_device_"),
             "rows": n_rows, "rows_cut": cut, "table_bytes": 16 * n_rows * k, "list_bytes": 16 * total,
-            "table_over_fill": round(med(table_t) / med(fill_t), 3)}
+            "table_over_fill": round(median(times["table"]) / median(times["fill"]), 3)}
 
 
 def measure(crate, base, reps, shapes, check_rule):
@@ -146,12 +100,13 @@ def measure(crate, base, reps, shapes, check_rule):
             torch.cuda.synchronize()
 
         times = alternate({"list route": list_route,
-                           "neighbor_tensors": lambda: crate.neighbor_tensors(k, radius, squared_distances=True)}, reps)
+                           "neighbor_tensors": lambda: crate.neighbor_tensors(k, radius, squared_distances=True)},
+                          reps, WARMUP)
         print(json.dumps({**case, "case": "list route", **stats(times["list route"], "wall_"),
                           **stats(part[-reps:], "pair_tensors_part_wall_")}), flush=True)
         print(json.dumps({**case, "case": "neighbor_tensors", **stats(times["neighbor_tensors"], "wall_")}), flush=True)
         print(json.dumps({**case, "case": "kernels", **kernels(crate, radius, k, reps, total)}), flush=True)
-        med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+        med = {name: median(t) for name, t in times.items()}
         print(json.dumps({**case, "case": "verdict",
                           "neighbor_tensors_over_list_route": round(med["neighbor_tensors"] / med["list route"], 4)}), flush=True)
         del offsets, partners, d2
@@ -174,7 +129,8 @@ def measure_probes(crate, base, reps, probes):
     if not torch.equal((dist <= radius * radius).sum(dim=1), got[2][:64]):
         raise SystemExit("probes: the partner counts differ from the brute force")
     del d, dist
-    times = alternate({"neighbor_tensors": lambda: crate.neighbor_tensors(k, queries=queries, squared_distances=True)}, reps)
+    times = alternate({"neighbor_tensors": lambda: crate.neighbor_tensors(k, queries=queries, squared_distances=True)},
+                      reps, WARMUP)
     case = {**base, "k": k, "radius_in_diameters": 1.0, "probes": probes, "mean_partners": round(float(got[2].double().mean()), 3)}
     print(json.dumps({**case, "case": "probes: neighbor_tensors", **stats(times["neighbor_tensors"], "wall_")}), flush=True)
     dev = kernels(crate, radius, k, reps, 1, queries)
@@ -192,27 +148,14 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import bench
-    import sand_crate_amd as sc
+    use_library(args.lib)
 
     shapes = [(16, 1.0), (64, 1.0), (32, 2.0)]
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, shapes, True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     base = {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}
     big_reps = max(5, args.reps // 3)
     measure(crate, base, big_reps, shapes, False)

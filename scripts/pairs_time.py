@@ -22,40 +22,14 @@ repetitions, in microseconds.
 """
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, viewer_crate, wall_us
 
 ROOFLINE_BYTES_PER_S = 8e12
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def pair_kernels(crate, reps, total):
@@ -66,32 +40,24 @@ def pair_kernels(crate, reps, total):
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     partners = torch.empty(total, dtype=torch.int64, device=dev)
     d2 = torch.empty(total, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
     radius = crate.diameter
-    for _ in range(3):
+    began, wall = [], []                  # the enqueue of both calls: from before the count to after the fill
+
+    def count():
+        began.append(time.perf_counter())
         eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
+
+    def fill():
         eng.pairs_fill(partners, d2)
-    torch.cuda.synchronize(dev)
-    count_t, fill_t, wall = [], [], []
-    for _ in range(reps):
-        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        a.record(stream)
-        t0 = time.perf_counter()
-        eng.pairs_count(None, radius=radius, offsets=offsets, counts=counts)
-        b.record(stream)
-        eng.pairs_fill(partners, d2)
-        wall.append(1e6 * (time.perf_counter() - t0))
-        c.record(stream)
-        c.synchronize()
-        count_t.append(1000.0 * a.elapsed_time(b))
-        fill_t.append(1000.0 * b.elapsed_time(c))
-    eng.use_own_stream()
+        wall.append(1e6 * (time.perf_counter() - began[-1]))
+
+    times = device_times(eng, {"count": count, "fill": fill}, reps, WARMUP)
     n = int(counts[0])
     written = 8 * (n + 1) + 16 * total
-    both = sorted(x + y for x, y in zip(count_t, fill_t))[len(count_t) // 2]
-    return {**stats(count_t, "count_device_"), **stats(fill_t, "fill_device_"), **stats(wall, "enqueue_wall_"),
-            "bytes_written": written, "roofline_fraction": round(written / (both * 1e-6) / ROOFLINE_BYTES_PER_S, 4)}
+    both = median([x + y for x, y in zip(times["count"], times["fill"])])
+    return {**stats(times["count"], "count_device_"), **stats(times["fill"], "fill_device_"),
+            **stats(wall[-reps:], "enqueue_wall_"), "bytes_written": written,
+            "roofline_fraction": round(written / (both * 1e-6) / ROOFLINE_BYTES_PER_S, 4)}
 
 
 def measure(crate, base, reps, check_rule):
@@ -111,7 +77,7 @@ def measure(crate, base, reps, check_rule):
             raise SystemExit("the half list is not half the list")
     base = {**base, "E": total, "E_per_n": round(total / max(n, 1), 3)}
     times = alternate({"download": eng.download, "state_tensors": lambda: crate.state_tensors(ids=True),
-                       "pair_tensors": lambda: crate.pair_tensors(squared_distances=True)}, reps)
+                       "pair_tensors": lambda: crate.pair_tensors(squared_distances=True)}, reps, WARMUP)
     for name, t in times.items():
         print(json.dumps({**base, "case": name, **stats(t, "wall_")}), flush=True)
     print(json.dumps({**base, "case": "pair kernels", **pair_kernels(crate, reps, total)}), flush=True)
@@ -120,7 +86,7 @@ def measure(crate, base, reps, check_rule):
         p = eng.download()[0]
         t = [wall_us(lambda: pairs_spec.pairs(p, crate.diameter)) for _ in range(5)]
         print(json.dumps({**base, "case": "host search (NumPy brute force, after the download)", **stats(t, "wall_")}), flush=True)
-    med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+    med = {name: median(t) for name, t in times.items()}
     print(json.dumps({**base, "case": "verdict", "pair_tensors_over_download": round(med["pair_tensors"] / med["download"], 4),
                       "pair_tensors_is_faster_than_download": bool(med["pair_tensors"] < med["download"])}), flush=True)
     torch.cuda.synchronize()
@@ -134,23 +100,12 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
-    import sand_crate_amd as sc
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps, True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     measure(crate, {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}, max(5, args.reps // 3), False)
 
 

@@ -1,17 +1,13 @@
 """Pile-up regime: the size distribution of the buckets k_sort_big is given (cells above 96 particles) and its tasks.
    python scripts/pile_buckets.py [particles] [tick]"""
-import copy, sys
-sys.path.insert(0, ".")
+import sys
 import numpy as np, torch
 torch.cuda.init()
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 450
-wc, d = bench.world_for(n)
-p, v = bench.synthetic_state(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-s.particles = p; s.particle_velocities = v
-s.run(T - 1); s.synchronize()
+s = bench_crate(n, T - 1)
+d = s.diameter
 pos0, _, _, ids0 = s.engine.download()
 s.run(1); s.synchronize()
 pos, vel, _, ids = s.engine.download()

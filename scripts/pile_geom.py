@@ -1,16 +1,12 @@
 """Where the big cells of the pile-up regime are and how their particles are spread inside them.
    python scripts/pile_geom.py [tick]"""
-import copy, sys
-sys.path.insert(0, ".")
+import sys
 import numpy as np, torch
 torch.cuda.init()
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 n = 1048576; T = int(sys.argv[1]) if len(sys.argv) > 1 else 450
-wc, d = bench.world_for(n)
-p, v = bench.synthetic_state(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-s.particles = p; s.particle_velocities = v
-s.run(T); s.synchronize()
+s = bench_crate(n, T)
+d = s.diameter
 pos, vel, ids, _ = s.engine.download()
 cx = np.floor(pos[:, 0] / d).astype(np.int64); cy = np.floor(pos[:, 1] / d).astype(np.int64)
 ncol = cx.max() - cx.min() + 3

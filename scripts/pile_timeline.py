@@ -1,19 +1,14 @@
 """The sort kernels (scan, scatter, k_sort_big, reorder) of one tick deep in the pile-up regime, wave by wave, from a
 -DSC_TIMELINE build: span, wave lives, and how long the kernel runs on its last few waves.
    python scripts/pile_timeline.py [particles] [ticks before the stamped one]"""
-import copy, ctypes as C, sys
-sys.path.insert(0, ".")
+import ctypes as C, sys
 import numpy as np
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 from sand_crate_amd import _native as N
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
 ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 470
-wc, d = bench.world_for(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-p, v = bench.synthetic_state(n)
-s.particles = p; s.particle_velocities = v
-s.run(ticks); s.synchronize()
+s = bench_crate(n, ticks)
 lib = N.load()
 buf = np.zeros((8, 1 << 16, 4), dtype=np.int64)
 lib.sc_debug_timeline.restype = C.c_int

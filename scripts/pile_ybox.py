@@ -1,15 +1,11 @@
 """pile-up regime: how many adjacent-row candidates a per-cell y box would let the search skip"""
-import copy, sys
-sys.path.insert(0, ".")
+import sys
 import numpy as np, torch
 torch.cuda.init()
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 n = 1048576; T = int(sys.argv[1]) if len(sys.argv) > 1 else 450
-wc, d = bench.world_for(n)
-p, v = bench.synthetic_state(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-s.particles = p; s.particle_velocities = v
-s.run(T); s.synchronize()
+s = bench_crate(n, T)
+d = s.diameter
 pos, vel, ids, _ = s.engine.download()
 x, y = pos[:, 0], pos[:, 1]
 cx = np.floor(x / d).astype(np.int64); cy = np.floor(y / d).astype(np.int64)

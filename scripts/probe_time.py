@@ -13,18 +13,13 @@ rounds' medians, and the time of a device-to-device copy of 40 bytes per particl
 probe cannot avoid), with the ratio of the two."""
 import argparse
 import json
-import sys
-from pathlib import Path
+from functools import partial
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+import timing_support
+from timing_support import ROOT, bench_crate, viewer_crate
 
 SETTINGS = {"off": None, "on, no bins": 0, "on, 1024 bins": 1024}
-
-
-def stats(times):
-    times = sorted(times)
-    return {"median_us": round(times[len(times) // 2], 3), "min_us": round(times[0], 3)}
+stats = partial(timing_support.stats, digits=3)                                      # (per tick: three digits)
 
 
 def block_times(crate, advance, ticks, blocks, bins):
@@ -105,21 +100,13 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
     import sand_crate_amd as sc
 
-    n = 1048576
-    wc, _ = bench.world_for(n)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles, crate.particle_velocities = bench.synthetic_state(n)
-    crate.run(20)
-    crate.synchronize()
+    crate = bench_crate(1048576, 20)
     report({"scene": "M2"}, crate, crate.run, args.ticks, args.blocks, args.rounds)
     del crate
 
-    seed = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(215):
-        seed.physics_tick()
+    seed = viewer_crate(215)
     wc = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
     wc.particle_sources = []
     crate = sc.Crate(wc, noise="counter", noise_seed=1)

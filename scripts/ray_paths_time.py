@@ -22,49 +22,16 @@ The sides of a comparison alternate inside one loop, after 2 warm-up rounds.  On
 max over the repetitions, microseconds."""
 import argparse
 import json
-import sys
-from pathlib import Path
+from functools import partial
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "scripts"))
-
-from rays_time import alternate  # noqa: E402
+from timing_support import alternate, bench_crate, device_times, median, use_library, viewer_crate
+import timing_support
 
 EPSILON = 1e-9                        # of a particle diameter: the loop's nudge off the surface it has just hit
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2),
-            f"{prefix}max_us": round(times[-1], 2)}
-
-
-def device_times(eng, calls, reps):
-    """{name: call} -> {name: [device us]}: every repetition records an event before each call and one after the last."""
-    import torch
-    dev = torch.device("cuda", eng.device)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    names = list(calls)
-    for _ in range(2):
-        for call in calls.values():
-            call()
-    torch.cuda.synchronize(dev)
-    out = {name: [] for name in names}
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
-        for mark, name in zip(ev, names):
-            mark.record(stream)
-            calls[name]()
-        ev[-1].record(stream)
-        ev[-1].synchronize()
-        for k, name in enumerate(names):
-            out[name].append(1000.0 * ev[k].elapsed_time(ev[k + 1]))
-    eng.use_own_stream()
-    return out
+WARMUP = 2                            # rounds before anything is recorded, wall and device alike
+stats = partial(timing_support.stats, maximum=True)                                  # (this script reports the max as well)
 
 
 def kernels(crate, points, origins, directions, max_t, walls, bounces, reps, paths=True):
@@ -86,7 +53,7 @@ def kernels(crate, points, origins, directions, max_t, walls, bounces, reps, pat
                 torch.empty((rays, legs, 2), dtype=torch.float64, device=dev), torch.empty((rays, legs, 2), dtype=torch.float64, device=dev),
                 torch.empty(rays, dtype=torch.int64, device=dev))
         calls["paths"] = lambda: eng.pairs_ray_paths(*held, bounces=bounces, max_t=max_t * legs, **kw)
-    times = device_times(eng, calls, reps)
+    times = device_times(eng, calls, reps, WARMUP)
     if int(out[1]) != 0:
         raise SystemExit(f"kernels: status {int(out[1])}")
     return times
@@ -125,24 +92,24 @@ def measure(crate, base, points, origins, directions, max_t, walls, reps):
     if not (torch.equal(flat.hit[:, 0], hit) and torch.equal(flat.t[:, 0], t)):
         raise SystemExit(f"{case}: ray_paths(bounces=0) differs from ray_tensors")
     wall = alternate({"ray_tensors": lambda: crate.ray_tensors(origins, directions, max_t, walls=walls, points=points),
-                      "ray_paths": lambda: crate.ray_paths(origins, directions, max_t, 0, walls=walls, points=points)}, reps)
+                      "ray_paths": lambda: crate.ray_paths(origins, directions, max_t, 0, walls=walls, points=points)},
+                     reps, WARMUP)
     dev = kernels(crate, points, origins, directions, max_t, walls, 0, reps)
-    med = lambda series: sorted(series)[len(series) // 2]  # noqa: E731
     print(json.dumps({**case, "case": "bounces 0", **stats(wall["ray_tensors"], "ray_tensors_wall_"), **stats(wall["ray_paths"], "ray_paths_wall_"),
                       **stats(dev["rays"], "rays_device_"), **stats(dev["paths"], "paths_device_"),
-                      "paths_over_rays_wall": round(med(wall["ray_paths"]) / med(wall["ray_tensors"]), 3),
-                      "paths_over_rays_device": round(med(dev["paths"]) / med(dev["rays"]), 3)}), flush=True)
+                      "paths_over_rays_wall": round(median(wall["ray_paths"]) / median(wall["ray_tensors"]), 3),
+                      "paths_over_rays_device": round(median(dev["paths"]) / median(dev["rays"]), 3)}), flush=True)
     for bounces in (1, 3, 7):
         got = crate.ray_paths(origins, directions, max_t * (bounces + 1), bounces, walls=walls, points=points)
         wall = alternate({"loop": lambda: loop_route(crate, cloud, points, origins, directions, max_t, walls, bounces),
                           "ray_paths": lambda: crate.ray_paths(origins, directions, max_t * (bounces + 1), bounces, walls=walls,
-                                                               points=points)}, reps)
+                                                               points=points)}, reps, WARMUP)
         dev = kernels(crate, points, origins, directions, max_t, walls, bounces, reps)
         print(json.dumps({**case, "case": f"bounces {bounces}", "legs_that_hit": int((got.hit != -1).sum()),
                           "ends": {str(k): int((got.end == k).sum()) for k in (0, 1, 2, -1, -4)},
                           **stats(wall["loop"], "loop_wall_"), **stats(wall["ray_paths"], "ray_paths_wall_"),
                           **stats(dev["paths"], "paths_device_"),
-                          "paths_over_loop_wall": round(med(wall["ray_paths"]) / med(wall["loop"]), 4)}), flush=True)
+                          "paths_over_loop_wall": round(median(wall["ray_paths"]) / median(wall["loop"]), 4)}), flush=True)
 
 
 def main():
@@ -155,33 +122,20 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
+    if use_library(args.lib) and args.rays_only:                                    # (a build from before the paths has no such export)
         from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-        if args.rays_only:                                                          # (a build from before the paths has no such export)
-            _native.SIGNATURES.pop("sc_pairs_ray_paths_device", None)
-    import bench
-    import sand_crate_amd as sc
+        _native.SIGNATURES.pop("sc_pairs_ray_paths_device", None)
     from sand_crate_amd import pairs
 
     dev = torch.device("cuda", 0)
     fan = pairs.ray_fan((0.5, 0.5), 256, 0.0, 2 * np.pi, device=dev)
     if not args.rays_only:
-        crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-        for _ in range(args.ticks):
-            crate.physics_tick()
-        crate.synchronize()
+        crate = viewer_crate(args.ticks)
         torch.cuda.synchronize()
         measure(crate, {"state": "wave_machine", "ticks": args.ticks}, None, *fan, 2.0, crate.segments, args.reps)
         crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     walls = crate.segments
     side = 512
     k = (torch.arange(side, dtype=torch.float64, device=dev) + 0.5) / side

@@ -27,40 +27,13 @@ JSON line per case: median and min over the repetitions, microseconds.
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+from timing_support import alternate, bench_crate, device_times, median, stats, use_library, viewer_crate
 
 CHUNK = 256
-
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=2):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 2                            # rounds before anything is recorded, wall and device alike
 
 
 def torch_route(points, walls, origins, directions, rho, max_t):
@@ -96,7 +69,7 @@ def torch_route(points, walls, origins, directions, rho, max_t):
     return best, hit
 
 
-def device_times(crate, points, origins, directions, rho, max_t, walls, reps):
+def kernels(crate, points, origins, directions, rho, max_t, walls, reps):
     """Device time of the count and of the rays by events, into tensors made once."""
     import torch
     eng = crate.engine
@@ -106,35 +79,14 @@ def device_times(crate, points, origins, directions, rho, max_t, walls, reps):
     offsets = torch.empty(bound + 1, dtype=torch.int64, device=dev)
     counts, out = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(2, dtype=torch.int64, device=dev)
     t, hit = torch.empty(rays, dtype=torch.float64, device=dev), torch.empty(rays, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-
-    calls = (lambda: eng.pairs_count(points, radius=2 * rho, offsets=offsets, counts=counts),
-             lambda: eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho, max_t=max_t, segments=walls,
-                                    counts=out), lambda: None)
-
-    def once(events=None):
-        for mark, call in zip(events or [None] * len(calls), calls):
-            if mark is not None:
-                mark.record(stream)
-            call()
-
-    for _ in range(2):
-        once()
-    torch.cuda.synchronize(dev)
-    times = [[] for _ in range(len(calls) - 1)]
-    for _ in range(reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in calls]
-        once(ev)
-        ev[-1].synchronize()
-        for k, series in enumerate(times):
-            series.append(1000.0 * ev[k].elapsed_time(ev[k + 1]))
-    eng.use_own_stream()
+    times = device_times(eng, {
+        "count": lambda: eng.pairs_count(points, radius=2 * rho, offsets=offsets, counts=counts),
+        "rays": lambda: eng.pairs_rays(t, hit, origins=origins, directions=directions, disc_radius=rho, max_t=max_t, segments=walls,
+                                       counts=out)}, reps, WARMUP)
     if int(out[1]) != 0:
         raise SystemExit(f"kernels: status {int(out[1])}")
-    med = lambda series: sorted(series)[len(series) // 2]  # noqa: E731
-    return {**stats(times[0], "count_device_"), **stats(times[1], "rays_device_"),
-            "rays_over_count": round(med(times[1]) / med(times[0]), 3)}
+    return {**stats(times["count"], "count_device_"), **stats(times["rays"], "rays_device_"),
+            "rays_over_count": round(median(times["rays"]) / median(times["count"]), 3)}
 
 
 def measure(crate, base, points, origins, directions, max_t, walls, reps, check_rule=False):
@@ -164,16 +116,17 @@ def measure(crate, base, points, origins, directions, max_t, walls, reps, check_
         torch.cuda.synchronize()
 
     times = alternate({"torch": by_torch,
-                       "ray_tensors": lambda: crate.ray_tensors(origins, directions, max_t, walls=walls, points=points)}, reps)
+                       "ray_tensors": lambda: crate.ray_tensors(origins, directions, max_t, walls=walls, points=points)},
+                      reps, WARMUP)
     scale = ((rays + CHUNK - 1) // CHUNK) / chunks
     print(json.dumps({**case, "case": "torch broadcast", "chunks_timed": chunks, "extrapolated": scale != 1.0,
                       "equal_to_the_kernel": equal, **stats([v * scale for v in times["torch"]], "wall_")}), flush=True)
-    med = {name: sorted(series)[len(series) // 2] for name, series in times.items()}
+    med = {name: median(series) for name, series in times.items()}
     print(json.dumps({**case, "case": "ray_tensors", **stats(times["ray_tensors"], "wall_"),
                       "ray_tensors_over_torch": round(med["ray_tensors"] / (med["torch"] * scale), 5)}), flush=True)
     print(json.dumps({**case, "case": "kernels", "hits_on_particles": int((hit >= 0).sum()), "hits_on_walls": int((hit <= -2).sum()),
                       "mean_t_in_cells": round(float(t[torch.isfinite(t)].mean()) / crate.diameter, 2),
-                      **device_times(crate, points, origins, directions, rho, max_t, walls, reps)}), flush=True)
+                      **kernels(crate, points, origins, directions, rho, max_t, walls, reps)}), flush=True)
 
 
 def sweep(crate, base, points, origins, directions, max_t, walls, reps):
@@ -181,7 +134,7 @@ def sweep(crate, base, points, origins, directions, max_t, walls, reps):
     for rays in (256, 1024, 4096, 16384, 65536, 262144):
         step = max(1, int(origins.shape[0]) // rays)
         o, d = origins[::step][:rays].contiguous(), directions[::step][:rays].contiguous()
-        got = device_times(crate, points, o, d, rho, max_t, walls, reps)
+        got = kernels(crate, points, o, d, rho, max_t, walls, reps)
         print(json.dumps({**base, "case": "sweep", "rays": int(o.shape[0]),
                           **{k: v for k, v in got.items() if not k.startswith("count")}}), flush=True)
 
@@ -195,30 +148,17 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    if args.lib:
-        from sand_crate_amd import _native
-        _native.LIB_PATH = Path(args.lib).resolve()
-    import bench
-    import sand_crate_amd as sc
+    use_library(args.lib)
     from sand_crate_amd import pairs
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     dev = torch.device("cuda", crate.engine.device)
     fan = pairs.ray_fan((0.5, 0.5), 256, 0.0, 2 * np.pi, device=dev)
     torch.cuda.synchronize()
     measure(crate, {"state": "wave_machine", "ticks": args.ticks}, None, *fan, 2.0, crate.segments, args.reps, check_rule=True)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     walls = crate.segments
     side = 512
     k = (torch.arange(side, dtype=torch.float64, device=dev) + 0.5) / side

@@ -21,54 +21,26 @@ older library.
 """
 import argparse
 import json
-import sys
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+from timing_support import ROOT, alternate, bench_crate, device_times, stats, viewer_crate
 
-
-def stats(times):
-    times = sorted(times)
-    return {"median_us": round(times[len(times) // 2], 2), "min_us": round(times[0], 2)}
+WARMUP = 3                            # rounds before anything is recorded: first-use costs, buffer growth, code object load
 
 
-def device_times(crate, width, height, reps, **kw):
+def render_times(crate, width, height, reps, **kw):
     """Device time of `reps` renders (with these keywords of `Crate.render`), HIP events around each."""
     import torch
-    stream = torch.cuda.current_stream()
-    crate.engine.set_stream(stream.cuda_stream)
     out = torch.empty((height, width, 3), dtype=torch.uint8, device="cuda")
-    for _ in range(3):  # first-use costs: buffer growth, code object load
-        crate.render(width, height, out=out, **kw)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        crate.render(width, height, out=out, **kw)
-        b.record(stream)
-        b.synchronize()
-        times.append(1000.0 * a.elapsed_time(b))
-    crate.engine.use_own_stream()
-    return times
+    return device_times(crate.engine, {"render": lambda: crate.render(width, height, out=out, **kw)}, reps, WARMUP)["render"]
 
 
 def time_render(crate, width, height, reps):
-    return stats(device_times(crate, width, height, reps))
+    return stats(render_times(crate, width, height, reps))
 
 
 def wall_times(call, reps):
     """Host wall time of a call that ends in a device synchronise."""
-    import time
-    for _ in range(3):
-        call()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        call()
-        times.append(1e6 * (time.perf_counter() - t0))
-    return times
+    return alternate({"call": call}, reps, WARMUP)["call"]
 
 
 def hud_report(reps):
@@ -87,7 +59,7 @@ def hud_report(reps):
     print(json.dumps({**head, "hud_bytes": len(text), "hud_lines": len(lines), "hud_longest_line": max(map(len, lines)),
                       "hud_available": has_hud}), flush=True)
     cases = {
-        "render": ("device", lambda **kw: device_times(crate, side, side, reps, **kw)),
+        "render": ("device", lambda **kw: render_times(crate, side, side, reps, **kw)),
         "render_jpeg": ("wall", lambda **kw: wall_times(lambda: crate.render_jpeg(side, side, **kw), reps)),
         "render_gif": ("wall", lambda **kw: wall_times(lambda: crate.render_gif(side, side, **kw), reps)),
     }
@@ -121,20 +93,14 @@ def hud_report(reps):
     whole = stats(wall_times(host_hud, reps))
     print(json.dumps({**head, "case": "host HUD (download + PIL text + upload)", "clock": "wall", **whole,
                       "render_to_host_median_us": plain["median_us"],
-                      "added_over_device_frame_us": round(whole["median_us"] - stats(device_times(crate, side, side, reps))["median_us"], 2)}),
+                      "added_over_device_frame_us": round(whole["median_us"] - stats(render_times(crate, side, side, reps))["median_us"], 2)}),
           flush=True)
 
 
 def arrows_report(reps, rounds=3):
     import numpy as np
-    import bench
-    import sand_crate_amd as sc
-    side, n = 1000, 1048576
-    wc, _ = bench.world_for(n)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles, crate.particle_velocities = bench.synthetic_state(n)
-    crate.run(5)
-    crate.synchronize()
+    side = 1000
+    crate = bench_crate(1048576, 5)
     has_arrows = hasattr(crate.engine, "set_arrows")
     rs = np.random.RandomState(2048)
     pairs = np.stack([rs.rand(2048, 2), (rs.rand(2048, 2) - 0.5) * 0.1], axis=1)  # (start, direction): 10 to 40 pixels
@@ -148,7 +114,7 @@ def arrows_report(reps, rounds=3):
     medians = {kind: [] for kind in kinds}
     for rnd in range(rounds):
         for kind, kw in kinds.items():
-            times = device_times(crate, side, side, reps, **kw)
+            times = render_times(crate, side, side, reps, **kw)
             got[kind] += times
             medians[kind].append(stats(times)["median_us"])
             print(json.dumps({**head, "arrows": kind, "round": rnd, "clock": "device", **stats(times)}), flush=True)
@@ -175,15 +141,8 @@ def main():
     if args.arrows:
         arrows_report(args.reps)
         return
-    import bench
-    import sand_crate_amd as sc
 
-    n = 1048576
-    wc, _ = bench.world_for(n)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=n + 1024)
-    crate.particles, crate.particle_velocities = bench.synthetic_state(n)
-    crate.run(5)
-    crate.synchronize()
+    crate = bench_crate(1048576, 5)
     for side in (1000, 4096):
         radius = int(side * crate.particle_radius)
         print(json.dumps({"scene": "M2", "particles": crate.particle_count, "frame": f"{side}x{side}", "disc_radius": radius,
@@ -191,10 +150,7 @@ def main():
                           **time_render(crate, side, side, args.reps)}), flush=True)
     del crate
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(200):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(200)
     print(json.dumps({"scene": "wave_machine", "particles": crate.particle_count, "frame": "1000x1000", "disc_radius": 5,
                       "splat": "wave per disc", **time_render(crate, 1000, 1000, args.reps)}), flush=True)
 

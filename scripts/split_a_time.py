@@ -1,15 +1,14 @@
 """Pass A split into its two halves at full size: the search alone (ENUM launch) and the pair math alone (DENS launch
 reading the lists back), via the host-noise path of the C ABI with a zero noise block."""
-import copy, sys
-sys.path.insert(0, ".")
-import numpy as np, bench, sand_crate_amd as sc
-from sand_crate_amd import _native as N
+import sys
+import numpy as np
+from timing_support import bench_crate, use_library
+use_library()  # $SAND_CRATE_LIB: a variant build (scripts/run_variants.sh), else the package's own library
+import bench, sand_crate_amd as sc
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
-wc, d = bench.world_for(n); p, v = bench.synthetic_state(n)
-c = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024); c.particles = p; c.particle_velocities = v
-c.run(10); c.synchronize()
+c = bench_crate(n, 10)
 p, v, _, _ = c.engine.download()
-h = sc.Crate(copy.deepcopy(wc), noise="host-sync", capacity=n + 1024)
+h = sc.Crate(bench.world_for(n)[0], noise="host-sync", capacity=n + 1024)
 e = h.engine
 acc = {}
 for rep in range(6):

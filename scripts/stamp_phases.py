@@ -1,17 +1,12 @@
 """Where a wave of pass A / pass B spends its life (diagnostic build with -DSC_STAMPS): median clock ticks between
 the phase stamps of sc_tiled.h, the last tick of a 20-tick run of the contract workload (that tick has no look-ahead:
 pass B runs without its fused wall pass -- scripts/stamp_phases_b.py shows both).   python scripts/stamp_phases.py [particles]"""
-import copy, ctypes as C, sys
-sys.path.insert(0, ".")
+import ctypes as C, sys
 import numpy as np
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 from sand_crate_amd import _native as N
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
-wc, d = bench.world_for(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-p, v = bench.synthetic_state(n)
-s.particles = p; s.particle_velocities = v
-s.run(20); s.synchronize()
+s = bench_crate(n, 20)
 lib = N.load()
 buf = np.zeros((6, 1 << 16, 24), dtype=np.int64)
 lib.sc_debug_stamps.restype = C.c_int

@@ -1,18 +1,13 @@
 """Where a wave of pass B spends its life, with and without the look-ahead epilogue (diagnostic build with -DSC_STAMPS):
 the last tick of a run has no look-ahead, the tick before it has; their stamps go to different buffers (sc_tiled.h:
 SC_STAMP_B).   python scripts/stamp_phases_b.py [particles]"""
-import copy, ctypes as C, sys
-sys.path.insert(0, ".")
+import ctypes as C, sys
 import numpy as np
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 from sand_crate_amd import _native as N
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
-wc, d = bench.world_for(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-p, v = bench.synthetic_state(n)
-s.particles = p; s.particle_velocities = v
 ticks = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-s.run(ticks); s.synchronize()
+s = bench_crate(n, ticks)
 lib = N.load()
 buf = np.zeros((6, 1 << 16, 24), dtype=np.int64)
 lib.sc_debug_stamps.restype = C.c_int

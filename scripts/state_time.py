@@ -19,37 +19,12 @@ with the download, byte for byte.  One JSON line per case: median and min over t
 """
 import argparse
 import json
-import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
+from timing_support import alternate, bench_crate, device_times, stats, viewer_crate, with_wall
 
-
-def stats(times, prefix=""):
-    times = sorted(times)
-    return {f"{prefix}median_us": round(times[len(times) // 2], 2), f"{prefix}min_us": round(times[0], 2)}
-
-
-def wall_us(fn):
-    t0 = time.perf_counter()
-    fn()
-    return 1e6 * (time.perf_counter() - t0)
-
-
-def alternate(cases, reps, warmup=3):
-    """{name: fn} -> {name: [wall us]}: every repetition runs each case once, in turn."""
-    for _ in range(warmup):
-        for fn in cases.values():
-            fn()
-    out = {name: [] for name in cases}
-    for _ in range(reps):
-        for name, fn in cases.items():
-            out[name].append(wall_us(fn))
-    return out
+WARMUP = 3                            # rounds before anything is recorded, wall and device alike
 
 
 def check_equal(crate):
@@ -69,28 +44,17 @@ def export_kernels(crate, reps):
     pr = torch.empty(room, dtype=torch.float64, device=dev)
     ids = torch.empty(room, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    eng.set_stream(stream.cuda_stream)
-    for _ in range(3):
-        eng.export_state(p, v, pr, ids, count=count)
-    torch.cuda.synchronize(dev)
-    device, wall = [], []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        wall.append(wall_us(lambda: eng.export_state(p, v, pr, ids, count=count)))
-        b.record(stream)
-        b.synchronize()
-        device.append(1000.0 * a.elapsed_time(b))
-    eng.use_own_stream()
-    return {**stats(device, "device_"), **stats(wall, "enqueue_wall_")}
+    wall = []
+    export = with_wall(lambda: eng.export_state(p, v, pr, ids, count=count), wall)
+    device = device_times(eng, {"export": export}, reps, WARMUP)["export"]
+    return {**stats(device, "device_"), **stats(wall[-reps:], "enqueue_wall_")}
 
 
 def measure(crate, base, reps):
     import torch
     check_equal(crate)
     eng = crate.engine
-    times = alternate({"download": eng.download, "state_tensors": lambda: crate.state_tensors(ids=True)}, reps)
+    times = alternate({"download": eng.download, "state_tensors": lambda: crate.state_tensors(ids=True)}, reps, WARMUP)
     for name, t in times.items():
         print(json.dumps({**base, "case": name, **stats(t, "wall_")}), flush=True)
     print(json.dumps({**base, "case": "export kernels", **export_kernels(crate, reps)}), flush=True)
@@ -108,7 +72,7 @@ def measure(crate, base, reps):
     times = alternate({"upload": synced(lambda: eng.upload(p, v)),
                        "load_tensors": synced(lambda: crate.load_state_tensors(tp, tv)),
                        "upload_ids": synced(lambda: eng.upload_with_ids(p, v, ids)),
-                       "load_tensors_ids": synced(lambda: crate.load_state_tensors(tp, tv, ti))}, reps)
+                       "load_tensors_ids": synced(lambda: crate.load_state_tensors(tp, tv, ti))}, reps, WARMUP)
     for name, t in times.items():
         print(json.dumps({**base, "case": name, **stats(t, "wall_")}), flush=True)
     check_equal(crate)
@@ -122,23 +86,12 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    import bench
-    import sand_crate_amd as sc
 
-    crate = sc.Crate(sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config)
-    for _ in range(args.ticks):
-        crate.physics_tick()
-    crate.synchronize()
+    crate = viewer_crate(args.ticks)
     measure(crate, {"state": "wave_machine", "ticks": args.ticks, "particles": crate.particle_count}, args.reps)
     crate.engine.close()
 
-    wc, _ = bench.world_for(args.big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=args.big + 1024)
-    p, v = bench.synthetic_state(args.big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(args.big, 3)
     measure(crate, {"state": "synthetic", "ticks": 3, "particles": crate.particle_count}, max(5, args.reps // 3))
 
 

@@ -3,20 +3,15 @@
 
 Prints, per kernel: span, workgroup life, how many workgroups are resident per CU over time, and -- the question this was
 written for -- how long a CU's slot stays empty between one workgroup's end and the next one's start."""
-import copy, ctypes as C, sys
-sys.path.insert(0, ".")
+import ctypes as C, sys
 import numpy as np
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 from sand_crate_amd import _native as N
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
 wpb = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-wc, d = bench.world_for(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-p, v = bench.synthetic_state(n)
-s.particles = p; s.particle_velocities = v
 import time
-s.run(20); s.synchronize()
+s = bench_crate(n, 20)
 t_run = time.perf_counter(); s.run(20); s.synchronize(); period = (time.perf_counter() - t_run) / 20 * 1e6
 print(f"tick period over 20 ticks: {period:.1f} us (the gap between pass B's last wave and the next tick's first wave is this minus the tick's span below)")
 lib = N.load()

@@ -1,17 +1,12 @@
 """Pass A's and pass B's waves inside the ONE launch of k_pass_ab, from a -DSC_TIMELINE build: when each role's waves start
 and end, and how many waves of each role a CU holds over the launch.   python scripts/timeline_ab.py [particles]"""
-import copy, ctypes as C, sys
-sys.path.insert(0, ".")
+import ctypes as C, sys
 import numpy as np
-import bench, sand_crate_amd as sc
+from timing_support import bench_crate
 from sand_crate_amd import _native as N
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1048576
-wc, d = bench.world_for(n)
-s = sc.Crate(copy.deepcopy(wc), noise="counter", noise_seed=1, capacity=n + 1024)
-p, v = bench.synthetic_state(n)
-s.particles = p; s.particle_velocities = v
-s.run(20); s.synchronize()
+s = bench_crate(n, 20)
 lib = N.load()
 buf = np.zeros((8, 1 << 16, 4), dtype=np.int64)
 lib.sc_debug_timeline.restype = C.c_int

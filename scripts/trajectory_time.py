@@ -25,19 +25,13 @@ The sides of a comparison alternate inside one loop.  Before anything is timed a
 export scattered by torch, byte for byte.  One JSON line per case: median, min and max over the repetitions."""
 import argparse
 import json
-import sys
 import time
-from pathlib import Path
+from functools import partial
 
+import timing_support
+from timing_support import bench_crate, viewer_crate
 
-ROOT = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(ROOT))
-
-
-def stats(values, prefix="", digits=2):
-    values = sorted(values)
-    return {f"{prefix}median": round(values[len(values) // 2], digits), f"{prefix}min": round(values[0], digits),
-            f"{prefix}max": round(values[-1], digits)}
+stats = partial(timing_support.stats, maximum=True, unit="")                         # (the unit is in the prefix: us, ticks per s)
 
 
 class Frames:
@@ -160,24 +154,12 @@ def frames_only(n_frames, ticks, big, which):
 
 def states(ticks, big, which="both"):
     """-> (name, crate, rows of the default window) per state."""
-    import bench
-    import sand_crate_amd as sc
     if which in ("both", "wave_machine"):
-        cfg = sc.load_config(ROOT / "config" / "wave_machine.yaml").world_config
-        crate = sc.Crate(cfg)
-        for _ in range(ticks):
-            crate.physics_tick()
-        crate.synchronize()
-        yield "wave_machine", crate, int(cfg.coefficients["max_particles"])
+        crate = viewer_crate(ticks)
+        yield "wave_machine", crate, int(crate.world_config.coefficients["max_particles"])
     if which == "wave_machine":
         return
-    wc, _ = bench.world_for(big)
-    crate = sc.Crate(wc, noise="counter", noise_seed=1, capacity=big + 1024)
-    p, v = bench.synthetic_state(big)
-    crate.particles = p
-    crate.particle_velocities = v
-    crate.run(3)
-    crate.synchronize()
+    crate = bench_crate(big, 3)
     yield "synthetic", crate, big
 
 
