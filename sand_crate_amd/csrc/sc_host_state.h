@@ -623,31 +623,42 @@ int sc_pairs_hist_batch_device(sc_ctx* c, const double* dev_queries, int64_t n_q
 
 // ---- ray sensors (sc_rays.h) ----------------------------------------------------------------------
 
-// What the rays and the ray paths ask of their common arguments, before the reader's own checks.
-static int rays_arguments(const double* dev_directions, int64_t n_rays, double disc_radius, double max_t, const double* segments,
-                          int32_t n_segments) {
+// What a rays call launches with: the reader, the directions, the walls by value, a wave per ray.
+struct RaysCall {
+  Reader r;
+  const XY* dirs;
+  RayWalls walls;
+  unsigned grid;  // (one at least: it writes the counts)
+};
+
+// What the rays and the ray paths share, after the checks of their own arguments: the checks of the common ones, the
+// reader's, the disc radius against the count's, and the check passes over leg 0.  `one`, `many`: the call and its
+// batched form, `batched` says which this is.
+static int rays_begin(sc_ctx* c, bool batched, const char* one, const char* many, const char* holder, const double* dev_origins,
+                      const double* dev_directions, int64_t n_rays, double disc_radius, double max_t, const double* segments,
+                      int32_t n_segments, int64_t room_rows, int64_t* dev_counts, RaysCall* call) {
   if (n_rays < 0) return fail(SC_ERR_ARG, "negative ray count");
   if ((uintptr_t)dev_directions & 15) return fail(SC_ERR_ARG, "the directions must be aligned to 16 bytes");
   if (!(max_t >= 0) || !std::isfinite(max_t)) return fail(SC_ERR_ARG, "max_t must be finite and not negative");
   if (!(disc_radius >= 0) || !std::isfinite(disc_radius)) return fail(SC_ERR_ARG, "the disc radius must be finite and not negative");
   if (n_segments < 0 || n_segments > kMaxSeg) return fail(SC_ERR_CAPACITY, "%d segments, at most %d", (int)n_segments, kMaxSeg);
   if (n_segments > 0 && !segments) return fail(SC_ERR_ARG, "null segment array");
-  return SC_OK;
-}
-
-// ... and after them: the disc radius against the count's, the walls by value, and the check passes over leg 0.
-static int rays_check(sc_ctx* c, const Reader& r, double disc_radius, double max_t, const double* segments, int32_t n_segments,
-                      const XY* dirs, int64_t* dev_counts, RayWalls* walls) {
+  const ReaderCall names = batched ? ReaderCall{many, "send rays through", holder, true, true, one}
+                                   : ReaderCall{one, "send rays through", holder, false, true, many};
+  Reader& r = call->r;
+  if (const int rc = reader_begin(c, names, dev_origins, n_rays, room_rows, &r)) return rc;
   if (!(disc_radius <= c->pairs.grid.radius / 2))
     return fail(SC_ERR_ARG, "the disc radius %.17g is more than half the count's radius %.17g: count at twice the disc radius",
                 disc_radius, c->pairs.grid.radius);
-  *walls = RayWalls{};
-  walls->n = n_segments;
-  if (n_segments) std::memcpy(walls->s, segments, sizeof(double) * 4 * (size_t)n_segments);
+  call->dirs = (const XY*)dev_directions;
+  call->walls = RayWalls{};
+  call->walls.n = n_segments;
+  if (n_segments) std::memcpy(call->walls.s, segments, sizeof(double) * 4 * (size_t)n_segments);
+  call->grid = (unsigned)std::max<int64_t>(1, r.rows);
   if (const int rc = reader_check(c, r, -1, -1, dev_counts)) return rc;
   if (disc_radius > 0)
-    hipLaunchKernelGGL(k_rays_check, dim3(grid_for(r.rows)), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, *walls, max_t,
-                       r.queries, dirs, (long long)r.rows, c->pairs.readerFlag.get());
+    hipLaunchKernelGGL(k_rays_check, dim3(grid_for(r.rows)), dim3(kBlock), 0, c->stream, c->pairs.grid.radius, call->walls, max_t,
+                       r.queries, call->dirs, (long long)r.rows, c->pairs.readerFlag.get());
   return SC_OK;
 }
 
@@ -658,21 +669,14 @@ static int pairs_rays(sc_ctx* c, bool batched, const double* dev_origins, const 
   if (!c) return fail(SC_ERR_ARG, "null context");
   if (!dev_origins || !dev_directions || !dev_t || !dev_hit || !dev_counts)
     return fail(SC_ERR_ARG, "null origins, directions, t, hit or counts pointer");
-  if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
-  Reader r;
-  const ReaderCall call = batched ? ReaderCall{"sc_pairs_rays_batch_device", "send rays through", "t and hit hold", true, true,
-                                               "sc_pairs_rays_device"}
-                                  : ReaderCall{"sc_pairs_rays_device", "send rays through", "t and hit hold", false, true,
-                                               "sc_pairs_rays_batch_device"};
-  if (const int rc = reader_begin(c, call, dev_origins, n_rays, room_rows, &r)) return rc;
-  const XY* dirs = (const XY*)dev_directions;
+  RaysCall k;
+  if (const int rc = rays_begin(c, batched, "sc_pairs_rays_device", "sc_pairs_rays_batch_device", "t and hit hold", dev_origins,
+                                dev_directions, n_rays, disc_radius, max_t, segments, n_segments, room_rows, dev_counts, &k))
+    return rc;
   const RayOut out{dev_t, (long long*)dev_hit, (long long*)dev_counts};
-  RayWalls walls;
-  if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
-  const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
-  hipLaunchKernelGGL(batched ? k_rays<true> : k_rays<false>, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view, walls,
-                     (int)(disc_radius > 0), disc_radius * disc_radius, max_t, c->pairs.readerFlag.get(), r.queries, dirs,
-                     (long long)r.rows, out);
+  hipLaunchKernelGGL(batched ? k_rays<true> : k_rays<false>, dim3(k.grid), dim3(kRayBlock), 0, c->stream, k.r.view, k.walls,
+                     (int)(disc_radius > 0), disc_radius * disc_radius, max_t, c->pairs.readerFlag.get(), k.r.queries, k.dirs,
+                     (long long)k.r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }
@@ -689,21 +693,15 @@ static int pairs_ray_paths(sc_ctx* c, bool batched, const double* dev_origins, c
     return fail(SC_ERR_ARG, "%d bounces, it must be 0 .. %d", (int)bounces, (int)SC_RAY_MAX_BOUNCES);
   static_assert(kRayMaxLegs == SC_RAY_MAX_BOUNCES + 1, "the header's bound is the kernel's");
   if (((uintptr_t)dev_points | (uintptr_t)dev_normals) & 15) return fail(SC_ERR_ARG, "the points and the normals must be aligned to 16 bytes");
-  if (const int rc = rays_arguments(dev_directions, n_rays, disc_radius, max_t, segments, n_segments)) return rc;
-  Reader r;
-  const ReaderCall call = batched ? ReaderCall{"sc_pairs_ray_paths_batch_device", "send rays through", "the paths hold", true, true,
-                                               "sc_pairs_ray_paths_device"}
-                                  : ReaderCall{"sc_pairs_ray_paths_device", "send rays through", "the paths hold", false, true,
-                                               "sc_pairs_ray_paths_batch_device"};
-  if (const int rc = reader_begin(c, call, dev_origins, n_rays, room_rows, &r)) return rc;
-  const XY* dirs = (const XY*)dev_directions;
+  RaysCall k;
+  if (const int rc = rays_begin(c, batched, "sc_pairs_ray_paths_device", "sc_pairs_ray_paths_batch_device", "the paths hold",
+                                dev_origins, dev_directions, n_rays, disc_radius, max_t, segments, n_segments, room_rows,
+                                dev_counts, &k))
+    return rc;
   const RayPathOut out{dev_t, (long long*)dev_hit, (XY*)dev_points, (XY*)dev_normals, (long long*)dev_end, (long long*)dev_counts};
-  RayWalls walls;
-  if (const int rc = rays_check(c, r, disc_radius, max_t, segments, n_segments, dirs, dev_counts, &walls)) return rc;
-  const int64_t grid = std::max<int64_t>(1, r.rows);  // a wave per ray (one at least: it writes the counts)
-  hipLaunchKernelGGL(batched ? k_ray_paths<true> : k_ray_paths<false>, dim3((unsigned)grid), dim3(kRayBlock), 0, c->stream, r.view,
-                     walls, (int)(disc_radius > 0), disc_radius * disc_radius, max_t, (int)bounces + 1,
-                     c->pairs.readerFlag.get(), r.queries, dirs, (long long)r.rows, out);
+  hipLaunchKernelGGL(batched ? k_ray_paths<true> : k_ray_paths<false>, dim3(k.grid), dim3(kRayBlock), 0, c->stream, k.r.view,
+                     k.walls, (int)(disc_radius > 0), disc_radius * disc_radius, max_t, (int)bounces + 1,
+                     c->pairs.readerFlag.get(), k.r.queries, k.dirs, (long long)k.r.rows, out);
   HIPCHK(hipGetLastError());
   return SC_OK;
 }

@@ -18,11 +18,15 @@
 //   k_reader_check (sc_pairs.h) prepares counts[1] and raises the domain bit of the readers' flag for an origin outside
 //                  the domain: the origins are the queries;
 //   k_rays_check   a thread per ray: the domain bit for a live ray's end point fl(o + fl(max_t d)) that fails
-//                  pairs_outside's rule or is not finite, and kRayFlagRange for a live ray whose walk would take more
-//                  than kRayMaxSteps steps (below).  Not launched for walls alone;
+//                  pairs_outside's rule or is not finite (ray_end_outside), and kRayFlagRange for a live ray whose walk
+//                  would take more than kRayMaxSteps steps (ray_too_long).  Not launched for walls alone;
 //   k_rays         a wave per ray: the walls, the walk, the result -- unless a flag is up: then counts[1] = -1 (the
-//                  domain) or -4 (the range) is all that is written;
-//   k_ray_paths    (sc_pairs_ray_paths_device) the same wave, kept for bounces + 1 legs: "Paths" below.
+//                  domain) or -4 (the range) is all that is written (ray_begin).  A ray is one leg;
+//   k_ray_paths    (sc_pairs_ray_paths_device) the same wave, kept for bounces + 1 legs in a loop: "Paths" below.
+//
+// A leg is what is walked: an origin o, a direction d, a budget max_t -- and, in a path, the object the leg before it hit,
+// which takes no part in it.  There is one walk, ray_walk, with one scan, ray_scan, for the legs of both kernels; what
+// follows is about that one loop.
 //
 // The walk.  s is the count's radius and the host requires rho <= s / 2; the cells are h = fl(s (1 + 2^-20)) wide.  With
 // dt = fl(s / sqrt(a)), step k covers t in [fl(k dt), fl((k + 1) dt)] -- consecutive steps share their border, so the
@@ -32,9 +36,16 @@
 // which candidates are met does not reach the output.  The walls are tested first; t_end = min(max_t, the nearest wall's
 // t) caps the walk: step k is walked iff fl(k dt) <= t_end.  The walk ends after the first step k with
 // best t < fl((k + 1) dt).  A disc that would win has t* <= best t; its own step k* (the one whose piece holds t*) is
-// then at most k, and -- the claim below -- the disc was a candidate of step k*.  The kernel takes kRayWaveSteps steps
+// then at most k, and -- the claim below -- the disc was a candidate of step k*.  ray_walk takes kRayWaveSteps steps
 // at a time, lane L the cell L % 9 of step k0 + L / 9, takes the minimum key over the wave, and ends after the first
 // batch with best t < fl((k0 + kRayWaveSteps) dt): the same argument with the batch's last step for k.
+//
+// What the walk asks of a leg, and who has seen to it before the leg is walked:
+//   * the domain: o and the end point fl(o + fl(max_t d)) are finite and have |c| / s < 2^31;
+//   * the range: fl(kRayMaxSteps dt) > t_end, with the leg's own dt and its own walls ("The cap" below).
+// Leg 0 -- a ray of k_rays, the first leg of a path -- is tested by the two check kernels (the origins are the queries of
+// k_reader_check) and refuses the call.  A later leg of a path is data: every lane of k_ray_paths tests (o', d', m') with
+// the same ray_end_outside and ray_too_long, and the origin as well, and a leg that fails ends its ray alone.
 //
 // The claim: the disc hit at t* in step k has its centre c in the 3 x 3 block of M's cell, in computed cells.  With
 // u = 2^-53 and |f| the distance from the origin to c:
@@ -43,11 +54,13 @@
 //     problem up to the roundings of disc (3u b^2, seen through t / q <= t / |b|), of sqrt, the sum and the quotient
 //     (3u t), and t* |d| <= |f| for a hit on the near side: put into |P - c|^2 - rho^2 = a t^2 + 2 b t + cc the terms add
 //     up to at most 18 u |f|^2.  A walk has at most kRayMaxSteps = 2^13 steps, so |f| <= (2^13 + 1.5) s and, at
-//     rho = s / 2 where it is worst, |P - c| <= s / 2 + 2^-22.8 s;
+//     rho = s / 2 where it is worst, |P - c| <= s / 2 + 2^-22.8 s.  Nothing here assumes an exact origin: a, b and cc
+//     are computed from a later leg's (o', d') exactly as from (o, d), whatever roundings made o' and d', and the walk
+//     starts again at step 0;
 //   * |P - M'| <= s / 2 (1 + 2^-35) for the exact midpoint M' = o + tm d: dt |d| = s (1 + 3u), and fl(k dt), tm and
 //     fl((k + 1) dt) are each off by at most u 2^13 dt;
 //   * the computed M is off M' by at most u (|M| + |tm d|) <= 2^-22 s (1 + 2^-17) per axis inside the domain
-//     |c| / s < 2^31, which holds the origin and the end point (k_reader_check, k_rays_check) and so every M between.
+//     |c| / s < 2^31, which holds the origin and the end point and so every M between.
 //     The last step walked has fl(k dt) <= t_end <= max_t, so its midpoint may lie up to half a cell BEYOND the end
 //     point: |M| / s < 2^31 + 1/2 then, and M / h still below 2^31 by some 2^11 cells, because h > s (sc_pairs.h: 2047
 //     cells short of the ends of int) -- the (int) conversion in pairs_cell is defined, and cx +- 1 does not overflow;
@@ -59,36 +72,24 @@
 // the cap is the largest power of two the margin of sc_pairs.h carries.  An origin inside a disc (cc <= 0, t = 0) has c
 // within rho (1 + 2u) of o, which lies in step 0's piece: the same bound with room to spare.
 //
-// The cap.  A live ray needs fl(kRayMaxSteps dt) > t_end, else kRayFlagRange goes up and the call ends as status -4: a
-// max_t of 1e12 in an open scene is a status, not a kernel that walks for minutes.  (An a that overflowed gives dt = 0
-// and the same status.)  With the flag down every walk ends by step kRayMaxSteps: fl(k dt) is monotone in k.
+// The cap.  A live leg needs fl(kRayMaxSteps dt) > t_end: for leg 0 kRayFlagRange goes up otherwise and the call ends as
+// status -4 -- a max_t of 1e12 in an open scene is a status, not a kernel that walks for minutes --, a later leg ends its
+// ray with `end` -4.  (An a that overflowed gives dt = 0 and the same.)  A leg that passed ends its walk by step
+// kRayMaxSteps: fl(k dt) is monotone in k.
 //
 // Paths (sc_pairs_ray_paths_device, k_ray_paths; the rule is tests/ray_path_spec.py).  The ray stays in its wave for
-// L = bounces + 1 legs.  A leg has o, d, a budget m and the object the leg before it hit, which takes no part in it; a
-// disc with cc <= 0 is hit (at t = +0) by a later leg only if b < 0 -- the ray heads inward --, else the ray is leaving
-// it.  A leg therefore starts ON the surface it has left and names it: no epsilon moves the origin, and no bit depends on
+// L = bounces + 1 legs, each with its budget m.  A disc with cc <= 0 is hit (at t = +0) by a later leg only if b < 0 --
+// the ray heads inward --, else the ray is leaving it.  A leg therefore starts ON the surface it has left and names it: no epsilon moves the origin, and no bit depends on
 // one.  A leg that hit has P = fl(o + fl(t d)) and the normal n -- g = P - c, n = g / sqrt(fl(fl(gx gx) + fl(gy gy)))
 // for a disc; n0 = (ey, -ex) / sqrt(fl(fl(ex ex) + fl(ey ey))) for a wall, negated if fl(fl(dx n0x) + fl(dy n0y)) > 0 --;
 // the next leg has o' = P, m' = fl(m - t) and, with dn = fl(fl(dx nx) + fl(dy ny)) < 0, d' = fl(d - fl(fl(2 dn) n)),
 // else d' = d.  How a path ends is `end`: 0 all legs hit, 1 a leg met nothing, 2 dead (leg 0, a normal that is not
-// finite, the next leg), -1 and -4 the next leg fails the two tests below.  Leg 0 is tested by the two check kernels
-// and refuses the call; a later leg is data and ends its ray alone.
-//
-// The claim, for later legs.  Before leg k >= 1 is walked every lane has tested (o', d', m') as k_rays_check tests leg 0:
-//   * the domain: o' and the end point fl(o' + fl(m' d')) are finite and have |c| / s < 2^31.  Every midpoint of the leg's
-//     walk lies between the two, up to the half cell beyond the end point that the last step may reach: the third bullet
-//     above holds word for word, the conversions in pairs_cell are defined and cx +- 1 does not overflow;
-//   * the range: fl(kRayMaxSteps dt) > t_end with the leg's OWN dt = fl(s / sqrt(a')) and its own walls -- the excluded
-//     one left out, as in the walk.  The walk starts again at step 0, so |f| <= (2^13 + 1.5) s for every disc it can
-//     hit, and the first bullet's 18 u |f|^2 is the same number: a, b and cc are computed from (o', d') exactly as from
-//     (o, d), whatever roundings made o' and d'.  The leg is a ray of its own; that its origin is a computed point
-//     changes nothing in the bound, which never assumed an exact origin.
+// finite, the next leg), -1 and -4 the next leg fails the two tests above.
 // The excluded disc is skipped by its index before the rule is asked, so it cannot win; skipping a candidate removes a
-// key from a minimum and leaves the argument for the others as it was.  A disc with cc <= 0 that is hit (b < 0) has its
-// centre within rho (1 + 2u) of o', which lies in step 0's piece: the bound of the last sentence of the claim.  A disc
-// with cc <= 0 that is NOT hit (b >= 0) is not a candidate at all, in the rule as in the walk.  The stop test is the
-// walk's: after the first batch with best t < fl((k0 + kRayWaveSteps) dt), per leg.  The path is finite because every
-// leg, a t = 0 leg included, uses up one of L.
+// key from a minimum and leaves the walk's argument for the others as it was.  A disc with cc <= 0 that is hit (b < 0)
+// has its centre within rho (1 + 2u) of o', which lies in step 0's piece: the bound of the last sentence of the claim.  A
+// disc with cc <= 0 that is NOT hit (b >= 0) is not a candidate at all, in the rule as in the walk.  The excluded wall is
+// left out of t_end as out of the result.  The path is finite because every leg, a t = 0 leg included, uses up one of L.
 //
 // The form (profiles/rays_time.txt).  What every other reader does, a thread per row in workgroups of one wave, was
 // built too -- the same ray_scan, the eighteen `start` loads of a step's nine buckets issued together -- and MEASURED
@@ -182,22 +183,87 @@ __device__ __forceinline__ bool ray_disc(XY o, XY d, double a, XY c, double rho2
 }
 
 // The candidates of one bucket, places lo .. hi - 1: those whose own cell is (cx, cy) -- and, batched, whose index lies
-// in the ray's cloud --, by the rule, into the best key.  (`row` by value: by reference the compiler scheduled the
-// unbatched k_rays differently from the kernel without a record; by value it is that kernel, instruction for instruction.)
-template <bool batched>
+// in the ray's cloud --, by the rule, into the best key.  kPath, a leg of a path: disc `skip` takes no part (a global
+// index, as j is, batched or not), `later` is ray_disc's, and the place in the sorted arrays of the best candidate rides
+// along with its key, for the normal.  (`row` by value: by reference the compiler scheduled the unbatched k_rays
+// differently from a kernel without a record.)
+template <bool batched, bool kPath>
 __device__ __forceinline__ void ray_scan(const PairsView& v, const PairsRow row, XY o, XY d, double a, double rho2,
-                                         double max_t, unsigned cx, unsigned cy, int lo, int hi, double& best, int& who) {
+                                         double max_t, bool later, int skip, unsigned cx, unsigned cy, int lo, int hi,
+                                         double& best, int& who, int& place) {
   for (int k = lo; k < hi; ++k) {
     const uint2 cell = v.scell[k];
     if (cell.x != cx || cell.y != cy) continue;
     const int j = v.sidx[k];
     double t;
-    if (!pairs_in<batched>(row, j) || !ray_disc(o, d, a, v.sxy[k], rho2, max_t, t)) continue;
+    if (kPath && j == skip) continue;
+    if (!pairs_in<batched>(row, j) || !ray_disc<kPath>(o, d, a, v.sxy[k], rho2, max_t, t, later)) continue;
     if (t < best || (t == best && j < who)) {
       best = t;
       who = j;
+      if (kPath) place = k;
     }
   }
+}
+
+// The walk of a leg (o, d, a) with the budget max_t and the nearest wall at tw, in steps of dt: the smallest key (best, who) among
+// its discs, in every lane, and under kPath its place.  The caller sets (+inf, kRayNoDisc, any place).  Lane L < 63 takes
+// cell L % 9 of step k0 + L / 9 of the batch (the lane is read here, where its range shows); everything else is uniform
+// over the wave.  v.g.h is the count's; batched, the cells hash with the ray's cloud and ray_scan tests pairs_in.
+template <bool batched, bool kPath>
+__device__ __forceinline__ void ray_walk(const PairsView& v, const PairsRow row, XY o, XY d, double a, double rho2,
+                                         double max_t, double tw, double dt, bool later, int skip, double& best, int& who,
+                                         int& place) {
+  const double t_end = fmin(max_t, tw);
+  static_assert(9 * kRayWaveSteps <= kRayBlock && kRayBlock == 64, "a lane per (step, cell) pair of a batch, one wave");
+  const int lane = (int)threadIdx.x, step = lane / 9, c = lane % 9;
+  for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
+    const int k = k0 + step;
+    if (step < kRayWaveSteps && (double)k * dt <= t_end) {
+      const double tm = ((double)k + 0.5) * dt;
+      const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
+      const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
+      const unsigned bk = pairs_bucket(cx, cy, row.cloud, v.g.mask);
+      ray_scan<batched, kPath>(v, row, o, d, a, rho2, max_t, later, skip, cx, cy, v.start[bk], v.start[bk + 1], best, who, place);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave, in every lane
+      const double t2 = __shfl_xor(best, off, 64);
+      const int j2 = __shfl_xor(who, off, 64);
+      const int p2 = kPath ? __shfl_xor(place, off, 64) : 0;
+      if (t2 < best || (t2 == best && j2 < who)) {
+        best = t2;
+        who = j2;
+        if (kPath) place = p2;
+      }
+    }
+    if (best < (double)(k0 + kRayWaveSteps) * dt) break;
+  }
+}
+
+// The two tests a leg passes before it is walked (k_rays_check for leg 0, k_ray_paths for a later one).  The domain: the
+// end point fl(o + fl(max_t d)) fails pairs_outside's rule with s, the count's radius, or is not finite ...
+__device__ __forceinline__ bool ray_end_outside(XY o, XY d, double max_t, double s) {
+  const double ex = fabs(o.x + max_t * d.x), ey = fabs(o.y + max_t * d.y);
+  return !(ex / s < kPairsDomain) | !(ey / s < kPairsDomain);  // (inf too; no branch between the axes)
+}
+
+// ... and the range: up to t_end = min(max_t, the nearest wall's tw) the walk would take more than kRayMaxSteps steps.
+__device__ __forceinline__ bool ray_too_long(double dt, double max_t, double tw) {
+  return (double)kRayMaxSteps * dt <= fmin(max_t, tw);
+}
+
+// What a ray's wave begins with: lane 0 of ray 0 writes the ray count -- or, with a flag up, the status, which is then all
+// that is written.  Is ray r to be done?
+template <bool batched>
+__device__ __forceinline__ bool ray_begin(const PairsView& v, const int* own_flag, long long r, int lane, long long n_rays,
+                                          long long* counts) {
+  const bool up = *v.flag || *own_flag;
+  if (r == 0 && lane == 0) {
+    if (up) counts[1] = ray_status<batched>(*v.flag, *own_flag);
+    else counts[0] = n_rays;
+  }
+  return !up && r < n_rays;
 }
 
 // The result of a live ray from its nearest wall (tw, sw) and its nearest disc (td, jd): a wall wins a tie.
@@ -216,32 +282,24 @@ __global__ void __launch_bounds__(kBlock)
   const XY o = origins[r], d = dirs[r];
   double a;
   if (!ray_live(o, d, a)) return;
-  const double ex = fabs(o.x + max_t * d.x), ey = fabs(o.y + max_t * d.y);
-  if (!(ex / radius < kPairsDomain) || !(ey / radius < kPairsDomain)) atomicOr(own_flag, kReaderFlagDomain);  // (inf too)
+  if (ray_end_outside(o, d, max_t, radius)) atomicOr(own_flag, kReaderFlagDomain);
   double tw;
   int sw;
   ray_walls(walls, o, d, max_t, tw, sw);
   const double dt = radius / sqrt(a);
-  if ((double)kRayMaxSteps * dt <= fmin(max_t, tw)) atomicOr(own_flag, kRayFlagRange);
+  if (ray_too_long(dt, max_t, tw)) atomicOr(own_flag, kRayFlagRange);
 }
 
-// A wave per ray: workgroup r is ray r.  Every lane computes the ray and its walls (uniform: scalar work); lane L < 63
-// takes cell L % 9 of step k0 + L / 9 of the batch.  `discs` 0: walls alone.  v.g.radius and v.g.h are the count's.
-// Batched: the ray's record (lo, hi, cloud) comes from pairs_row over query_ptr -- the rays are queries --, uniform over
-// the wave and so scalar work; the cells hash with the ray's cloud and ray_scan tests pairs_in.  `who` stays global.
+// A wave per ray: workgroup r is ray r, and a ray is one leg.  Every lane computes the ray and its walls (uniform: scalar
+// work).  `discs` 0: walls alone.  v.g.radius is the count's.  Batched: the ray's record (lo, hi, cloud) comes from
+// pairs_row over query_ptr -- the rays are queries --, uniform over the wave and so scalar work.  `who` stays global.
 template <bool batched>
 __global__ void __launch_bounds__(kRayBlock)
     k_rays(PairsView v, RayWalls walls, int discs, double rho2, double max_t, const int* __restrict__ own_flag,
            const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayOut out) {
-  static_assert(9 * kRayWaveSteps <= kRayBlock && kRayBlock == 64, "a lane per (step, cell) pair of a batch, one wave");
   const long long r = blockIdx.x;
   const int lane = (int)threadIdx.x;
-  const bool up = *v.flag || *own_flag;
-  if (r == 0 && lane == 0) {
-    if (up) out.counts[1] = ray_status<batched>(*v.flag, *own_flag);
-    else out.counts[0] = n_rays;
-  }
-  if (up || r >= n_rays) return;
+  if (!ray_begin<batched>(v, own_flag, r, lane, n_rays, out.counts)) return;
   const XY o = origins[r], d = dirs[r];
   double a;
   if (!ray_live(o, d, a)) {
@@ -252,33 +310,11 @@ __global__ void __launch_bounds__(kRayBlock)
     return;
   }
   double tw, best = __builtin_inf();
-  int sw, who = kRayNoDisc;
+  int sw, who = kRayNoDisc, place = 0;  // (the place is a path's)
   ray_walls(walls, o, d, max_t, tw, sw);
-  if (discs) {
-    const PairsRow row = pairs_row<batched>(v.bt, r);
-    const double t_end = fmin(max_t, tw), dt = v.g.radius / sqrt(a);
-    const int step = lane / 9, c = lane % 9;
-    for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
-      const int k = k0 + step;
-      if (step < kRayWaveSteps && (double)k * dt <= t_end) {
-        const double tm = ((double)k + 0.5) * dt;
-        const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
-        const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
-        const unsigned bk = pairs_bucket(cx, cy, row.cloud, v.g.mask);
-        ray_scan<batched>(v, row, o, d, a, rho2, max_t, cx, cy, v.start[bk], v.start[bk + 1], best, who);
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave, in every lane
-        const double t2 = __shfl_xor(best, off, 64);
-        const int j2 = __shfl_xor(who, off, 64);
-        if (t2 < best || (t2 == best && j2 < who)) {
-          best = t2;
-          who = j2;
-        }
-      }
-      if (best < (double)(k0 + kRayWaveSteps) * dt) break;
-    }
-  }
+  if (discs)
+    ray_walk<batched, false>(v, pairs_row<batched>(v.bt, r), o, d, a, rho2, max_t, tw, v.g.radius / sqrt(a), false,
+                             -1, best, who, place);
   if (lane == 0) ray_write(out, r, tw, sw, best, who);
 }
 
@@ -296,26 +332,6 @@ struct RayPathOut {
   long long* counts;  // [2]: rays, status
 };
 
-// ray_scan for a leg of a path: disc `skip` takes no part, `later` is ray_disc's, and the place in the sorted arrays of
-// the best candidate rides along with its key, for the normal.  `skip` is a global index, as j is, batched or not.
-template <bool batched>
-__device__ __forceinline__ void ray_scan_path(const PairsView& v, const PairsRow row, XY o, XY d, double a, double rho2,
-                                              double max_t, bool later, int skip, unsigned cx, unsigned cy, int lo, int hi,
-                                              double& best, int& who, int& place) {
-  for (int k = lo; k < hi; ++k) {
-    const uint2 cell = v.scell[k];
-    if (cell.x != cx || cell.y != cy) continue;
-    const int j = v.sidx[k];
-    double t;
-    if (j == skip || !pairs_in<batched>(row, j) || !ray_disc<true>(o, d, a, v.sxy[k], rho2, max_t, t, later)) continue;
-    if (t < best || (t == best && j < who)) {
-      best = t;
-      who = j;
-      place = k;
-    }
-  }
-}
-
 __device__ __forceinline__ void ray_path_write(const RayPathOut& out, long long at, double t, long long hit, XY p, XY n) {
   out.t[at] = t;
   out.hit[at] = hit;
@@ -325,7 +341,7 @@ __device__ __forceinline__ void ray_path_write(const RayPathOut& out, long long 
 
 // A wave per ray, as k_rays: workgroup r is ray r, and the leg loop runs here.  Every lane holds the leg -- o, d, a, the
 // budget m and the excluded wall and disc -- and computes the walls, the normal, the reflection and the tests of the next
-// leg: all uniform over the wave.  The walk of a leg is k_rays', from step 0 with the leg's own dt.  Lane 0 writes the
+// leg: all uniform over the wave.  Every leg is walked by ray_walk, from step 0 with the leg's own dt.  Lane 0 writes the
 // legs; the lanes share the rows the path never reached.  Leg 0's own domain and range are the call's (the flags); a
 // later leg's end the ray only.  Batched: the ray's record once, before leg 0, as in k_rays; every leg stays in the
 // ray's cloud.
@@ -335,12 +351,7 @@ __global__ void __launch_bounds__(kRayBlock)
                 const XY* __restrict__ origins, const XY* __restrict__ dirs, long long n_rays, RayPathOut out) {
   const long long r = blockIdx.x;
   const int lane = (int)threadIdx.x;
-  const bool up = *v.flag || *own_flag;
-  if (r == 0 && lane == 0) {
-    if (up) out.counts[1] = ray_status<batched>(*v.flag, *own_flag);
-    else out.counts[0] = n_rays;
-  }
-  if (up || r >= n_rays) return;
+  if (!ray_begin<batched>(v, own_flag, r, lane, n_rays, out.counts)) return;
   const double nan = __builtin_nan(""), inf = __builtin_inf();
   const XY none{nan, nan};
   const long long row = r * legs;
@@ -356,35 +367,12 @@ __global__ void __launch_bounds__(kRayBlock)
     int sw, who = kRayNoDisc, place = 0;
     ray_walls<true>(walls, o, d, m, tw, sw, skip_wall);
     if (discs) {
-      const double t_end = fmin(m, tw), dt = v.g.radius / sqrt(a);
-      if ((double)kRayMaxSteps * dt <= t_end) {  // (never leg 0: k_rays_check has raised the flag for it)
+      const double dt = v.g.radius / sqrt(a);
+      if (ray_too_long(dt, m, tw)) {  // (never leg 0: k_rays_check has raised the flag for it)
         end = kRayStatusRange;
         break;
       }
-      const int step = lane / 9, c = lane % 9;
-      for (int k0 = 0; k0 < kRayMaxSteps && (double)k0 * dt <= t_end; k0 += kRayWaveSteps) {  // (uniform over the wave)
-        const int k = k0 + step;
-        if (step < kRayWaveSteps && (double)k * dt <= t_end) {
-          const double tm = ((double)k + 0.5) * dt;
-          const unsigned cx = pairs_cell(o.x + tm * d.x, v.g.h) + (unsigned)(c % 3 - 1);
-          const unsigned cy = pairs_cell(o.y + tm * d.y, v.g.h) + (unsigned)(c / 3 - 1);
-          const unsigned bk = pairs_bucket(cx, cy, rec.cloud, v.g.mask);
-          ray_scan_path<batched>(v, rec, o, d, a, rho2, m, leg > 0, skip_disc, cx, cy, v.start[bk], v.start[bk + 1], best, who,
-                                 place);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {  // the smallest key of the wave and its place, in every lane
-          const double t2 = __shfl_xor(best, off, 64);
-          const int j2 = __shfl_xor(who, off, 64);
-          const int p2 = __shfl_xor(place, off, 64);
-          if (t2 < best || (t2 == best && j2 < who)) {
-            best = t2;
-            who = j2;
-            place = p2;
-          }
-        }
-        if (best < (double)(k0 + kRayWaveSteps) * dt) break;
-      }
+      ray_walk<batched, true>(v, rec, o, d, a, rho2, m, tw, dt, leg > 0, skip_disc, best, who, place);
     }
     const bool disc = best < tw;  // (a wall wins a tie)
     if (!disc && sw < 0) {
@@ -427,9 +415,8 @@ __global__ void __launch_bounds__(kRayBlock)
     if (!ray_live(o, d, a)) {
       end = kRayEndDead;
     } else if (discs) {
-      const double ex = fabs(o.x + m * d.x), ey = fabs(o.y + m * d.y), s = v.g.radius;
-      if (!(fabs(o.x) / s < kPairsDomain) || !(fabs(o.y) / s < kPairsDomain) || !(ex / s < kPairsDomain) ||
-          !(ey / s < kPairsDomain))  // (inf too)
+      const double s = v.g.radius;
+      if (!(fabs(o.x) / s < kPairsDomain) || !(fabs(o.y) / s < kPairsDomain) || ray_end_outside(o, d, m, s))
         end = kPairsStatusDomain;
     }
   }

@@ -575,7 +575,7 @@ class Engine:
         ``origin + max_t * direction`` lies outside the domain, -4 when a ray would walk more than 8192 cells (then
         nothing else is written).  `room` defaults to R rows.  Refuses a batched grid: `pairs_rays_batch` reads one.
         Enqueued on the context's stream, no synchronisation.  Returns `counts`."""
-        return self._rays("sc_pairs_rays_device", None, t, hit, origins, directions, disc_radius, max_t, segments,
+        return self._rays("sc_pairs_rays_device", None, t, hit, (), origins, directions, disc_radius, max_t, segments,
                           counts, room)
 
     def pairs_rays_batch(self, t, hit, *, origins, directions, ray_batch, disc_radius: float, max_t: float, segments=None,
@@ -585,21 +585,34 @@ class Engine:
         (`pairs_set_query_batch`: the rays are queries), rays ``ray_batch[b]:ray_batch[b + 1]`` meet the discs of cloud b
         only, the walls are shared, and `hit` is the global row.  Status -3 says that offsets were not in order (nothing
         else is written).  Refuses an unbatched grid."""
-        return self._rays("sc_pairs_rays_batch_device", ray_batch, t, hit, origins, directions, disc_radius, max_t,
+        return self._rays("sc_pairs_rays_batch_device", ray_batch, t, hit, (), origins, directions, disc_radius, max_t,
                           segments, counts, room)
 
-    def _rays(self, fn, ray_batch, t, hit, origins, directions, disc_radius, max_t, segments, counts, room):
+    def _rays(self, fn, ray_batch, t, hit, path, origins, directions, disc_radius, max_t, segments, counts, room):
+        # `path`: () for the rays; (points, normals, end, bounces) for the ray paths, a row of L legs per ray then
         disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
-        rows = _state_tensor(t, "t", "float64", (), self.device)
-        _state_tensor(hit, "hit", "int64", (), self.device, rows)
+        legs, bounces = (), ()
+        if path:
+            *path, bounces = path
+            bounces = (int(bounces),)
+            if not 0 <= bounces[0] <= N.RAY_MAX_BOUNCES:
+                raise ValueError(f"bounces must be 0 .. {N.RAY_MAX_BOUNCES}")
+            legs = (bounces[0] + 1,)
+        rows = _state_tensor(t, "t", "float64", legs, self.device)
+        _state_tensor(hit, "hit", "int64", legs, self.device, rows)
+        if path:
+            points, normals, end = path
+            _state_tensor(points, "points", "float64", legs + (2,), self.device, rows)
+            _state_tensor(normals, "normals", "float64", legs + (2,), self.device, rows)
+            _state_tensor(end, "end", "int64", (), self.device, rows)
         q = _state_tensor(origins, "origins", "float64", (2,), self.device)
         _state_tensor(directions, "directions", "float64", (2,), self.device, q)
         _counts_tensor(counts, self.device)
         room = _room(room, rows, "the tensors'")
-        origins_at, directions_at, t_at, hit_at = _addresses(counts, origins, directions, t, hit)
+        origins_at, directions_at, *out_at = _addresses(counts, origins, directions, t, hit, *path)
         self._query_batch(origins, ray_batch)
-        N.check(getattr(self._lib, fn)(self._ctx, origins_at, directions_at, q, disc_radius, max_t,
-                                       N.dptr(seg) if len(seg) else None, len(seg), t_at, hit_at, room, N._P(counts.data_ptr())))
+        N.check(getattr(self._lib, fn)(self._ctx, origins_at, directions_at, q, *bounces, disc_radius, max_t,
+                                       N.dptr(seg) if len(seg) else None, len(seg), *out_at, room, N._P(counts.data_ptr())))
         return counts
 
     def pairs_ray_paths(self, t, hit, points, normals, end, *, origins, directions, bounces: int, disc_radius: float,
@@ -615,37 +628,15 @@ class Engine:
         `counts`, int64 (2,), receives the ray count and the status of leg 0: 0, -1 or -4 as `pairs_rays` (then nothing
         else is written).  `room` defaults to R rows.  Refuses a batched grid: `pairs_ray_paths_batch` reads one.  Enqueued
         on the context's stream, no synchronisation.  Returns `counts`."""
-        return self._ray_paths("sc_pairs_ray_paths_device", None, t, hit, points, normals, end, origins, directions,
-                               bounces, disc_radius, max_t, segments, counts, room)
+        return self._rays("sc_pairs_ray_paths_device", None, t, hit, (points, normals, end, bounces), origins, directions,
+                          disc_radius, max_t, segments, counts, room)
 
     def pairs_ray_paths_batch(self, t, hit, points, normals, end, *, origins, directions, ray_batch, bounces: int,
                               disc_radius: float, max_t: float, segments=None, counts, room: int | None = None):
         """`pairs_ray_paths` of a batched grid (sc_pairs_ray_paths_batch_device): `ray_batch` and everything about the
         clouds as in `pairs_rays_batch`; every leg of a path stays in its ray's cloud."""
-        return self._ray_paths("sc_pairs_ray_paths_batch_device", ray_batch, t, hit, points, normals, end, origins,
-                               directions, bounces, disc_radius, max_t, segments, counts, room)
-
-    def _ray_paths(self, fn, ray_batch, t, hit, points, normals, end, origins, directions, bounces, disc_radius, max_t, segments,
-                   counts, room):
-        disc_radius, max_t, seg = _ray_numbers(disc_radius, max_t, segments)
-        bounces = int(bounces)
-        if not 0 <= bounces <= N.RAY_MAX_BOUNCES:
-            raise ValueError(f"bounces must be 0 .. {N.RAY_MAX_BOUNCES}")
-        legs = bounces + 1
-        rows = _state_tensor(t, "t", "float64", (legs,), self.device)
-        _state_tensor(hit, "hit", "int64", (legs,), self.device, rows)
-        _state_tensor(points, "points", "float64", (legs, 2), self.device, rows)
-        _state_tensor(normals, "normals", "float64", (legs, 2), self.device, rows)
-        _state_tensor(end, "end", "int64", (), self.device, rows)
-        q = _state_tensor(origins, "origins", "float64", (2,), self.device)
-        _state_tensor(directions, "directions", "float64", (2,), self.device, q)
-        _counts_tensor(counts, self.device)
-        room = _room(room, rows, "the tensors'")
-        origins_at, directions_at, *out_at = _addresses(counts, origins, directions, t, hit, points, normals, end)
-        self._query_batch(origins, ray_batch)
-        N.check(getattr(self._lib, fn)(self._ctx, origins_at, directions_at, q, bounces, disc_radius, max_t,
-                                       N.dptr(seg) if len(seg) else None, len(seg), *out_at, room, N._P(counts.data_ptr())))
-        return counts
+        return self._rays("sc_pairs_ray_paths_batch_device", ray_batch, t, hit, (points, normals, end, bounces), origins,
+                          directions, disc_radius, max_t, segments, counts, room)
 
     # -- frames
     @staticmethod
